@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json's metric on one node: SPERR 3D fixed-rate compress + decompress
 throughput (GB/s of uncompressed fp32 bytes) on 256^3 chunks at BPP = 2.0.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of the hot path over one synthetic volume already resident in HBM:
@@ -11,7 +11,14 @@ into a device volume.  Every rank owns its own volume of `--size`^3 fp32 samples
 256^3 chunks (independent chunks, no data-path collective: weak scaling).  `value` is the
 whole-job rate: N * volume bytes / max-over-ranks(time per step).
 
-Besides the contract fields the JSON line carries
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step,
+the compress / decompress split of the timed steps, the container length and the round-trip error of
+the last step).  --dump-outputs DIR writes what rank 0's last timed step computed: DIR/container.npy
+(the container bytes) and DIR/decoded.npy (the decoded volume), float32, under 64 MB in all: an array
+larger than its share is written at a fixed, seeded sample of positions; the same arguments give the
+same inputs, so two builds can be compared output for output.
+
+With --full the JSON line carries as well
   roofline      the dominant kernel's algorithmic bytes / its measured time vs the HBM peak
   cpu_baseline  the CPU oracle (the real reference build when oracle/_ref is present, else this
                 repo's C restatement) timed on the same volume on this host (all threads: the
@@ -42,8 +49,27 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E: 8.0 TB/s spec
 ALGO_BYTES_PER_VALUE = 4.25    # 4 B fp32 + BPP/8 B stream per value
+DUMP_BYTES = 60_000_000        # --dump-outputs: the values written in all (under 64 MB, .npy headers included)
+DUMP_SEED = 20240607           # --dump-outputs: the positions sampled from an output larger than its share
+
+
+def dump_outputs(path, outputs):
+    """Writes {name: device tensor} as path/<name>.npy in float32, together at most DUMP_BYTES: a tensor
+    larger than its share is written at a fixed, seeded sample of positions (sorted, the same on every run
+    for the same number of elements)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // 4 // len(outputs)   # float32 values per output
+    for k, (name, t) in enumerate(sorted(outputs.items())):
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            rng = np.random.default_rng(DUMP_SEED + k)
+            idx = np.unique(rng.integers(0, flat.numel(), size=share, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.to(torch.float32).cpu().numpy())
 
 
 def run_host_path(eng, vol, chunks, bpp, devices, reps, dev_stream, dev_out, mode=1, pageable=True):
@@ -170,6 +196,19 @@ def compact_line(line):
     return c
 
 
+def emit_line(line, args, world):
+    # ONE line either way.  The default is the compact one (under 4 KB, so that a record which keeps only the tail
+    # of stdout keeps all of it): every number, none of the prose -- --verbose prints the line with its
+    # "what" / "sample" descriptions, --full-out writes that one to a file.
+    if args.full_out:
+        with open(args.full_out, "w") as f:
+            json.dump(line, f, indent=1)
+    print(json.dumps(line if args.verbose else compact_line(line), separators=(",", ":")))
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -189,7 +228,19 @@ def main():
     ap.add_argument("--no-other-modes", action="store_true", help="skip the point-wise error run and the 2D slice")
     ap.add_argument("--verbose", action="store_true", help="the JSON line with its descriptions (about 12 KB)")
     ap.add_argument("--full-out", default="", help="write the verbose record to this file as well")
+    ap.add_argument("--full", action="store_true",
+                    help="measure what goes beside the headline as well: the per-kernel profile and roofline, the CPU "
+                         "baseline, the host path, the small batch, the ragged volume, the other modes, the workspace "
+                         "(the --no-* options and --profile-out apply to such a run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.profile_out and not args.full:
+        ap.error("--profile-out needs --full (the per-kernel table comes from its profiled step)")
+    if not args.full:   # a plain run: the headline figure and nothing beside it
+        args.no_cpu_baseline = args.no_host_path = args.no_small_batch = args.no_ragged = args.no_other_modes = True
 
     import torch
     import torch.distributed as dist
@@ -239,17 +290,18 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # one untimed step with every kernel bracketed by HIP events finds the dominant kernel and the
-    # per-kernel table; in the timed region only the dominant kernel is bracketed (two event
-    # records per launch of EVERY kernel cost about 6 % of a step)
-    eng.profile(True)
-    step()
-    torch.cuda.synchronize()
-    eng.profile(False)
-    prof_all = eng.profile_report(with_sum=True)   # {kernel: (busy ms, launches, sum of durations)}
-    # dominant = largest SUM of launch durations (launches x average duration, what a kernel trace reports)
-    top_name = max(prof_all.items(), key=lambda kv: kv[1][2])[0]
-    eng.profile(True, only=top_name)
+    if args.full:
+        # one untimed step with every kernel bracketed by HIP events finds the dominant kernel and the
+        # per-kernel table; in the timed region only the dominant kernel is bracketed (two event
+        # records per launch of EVERY kernel cost about 6 % of a step)
+        eng.profile(True)
+        step()
+        torch.cuda.synchronize()
+        eng.profile(False)
+        prof_all = eng.profile_report(with_sum=True)   # {kernel: (busy ms, launches, sum of durations)}
+        # dominant = largest SUM of launch durations (launches x average duration, what a kernel trace reports)
+        top_name = max(prof_all.items(), key=lambda kv: kv[1][2])[0]
+        eng.profile(True, only=top_name)
     timers = []
     barrier()
     t0 = time.perf_counter()
@@ -257,8 +309,11 @@ def main():
         stream = step(timers)
     barrier()
     t1 = time.perf_counter()
-    eng.profile(False)
-    prof = eng.profile_report(with_sum=True)
+    if args.full:
+        eng.profile(False)
+        prof = eng.profile_report(with_sum=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"container": stream, "decoded": out})
 
     dt = (t1 - t0) / args.steps
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -298,6 +353,26 @@ def main():
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
+        return
+
+    line = {
+        "metric": "compress+decompress GB/s/GPU on 256^3 fp32 chunks @ BPP=2.0; bitstream-exact vs ref",
+        "value": round(world * nbytes / dt_max / 1e9, 4),
+        "unit": "GB/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt_max * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"synthetic {S}^3 fp32 turbulence per GPU, {C}^3 chunks, BPP={args.bpp}, "
+                               "step = compress + decompress, volume and container resident in HBM",
+                   "chunks_per_gpu": nchunks, "parallelism": f"chunks farmed over {world} GPU(s), no collective"},
+        "compress_GBps_per_gpu": round(nbytes / tc / 1e9, 4),
+        "decompress_GBps_per_gpu": round(nbytes / td / 1e9, 4),
+        "container_bytes": int(stream.numel()), "container_len_exact": ok_len,
+        "max_abs_err": err,
+    }
+    if not args.full:
+        emit_line(line, args, world)
         return
 
     # ---- device workspace of the call: the engine's arena holds every chunk of the batch in flight
@@ -591,21 +666,7 @@ def main():
             "hip_stream_identical": hs == cs,
         }
 
-    line = {
-        "metric": "compress+decompress GB/s/GPU on 256^3 fp32 chunks @ BPP=2.0; bitstream-exact vs ref",
-        "value": round(world * nbytes / dt_max / 1e9, 4),
-        "unit": "GB/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt_max * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"synthetic {S}^3 fp32 turbulence per GPU, {C}^3 chunks, BPP={args.bpp}, "
-                               "step = compress + decompress, volume and container resident in HBM",
-                   "chunks_per_gpu": nchunks, "parallelism": f"chunks farmed over {world} GPU(s), no collective"},
-        "compress_GBps_per_gpu": round(nbytes / tc / 1e9, 4),
-        "decompress_GBps_per_gpu": round(nbytes / td / 1e9, 4),
-        "container_bytes": int(stream.numel()), "container_len_exact": ok_len,
-        "max_abs_err": err,
+    line.update({
         "roofline": roofline,
         "cpu_baseline": cpu,
         "host_path": host_path,
@@ -627,16 +688,8 @@ def main():
         "workspace": workspace,
         "ragged_volume": ragged,
         "other_modes": other,
-    }
-    # ONE line either way.  The default is the compact one (under 4 KB: the driver's record keeps the tail of
-    # stdout, and round 5's 12 KB line lost its host_path* fields there): every number, none of the prose --
-    # --verbose prints the line with its "what" / "sample" descriptions, --full-out writes that one to a file.
-    if args.full_out:
-        with open(args.full_out, "w") as f:
-            json.dump(line, f, indent=1)
-    print(json.dumps(line if args.verbose else compact_line(line), separators=(",", ":")))
-    if world > 1:
-        dist.destroy_process_group()
+    })
+    emit_line(line, args, world)
 
 
 if __name__ == "__main__":

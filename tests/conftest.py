@@ -19,10 +19,23 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def ref():
-    """The real reference build (oracle/_ref). Present in the dev container and, as a prebuilt
-    .so, on the GPU box; tests that need it are skipped when it is absent."""
+def _ref_session():
+    """(the real reference build oracle/_ref or None where it is not built, the recorded digests, recording?)"""
+    import refbits
     from oracle import pyoracle
-    if not pyoracle.have_ref():
-        pytest.skip("oracle/_ref not built")
-    return pyoracle.Ref()
+    recording = bool(os.environ.get(refbits.RECORD_ENV))
+    live = pyoracle.Ref() if pyoracle.have_ref() else None
+    if recording and live is None:
+        pytest.exit("recording the reference's digests needs oracle/_ref")
+    table = refbits.load_table(recording)
+    yield live, table, recording
+    if recording:
+        refbits.save_table(table)
+
+
+@pytest.fixture
+def ref(request, _ref_session):
+    """The reference's results for this test (tests/refbits.py): from the real reference build
+    (oracle/_ref) where it is present, else the digests recorded from it."""
+    import refbits
+    return refbits.RefBits(request.node.nodeid.split("::", 1)[1], *_ref_session)

@@ -2,7 +2,7 @@
 # A/B of environment settings on the host-resident farm path (GPU box): bash tools/ab_host.sh OUT "ENV..." ...
 out=$1; shift
 for envs in "$@"; do
-  env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --no-ragged --no-other-modes --steps 3 2>/dev/null < /dev/null | python -c "
+  env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-ragged --no-other-modes --steps 3 2>/dev/null < /dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.readline())
 hp=l.get('host_path') or {}; hw=l.get('host_path_pwe') or {}; sb=l.get('small_batch') or {}

@@ -7,5 +7,5 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-timeout 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o run -- python3 bench.py --size 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path > $out/fetch.log 2>&1
+timeout 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o run -- python3 bench.py --full --size 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path > $out/fetch.log 2>&1
 echo "fetch rc=$?"

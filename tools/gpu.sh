@@ -10,7 +10,7 @@
 #   short[:ENV..]       the short bench line (no CPU baseline, host path, ragged volume, other modes) under the
 #                       environment ENV ("A=1 B=2"; may be empty), with the engine's event table -> short.txt, eventsN.csv
 #   lib:PATH            the same under SPERR_HIP_LIB=PATH (a variant library of tools/build_variant.sh)
-#   full                the default bench line, as the driver runs it       -> bench.json (+ a digest on stdout)
+#   full                the bench line with --full (every figure beside the metric) -> bench.json (+ a digest)
 #   trace[:N]           rocprofv3 kernel trace + stats of one bench step (N = 64 chunks: the 1024^3 volume; N = 8:
 #                       tools/small_batch.py 512) and the decoder's plane table -> traceN/, plane_tableN.txt
 #   ragged              kernel trace of the 1000^3 volume's decompression per queue -> ragged.txt
@@ -22,7 +22,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-$(dirname $0)/..}"
-short_args="--no-cpu-baseline --no-host-path --no-ragged --no-other-modes --steps 5"
+short_args="--full --no-cpu-baseline --no-host-path --no-ragged --no-other-modes --steps 5"
 digest='
 import json,sys
 l=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -46,12 +46,12 @@ for step in "$@"; do
       env $envs timeout -k 10 300 python3 bench.py $short_args --profile-out $out/events$n.csv > $out/short$n.json 2> $out/short$n.err < /dev/null
       rc=$?; [ $rc -eq 0 ] && python3 -c "$digest" $out/short$n.json "[$envs]" | tee -a $out/short.txt ;;
     full)
-      timeout -k 10 1000 python3 bench.py > $out/bench.json 2> $out/bench.err
+      timeout -k 10 1000 python3 bench.py --full > $out/bench.json 2> $out/bench.err
       rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] && tail -1 $out/bench.json | cut -c1-1500 ;;
     trace)
       N=${arg:-64}
       if [ "$N" = 8 ]; then prog="tools/small_batch.py 512"
-      else prog="bench.py --size 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path --no-ragged --no-other-modes --no-small-batch"; fi
+      else prog="bench.py --full --size 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path --no-ragged --no-other-modes --no-small-batch"; fi
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace$N -o run -- python3 $prog > $out/trace$N.log 2>&1
       rc=$?; echo "trace$N rc=$rc"
       python3 tools/plane_table2.py $out/trace$N/run_kernel_trace.csv > $out/plane_table$N.txt 2>&1
