@@ -70,6 +70,8 @@ int main(int argc, char** argv)
   std::string input_file, bitstream, decomp_f32, decomp_f64, low_f32, low_f64;
   bool cflag = false, dflag = false, print_stats = false;
   size_t omp = 0, ftype = 0, dims[3] = {0, 0, 0}, chunks[3] = {256, 256, 256};
+  // (SIZE_MAX: no --box_dims given; the parser makes --box_origin and --box_dims come together)
+  size_t box_origin[3] = {0, 0, 0}, box_dims[3] = {SIZE_MAX, SIZE_MAX, SIZE_MAX};
   double pwe = 0.0, psnr = 0.0, bpp = 0.0;
 
   cli::Parser app("3D SPERR compression and decompression (MI355X)\n");
@@ -87,6 +89,14 @@ int main(int argc, char** argv)
   app.text("--decomp_d", decomp_f64, "Output decompressed volume in f64 precision.", go);
   app.text("--decomp_lowres_f", low_f32, "Output lower resolutions of the decompressed volume in f32 precision.", go);
   app.text("--decomp_lowres_d", low_f64, "Output lower resolutions of the decompressed volume in f64 precision.", go);
+  // (this tool's addition: decode a sub-box, reading only the chunks it meets)
+  app.counts("--box_origin", box_origin, 3, "Decode only the box at this origin: --decomp_f / --decomp_d\n"
+             "hold the box. E.g., `--box_origin 0 0 0` (with --box_dims).", go).needs = {"-d", "--box_dims"};
+  {
+    cli::Option& o = app.counts("--box_dims", box_dims, 3, "Dimensions of the box to decode (with --box_origin).", go);
+    o.needs = {"-d", "--box_origin"};
+    o.excludes = {"--decomp_lowres_f", "--decomp_lowres_d"};
+  }
   app.flag("--print_stats", print_stats, "Print statistics measuring the compression quality.", go).needs = {"-c"};
   app.counts("--chunks", chunks, 3, "Dimensions of the preferred chunk size. Default: 256 256 256\n"
              "(Volume dims don't need to be divisible by these chunk dims.)", gc);
@@ -186,6 +196,16 @@ int main(int argc, char** argv)
                std::log2(s.sigma / s.rmse) - rate);
       }
     }
+  }
+  else if (box_dims[0] != SIZE_MAX || box_dims[1] != SIZE_MAX || box_dims[2] != SIZE_MAX) {
+    Freed box;
+    if (sperrhip_decomp_3d_box(input.data(), input.size(), 0, box_origin, box_dims, &box.p) != 0) {
+      printf("Decompression failed!\n");
+      return 1;
+    }
+    const size_t n = box_dims[0] * box_dims[1] * box_dims[2];
+    if (!cli::write_volume(static_cast<const double*>(box.p), n, decomp_f64, decomp_f32, "data"))
+      return 1;
   }
   else {
     Freed vol;

@@ -211,6 +211,29 @@ int sperrhip_decomp_2d_multires(const void* src, size_t src_len, int output_floa
                                 size_t dimy, void** dst, size_t* nlev, size_t* level_dims,
                                 double** levels);
 
+/* ---- a sub-box of a 3D container ------------------------------------------------------------- */
+/* The box [lo, lo + dims) of the volume, decoded from the chunks it meets only: no byte of any other
+ * chunk's stream is read.  The result is the box cut out of the whole decode, bit for bit, as
+ * box_dims[0]*box_dims[1]*box_dims[2] values, x fastest.  Any container kind decodes this way
+ * (fixed-rate, PSNR, point-wise error, truncated; fp32 or fp64 data, float or double output).  The
+ * calls return -1 without writing to the output when an extent is 0, when lo + dims leaves the
+ * volume, when the output is too small, or when the container is refused as
+ * sperrhip_decompress_dev refuses it. */
+/* host only: the ids (chunk_volume order) of the chunks the box meets.  Returns 0 ok (*count ids
+ * written), 1 when `ids` is NULL or `cap` is less than *count (nothing written), -1 bad box. */
+int sperrhip_box_chunks(size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y,
+                        size_t chunk_z, const size_t box_lo[3], const size_t box_dims[3],
+                        uint32_t* ids, size_t cap, size_t* count);
+/* device container -> device box on `hip_stream` (its device). Returns 0 ok, -1 error. */
+int sperrhip_decompress_box_dev(const void* d_src, size_t src_len, int output_float,
+                                const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
+                                size_t dst_cap_bytes, void* hip_stream);
+/* host container -> malloc'd host box (*dst must be NULL, free() it).  The chosen chunks' bytes
+ * travel to the calling thread's device, packed; one device does the work.  Returns 0 ok,
+ * 1 *dst not NULL, -1 error. */
+int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float,
+                           const size_t box_lo[3], const size_t box_dims[3], void** dst);
+
 /* ---- profiling ------------------------------------------------------------------------------ */
 
 /* When enabled, the engine brackets every pipeline stage with HIP events on the launch stream

@@ -161,6 +161,21 @@ class SPERR3D_OMP_D {
     std::free(dst);
     return RTNType::Good;
   }
+  // (this library's addition) only the box [lo, lo + dims) of the volume, decoded from the chunks it
+  // meets (sperrhip_decomp_3d_box); view_decoded_data() then holds the box, x fastest
+  auto decompress_box(const void* bitstream, dims_type lo, dims_type dims) -> RTNType
+  {
+    if (bitstream == nullptr || m_ptr == nullptr || bitstream != m_ptr)
+      return RTNType::Error;
+    void* dst = nullptr;
+    m_hierarchy.clear();
+    if (sperrhip_decomp_3d_box(m_ptr, m_len, 0, lo.data(), dims.data(), &dst) != 0)
+      return RTNType::Error;
+    const auto* d = static_cast<const double*>(dst);
+    m_vol.assign(d, d + dims[0] * dims[1] * dims[2]);
+    std::free(dst);
+    return RTNType::Good;
+  }
   auto view_decoded_data() const -> const vecd_type& { return m_vol; }
   auto release_decoded_data() -> vecd_type&& { return std::move(m_vol); }
   auto view_hierarchy() const -> const std::vector<vecd_type>& { return m_hierarchy; }

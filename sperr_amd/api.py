@@ -33,6 +33,7 @@ EXPORTS = [
     "sperrhip_farm_selftest", "sperrhip_release", "sperrhip_debug_counter",
     "sperrhip_numa_probe", "sperrhip_numa_bind_self", "sperrhip_farm_device_place",
     "sperrhip_host_cpus", "sperrhip_host_throttle", "sperrhip_farm_threads",
+    "sperrhip_box_chunks", "sperrhip_decompress_box_dev", "sperrhip_decomp_3d_box",
 ]
 
 
@@ -51,6 +52,19 @@ def host_cpus(lib):
     if rc != 0:
         raise SperrHipError(f"sperrhip_host_cpus returned {rc}")
     return {"cores_visible": vis.value, "affinity": aff.value, "cpu_quota": quota.value or None, "usable": use.value}
+
+
+def box_chunks(lib, vol_xyz, chunks_xyz, box_lo_xyz, box_dims_xyz):
+    """ids (chunk_volume order) of the chunks that the box [lo, lo + dims) of a volume meets; host only.
+    Raises SperrHipError for an empty box or one that leaves the volume."""
+    lo, dims, count = (_sz * 3)(*box_lo_xyz), (_sz * 3)(*box_dims_xyz), _sz(0)
+    rc = lib.sperrhip_box_chunks(*vol_xyz, *chunks_xyz, lo, dims, None, 0, C.byref(count))
+    if rc == 1:
+        ids = (C.c_uint32 * max(count.value, 1))()
+        rc = lib.sperrhip_box_chunks(*vol_xyz, *chunks_xyz, lo, dims, ids, count.value, C.byref(count))
+    if rc != 0:
+        raise SperrHipError(f"sperrhip_box_chunks returned {rc}")
+    return list(ids[:count.value])
 
 
 def host_throttle(lib):
@@ -94,6 +108,13 @@ def load_library():
     lib.sperrhip_decompress_dev.restype = C.c_int
     lib.sperrhip_decompress_dev.argtypes = [_vp, _sz, C.c_int, _vp, _sz, C.POINTER(_sz),
                                             C.POINTER(_sz), C.POINTER(_sz), _vp]
+    lib.sperrhip_box_chunks.restype = C.c_int
+    lib.sperrhip_box_chunks.argtypes = [_sz] * 6 + [C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint32), _sz,
+                                                    C.POINTER(_sz)]
+    lib.sperrhip_decompress_box_dev.restype = C.c_int
+    lib.sperrhip_decompress_box_dev.argtypes = [_vp, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, _vp]
+    lib.sperrhip_decomp_3d_box.restype = C.c_int
+    lib.sperrhip_decomp_3d_box.argtypes = [_vp, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_vp)]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -196,6 +217,22 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_decompress_dev returned {rtn}")
         return out
 
+    def decompress_box(self, container, box_lo_xyz, box_dims_xyz, output_float=True, out=None):
+        """The box [lo, lo + dims) (x, y, z order) of a device container's volume, decoded from the chunks it
+        meets only; a cuda tensor shaped (dims z, dims y, dims x) -- `out` when given."""
+        torch = self.torch
+        assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            out = torch.empty(tuple(int(d) for d in reversed(box_dims_xyz)), dtype=dt, device=container.device)
+        assert out.dtype == dt and out.is_contiguous() and out.is_cuda
+        rtn = self.lib.sperrhip_decompress_box_dev(container.data_ptr(), container.numel(), int(output_float),
+                                                   (_sz * 3)(*box_lo_xyz), (_sz * 3)(*box_dims_xyz), out.data_ptr(),
+                                                   out.numel() * out.element_size(), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_box_dev returned {rtn}")
+        return out
+
     # ---- stage access ----------------------------------------------------------------------
     def dwt3d(self, vals, inverse=False):
         """In-place on a contiguous cuda float64 tensor shaped (z, y, x)."""
@@ -283,6 +320,21 @@ class SperrHip:
         out = np.frombuffer(C.string_at(dst.value, n * np.dtype(dt).itemsize), dtype=dt).copy()
         self._libc.free(dst)
         return out.reshape(dz.value, dy.value, dx.value)
+
+    def decomp_3d_box(self, stream, box_lo_xyz, box_dims_xyz, output_float=True):
+        """The box [lo, lo + dims) (x, y, z order) of a host container (bytes or a uint8 array, pageable or
+        pinned) as a numpy array shaped (dims z, dims y, dims x); one device decodes it."""
+        buf = stream if isinstance(stream, np.ndarray) else np.frombuffer(stream, dtype=np.uint8)
+        dst = _vp(None)
+        rtn = self.lib.sperrhip_decomp_3d_box(buf.ctypes.data, buf.size, int(output_float), (_sz * 3)(*box_lo_xyz),
+                                              (_sz * 3)(*box_dims_xyz), C.byref(dst))
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decomp_3d_box returned {rtn}")
+        dx, dy, dz = (int(d) for d in box_dims_xyz)
+        dt = np.float32 if output_float else np.float64
+        out = np.frombuffer(C.string_at(dst.value, dx * dy * dz * np.dtype(dt).itemsize), dtype=dt).copy()
+        self._libc.free(dst)
+        return out.reshape(dz, dy, dx)
 
     # ---- chunk farm on an explicit device list (include/sperr_hip.h) -------------------------
     @staticmethod

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include <stdlib.h>
+#include <type_traits>
 #include "speck_tree.h"
 
 #define HIP_CHECK(expr)                                                                       \
@@ -61,6 +62,18 @@ struct ChunkGeom {         // one entry per chunk of the batch (device array)
 struct VolDesc {
   uint64_t dims[3];        // volume dims (x fastest)
 };
+
+// The crop variant of the last writers (kCrop kernels, decoding a sub-box): the output is a box of the
+// volume (VolDesc then holds the box's dims) and a chunk writes only its samples in [lo, hi) (chunk
+// coordinates), at the chunk's origin relative to the box -- negative where the chunk starts before it.
+struct CropGeom {          // one entry per chunk of the batch (device array)
+  int32_t rel[3];          // chunk origin minus box origin
+  uint32_t lo[3], hi[3];   // the chunk's window inside the box, [lo, hi) per axis
+};
+
+// the geometry record a writer reads: ChunkGeom, or CropGeom in the crop variant
+template <bool kCrop>
+using GeomOf = typename std::conditional<kCrop, CropGeom, ChunkGeom>::type;
 
 // ---- per-chunk state, device resident -----------------------------------------------------------
 struct PlaneRec {

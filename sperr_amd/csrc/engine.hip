@@ -234,6 +234,7 @@ size_t round_up(size_t v, size_t m)
 
 using hostc::Dims;
 using hostc::chunk_count;
+using hostc::box_chunks;
 using hostc::chunk_volume;
 using hostc::ContainerInfo;
 using hostc::parse_container_host;
@@ -2279,6 +2280,7 @@ std::vector<uint64_t> g_lis_stamps_host;   // chunk 0 of the last decoded batch
 struct DecBatchBufs {
   DecBuffers db;
   ChunkGeom* geom;
+  CropGeom* crop;   // the chunks' windows of a sub-box (null: the whole volume is decoded)
   uint64_t *chunkOff, *chunkLen;
   double* vals;
   size_t valsStride;
@@ -2288,8 +2290,9 @@ struct DecBatchBufs {
 
 // valsElems: fp64 samples per chunk of the chunk buffer (0: the whole chunk; compact_box() otherwise)
 // refNPlanes: refinement bit planes per chunk (DecBuffers::refPlanes; 0: the coefficients are updated plane by plane)
+// crop: a sub-box is decoded (DecBatchBufs::crop)
 bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadBytes, DecBatchBufs& o,
-               size_t valsElems = 0, uint32_t refNPlanes = 0)
+               size_t valsElems = 0, uint32_t refNPlanes = 0, bool crop = false)
 {
   const size_t N = P.N, Npad = round_up(N, 512);   // (512: k_ref_assemble takes eight mask words per round)
   DecBuffers& d = o.db;
@@ -2306,6 +2309,10 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   TAKE(d.cst, CoderState, B);
   TAKE(d.st, DecState, B);
   TAKE(o.geom, ChunkGeom, B);
+  o.crop = nullptr;
+  if (crop) {
+    TAKE(o.crop, CropGeom, B);
+  }
   TAKE(o.chunkOff, uint64_t, B);
   TAKE(o.chunkLen, uint64_t, B);
   TAKE(o.live, uint32_t, 64);
@@ -2518,17 +2525,43 @@ k_sub_volume(const double* vals, size_t valsStride, const CoderState* cst, const
   }
 }
 
+// a sub-box of the volume to decode (sperrhip_decompress_box_dev): [lo, lo + dims), and the chunks it
+// meets (box_chunks, chunk_volume order)
+struct BoxSel {
+  Dims lo, dims;
+  std::vector<uint32_t> ids;
+};
+
 template <typename T>
 int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, size_t dst_cap_vals,
                     const ContainerInfo& ci, hipStream_t st, const MultiRes* mr = nullptr,
-                    bool slice = false)
+                    bool slice = false, const BoxSel* box = nullptr)
 {   // slice: `ci` describes one chunk of dims (x, y, 1) whose stream starts at d_src (2D coder)
+    // box: only the chunks the box meets are read and decoded, and d_dst is the box (not with mr or slice)
   DrainOnError drainGuard{E, st};
   const auto chunks = chunk_volume(ci.vol, ci.chunk);
-  const uint32_t nchunks = (uint32_t)chunks.size();
-  if (ci.nvals == 0 || ci.nvals > dst_cap_vals)
+  if (box && (mr || slice))
+    return -1;
+  // The chunks of this call, slot by slot: slot i is container chunk sel[i] (all of them in order, or the
+  // box's).  Heads, outlier heads and batches are per slot; offsets and lengths come from the container.
+  std::vector<uint32_t> sel;
+  if (box)
+    sel = box->ids;
+  else {
+    sel.resize(chunks.size());
+    for (uint32_t i = 0; i < (uint32_t)sel.size(); i++)
+      sel[i] = i;
+  }
+  const uint32_t nchunks = (uint32_t)sel.size();
+  const size_t outVals = box ? box->dims[0] * box->dims[1] * box->dims[2] : ci.nvals;
+  if (outVals == 0 || outVals > dst_cap_vals || nchunks == 0)
     return -1;
   (void)src_len;
+  std::vector<uint64_t> selOff(nchunks), selLen(nchunks);
+  for (uint32_t i = 0; i < nchunks; i++) {
+    selOff[i] = ci.off[sel[i]];
+    selLen[i] = ci.len[sel[i]];
+  }
 
   // chunk heads (flags, number of planes) decide the integer width and the plane count
   const size_t miscBytes = round_up((size_t)nchunks * 8, 256) * 2 + (size_t)nchunks * 32 + 256;
@@ -2537,8 +2570,8 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
   uint64_t* d_off = reinterpret_cast<uint64_t*>(E.misc.p);
   uint64_t* d_len = d_off + round_up(nchunks, 32);
   uint8_t* d_heads = reinterpret_cast<uint8_t*>(d_len + round_up(nchunks, 32));
-  HIP_CHECK(hipMemcpyAsync(d_off, ci.off.data(), nchunks * 8, hipMemcpyHostToDevice, st));
-  HIP_CHECK(hipMemcpyAsync(d_len, ci.len.data(), nchunks * 8, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d_off, selOff.data(), nchunks * 8, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d_len, selLen.data(), nchunks * 8, hipMemcpyHostToDevice, st));
   LAUNCH_K(k_gather_heads, dim3((nchunks + 63) / 64), dim3(64), 0, st, d_src, d_off, d_len,
            d_heads, nchunks);
   std::vector<uint8_t> heads((size_t)nchunks * 32);
@@ -2559,14 +2592,14 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
     bool anyTail = false;
     for (uint32_t i = 0; i < nchunks; i++) {
       const uint8_t* hd = heads.data() + (size_t)i * 32;
-      if (ci.len[i] < 26 || (hd[0] & 0x01))
+      if (selLen[i] < 26 || (hd[0] & 0x01))
         continue;
       uint64_t tb;
       memcpy(&tb, hd + 18, 8);
-      const uint64_t speckLen = std::min<uint64_t>(9 + bytes_of_bits(tb), ci.len[i] - 17);
-      if (17 + speckLen + 9 <= ci.len[i]) {
-        tailOff[i] = ci.off[i] + 17 + speckLen;
-        tailLen[i] = ci.len[i] - 17 - speckLen;
+      const uint64_t speckLen = std::min<uint64_t>(9 + bytes_of_bits(tb), selLen[i] - 17);
+      if (17 + speckLen + 9 <= selLen[i]) {
+        tailOff[i] = selOff[i] + 17 + speckLen;
+        tailLen[i] = selLen[i] - 17 - speckLen;
         anyTail = true;
       }
     }
@@ -2596,18 +2629,23 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
   }
 
   struct Ref {
-    uint32_t gid;
+    uint32_t gid;    // container chunk (ci.off / ci.len)
+    uint32_t slot;   // this call's slot (heads, outHead)
     uint32_t org[3];
   };
   std::map<Dims, std::vector<Ref>> groups;
   for (uint32_t i = 0; i < nchunks; i++) {
-    const auto& c = chunks[i];
-    groups[Dims{c[1], c[3], c[5]}].push_back({i, {(uint32_t)c[0], (uint32_t)c[2], (uint32_t)c[4]}});
+    const auto& c = chunks[sel[i]];
+    groups[Dims{c[1], c[3], c[5]}].push_back({sel[i], i, {(uint32_t)c[0], (uint32_t)c[2], (uint32_t)c[4]}});
   }
 
+  // the output: the volume, or the box (its chunks write their windows: CropGeom, the kCrop writers)
   VolDesc vd{{ci.vol[0], ci.vol[1], ci.vol[2]}};
+  if (box)
+    vd = VolDesc{{box->dims[0], box->dims[1], box->dims[2]}};
   struct SubHost {
     std::vector<ChunkGeom> hg;
+    std::vector<CropGeom> hc;
     std::vector<uint64_t> ho, hl;
     std::vector<DecState> hs;
     DecBatchBufs bb;
@@ -2666,7 +2704,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
     probe.base = reinterpret_cast<char*>(uintptr_t(4096));  // size probe only
     probe.cap = ~size_t(0) / 2;
     DecBatchBufs tmp;
-    carve_dec(probe, P, 1, maxPayload, tmp, valsElems, refNPlanes);
+    carve_dec(probe, P, 1, maxPayload, tmp, valsElems, refNPlanes, box != nullptr);
     return probe.used;
   };
   // Refinement bit planes (speck_dec.h, DecBuffers::refPlanes): as many as the chunks of a group with 32-bit
@@ -2679,7 +2717,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
       return 0;
     uint32_t n = 0;
     for (const Ref& r : refs) {
-      const uint8_t* hd = heads.data() + (size_t)r.gid * 32;
+      const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
       if (ci.len[r.gid] >= 26 && !(hd[0] & 0x01) && hd[17] <= 32)
         n = std::max<uint32_t>(n, hd[17]);
     }
@@ -2696,7 +2734,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
     if (!compactEnv || !fuse_xyz(P) || !plan_fusable(P) || mr || slice || anyOutlier || P.fwd.size() < 3)
       return 0;
     for (const Ref& r : refs) {
-      const uint8_t* hd = heads.data() + (size_t)r.gid * 32;
+      const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
       if (ci.len[r.gid] >= 26 && !(hd[0] & 0x01) && hd[17] > 32)
         return 0;   // a chunk with 64-bit coefficients
     }
@@ -2856,7 +2894,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
         S.nb = (nbAll - done + (nsub - q) - 1) / (nsub - q);
         S.first = b0 + done;
         done += S.nb;
-        if (S.nb && !carve_dec(A, *P, S.nb, maxPayload, S.bb, compactElems, refNPlanes))
+        if (S.nb && !carve_dec(A, *P, S.nb, maxPayload, S.bb, compactElems, refNPlanes, box != nullptr))
           return -1;
         if (S.nb && compactElems)
           g_dbg_counter[2]++;
@@ -2889,7 +2927,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
             S.hg[i].org[a] = r.org[a];
           S.ho[i] = ci.off[r.gid];
           S.hl[i] = ci.len[r.gid];
-          const uint8_t* hd = heads.data() + (size_t)r.gid * 32;
+          const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
           if (S.hl[i] >= 26 && !(hd[0] & 0x01)) {
             const int nbp = hd[17];
             if (nbp > 32)
@@ -2904,7 +2942,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
         // beside everything below: it needs the container only; the correctors are added at the end
         bool batchOutliers = false;
         for (uint32_t i = 0; i < nb; i++)
-          batchOutliers |= outHead[g.second[first + i].gid].has;
+          batchOutliers |= outHead[g.second[first + i].slot].has;
         std::vector<OutlierChunk> hoc;
         OutlierBufs ob;
         {
@@ -2919,7 +2957,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
             uint64_t maxBits = 0;
             int maxNbp = 1;
             for (uint32_t i = 0; i < nb; i++) {
-              const OutHead& oh = outHead[g.second[first + i].gid];
+              const OutHead& oh = outHead[g.second[first + i].slot];
               if (!oh.has)
                 continue;
               hoc[i].has = 1;
@@ -2968,6 +3006,17 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
 
         }
         HIP_CHECK(hipMemcpyAsync(bb.geom, S.hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
+        if (box) {   // each chunk's window of the box and its origin relative to the box
+          S.hc.resize(nb);
+          for (uint32_t i = 0; i < nb; i++)
+            for (int a = 0; a < 3; a++) {
+              const size_t o = S.hg[i].org[a], lo = box->lo[a], hi = box->lo[a] + box->dims[a];
+              S.hc[i].rel[a] = (int32_t)((int64_t)o - (int64_t)lo);
+              S.hc[i].lo[a] = (uint32_t)(lo > o ? lo - o : 0);
+              S.hc[i].hi[a] = (uint32_t)std::min<size_t>(hi - o, cd[a]);
+            }
+          HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
+        }
         HIP_CHECK(hipMemcpyAsync(bb.chunkOff, S.ho.data(), nb * 8, hipMemcpyHostToDevice, ss));
         HIP_CHECK(hipMemcpyAsync(bb.chunkLen, S.hl.data(), nb * 8, hipMemcpyHostToDevice, ss));
         HIP_CHECK(hipMemsetAsync(d.cst, 0, nb * sizeof(CoderState), ss));
@@ -3146,10 +3195,10 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
             return -1;
           LiftFuse lf;
           dequant_fuse(k, lf);
+          const bool last = k == 0 && !batchOutliers;   // (the pass that writes the volume / the box)
           if (launch_lift(ss, false, fbrick ? boxVals : bb.vals, fbrick ? boxStride : bb.valsStride, nb, cd, ps.axis,
-                          ps.region, d.cst,
-                          (k == 0 && !batchOutliers) ? (std::is_same<T, float>::value ? 1 : 2) : 0,
-                          d_dst, vd, bb.geom, &lf))
+                          ps.region, d.cst, last ? (std::is_same<T, float>::value ? 1 : 2) : 0,
+                          d_dst, vd, bb.geom, &lf, last ? bb.crop : nullptr))
             return -1;
         }
         if (fbrick) {   // the finest level into the chunk buffer, as doubles
@@ -3166,13 +3215,13 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
           LiftFuse lf;
           dequant_fuse(2, lf);
           if (launch_lift_xyz(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst, std::is_same<T, float>::value ? 1 : 2,
-                              d_dst, vd, bb.geom, &lf))
+                              d_dst, vd, bb.geom, &lf, bb.crop))
             return -1;
         }
         if (fxy && mr && mr->nlev && slice && sub_volume(1))   // the finest level of a slice is the fused pair
           return -1;
         if (fxy && launch_lift_xy(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst,
-                                  std::is_same<T, float>::value ? 1 : 2, d_dst, vd, bb.geom))
+                                  std::is_same<T, float>::value ? 1 : 2, d_dst, vd, bb.geom, bb.crop))
           return -1;
         if (batchOutliers) {   // the correctors of the values the 1D decoder found meanwhile
           HIP_CHECK(hipStreamWaitEvent(ss, E.evOutl[q], 0));
@@ -3187,7 +3236,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
             }
         }
         if ((P->fwd.empty() || batchOutliers) &&
-            launch_scatter<T>(ss, d_dst, vd, bb.geom, nb, cd, bb.vals, bb.valsStride, d.cst))
+            launch_scatter<T>(ss, d_dst, vd, bb.geom, nb, cd, bb.vals, bb.valsStride, d.cst, bb.crop))
           return -1;
         if (nsub > 1)
           HIP_CHECK(hipEventRecord(E.evJoin[q], ss));
@@ -3376,6 +3425,38 @@ int set_max_dyn_lds(const void* fn, int bytes)
   HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   done[{dev, fn}] = bytes;
   return 0;
+}
+
+// The box [lo, lo + dims) of a container's volume: the chunks it meets; -1 when it is empty, leaves the
+// volume, or is too long along an axis for a chunk's origin relative to it (CropGeom::rel)
+int box_select(const ContainerInfo& ci, const size_t lo[3], const size_t dims[3], BoxSel& b)
+{
+  for (int a = 0; a < 3; a++) {
+    if (dims[a] > (size_t)INT32_MAX)
+      return -1;
+    b.lo[a] = lo[a];
+    b.dims[a] = dims[a];
+  }
+  return box_chunks(ci.vol, ci.chunk, b.lo, b.dims, b.ids) ? 0 : -1;
+}
+
+// a box that is the whole volume goes through the whole-volume decode
+bool box_is_volume(const ContainerInfo& ci, const BoxSel& b)
+{
+  return b.lo == Dims{0, 0, 0} && b.dims == ci.vol;
+}
+
+// the box `b` of the container at d_src (described by `ci`) into d_dst (x fastest); the caller has checked
+// that d_dst holds it
+int decompress_box(Engine& E, const uint8_t* d_src, size_t src_len, int output_float, const ContainerInfo& ci,
+                   const BoxSel& b, void* d_dst, size_t dst_cap_bytes, hipStream_t st)
+{
+  const BoxSel* box = box_is_volume(ci, b) ? nullptr : &b;
+  if (output_float)
+    return decompress_impl<float>(E, d_src, src_len, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci,
+                                  st, nullptr, false, box);
+  return decompress_impl<double>(E, d_src, src_len, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
+                                 st, nullptr, false, box);
 }
 
 }  // namespace sperrhip
@@ -3631,6 +3712,50 @@ int sperrhip_decompress_dev(const void* d_src, size_t src_len, int output_float,
     return decompress_impl<double>(E, static_cast<const uint8_t*>(d_src), src_len,
                                    static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
                                    st);
+  });
+}
+
+int sperrhip_box_chunks(size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y,
+                        size_t chunk_z, const size_t box_lo[3], const size_t box_dims[3], uint32_t* ids,
+                        size_t cap, size_t* count)
+{
+  return guarded("sperrhip_box_chunks", [&]() -> int {
+    if (!box_lo || !box_dims || !count)
+      return -1;
+    std::vector<uint32_t> v;
+    if (!box_chunks(Dims{dimx, dimy, dimz}, Dims{chunk_x, chunk_y, chunk_z}, Dims{box_lo[0], box_lo[1], box_lo[2]},
+                    Dims{box_dims[0], box_dims[1], box_dims[2]}, v))
+      return -1;
+    *count = v.size();
+    if (!ids || cap < v.size())
+      return 1;
+    memcpy(ids, v.data(), v.size() * sizeof(uint32_t));
+    return 0;
+  });
+}
+
+int sperrhip_decompress_box_dev(const void* d_src, size_t src_len, int output_float, const size_t box_lo[3],
+                                const size_t box_dims[3], void* d_dst, size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_decompress_box_dev", [&]() -> int {
+    if (!d_src || !d_dst || !box_lo || !box_dims)
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    ContainerInfo ci;
+    if (read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st))
+      return -1;
+    BoxSel b;
+    if (box_select(ci, box_lo, box_dims, b))
+      return -1;
+    const size_t esz = output_float ? sizeof(float) : sizeof(double);
+    if (dst_cap_bytes / esz < b.dims[0] * b.dims[1] * b.dims[2])
+      return -1;
+    return decompress_box(E, static_cast<const uint8_t*>(d_src), src_len, output_float, ci, b, d_dst,
+                          dst_cap_bytes, st);
   });
 }
 
@@ -4324,6 +4449,78 @@ int sperrhip_decomp_3d_multires(const void* src, size_t src_len, int output_floa
         *dimx = ci.vol[0];
         *dimy = ci.vol[1];
         *dimz = ci.vol[2];
+      }
+    }
+    release();
+    return rtn;
+  });
+}
+
+// host container in, malloc'd host box out: only the chunks the box meets travel to the device (packed,
+// one copy per run of consecutive chunks), are decoded there by the device path on the calling thread's
+// device and stream 0, and the box comes back in one copy
+int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float, const size_t box_lo[3],
+                           const size_t box_dims[3], void** dst)
+{
+  return guarded("sperrhip_decomp_3d_box", [&]() -> int {
+    if (!dst || *dst != nullptr)
+      return 1;
+    if (!src || !box_lo || !box_dims)
+      return -1;
+    ContainerInfo ci;
+    size_t need = 0;
+    if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
+      return -1;
+    BoxSel b;
+    if (box_select(ci, box_lo, box_dims, b))
+      return -1;
+    const size_t esz = output_float ? sizeof(float) : sizeof(double);
+    const size_t outBytes = b.dims[0] * b.dims[1] * b.dims[2] * esz;
+    // the chosen chunks' streams, packed in their order: the offsets of `packed` point into that buffer
+    ContainerInfo packed = ci;
+    size_t total = 0;
+    for (uint32_t id : b.ids) {
+      packed.off[id] = total;
+      total += ci.len[id];
+    }
+    void *d_in = nullptr, *d_out = nullptr;
+    auto release = [&]() {
+      if (d_in)
+        (void)hipFree(d_in);
+      if (d_out)
+        (void)hipFree(d_out);
+    };
+    if (hipMalloc(&d_in, std::max<size_t>(total, 1)) != hipSuccess || hipMalloc(&d_out, outBytes) != hipSuccess) {
+      (void)hipGetLastError();
+      fprintf(stderr, "[sperr_hip] device allocation failed\n");
+      release();
+      return -1;
+    }
+    const uint8_t* h = static_cast<const uint8_t*>(src);
+    int rtn = 0;
+    for (size_t i = 0; rtn == 0 && i < b.ids.size();) {   // runs of chunks that lie back to back in the container
+      size_t j = i + 1;
+      while (j < b.ids.size() && ci.off[b.ids[j]] == ci.off[b.ids[j - 1]] + ci.len[b.ids[j - 1]])
+        j++;
+      const size_t bytes = ci.off[b.ids[j - 1]] + ci.len[b.ids[j - 1]] - ci.off[b.ids[i]];
+      if (bytes && hipMemcpy(static_cast<uint8_t*>(d_in) + packed.off[b.ids[i]], h + ci.off[b.ids[i]], bytes,
+                             hipMemcpyHostToDevice) != hipSuccess)
+        rtn = -1;
+      i = j;
+    }
+    if (rtn == 0) {
+      Lease L;
+      rtn = L.e ? decompress_box(*L.e, static_cast<const uint8_t*>(d_in), total, output_float, packed, b, d_out,
+                                 outBytes, nullptr)
+                : -1;
+    }
+    if (rtn == 0) {
+      void* buf = malloc(outBytes);
+      if (buf && hipMemcpy(buf, d_out, outBytes, hipMemcpyDeviceToHost) == hipSuccess)
+        *dst = buf;
+      else {
+        free(buf);
+        rtn = -1;
       }
     }
     release();

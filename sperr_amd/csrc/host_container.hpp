@@ -69,6 +69,34 @@ inline std::vector<std::array<size_t, 6>> chunk_volume(const Dims& vol, const Di
   return out;
 }
 
+// The chunks (ids in chunk_volume order) that the box [lo, lo + dims) meets.  The segments along an
+// axis are chunk_volume's: all but the last start at multiples of the chunk extent, and the last one
+// runs to the end of the volume (it takes a short remainder in, or is that remainder).  Returns false,
+// with no ids, for an empty box, a box that leaves the volume, or a chunk extent of 0.
+inline bool box_chunks(const Dims& vol, const Dims& chunk, const Dims& lo, const Dims& dims,
+                       std::vector<uint32_t>& ids)
+{
+  ids.clear();
+  for (int a = 0; a < 3; a++)
+    if (vol[a] == 0 || chunk[a] == 0 || dims[a] == 0 || lo[a] >= vol[a] || dims[a] > vol[a] - lo[a])
+      return false;
+  const size_t n = chunk_count(vol, chunk);
+  if (n > UINT32_MAX)
+    return false;
+  size_t nseg[3], s0[3], s1[3];
+  chunk_segments(vol, chunk, nseg);
+  for (int a = 0; a < 3; a++) {   // segment of a position: p / chunk, the last one taking what is past it
+    s0[a] = std::min(lo[a] / chunk[a], nseg[a] - 1);
+    s1[a] = std::min((lo[a] + dims[a] - 1) / chunk[a], nseg[a] - 1);
+  }
+  ids.reserve((s1[0] - s0[0] + 1) * (s1[1] - s0[1] + 1) * (s1[2] - s0[2] + 1));
+  for (size_t z = s0[2]; z <= s1[2]; z++)
+    for (size_t y = s0[1]; y <= s1[1]; y++)
+      for (size_t x = s0[0]; x <= s1[0]; x++)
+        ids.push_back((uint32_t)((z * nseg[1] + y) * nseg[0] + x));
+  return true;
+}
+
 struct ContainerInfo {
   Dims vol, chunk;
   size_t nvals = 0;   // vol[0] * vol[1] * vol[2], checked not to wrap

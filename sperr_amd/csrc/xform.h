@@ -20,10 +20,12 @@ int launch_condition(hipStream_t stream, const T* vol, VolDesc vd, const ChunkGe
                      size_t valsStride, CoderState* st, bool gather, bool want_range = false,
                      bool org_x_aligned = false);   // every chunk's x origin is a multiple of 16 bytes
 
+// crop (all the writers below): not null, the volume is a box of `vd`'s dims and every chunk writes
+// its window of it (CropGeom, one per chunk); `geom` is not read then
 template <typename T>
 int launch_scatter(hipStream_t stream, T* vol, VolDesc vd, const ChunkGeom* geom,
                    uint32_t nchunks, const uint32_t cdims[3], const double* vals,
-                   size_t valsStride, const CoderState* st);
+                   size_t valsStride, const CoderState* st, const CropGeom* crop = nullptr);
 
 // What a lifting pass can do on the way for the samples of its region that no LATER pass (in
 // forward order) touches, i.e. those outside `inner`, the region of the next pass:
@@ -64,14 +66,15 @@ struct LiftFuse {
 int launch_lift(hipStream_t stream, bool forward, double* vals, size_t valsStride,
                 uint32_t nchunks, const uint32_t cdims[3], int axis, const uint32_t region[3],
                 CoderState* st, int io = 0, void* volume = nullptr, VolDesc vd = VolDesc{},
-                const ChunkGeom* geom = nullptr, const LiftFuse* fuse = nullptr);
+                const ChunkGeom* geom = nullptr, const LiftFuse* fuse = nullptr,
+                const CropGeom* crop = nullptr);
 
 // The x and y passes of the finest level fused with the volume access (forward: volume -> vals,
 // inverse: vals -> volume); only for chunks whose first two passes are the full-size x and y ones.
 bool lift_xy_applicable(const uint32_t cdims[3]);
 int launch_lift_xy(hipStream_t stream, bool forward, double* vals, size_t valsStride,
                    uint32_t nchunks, const uint32_t cdims[3], const CoderState* st, int io,
-                   void* volume, VolDesc vd, const ChunkGeom* geom);
+                   void* volume, VolDesc vd, const ChunkGeom* geom, const CropGeom* crop = nullptr);
 
 // The x, y AND z pass of the finest level in one kernel (k_lift_xyz_fwd / _inv): the z direction is
 // a sliding window of per-position lifting pipelines in registers.  Forward: volume -> vals, with
@@ -81,7 +84,7 @@ int launch_lift_xy(hipStream_t stream, bool forward, double* vals, size_t valsSt
 bool lift_xyz_applicable(const uint32_t cdims[3]);
 int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsStride, uint32_t nchunks,
                     const uint32_t cdims[3], CoderState* st, int io, void* volume, VolDesc vd,
-                    const ChunkGeom* geom, const LiftFuse* fuse);
+                    const ChunkGeom* geom, const LiftFuse* fuse, const CropGeom* crop = nullptr);
 
 // have_max: CoderState::maxabs is already there (the lifting passes collected it)
 int launch_maxabs_q(hipStream_t stream, const double* vals, size_t valsStride, uint32_t nchunks,

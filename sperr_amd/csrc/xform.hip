@@ -200,14 +200,30 @@ __global__ void k_gather_condition(const T* __restrict__ vol, VolDesc vd, const 
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// crop variant of the writers (kCrop, CropGeom): a chunk writes only the samples of its window, at box
+// addresses.  kCrop false is the whole-volume decode: those instantiations compile to what they were.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool crop_has(const CropGeom& g, uint32_t x, uint32_t y, uint32_t z)
+{
+  return x - g.lo[0] < g.hi[0] - g.lo[0] && y - g.lo[1] < g.hi[1] - g.lo[1] && z - g.lo[2] < g.hi[2] - g.lo[2];
+}
+// box address of chunk sample (x, y, z) of the window
+__device__ __forceinline__ size_t crop_addr(const CropGeom& g, const VolDesc& vd, uint32_t x, uint32_t y, uint32_t z)
+{
+  const size_t bx = (size_t)((int64_t)x + g.rel[0]), by = (size_t)((int64_t)y + g.rel[1]),
+               bz = (size_t)((int64_t)z + g.rel[2]);
+  return (bz * vd.dims[1] + by) * vd.dims[0] + bx;
+}
+
 // out[scatter(i)] = (T)(vals[i] + mean), or the constant value (Conditioner.cpp:66-96)
-template <typename T>
-__global__ void k_scatter_uncondition(T* __restrict__ vol, VolDesc vd, const ChunkGeom* geom,
+template <typename T, bool kCrop = false>
+__global__ void k_scatter_uncondition(T* __restrict__ vol, VolDesc vd, const GeomOf<kCrop>* geom,
                                       uint32_t cx, uint32_t cy, uint32_t n, const double* vals,
                                       size_t valsStride, const CoderState* st)
 {
   const uint32_t c = blockIdx.y;
-  const ChunkGeom g = geom[c];
+  const GeomOf<kCrop> g = geom[c];
   const double mean = st[c].mean;
   const bool is_const = st[c].is_const != 0;
   const size_t vx = vd.dims[0], vy = vd.dims[1];
@@ -216,8 +232,14 @@ __global__ void k_scatter_uncondition(T* __restrict__ vol, VolDesc vd, const Chu
        k++, i += blockDim.x) {
     const uint32_t x = i % cx, r = i / cx;
     const uint32_t y = r % cy, z = r / cy;
-    const double v = is_const ? mean : in[i] + mean;
-    vol[((size_t)(g.org[2] + z) * vy + (g.org[1] + y)) * vx + g.org[0] + x] = (T)v;
+    if constexpr (kCrop) {
+      if (crop_has(g, x, y, z))
+        vol[crop_addr(g, vd, x, y, z)] = (T)(is_const ? mean : in[i] + mean);
+    }
+    else {
+      const double v = is_const ? mean : in[i] + mean;
+      vol[((size_t)(g.org[2] + z) * vy + (g.org[1] + y)) * vx + g.org[0] + x] = (T)v;
+    }
   }
 }
 
@@ -240,12 +262,15 @@ extern __shared__ __attribute__((aligned(16))) char dyn_smem[];
 // SPERR3D_OMP_D.cpp:167-184, SPERR_C_API.cpp:246-250).  Both passes cover the whole chunk.
 constexpr int kLoadBatch = 8;
 
-template <bool FORWARD, int IO>
+// kCrop (inverse, IO != 0 only): the pass writes the chunk's window into the box; a tile with no line
+// in the window has nothing to do
+template <bool FORWARD, int IO, bool kCrop = false>
 __global__ void __launch_bounds__(kThreads)
 k_lift_axis(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, int axis, uint32_t rx,
             uint32_t ry, uint32_t rz, int NL, LiftConsts K, CoderState* st, void* volume,
-            VolDesc vd, const ChunkGeom* geom, LiftFuse F)
+            VolDesc vd, const GeomOf<kCrop>* geom, LiftFuse F)
 {
+  static_assert(!kCrop || (!FORWARD && IO != 0), "the crop variant is a last inverse pass");
   const uint32_t c = blockIdx.y;
   const bool is_const = st[c].is_const != 0;
   if (is_const && !(IO != 0 && !FORWARD))
@@ -273,7 +298,14 @@ k_lift_axis(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, int axis,
   VT* vol = reinterpret_cast<VT*>(volume);
   size_t vbase = 0, vsl = 0, vsu = 0;
   double mean = 0.0;
-  if (IO != 0) {
+  CropGeom cg{};
+  if constexpr (kCrop) {   // (uniform)
+    cg = geom[c];
+    if (tw - cg.lo[wa] >= cg.hi[wa] - cg.lo[wa] || u0 >= cg.hi[ua] || u0 + nl <= cg.lo[ua])
+      return;
+    mean = st[c].mean;
+  }
+  else if (IO != 0) {
     const ChunkGeom g = geom[c];
     const size_t vstride[3] = {1, (size_t)vd.dims[0], (size_t)vd.dims[0] * vd.dims[1]};
     vbase = (size_t)g.org[0] * vstride[0] + (size_t)g.org[1] * vstride[1] +
@@ -426,6 +458,16 @@ k_lift_axis(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, int axis,
   }
 
   // ---- store ----
+  // (crop variant: sample (line l, position p) goes to the box when it lies in the chunk's window)
+  auto crop_store = [&](uint32_t l, uint32_t p, VT v) {
+    uint32_t xyz[3];
+    xyz[axis] = p;
+    xyz[ua] = u0 + l;
+    xyz[wa] = tw;
+    if (crop_has(cg, xyz[0], xyz[1], xyz[2]))
+      vol[crop_addr(cg, vd, xyz[0], xyz[1], xyz[2])] = v;
+  };
+  (void)crop_store;
   const bool wantMax = FORWARD && F.mode == 1 && !is_const;
   double vmax = 0.0;
   if (axis == 0) {
@@ -435,7 +477,9 @@ k_lift_axis(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, int axis,
       if (p >= len)
         continue;
       const uint32_t src = FORWARD ? p : ((p & 1) ? even_len + (p >> 1) : (p >> 1));
-      if (IO != 0 && !FORWARD)
+      if constexpr (kCrop)
+        crop_store(l, p, (VT)(is_const ? mean : sm[src * NLP + l] + mean));
+      else if (IO != 0 && !FORWARD)
         vol[vbase + l * vsu + p * vsl] = (VT)(is_const ? mean : sm[src * NLP + l] + mean);
       else {
         const double v = sm[src * NLP + l];
@@ -451,7 +495,9 @@ k_lift_axis(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, int axis,
     if (l < nl)
       for (uint32_t p = k0; p < len; p += kg) {
         const uint32_t src = FORWARD ? p : ((p & 1) ? even_len + (p >> 1) : (p >> 1));
-        if (IO != 0 && !FORWARD)
+        if constexpr (kCrop)
+          crop_store(l, p, (VT)(is_const ? mean : sm[src * NLP + l] + mean));
+        else if (IO != 0 && !FORWARD)
           vol[vbase + l * vsu + p * vsl] = (VT)(is_const ? mean : sm[src * NLP + l] + mean);
         else {
           const double v = sm[src * NLP + l];
@@ -544,12 +590,14 @@ __device__ __forceinline__ void lift16(double (&r)[16], const LiftConsts& K)
   }
 }
 
-template <bool FORWARD, int IO>
+// kCrop (inverse only): the tile's rows of the chunk's window go to the box; a tile without one returns
+template <bool FORWARD, int IO, bool kCrop = false>
 __global__ void __launch_bounds__(kXYThreads)
 k_lift_xy(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz, int R,
-          LiftConsts K, const CoderState* st, void* volume, VolDesc vd, const ChunkGeom* geom)
+          LiftConsts K, const CoderState* st, void* volume, VolDesc vd, const GeomOf<kCrop>* geom)
 {
   static_assert(IO == 1 || IO == 2, "float or double volume");
+  static_assert(!kCrop || !FORWARD, "the crop variant is a last inverse pass");
   using VT = typename std::conditional<IO == 1, float, double>::type;
   const uint32_t c = blockIdx.y;
   const bool is_const = st[c].is_const != 0;
@@ -564,17 +612,42 @@ k_lift_xy(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz
   const uint32_t nrow = yhi - ylo;
   const uint32_t RS = cx + 1;                           // row stride in LDS
   const uint32_t xe = cx - cx / 2, ye = cy - cy / 2;    // even samples of a row / of a column
-  const ChunkGeom g = geom[c];
+  const GeomOf<kCrop> g = geom[c];
   VT* vol = reinterpret_cast<VT*>(volume);
   const size_t vsy = vd.dims[0], vsz = (size_t)vd.dims[0] * vd.dims[1];
-  const size_t vbase = (size_t)(g.org[2] + z) * vsz + (size_t)g.org[1] * vsy + g.org[0];
+  size_t vbase = 0;
+  // rows [wy0, wy1) and columns [wx0, wx1) of the tile are written (all of them but in the crop variant)
+  uint32_t wy0 = y0, wy1 = yend, wx0 = 0, wx1 = cx;
+  if constexpr (kCrop) {   // (uniform)
+    wy0 = max(y0, g.lo[1]);
+    wy1 = min(yend, g.hi[1]);
+    wx0 = g.lo[0];
+    wx1 = g.hi[0];
+    if (z - g.lo[2] >= g.hi[2] - g.lo[2] || wy0 >= wy1)
+      return;
+  }
+  else
+    vbase = (size_t)(g.org[2] + z) * vsz + (size_t)g.org[1] * vsy + g.org[0];
+  // address of sample (x, y) of the tile's slice
+  auto out_at = [&](uint32_t x, uint32_t y) -> size_t {
+    if constexpr (kCrop)
+      return crop_addr(g, vd, x, y, z);
+    else
+      return vbase + (size_t)y * vsy + x;
+  };
   double* buf = vals + c * valsStride + (size_t)z * cx * cy;
   const double mean = st[c].mean;
   const uint32_t tid = threadIdx.x;
 
   if (is_const) {   // inverse only: the chunk is its constant
-    for (uint32_t k = tid; k < (yend - y0) * cx; k += kXYThreads)
-      vol[vbase + (size_t)(y0 + k / cx) * vsy + k % cx] = (VT)mean;
+    if constexpr (kCrop) {
+      const uint32_t w = wx1 - wx0;
+      for (uint32_t k = tid; k < (wy1 - wy0) * w; k += kXYThreads)
+        vol[out_at(wx0 + k % w, wy0 + k / w)] = (VT)mean;
+    }
+    else
+      for (uint32_t k = tid; k < (yend - y0) * cx; k += kXYThreads)
+        vol[vbase + (size_t)(y0 + k / cx) * vsy + k % cx] = (VT)mean;
     return;
   }
 
@@ -723,6 +796,15 @@ k_lift_xy(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz
     }
     __syncthreads();
     lift_x(y0 - ylo, yend - ylo);   // (only the tile's own rows go on)
+    if constexpr (kCrop) {
+      for (uint32_t y = wy0 + wave; y < wy1; y += nwaves) {
+        VT* dstrow = vol + out_at(wx0, y);   // (any x origin: one sample per lane)
+        const double* srow = sm + (size_t)(y - ylo) * RS;
+        for (uint32_t x = wx0 + lane; x < wx1; x += 64)
+          dstrow[x - wx0] = (VT)(srow[x] + mean);
+      }
+    }
+    else
     for (uint32_t y = y0 + wave; y < yend; y += nwaves) {
       VT* dstrow = vol + vbase + (size_t)y * vsy;
       const double* srow = sm + (size_t)(y - ylo) * RS;
@@ -1032,10 +1114,11 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
 // SG: the coefficients carry their sign where the chunk allows it (LiftFuse::coefSigned, coef_scheme), a kernel of its own -- with both fast paths in
 // one function the register allocator spilled inside the slice loop (88 registers against 38) and the kernel took 5.4 ms
 // instead of 3.7
-template <int IO, bool SG>
+// kCrop: the rows of the chunk's window go to the box; a tile with no row in the window returns at once
+template <int IO, bool SG, bool kCrop = false>
 __global__ void __launch_bounds__(kXYZThreadsI) __attribute__((amdgpu_waves_per_eu(kXYZThreadsI / 256, kXYZThreadsI / 256)))
 k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz, LiftConsts K,
-               const CoderState* st, void* volume, VolDesc vd, const ChunkGeom* geom, LiftFuse F, uint32_t nseg)
+               const CoderState* st, void* volume, VolDesc vd, const GeomOf<kCrop>* geom, LiftFuse F, uint32_t nseg)
 {
   static_assert(IO == 1 || IO == 2, "float or double volume");
   using VT = typename std::conditional<IO == 1, float, double>::type;
@@ -1056,7 +1139,22 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   const uint32_t xe = cx - cx / 2, ye = cy - cy / 2, ze = cz - cz / 2;
   VT* vol = reinterpret_cast<VT*>(volume);
   const size_t vsy = vd.dims[0], vsz = (size_t)vd.dims[0] * vd.dims[1];
-  VT* volc = vol + ((size_t)geom[c].org[2] * vsz + (size_t)geom[c].org[1] * vsy + geom[c].org[0]);
+  VT* volc = vol;
+  CropGeom cg{};
+  uint32_t wy0 = 0, wy1 = 0;   // crop variant: the tile's rows [y0 + wy0, y0 + wy1) lie in the window
+  if constexpr (kCrop) {   // (uniform)
+    cg = geom[c];
+    wy0 = max(y0, cg.lo[1]) - y0;
+    wy1 = min(y0 + nt, cg.hi[1]);
+    if (y0 + wy0 >= wy1)
+      return;
+    wy1 -= y0;
+  }
+  else
+    volc = vol + ((size_t)geom[c].org[2] * vsz + (size_t)geom[c].org[1] * vsy + geom[c].org[0]);
+  // crop variant: row y0 + r of slice z -> the box row that holds its window, x = wx0 at its start
+  auto crop_row = [&](uint32_t z, uint32_t r) -> VT* { return vol + crop_addr(cg, vd, cg.lo[0], y0 + r, z); };
+  (void)crop_row;
   const double* buf = vals + c * valsStride;
   const size_t sliceN = (size_t)cx * cy;
   const uint32_t bufx = F.bufx ? F.bufx : cx;                       // the chunk buffer may be compact:
@@ -1065,6 +1163,13 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   const uint32_t lane = tid & 63u, wave = tid >> 6, nwaves = kXYZThreadsI / 64;
 
   if (st[c].is_const != 0) {   // the chunk is its constant
+    if constexpr (kCrop) {
+      const uint32_t w = cg.hi[0] - cg.lo[0], nr = wy1 - wy0;
+      for (uint32_t z = cg.lo[2] + seg; z < cg.hi[2]; z += nseg)
+        for (uint32_t k = tid; k < nr * w; k += kXYZThreadsI)
+          crop_row(z, wy0 + k / w)[k % w] = (VT)mean;
+    }
+    else
     for (uint32_t z = seg; z < cz; z += nseg)
       for (uint32_t k = tid; k < nt * cx; k += kXYZThreadsI)
         volc[(size_t)z * vsz + (size_t)(y0 + k / cx) * vsy + k % cx] = (VT)mean;
@@ -1143,6 +1248,17 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   // rows of a finished slice (in staging buffer `which`) -> volume, mean added, narrowed
   auto store_rows = [&](uint32_t z, uint32_t which) {
     const double* X = sm + (which ? bufN : 0u);
+    if constexpr (kCrop) {   // (any x origin: one sample per lane)
+      if (z - cg.lo[2] >= cg.hi[2] - cg.lo[2])
+        return;
+      for (uint32_t r = wy0 + wave; r < wy1; r += nwaves) {
+        VT* dstrow = crop_row(z, r);
+        const double* srow = X + (size_t)(kXYHalo + r) * RS + 4;
+        for (uint32_t x = cg.lo[0] + lane; x < cg.hi[0]; x += 64)
+          dstrow[x - cg.lo[0]] = (VT)(F.noMean ? srow[x] : srow[x] + mean);
+      }
+      return;
+    }
     for (uint32_t r = wave; r < nt; r += nwaves) {
       VT* dstrow = volc + (size_t)z * vsz + (size_t)(y0 + r) * vsy;
       const double* srow = X + (size_t)(kXYHalo + r) * RS + 4;
@@ -1750,16 +1866,20 @@ static int pick_nl(uint32_t len, int axis, size_t* smem)
 int launch_lift(hipStream_t stream, bool forward, double* vals, size_t valsStride,
                 uint32_t nchunks, const uint32_t cdims[3], int axis, const uint32_t region[3],
                 CoderState* st, int io, void* volume, VolDesc vd, const ChunkGeom* geom,
-                const LiftFuse* fuse)
+                const LiftFuse* fuse, const CropGeom* crop)
 {
   const LiftFuse F = fuse ? *fuse : LiftFuse{};
+  if (crop && (forward || io == 0))
+    return -1;
   {
-    const void* fns[6] = {reinterpret_cast<const void*>(&k_lift_axis<true, 0>),
+    const void* fns[8] = {reinterpret_cast<const void*>(&k_lift_axis<true, 0>),
                           reinterpret_cast<const void*>(&k_lift_axis<true, 1>),
                           reinterpret_cast<const void*>(&k_lift_axis<true, 2>),
                           reinterpret_cast<const void*>(&k_lift_axis<false, 0>),
                           reinterpret_cast<const void*>(&k_lift_axis<false, 1>),
-                          reinterpret_cast<const void*>(&k_lift_axis<false, 2>)};
+                          reinterpret_cast<const void*>(&k_lift_axis<false, 2>),
+                          reinterpret_cast<const void*>(&k_lift_axis<false, 1, true>),
+                          reinterpret_cast<const void*>(&k_lift_axis<false, 2, true>)};
     for (const void* f : fns)
       if (set_max_dyn_lds(f, 160 * 1024))
         return -1;
@@ -1785,6 +1905,14 @@ int launch_lift(hipStream_t stream, bool forward, double* vals, size_t valsStrid
       LAUNCH_K((k_lift_axis<true, 2>), grid, dim3(kThreads), smem, stream, LIFT_ARGS);
     else
       LAUNCH_K((k_lift_axis<true, 0>), grid, dim3(kThreads), smem, stream, LIFT_ARGS);
+  }
+  else if (crop) {
+#define CROP_ARGS vals, valsStride, cdims[0], cdims[1], axis, region[0], region[1], region[2], NL, K, st, volume, vd, crop, F
+    if (io == 1)
+      LAUNCH_K((k_lift_axis<false, 1, true>), grid, dim3(kThreads), smem, stream, CROP_ARGS);
+    else
+      LAUNCH_K((k_lift_axis<false, 2, true>), grid, dim3(kThreads), smem, stream, CROP_ARGS);
+#undef CROP_ARGS
   }
   else {
     if (io == 1)
@@ -1823,13 +1951,17 @@ bool lift_xy_applicable(const uint32_t cdims[3])
 
 int launch_lift_xy(hipStream_t stream, bool forward, double* vals, size_t valsStride,
                    uint32_t nchunks, const uint32_t cdims[3], const CoderState* st, int io,
-                   void* volume, VolDesc vd, const ChunkGeom* geom)
+                   void* volume, VolDesc vd, const ChunkGeom* geom, const CropGeom* crop)
 {
+  if (crop && forward)
+    return -1;
   {
-    const void* fns[4] = {reinterpret_cast<const void*>(&k_lift_xy<true, 1>),
+    const void* fns[6] = {reinterpret_cast<const void*>(&k_lift_xy<true, 1>),
                           reinterpret_cast<const void*>(&k_lift_xy<true, 2>),
                           reinterpret_cast<const void*>(&k_lift_xy<false, 1>),
-                          reinterpret_cast<const void*>(&k_lift_xy<false, 2>)};
+                          reinterpret_cast<const void*>(&k_lift_xy<false, 2>),
+                          reinterpret_cast<const void*>(&k_lift_xy<false, 1, true>),
+                          reinterpret_cast<const void*>(&k_lift_xy<false, 2, true>)};
     for (const void* f : fns)
       if (set_max_dyn_lds(f, 160 * 1024))
         return -1;
@@ -1847,6 +1979,14 @@ int launch_lift_xy(hipStream_t stream, bool forward, double* vals, size_t valsSt
       LAUNCH_K((k_lift_xy<true, 1>), grid, dim3(kXYThreads), smem, stream, XY_ARGS);
     else
       LAUNCH_K((k_lift_xy<true, 2>), grid, dim3(kXYThreads), smem, stream, XY_ARGS);
+  }
+  else if (crop) {
+#define CROP_ARGS vals, valsStride, cdims[0], cdims[1], cdims[2], R, K, st, volume, vd, crop
+    if (io == 1)
+      LAUNCH_K((k_lift_xy<false, 1, true>), grid, dim3(kXYThreads), smem, stream, CROP_ARGS);
+    else
+      LAUNCH_K((k_lift_xy<false, 2, true>), grid, dim3(kXYThreads), smem, stream, CROP_ARGS);
+#undef CROP_ARGS
   }
   else {
     if (io == 1)
@@ -1873,9 +2013,9 @@ bool lift_xyz_applicable(const uint32_t cdims[3])
 
 int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsStride, uint32_t nchunks,
                     const uint32_t cdims[3], CoderState* st, int io, void* volume, VolDesc vd,
-                    const ChunkGeom* geom, const LiftFuse* fuse)
+                    const ChunkGeom* geom, const LiftFuse* fuse, const CropGeom* crop)
 {
-  if (!lift_xyz_applicable(cdims) || (io != 1 && io != 2))
+  if (!lift_xyz_applicable(cdims) || (io != 1 && io != 2) || (crop && forward))
     return -1;
   const LiftFuse F = fuse ? *fuse : LiftFuse{};
   size_t smem = 2 * (size_t)kXYZStaged * xyz_row_stride(cdims[0]) * sizeof(double);   // two staging buffers
@@ -1885,9 +2025,11 @@ int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsS
             (size_t)kXYZBoxSlots * 64 * sizeof(uint32_t);              //   and the box samples (k_lift_xyz_inv<.., true>)
 #endif
   {
-    const void* fns[6] = {reinterpret_cast<const void*>(&k_lift_xyz_fwd<1>), reinterpret_cast<const void*>(&k_lift_xyz_fwd<2>),
-                          reinterpret_cast<const void*>(&k_lift_xyz_inv<1, false>), reinterpret_cast<const void*>(&k_lift_xyz_inv<2, false>),
-                          reinterpret_cast<const void*>(&k_lift_xyz_inv<1, true>), reinterpret_cast<const void*>(&k_lift_xyz_inv<2, true>)};
+    const void* fns[10] = {reinterpret_cast<const void*>(&k_lift_xyz_fwd<1>), reinterpret_cast<const void*>(&k_lift_xyz_fwd<2>),
+                           reinterpret_cast<const void*>(&k_lift_xyz_inv<1, false>), reinterpret_cast<const void*>(&k_lift_xyz_inv<2, false>),
+                           reinterpret_cast<const void*>(&k_lift_xyz_inv<1, true>), reinterpret_cast<const void*>(&k_lift_xyz_inv<2, true>),
+                           reinterpret_cast<const void*>(&k_lift_xyz_inv<1, false, true>), reinterpret_cast<const void*>(&k_lift_xyz_inv<2, false, true>),
+                           reinterpret_cast<const void*>(&k_lift_xyz_inv<1, true, true>), reinterpret_cast<const void*>(&k_lift_xyz_inv<2, true, true>)};
     for (const void* f : fns)
       if (set_max_dyn_lds(f, 160 * 1024))
         return -1;
@@ -1913,7 +2055,20 @@ int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsS
 #define XYZ_INV_LAUNCH(io_, sg_)                                                                                    \
   LAUNCH_K((k_lift_xyz_inv<io_, sg_>), grid, dim3(kXYZThreadsI), smem, stream, vals, valsStride, cdims[0], cdims[1], \
            cdims[2], K, st, volume, vd, geom, F, nseg)
-    if (io == 1) {
+#define XYZ_CROP_LAUNCH(io_, sg_)                                                                                   \
+  LAUNCH_K((k_lift_xyz_inv<io_, sg_, true>), grid, dim3(kXYZThreadsI), smem, stream, vals, valsStride, cdims[0],      \
+           cdims[1], cdims[2], K, st, volume, vd, crop, F, nseg)
+    if (crop) {
+      if (io == 1 && sg)
+        XYZ_CROP_LAUNCH(1, true);
+      else if (io == 1)
+        XYZ_CROP_LAUNCH(1, false);
+      else if (sg)
+        XYZ_CROP_LAUNCH(2, true);
+      else
+        XYZ_CROP_LAUNCH(2, false);
+    }
+    else if (io == 1) {
       if (sg)
         XYZ_INV_LAUNCH(1, true);
       else
@@ -1926,6 +2081,7 @@ int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsS
         XYZ_INV_LAUNCH(2, false);
     }
 #undef XYZ_INV_LAUNCH
+#undef XYZ_CROP_LAUNCH
   }
   HIP_CHECK(hipGetLastError());
   return 0;
@@ -1971,9 +2127,13 @@ template int launch_condition<double>(hipStream_t, const double*, VolDesc, const
 template <typename T>
 int launch_scatter(hipStream_t stream, T* vol, VolDesc vd, const ChunkGeom* geom,
                    uint32_t nchunks, const uint32_t cdims[3], const double* vals,
-                   size_t valsStride, const CoderState* st)
+                   size_t valsStride, const CoderState* st, const CropGeom* crop)
 {
   const uint32_t n = cdims[0] * cdims[1] * cdims[2];
+  if (crop)
+    LAUNCH_K((k_scatter_uncondition<T, true>), dim3((n + kThreads * 4 - 1) / (kThreads * 4), nchunks), dim3(kThreads), 0,
+             stream, vol, vd, crop, cdims[0], cdims[1], n, vals, valsStride, st);
+  else
   LAUNCH_K(k_scatter_uncondition<T>,
                      dim3((n + kThreads * 4 - 1) / (kThreads * 4), nchunks), dim3(kThreads), 0,
                      stream, vol, vd, geom, cdims[0], cdims[1], n, vals, valsStride, st);
@@ -1981,9 +2141,11 @@ int launch_scatter(hipStream_t stream, T* vol, VolDesc vd, const ChunkGeom* geom
   return 0;
 }
 template int launch_scatter<float>(hipStream_t, float*, VolDesc, const ChunkGeom*, uint32_t,
-                                   const uint32_t[3], const double*, size_t, const CoderState*);
+                                   const uint32_t[3], const double*, size_t, const CoderState*,
+                                   const CropGeom*);
 template int launch_scatter<double>(hipStream_t, double*, VolDesc, const ChunkGeom*, uint32_t,
-                                    const uint32_t[3], const double*, size_t, const CoderState*);
+                                    const uint32_t[3], const double*, size_t, const CoderState*,
+                                    const CropGeom*);
 
 int launch_maxabs_q(hipStream_t stream, const double* vals, size_t valsStride, uint32_t nchunks,
                     uint32_t n, CoderState* st, bool have_max)
