@@ -20,6 +20,7 @@
 #include <memory>
 #include <condition_variable>
 #include <mutex>
+#include <numeric>
 #include <thread>
 #include <string>
 #include <vector>
@@ -525,7 +526,7 @@ struct Engine {
   std::vector<Dims> planOrder;             // least recently used first
   DevBuf arena, slots, misc;
   DevBuf outlFixed, outlVar, outlStream;   // point-wise error mode: workspace of the outlier coder
-  DevBuf pweBox;                           //   ... and the coarser levels' box of its reconstruction (pwe_outlier_stage)
+  DevBuf pweBox;                           //   ... and the coarser levels' box of its reconstruction (pwe_stage_begin)
   hipStream_t pweLastStream = nullptr;     //   stream the last batch's outlier stage ended on without a wait (round 6): the
                                            //   next batch of the SAME call may run its stage on another one and reuses the buffers
   DevBuf outlDec[kSubStreams];             //   (decoder: one per sub-batch of a call)
@@ -615,10 +616,9 @@ struct Engine {
     for (uint32_t q = 0; q < kSubStreams; q++) {
       HIP_CHECK(hipEventCreateWithFlags(&evOutl[q], hipEventDisableTiming));
       HIP_CHECK(hipEventCreateWithFlags(&evOutlFork[q], hipEventDisableTiming));
-      if (q == 0)
-        HIP_CHECK(hipEventCreateWithFlags(&evPweFork, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&evPweJoin, hipEventDisableTiming));
     }
+    HIP_CHECK(hipEventCreateWithFlags(&evPweFork, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&evPweJoin, hipEventDisableTiming));
     for (uint32_t q = 0; q < kSubStreams; q++) {
       HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&liveHost[q]), kLiveSlots * sizeof(uint32_t), hipHostMallocDefault));
       for (int k = 0; k < kLiveSlots; k++)
@@ -1052,12 +1052,11 @@ bool carve_enc(Arena& A, const ShapePlan& P, uint32_t B, uint64_t raw_budget, En
   // The coder's node arrays, birth records and second list are written after the quantiser has read
   // the chunk buffer for the last time: they lie over it (round 3; 127 of the 421 MB a 256^3 chunk
   // took).  A batch that needs the 64-bit retry transforms its chunks again and gives these arrays
-  // memory of their own (Engine::wideScratch, compress_impl).  SPERR_HIP_ENC_ALIAS=0: no overlay.
-  static const bool aliasEnv = !(tune_getenv("SPERR_HIP_ENC_ALIAS") && atoi(tune_getenv("SPERR_HIP_ENC_ALIAS")) == 0);
+  // memory of their own (Engine::wideScratch, compress_impl).
   {
     Arena over;
     over.base = reinterpret_cast<char*>(o.vals);
-    over.cap = (aliasEnv && alias) ? Npad * B * sizeof(double) : 0;
+    over.cap = alias ? Npad * B * sizeof(double) : 0;
     const size_t before = A.used;
     if (!carve_enc_coder(over, &A, P, B, e))
       return false;
@@ -1181,9 +1180,6 @@ bool plan_fusable(const ShapePlan& P)
 {
   if (P.fwd.empty())
     return false;
-  static const bool on = !(tune_getenv("SPERR_HIP_LIFT_FUSE") && atoi(tune_getenv("SPERR_HIP_LIFT_FUSE")) == 0);
-  if (!on)
-    return false;
   uint32_t inner[3];
   for (size_t k = 0; k < P.fwd.size(); k++)
     if (pass_fuse(P, k, inner) < 0)
@@ -1272,10 +1268,12 @@ int wide_retry_prepare(hipStream_t ss, Engine& E, const ShapePlan& P, EncBatchBu
 // the host (the same libm the reference uses), the error estimate on the device with the
 // reference's summation order; chunks whose largest coefficient needs more than 32 bits are
 // flagged for the 64-bit pass (SPECK_FLT.cpp:324-337).
-int psnr_q_search(hipStream_t st, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb, double psnr)
+// (`hc`, `got`: the caller's, alive until the call's last wait)
+int psnr_q_search(hipStream_t st, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb, double psnr,
+                  std::vector<CoderState>& hc, std::vector<CoderState>& got)
 {
   EncBuffers& e = bb.eb;
-  std::vector<CoderState> hc(nb);
+  hc.assign(nb, CoderState{});
   HIP_CHECK(hipMemcpyAsync(hc.data(), e.cst, nb * sizeof(CoderState), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   std::vector<double> tmse(nb, 0.0);
@@ -1299,7 +1297,7 @@ int psnr_q_search(hipStream_t st, const ShapePlan& P, EncBatchBufs& bb, uint32_t
     HIP_CHECK(hipMemcpyAsync(e.cst, hc.data(), nb * sizeof(CoderState), hipMemcpyHostToDevice, st));
     if (launch_mse(st, bb.vals, bb.valsStride, nb, P.N, bb.strideMean, bb.strideMeanStride, e.cst))
       return -1;
-    std::vector<CoderState> got(nb);
+    got.assign(nb, CoderState{});
     HIP_CHECK(hipMemcpyAsync(got.data(), e.cst, nb * sizeof(CoderState), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     any = false;
@@ -1327,7 +1325,7 @@ int psnr_q_search(hipStream_t st, const ShapePlan& P, EncBatchBufs& bb, uint32_t
     c.need_retry = std::llrint(m) > (long long)0xffffffffll ? 1u : 0u;
   }
   HIP_CHECK(hipMemcpyAsync(e.cst, hc.data(), nb * sizeof(CoderState), hipMemcpyHostToDevice, st));
-  HIP_CHECK(hipStreamSynchronize(st));   // hc goes out of scope
+  HIP_CHECK(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -1386,9 +1384,7 @@ struct PweKeep {
 };
 // (the memory belongs to the engine, Engine::pweBufs, and is reused by later calls: a hipFree per
 //  batch waits for every stream of the device, which stalls the other workers of the chunk farm)
-struct PweKeepList {
-  std::vector<PweKeep> v;
-};
+using PweKeepList = std::vector<PweKeep>;
 
 // list storage of the 1D coder: level l holds at most 2^l runs, and never more than `most`
 void speck1d_level_offsets(OutlierBufs& ob, uint32_t N, uint64_t most)
@@ -1434,9 +1430,8 @@ int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs&
   // load (LiftFuse mode 2), the finest level by k_lift_xyz_inv writing doubles into the chunk buffer as if it were a
   // volume of bricks (a chunk's offset rides in org[0]; no mean added) -- instead of an inverse quantiser pass and
   // fifteen per-axis passes over the whole chunk (14.9 of the 56 ms a 1024^3 volume took to compress in this mode).
-  static const bool fusedEnv = !(tune_getenv("SPERR_HIP_PWE_FUSED_INV") && atoi(tune_getenv("SPERR_HIP_PWE_FUSED_INV")) == 0);
   bricks.assign(nb, ChunkGeom{});   // (lives until the stage's next wait for the stream)
-  const bool fused = fusedEnv && !anyWide && fuse_xyz(P) && plan_fusable(P) && P.fwd.size() >= 3 &&
+  const bool fused = !anyWide && fuse_xyz(P) && plan_fusable(P) && P.fwd.size() >= 3 &&
                      (uint64_t)nb * bb.valsStride <= 0xffffffffull;
   if (fused) {
     uint32_t cbox[3] = {1, 1, 1};
@@ -1650,14 +1645,14 @@ int pwe_stage_finish(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs
   PweKeep K;
   K.nb = nb;
   const size_t headBytes = round_up((size_t)nb * 8, 256) + round_up((size_t)nb * 4, 256);
-  if (keep.v.size() >= E.pweBufs.size())
+  if (keep.size() >= E.pweBufs.size())
     E.pweBufs.push_back(std::make_unique<DevBuf>());
-  DevBuf& kb = *E.pweBufs[keep.v.size()];
+  DevBuf& kb = *E.pweBufs[keep.size()];
   if (kb.ensure(headBytes + off2[nb] + 256))
     return -1;
   K.mem = kb.p;
-  keep.v.push_back(K);
-  PweKeep& kk = keep.v.back();
+  keep.push_back(K);
+  PweKeep& kk = keep.back();
   kk.slotOff = reinterpret_cast<uint64_t*>(kk.mem);
   kk.gids = reinterpret_cast<uint32_t*>(static_cast<char*>(kk.mem) + round_up((size_t)nb * 8, 256));
   kk.slots = reinterpret_cast<uint8_t*>(static_cast<char*>(kk.mem) + headBytes);
@@ -1669,18 +1664,6 @@ int pwe_stage_finish(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs
   E.pweLastStream = st;
   hm.mark("stream out", st);
   return 0;
-}
-
-template <typename T>
-int pwe_outlier_stage(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb,
-                      const T* d_src, VolDesc vd, const uint32_t cd[3], double tol,
-                      uint64_t* d_lens2, PweKeepList& keep, bool anyWide)
-{
-  PweStage S;
-  return pwe_stage_begin<T>(st, E, P, bb, nb, d_src, vd, cd, tol, anyWide, S) ||
-                 pwe_stage_finish<T>(st, E, P, bb, nb, d_src, vd, cd, tol, d_lens2, keep, S)
-             ? -1
-             : 0;
 }
 
 // SPERR_HIP_SLICE_MIXED=0: slices are coded by k_speck2d's quadtree walk (one workgroup) instead of
@@ -1743,56 +1726,103 @@ __global__ void k_slice_header(uint8_t* dst, const uint64_t* lens, const uint64_
   *total = pos + lens[0] + lens2[0];
 }
 
-// Work queued by a call that fails must not outlive the call: the caller's buffers and the engine's
-// arena are reused as soon as it returns.  Every exit that is not marked ok waits for the caller's
-// stream and the engine's sub-streams first.
-struct DrainOnError {
-  Engine& E;
-  hipStream_t st;
-  bool ok = false;
-  ~DrainOnError()
-  {
-    if (ok)
-      return;
-    (void)hipStreamSynchronize(st);
-    for (uint32_t q = 0; q < kSubStreams; q++)
-      if (E.sub[q])
-        (void)hipStreamSynchronize(E.sub[q]);
-    for (uint32_t q = 0; q < kSubStreams; q++) {
-      if (E.outlQ[q])
-        (void)hipStreamSynchronize(E.outlQ[q]);
-      if (E.sideQ[q])
-        (void)hipStreamSynchronize(E.sideQ[q]);
-    }
-    (void)hipGetLastError();
-  }
-};
+// Work queued by a call that fails must not outlive the call: the caller's buffers and the engine's arena are
+// reused as soon as it returns.  A call (EncodeCall, DecodeCall) that did not end well waits for the caller's stream
+// and the engine's in its destructor, before its members -- the host buffers queued copies read and write -- go.
+void drain_after_error(Engine& E, hipStream_t st)
+{
+  (void)hipStreamSynchronize(st);
+  for (uint32_t q = 0; q < kSubStreams; q++)
+    for (hipStream_t s : {E.sub[q], E.outlQ[q], E.sideQ[q]})
+      if (s)
+        (void)hipStreamSynchronize(s);
+  (void)hipGetLastError();
+  E.pweLastStream = nullptr;
+}
 
+// One compression call (compress_impl), stage by stage.  slice: 0 = a 3D container; 1 / 2 = one 2D slice
+// without / with the 10-byte header.  mode 1: fixed rate, `quality` bits per value; mode 2: fixed PSNR and
+// mode 3: fixed point-wise error, every bit plane is coded
 template <typename T>
-int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkPref, int mode, double quality,
-                  uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st, int slice = 0)
-{   // slice: 0 = a 3D container; 1 / 2 = one 2D slice without / with the 10-byte header
-  // mode 1: fixed rate, `quality` bits per value; mode 2: fixed PSNR and mode 3: fixed point-wise
-  // error, every bit plane is coded
+struct EncodeCall {
+  using GKey = std::array<size_t, 4>;   // chunk extents + part
+  // a batch of one shape group's chunks; kept until the call's end: its host arrays are what queued copies
+  // read and write, and a group side by side has its plane loop and 64-bit retry enqueued after every group
+  struct Batch {
+    ShapePlan* P;
+    EncBatchBufs bb;
+    uint32_t nb, wblocks = 0;
+    uint64_t raw_budget;
+    hipStream_t ss;
+    std::vector<CoderState> hc;
+    std::vector<ChunkGeom> hg;
+    std::vector<uint32_t> hid;
+    bool orgAligned = true, quadWalk = false;   // (quadWalk: a slice whose plan is no 2D forest, SPERR_HIP_SLICE_MIXED=0)
+    EncPlanHost ph;
+    Speck2dBufs sb;
+  };
+  Engine& E;
+  const T* d_src;
+  const Dims vol;
+  const int mode;
+  const double quality;
+  uint8_t* d_dst;
+  size_t dst_cap;
+  hipStream_t st;
+  const int slice;
   const bool rate = mode == 1;
   const double bpp = rate ? quality : 0.0;
-  DrainOnError drainGuard{E, st};
+  const VolDesc vd{{vol[0], vol[1], vol[2]}};
   Dims cdim;
-  for (int a = 0; a < 3; a++)  // SPERR3D_OMP_C.cpp:23-30
-    cdim[a] = std::min(std::max<size_t>(1, chunkPref[a]), vol[a]);
-  const auto chunks = chunk_volume(vol, cdim);
-  const uint32_t nchunks = (uint32_t)chunks.size();
-  for (int a = 0; a < 3; a++)
-    if (vol[a] > 0xffffffffull || cdim[a] > 0xffff)
-      return -1;
-
-  // group chunks by shape, keeping chunk order inside a group.  (key: extents + part.)  In fixed-rate
-  // mode a group of 64 and more chunks is cut into parts (four: round 5, 16 chunks each of the bench volume -- three
-  // before; five and more fall under the sixteen chunks the capped grids want) that run side by side like the shape
-  // groups of a ragged volume do: the per-plane chains of small launches of one part overlap the
-  // bandwidth-bound kernels of the other (SPERR_HIP_ENC_PARTS=1: one part)
-  using GKey = std::array<size_t, 4>;
+  uint32_t nchunks = 0;
   std::map<GKey, std::vector<ChunkRef>> groups;
+  std::vector<ShapePlan*> groupPlan;
+  std::vector<uint64_t> slotOff;       // slots for the finished chunk streams
+  uint64_t *d_slotOff = nullptr, *d_lens = nullptr, *d_offs = nullptr, *d_lens2 = nullptr, *d_total = nullptr;
+  bool sideBySide = false;
+  std::vector<size_t> groupOff;        // (side by side: each group's piece of the arena)
+  std::deque<Batch> batches;
+  std::vector<Batch*> late;            // (side by side: each group's batch)
+  PweKeepList pweKeep;
+  std::deque<std::vector<CoderState>> hcKeep;   // chunk states of PSNR / PWE setups (one host thread: no lock)
+  std::deque<PweStage> pweStages;
+  uint64_t total = 0;
+  bool ok = false;
+  ~EncodeCall() { if (!ok) drain_after_error(E, st); }
+  // (a slice is coded on the 2D coder's forest, the plan with z extent 0; SPERR_HIP_SLICE_MIXED=0: k_speck2d's walk)
+  ShapePlan* plan_of(const GKey& d) { return E.plan(d[0], d[1], slice && slice_forest_enabled() ? 0 : d[2]); }
+  int run(const Dims& chunkPref)
+  {
+    for (int a = 0; a < 3; a++)  // SPERR3D_OMP_C.cpp:23-30
+      cdim[a] = std::min(std::max<size_t>(1, chunkPref[a]), vol[a]);
+    const auto chunks = chunk_volume(vol, cdim);
+    nchunks = (uint32_t)chunks.size();
+    for (int a = 0; a < 3; a++)
+      if (vol[a] > 0xffffffffull || cdim[a] > 0xffff)
+        return -1;
+    group_chunks(chunks);
+    if (size_slots() || plan_side_by_side())
+      return -1;
+    late.assign(groups.size(), nullptr);
+    uint32_t gi = 0;
+    for (auto& g : groups)
+      if (encode_group(gi++, g.second))
+        return -1;
+    if (late_planes() || late_retry())
+      return -1;
+    if (sideBySide)
+      for (uint32_t q = 0; q < kSubStreams; q++) {
+        HIP_CHECK(hipEventRecord(E.evJoin[q], E.sub[q]));
+        HIP_CHECK(hipStreamWaitEvent(st, E.evJoin[q], 0));
+      }
+    return container();
+  }
+  // Group chunks by shape, keeping chunk order inside a group.  In fixed-rate mode a group of 64 and more chunks
+  // is cut into parts (four: round 5, 16 chunks each of the bench volume -- three before; five and more fall under
+  // the sixteen chunks the capped grids want) that run side by side like the shape groups of a ragged volume do:
+  // the per-plane chains of small launches of one part overlap the bandwidth-bound kernels of the other
+  // (SPERR_HIP_ENC_PARTS=1: one part)
+  void group_chunks(const std::vector<std::array<size_t, 6>>& chunks)
   {
     std::map<Dims, uint32_t> count, seen;
     for (uint32_t i = 0; i < nchunks; i++)
@@ -1808,19 +1838,16 @@ int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkP
           {i, {(uint32_t)c[0], (uint32_t)c[2], (uint32_t)c[4]}});
     }
   }
-
-  // (a slice is coded on the 2D coder's forest, the plan with z extent 0; SPERR_HIP_SLICE_MIXED=0: by
-  //  k_speck2d's quadtree walk)
-  auto planZ = [&](const GKey& d) -> size_t { return slice && slice_forest_enabled() ? 0 : d[2]; };
-
-  // slots for the finished chunk streams
-  std::vector<uint64_t> slotOff(nchunks + 1, 0);
+  // a slot per chunk for its finished stream, and the call's offsets and lengths
+  int size_slots()
   {
+    slotOff.assign(nchunks + 1, 0);
     std::vector<uint64_t> slotLen(nchunks, 0);
     for (auto& g : groups) {
-      ShapePlan* P = E.plan(g.first[0], g.first[1], planZ(g.first));
+      ShapePlan* P = plan_of(g.first);
       if (!P)
         return -1;
+      groupPlan.push_back(P);
       const uint64_t raw = (uint64_t)(bpp * (double)P->N);
       const uint64_t len = 26 + (max_payload_bits(*P, raw) + 7) / 8;
       for (auto& r : g.second)
@@ -1828,49 +1855,32 @@ int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkP
     }
     for (uint32_t i = 0; i < nchunks; i++)
       slotOff[i + 1] = slotOff[i] + slotLen[i];
+    if (E.slots.ensure(slotOff[nchunks] + 256))
+      return -1;
+    if (E.misc.ensure(round_up((size_t)nchunks * 8, 256) * 4 + 256))
+      return -1;
+    d_slotOff = reinterpret_cast<uint64_t*>(E.misc.p);
+    d_lens = d_slotOff + round_up(nchunks, 32);
+    d_offs = d_lens + round_up(nchunks, 32);
+    d_lens2 = d_offs + round_up(nchunks, 32);   // outlier streams (PWE mode)
+    d_total = d_lens2 + round_up(nchunks, 32);
+    HIP_CHECK(hipMemsetAsync(d_lens2, 0, (size_t)nchunks * 8, st));
+    HIP_CHECK(hipMemcpyAsync(d_slotOff, slotOff.data(), nchunks * 8, hipMemcpyHostToDevice, st));
+    return 0;
   }
-  if (E.slots.ensure(slotOff[nchunks] + 256))
-    return -1;
-  const size_t miscBytes = round_up((size_t)nchunks * 8, 256) * 4 + 256;
-  if (E.misc.ensure(miscBytes))
-    return -1;
-  uint64_t* d_slotOff = reinterpret_cast<uint64_t*>(E.misc.p);
-  uint64_t* d_lens = d_slotOff + round_up(nchunks, 32);
-  uint64_t* d_offs = d_lens + round_up(nchunks, 32);
-  uint64_t* d_lens2 = d_offs + round_up(nchunks, 32);   // outlier streams (PWE mode)
-  uint64_t* d_total = d_lens2 + round_up(nchunks, 32);
-  HIP_CHECK(hipMemsetAsync(d_lens2, 0, (size_t)nchunks * 8, st));
-  PweKeepList pweKeep;
-  std::deque<std::vector<CoderState>> pweHcKeep;   // (mode 3 is enqueued by one host thread: no lock)
-  HIP_CHECK(hipMemcpyAsync(d_slotOff, slotOff.data(), nchunks * 8, hipMemcpyHostToDevice, st));
-
-  VolDesc vd{{vol[0], vol[1], vol[2]}};
-  // Shape groups side by side (fixed-rate mode, a volume the chunk size does not divide): every
-  // group gets a piece of the arena and a sub-stream of its own, the check for the rare 64-bit
-  // retry (one read-back per group) waits until all groups are enqueued.  SPERR_HIP_ENC_GROUPS=0:
-  // group after group.
-  struct LateGroup {
-    ShapePlan* P;
-    EncBatchBufs bb;
-    uint32_t nb, wblocks;
-    uint64_t raw_budget;
-    hipStream_t ss;
-    std::vector<CoderState> hc;
-    std::vector<ChunkGeom> hg;
-    std::vector<uint32_t> hid;
-    bool orgAligned;
-    EncPlanHost ph;   // the plane loop of the group is enqueued after every group's first half (launch_speck_encode_planes)
-  };
-  std::vector<std::unique_ptr<LateGroup>> late;
-  static const bool encGroupsEnv = !(tune_getenv("SPERR_HIP_ENC_GROUPS") && atoi(tune_getenv("SPERR_HIP_ENC_GROUPS")) == 0);
-  bool sideBySide = encGroupsEnv && mode == 1 && !slice && groups.size() > 1;
-  std::vector<size_t> groupOff;
-  if (sideBySide) {
+  // Shape groups side by side (fixed-rate mode, a volume the chunk size does not divide): every group gets a
+  // piece of the arena and a sub-stream of its own, the check for the rare 64-bit retry (one read-back per group)
+  // waits until all groups are enqueued
+  int plan_side_by_side()
+  {
+    sideBySide = mode == 1 && !slice && groups.size() > 1;
+    if (!sideBySide)
+      return 0;
     size_t fr = 0, tot = 0, need = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const size_t budgetBytes = arena_budget(E.arena.n, fr);
     for (auto& g : groups) {
-      ShapePlan* P = E.plan(g.first[0], g.first[1], planZ(g.first));
+      ShapePlan* P = plan_of(g.first);
       groupOff.push_back(need);
       need += round_up(enc_bytes_for(*P, (uint32_t)g.second.size(), (uint64_t)(bpp * (double)P->N)) + 4096, 4096);
       sideBySide = sideBySide && g.second.size() <= 256;
@@ -1883,331 +1893,301 @@ int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkP
       for (uint32_t q = 0; q < kSubStreams; q++)
         HIP_CHECK(hipStreamWaitEvent(E.sub[q], E.evFork, 0));
     }
+    return 0;
   }
-  late.resize(groups.size());
-  std::vector<ShapePlan*> groupPlan;   // (looked up here: the plan cache is not for several threads)
-  for (auto& g : groups)
-    groupPlan.push_back(E.plan(g.first[0], g.first[1], planZ(g.first)));
-  auto do_group = [&](uint32_t gi, std::pair<const GKey, std::vector<ChunkRef>>& g) -> int {
+  int encode_group(uint32_t gi, const std::vector<ChunkRef>& refs)
+  {
     hipStream_t ss = sideBySide ? E.sub[gi % kSubStreams] : st;
     ShapePlan* P = groupPlan[gi];
     const uint64_t raw_budget = (uint64_t)(bpp * (double)P->N);  // SPECK_FLT.cpp:491
     // (point-wise error mode: the coder's arrays get memory of their own -- 127 MB more per 256^3 chunk --, so that the
     //  outlier stage's reconstruction can be written into the chunk buffer while the coder runs, see below)
-    static const bool pweOverlapEnv0 = !(tune_getenv("SPERR_HIP_PWE_OVERLAP") && atoi(tune_getenv("SPERR_HIP_PWE_OVERLAP")) == 0);
-    const bool encAlias = !(mode == 3 && pweOverlapEnv0 && !sideBySide);
+    const bool encAlias = mode != 3;
     const size_t per = enc_bytes_per_chunk(*P, raw_budget, encAlias);
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const size_t budgetBytes = arena_budget(E.arena.n, fr);
-    uint32_t B = (uint32_t)std::min<size_t>(g.second.size(), std::max<size_t>(1, budgetBytes / per));
+    uint32_t B = (uint32_t)std::min<size_t>(refs.size(), std::max<size_t>(1, budgetBytes / per));
     B = std::min<uint32_t>(B, 256);
     if (sideBySide)
-      B = (uint32_t)g.second.size();
+      B = (uint32_t)refs.size();
     else if (E.arena.ensure(std::max((size_t)B * per, enc_bytes_for(*P, B, raw_budget, encAlias)) + 4096))
       return -1;
-    const uint32_t cd[3] = {P->dims[0], P->dims[1], P->dims[2]};
-    for (size_t b0 = 0; b0 < g.second.size(); b0 += B) {
-      const uint32_t nb = (uint32_t)std::min<size_t>(B, g.second.size() - b0);
-      Arena A;
-      A.base = static_cast<char*>(E.arena.p) + (sideBySide ? groupOff[gi] : 0);
-      A.cap = E.arena.n - (sideBySide ? groupOff[gi] : 0);
-      EncBatchBufs bb;
-      if (!carve_enc(A, *P, nb, raw_budget, bb, encAlias))
-        return -1;
-      if (bb.aliased)
-        g_dbg_counter[1]++;
-      EncBuffers& e = bb.eb;
-      std::vector<ChunkGeom> hg(nb);
-      std::vector<uint32_t> hid(nb);
-      for (uint32_t i = 0; i < nb; i++) {
-        const ChunkRef& r = g.second[b0 + i];
-        hid[i] = r.gid;
-        for (int a = 0; a < 3; a++)
-          hg[i].org[a] = r.org[a];
-      }
-      HIP_CHECK(hipMemcpyAsync(bb.geom, hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
-      HIP_CHECK(hipMemcpyAsync(bb.gids, hid.data(), nb * 4, hipMemcpyHostToDevice, ss));
-      HIP_CHECK(hipMemsetAsync(e.cst, 0, nb * sizeof(CoderState), ss));
-
-      // ---- float stages ----
-      // the first lifting pass covers the whole chunk: it reads the volume itself (gather, widen,
-      // subtract the mean); chunks too small to be transformed take the plain gather kernel
-      const bool fuse = !P->fwd.empty();
-      const int io = std::is_same<T, float>::value ? 1 : 2;
-      bool orgAligned = true;   // (lets the conditioner stream rows with 16-byte loads)
-      for (uint32_t i = 0; i < nb; i++)
-        orgAligned = orgAligned && hg[i].org[0] % (16 / sizeof(T)) == 0;
-      const bool fuseMax = plan_fusable(*P);
-      if (float_stages<T>(ss, *P, bb, nb, cd, d_src, vd, orgAligned, mode == 2))
-        return -1;
-      if (launch_maxabs_q(ss, bb.vals, bb.valsStride, nb, P->N, e.cst, fuseMax))
-        return -1;
-      if (mode == 2 && psnr_q_search(ss, *P, bb, nb, quality))
-        return -1;
-      bool pweWide = false;
-      if (mode == 3) {
-        pweHcKeep.emplace_back();   // (the upload of the chunks' states is not waited for: alive until the call's end)
-        if (pwe_q_setup(ss, bb, nb, quality, pweHcKeep.back(), &pweWide))
-          return -1;
-      }
-      if (launch_quantize(ss, false, bb.vals, bb.valsStride, nb, P->N, bb.coef32, e.coefStride,
-                          const_cast<uint64_t*>(e.sign), e.signStride, bb.msb, e.pixStride, e.cst))
-        return -1;
-      // (only now: the coder's arrays may lie over the chunk buffer the quantiser has just read)
-      if (reset_enc_pass(ss, bb, nb))
-        return -1;
-      // Point-wise error mode: what the decoder will reconstruct, and which samples miss the tolerance, follows from
-      // the quantiser's coefficients alone -- the first half of the outlier stage (reconstruction, first outlier
-      // pass) runs on a stream of its own BESIDE the 3D coder (round 5; behind it, one stream, before: the 1D coder
-      // alone is 3.2 of the 11.8 ms a batch of eight chunks took).  Not when the coder's arrays lie over the chunk
-      // buffer the reconstruction is written to, and given up when a chunk turns out to need 64-bit coefficients.
-      static const bool pweOverlapEnv = !(tune_getenv("SPERR_HIP_PWE_OVERLAP") && atoi(tune_getenv("SPERR_HIP_PWE_OVERLAP")) == 0);
-      PweStage pweSt;
-      hipStream_t pweQ = E.outlQ[1];
-      const bool pweEarly = mode == 3 && pweOverlapEnv && !bb.aliased && !sideBySide && !pweWide && pweQ != nullptr &&
-                            E.evPweFork != nullptr && E.evPweJoin != nullptr;
-      if (pweEarly) {
-        HIP_CHECK(hipEventRecord(E.evPweFork, ss));
-        HIP_CHECK(hipStreamWaitEvent(pweQ, E.evPweFork, 0));
-        if (pwe_stage_begin<T>(pweQ, E, *P, bb, nb, d_src, vd, cd, quality, false, pweSt))
-          return -1;
-      }
-
-      // ---- integer coder, 32-bit coefficients ----
-      const bool quadWalkGroup = slice && !(P->ht.flags & spk::kTree2D);   // (SPERR_HIP_SLICE_MIXED=0)
-      EncPlanHost ph{P->d_initLIS, P->d_initLen, P->d_depthBlocks, P->depthBlockOff, P->ht.nsets};
-      // (the census of the pixel passes on a stream of its own beside the pyramid's upper levels: the
-      //  decoder's outlier streams and events are idle during a compression call)
-      static const bool sideEnv = !(tune_getenv("SPERR_HIP_ENC_SIDE") && atoi(tune_getenv("SPERR_HIP_ENC_SIDE")) == 0);
-      if (sideEnv) {
-        ph.side = E.sideQ[gi % kSubStreams];
-        ph.evFork = E.evOutlFork[gi % kSubStreams];
-        ph.evJoin = E.evOutl[gi % kSubStreams];
-      }
-      // the planes that can hold work are asked of the device before the plane loop is enqueued (speck_enc.h;
-      // the decoder's pinned words and events are idle during a compression call).  SPERR_HIP_ENC_BOUND=0: all planes
-      static const bool boundEnv = !(tune_getenv("SPERR_HIP_ENC_BOUND") && atoi(tune_getenv("SPERR_HIP_ENC_BOUND")) == 0);
-      if (boundEnv && !quadWalkGroup) {
-        ph.d_bound = A.take<uint32_t>(64);
-        // (a pinned word pair and an event per GROUP: groups gi and gi + kSubStreams share a stream, and every head
-        //  is enqueued before any plane loop reads its bounds back -- a ragged volume has up to 4 parts + 7 border
-        //  shapes = 11 groups.  Past kSubStreams * kLiveSlots / 2 groups: all planes are launched)
-        const uint32_t lane = gi % kSubStreams, turn = gi / kSubStreams;
-        if (turn < (uint32_t)kLiveSlots / 2) {
-          ph.h_bound = E.liveHost[lane] + 2 * turn;
-          ph.evBound = E.liveEv[lane][turn];
-        }
-        if (!ph.d_bound)
-          ph.h_bound = nullptr;
-      }
-      Speck2dBufs sb;
-      const bool quadWalk = quadWalkGroup;
-      if (quadWalk) {
-        if (carve_slice2d(E, *P, sb))
-          return -1;
-        sb.coef = bb.coef32;
-        sb.sign = const_cast<uint64_t*>(e.sign);
-        sb.msb = bb.msb;
-        sb.stream = e.stream;
-        sb.streamWords = e.streamStride;
-        sb.cst = e.cst;
-        if (launch_speck2d_encode(ss, sb, raw_budget, rate, false))
-          return -1;
-      }
-      else if (sideBySide && ph.h_bound
-                   ? launch_speck_encode_head(ss, e, ph, raw_budget, rate, false)   // (its planes: once every group's first half is enqueued)
-                   : launch_speck_encode(ss, e, ph, raw_budget, rate, false))
-        return -1;
-      const uint32_t wblocks = (uint32_t)std::min<size_t>(4096, (e.streamStride * 8 + kThreads - 1) / kThreads);
-      if (!(sideBySide && ph.h_bound))
-        LAUNCH_K(k_write_slot, dim3(std::max(1u, wblocks), nb), dim3(kThreads), 0, ss, e.cst, e.st,
-                 e.stream, e.streamStride, bb.gids, static_cast<uint8_t*>(E.slots.p), d_slotOff,
-                 d_lens, P->N, 0);
-
-      // (point-wise error mode: the outlier stage's second half -- its waits are for its own stream -- while the plane
-      //  loop above runs)
-      if (pweEarly) {
-        if (pwe_stage_finish<T>(pweQ, E, *P, bb, nb, d_src, vd, cd, quality, d_lens2, pweKeep, pweSt))
-          return -1;
-        // (the stage no longer ends in a wait of the host: what follows on the batch's stream -- the container's
-        //  kernels read the outlier streams and their lengths -- waits for it on the device)
-        HIP_CHECK(hipEventRecord(E.evPweJoin, pweQ));
-        HIP_CHECK(hipStreamWaitEvent(ss, E.evPweJoin, 0));
-      }
-      // ---- fixed-rate retry with 64-bit coefficients (SPECK_FLT.cpp:530-538) ----
-      if (sideBySide) {   // (the read-back is looked at once every group is enqueued)
-        std::unique_ptr<LateGroup> L(new LateGroup{P, bb, nb, wblocks, raw_budget, ss, std::vector<CoderState>(nb),
-                                                   std::move(hg), std::move(hid), orgAligned, ph});
-        late[gi] = std::move(L);        // (a read-back into pageable memory would block the host until
-        continue;                       //  this group's stream has drained: it is done further down)
-      }
-      std::vector<CoderState> hc(nb);
-      HIP_CHECK(hipMemcpyAsync(hc.data(), e.cst, nb * sizeof(CoderState), hipMemcpyDeviceToHost, ss));
-      HIP_CHECK(hipStreamSynchronize(ss));
-      bool retry = false;
-      for (auto& c : hc)
-        retry |= (c.need_retry != 0);
-      if (retry) {
-        // the DWT coefficients again when the coder's arrays were written over them, and memory of
-        // their own for those arrays (the 64-bit magnitudes live in the chunk buffer)
-        if (bb.aliased && wide_retry_prepare<T>(ss, E, *P, bb, nb, cd, d_src, vd, orgAligned, mode == 2))
-          return -1;
-        if (pweEarly) {   // (cannot be: this mode knows the width before it codes, pwe_q_setup)
-          fprintf(stderr, "[sperr_hip] a chunk asked for 64-bit coefficients after its outlier stage had run\n");
-          return -1;
-        }
-        // fixed rate: a finer q for the flagged chunks; PSNR: the same q, coefficients need 64 bits
-        if ((rate ? launch_make_q_wide(ss, nb, e.cst) : launch_mark_wide(ss, nb, e.cst)) ||
-            reset_enc_pass(ss, bb, nb))
-          return -1;
-        // 64-bit magnitudes overwrite the DWT coefficients in place (same element size)
-        if (launch_quantize(ss, true, bb.vals, bb.valsStride, nb, P->N, bb.vals, bb.valsStride,
-                            const_cast<uint64_t*>(e.sign), e.signStride, bb.msb, e.pixStride, e.cst))
-          return -1;
-        EncBuffers ew = e;
-        ew.coef = bb.vals;
-        ew.coefStride = bb.valsStride;
-        if (quadWalk) {
-          sb.coef = bb.vals;
-          if (launch_speck2d_encode(ss, sb, raw_budget, rate, true))
-            return -1;
-        }
-        else if (launch_speck_encode(ss, ew, ph, raw_budget, rate, true))
-          return -1;
-        LAUNCH_K(k_write_slot, dim3(std::max(1u, wblocks), nb), dim3(kThreads), 0, ss, e.cst, e.st,
-                 e.stream, e.streamStride, bb.gids, static_cast<uint8_t*>(E.slots.p), d_slotOff,
-                 d_lens, P->N, 1);
-      }
-      if (mode == 3 && pweEarly) {
-        // (done above, beside the coder)
-      }
-      else if (mode == 3 &&
-               pwe_outlier_stage<T>(ss, E, *P, bb, nb, d_src, vd, cd, quality, d_lens2, pweKeep,
-                                    retry))   // (a chunk that was coded again has 64-bit coefficients)
+    for (size_t b0 = 0; b0 < refs.size(); b0 += B) {
+      Batch& b = batches.emplace_back(Batch{P, {}, (uint32_t)std::min<size_t>(B, refs.size() - b0), 0, raw_budget, ss});
+      if (encode_batch(gi, refs, b0, b, encAlias))
         return -1;
     }
-  
     return 0;
-  };
+  }
+  // one batch: conditioner, transform and quantiser; the coder, in point-wise error mode beside the outlier
+  // stage; and the 64-bit retry where a chunk asks for it
+  int encode_batch(uint32_t gi, const std::vector<ChunkRef>& refs, size_t b0, Batch& b, bool encAlias)
   {
-    // SPERR_HIP_ENC_THREADS=1: side by side, every group is enqueued by a host thread of its own
-    // (measured on MI355X, 1000^3 in 256^3 chunks, eight groups of about 1100 launches: 64.6 ms
-    // with one thread, 66 ms with eight -- the groups' chains of small launches bound the call,
-    // not the enqueueing host thread; off by default)
-    static const bool encThreadsEnv = tune_getenv("SPERR_HIP_ENC_THREADS") && atoi(tune_getenv("SPERR_HIP_ENC_THREADS")) != 0;
-    const bool threaded = sideBySide && encThreadsEnv && !(t_prof && t_prof->on);
-    std::vector<int> rcs(groups.size(), 0);
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    std::vector<std::thread> workers;
-    uint32_t groupIdx = 0;
-    for (auto& g : groups) {
-      const uint32_t gi = groupIdx++;
-      if (threaded)
-        workers.emplace_back([&, gi, dev]() {
-          rcs[gi] = hipSetDevice(dev) == hipSuccess ? do_group(gi, g) : -1;
-        });
-      else
-        rcs[gi] = do_group(gi, g);
-      if (!threaded && rcs[gi])
+    const uint32_t nb = b.nb;
+    const uint32_t* cd = b.P->dims;
+    Arena A;
+    A.base = static_cast<char*>(E.arena.p) + (sideBySide ? groupOff[gi] : 0);
+    A.cap = E.arena.n - (sideBySide ? groupOff[gi] : 0);
+    if (!carve_enc(A, *b.P, nb, b.raw_budget, b.bb, encAlias))
+      return -1;
+    if (b.bb.aliased)
+      g_dbg_counter[1]++;
+    b.hg.resize(nb);
+    b.hid.resize(nb);
+    for (uint32_t i = 0; i < nb; i++) {
+      const ChunkRef& r = refs[b0 + i];
+      b.hid[i] = r.gid;
+      for (int a = 0; a < 3; a++)
+        b.hg[i].org[a] = r.org[a];
+      b.orgAligned = b.orgAligned && r.org[0] % (16 / sizeof(T)) == 0;   // (lets the conditioner stream rows with 16-byte loads)
+    }
+    bool pweWide = false;
+    if (quantise(b, &pweWide))
+      return -1;
+    // Point-wise error mode: what the decoder will reconstruct, and which samples miss the tolerance, follows from
+    // the quantiser's coefficients alone -- the first half of the outlier stage (reconstruction, first outlier
+    // pass) runs on a stream of its own BESIDE the 3D coder (round 5; behind it, one stream, before: the 1D coder
+    // alone is 3.2 of the 11.8 ms a batch of eight chunks took).  Not when the coder's arrays lie over the chunk
+    // buffer the reconstruction is written to, and given up when a chunk turns out to need 64-bit coefficients.
+    hipStream_t pweQ = E.outlQ[1];
+    const bool pweEarly = mode == 3 && !b.bb.aliased && !pweWide;
+    if (pweEarly) {
+      HIP_CHECK(hipEventRecord(E.evPweFork, b.ss));
+      HIP_CHECK(hipStreamWaitEvent(pweQ, E.evPweFork, 0));
+      if (pwe_stage_begin<T>(pweQ, E, *b.P, b.bb, nb, d_src, vd, cd, quality, false, pweStages.emplace_back()))
         return -1;
     }
-    for (auto& w : workers)
-      w.join();
-    for (int r : rcs)
-      if (r)
-        return -1;
-  }
-  for (auto& L : late) {   // the groups that ran side by side: their plane loops, each over the planes that can hold work
-    if (!L || !L->ph.h_bound)
-      continue;
-    EncBuffers& e = L->bb.eb;
-    if (launch_speck_encode_planes(L->ss, e, L->ph, L->raw_budget, rate, false))
+    if (code(gi, A, b))
       return -1;
-    LAUNCH_K(k_write_slot, dim3(std::max(1u, L->wblocks), L->nb), dim3(kThreads), 0, L->ss, e.cst, e.st,
-             e.stream, e.streamStride, L->bb.gids, static_cast<uint8_t*>(E.slots.p), d_slotOff, d_lens, L->P->N, 0);
-  }
-  for (auto& L : late) {   // the 64-bit retry, where a chunk asked for it
-    if (!L)
-      continue;
-    HIP_CHECK(hipMemcpyAsync(L->hc.data(), L->bb.eb.cst, L->nb * sizeof(CoderState), hipMemcpyDeviceToHost, L->ss));
-    HIP_CHECK(hipStreamSynchronize(L->ss));
+    // (point-wise error mode: the outlier stage's second half -- its waits are for its own stream -- while the plane
+    //  loop above runs)
+    if (pweEarly) {
+      if (pwe_stage_finish<T>(pweQ, E, *b.P, b.bb, nb, d_src, vd, cd, quality, d_lens2, pweKeep, pweStages.back()))
+        return -1;
+      // (the stage no longer ends in a wait of the host: what follows on the batch's stream -- the container's
+      //  kernels read the outlier streams and their lengths -- waits for it on the device)
+      HIP_CHECK(hipEventRecord(E.evPweJoin, pweQ));
+      HIP_CHECK(hipStreamWaitEvent(b.ss, E.evPweJoin, 0));
+    }
+    if (sideBySide) {   // (a read-back into pageable memory would block the host until this group's stream has
+      late[gi] = &b;    //  drained: the retry is looked at once every group is enqueued, late_retry)
+      return 0;
+    }
+    b.hc.resize(nb);
+    HIP_CHECK(hipMemcpyAsync(b.hc.data(), b.bb.eb.cst, nb * sizeof(CoderState), hipMemcpyDeviceToHost, b.ss));
+    HIP_CHECK(hipStreamSynchronize(b.ss));
     bool retry = false;
-    for (auto& cs : L->hc)
-      retry |= (cs.need_retry != 0);
-    if (!retry)
-      continue;
-    EncBatchBufs& bb = L->bb;
-    EncBuffers& e = bb.eb;
-    ShapePlan* P = L->P;
-    EncPlanHost ph{P->d_initLIS, P->d_initLen, P->d_depthBlocks, P->depthBlockOff, P->ht.nsets};
-    // (wide_retry_prepare clears bb.aliased: remember it, the guard after the launches needs it)
-    const bool wasAliased = bb.aliased;
-    if (wasAliased) {   // (see the retry above; the scratch memory is the engine's: one group at a time --
-                        // the previous retrying group synchronised its stream below before this one starts)
-      const uint32_t cdl[3] = {P->dims[0], P->dims[1], P->dims[2]};
-      if (wide_retry_prepare<T>(L->ss, E, *P, bb, L->nb, cdl, d_src, vd, L->orgAligned, false))
+    for (auto& c : b.hc)
+      retry |= (c.need_retry != 0);
+    if (retry) {
+      if (pweEarly) {   // (cannot be: this mode knows the width before it codes, pwe_q_setup)
+        fprintf(stderr, "[sperr_hip] a chunk asked for 64-bit coefficients after its outlier stage had run\n");
+        return -1;
+      }
+      if (retry_wide(b, b.ph))
         return -1;
     }
-    if (launch_make_q_wide(L->ss, L->nb, e.cst) || reset_enc_pass(L->ss, bb, L->nb))
+    if (mode == 3 && !pweEarly) {   // (a chunk that was coded again has 64-bit coefficients)
+      PweStage& S = pweStages.emplace_back();
+      if (pwe_stage_begin<T>(b.ss, E, *b.P, b.bb, nb, d_src, vd, cd, quality, retry, S) ||
+          pwe_stage_finish<T>(b.ss, E, *b.P, b.bb, nb, d_src, vd, cd, quality, d_lens2, pweKeep, S))
+        return -1;
+    }
+    return 0;
+  }
+  // ---- float stages: the first lifting pass covers the whole chunk: it reads the volume itself (gather, widen,
+  // subtract the mean); chunks too small to be transformed take the plain gather kernel.  Then the quantiser ----
+  int quantise(Batch& b, bool* pweWide)
+  {
+    EncBatchBufs& bb = b.bb;
+    EncBuffers& e = bb.eb;
+    const uint32_t nb = b.nb;
+    HIP_CHECK(hipMemcpyAsync(bb.geom, b.hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, b.ss));
+    HIP_CHECK(hipMemcpyAsync(bb.gids, b.hid.data(), nb * 4, hipMemcpyHostToDevice, b.ss));
+    HIP_CHECK(hipMemsetAsync(e.cst, 0, nb * sizeof(CoderState), b.ss));
+    if (float_stages<T>(b.ss, *b.P, bb, nb, b.P->dims, d_src, vd, b.orgAligned, mode == 2))
       return -1;
-    if (launch_quantize(L->ss, true, bb.vals, bb.valsStride, L->nb, P->N, bb.vals, bb.valsStride,
+    if (launch_maxabs_q(b.ss, bb.vals, bb.valsStride, nb, b.P->N, e.cst, plan_fusable(*b.P)))
+      return -1;
+    if (mode == 2 && psnr_q_search(b.ss, *b.P, bb, nb, quality, hcKeep.emplace_back(), hcKeep.emplace_back()))
+      return -1;
+    if (mode == 3 && pwe_q_setup(b.ss, bb, nb, quality, hcKeep.emplace_back(), pweWide))
+      return -1;
+    if (launch_quantize(b.ss, false, bb.vals, bb.valsStride, nb, b.P->N, bb.coef32, e.coefStride,
+                        const_cast<uint64_t*>(e.sign), e.signStride, bb.msb, e.pixStride, e.cst))
+      return -1;
+    // (only now: the coder's arrays may lie over the chunk buffer the quantiser has just read)
+    return reset_enc_pass(b.ss, bb, nb);
+  }
+  // ---- integer coder, 32-bit coefficients ----
+  int code(uint32_t gi, Arena& A, Batch& b)
+  {
+    const ShapePlan& P = *b.P;
+    EncBuffers& e = b.bb.eb;
+    b.quadWalk = slice && !(P.ht.flags & spk::kTree2D);
+    EncPlanHost& ph = b.ph = EncPlanHost{P.d_initLIS, P.d_initLen, P.d_depthBlocks, P.depthBlockOff, P.ht.nsets};
+    // (the census of the pixel passes on a stream of its own beside the pyramid's upper levels: the
+    //  decoder's outlier streams and events are idle during a compression call)
+    ph.side = E.sideQ[gi % kSubStreams];
+    ph.evFork = E.evOutlFork[gi % kSubStreams];
+    ph.evJoin = E.evOutl[gi % kSubStreams];
+    // the planes that can hold work are asked of the device before the plane loop is enqueued (speck_enc.h;
+    // the decoder's pinned words and events are idle during a compression call)
+    if (!b.quadWalk) {
+      ph.d_bound = A.take<uint32_t>(64);
+      // (a pinned word pair and an event per GROUP: groups gi and gi + kSubStreams share a stream, and every head
+      //  is enqueued before any plane loop reads its bounds back -- a ragged volume has up to 4 parts + 7 border
+      //  shapes = 11 groups.  Past kSubStreams * kLiveSlots / 2 groups: all planes are launched)
+      const uint32_t lane = gi % kSubStreams, turn = gi / kSubStreams;
+      if (turn < (uint32_t)kLiveSlots / 2) {
+        ph.h_bound = E.liveHost[lane] + 2 * turn;
+        ph.evBound = E.liveEv[lane][turn];
+      }
+      if (!ph.d_bound)
+        ph.h_bound = nullptr;
+    }
+    if (b.quadWalk) {
+      Speck2dBufs& sb = b.sb;
+      if (carve_slice2d(E, P, sb))
+        return -1;
+      sb.coef = b.bb.coef32;
+      sb.sign = const_cast<uint64_t*>(e.sign);
+      sb.msb = b.bb.msb;
+      sb.stream = e.stream;
+      sb.streamWords = e.streamStride;
+      sb.cst = e.cst;
+      if (launch_speck2d_encode(b.ss, sb, b.raw_budget, rate, false))
+        return -1;
+    }
+    else if (sideBySide && ph.h_bound
+                 ? launch_speck_encode_head(b.ss, e, ph, b.raw_budget, rate, false)   // (its planes: late_planes)
+                 : launch_speck_encode(b.ss, e, ph, b.raw_budget, rate, false))
+      return -1;
+    b.wblocks = (uint32_t)std::min<size_t>(4096, (e.streamStride * 8 + kThreads - 1) / kThreads);
+    if (!(sideBySide && ph.h_bound))
+      write_slots(b, 0);
+    return 0;
+  }
+  void write_slots(const Batch& b, int wide)
+  {
+    const EncBuffers& e = b.bb.eb;
+    LAUNCH_K(k_write_slot, dim3(std::max(1u, b.wblocks), b.nb), dim3(kThreads), 0, b.ss, e.cst, e.st, e.stream,
+             e.streamStride, b.bb.gids, static_cast<uint8_t*>(E.slots.p), d_slotOff, d_lens, b.P->N, wide);
+  }
+  // ---- retry with 64-bit coefficients (SPECK_FLT.cpp:530-538) ----
+  // fixed rate: a finer q for the flagged chunks; PSNR: the same q, coefficients need 64 bits
+  int retry_wide(Batch& b, const EncPlanHost& ph)
+  {
+    EncBatchBufs& bb = b.bb;
+    EncBuffers& e = bb.eb;
+    // the DWT coefficients again when the coder's arrays were written over them, and memory of
+    // their own for those arrays (the 64-bit magnitudes live in the chunk buffer)
+    if (bb.aliased && wide_retry_prepare<T>(b.ss, E, *b.P, bb, b.nb, b.P->dims, d_src, vd, b.orgAligned, mode == 2))
+      return -1;
+    if ((rate ? launch_make_q_wide(b.ss, b.nb, e.cst) : launch_mark_wide(b.ss, b.nb, e.cst)) ||
+        reset_enc_pass(b.ss, bb, b.nb))
+      return -1;
+    // 64-bit magnitudes overwrite the DWT coefficients in place (same element size)
+    if (launch_quantize(b.ss, true, bb.vals, bb.valsStride, b.nb, b.P->N, bb.vals, bb.valsStride,
                         const_cast<uint64_t*>(e.sign), e.signStride, bb.msb, e.pixStride, e.cst))
       return -1;
     EncBuffers ew = e;
     ew.coef = bb.vals;
     ew.coefStride = bb.valsStride;
-    if (launch_speck_encode(L->ss, ew, ph, L->raw_budget, true, true))
-      return -1;
-    LAUNCH_K(k_write_slot, dim3(std::max(1u, L->wblocks), L->nb), dim3(kThreads), 0, L->ss, e.cst, e.st,
-             e.stream, e.streamStride, bb.gids, static_cast<uint8_t*>(E.slots.p), d_slotOff, d_lens,
-             P->N, 1);
-    if (wasAliased)   // the next retrying group takes the engine's scratch memory over
-      HIP_CHECK(hipStreamSynchronize(L->ss));
-  }
-  if (sideBySide)
-    for (uint32_t q = 0; q < kSubStreams; q++) {
-      HIP_CHECK(hipEventRecord(E.evJoin[q], E.sub[q]));
-      HIP_CHECK(hipStreamWaitEvent(st, E.evJoin[q], 0));
+    if (b.quadWalk) {
+      b.sb.coef = bb.vals;
+      if (launch_speck2d_encode(b.ss, b.sb, b.raw_budget, rate, true))
+        return -1;
     }
-
-  // ---- container ----
-  // (the header kernels write before any length is known to them: check its room here)
-  if (dst_cap < (slice ? (slice == 2 ? 10u : 0u) : (nchunks > 1 ? 20u : 14u) + 4ull * nchunks)) {
-    fprintf(stderr, "[sperr_hip] output buffer too small for the container header (%zu bytes)\n", dst_cap);
-    return -1;
+    else if (launch_speck_encode(b.ss, ew, ph, b.raw_budget, rate, true))
+      return -1;
+    write_slots(b, 1);
+    return 0;
   }
-  if (slice)
-    LAUNCH_K(k_slice_header, dim3(1), dim3(1), 0, st, d_dst, d_lens, d_lens2, d_offs,
-             (uint32_t)vol[0], (uint32_t)vol[1], std::is_same<T, float>::value ? 1 : 0,
-             slice == 2 ? 1 : 0, d_total);
-  else
-    LAUNCH_K(k_container_header, dim3(1), dim3(1), 0, st, d_dst, d_lens, d_lens2, d_offs, nchunks,
-             (uint32_t)vol[0], (uint32_t)vol[1], (uint32_t)vol[2], (uint32_t)cdim[0],
-             (uint32_t)cdim[1], (uint32_t)cdim[2], std::is_same<T, float>::value ? 1 : 0, d_total);
+  // the groups that ran side by side: their plane loops, each over the planes that can hold work
+  int late_planes()
   {
+    for (Batch* L : late) {
+      if (!L || !L->ph.h_bound)
+        continue;
+      if (launch_speck_encode_planes(L->ss, L->bb.eb, L->ph, L->raw_budget, rate, false))
+        return -1;
+      write_slots(*L, 0);
+    }
+    return 0;
+  }
+  // the groups side by side: the 64-bit retry, where a chunk asked for it
+  int late_retry()
+  {
+    for (Batch* L : late) {
+      if (!L)
+        continue;
+      L->hc.resize(L->nb);
+      HIP_CHECK(hipMemcpyAsync(L->hc.data(), L->bb.eb.cst, L->nb * sizeof(CoderState), hipMemcpyDeviceToHost, L->ss));
+      HIP_CHECK(hipStreamSynchronize(L->ss));
+      bool retry = false;
+      for (auto& cs : L->hc)
+        retry |= (cs.need_retry != 0);
+      if (!retry)
+        continue;
+      const ShapePlan& P = *L->P;
+      const EncPlanHost ph{P.d_initLIS, P.d_initLen, P.d_depthBlocks, P.depthBlockOff, P.ht.nsets};
+      // (retry_wide clears bb.aliased: the scratch memory is the engine's, one group at a time -- the next
+      //  retrying group takes it over once this group's stream is through)
+      const bool wasAliased = L->bb.aliased;
+      if (retry_wide(*L, ph))
+        return -1;
+      if (wasAliased)
+        HIP_CHECK(hipStreamSynchronize(L->ss));
+    }
+    return 0;
+  }
+  // ---- container ----
+  int container()
+  {
+    // (the header kernels write before any length is known to them: check its room here)
+    if (dst_cap < (slice ? (slice == 2 ? 10u : 0u) : (nchunks > 1 ? 20u : 14u) + 4ull * nchunks)) {
+      fprintf(stderr, "[sperr_hip] output buffer too small for the container header (%zu bytes)\n", dst_cap);
+      return -1;
+    }
+    if (slice)
+      LAUNCH_K(k_slice_header, dim3(1), dim3(1), 0, st, d_dst, d_lens, d_lens2, d_offs,
+               (uint32_t)vol[0], (uint32_t)vol[1], std::is_same<T, float>::value ? 1 : 0,
+               slice == 2 ? 1 : 0, d_total);
+    else
+      LAUNCH_K(k_container_header, dim3(1), dim3(1), 0, st, d_dst, d_lens, d_lens2, d_offs, nchunks,
+               (uint32_t)vol[0], (uint32_t)vol[1], (uint32_t)vol[2], (uint32_t)cdim[0],
+               (uint32_t)cdim[1], (uint32_t)cdim[2], std::is_same<T, float>::value ? 1 : 0, d_total);
     const uint32_t gy = std::min<uint32_t>(nchunks, 32768u);
     const uint32_t gx = nchunks >= 4096 ? 4u : nchunks >= 256 ? 64u : 1024u;
     LAUNCH_K(k_copy_slots, dim3(gx, gy), dim3(kThreads), 0, st, d_dst, (uint64_t)dst_cap,
              static_cast<const uint8_t*>(E.slots.p), d_slotOff, d_lens, d_offs, nchunks);
+    for (auto& k : pweKeep)
+      LAUNCH_K(k_copy_slots2, dim3(256, k.nb), dim3(kThreads), 0, st, d_dst, (uint64_t)dst_cap, k.slots,
+               k.slotOff, k.gids, d_lens, d_lens2, d_offs);
+    HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    E.pweLastStream = nullptr;
+    E.prof.collect();
+    if (total > dst_cap) {
+      fprintf(stderr, "[sperr_hip] output buffer too small (%zu < %llu)\n", dst_cap, (unsigned long long)total);
+      return -1;
+    }
+    ok = true;
+    return 0;
   }
-  for (auto& k : pweKeep.v)
-    LAUNCH_K(k_copy_slots2, dim3(256, k.nb), dim3(kThreads), 0, st, d_dst, (uint64_t)dst_cap, k.slots,
-             k.slotOff, k.gids, d_lens, d_lens2, d_offs);
-  uint64_t total = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  HIP_CHECK(hipGetLastError());
-  E.pweLastStream = nullptr;
-  E.prof.collect();
-  if (total > dst_cap) {
-    fprintf(stderr, "[sperr_hip] output buffer too small (%zu < %llu)\n", dst_cap,
-            (unsigned long long)total);
+};
+
+template <typename T>
+int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkPref, int mode, double quality,
+                  uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st, int slice = 0)
+{
+  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, slice};
+  if (call.run(chunkPref))
     return -1;
-  }
-  *dst_len = (size_t)total;
-  drainGuard.ok = true;
+  *dst_len = (size_t)call.total;
   return 0;
 }
 
@@ -2354,11 +2334,10 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   TAKE(d.tileRefOff, uint32_t, d.tileStride * B);
   {
     // (only for the regular trees: there every birth of a sample comes through a leaf event; k_lis_mixed and
-    //  k_lis_walk set mask bits themselves.  SPERR_HIP_TILE_SKIP=0: every tile swept on every plane)
-    static const bool tileSkip = !(tune_getenv("SPERR_HIP_TILE_SKIP") && atoi(tune_getenv("SPERR_HIP_TILE_SKIP")) == 0);
+    //  k_lis_walk set mask bits themselves)
     uint8_t* tb = nullptr;
     TAKE(tb, uint8_t, d.tileStride * B);
-    d.tileBorn = (tileSkip && use_tables(P)) ? tb : nullptr;
+    d.tileBorn = use_tables(P) ? tb : nullptr;
   }
   d.lipResStride = Npad / 64 + 2;
   TAKE(d.lipSig, uint64_t, d.lipResStride * B);
@@ -2403,21 +2382,12 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   // larger sets are walked into bit by bit, which leaves the LDS to longer regions of the stream
   static const int hiKcap = tune_getenv("SPERR_HIP_HI_KCAP") ? std::max(2, atoi(tune_getenv("SPERR_HIP_HI_KCAP"))) : 5;
   d.hiK = (uint32_t)std::min(std::max(2, P.maxK), hiKcap);
-  {
-    static const uint32_t ahead = tune_getenv("SPERR_HIP_HI_AHEAD") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_HI_AHEAD")) : 512u;   // (round 5, with regions of 6912 positions: eight chunks 38.9 -> 39.7 GB/s, 64 chunks the same)
-    d.hiAhead = ahead;
-    static const uint32_t extra = tune_getenv("SPERR_HIP_HI_EXTRA") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_HI_EXTRA")) : 1u;
-    d.hiExtra = extra;
-    // (round 5: off -- without the second table a region holds 6912 positions instead of 5632, a chunk has a fifth
-    //  fewer regions on its serial chain, and the table it rebuilds now and then costs less than that:
-    //  decompression of the bench volume 91.5 -> 94.5 GB/s, eight chunks 38.2 -> 39.3)
-    static const uint32_t hop2 = tune_getenv("SPERR_HIP_HI_HOP2") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_HI_HOP2")) : 0u;
-    d.hiHop2 = hop2;
-    // (round 6: 1 -- class tables 48.0 K -> 36.1 K cycles per region, k_lis_hi 16.7 -> 14.7 ms summed per step,
-    //  decompression of 64 chunks 113.0 -> 115.0 GB/s in alternating runs, profiles/r6_hi_candidates_ab.txt)
-    static const uint32_t hiCandEnv = tune_getenv("SPERR_HIP_HI_CAND") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_HI_CAND")) : 1u;
-    d.hiCand = hiCandEnv;
-  }
+  static const uint32_t ahead = tune_getenv("SPERR_HIP_HI_AHEAD") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_HI_AHEAD")) : 512u;   // (round 5, with regions of 6912 positions: eight chunks 38.9 -> 39.7 GB/s, 64 chunks the same)
+  d.hiAhead = ahead;
+  static const uint32_t extra = tune_getenv("SPERR_HIP_HI_EXTRA") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_HI_EXTRA")) : 1u;
+  d.hiExtra = extra;
+  d.hiHop2 = 0;   // (no second table, round 5: bench volume decompression 91.5 -> 94.5 GB/s)
+  d.hiCand = 1;   // (round 6: 64 chunks decompress at 115.0 against 113.0 GB/s, profiles/r6_hi_candidates_ab.txt)
   d.hiSmemBytes = 148 * 1024;   // (k_lis_hi has 11.5 KB of static LDS)
   d.hiW = hi_window((int)d.hiK, d.hiSmemBytes, d.hiHop2);
   d.queueStride = (size_t)d.queueCap * 4 * d.hiGroupsMax;
@@ -2443,13 +2413,7 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   TAKE(d.sigbits, uint64_t, d.sigbitsStride * B);
   d.l0FlagStride = (d.streamStride * 64 + N) / 4096 + 4;   // (zero padding may be walked)
   TAKE(d.l0Flags, unsigned long long, d.l0FlagStride * B);
-  {
-    static const bool lbEnv = !(tune_getenv("SPERR_HIP_L01_LOOKBACK") && atoi(tune_getenv("SPERR_HIP_L01_LOOKBACK")) == 0);
-    d.l0Tab = nullptr;
-    if (lbEnv) {
-      TAKE(d.l0Tab, unsigned long long, d.l0FlagStride * 17 * B);
-    }
-  }
+  TAKE(d.l0Tab, unsigned long long, d.l0FlagStride * 17 * B);
   d.l0Level = P.l0Level;
   TAKE(d.l1Flags, unsigned long long, d.l0FlagStride * B);
   d.l1Level = P.l1Level;
@@ -2532,52 +2496,38 @@ struct BoxSel {
   std::vector<uint32_t> ids;
 };
 
+// bytes carve_dec takes for one chunk
+size_t dec_bytes_per_chunk(const ShapePlan& P, uint64_t maxPayload, size_t valsElems, uint32_t refNPlanes, bool crop)
+{
+  Arena probe;
+  probe.base = reinterpret_cast<char*>(uintptr_t(4096));  // size probe only
+  probe.cap = ~size_t(0) / 2;
+  DecBatchBufs tmp;
+  carve_dec(probe, P, 1, maxPayload, tmp, valsElems, refNPlanes, crop);
+  return probe.used;
+}
+
+// the list kernels a chunk shape takes
+DecPlanHost dec_plan_host(const ShapePlan& P)
+{
+  DecPlanHost ph{P.d_initLIS, P.d_initLen, use_tables(P), P.l0Level >= 0 && P.ht.grids.size() <= 288,
+                 P.l1Level >= 0 && P.ht.grids.size() <= 288, P.maxK};
+  ph.l2 = ph.l1 && P.l2Level >= 0;
+  ph.hi = use_lis_hi(P, ph.tables);   // the lists of the larger sets GPU-wide
+  ph.mixed = use_mixed(P);
+  return ph;
+}
+
+// One decompression call (decompress_impl), stage by stage.  slice: `ci` describes one chunk of dims (x, y, 1) whose
+// stream starts at d_src (2D coder).  box: only the chunks the box meets are read and decoded, and d_dst is the box
+// (not with mr or slice)
 template <typename T>
-int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, size_t dst_cap_vals,
-                    const ContainerInfo& ci, hipStream_t st, const MultiRes* mr = nullptr,
-                    bool slice = false, const BoxSel* box = nullptr)
-{   // slice: `ci` describes one chunk of dims (x, y, 1) whose stream starts at d_src (2D coder)
-    // box: only the chunks the box meets are read and decoded, and d_dst is the box (not with mr or slice)
-  DrainOnError drainGuard{E, st};
-  const auto chunks = chunk_volume(ci.vol, ci.chunk);
-  if (box && (mr || slice))
-    return -1;
-  // The chunks of this call, slot by slot: slot i is container chunk sel[i] (all of them in order, or the
-  // box's).  Heads, outlier heads and batches are per slot; offsets and lengths come from the container.
-  std::vector<uint32_t> sel;
-  if (box)
-    sel = box->ids;
-  else {
-    sel.resize(chunks.size());
-    for (uint32_t i = 0; i < (uint32_t)sel.size(); i++)
-      sel[i] = i;
-  }
-  const uint32_t nchunks = (uint32_t)sel.size();
-  const size_t outVals = box ? box->dims[0] * box->dims[1] * box->dims[2] : ci.nvals;
-  if (outVals == 0 || outVals > dst_cap_vals || nchunks == 0)
-    return -1;
-  (void)src_len;
-  std::vector<uint64_t> selOff(nchunks), selLen(nchunks);
-  for (uint32_t i = 0; i < nchunks; i++) {
-    selOff[i] = ci.off[sel[i]];
-    selLen[i] = ci.len[sel[i]];
-  }
-
-  // chunk heads (flags, number of planes) decide the integer width and the plane count
-  const size_t miscBytes = round_up((size_t)nchunks * 8, 256) * 2 + (size_t)nchunks * 32 + 256;
-  if (E.misc.ensure(miscBytes))
-    return -1;
-  uint64_t* d_off = reinterpret_cast<uint64_t*>(E.misc.p);
-  uint64_t* d_len = d_off + round_up(nchunks, 32);
-  uint8_t* d_heads = reinterpret_cast<uint8_t*>(d_len + round_up(nchunks, 32));
-  HIP_CHECK(hipMemcpyAsync(d_off, selOff.data(), nchunks * 8, hipMemcpyHostToDevice, st));
-  HIP_CHECK(hipMemcpyAsync(d_len, selLen.data(), nchunks * 8, hipMemcpyHostToDevice, st));
-  LAUNCH_K(k_gather_heads, dim3((nchunks + 63) / 64), dim3(64), 0, st, d_src, d_off, d_len,
-           d_heads, nchunks);
-  std::vector<uint8_t> heads((size_t)nchunks * 32);
-  HIP_CHECK(hipMemcpyAsync(heads.data(), d_heads, heads.size(), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-
+struct DecodeCall {
+  struct Ref {
+    uint32_t gid;    // container chunk (ci.off / ci.len)
+    uint32_t slot;   // this call's slot (heads, outHead)
+    uint32_t org[3];
+  };
   // PWE streams: a chunk's SPECK stream may be followed by an outlier stream, which counts only
   // when all of it is there (src/SPECK_FLT.cpp:88-103)
   struct OutHead {
@@ -2585,10 +2535,121 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
     uint64_t off = 0, total_bits = 0;
     int nbp = 0;
   };
-  std::vector<OutHead> outHead(nchunks);
+  // a sub-batch; kept until the call's end: its host arrays are what queued copies read and write
+  struct SubHost {
+    std::vector<ChunkGeom> hg, bricks;
+    std::vector<CropGeom> hc;
+    std::vector<uint64_t> ho, hl;
+    std::vector<DecState> hs;
+    std::vector<OutlierChunk> hoc;   // (the outlier streams' heads)
+    DecBatchBufs bb;
+    OutlierBufs ob;
+    uint32_t nb = 0;
+    size_t first = 0;
+    int maxNarrow = 0, maxWide = 0;
+    bool outliers = false;
+  };
+  // a batch of a shape group: what the group's sizing decided, and the batch's sub-batches
+  struct Batch {
+    const std::vector<Ref>* refs;
+    ShapePlan* P;
+    uint32_t cbox[3], refNPlanes, nsub = 1;
+    uint64_t maxPayload = 0;
+    size_t compactElems;
+    bool deferG, fuseDq;
+    hipStream_t deferStream = nullptr;
+    std::vector<SubHost>* subs = nullptr;
+    int devId = 0;
+  };
+  Engine& E;
+  const uint8_t* d_src;
+  T* d_dst;
+  const ContainerInfo& ci;
+  hipStream_t st;
+  const MultiRes* mr;
+  const bool slice;
+  const BoxSel* box;
+  // the output: the volume, or the box (its chunks write their windows: CropGeom, the kCrop writers)
+  const VolDesc vd = box ? VolDesc{{box->dims[0], box->dims[1], box->dims[2]}} : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
+  // The chunks of this call, slot by slot: slot i is container chunk sel[i] (all of them in order, or the
+  // box's).  Heads, outlier heads and batches are per slot; offsets and lengths come from the container.
+  std::vector<uint32_t> sel;
+  std::vector<uint64_t> selOff, selLen, tailOff, tailLen;
+  std::vector<uint8_t> heads, tails;
+  std::vector<OutHead> outHead;
   bool anyOutlier = false;
+  std::map<Dims, std::vector<Ref>> groups;
+  uint32_t mxGroupsCall = 0;
+  std::deque<std::vector<SubHost>> subHosts;   // every batch's sub-batches
+  // Small groups (the border shapes of a volume that the chunk size does not divide; their chunks
+  // decode through the serial walk, one wavefront each) are not waited for one by one: each gets
+  // its own piece of the arena and one of the sub-streams, and all of them are drained together.
+  bool deferOK = false, deferSized = false, deferForked = false;
+  std::vector<SubHost*> pending;
+  size_t deferOff = 0;
+  uint32_t deferNext = 0;
+  hipEvent_t timingFork = nullptr;
+  std::vector<std::pair<hipEvent_t, std::array<uint32_t, 4>>> timingEnds;
+  bool ok = false;
+  ~DecodeCall() { if (!ok) drain_after_error(E, st); }
+  int run(size_t dst_cap_vals)
   {
-    std::vector<uint64_t> tailOff(nchunks, 0), tailLen(nchunks, 0);
+    const auto chunks = chunk_volume(ci.vol, ci.chunk);
+    if (box && (mr || slice))
+      return -1;
+    sel = box ? box->ids : std::vector<uint32_t>(chunks.size());
+    if (!box)
+      std::iota(sel.begin(), sel.end(), 0u);
+    const uint32_t nchunks = (uint32_t)sel.size();
+    const size_t outVals = box ? box->dims[0] * box->dims[1] * box->dims[2] : ci.nvals;
+    if (outVals == 0 || outVals > dst_cap_vals || nchunks == 0)
+      return -1;
+    for (uint32_t i = 0; i < nchunks; i++) {
+      const auto& c = chunks[sel[i]];
+      selOff.push_back(ci.off[sel[i]]);
+      selLen.push_back(ci.len[sel[i]]);
+      groups[Dims{c[1], c[3], c[5]}].push_back({sel[i], i, {(uint32_t)c[0], (uint32_t)c[2], (uint32_t)c[4]}});
+    }
+    if (read_heads())
+      return -1;
+    deferOK = !anyOutlier && !mr && !slice && groups.size() > 1;
+    count_mx_groups();
+    for (int pass = 0; pass < 2; pass++)
+      for (auto& g : groups)
+        if (decode_group(g.first, g.second, pass))
+          return -1;
+    if (drain())
+      return -1;
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    E.prof.collect();
+    ok = true;
+    return 0;
+  }
+  // the chunk heads (flags, number of planes) decide the integer width and the plane count; and the heads of
+  // the outlier streams behind them
+  int read_heads()
+  {
+    const uint32_t nchunks = (uint32_t)sel.size();
+    if (E.misc.ensure(round_up((size_t)nchunks * 8, 256) * 2 + (size_t)nchunks * 32 + 256))
+      return -1;
+    uint64_t* d_off = reinterpret_cast<uint64_t*>(E.misc.p);
+    uint64_t* d_len = d_off + round_up(nchunks, 32);
+    uint8_t* d_heads = reinterpret_cast<uint8_t*>(d_len + round_up(nchunks, 32));
+    auto gather = [&](const std::vector<uint64_t>& off, const std::vector<uint64_t>& len, std::vector<uint8_t>& out) -> int {
+      HIP_CHECK(hipMemcpyAsync(d_off, off.data(), nchunks * 8, hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(d_len, len.data(), nchunks * 8, hipMemcpyHostToDevice, st));
+      LAUNCH_K(k_gather_heads, dim3((nchunks + 63) / 64), dim3(64), 0, st, d_src, d_off, d_len, d_heads, nchunks);
+      out.resize((size_t)nchunks * 32);
+      HIP_CHECK(hipMemcpyAsync(out.data(), d_heads, out.size(), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+      return 0;
+    };
+    if (gather(selOff, selLen, heads))
+      return -1;
+    outHead.resize(nchunks);
+    tailOff.assign(nchunks, 0);
+    tailLen.assign(nchunks, 0);
     bool anyTail = false;
     for (uint32_t i = 0; i < nchunks; i++) {
       const uint8_t* hd = heads.data() + (size_t)i * 32;
@@ -2603,73 +2664,641 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
         anyTail = true;
       }
     }
-    if (anyTail) {
-      HIP_CHECK(hipMemcpyAsync(d_off, tailOff.data(), nchunks * 8, hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(d_len, tailLen.data(), nchunks * 8, hipMemcpyHostToDevice, st));
-      LAUNCH_K(k_gather_heads, dim3((nchunks + 63) / 64), dim3(64), 0, st, d_src, d_off, d_len,
-               d_heads, nchunks);
-      std::vector<uint8_t> tails((size_t)nchunks * 32);
-      HIP_CHECK(hipMemcpyAsync(tails.data(), d_heads, tails.size(), hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipStreamSynchronize(st));
-      for (uint32_t i = 0; i < nchunks; i++) {
-        if (tailLen[i] < 9)
-          continue;
-        const uint8_t* t = tails.data() + (size_t)i * 32;
-        uint64_t ob;
-        memcpy(&ob, t + 1, 8);
-        if (tailLen[i] != 9 + bytes_of_bits(ob))   // no wrap for ob near 2^64
-          continue;
-        outHead[i].has = true;
-        outHead[i].off = tailOff[i];
-        outHead[i].total_bits = ob;
-        outHead[i].nbp = t[0];
-        anyOutlier = true;
+    if (!anyTail)
+      return 0;
+    if (gather(tailOff, tailLen, tails))
+      return -1;
+    for (uint32_t i = 0; i < nchunks; i++) {
+      if (tailLen[i] < 9)
+        continue;
+      const uint8_t* t = tails.data() + (size_t)i * 32;
+      uint64_t ob;
+      memcpy(&ob, t + 1, 8);
+      if (tailLen[i] != 9 + bytes_of_bits(ob))   // no wrap for ob near 2^64
+        continue;
+      outHead[i].has = true;
+      outHead[i].off = tailOff[i];
+      outHead[i].total_bits = ob;
+      outHead[i].nbp = t[0];
+      anyOutlier = true;
+    }
+    return 0;
+  }
+  // Chunks of this call that decode through k_lis_mx, whatever their shape group: they run side by side, each with
+  // several one-per-CU workgroups (the rows of a chunk's regions take about four workgroups to keep its serial walk
+  // fed), so the groups share one budget of workgroups (SPERR_HIP_MX_WGS; with more workgroups than CUs the chunks
+  // launched last wait for the first ones to END: 1000^3 in 256^3 chunks, 37 such chunks at 8 workgroups each,
+  // decoded no faster than with one workgroup per chunk)
+  void count_mx_groups()
+  {
+    size_t nmx = 0;
+    for (auto& h : groups) {
+      ShapePlan* Q = (slice && slice_forest_enabled()) ? E.plan(h.first[0], h.first[1], 0) : E.plan(h.first[0], h.first[1], h.first[2]);
+      if (Q && use_mixed(*Q))
+        nmx += h.second.size();
+    }
+    static const uint32_t mxBudget = getenv("SPERR_HIP_MX_WGS") ? (uint32_t)atoi(getenv("SPERR_HIP_MX_WGS")) : 208u;
+    // (calls that share the device -- the chunk farm's workers, several host threads -- share the budget: each of these
+    //  workgroups has a CU to itself for as long as its chunk's phase lasts)
+    size_t sharers = 1;
+    int devNow = 0;
+    if (hipGetDevice(&devNow) == hipSuccess)
+      sharers = std::max<size_t>(1, g_pool.busy_on(devNow));
+    if (nmx)
+      mxGroupsCall = std::min<uint32_t>(8u, std::max<uint32_t>(2u, (uint32_t)(mxBudget / (nmx * sharers))));
+  }
+  // (groups of 32 and more chunks of a shape the table kernels take keep the sub-batch scheme)
+  static bool deferrable(const ShapePlan& P, size_t nchunksOfShape) { return nchunksOfShape < 32 || !use_tables(P); }
+  // Refinement bit planes (speck_dec.h, DecBuffers::refPlanes): as many as the chunks of a group with 32-bit
+  // coefficients have planes (byte 17 of a chunk: src/SPECK_INT.cpp:284-308); not for a slice that goes through
+  // the quadtree walk of speck2d.hip, which updates coefficients itself
+  uint32_t ref_planes_of(const ShapePlan& P, const std::vector<Ref>& refs) const
+  {
+    if (slice && !(P.ht.flags & spk::kTree2D))
+      return 0;
+    uint32_t n = 0;
+    for (const Ref& r : refs) {
+      const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
+      if (ci.len[r.gid] >= 26 && !(hd[0] & 0x01) && hd[17] <= 32)
+        n = std::max<uint32_t>(n, hd[17]);
+    }
+    return n;
+  }
+  // The fp64 chunk buffer of a group can be COMPACT (round 3): when the finest level runs as the fused
+  // x-y-z kernel and every inverse pass dequantises the samples no coarser level produces straight
+  // from the integer coefficients, the buffer only ever holds the box of the second level (an eighth
+  // of the chunk: 17 MB instead of 134 MB for 256^3).  Not with 64-bit coefficients (they live in the
+  // buffer), outlier correctors (every pass stays in the buffer), the resolution hierarchy or slices.
+  size_t compact_box(const ShapePlan& P, const std::vector<Ref>& refs, uint32_t cbox[3]) const
+  {
+    cbox[0] = cbox[1] = cbox[2] = 0;
+    if (!fuse_xyz(P) || !plan_fusable(P) || mr || slice || anyOutlier || P.fwd.size() < 3)
+      return 0;
+    for (const Ref& r : refs) {
+      const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
+      if (ci.len[r.gid] >= 26 && !(hd[0] & 0x01) && hd[17] > 32)
+        return 0;   // a chunk with 64-bit coefficients
+    }
+    for (size_t k = 3; k < P.fwd.size(); k++)
+      for (int a = 0; a < 3; a++)
+        cbox[a] = std::max(cbox[a], P.fwd[k].region[a]);
+    for (int a = 0; a < 3; a++)
+      cbox[a] = std::max(cbox[a], 1u);
+    return (size_t)cbox[0] * cbox[1] * cbox[2];
+  }
+  // room for all the small groups at once, if the memory is there
+  int size_deferred()
+  {
+    deferSized = true;
+    size_t sum = 0;
+    for (auto& h : groups) {
+      ShapePlan* Q = E.plan(h.first[0], h.first[1], h.first[2]);
+      if (!Q)
+        return -1;
+      if (!deferrable(*Q, h.second.size()))
+        continue;
+      uint64_t mp = 0;
+      for (auto& r : h.second)
+        mp = std::max<uint64_t>(mp, ci.len[r.gid]);
+      uint32_t qbox[3];
+      sum += round_up(h.second.size() * dec_bytes_per_chunk(*Q, mp, compact_box(*Q, h.second, qbox), ref_planes_of(*Q, h.second), box != nullptr) + (1 << 20), 4096);
+    }
+    size_t fr = 0, tot = 0;
+    HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    const size_t room = arena_room(E.arena.n, fr);
+    return E.arena.ensure(std::min(sum, room)) ? -1 : 0;
+  }
+  // a shape group: its plan, buffer layout and batch size, then batch after batch.  Pass 0 decodes the groups that
+  // are not deferred, pass 1 the deferred ones
+  int decode_group(const Dims& shape, const std::vector<Ref>& refs, int pass)
+  {
+    // a slice is decoded by the kernels of the 3D decoder on the 2D coder's forest (k_lis_mx and its
+    // type-I phase); SPERR_HIP_SLICE_MIXED=0: by k_speck2d_decode, one workgroup walking the quadtree
+    ShapePlan* P = nullptr;
+    if (slice && slice_forest_enabled()) {
+      P = E.plan(shape[0], shape[1], 0);
+      if (P && !use_mixed(*P))
+        P = nullptr;
+    }
+    if (!P)
+      P = E.plan(shape[0], shape[1], shape[2]);
+    if (!P)
+      return -1;
+    Batch b{&refs, P};
+    b.deferG = deferOK && deferrable(*P, refs.size());
+    if (b.deferG != (pass == 1))
+      return 0;
+    if (b.deferG && !deferSized && size_deferred())
+      return -1;
+    for (auto& r : refs)
+      b.maxPayload = std::max<uint64_t>(b.maxPayload, ci.len[r.gid]);
+    b.compactElems = compact_box(*P, refs, b.cbox);
+    b.refNPlanes = ref_planes_of(*P, refs);
+    // the inverse passes dequantise on the way (not for the resolution hierarchy, whose coarsest
+    // level is read before any pass has run)
+    b.fuseDq = plan_fusable(*P) && !mr && !slice;
+    const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, box != nullptr);
+    size_t fr = 0, tot = 0;
+    HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    const size_t budgetBytes = arena_budget(E.arena.n, fr);
+    uint32_t B = (uint32_t)std::min<size_t>(refs.size(), std::max<size_t>(1, budgetBytes / per));
+    B = std::min<uint32_t>(B, 256);
+    const size_t needBytes = (size_t)B * per + (1 << 20);
+    if (b.deferG && deferOff + needBytes > E.arena.n && drain())   // no room beside the groups in flight
+      return -1;
+    if (E.arena.ensure(needBytes))   // (grows only when nothing is in flight: deferOff == 0 here)
+      return -1;
+    for (size_t b0 = 0; b0 < refs.size(); b0 += B) {
+      const uint32_t nbAll = (uint32_t)std::min<size_t>(B, refs.size() - b0);
+      if (b.deferG && deferOff + needBytes > E.arena.n && drain())
+        return -1;
+      if (decode_batch(b, b0, nbAll, needBytes))
+        return -1;
+    }
+    return 0;
+  }
+  int decode_batch(Batch& b, size_t b0, uint32_t nbAll, size_t needBytes)
+  {
+    Arena A;
+    A.base = static_cast<char*>(E.arena.p) + (b.deferG ? deferOff : 0);
+    A.cap = E.arena.n - (b.deferG ? deferOff : 0);
+    b.deferStream = nullptr;
+    if (b.deferG) {
+      if (!deferForked) {   // the sub-streams start behind what the caller's stream holds
+        HIP_CHECK(hipEventRecord(E.evFork, st));
+        for (uint32_t q = 0; q < kSubStreams; q++)
+          HIP_CHECK(hipStreamWaitEvent(E.sub[q], E.evFork, 0));
+        HIP_CHECK(hipStreamWaitEvent(E.outlQ[1], E.evFork, 0));
+        deferForked = true;
+      }
+      // (a group of regular chunks beside groups that decode through k_lis_mx: those hold most CUs for the whole
+      //  call with workgroups that mostly wait for their turn on a chunk's serial walk, and eight groups on the
+      //  eight normal-priority hardware queues -- one of which the caller's stream has -- put two groups on one
+      //  queue, one behind the other.  The regular chunks take the 1D decoder's idle high-priority stream: a queue
+      //  pool of its own, 1000^3 in 256^3 chunks 178 -> see DESIGN.md section 9)
+      b.deferStream = (mxGroupsCall != 0 && use_tables(*b.P)) ? E.outlQ[1] : E.sub[deferNext++ % kSubStreams];
+      deferOff += round_up(needBytes, 4096);
+    }
+    if (pick_sub_batches(b, A, b0, nbAll))
+      return -1;
+    std::vector<SubHost>& subs = *b.subs;
+    if (b.nsub == 1) {
+      static const bool enqTiming = getenv("SPERR_HIP_ENQ_TIMING") != nullptr;
+      const auto tq0 = std::chrono::steady_clock::now();
+      if (enqueue(b, 0))
+        return -1;
+      if (enqTiming) {
+        fprintf(stderr, "[sperr_hip] group %u x %u x %u, %u chunks: enqueued in %.2f ms\n", b.P->dims[0], b.P->dims[1], b.P->dims[2], nbAll,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count());
+        // (diagnostics: when the group's stream is through, measured from the caller's stream at the fork)
+        hipEvent_t evEnd = nullptr;
+        if (b.deferStream && hipEventCreate(&evEnd) == hipSuccess) {
+          if (!timingFork && hipEventCreate(&timingFork) == hipSuccess)
+            (void)hipEventRecord(timingFork, st);
+          (void)hipEventRecord(evEnd, b.deferStream);
+          timingEnds.push_back({evEnd, {b.P->dims[0], b.P->dims[1], b.P->dims[2], nbAll}});
+        }
+      }
+      if (b.deferG) {   // waited for in drain()
+        pending.push_back(&subs[0]);
+        return 0;
       }
     }
+    else {
+      // one host thread per sub-batch: one thread would start the last sub-batch only after launching all kernels
+      // of the others (about 1300 launches each).  By itself no gain on MI355X, but a thread of its own may wait for
+      // its stream, which lets the launcher stop at the plane where the chunks run out of bits (DecPlanHost::d_live)
+      std::vector<int> rc(b.nsub, 0);
+      std::vector<std::thread> workers;
+      for (uint32_t q = 0; q < b.nsub; q++)
+        workers.emplace_back([&, q]() { rc[q] = enqueue(b, q); });
+      for (auto& w : workers)
+        w.join();
+      for (uint32_t q = 0; q < b.nsub; q++) {
+        if (rc[q])
+          return -1;
+        if (subs[q].nb)
+          HIP_CHECK(hipStreamWaitEvent(st, E.evJoin[q], 0));
+      }
+    }
+    return collect_states(b);
   }
-
-  struct Ref {
-    uint32_t gid;    // container chunk (ci.off / ci.len)
-    uint32_t slot;   // this call's slot (heads, outHead)
-    uint32_t org[3];
-  };
-  std::map<Dims, std::vector<Ref>> groups;
-  for (uint32_t i = 0; i < nchunks; i++) {
-    const auto& c = chunks[sel[i]];
-    groups[Dims{c[1], c[3], c[5]}].push_back({sel[i], i, {(uint32_t)c[0], (uint32_t)c[2], (uint32_t)c[4]}});
+  // The LIS phase of a plane keeps one latency-bound workgroup per chunk busy; sub-batches on
+  // separate streams let the bandwidth-bound kernels of one sub-batch run beside the LIS
+  // kernels of another.  Measured on MI355X, 64 chunks of 256^3, decompression only: 1 stream
+  // 60.4 ms, 2 streams 58.0 ms, 3 streams 57.9 ms (round 1, with one workgroup per chunk in the
+  // LIS phase of the larger sets: 1 stream 74 ms, 3 streams 65 ms).
+  // SPERR_HIP_SUBSTREAMS=n overrides the choice (1 = a single stream).
+  int pick_sub_batches(Batch& b, Arena& A, size_t b0, uint32_t nbAll)
+  {
+    static const int subEnv = getenv("SPERR_HIP_SUBSTREAMS") ? atoi(getenv("SPERR_HIP_SUBSTREAMS")) : 0;
+    uint32_t nsub = nbAll >= 32 ? 2u : 1u;
+    // A call that has the device to itself cuts a smaller batch finer (round 3): the chunks' serial
+    // chains bound it, and four sub-batches side by side decode 8 chunks in 14.4 ms instead of 16.5,
+    // 27 chunks in 26.7 instead of 30.1 (64 chunks: two 85.0, three 83.3, four 82.1 GB/s).  Not when
+    // other calls run on the device (the chunk farm's workers: their items already overlap, and
+    // sub-batches on top took its decompression from 40 to 26 GB/s).
+    int devNow = 0;
+    if (!t_shared_device && hipGetDevice(&devNow) == hipSuccess && g_pool.busy_on(devNow) <= 1)
+      nsub = nbAll >= 56 ? 3u : nbAll >= 8 ? 4u : nbAll >= 4 ? 2u : 1u;   // (round 6: three from 56 chunks on -- with this round's
+                                                                           //  shorter k_lis_hi 64 chunks decode at 117.0 GB/s
+                                                                           //  against 115.5 with two, 110.4 with four)
+    if (subEnv > 0)
+      nsub = std::min<uint32_t>(kSubStreams, (uint32_t)subEnv);
+    if (nbAll < 2 * nsub || b.deferG)   // (eight sub-batches of one chunk each: 29.5 ms for 8 chunks against 14.1 with four)
+      nsub = 1;
+    b.nsub = nsub;
+    b.subs = &subHosts.emplace_back(nsub);
+    if (nsub > 1) {
+      HIP_CHECK(hipEventRecord(E.evFork, st));
+      for (uint32_t q = 0; q < nsub; q++)
+        HIP_CHECK(hipStreamWaitEvent(E.sub[q], E.evFork, 0));
+    }
+    uint32_t done = 0;
+    for (uint32_t q = 0; q < nsub; q++) {
+      SubHost& S = (*b.subs)[q];
+      S.nb = (nbAll - done + (nsub - q) - 1) / (nsub - q);
+      S.first = b0 + done;
+      done += S.nb;
+      if (S.nb && !carve_dec(A, *b.P, S.nb, b.maxPayload, S.bb, b.compactElems, b.refNPlanes, box != nullptr))
+        return -1;
+      if (S.nb && b.compactElems)
+        g_dbg_counter[2]++;
+    }
+    HIP_CHECK(hipGetDevice(&b.devId));
+    return 0;
   }
-
-  // the output: the volume, or the box (its chunks write their windows: CropGeom, the kCrop writers)
-  VolDesc vd{{ci.vol[0], ci.vol[1], ci.vol[2]}};
-  if (box)
-    vd = VolDesc{{box->dims[0], box->dims[1], box->dims[2]}};
-  struct SubHost {
-    std::vector<ChunkGeom> hg;
-    std::vector<CropGeom> hc;
-    std::vector<uint64_t> ho, hl;
-    std::vector<DecState> hs;
-    DecBatchBufs bb;
-    uint32_t nb = 0;
-    size_t first = 0;
-  };
-  // Small groups (the border shapes of a volume that the chunk size does not divide; their chunks
-  // decode through the serial walk, one wavefront each) are not waited for one by one: each gets
-  // its own piece of the arena and one of the sub-streams, and all of them are drained together.
-  // SPERR_HIP_DEFER_GROUPS=0 decodes group after group.
-  static const bool deferEnv = !(tune_getenv("SPERR_HIP_DEFER_GROUPS") && atoi(tune_getenv("SPERR_HIP_DEFER_GROUPS")) == 0);
-  const bool deferOK = deferEnv && !anyOutlier && !mr && !slice && groups.size() > 1;
-  // (groups of 32 and more chunks of a shape the table kernels take keep the sub-batch scheme)
-  auto deferrable = [](const ShapePlan& P, size_t nchunksOfShape) {
-    const bool tables = use_tables(P);
-    return nchunksOfShape < 32 || !tables;
-  };
-  std::vector<std::unique_ptr<SubHost>> pending;
-  size_t deferOff = 0;
-  uint32_t deferNext = 0;
-  bool deferForked = false;
-  hipEvent_t timingFork = nullptr;
-  std::vector<std::pair<hipEvent_t, std::array<uint32_t, 4>>> timingEnds;
-  auto drain = [&]() -> int {
+  // everything one sub-batch enqueues on its stream (with several sub-batches: from a host thread of its own)
+  int enqueue(const Batch& b, uint32_t q)
+  {
+    SubHost& S = (*b.subs)[q];
+    const uint32_t nb = S.nb;
+    if (nb == 0)
+      return 0;
+    if (b.nsub > 1) {
+      HIP_CHECK(hipSetDevice(b.devId));
+      t_prof = &E.prof;   // (this may be a thread of its own)
+    }
+    const hipStream_t ss = b.deferStream ? b.deferStream : (b.nsub > 1 ? E.sub[q] : st);
+    S.hg.resize(nb);
+    S.ho.resize(nb);
+    S.hl.resize(nb);
+    for (uint32_t i = 0; i < nb; i++) {
+      const Ref& r = (*b.refs)[S.first + i];
+      for (int a = 0; a < 3; a++)
+        S.hg[i].org[a] = r.org[a];
+      S.ho[i] = ci.off[r.gid];
+      S.hl[i] = ci.len[r.gid];
+      const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
+      if (S.hl[i] >= 26 && !(hd[0] & 0x01)) {
+        const int nbp = hd[17];
+        if (nbp > 32)
+          S.maxWide = std::max(S.maxWide, nbp);
+        else
+          S.maxNarrow = std::max(S.maxNarrow, nbp);
+      }
+      S.outliers |= outHead[r.slot].has;
+    }
+    if (S.maxWide > kMaxPlanes || (b.compactElems && S.maxWide))
+      return -1;
+    if (enqueue_outlier_decode(b, S, q, ss) || enqueue_lists(b, S, q, ss) || enqueue_inverse(b, S, q, ss))
+      return -1;
+    if (b.nsub > 1)
+      HIP_CHECK(hipEventRecord(E.evJoin[q], ss));
+    return 0;
+  }
+  // Outlier streams (point-wise error mode) are decoded by the 1D coder on a stream of its own,
+  // beside everything below: it needs the container only; the correctors are added at the end
+  int enqueue_outlier_decode(const Batch& b, SubHost& S, uint32_t q, hipStream_t ss)
+  {
+    if (!S.outliers)
+      return 0;
+    const uint32_t nb = S.nb, N = b.P->N;
+    hipStream_t so = E.outlQ[q];
+    HIP_CHECK(hipEventRecord(E.evOutlFork[q], ss));
+    HIP_CHECK(hipStreamWaitEvent(so, E.evOutlFork[q], 0));
+    S.hoc.assign(nb, OutlierChunk{});
+    memset(S.hoc.data(), 0, nb * sizeof(OutlierChunk));
+    uint64_t maxBits = 0;
+    int maxNbp = 1;
+    for (uint32_t i = 0; i < nb; i++) {
+      const OutHead& oh = outHead[(*b.refs)[S.first + i].slot];
+      if (!oh.has)
+        continue;
+      S.hoc[i].has = 1;
+      S.hoc[i].streamOff = oh.off;
+      S.hoc[i].total_bits = oh.total_bits;
+      S.hoc[i].nbp = oh.nbp;
+      if (oh.nbp > kMaxPlanes)
+        return -1;
+      maxBits = std::max(maxBits, oh.total_bits);
+      maxNbp = std::max(maxNbp, oh.nbp);
+    }
+    OutlierBufs& ob = S.ob;
+    memset(&ob, 0, sizeof(ob));
+    ob.nchunks = nb;
+    ob.N = N;
+    ob.nw = (N + 63) / 64;
+    ob.wordStride = round_up((size_t)ob.nw + 2, 32);
+    // every value found costs at least its sign bit, every run kept on a list its test bit
+    ob.kStride = round_up((size_t)std::min<uint64_t>(N, maxBits) + 1, 64);
+    speck1d_level_offsets(ob, N, std::min<uint64_t>(maxBits + 2, 2ull * N));
+    ob.streamStride = (size_t)(maxBits / 64) + 4;
+    ob.planeStride = (size_t)maxNbp * ob.wordStride;
+    const size_t bytes = round_up(nb * sizeof(OutlierChunk), 256) +
+                         (size_t)nb * (ob.wordStride * 16 + ob.kStride * 5 + ob.runStride * 8 +
+                                       ob.streamStride * 8 + ob.planeStride * 8) + 8192;
+    if (E.outlDec[q].ensure(bytes))   // (its own buffer: the sub-batches are enqueued by separate threads)
+      return -1;
+    Arena OA;
+    OA.base = static_cast<char*>(E.outlDec[q].p);
+    OA.cap = E.outlDec[q].n;
+    ob.oc = OA.take<OutlierChunk>(nb);
+    ob.lip = OA.take<uint64_t>(nb * ob.wordStride);
+    ob.lsp = OA.take<uint64_t>(nb * ob.wordStride);
+    ob.runs = OA.take<uint64_t>(nb * ob.runStride);
+    ob.stream = OA.take<uint64_t>(nb * ob.streamStride);
+    ob.planeBits = OA.take<uint64_t>(nb * ob.planeStride);
+    ob.pos = OA.take<uint32_t>(nb * ob.kStride);
+    ob.sgn = OA.take<uint8_t>(nb * ob.kStride);
+    if (!ob.oc || !ob.lip || !ob.lsp || !ob.runs || !ob.stream || !ob.planeBits || !ob.pos || !ob.sgn)
+      return -1;
+    HIP_CHECK(hipMemcpyAsync(ob.oc, S.hoc.data(), nb * sizeof(OutlierChunk), hipMemcpyHostToDevice, so));
+    HIP_CHECK(hipMemsetAsync(ob.lip, 0, (size_t)nb * ob.wordStride * 16, so));   // lip + lsp
+    if (launch_speck1d_decode(so, ob, d_src))
+      return -1;
+    HIP_CHECK(hipEventRecord(E.evOutl[q], so));
+    return 0;
+  }
+  // the chunks' geometry, then the list phase of every plane: 64-bit chunks first, their magnitudes are decoded
+  // into (and converted inside) the fp64 buffer, which the 32-bit pass then fills for the remaining chunks
+  int enqueue_lists(const Batch& b, SubHost& S, uint32_t q, hipStream_t ss)
+  {
+    const ShapePlan& P = *b.P;
+    const uint32_t nb = S.nb;
+    DecBatchBufs& bb = S.bb;
+    DecBuffers& d = bb.db;
+    HIP_CHECK(hipMemcpyAsync(bb.geom, S.hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
+    if (box) {   // each chunk's window of the box and its origin relative to the box
+      S.hc.resize(nb);
+      for (uint32_t i = 0; i < nb; i++)
+        for (int a = 0; a < 3; a++) {
+          const size_t o = S.hg[i].org[a], lo = box->lo[a], hi = box->lo[a] + box->dims[a];
+          S.hc[i].rel[a] = (int32_t)((int64_t)o - (int64_t)lo);
+          S.hc[i].lo[a] = (uint32_t)(lo > o ? lo - o : 0);
+          S.hc[i].hi[a] = (uint32_t)std::min<size_t>(hi - o, b.P->dims[a]);
+        }
+      HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
+    }
+    HIP_CHECK(hipMemcpyAsync(bb.chunkOff, S.ho.data(), nb * 8, hipMemcpyHostToDevice, ss));
+    HIP_CHECK(hipMemcpyAsync(bb.chunkLen, S.hl.data(), nb * 8, hipMemcpyHostToDevice, ss));
+    HIP_CHECK(hipMemsetAsync(d.cst, 0, nb * sizeof(CoderState), ss));
+    HIP_CHECK(hipMemsetAsync(d.st, 0, nb * sizeof(DecState), ss));
+    DecPlanHost ph = dec_plan_host(P);
+    ph.skipFinish = true;   // launch_inv_quantize / the dequantising inverse passes complete the coefficients
+    ph.mxGroups = mxGroupsCall;
+    const bool quadWalk = slice && !(P.ht.flags & spk::kTree2D);
+    if (!ph.tables && !ph.mixed && !quadWalk) {
+      // (a tree neither the table kernels nor k_lis_mx take -- more than 288 / 352 grids or 48 roots: chunks of
+      //  2^30 samples and more -- decodes correctly, through one serial wavefront per chunk: say so, once)
+      static std::atomic<bool> warned{false};
+      if (!warned.exchange(true))
+        fprintf(stderr, "[sperr_hip] note: chunks of %u x %u x %u decode through the serial walk (k_lis_walk): their tree "
+                        "(%zu grids, %zu roots) exceeds what the parallel list kernels hold in LDS -- expect it to be slow\n",
+                b.P->dims[0], b.P->dims[1], b.P->dims[2], P.ht.grids.size(), P.ht.roots.size());
+    }
+    static const uint32_t gdivEnv = tune_getenv("SPERR_HIP_MX_GRID_DIV") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_MX_GRID_DIV")) : 4u;
+    ph.gridDiv = (b.deferStream && mxGroupsCall != 0 && groups.size() >= 4) ? std::max<uint32_t>(1u, gdivEnv) : 1u;
+    // (the host thread may wait for this stream: it is the call's only one, or has a thread of its own)
+    ph.d_live = !b.deferStream ? bb.live : nullptr;
+    ph.h_live = E.liveHost[q % kSubStreams];
+    ph.liveEv = E.liveEv[q % kSubStreams];
+    // diagnostics: SPERR_HIP_LIS_GPUWIDE=0 leaves every list to k_lis_hi
+    static const bool gpuWide = !(getenv("SPERR_HIP_LIS_GPUWIDE") && atoi(getenv("SPERR_HIP_LIS_GPUWIDE")) == 0);
+    if (!gpuWide)
+      ph.l0 = ph.l1 = ph.l2 = false;
+    HIP_CHECK(hipMemsetAsync(d.mask, 0, std::max<size_t>(d.maskStride, 1) * nb * 8, ss));
+    HIP_CHECK(hipMemsetAsync(d.l0Flags, 0, d.l0FlagStride * nb * 8, ss));
+    HIP_CHECK(hipMemsetAsync(d.l0Tab, 0, d.l0FlagStride * 17 * nb * 8, ss));
+    HIP_CHECK(hipMemsetAsync(d.l1Flags, 0, d.l0FlagStride * nb * 8, ss));
+    HIP_CHECK(hipMemsetAsync(d.l2Flags, 0, d.l0FlagStride * nb * 8, ss));
+    HIP_CHECK(hipMemsetAsync(d.hiFlags, 0, d.hiFlagStride * nb * 8, ss));
+    HIP_CHECK(hipMemsetAsync(d.sigbits, 0, d.sigbitsStride * nb * 8, ss));
+    if (d.lisStamps)
+      HIP_CHECK(hipMemsetAsync(d.lisStamps, 0, 64 * 8 * nb, ss));
+    for (int wide = 1; wide >= 0; wide--) {
+      if (wide && S.maxWide == 0)
+        continue;
+      HIP_CHECK(hipMemsetAsync(d.bornM, 0, d.maskPixStride * nb * 8, ss));
+      if (d.tileBorn)
+        HIP_CHECK(hipMemsetAsync(d.tileBorn, 0, d.tileStride * nb, ss));
+      HIP_CHECK(hipMemsetAsync(d.sigOld, 0, d.maskPixStride * nb * 8, ss));
+      HIP_CHECK(hipMemsetAsync(d.sigNew, 0, d.maskPixStride * nb * 8, ss));
+      HIP_CHECK(hipMemsetAsync(d.sign, 0xff, d.signStride * nb * 8, ss));
+      HIP_CHECK(hipMemsetAsync(d.leafState, 0, d.leafStateStride * nb * 2, ss));
+      HIP_CHECK(hipMemsetAsync(d.leafDirty, 0, d.leafDirtyStride * nb, ss));
+      HIP_CHECK(hipMemsetAsync(d.stream, 0, d.streamStride * nb * 8, ss));
+      DecBuffers dw = d;
+      if (wide) {  // 64-bit magnitudes live in the fp64 buffer, converted in place afterwards
+        dw.coef = bb.vals;
+        dw.coefStride = bb.valsStride;
+        dw.refPlanes = nullptr;
+        HIP_CHECK(hipMemsetAsync(bb.vals, 0, bb.valsStride * nb * 8, ss));
+      }
+      else if (d.refPlanes) { // (k_ref_assemble writes every coefficient; a plane's words are valid from wordTop down)
+        HIP_CHECK(hipMemsetAsync(d.wordTop, 0, d.wordTopStride * nb, ss));
+        dw.coefSigned = b.fuseDq ? 1u : 0u;   // (read by the dequantising inverse passes only: LiftFuse::coefSigned)
+      }
+      else
+        HIP_CHECK(hipMemsetAsync(bb.coef32, 0, d.coefStride * nb * 4, ss));
+      if (quadWalk) {   // header + stream words by the 3D launcher (no planes), then the 2D coder
+        DecPlanHost ph2 = ph;
+        ph2.tables = ph2.l0 = ph2.l1 = ph2.mixed = false;
+        Speck2dBufs sb;
+        if (launch_speck_decode(ss, dw, ph2, d_src, bb.chunkOff, bb.chunkLen, wide != 0, 0) || carve_slice2d(E, P, sb))
+          return -1;
+        sb.coef = dw.coef;
+        sb.sign = d.sign;
+        sb.stream = d.stream;
+        sb.streamWords = d.streamStride;
+        sb.cst = d.cst;
+        sb.dst = d.st;
+        if (launch_speck2d_decode(ss, sb, wide != 0) ||
+            launch_inv_quantize(ss, wide != 0, dw.coef, dw.coefStride, d.sign, d.signStride, nb, P.N, bb.vals,
+                                bb.valsStride, d.cst))
+          return -1;
+        continue;
+      }
+      // the header kernel must run even when no plane does (constant / all-zero chunks)
+      if (launch_speck_decode(ss, dw, ph, d_src, bb.chunkOff, bb.chunkLen, wide != 0, wide ? S.maxWide : S.maxNarrow))
+        return -1;
+      // (32-bit coefficients are dequantised by the inverse passes as they load them, LiftFuse)
+      if ((wide || !b.fuseDq) &&
+          launch_inv_quantize(ss, wide != 0, dw.coef, dw.coefStride, d.sign, d.signStride, nb, P.N, bb.vals,
+                              bb.valsStride, d.cst, d.sigNew, d.sigOld, d.maskPixStride, d.st))
+        return -1;
+    }
+    return 0;
+  }
+  // The inverse transform.  Its last pass covers the whole chunk: it adds the mean, narrows and scatters --
+  // unless outlier correctors have to be added to the transformed values first (src/SPECK_FLT.cpp:573-590), in
+  // which case every pass stays in the chunk buffer
+  int enqueue_inverse(const Batch& b, SubHost& S, uint32_t q, hipStream_t ss)
+  {
+    const ShapePlan& P = *b.P;
+    const uint32_t nb = S.nb;
+    const uint32_t* cd = P.dims;
+    DecBatchBufs& bb = S.bb;
+    DecBuffers& d = bb.db;
+    const int io = std::is_same<T, float>::value ? 1 : 2;
+    const bool fxyz = fuse_xyz(P) && !S.outliers;
+    const bool fxy = fuse_xy(P) && !S.outliers && !fxyz;
+    // With outlier correctors the transformed values have to stay doubles a little longer -- but they can still
+    // come from the fused kernels (round 5): the coarser levels in a compact buffer of their box, the finest level
+    // by k_lift_xyz_inv writing doubles, no mean added, into the chunk buffer as if it were a volume of bricks (a
+    // chunk's offset rides in org[0]); the correctors and the scatter pass follow as before.  (Fifteen per-axis
+    // passes over the whole chunk before: 12.7 ms for 64 chunks of 256^3.)
+    const bool fbrick = S.outliers && fuse_xyz(P) && b.fuseDq && S.maxWide == 0 && P.fwd.size() >= 3 &&
+                        b.compactElems == 0 && (uint64_t)nb * bb.valsStride <= 0xffffffffull;
+    uint32_t bbox[3] = {1, 1, 1};
+    double* boxVals = nullptr;
+    size_t boxStride = 0;
+    ChunkGeom* d_bricks = nullptr;
+    if (fbrick) {
+      for (size_t k = 3; k < P.fwd.size(); k++)
+        for (int a = 0; a < 3; a++)
+          bbox[a] = std::max(bbox[a], P.fwd[k].region[a]);
+      boxStride = round_up((size_t)bbox[0] * bbox[1] * bbox[2], 64);
+      const size_t geomOff = round_up((size_t)nb * boxStride * 8, 256);
+      if (E.decBox[q].ensure(geomOff + (size_t)nb * sizeof(ChunkGeom) + 256))
+        return -1;
+      boxVals = static_cast<double*>(E.decBox[q].p);
+      d_bricks = reinterpret_cast<ChunkGeom*>(static_cast<char*>(E.decBox[q].p) + geomOff);
+      S.bricks.resize(nb);
+      for (uint32_t i = 0; i < nb; i++) {
+        S.bricks[i].org[0] = (uint32_t)((size_t)i * bb.valsStride);
+        S.bricks[i].org[1] = S.bricks[i].org[2] = 0;
+      }
+      HIP_CHECK(hipMemcpyAsync(d_bricks, S.bricks.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
+    }
+    // a level of the inverse transform is 3 passes (z y x) of a dyadic chunk, 2 (y x) of a slice
+    const size_t perLevel = slice ? 2 : 3;
+    auto sub_volume = [&](size_t k) -> int {   // before pass k, the first of its level
+      if (!mr || !mr->nlev)
+        return 0;
+      const size_t h = mr->nlev - (k / perLevel + 1);
+      const auto& r = mr->cres[h];
+      const uint32_t blocks = capped_blocks((r[0] * r[1] * r[2] + kThreads - 1) / kThreads, nb);
+      LAUNCH_K(k_sub_volume, dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, d.cst, bb.geom,
+               cd[0], cd[1], cd[0], cd[1], cd[2], r[0], r[1], r[2], mr->grid[0], mr->grid[1], mr->d_level[h]);
+      return 0;
+    };
+    auto dequant_fuse = [&](size_t k, LiftFuse& lf) {
+      if (b.fuseDq && pass_fuse(P, k, lf.inner) > 0) {
+        lf.mode = 2;
+        lf.coef = bb.coef32;
+        lf.coefStride = d.coefStride;
+        lf.sign = d.sign;
+        lf.signStride = d.signStride;
+        lf.sigNew = d.sigNew;
+        lf.sigOld = d.sigOld;
+        lf.maskStride = d.maskPixStride;
+        lf.dst = d.st;
+        lf.coefSigned = d.refPlanes ? 1 : 0;
+      }
+      if (b.compactElems) {
+        lf.bufx = b.cbox[0];
+        lf.bufy = b.cbox[1];
+      }
+      if (fbrick) {
+        lf.bufx = bbox[0];
+        lf.bufy = bbox[1];
+      }
+    };
+    for (size_t k = P.fwd.size(); k-- > ((fxyz || fbrick) ? 3u : fxy ? 2u : 0u);) {
+      const LiftPass& ps = P.fwd[k];
+      if (k % perLevel == perLevel - 1 && sub_volume(k))
+        return -1;
+      LiftFuse lf;
+      dequant_fuse(k, lf);
+      const bool last = k == 0 && !S.outliers;   // (the pass that writes the volume / the box)
+      if (launch_lift(ss, false, fbrick ? boxVals : bb.vals, fbrick ? boxStride : bb.valsStride, nb, cd, ps.axis,
+                      ps.region, d.cst, last ? io : 0, d_dst, vd, bb.geom, &lf, last ? bb.crop : nullptr))
+        return -1;
+    }
+    if (fbrick) {   // the finest level into the chunk buffer, as doubles
+      LiftFuse lf;
+      dequant_fuse(2, lf);
+      lf.noMean = 1;
+      const VolDesc brickVol{{cd[0], cd[1], cd[2]}};
+      if (launch_lift_xyz(ss, false, boxVals, boxStride, nb, cd, d.cst, 2, bb.vals, brickVol, d_bricks, &lf))
+        return -1;
+    }
+    if (fxyz) {   // the finest level: z, y and x pass in one kernel, into the volume
+      if (sub_volume(2))
+        return -1;
+      LiftFuse lf;
+      dequant_fuse(2, lf);
+      if (launch_lift_xyz(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst, io, d_dst, vd, bb.geom, &lf, bb.crop))
+        return -1;
+    }
+    if (fxy && slice && sub_volume(1))   // the finest level of a slice is the fused pair
+      return -1;
+    if (fxy && launch_lift_xy(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst, io, d_dst, vd, bb.geom, bb.crop))
+      return -1;
+    if (S.outliers) {   // the correctors of the values the 1D decoder found meanwhile
+      HIP_CHECK(hipStreamWaitEvent(ss, E.evOutl[q], 0));
+      if (launch_outlier_apply(ss, S.ob, d.cst, bb.vals, bb.valsStride))
+        return -1;
+      HIP_CHECK(hipMemcpyAsync(S.hoc.data(), S.ob.oc, nb * sizeof(OutlierChunk), hipMemcpyDeviceToHost, ss));
+      HIP_CHECK(hipStreamSynchronize(ss));
+      for (auto& o : S.hoc)
+        if (o.error) {
+          fprintf(stderr, "[sperr_hip] outlier decoder failed (code %u)\n", o.error);
+          return -1;
+        }
+    }
+    if ((P.fwd.empty() || S.outliers) &&
+        launch_scatter<T>(ss, d_dst, vd, bb.geom, nb, cd, bb.vals, bb.valsStride, d.cst, bb.crop))
+      return -1;
+    return 0;
+  }
+  // read-backs only after every sub-batch is enqueued: a device-to-host copy into pageable
+  // memory blocks the host until its stream has drained
+  int collect_states(const Batch& b)
+  {
+    for (uint32_t q = 0; q < b.nsub; q++) {
+      SubHost& S = (*b.subs)[q];
+      if (S.nb == 0)
+        continue;
+      hipStream_t ss = b.nsub > 1 ? E.sub[q] : st;
+      if (S.bb.db.lisStamps && q == 0) {
+        g_lis_stamps_host.assign(64, 0);
+        // (SPERR_HIP_STAMP_CHUNK=i: the counters of the batch's i-th chunk instead of the first)
+        const uint32_t sc = getenv("SPERR_HIP_STAMP_CHUNK")
+                                ? std::min<uint32_t>(S.nb - 1, (uint32_t)atoi(getenv("SPERR_HIP_STAMP_CHUNK")))
+                                : 0u;
+        HIP_CHECK(hipMemcpyAsync(g_lis_stamps_host.data(), S.bb.db.lisStamps + (size_t)sc * 64, 64 * 8,
+                                 hipMemcpyDeviceToHost, ss));
+      }
+      S.hs.resize(S.nb);   // stream errors (wrong lengths) surface here
+      HIP_CHECK(hipMemcpyAsync(S.hs.data(), S.bb.db.st, S.nb * sizeof(DecState), hipMemcpyDeviceToHost, ss));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (b.nsub > 1)
+      for (uint32_t q = 0; q < b.nsub; q++)
+        HIP_CHECK(hipStreamSynchronize(E.sub[q]));
+    for (auto& S : *b.subs)
+      for (auto& hsx : S.hs)
+        if (hsx.error) {
+          report_dec_error(hsx.error);
+          return -1;
+        }
+    return 0;
+  }
+  // waits for the deferred groups, and reads their states back
+  int drain()
+  {
     int rc = 0;
     for (uint32_t q = 0; q < kSubStreams; q++)
       HIP_CHECK(hipStreamSynchronize(E.sub[q]));
@@ -2686,7 +3315,7 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
       (void)hipEventDestroy(timingFork);
       timingFork = nullptr;
     }
-    for (auto& S : pending) {                  // stream errors (wrong lengths) surface here
+    for (SubHost* S : pending) {   // stream errors (wrong lengths) surface here
       S->hs.resize(S->nb);
       HIP_CHECK(hipMemcpy(S->hs.data(), S->bb.db.st, S->nb * sizeof(DecState), hipMemcpyDeviceToHost));
       for (auto& hsx : S->hs)
@@ -2698,633 +3327,16 @@ int decompress_impl(Engine& E, const uint8_t* d_src, size_t src_len, T* d_dst, s
     pending.clear();
     deferOff = 0;
     return rc;
-  };
-  auto bytes_per_chunk = [&](const ShapePlan& P, uint64_t maxPayload, size_t valsElems = 0, uint32_t refNPlanes = 0) -> size_t {
-    Arena probe;
-    probe.base = reinterpret_cast<char*>(uintptr_t(4096));  // size probe only
-    probe.cap = ~size_t(0) / 2;
-    DecBatchBufs tmp;
-    carve_dec(probe, P, 1, maxPayload, tmp, valsElems, refNPlanes, box != nullptr);
-    return probe.used;
-  };
-  // Refinement bit planes (speck_dec.h, DecBuffers::refPlanes): as many as the chunks of a group with 32-bit
-  // coefficients have planes (byte 17 of a chunk: src/SPECK_INT.cpp:284-308); not for a slice that goes through
-  // the quadtree walk of speck2d.hip, which updates coefficients itself.  SPERR_HIP_REF_PLANES=0: none
-  // (k_ref_apply2 updates the coefficients plane by plane, as rounds 3 and 4 did).
-  static const bool refPlanesEnv = !(tune_getenv("SPERR_HIP_REF_PLANES") && atoi(tune_getenv("SPERR_HIP_REF_PLANES")) == 0);
-  auto ref_planes_of = [&](const ShapePlan& P, const std::vector<Ref>& refs) -> uint32_t {
-    if (!refPlanesEnv || (slice && !(P.ht.flags & spk::kTree2D)))
-      return 0;
-    uint32_t n = 0;
-    for (const Ref& r : refs) {
-      const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
-      if (ci.len[r.gid] >= 26 && !(hd[0] & 0x01) && hd[17] <= 32)
-        n = std::max<uint32_t>(n, hd[17]);
-    }
-    return n;
-  };
-  // The fp64 chunk buffer of a group can be COMPACT (round 3): when the finest level runs as the fused
-  // x-y-z kernel and every inverse pass dequantises the samples no coarser level produces straight
-  // from the integer coefficients, the buffer only ever holds the box of the second level (an eighth
-  // of the chunk: 17 MB instead of 134 MB for 256^3).  Not with 64-bit coefficients (they live in the
-  // buffer), outlier correctors (every pass stays in the buffer), the resolution hierarchy or slices.
-  static const bool compactEnv = !(tune_getenv("SPERR_HIP_DEC_COMPACT") && atoi(tune_getenv("SPERR_HIP_DEC_COMPACT")) == 0);
-  auto compact_box = [&](const ShapePlan& P, const std::vector<Ref>& refs, uint32_t box[3]) -> size_t {
-    box[0] = box[1] = box[2] = 0;
-    if (!compactEnv || !fuse_xyz(P) || !plan_fusable(P) || mr || slice || anyOutlier || P.fwd.size() < 3)
-      return 0;
-    for (const Ref& r : refs) {
-      const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
-      if (ci.len[r.gid] >= 26 && !(hd[0] & 0x01) && hd[17] > 32)
-        return 0;   // a chunk with 64-bit coefficients
-    }
-    for (size_t k = 3; k < P.fwd.size(); k++)
-      for (int a = 0; a < 3; a++)
-        box[a] = std::max(box[a], P.fwd[k].region[a]);
-    for (int a = 0; a < 3; a++)
-      box[a] = std::max(box[a], 1u);
-    return (size_t)box[0] * box[1] * box[2];
-  };
-  bool deferSized = false;
-  // chunks of this call that decode through k_lis_mx, whatever their shape group: they run side by side, each with
-  // several one-per-CU workgroups (the rows of a chunk's regions take about four workgroups to keep its serial walk
-  // fed), so the groups share one budget of workgroups (SPERR_HIP_MX_WGS; with more workgroups than CUs the chunks
-  // launched last wait for the first ones to END: 1000^3 in 256^3 chunks, 37 such chunks at 8 workgroups each,
-  // decoded no faster than with one workgroup per chunk)
-  uint32_t mxGroupsCall = 0;
-  {
-    size_t nmx = 0;
-    for (auto& h : groups) {
-      ShapePlan* Q = (slice && slice_forest_enabled()) ? E.plan(h.first[0], h.first[1], 0) : E.plan(h.first[0], h.first[1], h.first[2]);
-      if (Q && use_mixed(*Q))
-        nmx += h.second.size();
-    }
-    static const uint32_t mxBudget = getenv("SPERR_HIP_MX_WGS") ? (uint32_t)atoi(getenv("SPERR_HIP_MX_WGS")) : 208u;
-    // (calls that share the device -- the chunk farm's workers, several host threads -- share the budget: each of these
-    //  workgroups has a CU to itself for as long as its chunk's phase lasts)
-    size_t sharers = 1;
-    {
-      int devNow = 0;
-      if (hipGetDevice(&devNow) == hipSuccess)
-        sharers = std::max<size_t>(1, g_pool.busy_on(devNow));
-    }
-    if (nmx)
-      mxGroupsCall = std::min<uint32_t>(8u, std::max<uint32_t>(2u, (uint32_t)(mxBudget / (nmx * sharers))));
   }
-  // a slice is decoded by the kernels of the 3D decoder on the 2D coder's forest (k_lis_mx and its
-  // type-I phase); SPERR_HIP_SLICE_MIXED=0: by k_speck2d_decode, one workgroup walking the quadtree
-  const bool sliceMixed = slice_forest_enabled();
-  for (int pass = 0; pass < 2; pass++)
-  for (auto& g : groups) {
-    ShapePlan* P = nullptr;
-    if (slice && sliceMixed) {
-      P = E.plan(g.first[0], g.first[1], 0);
-      if (P && !use_mixed(*P))
-        P = nullptr;
-    }
-    if (!P)
-      P = E.plan(g.first[0], g.first[1], g.first[2]);
-    if (!P)
-      return -1;
-    const bool deferG = deferOK && deferrable(*P, g.second.size());
-    if (deferG != (pass == 1))
-      continue;
-    if (deferG && !deferSized) {   // room for all the small groups at once, if the memory is there
-      deferSized = true;
-      size_t sum = 0;
-      for (auto& h : groups) {
-        ShapePlan* Q = E.plan(h.first[0], h.first[1], h.first[2]);
-        if (!Q)
-          return -1;
-        if (!deferrable(*Q, h.second.size()))
-          continue;
-        uint64_t mp = 0;
-        for (auto& r : h.second)
-          mp = std::max<uint64_t>(mp, ci.len[r.gid]);
-        uint32_t qbox[3];
-        sum += round_up(h.second.size() * bytes_per_chunk(*Q, mp, compact_box(*Q, h.second, qbox), ref_planes_of(*Q, h.second)) + (1 << 20), 4096);
-      }
-      size_t fr = 0, tot = 0;
-      HIP_CHECK(hipMemGetInfo(&fr, &tot));
-      const size_t room = arena_room(E.arena.n, fr);
-      if (E.arena.ensure(std::min(sum, room)))
-        return -1;
-    }
-    uint64_t maxPayload = 0;
-    for (auto& r : g.second)
-      maxPayload = std::max<uint64_t>(maxPayload, ci.len[r.gid]);
-    uint32_t cbox[3];
-    const size_t compactElems = compact_box(*P, g.second, cbox);
-    const uint32_t refNPlanes = ref_planes_of(*P, g.second);
-    const size_t per = bytes_per_chunk(*P, maxPayload, compactElems, refNPlanes);
-    size_t fr = 0, tot = 0;
-    HIP_CHECK(hipMemGetInfo(&fr, &tot));
-    const size_t budgetBytes = arena_budget(E.arena.n, fr);
-    uint32_t B = (uint32_t)std::min<size_t>(g.second.size(), std::max<size_t>(1, budgetBytes / per));
-    B = std::min<uint32_t>(B, 256);
-    const size_t needBytes = (size_t)B * per + (1 << 20);
-    if (deferG && deferOff + needBytes > E.arena.n && drain())   // no room beside the groups in flight
-      return -1;
-    if (E.arena.ensure(needBytes))   // (grows only when nothing is in flight: deferOff == 0 here)
-      return -1;
-    const uint32_t cd[3] = {P->dims[0], P->dims[1], P->dims[2]};
-    for (size_t b0 = 0; b0 < g.second.size(); b0 += B) {
-      const uint32_t nbAll = (uint32_t)std::min<size_t>(B, g.second.size() - b0);
-      if (deferG && deferOff + needBytes > E.arena.n && drain())
-        return -1;
-      Arena A;
-      A.base = static_cast<char*>(E.arena.p) + (deferG ? deferOff : 0);
-      A.cap = E.arena.n - (deferG ? deferOff : 0);
-      hipStream_t deferStream = nullptr;
-      if (deferG) {
-        if (!deferForked) {   // the sub-streams start behind what the caller's stream holds
-          HIP_CHECK(hipEventRecord(E.evFork, st));
-          for (uint32_t q = 0; q < kSubStreams; q++)
-            HIP_CHECK(hipStreamWaitEvent(E.sub[q], E.evFork, 0));
-          HIP_CHECK(hipStreamWaitEvent(E.outlQ[1], E.evFork, 0));
-          deferForked = true;
-        }
-        // (a group of regular chunks beside groups that decode through k_lis_mx: those hold most CUs for the whole
-        //  call with workgroups that mostly wait for their turn on a chunk's serial walk, and eight groups on the
-        //  eight normal-priority hardware queues -- one of which the caller's stream has -- put two groups on one
-        //  queue, one behind the other.  The regular chunks take the 1D decoder's idle high-priority stream: a queue
-        //  pool of its own, 1000^3 in 256^3 chunks 178 -> see DESIGN.md section 9)
-        if (mxGroupsCall != 0 && use_tables(*P))
-          deferStream = E.outlQ[1];
-        else
-          deferStream = E.sub[deferNext++ % kSubStreams];
-        deferOff += round_up(needBytes, 4096);
-      }
-      // The LIS phase of a plane keeps one latency-bound workgroup per chunk busy; sub-batches on
-      // separate streams let the bandwidth-bound kernels of one sub-batch run beside the LIS
-      // kernels of another.  Measured on MI355X, 64 chunks of 256^3, decompression only: 1 stream
-      // 60.4 ms, 2 streams 58.0 ms, 3 streams 57.9 ms (round 1, with one workgroup per chunk in the
-      // LIS phase of the larger sets: 1 stream 74 ms, 3 streams 65 ms).
-      // SPERR_HIP_SUBSTREAMS=n overrides the choice (1 = a single stream).
-      static const int subEnv = getenv("SPERR_HIP_SUBSTREAMS") ? atoi(getenv("SPERR_HIP_SUBSTREAMS")) : 0;
-      static const bool threads = !(tune_getenv("SPERR_HIP_ENQUEUE_THREADS") && atoi(tune_getenv("SPERR_HIP_ENQUEUE_THREADS")) == 0);
-      uint32_t nsub = nbAll >= 32 ? 2u : 1u;
-      // A call that has the device to itself cuts a smaller batch finer (round 3): the chunks' serial
-      // chains bound it, and four sub-batches side by side decode 8 chunks in 14.4 ms instead of 16.5,
-      // 27 chunks in 26.7 instead of 30.1 (64 chunks: two 85.0, three 83.3, four 82.1 GB/s).  Not when
-      // other calls run on the device (the chunk farm's workers: their items already overlap, and
-      // sub-batches on top took its decompression from 40 to 26 GB/s).
-      {
-        int devNow = 0;
-        if (!t_shared_device && hipGetDevice(&devNow) == hipSuccess && g_pool.busy_on(devNow) <= 1)
-          nsub = nbAll >= 56 ? 3u : nbAll >= 8 ? 4u : nbAll >= 4 ? 2u : 1u;   // (round 6: three from 56 chunks on -- with this round's
-                                                                               //  shorter k_lis_hi 64 chunks decode at 117.0 GB/s
-                                                                               //  against 115.5 with two, 110.4 with four)
-      }
-      if (subEnv > 0)
-        nsub = std::min<uint32_t>(kSubStreams, (uint32_t)subEnv);
-      // (with outlier streams every sub-batch waits for its stream when it reads back the 1D decoder's
-      //  state: several sub-batches only when each has a host thread of its own)
-      if ((anyOutlier && !threads) || nbAll < 2 * nsub || deferG)   // (eight sub-batches of one chunk each: 29.5 ms for 8 chunks against 14.1 with four)
-        nsub = 1;
-      std::vector<SubHost> subs(nsub);
-      if (nsub > 1) {
-        HIP_CHECK(hipEventRecord(E.evFork, st));
-        for (uint32_t q = 0; q < nsub; q++)
-          HIP_CHECK(hipStreamWaitEvent(E.sub[q], E.evFork, 0));
-      }
-      uint32_t done = 0;
-      for (uint32_t q = 0; q < nsub; q++) {
-        SubHost& S = subs[q];
-        S.nb = (nbAll - done + (nsub - q) - 1) / (nsub - q);
-        S.first = b0 + done;
-        done += S.nb;
-        if (S.nb && !carve_dec(A, *P, S.nb, maxPayload, S.bb, compactElems, refNPlanes, box != nullptr))
-          return -1;
-        if (S.nb && compactElems)
-          g_dbg_counter[2]++;
-      }
-      int devId = 0;
-      HIP_CHECK(hipGetDevice(&devId));
-      // everything one sub-batch enqueues on its stream.  With several sub-batches each is
-      // enqueued by its own host thread: one thread would start the last sub-batch only after
-      // launching all kernels of the others (about 1300 launches each)
-      auto enqueue = [&](uint32_t q) -> int {
-        SubHost& S = subs[q];
-        const uint32_t nb = S.nb;
-        const size_t first = S.first;
-        if (nb == 0)
-          return 0;
-        if (nsub > 1) {
-          HIP_CHECK(hipSetDevice(devId));
-          t_prof = &E.prof;   // (this may be a thread of its own)
-        }
-        hipStream_t ss = deferStream ? deferStream : (nsub > 1 ? E.sub[q] : st);
-        DecBatchBufs& bb = S.bb;
-        DecBuffers& d = bb.db;
-        S.hg.resize(nb);
-        S.ho.resize(nb);
-        S.hl.resize(nb);
-        int maxNarrow = 0, maxWide = 0;
-        for (uint32_t i = 0; i < nb; i++) {
-          const Ref& r = g.second[first + i];
-          for (int a = 0; a < 3; a++)
-            S.hg[i].org[a] = r.org[a];
-          S.ho[i] = ci.off[r.gid];
-          S.hl[i] = ci.len[r.gid];
-          const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
-          if (S.hl[i] >= 26 && !(hd[0] & 0x01)) {
-            const int nbp = hd[17];
-            if (nbp > 32)
-              maxWide = std::max(maxWide, nbp);
-            else
-              maxNarrow = std::max(maxNarrow, nbp);
-          }
-        }
-        if (maxWide > kMaxPlanes || (compactElems && maxWide))
-          return -1;
-        // Outlier streams (point-wise error mode) are decoded by the 1D coder on a stream of their own,
-        // beside everything below: it needs the container only; the correctors are added at the end
-        bool batchOutliers = false;
-        for (uint32_t i = 0; i < nb; i++)
-          batchOutliers |= outHead[g.second[first + i].slot].has;
-        std::vector<OutlierChunk> hoc;
-        OutlierBufs ob;
-        {
-          hipStream_t so = E.outlQ[q];
-          if (batchOutliers) {
-            HIP_CHECK(hipEventRecord(E.evOutlFork[q], ss));
-            HIP_CHECK(hipStreamWaitEvent(so, E.evOutlFork[q], 0));
-          }
-          if (batchOutliers) {
-            hoc.assign(nb, OutlierChunk{});
-            memset(hoc.data(), 0, nb * sizeof(OutlierChunk));
-            uint64_t maxBits = 0;
-            int maxNbp = 1;
-            for (uint32_t i = 0; i < nb; i++) {
-              const OutHead& oh = outHead[g.second[first + i].slot];
-              if (!oh.has)
-                continue;
-              hoc[i].has = 1;
-              hoc[i].streamOff = oh.off;
-              hoc[i].total_bits = oh.total_bits;
-              hoc[i].nbp = oh.nbp;
-              if (oh.nbp > kMaxPlanes)
-                return -1;
-              maxBits = std::max(maxBits, oh.total_bits);
-              maxNbp = std::max(maxNbp, oh.nbp);
-            }
-            memset(&ob, 0, sizeof(ob));
-            ob.nchunks = nb;
-            ob.N = P->N;
-            ob.nw = (P->N + 63) / 64;
-            ob.wordStride = round_up((size_t)ob.nw + 2, 32);
-            // every value found costs at least its sign bit, every run kept on a list its test bit
-            ob.kStride = round_up((size_t)std::min<uint64_t>(P->N, maxBits) + 1, 64);
-            speck1d_level_offsets(ob, P->N, std::min<uint64_t>(maxBits + 2, 2ull * P->N));
-            ob.streamStride = (size_t)(maxBits / 64) + 4;
-            ob.planeStride = (size_t)maxNbp * ob.wordStride;
-            const size_t bytes = round_up(nb * sizeof(OutlierChunk), 256) +
-                                 (size_t)nb * (ob.wordStride * 16 + ob.kStride * 5 + ob.runStride * 8 +
-                                               ob.streamStride * 8 + ob.planeStride * 8) + 8192;
-            if (E.outlDec[q].ensure(bytes))   // (its own buffer: the sub-batches are enqueued by separate threads)
-              return -1;
-            Arena OA;
-            OA.base = static_cast<char*>(E.outlDec[q].p);
-            OA.cap = E.outlDec[q].n;
-            ob.oc = OA.take<OutlierChunk>(nb);
-            ob.lip = OA.take<uint64_t>(nb * ob.wordStride);
-            ob.lsp = OA.take<uint64_t>(nb * ob.wordStride);
-            ob.runs = OA.take<uint64_t>(nb * ob.runStride);
-            ob.stream = OA.take<uint64_t>(nb * ob.streamStride);
-            ob.planeBits = OA.take<uint64_t>(nb * ob.planeStride);
-            ob.pos = OA.take<uint32_t>(nb * ob.kStride);
-            ob.sgn = OA.take<uint8_t>(nb * ob.kStride);
-            if (!ob.oc || !ob.lip || !ob.lsp || !ob.runs || !ob.stream || !ob.planeBits || !ob.pos || !ob.sgn)
-              return -1;
-            HIP_CHECK(hipMemcpyAsync(ob.oc, hoc.data(), nb * sizeof(OutlierChunk), hipMemcpyHostToDevice, so));
-            HIP_CHECK(hipMemsetAsync(ob.lip, 0, (size_t)nb * ob.wordStride * 16, so));   // lip + lsp
-            if (launch_speck1d_decode(so, ob, d_src))
-              return -1;
-            HIP_CHECK(hipEventRecord(E.evOutl[q], so));
-          }
+};
 
-        }
-        HIP_CHECK(hipMemcpyAsync(bb.geom, S.hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
-        if (box) {   // each chunk's window of the box and its origin relative to the box
-          S.hc.resize(nb);
-          for (uint32_t i = 0; i < nb; i++)
-            for (int a = 0; a < 3; a++) {
-              const size_t o = S.hg[i].org[a], lo = box->lo[a], hi = box->lo[a] + box->dims[a];
-              S.hc[i].rel[a] = (int32_t)((int64_t)o - (int64_t)lo);
-              S.hc[i].lo[a] = (uint32_t)(lo > o ? lo - o : 0);
-              S.hc[i].hi[a] = (uint32_t)std::min<size_t>(hi - o, cd[a]);
-            }
-          HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
-        }
-        HIP_CHECK(hipMemcpyAsync(bb.chunkOff, S.ho.data(), nb * 8, hipMemcpyHostToDevice, ss));
-        HIP_CHECK(hipMemcpyAsync(bb.chunkLen, S.hl.data(), nb * 8, hipMemcpyHostToDevice, ss));
-        HIP_CHECK(hipMemsetAsync(d.cst, 0, nb * sizeof(CoderState), ss));
-        HIP_CHECK(hipMemsetAsync(d.st, 0, nb * sizeof(DecState), ss));
-        DecPlanHost ph{P->d_initLIS, P->d_initLen,
-                       use_tables(*P), P->l0Level >= 0 && P->ht.grids.size() <= 288, P->l1Level >= 0 && P->ht.grids.size() <= 288, P->maxK};
-        ph.skipFinish = true;   // launch_inv_quantize / the dequantising inverse passes complete the coefficients
-        ph.l2 = ph.l1 && P->l2Level >= 0;
-        // the lists of the larger sets GPU-wide
-        ph.hi = use_lis_hi(*P, ph.tables);
-        ph.mixed = use_mixed(*P);
-        ph.mxGroups = mxGroupsCall;
-        if (!ph.tables && !ph.mixed && !(slice && !(P->ht.flags & spk::kTree2D))) {
-          // (a tree neither the table kernels nor k_lis_mx take -- more than 288 / 352 grids or 48 roots: chunks of
-          //  2^30 samples and more -- decodes correctly, through one serial wavefront per chunk: say so, once)
-          static std::atomic<bool> warned{false};
-          if (!warned.exchange(true))
-            fprintf(stderr, "[sperr_hip] note: chunks of %u x %u x %u decode through the serial walk (k_lis_walk): their tree "
-                            "(%zu grids, %zu roots) exceeds what the parallel list kernels hold in LDS -- expect it to be slow\n",
-                    cd[0], cd[1], cd[2], P->ht.grids.size(), P->ht.roots.size());
-        }
-        {
-          static const uint32_t gdivEnv = tune_getenv("SPERR_HIP_MX_GRID_DIV") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_MX_GRID_DIV")) : 4u;
-          ph.gridDiv = (deferStream && mxGroupsCall != 0 && groups.size() >= 4) ? std::max<uint32_t>(1u, gdivEnv) : 1u;
-        }
-        // (the host thread may wait for this stream: it is the call's only one, or has a thread of its own)
-        static const bool liveEnv = !(tune_getenv("SPERR_HIP_LIVE_CHECK") && atoi(tune_getenv("SPERR_HIP_LIVE_CHECK")) == 0);
-        ph.d_live = (liveEnv && !deferStream && (nsub == 1 || threads)) ? bb.live : nullptr;
-        ph.h_live = E.liveHost[q % kSubStreams];
-        ph.liveEv = E.liveEv[q % kSubStreams];
-        // the inverse passes dequantise on the way (not for the resolution hierarchy, whose coarsest
-        // level is read before any pass has run)
-        const bool fuseDq = plan_fusable(*P) && !mr && !slice;
-        // diagnostics: SPERR_HIP_LIS_GPUWIDE=0 leaves every list to k_lis_hi
-        static const bool gpuWide = !(getenv("SPERR_HIP_LIS_GPUWIDE") && atoi(getenv("SPERR_HIP_LIS_GPUWIDE")) == 0);
-        if (!gpuWide)
-          ph.l0 = ph.l1 = ph.l2 = false;
-        HIP_CHECK(hipMemsetAsync(d.mask, 0, std::max<size_t>(d.maskStride, 1) * nb * 8, ss));
-        HIP_CHECK(hipMemsetAsync(d.l0Flags, 0, d.l0FlagStride * nb * 8, ss));
-        if (d.l0Tab)
-          HIP_CHECK(hipMemsetAsync(d.l0Tab, 0, d.l0FlagStride * 17 * nb * 8, ss));
-        HIP_CHECK(hipMemsetAsync(d.l1Flags, 0, d.l0FlagStride * nb * 8, ss));
-        HIP_CHECK(hipMemsetAsync(d.l2Flags, 0, d.l0FlagStride * nb * 8, ss));
-        HIP_CHECK(hipMemsetAsync(d.hiFlags, 0, d.hiFlagStride * nb * 8, ss));
-        HIP_CHECK(hipMemsetAsync(d.sigbits, 0, d.sigbitsStride * nb * 8, ss));
-        if (d.lisStamps)
-          HIP_CHECK(hipMemsetAsync(d.lisStamps, 0, 64 * 8 * nb, ss));
-        // 64-bit chunks first: their magnitudes are decoded into (and converted inside) the fp64
-        // buffer, which the 32-bit pass then fills for the remaining chunks
-        for (int wide = 1; wide >= 0; wide--) {
-          if (wide && maxWide == 0)
-            continue;
-          HIP_CHECK(hipMemsetAsync(d.bornM, 0, d.maskPixStride * nb * 8, ss));
-          if (d.tileBorn)
-            HIP_CHECK(hipMemsetAsync(d.tileBorn, 0, d.tileStride * nb, ss));
-          HIP_CHECK(hipMemsetAsync(d.sigOld, 0, d.maskPixStride * nb * 8, ss));
-          HIP_CHECK(hipMemsetAsync(d.sigNew, 0, d.maskPixStride * nb * 8, ss));
-          HIP_CHECK(hipMemsetAsync(d.sign, 0xff, d.signStride * nb * 8, ss));
-          HIP_CHECK(hipMemsetAsync(d.leafState, 0, d.leafStateStride * nb * 2, ss));
-          HIP_CHECK(hipMemsetAsync(d.leafDirty, 0, d.leafDirtyStride * nb, ss));
-          HIP_CHECK(hipMemsetAsync(d.stream, 0, d.streamStride * nb * 8, ss));
-          DecBuffers dw = d;
-          if (wide) {  // 64-bit magnitudes live in the fp64 buffer, converted in place afterwards
-            dw.coef = bb.vals;
-            dw.coefStride = bb.valsStride;
-            dw.refPlanes = nullptr;
-            HIP_CHECK(hipMemsetAsync(bb.vals, 0, bb.valsStride * nb * 8, ss));
-          }
-          else if (d.refPlanes) { // (k_ref_assemble writes every coefficient; a plane's words are valid from wordTop down)
-            HIP_CHECK(hipMemsetAsync(d.wordTop, 0, d.wordTopStride * nb, ss));
-            dw.coefSigned = fuseDq ? 1u : 0u;   // (read by the dequantising inverse passes only: LiftFuse::coefSigned)
-          }
-          else
-            HIP_CHECK(hipMemsetAsync(bb.coef32, 0, d.coefStride * nb * 4, ss));
-          if (slice && !(P->ht.flags & spk::kTree2D)) {   // header + stream words by the 3D launcher (no planes), then the 2D coder
-            DecPlanHost ph2 = ph;
-            ph2.tables = ph2.l0 = ph2.l1 = ph2.mixed = false;
-            Speck2dBufs sb;
-            if (launch_speck_decode(ss, dw, ph2, d_src, bb.chunkOff, bb.chunkLen, wide != 0, 0) ||
-                carve_slice2d(E, *P, sb))
-              return -1;
-            sb.coef = dw.coef;
-            sb.sign = d.sign;
-            sb.stream = d.stream;
-            sb.streamWords = d.streamStride;
-            sb.cst = d.cst;
-            sb.dst = d.st;
-            if (launch_speck2d_decode(ss, sb, wide != 0) ||
-                launch_inv_quantize(ss, wide != 0, dw.coef, dw.coefStride, d.sign, d.signStride, nb,
-                                    P->N, bb.vals, bb.valsStride, d.cst))
-              return -1;
-            continue;
-          }
-          // the header kernel must run even when no plane does (constant / all-zero chunks)
-          if (launch_speck_decode(ss, dw, ph, d_src, bb.chunkOff, bb.chunkLen, wide != 0,
-                                  wide ? maxWide : maxNarrow))
-            return -1;
-          // (32-bit coefficients are dequantised by the inverse passes as they load them, LiftFuse)
-          if ((wide || !fuseDq) &&
-              launch_inv_quantize(ss, wide != 0, dw.coef, dw.coefStride, d.sign, d.signStride, nb,
-                                  P->N, bb.vals, bb.valsStride, d.cst, d.sigNew, d.sigOld,
-                                  d.maskPixStride, d.st))
-            return -1;
-        }
-        // the last inverse pass covers the whole chunk: it adds the mean, narrows and scatters --
-        // unless outlier correctors have to be added to the transformed values first
-        // (src/SPECK_FLT.cpp:573-590), in which case every pass stays in the chunk buffer
-        const bool fxyz = fuse_xyz(*P) && !batchOutliers;
-        const bool fxy = fuse_xy(*P) && !batchOutliers && !fxyz;
-        // With outlier correctors the transformed values have to stay doubles a little longer -- but they can still
-        // come from the fused kernels (round 5): the coarser levels in a compact buffer of their box, the finest level
-        // by k_lift_xyz_inv writing doubles, no mean added, into the chunk buffer as if it were a volume of bricks (a
-        // chunk's offset rides in org[0]); the correctors and the scatter pass follow as before.  (Fifteen per-axis
-        // passes over the whole chunk before: 12.7 ms for 64 chunks of 256^3.)
-        static const bool brickEnv = !(tune_getenv("SPERR_HIP_PWE_FUSED_INV") && atoi(tune_getenv("SPERR_HIP_PWE_FUSED_INV")) == 0);
-        const bool fbrick = brickEnv && batchOutliers && fuse_xyz(*P) && fuseDq && maxWide == 0 && P->fwd.size() >= 3 &&
-                            compactElems == 0 && (uint64_t)nb * bb.valsStride <= 0xffffffffull;
-        uint32_t bbox[3] = {1, 1, 1};
-        double* boxVals = nullptr;
-        size_t boxStride = 0;
-        ChunkGeom* d_bricks = nullptr;
-        std::vector<ChunkGeom> bricks;   // (lives until the wait for the stream below: batchOutliers)
-        if (fbrick) {
-          for (size_t k = 3; k < P->fwd.size(); k++)
-            for (int a = 0; a < 3; a++)
-              bbox[a] = std::max(bbox[a], P->fwd[k].region[a]);
-          boxStride = round_up((size_t)bbox[0] * bbox[1] * bbox[2], 64);
-          const size_t geomOff = round_up((size_t)nb * boxStride * 8, 256);
-          if (E.decBox[q].ensure(geomOff + (size_t)nb * sizeof(ChunkGeom) + 256))
-            return -1;
-          boxVals = static_cast<double*>(E.decBox[q].p);
-          d_bricks = reinterpret_cast<ChunkGeom*>(static_cast<char*>(E.decBox[q].p) + geomOff);
-          bricks.resize(nb);
-          for (uint32_t i = 0; i < nb; i++) {
-            bricks[i].org[0] = (uint32_t)((size_t)i * bb.valsStride);
-            bricks[i].org[1] = bricks[i].org[2] = 0;
-          }
-          HIP_CHECK(hipMemcpyAsync(d_bricks, bricks.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
-        }
-        // a level of the inverse transform is 3 passes (z y x) of a dyadic chunk, 2 (y x) of a slice
-        const size_t perLevel = slice ? 2 : 3;
-        auto sub_volume = [&](size_t k) -> int {   // before pass k, the first of its level
-          const size_t h = mr->nlev - (k / perLevel + 1);
-          const auto& r = mr->cres[h];
-          const uint32_t blocks = capped_blocks((r[0] * r[1] * r[2] + kThreads - 1) / kThreads, nb);
-          LAUNCH_K(k_sub_volume, dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride,
-                   d.cst, bb.geom, cd[0], cd[1], cd[0], cd[1], cd[2], r[0], r[1], r[2],
-                   mr->grid[0], mr->grid[1], mr->d_level[h]);
-          return 0;
-        };
-        auto dequant_fuse = [&](size_t k, LiftFuse& lf) {
-          if (fuseDq && pass_fuse(*P, k, lf.inner) > 0) {
-            lf.mode = 2;
-            lf.coef = bb.coef32;
-            lf.coefStride = d.coefStride;
-            lf.sign = d.sign;
-            lf.signStride = d.signStride;
-            lf.sigNew = d.sigNew;
-            lf.sigOld = d.sigOld;
-            lf.maskStride = d.maskPixStride;
-            lf.dst = d.st;
-            lf.coefSigned = d.refPlanes ? 1 : 0;
-          }
-          if (compactElems) {
-            lf.bufx = cbox[0];
-            lf.bufy = cbox[1];
-          }
-          if (fbrick) {
-            lf.bufx = bbox[0];
-            lf.bufy = bbox[1];
-          }
-        };
-        for (size_t k = P->fwd.size(); k-- > ((fxyz || fbrick) ? 3u : fxy ? 2u : 0u);) {
-          const LiftPass& ps = P->fwd[k];
-          if (mr && mr->nlev && k % perLevel == perLevel - 1 && sub_volume(k))
-            return -1;
-          LiftFuse lf;
-          dequant_fuse(k, lf);
-          const bool last = k == 0 && !batchOutliers;   // (the pass that writes the volume / the box)
-          if (launch_lift(ss, false, fbrick ? boxVals : bb.vals, fbrick ? boxStride : bb.valsStride, nb, cd, ps.axis,
-                          ps.region, d.cst, last ? (std::is_same<T, float>::value ? 1 : 2) : 0,
-                          d_dst, vd, bb.geom, &lf, last ? bb.crop : nullptr))
-            return -1;
-        }
-        if (fbrick) {   // the finest level into the chunk buffer, as doubles
-          LiftFuse lf;
-          dequant_fuse(2, lf);
-          lf.noMean = 1;
-          const VolDesc brickVol{{cd[0], cd[1], cd[2]}};
-          if (launch_lift_xyz(ss, false, boxVals, boxStride, nb, cd, d.cst, 2, bb.vals, brickVol, d_bricks, &lf))
-            return -1;
-        }
-        if (fxyz) {   // the finest level: z, y and x pass in one kernel, into the volume
-          if (mr && mr->nlev && sub_volume(2))
-            return -1;
-          LiftFuse lf;
-          dequant_fuse(2, lf);
-          if (launch_lift_xyz(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst, std::is_same<T, float>::value ? 1 : 2,
-                              d_dst, vd, bb.geom, &lf, bb.crop))
-            return -1;
-        }
-        if (fxy && mr && mr->nlev && slice && sub_volume(1))   // the finest level of a slice is the fused pair
-          return -1;
-        if (fxy && launch_lift_xy(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst,
-                                  std::is_same<T, float>::value ? 1 : 2, d_dst, vd, bb.geom, bb.crop))
-          return -1;
-        if (batchOutliers) {   // the correctors of the values the 1D decoder found meanwhile
-          HIP_CHECK(hipStreamWaitEvent(ss, E.evOutl[q], 0));
-          if (launch_outlier_apply(ss, ob, d.cst, bb.vals, bb.valsStride))
-            return -1;
-          HIP_CHECK(hipMemcpyAsync(hoc.data(), ob.oc, nb * sizeof(OutlierChunk), hipMemcpyDeviceToHost, ss));
-          HIP_CHECK(hipStreamSynchronize(ss));
-          for (auto& o : hoc)
-            if (o.error) {
-              fprintf(stderr, "[sperr_hip] outlier decoder failed (code %u)\n", o.error);
-              return -1;
-            }
-        }
-        if ((P->fwd.empty() || batchOutliers) &&
-            launch_scatter<T>(ss, d_dst, vd, bb.geom, nb, cd, bb.vals, bb.valsStride, d.cst, bb.crop))
-          return -1;
-        if (nsub > 1)
-          HIP_CHECK(hipEventRecord(E.evJoin[q], ss));
-        return 0;
-      };
-      if (nsub == 1) {
-        static const bool enqTiming = getenv("SPERR_HIP_ENQ_TIMING") != nullptr;
-        const auto tq0 = std::chrono::steady_clock::now();
-        if (enqueue(0))
-          return -1;
-        if (enqTiming) {
-          fprintf(stderr, "[sperr_hip] group %u x %u x %u, %u chunks: enqueued in %.2f ms\n", cd[0], cd[1], cd[2], nbAll,
-                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count());
-          // (diagnostics: when the group's stream is through, measured from the caller's stream at the fork)
-          hipEvent_t evEnd = nullptr;
-          if (deferStream && hipEventCreate(&evEnd) == hipSuccess) {
-            if (!timingFork && hipEventCreate(&timingFork) == hipSuccess)
-              (void)hipEventRecord(timingFork, st);
-            (void)hipEventRecord(evEnd, deferStream);
-            timingEnds.push_back({evEnd, {cd[0], cd[1], cd[2], nbAll}});
-          }
-        }
-        if (deferG) {   // waited for in drain()
-          pending.push_back(std::make_unique<SubHost>(std::move(subs[0])));
-          continue;
-        }
-      }
-      else {
-        // one host thread per sub-batch (SPERR_HIP_ENQUEUE_THREADS=0: one thread for all): by itself no
-        // gain on MI355X, but a thread of its own may wait for its stream, which lets the launcher
-        // stop at the plane where the chunks run out of bits (DecPlanHost::d_live)
-        std::vector<int> rc(nsub, 0);
-        if (threads) {
-          std::vector<std::thread> workers;
-          for (uint32_t q = 0; q < nsub; q++)
-            workers.emplace_back([&, q]() { rc[q] = enqueue(q); });
-          for (auto& w : workers)
-            w.join();
-        }
-        else
-          for (uint32_t q = 0; q < nsub; q++)
-            rc[q] = enqueue(q);
-        for (uint32_t q = 0; q < nsub; q++) {
-          if (rc[q])
-            return -1;
-          if (subs[q].nb)
-            HIP_CHECK(hipStreamWaitEvent(st, E.evJoin[q], 0));
-        }
-      }
-      // read-backs only after every sub-batch is enqueued: a device-to-host copy into pageable
-      // memory blocks the host until its stream has drained
-      for (uint32_t q = 0; q < nsub; q++) {
-        SubHost& S = subs[q];
-        if (S.nb == 0)
-          continue;
-        hipStream_t ss = nsub > 1 ? E.sub[q] : st;
-        if (S.bb.db.lisStamps && q == 0) {
-          g_lis_stamps_host.assign(64, 0);
-          // (SPERR_HIP_STAMP_CHUNK=i: the counters of the batch's i-th chunk instead of the first)
-          const uint32_t sc = getenv("SPERR_HIP_STAMP_CHUNK")
-                                  ? std::min<uint32_t>(S.nb - 1, (uint32_t)atoi(getenv("SPERR_HIP_STAMP_CHUNK")))
-                                  : 0u;
-          HIP_CHECK(hipMemcpyAsync(g_lis_stamps_host.data(), S.bb.db.lisStamps + (size_t)sc * 64, 64 * 8,
-                                   hipMemcpyDeviceToHost, ss));
-        }
-        S.hs.resize(S.nb);   // stream errors (wrong lengths) surface here
-        HIP_CHECK(hipMemcpyAsync(S.hs.data(), S.bb.db.st, S.nb * sizeof(DecState),
-                                 hipMemcpyDeviceToHost, ss));
-      }
-      HIP_CHECK(hipStreamSynchronize(st));
-      if (nsub > 1)
-        for (uint32_t q = 0; q < nsub; q++)
-          HIP_CHECK(hipStreamSynchronize(E.sub[q]));
-      for (auto& S : subs)
-        for (auto& hsx : S.hs)
-          if (hsx.error) {
-            report_dec_error(hsx.error);
-            return -1;
-          }
-    }
-  }
-  if (drain())
-    return -1;
-  HIP_CHECK(hipStreamSynchronize(st));
-  HIP_CHECK(hipGetLastError());
-  E.prof.collect();
-  drainGuard.ok = true;
-  return 0;
+template <typename T>
+int decompress_impl(Engine& E, const uint8_t* d_src, size_t /*src_len*/, T* d_dst, size_t dst_cap_vals,
+                    const ContainerInfo& ci, hipStream_t st, const MultiRes* mr = nullptr,
+                    bool slice = false, const BoxSel* box = nullptr)
+{
+  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box};
+  return call.run(dst_cap_vals);
 }
 
 
@@ -4101,15 +4113,8 @@ int sperrhip_speck3d_decode_dev(const void* d_stream, size_t stream_len, size_t 
     uint8_t* wrap = static_cast<uint8_t*>(E.misc.p);
     LAUNCH_K(k_fake_condi_header, dim3(1), dim3(1), 0, st, wrap);
     HIP_CHECK(hipMemcpyAsync(wrap + 17, d_stream, stream_len, hipMemcpyDeviceToDevice, st));
-    Arena probe;
-    probe.base = reinterpret_cast<char*>(uintptr_t(4096));  // size probe only
-    probe.cap = ~size_t(0) / 2;
-    DecBatchBufs tmp;
-    // (refinement bit planes like decompress_impl's: SPERR_HIP_REF_PLANES=0 switches them off)
-    static const bool refPlanesEnv = !(tune_getenv("SPERR_HIP_REF_PLANES") && atoi(tune_getenv("SPERR_HIP_REF_PLANES")) == 0);
-    const uint32_t refNPlanes = (refPlanesEnv && !wide) ? (uint32_t)nbp : 0u;
-    carve_dec(probe, *P, 1, 17 + stream_len, tmp, 0, refNPlanes);
-    if (E.arena.ensure(probe.used + 4096))
+    const uint32_t refNPlanes = !wide ? (uint32_t)nbp : 0u;   // (refinement bit planes like decompress_impl's)
+    if (E.arena.ensure(dec_bytes_per_chunk(*P, 17 + stream_len, 0, refNPlanes, false) + 4096))
       return -1;
     Arena A;
     A.base = static_cast<char*>(E.arena.p);
@@ -4142,15 +4147,10 @@ int sperrhip_speck3d_decode_dev(const void* d_stream, size_t stream_len, size_t 
       HIP_CHECK(hipMemsetAsync(d.wordTop, 0, d.wordTopStride, st));
     else
       HIP_CHECK(hipMemsetAsync(bb.coef32, 0, (size_t)n * 4, st));
-    DecPlanHost ph{P->d_initLIS, P->d_initLen, use_tables(*P),
-                   P->l0Level >= 0 && P->ht.grids.size() <= 288, P->l1Level >= 0 && P->ht.grids.size() <= 288, P->maxK};
-    ph.l2 = ph.l1 && P->l2Level >= 0;
-    ph.hi = use_lis_hi(*P, ph.tables);
-    ph.mixed = use_mixed(*P);
+    const DecPlanHost ph = dec_plan_host(*P);
     HIP_CHECK(hipMemsetAsync(d.mask, 0, std::max<size_t>(d.maskStride, 1) * 8, st));
     HIP_CHECK(hipMemsetAsync(d.l0Flags, 0, d.l0FlagStride * 8, st));
-    if (d.l0Tab)
-      HIP_CHECK(hipMemsetAsync(d.l0Tab, 0, d.l0FlagStride * 17 * 8, st));
+    HIP_CHECK(hipMemsetAsync(d.l0Tab, 0, d.l0FlagStride * 17 * 8, st));
     HIP_CHECK(hipMemsetAsync(d.l1Flags, 0, d.l0FlagStride * 8, st));
     HIP_CHECK(hipMemsetAsync(d.l2Flags, 0, d.l0FlagStride * 8, st));
     HIP_CHECK(hipMemsetAsync(d.hiFlags, 0, d.hiFlagStride * 8, st));

@@ -2001,8 +2001,7 @@ int launch_lift_xy(hipStream_t stream, bool forward, double* vals, size_t valsSt
 
 bool lift_xyz_applicable(const uint32_t cdims[3])
 {
-  static const bool on = !(tune_getenv("SPERR_HIP_LIFT_XYZ") && atoi(tune_getenv("SPERR_HIP_LIFT_XYZ")) == 0);
-  if (!on || cdims[0] < 9 || cdims[1] < 9 || cdims[2] < 9)
+  if (cdims[0] < 9 || cdims[1] < 9 || cdims[2] < 9)
     return false;
   // a thread's z pipelines are registers: (rows + halo) * cx positions over the workgroup's threads
   // (and the packed staging map holds 12 bits of x, 15 bits of y)

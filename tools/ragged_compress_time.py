@@ -1,5 +1,5 @@
-"""Compress time of a volume the chunk size does not divide (shape groups side by side or one after the
-other: SPERR_HIP_ENC_GROUPS=0): python tools/ragged_compress_time.py [edge] [chunk]"""
+"""Compress time of a volume the chunk size does not divide (shape groups side by side):
+python tools/ragged_compress_time.py [edge] [chunk]"""
 import os
 import sys
 import time
