@@ -16,7 +16,9 @@
  *    is what bench.py times and what an application that already holds its field on the GPU
  *    should call.  All pointers marked `d_` are device pointers; `hip_stream` is a hipStream_t
  *    passed as void* (NULL = the default stream).  Calls are synchronous with respect to the
- *    host when they return.
+ *    host when they return.  Many small volumes of one shape that each want a container go
+ *    through the batch calls (sperrhip_compress_batch_dev / sperrhip_decompress_batch_dev): one
+ *    call for all of them, the same containers as one call per volume.
  *
  * There is no CPU fallback: every entry point returns -1 (and prints the HIP error) when no
  * gfx950 device or kernel image is available.
@@ -233,6 +235,32 @@ int sperrhip_decompress_box_dev(const void* d_src, size_t src_len, int output_fl
  * 1 *dst not NULL, -1 error. */
 int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float,
                            const size_t box_lo[3], const size_t box_dims[3], void** dst);
+
+/* ---- a batch of same-shape volumes, one container each ----------------------------------------- */
+/* N volumes of the same dims in one call: the chunks of every volume are coded together (a batch is
+ * more chunks for the same shape groups), and each volume gets a container of its own.  Container v
+ * is byte for byte what sperrhip_compress_dev makes of volume v alone, and volume v of a batch decode
+ * is bit for bit sperrhip_decompress_dev of container v.  Chunk origins of the batch, read as one
+ * volume of dims (x, y, nvol * z), are 32-bit: nvol * dimz and the batch's chunk count must not
+ * exceed 2^32 - 1.  The batch calls return -1 for nvol == 0, a zero dim, a NULL pointer, an output
+ * that is too small, decreasing offsets, a container sperrhip_decompress_dev would refuse, or
+ * containers whose volume dims differ; a refusal found before decoding starts leaves d_dst as it
+ * was, and compression never writes past dst_cap. */
+/* Upper bound for sperrhip_compress_batch_dev: nvol times the single-volume bound; 0 if that overflows size_t. */
+size_t sperrhip_max_compressed_size_batch(size_t nvol, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                                          size_t chunk_y, size_t chunk_z, int mode, double quality);
+/* nvol volumes back to back in d_src; volume v starts at element v*dimx*dimy*dimz, x fastest.
+ * Writes nvol containers back to back into d_dst.  offsets (host, nvol + 1 entries) receives the byte ranges:
+ * container v is [offsets[v], offsets[v+1]).  Return codes as sperrhip_compress_dev. */
+int sperrhip_compress_batch_dev(const void* d_src, int is_float, size_t nvol, size_t dimx, size_t dimy, size_t dimz,
+                                size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
+                                void* d_dst, size_t dst_cap, size_t* offsets, void* hip_stream);
+/* nvol containers back to back in d_src, container v at [offsets[v], offsets[v+1]) (host array).  All of them
+ * must describe the same volume dims.  Chunk dims, mode, rate, truncation and is_float may differ.  d_dst receives
+ * nvol volumes back to back (float or double).  *dimx..*dimz receive the shared dims.  Returns 0 ok, -1 error. */
+int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, int output_float,
+                                  void* d_dst, size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
+                                  void* hip_stream);
 
 /* ---- profiling ------------------------------------------------------------------------------ */
 

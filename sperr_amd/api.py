@@ -34,6 +34,7 @@ EXPORTS = [
     "sperrhip_numa_probe", "sperrhip_numa_bind_self", "sperrhip_farm_device_place",
     "sperrhip_host_cpus", "sperrhip_host_throttle", "sperrhip_farm_threads",
     "sperrhip_box_chunks", "sperrhip_decompress_box_dev", "sperrhip_decomp_3d_box",
+    "sperrhip_max_compressed_size_batch", "sperrhip_compress_batch_dev", "sperrhip_decompress_batch_dev",
 ]
 
 
@@ -108,6 +109,14 @@ def load_library():
     lib.sperrhip_decompress_dev.restype = C.c_int
     lib.sperrhip_decompress_dev.argtypes = [_vp, _sz, C.c_int, _vp, _sz, C.POINTER(_sz),
                                             C.POINTER(_sz), C.POINTER(_sz), _vp]
+    lib.sperrhip_max_compressed_size_batch.restype = _sz
+    lib.sperrhip_max_compressed_size_batch.argtypes = [_sz] * 7 + [C.c_int, C.c_double]
+    lib.sperrhip_compress_batch_dev.restype = C.c_int
+    lib.sperrhip_compress_batch_dev.argtypes = [_vp, C.c_int] + [_sz] * 7 + [C.c_int, C.c_double, _vp, _sz,
+                                                                             C.POINTER(_sz), _vp]
+    lib.sperrhip_decompress_batch_dev.restype = C.c_int
+    lib.sperrhip_decompress_batch_dev.argtypes = [_vp, C.POINTER(_sz), _sz, C.c_int, _vp, _sz] + \
+        [C.POINTER(_sz)] * 3 + [_vp]
     lib.sperrhip_box_chunks.restype = C.c_int
     lib.sperrhip_box_chunks.argtypes = [_sz] * 6 + [C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint32), _sz,
                                                     C.POINTER(_sz)]
@@ -231,6 +240,59 @@ class SperrHip:
                                                    out.numel() * out.element_size(), self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decompress_box_dev returned {rtn}")
+        return out
+
+    def max_compressed_size_batch(self, nvol, shape_zyx, chunks_xyz, quality, mode=1):
+        dz, dy, dx = shape_zyx
+        return self.lib.sperrhip_max_compressed_size_batch(nvol, dx, dy, dz, *chunks_xyz, mode, quality)
+
+    def compress_batch(self, vols, chunks_xyz, quality, mode=1, out=None):
+        """vols: contiguous cuda tensor float32/float64 shaped (N, z, y, x).  Returns N cuda uint8 tensors, views into
+        one buffer (`out` when it is large enough) in order: container v is what compress() makes of vols[v]."""
+        torch = self.torch
+        assert vols.is_cuda and vols.is_contiguous() and vols.dim() == 4
+        assert vols.dtype in (torch.float32, torch.float64)
+        nvol, dz, dy, dx = vols.shape
+        cap = self.max_compressed_size_batch(nvol, vols.shape[1:], chunks_xyz, quality, mode)
+        if cap == 0:
+            raise SperrHipError("sperrhip_max_compressed_size_batch overflows")
+        if out is None or out.numel() < cap:
+            out = torch.empty(cap, dtype=torch.uint8, device=vols.device)
+        offs = (_sz * (nvol + 1))()
+        rtn = self.lib.sperrhip_compress_batch_dev(vols.data_ptr(), int(vols.dtype == torch.float32), nvol, dx, dy,
+                                                   dz, *chunks_xyz, mode, float(quality), out.data_ptr(),
+                                                   out.numel(), offs, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_batch_dev returned {rtn}")
+        return [out[offs[v]:offs[v + 1]] for v in range(nvol)]
+
+    def decompress_batch(self, containers, output_float=True, out=None):
+        """containers: a list of cuda uint8 tensors (compress_batch's views, or any), each a container of a volume of
+        the same dims.  They are concatenated first unless they already lie back to back in one buffer.  Returns a
+        cuda tensor shaped (N, z, y, x) -- `out` when given."""
+        torch = self.torch
+        assert len(containers) > 0
+        for c in containers:
+            assert c.is_cuda and c.dtype == torch.uint8 and c.dim() == 1 and c.is_contiguous()
+        nvol = len(containers)
+        packed = all(b.data_ptr() == a.data_ptr() + a.numel() and
+                     b.untyped_storage().data_ptr() == a.untyped_storage().data_ptr()
+                     for a, b in zip(containers, containers[1:]))
+        src = containers[0] if packed else torch.cat(list(containers))
+        offs = (_sz * (nvol + 1))()
+        for v, c in enumerate(containers):
+            offs[v + 1] = offs[v] + c.numel()
+        shape_zyx, _, _ = self.parse_header(src[:offs[1]])
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            out = torch.empty((nvol,) + tuple(shape_zyx), dtype=dt, device=src.device)
+        assert out.dtype == dt and out.is_contiguous() and out.is_cuda
+        dx, dy, dz = _sz(0), _sz(0), _sz(0)
+        rtn = self.lib.sperrhip_decompress_batch_dev(src.data_ptr(), offs, nvol, int(output_float), out.data_ptr(),
+                                                     out.numel() * out.element_size(), C.byref(dx), C.byref(dy),
+                                                     C.byref(dz), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_batch_dev returned {rtn}")
         return out
 
     # ---- stage access ----------------------------------------------------------------------

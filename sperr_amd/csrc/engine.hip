@@ -916,6 +916,91 @@ __global__ void k_container_header(uint8_t* dst, const uint64_t* lens, const uin
   *total = off;
 }
 
+// The containers of a batch of nvol volumes of one shape (sperrhip_compress_batch_dev), back to back: container v
+// holds chunks [v cpv, (v + 1) cpv), and every container has the same header of H = 14 | 20 + 4 cpv bytes, so chunk g
+// of container v starts at (v + 1) H + the bytes (SPECK + outlier) of the chunks before g, and container v at its
+// first chunk's offset minus H.  One workgroup: an exclusive scan of the batch's chunk lengths in tiles of
+// kBatchThreads (wave64 shuffles, then the waves' sums), then every header and chunk-length table.  Writes past
+// dst_cap are dropped (the host refuses the batch then).  bases[0..nvol]: each container's start, then the total
+constexpr uint32_t kBatchThreads = 1024;
+__global__ void __launch_bounds__(kBatchThreads)
+k_batch_container(uint8_t* dst, uint64_t dst_cap, const uint64_t* lens, const uint64_t* lens2, uint64_t* offs,
+                  uint32_t nchunks, uint32_t cpv, uint32_t vx, uint32_t vy, uint32_t vz, uint32_t cx, uint32_t cy,
+                  uint32_t cz, int is_float, uint64_t* bases)
+{
+  __shared__ uint64_t waveSum[kBatchThreads / 64];
+  __shared__ uint64_t carry;
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const bool multi = cpv > 1;
+  const uint32_t pos = multi ? 20u : 14u;
+  const uint64_t H = pos + 4ull * cpv;
+  const uint32_t nvol = nchunks / cpv;
+  if (t == 0)
+    carry = 0;
+  __syncthreads();
+  for (uint32_t t0 = 0; t0 < nchunks; t0 += kBatchThreads) {
+    const uint32_t g = t0 + t;
+    const uint64_t both = g < nchunks ? lens[g] + lens2[g] : 0;
+    uint64_t x = both;   // inclusive scan of the wavefront
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t y = __shfl_up(x, d, 64);
+      if (lane >= (uint32_t)d)
+        x += y;
+    }
+    if (lane == 63)
+      waveSum[w] = x;
+    __syncthreads();
+    uint64_t before = carry;
+    for (uint32_t i = 0; i < w; i++)
+      before += waveSum[i];
+    if (g < nchunks) {
+      const uint32_t v = g / cpv;
+      const uint64_t at = (uint64_t)(v + 1) * H + before + x - both;
+      offs[g] = at;
+      if (g == v * cpv)
+        bases[v] = at - H;
+    }
+    __syncthreads();   // (everyone has read carry and waveSum)
+    if (t == kBatchThreads - 1)
+      carry = before + x;
+    __syncthreads();
+  }
+  if (t == 0)
+    bases[nvol] = (uint64_t)nvol * H + carry;
+  __syncthreads();   // (bases[] of this workgroup's writes are read below)
+  for (uint32_t g = t; g < nchunks; g += kBatchThreads) {
+    const uint32_t v = g / cpv;
+    const uint64_t at = bases[v] + pos + 4ull * (g - v * cpv);
+    const uint32_t l = (uint32_t)(lens[g] + lens2[g]);
+    if (at + 4 <= dst_cap)
+      memcpy(dst + at, &l, 4);
+  }
+  for (uint32_t v = t; v < nvol; v += kBatchThreads) {   // k_container_header's bytes
+    uint8_t* h = dst + bases[v];
+    if (bases[v] + pos > dst_cap)
+      continue;
+    h[0] = 0;
+    h[1] = (uint8_t)(0x40 | (is_float ? 0x20 : 0) | (multi ? 0x10 : 0));
+    const uint32_t v3[3] = {vx, vy, vz};
+    memcpy(h + 2, v3, 12);
+    if (multi) {
+      const uint16_t c3[3] = {(uint16_t)cx, (uint16_t)cy, (uint16_t)cz};
+      memcpy(h + 14, c3, 6);
+    }
+  }
+}
+
+// bytes [srcOff[i], srcOff[i] + len[i]) of every container of a batch, packed at dstOff[i] (the full headers,
+// sperrhip_decompress_batch_dev)
+__global__ void __launch_bounds__(kThreads)
+k_gather_bytes(const uint8_t* src, const uint64_t* srcOff, const uint64_t* len, const uint64_t* dstOff, uint8_t* dst,
+               uint32_t n)
+{
+  for (uint32_t i = blockIdx.y; i < n; i += gridDim.y)
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < len[i]; k += (uint64_t)gridDim.x * blockDim.x)
+      dst[dstOff[i] + k] = src[srcOff[i] + k];
+}
+
 __global__ void __launch_bounds__(kThreads)
 k_copy_slots(uint8_t* dst, uint64_t dst_cap, const uint8_t* slots, const uint64_t* slotOff,
              const uint64_t* lens, const uint64_t* offs, uint32_t nchunks)
@@ -1770,9 +1855,12 @@ struct EncodeCall {
   size_t dst_cap;
   hipStream_t st;
   const int slice;
+  // a batch (sperrhip_compress_batch_dev): nvol volumes of dims `vol` back to back in d_src, read as one volume of
+  // (x, y, nvol z) -- the stacked view -- whose chunks are each volume's, and coded into nvol containers
+  const size_t nvol = 1;
   const bool rate = mode == 1;
   const double bpp = rate ? quality : 0.0;
-  const VolDesc vd{{vol[0], vol[1], vol[2]}};
+  const VolDesc vd{{vol[0], vol[1], vol[2] * nvol}};
   Dims cdim;
   uint32_t nchunks = 0;
   std::map<GKey, std::vector<ChunkRef>> groups;
@@ -1787,6 +1875,7 @@ struct EncodeCall {
   std::deque<std::vector<CoderState>> hcKeep;   // chunk states of PSNR / PWE setups (one host thread: no lock)
   std::deque<PweStage> pweStages;
   uint64_t total = 0;
+  std::vector<uint64_t> bases;   // (a batch: where each container starts, then the total)
   bool ok = false;
   ~EncodeCall() { if (!ok) drain_after_error(E, st); }
   // (a slice is coded on the 2D coder's forest, the plan with z extent 0; SPERR_HIP_SLICE_MIXED=0: k_speck2d's walk)
@@ -1795,11 +1884,23 @@ struct EncodeCall {
   {
     for (int a = 0; a < 3; a++)  // SPERR3D_OMP_C.cpp:23-30
       cdim[a] = std::min(std::max<size_t>(1, chunkPref[a]), vol[a]);
-    const auto chunks = chunk_volume(vol, cdim);
-    nchunks = (uint32_t)chunks.size();
+    auto chunks = chunk_volume(vol, cdim);
     for (int a = 0; a < 3; a++)
       if (vol[a] > 0xffffffffull || cdim[a] > 0xffff)
         return -1;
+    if (nvol > 1) {   // (each volume's own chunks, z origins shifted: the tall volume's remainders would differ)
+      const size_t per = chunks.size();
+      if (nvol > 0xffffffffull / vol[2] || per > 0xffffffffull / nvol)
+        return -1;
+      chunks.reserve(per * nvol);
+      for (size_t v = 1; v < nvol; v++)
+        for (size_t i = 0; i < per; i++) {
+          auto c = chunks[i];
+          c[4] += v * vol[2];
+          chunks.push_back(c);
+        }
+    }
+    nchunks = (uint32_t)chunks.size();
     group_chunks(chunks);
     if (size_slots() || plan_side_by_side())
       return -1;
@@ -1857,7 +1958,7 @@ struct EncodeCall {
       slotOff[i + 1] = slotOff[i] + slotLen[i];
     if (E.slots.ensure(slotOff[nchunks] + 256))
       return -1;
-    if (E.misc.ensure(round_up((size_t)nchunks * 8, 256) * 4 + 256))
+    if (E.misc.ensure(round_up((size_t)nchunks * 8, 256) * 4 + round_up((nvol + 1) * 8, 256)))
       return -1;
     d_slotOff = reinterpret_cast<uint64_t*>(E.misc.p);
     d_lens = d_slotOff + round_up(nchunks, 32);
@@ -2147,11 +2248,16 @@ struct EncodeCall {
   int container()
   {
     // (the header kernels write before any length is known to them: check its room here)
-    if (dst_cap < (slice ? (slice == 2 ? 10u : 0u) : (nchunks > 1 ? 20u : 14u) + 4ull * nchunks)) {
+    const uint32_t cpv = (uint32_t)(nchunks / nvol);   // chunks per container
+    if (dst_cap < (slice ? (slice == 2 ? 10u : 0u) : ((cpv > 1 ? 20u : 14u) + 4ull * cpv) * nvol)) {
       fprintf(stderr, "[sperr_hip] output buffer too small for the container header (%zu bytes)\n", dst_cap);
       return -1;
     }
-    if (slice)
+    if (nvol > 1)   // (one container: k_container_header, as before)
+      LAUNCH_K(k_batch_container, dim3(1), dim3(kBatchThreads), 0, st, d_dst, (uint64_t)dst_cap, d_lens, d_lens2,
+               d_offs, nchunks, cpv, (uint32_t)vol[0], (uint32_t)vol[1], (uint32_t)vol[2], (uint32_t)cdim[0],
+               (uint32_t)cdim[1], (uint32_t)cdim[2], std::is_same<T, float>::value ? 1 : 0, d_total);
+    else if (slice)
       LAUNCH_K(k_slice_header, dim3(1), dim3(1), 0, st, d_dst, d_lens, d_lens2, d_offs,
                (uint32_t)vol[0], (uint32_t)vol[1], std::is_same<T, float>::value ? 1 : 0,
                slice == 2 ? 1 : 0, d_total);
@@ -2166,11 +2272,18 @@ struct EncodeCall {
     for (auto& k : pweKeep)
       LAUNCH_K(k_copy_slots2, dim3(256, k.nb), dim3(kThreads), 0, st, d_dst, (uint64_t)dst_cap, k.slots,
                k.slotOff, k.gids, d_lens, d_lens2, d_offs);
-    HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    if (nvol > 1) {
+      bases.resize(nvol + 1);
+      HIP_CHECK(hipMemcpyAsync(bases.data(), d_total, (nvol + 1) * 8, hipMemcpyDeviceToHost, st));
+    }
+    else
+      HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     HIP_CHECK(hipGetLastError());
     E.pweLastStream = nullptr;
     E.prof.collect();
+    if (nvol > 1)
+      total = bases[nvol];
     if (total > dst_cap) {
       fprintf(stderr, "[sperr_hip] output buffer too small (%zu < %llu)\n", dst_cap, (unsigned long long)total);
       return -1;
@@ -2188,6 +2301,25 @@ int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkP
   if (call.run(chunkPref))
     return -1;
   *dst_len = (size_t)call.total;
+  return 0;
+}
+
+// nvol volumes of dims `vol` back to back into nvol containers back to back: container v at
+// [offsets[v], offsets[v + 1])
+template <typename T>
+int compress_batch_impl(Engine& E, const T* d_src, size_t nvol, const Dims& vol, const Dims& chunkPref, int mode,
+                        double quality, uint8_t* d_dst, size_t dst_cap, size_t* offsets, hipStream_t st)
+{
+  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, 0, nvol};
+  if (call.run(chunkPref))
+    return -1;
+  if (nvol == 1) {
+    offsets[0] = 0;
+    offsets[1] = (size_t)call.total;
+  }
+  else
+    for (size_t v = 0; v <= nvol; v++)
+      offsets[v] = (size_t)call.bases[v];
   return 0;
 }
 
@@ -2221,6 +2353,94 @@ int read_container_info(const uint8_t* d_src, size_t src_len, ContainerInfo& ci,
     r = parse_container_host(h.data(), h.size(), src_len, ci, &need);
   }
   return r == 0 ? 0 : -1;
+}
+
+// The containers of a batch (sperrhip_decompress_batch_dev), container v at [offs[v], offs[v + 1]) of d_src: every
+// header's prefix in one gather and one read-back, then the full headers of those with more to read in a second, each
+// parsed by parse_container_host.  All of them must describe the same volume.  `all` becomes the stacked view,
+// (x, y, nvol z) with every chunk's absolute offset and length; `list` its chunks (each container's chunk_volume, z
+// origins shifted by v z).  No container base is assumed aligned: the gathers read bytes
+int read_batch_info(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, ContainerInfo& all,
+                    std::vector<std::array<size_t, 6>>& list, hipStream_t st)
+{
+  if (nvol == 0 || nvol > 0xffffffffull)
+    return -1;
+  const uint32_t n = (uint32_t)nvol;
+  std::vector<uint64_t> off(nvol), len(nvol), need(nvol, 0), at(nvol + 1, 0);
+  for (size_t v = 0; v < nvol; v++) {
+    if (offs[v + 1] < offs[v])
+      return -1;
+    off[v] = offs[v];
+    len[v] = offs[v + 1] - offs[v];
+  }
+  const size_t arr = round_up(nvol * 8, 256);
+  if (E.misc.ensure(arr * 3 + nvol * 32 + 256))
+    return -1;
+  uint64_t* d_off = reinterpret_cast<uint64_t*>(E.misc.p);
+  uint64_t* d_len = d_off + arr / 8;
+  uint64_t* d_at = d_len + arr / 8;
+  uint8_t* d_bytes = reinterpret_cast<uint8_t*>(d_at + arr / 8);
+  std::vector<uint8_t> heads(nvol * 32);
+  HIP_CHECK(hipMemcpyAsync(d_off, off.data(), nvol * 8, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d_len, len.data(), nvol * 8, hipMemcpyHostToDevice, st));
+  LAUNCH_K(k_gather_heads, dim3((n + 63) / 64), dim3(64), 0, st, d_src, d_off, d_len, d_bytes, n);
+  HIP_CHECK(hipMemcpyAsync(heads.data(), d_bytes, heads.size(), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  std::vector<ContainerInfo> ci(nvol);
+  for (size_t v = 0; v < nvol; v++) {
+    size_t nd = 0;
+    const int r = parse_container_host(heads.data() + v * 32, std::min<uint64_t>(len[v], 26), len[v], ci[v], &nd);
+    if (r < 0 || (r == 1 && nd > len[v]))
+      return -1;
+    need[v] = r == 1 ? nd : 0;
+    at[v + 1] = at[v] + need[v];
+  }
+  if (at[nvol]) {   // the chunk-length tables
+    if (E.misc.ensure(arr * 3 + round_up(at[nvol], 256) + 256))
+      return -1;
+    d_off = reinterpret_cast<uint64_t*>(E.misc.p);
+    d_len = d_off + arr / 8;
+    d_at = d_len + arr / 8;
+    d_bytes = reinterpret_cast<uint8_t*>(d_at + arr / 8);
+    std::vector<uint8_t> hdr(at[nvol]);
+    HIP_CHECK(hipMemcpyAsync(d_off, off.data(), nvol * 8, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_len, need.data(), nvol * 8, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_at, at.data(), nvol * 8, hipMemcpyHostToDevice, st));
+    LAUNCH_K(k_gather_bytes, dim3(4, std::min<uint32_t>(n, 65535u)), dim3(kThreads), 0, st, d_src, d_off, d_len, d_at,
+             d_bytes, n);
+    HIP_CHECK(hipMemcpyAsync(hdr.data(), d_bytes, hdr.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t v = 0; v < nvol; v++) {
+      size_t nd = 0;
+      if (need[v] && parse_container_host(hdr.data() + at[v], need[v], len[v], ci[v], &nd) != 0)
+        return -1;
+    }
+  }
+  const Dims vol = ci[0].vol;
+  for (size_t v = 1; v < nvol; v++)
+    if (ci[v].vol != vol)
+      return -1;
+  if (nvol > 0xffffffffull / vol[2] || ci[0].nvals > SIZE_MAX / 8 / nvol)   // (uint32_t z origins)
+    return -1;
+  all.vol = {vol[0], vol[1], vol[2] * nvol};
+  all.chunk = ci[0].chunk;
+  all.nvals = ci[0].nvals * nvol;
+  all.off.clear();
+  all.len.clear();
+  list.clear();
+  for (size_t v = 0; v < nvol; v++) {
+    const auto per = chunk_volume(ci[v].vol, ci[v].chunk);
+    if (per.size() != ci[v].off.size() || list.size() + per.size() > 0xffffffffull)
+      return -1;
+    for (size_t i = 0; i < per.size(); i++) {
+      auto c = per[i];
+      c[4] += v * vol[2];
+      list.push_back(c);
+      all.off.push_back(off[v] + ci[v].off[i]);
+      all.len.push_back(ci[v].len[i]);
+    }
+  }
+  return 0;
 }
 
 // the lists of the larger sets GPU-wide (k_lis_hi); SPERR_HIP_LIS_HI=0 and regular trees whose geometry
@@ -2569,6 +2789,9 @@ struct DecodeCall {
   const MultiRes* mr;
   const bool slice;
   const BoxSel* box;
+  // a batch (sperrhip_decompress_batch_dev): the chunks of every container, z origins shifted into the stacked view
+  // that `ci` describes -- the volume (x, y, nvol z) and every chunk's absolute offset and length (null: chunk_volume)
+  const std::vector<std::array<size_t, 6>>* list = nullptr;
   // the output: the volume, or the box (its chunks write their windows: CropGeom, the kCrop writers)
   const VolDesc vd = box ? VolDesc{{box->dims[0], box->dims[1], box->dims[2]}} : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
   // The chunks of this call, slot by slot: slot i is container chunk sel[i] (all of them in order, or the
@@ -2594,8 +2817,8 @@ struct DecodeCall {
   ~DecodeCall() { if (!ok) drain_after_error(E, st); }
   int run(size_t dst_cap_vals)
   {
-    const auto chunks = chunk_volume(ci.vol, ci.chunk);
-    if (box && (mr || slice))
+    const auto chunks = list ? *list : chunk_volume(ci.vol, ci.chunk);
+    if ((box || list) && (mr || slice))
       return -1;
     sel = box ? box->ids : std::vector<uint32_t>(chunks.size());
     if (!box)
@@ -3333,9 +3556,10 @@ struct DecodeCall {
 template <typename T>
 int decompress_impl(Engine& E, const uint8_t* d_src, size_t /*src_len*/, T* d_dst, size_t dst_cap_vals,
                     const ContainerInfo& ci, hipStream_t st, const MultiRes* mr = nullptr,
-                    bool slice = false, const BoxSel* box = nullptr)
+                    bool slice = false, const BoxSel* box = nullptr,
+                    const std::vector<std::array<size_t, 6>>* list = nullptr)
 {
-  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box};
+  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box, list};
   return call.run(dst_cap_vals);
 }
 
@@ -3724,6 +3948,75 @@ int sperrhip_decompress_dev(const void* d_src, size_t src_len, int output_float,
     return decompress_impl<double>(E, static_cast<const uint8_t*>(d_src), src_len,
                                    static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
                                    st);
+  });
+}
+
+size_t sperrhip_max_compressed_size_batch(size_t nvol, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                                          size_t chunk_y, size_t chunk_z, int mode, double quality)
+{
+  const size_t one = sperrhip_max_compressed_size(dimx, dimy, dimz, chunk_x, chunk_y, chunk_z, mode, quality);
+  if (nvol != 0 && one > SIZE_MAX / nvol)
+    return 0;
+  return nvol * one;
+}
+
+int sperrhip_compress_batch_dev(const void* d_src, int is_float, size_t nvol, size_t dimx, size_t dimy, size_t dimz,
+                                size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
+                                void* d_dst, size_t dst_cap, size_t* offsets, void* hip_stream)
+{
+  return guarded("sperrhip_compress_batch_dev", [&]() -> int {
+    if (quality <= 0.0)
+      return 2;
+    if (mode < 1 || mode > 3)
+      return 2;
+    if (!d_src || !d_dst || !offsets || nvol == 0 || dimx == 0 || dimy == 0 || dimz == 0)
+      return -1;
+    if (nvol > 0xffffffffull / dimz)   // (chunk origins of the stacked view are 32-bit)
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (is_float)
+      return compress_batch_impl<float>(E, static_cast<const float*>(d_src), nvol, vol, ch, mode, quality,
+                                        static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
+    return compress_batch_impl<double>(E, static_cast<const double*>(d_src), nvol, vol, ch, mode, quality,
+                                       static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
+  });
+}
+
+int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, int output_float,
+                                  void* d_dst, size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
+                                  void* hip_stream)
+{
+  return guarded("sperrhip_decompress_batch_dev", [&]() -> int {
+    if (!d_src || !offsets || !d_dst || nvol == 0)
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    ContainerInfo all;
+    std::vector<std::array<size_t, 6>> list;
+    if (read_batch_info(E, src, offsets, nvol, all, list, st))
+      return -1;
+    if (all.nvals > dst_cap_bytes / (output_float ? sizeof(float) : sizeof(double)))
+      return -1;
+    if (dimx)
+      *dimx = all.vol[0];
+    if (dimy)
+      *dimy = all.vol[1];
+    if (dimz)
+      *dimz = all.vol[2] / nvol;
+    if (output_float)
+      return decompress_impl<float>(E, src, 0, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), all, st,
+                                    nullptr, false, nullptr, &list);
+    return decompress_impl<double>(E, src, 0, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), all, st,
+                                   nullptr, false, nullptr, &list);
   });
 }
 
