@@ -262,6 +262,37 @@ int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size
                                   void* d_dst, size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
                                   void* hip_stream);
 
+/* ---- a batch of same-shape 2D slices, one stream each ------------------------------------------ */
+/* N slices of the same (dimx, dimy) in one call, all of them coded side by side on the 2D coder: the
+ * levels or time steps of a field, the frames of a detector, the z planes of a volume coded plane by
+ * plane.  Stream s is byte for byte what sperrhip_compress_2d_dev makes of slice s alone, and slice s of
+ * a batch decode is bit for bit sperrhip_decompress_2d_dev of stream s.  The slices are read as one
+ * volume of dims (x, y, nslice) with 32-bit chunk origins: nslice must not exceed 2^32 - 1.  The batch
+ * calls return -1 for nslice == 0, a zero dim, a NULL pointer, an output that is too small, decreasing
+ * offsets, a stream sperrhip_decompress_2d_dev would refuse (shorter than 17 bytes) and, with
+ * has_header, a header whose dims differ from the arguments'; a refusal found before decoding starts
+ * leaves d_dst as it was, and compression never writes past dst_cap.  With SPERR_HIP_SLICE_MIXED=0 (the
+ * quadtree walk of the 2D coder, whose buffers hold one slice) the batch calls run the slices through
+ * the single-slice path one after the other: the same bytes, no gain in speed. */
+/* Upper bound for sperrhip_compress_2d_batch_dev: nslice times sperrhip_max_compressed_size_2d; 0 for
+ * nslice == 0 or if the product overflows size_t.  Host only. */
+size_t sperrhip_max_compressed_size_2d_batch(size_t nslice, size_t dimx, size_t dimy, int mode, double quality);
+/* nslice slices back to back in d_src, slice s at element s*dimx*dimy, x fastest (a contiguous (N, y, x)
+ * array).  Writes nslice streams back to back into d_dst; out_inc_header != 0: each starts with its own
+ * 10-byte header.  offsets (host, nslice + 1 entries) receives the byte ranges: stream s is
+ * [offsets[s], offsets[s+1]).  Return codes as sperrhip_compress_2d_dev. */
+int sperrhip_compress_2d_batch_dev(const void* d_src, int is_float, size_t nslice, size_t dimx, size_t dimy,
+                                   int mode, double quality, int out_inc_header,
+                                   void* d_dst, size_t dst_cap, size_t* offsets, void* hip_stream);
+/* nslice streams in d_src, stream s at [offsets[s], offsets[s+1]) (host array), at any byte alignment.
+ * has_header == 0: the streams are what sperr_decomp_2d takes; has_header != 0: each starts with the
+ * 10-byte header, which is checked against dimx, dimy and skipped.  Mode, rate, truncation and the
+ * precision of the coded data may differ from stream to stream.  d_dst receives nslice slices back to
+ * back (float or double).  Returns 0 ok, -1 error. */
+int sperrhip_decompress_2d_batch_dev(const void* d_src, const size_t* offsets, size_t nslice, int has_header,
+                                     int output_float, size_t dimx, size_t dimy,
+                                     void* d_dst, size_t dst_cap_bytes, void* hip_stream);
+
 /* ---- profiling ------------------------------------------------------------------------------ */
 
 /* When enabled, the engine brackets every pipeline stage with HIP events on the launch stream

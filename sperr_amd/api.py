@@ -35,6 +35,7 @@ EXPORTS = [
     "sperrhip_host_cpus", "sperrhip_host_throttle", "sperrhip_farm_threads",
     "sperrhip_box_chunks", "sperrhip_decompress_box_dev", "sperrhip_decomp_3d_box",
     "sperrhip_max_compressed_size_batch", "sperrhip_compress_batch_dev", "sperrhip_decompress_batch_dev",
+    "sperrhip_max_compressed_size_2d_batch", "sperrhip_compress_2d_batch_dev", "sperrhip_decompress_2d_batch_dev",
 ]
 
 
@@ -117,6 +118,14 @@ def load_library():
     lib.sperrhip_decompress_batch_dev.restype = C.c_int
     lib.sperrhip_decompress_batch_dev.argtypes = [_vp, C.POINTER(_sz), _sz, C.c_int, _vp, _sz] + \
         [C.POINTER(_sz)] * 3 + [_vp]
+    lib.sperrhip_max_compressed_size_2d_batch.restype = _sz
+    lib.sperrhip_max_compressed_size_2d_batch.argtypes = [_sz, _sz, _sz, C.c_int, C.c_double]
+    lib.sperrhip_compress_2d_batch_dev.restype = C.c_int
+    lib.sperrhip_compress_2d_batch_dev.argtypes = [_vp, C.c_int, _sz, _sz, _sz, C.c_int, C.c_double, C.c_int, _vp, _sz,
+                                                   C.POINTER(_sz), _vp]
+    lib.sperrhip_decompress_2d_batch_dev.restype = C.c_int
+    lib.sperrhip_decompress_2d_batch_dev.argtypes = [_vp, C.POINTER(_sz), _sz, C.c_int, C.c_int, _sz, _sz, _vp, _sz,
+                                                     _vp]
     lib.sperrhip_box_chunks.restype = C.c_int
     lib.sperrhip_box_chunks.argtypes = [_sz] * 6 + [C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint32), _sz,
                                                     C.POINTER(_sz)]
@@ -510,6 +519,60 @@ class SperrHip:
                                                   out.numel() * out.element_size(), self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decompress_2d_dev returned {rtn}")
+        return out
+
+    # ---- a batch of same-shape slices --------------------------------------------------------
+    def max_compressed_size_2d_batch(self, nslice, shape_yx, quality, mode=1):
+        dy, dx = shape_yx
+        return self.lib.sperrhip_max_compressed_size_2d_batch(nslice, dx, dy, mode, float(quality))
+
+    def compress_2d_batch(self, imgs, quality, mode=1, header=False, out=None):
+        """imgs: contiguous cuda tensor float32/float64 shaped (N, y, x) -- N slices, or a (z, y, x) volume coded
+        plane by plane.  Returns N cuda uint8 tensors, views into one buffer (`out` when it is large enough) in order:
+        stream s is what compress_2d() makes of imgs[s]."""
+        torch = self.torch
+        assert imgs.is_cuda and imgs.is_contiguous() and imgs.dim() == 3
+        assert imgs.dtype in (torch.float32, torch.float64)
+        n, dy, dx = imgs.shape
+        cap = self.max_compressed_size_2d_batch(n, (dy, dx), quality, mode)
+        if cap == 0:
+            raise SperrHipError("sperrhip_max_compressed_size_2d_batch: no slices, or the bound overflows")
+        if out is None or out.numel() < cap:
+            out = torch.empty(cap, dtype=torch.uint8, device=imgs.device)
+        offs = (_sz * (n + 1))()
+        rtn = self.lib.sperrhip_compress_2d_batch_dev(imgs.data_ptr(), int(imgs.dtype == torch.float32), n, dx, dy,
+                                                      mode, float(quality), int(header), out.data_ptr(), out.numel(),
+                                                      offs, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_2d_batch_dev returned {rtn}")
+        return [out[offs[s]:offs[s + 1]] for s in range(n)]
+
+    def decompress_2d_batch(self, streams, shape_yx, output_float=True, header=False, out=None):
+        """streams: a list of cuda uint8 tensors (compress_2d_batch's views, or any), each the stream of a slice of
+        shape_yx -- with the 10-byte header in front when `header`.  They are concatenated first unless they already
+        lie back to back in one buffer.  Returns a cuda tensor shaped (N, y, x) -- `out` when given."""
+        torch = self.torch
+        assert len(streams) > 0
+        for c in streams:
+            assert c.is_cuda and c.dtype == torch.uint8 and c.dim() == 1 and c.is_contiguous()
+        n = len(streams)
+        dy, dx = shape_yx
+        packed = all(b.data_ptr() == a.data_ptr() + a.numel() and
+                     b.untyped_storage().data_ptr() == a.untyped_storage().data_ptr()
+                     for a, b in zip(streams, streams[1:]))
+        src = streams[0] if packed else torch.cat(list(streams))
+        offs = (_sz * (n + 1))()
+        for s, c in enumerate(streams):
+            offs[s + 1] = offs[s] + c.numel()
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            out = torch.empty((n, dy, dx), dtype=dt, device=src.device)
+        assert out.dtype == dt and out.is_contiguous() and out.is_cuda
+        rtn = self.lib.sperrhip_decompress_2d_batch_dev(src.data_ptr(), offs, n, int(header), int(output_float), dx,
+                                                        dy, out.data_ptr(), out.numel() * out.element_size(),
+                                                        self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_2d_batch_dev returned {rtn}")
         return out
 
     # ---- multi-resolution decoding ----------------------------------------------------------

@@ -990,6 +990,66 @@ k_batch_container(uint8_t* dst, uint64_t dst_cap, const uint64_t* lens, const ui
   }
 }
 
+// The streams of a batch of n slices of one shape (sperrhip_compress_2d_batch_dev), back to back: a slice is one
+// chunk, there is no chunk-length table, and the optional 10-byte header {version, flags, u32 dimx, u32 dimy}
+// (k_slice_header's bytes) is per stream.  Stream s starts at bases[s] = H s + the bytes (SPECK + outlier) of the
+// slices before s, its chunk at offs[s] = bases[s] + H, H = 10 with headers and 0 without; bases[n] is the total.
+// One workgroup whatever n is: an exclusive scan of lens + lens2 in tiles of kBatchThreads -- wave64 shuffles, the 16
+// waves' sums through LDS (scanned by the first wavefront, read back as one broadcast word per wavefront: no bank
+// conflict), a carry between tiles.  Writes past dst_cap are dropped (the host refuses the batch then).
+__global__ void __launch_bounds__(kBatchThreads)
+k_slice_batch_layout(uint8_t* dst, uint64_t dst_cap, const uint64_t* lens, const uint64_t* lens2, uint64_t* offs,
+                     uint32_t n, uint32_t vx, uint32_t vy, int is_float, int with_header, uint64_t* bases)
+{
+  constexpr uint32_t kWaves = kBatchThreads / 64;
+  __shared__ uint64_t waveBefore[kWaves + 1];   // (exclusive sums of the tile's waves, then the tile's sum)
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint64_t H = with_header ? 10u : 0u;
+  uint64_t carry = 0;   // (every thread keeps its own copy: the same value in all of them)
+  for (uint32_t t0 = 0; t0 < n; t0 += kBatchThreads) {
+    const uint32_t s = t0 + t;
+    const uint64_t both = s < n ? lens[s] + lens2[s] : 0;
+    uint64_t x = both;   // inclusive scan of the wavefront
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t y = __shfl_up(x, d, 64);
+      if (lane >= (uint32_t)d)
+        x += y;
+    }
+    __syncthreads();   // (the previous tile's waveBefore has been read)
+    if (lane == 63)
+      waveBefore[w + 1] = x;
+    __syncthreads();
+    if (w == 0) {   // the waves' sums: an inclusive scan in the first wavefront
+      uint64_t ws = lane < kWaves ? waveBefore[lane + 1] : 0;
+      for (int d = 1; d < (int)kWaves; d <<= 1) {
+        const uint64_t y = __shfl_up(ws, d, 64);
+        if (lane >= (uint32_t)d)
+          ws += y;
+      }
+      if (lane < kWaves)
+        waveBefore[lane + 1] = ws;
+      if (lane == 0)
+        waveBefore[0] = 0;
+    }
+    __syncthreads();
+    if (s < n) {
+      const uint64_t at = carry + waveBefore[w] + x - both + H * s;
+      bases[s] = at;
+      offs[s] = at + H;
+      if (with_header && at + 10 <= dst_cap) {
+        uint8_t* h = dst + at;
+        h[0] = 0;
+        h[1] = (uint8_t)(is_float ? 0x20 : 0);
+        const uint32_t d2[2] = {vx, vy};
+        memcpy(h + 2, d2, 8);
+      }
+    }
+    carry += waveBefore[kWaves];
+  }
+  if (t == 0)
+    bases[n] = carry + H * n;
+}
+
 // bytes [srcOff[i], srcOff[i] + len[i]) of every container of a batch, packed at dstOff[i] (the full headers,
 // sperrhip_decompress_batch_dev)
 __global__ void __launch_bounds__(kThreads)
@@ -1856,7 +1916,9 @@ struct EncodeCall {
   hipStream_t st;
   const int slice;
   // a batch (sperrhip_compress_batch_dev): nvol volumes of dims `vol` back to back in d_src, read as one volume of
-  // (x, y, nvol z) -- the stacked view -- whose chunks are each volume's, and coded into nvol containers
+  // (x, y, nvol z) -- the stacked view -- whose chunks are each volume's, and coded into nvol containers.  With
+  // `slice` (sperrhip_compress_2d_batch_dev): nvol slices, chunk s of dims (x, y, 1) at (0, 0, s), one shape group on
+  // the 2D coder's forest, coded into nvol streams (k_slice_batch_layout)
   const size_t nvol = 1;
   const bool rate = mode == 1;
   const double bpp = rate ? quality : 0.0;
@@ -2253,7 +2315,11 @@ struct EncodeCall {
       fprintf(stderr, "[sperr_hip] output buffer too small for the container header (%zu bytes)\n", dst_cap);
       return -1;
     }
-    if (nvol > 1)   // (one container: k_container_header, as before)
+    if (nvol > 1 && slice)   // (a batch of slices: no length tables, a header per stream if any)
+      LAUNCH_K(k_slice_batch_layout, dim3(1), dim3(kBatchThreads), 0, st, d_dst, (uint64_t)dst_cap, d_lens, d_lens2,
+               d_offs, nchunks, (uint32_t)vol[0], (uint32_t)vol[1], std::is_same<T, float>::value ? 1 : 0,
+               slice == 2 ? 1 : 0, d_total);
+    else if (nvol > 1)   // (one container: k_container_header, as before)
       LAUNCH_K(k_batch_container, dim3(1), dim3(kBatchThreads), 0, st, d_dst, (uint64_t)dst_cap, d_lens, d_lens2,
                d_offs, nchunks, cpv, (uint32_t)vol[0], (uint32_t)vol[1], (uint32_t)vol[2], (uint32_t)cdim[0],
                (uint32_t)cdim[1], (uint32_t)cdim[2], std::is_same<T, float>::value ? 1 : 0, d_total);
@@ -2308,9 +2374,9 @@ int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkP
 // [offsets[v], offsets[v + 1])
 template <typename T>
 int compress_batch_impl(Engine& E, const T* d_src, size_t nvol, const Dims& vol, const Dims& chunkPref, int mode,
-                        double quality, uint8_t* d_dst, size_t dst_cap, size_t* offsets, hipStream_t st)
+                        double quality, uint8_t* d_dst, size_t dst_cap, size_t* offsets, hipStream_t st, int slice = 0)
 {
-  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, 0, nvol};
+  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, slice, nvol};
   if (call.run(chunkPref))
     return -1;
   if (nvol == 1) {
@@ -2739,8 +2805,8 @@ DecPlanHost dec_plan_host(const ShapePlan& P)
 }
 
 // One decompression call (decompress_impl), stage by stage.  slice: `ci` describes one chunk of dims (x, y, 1) whose
-// stream starts at d_src (2D coder).  box: only the chunks the box meets are read and decoded, and d_dst is the box
-// (not with mr or slice)
+// stream starts at d_src (2D coder); with `list`, a batch of slices: chunk s of dims (x, y, 1) at (0, 0, s).  box: only
+// the chunks the box meets are read and decoded, and d_dst is the box (not with mr or slice)
 template <typename T>
 struct DecodeCall {
   struct Ref {
@@ -2792,6 +2858,9 @@ struct DecodeCall {
   // a batch (sperrhip_decompress_batch_dev): the chunks of every container, z origins shifted into the stacked view
   // that `ci` describes -- the volume (x, y, nvol z) and every chunk's absolute offset and length (null: chunk_volume)
   const std::vector<std::array<size_t, 6>>* list = nullptr;
+  // a batch of slices whose streams carry the 10-byte header (sperrhip_decompress_2d_batch_dev): ci.off points behind
+  // each header; {dimx, dimy} that every header has to name (null: no headers)
+  const uint32_t* sliceHdr = nullptr;
   // the output: the volume, or the box (its chunks write their windows: CropGeom, the kCrop writers)
   const VolDesc vd = box ? VolDesc{{box->dims[0], box->dims[1], box->dims[2]}} : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
   // The chunks of this call, slot by slot: slot i is container chunk sel[i] (all of them in order, or the
@@ -2818,7 +2887,7 @@ struct DecodeCall {
   int run(size_t dst_cap_vals)
   {
     const auto chunks = list ? *list : chunk_volume(ci.vol, ci.chunk);
-    if ((box || list) && (mr || slice))
+    if ((box && (mr || slice)) || (list && mr))   // (a list of slices: sperrhip_decompress_2d_batch_dev)
       return -1;
     sel = box ? box->ids : std::vector<uint32_t>(chunks.size());
     if (!box)
@@ -2854,22 +2923,47 @@ struct DecodeCall {
   int read_heads()
   {
     const uint32_t nchunks = (uint32_t)sel.size();
-    if (E.misc.ensure(round_up((size_t)nchunks * 8, 256) * 2 + (size_t)nchunks * 32 + 256))
+    if (E.misc.ensure(round_up((size_t)nchunks * 8, 256) * 4 + (size_t)nchunks * 64 + 256))
       return -1;
     uint64_t* d_off = reinterpret_cast<uint64_t*>(E.misc.p);
     uint64_t* d_len = d_off + round_up(nchunks, 32);
-    uint8_t* d_heads = reinterpret_cast<uint8_t*>(d_len + round_up(nchunks, 32));
-    auto gather = [&](const std::vector<uint64_t>& off, const std::vector<uint64_t>& len, std::vector<uint8_t>& out) -> int {
+    uint64_t* d_hoff = d_len + round_up(nchunks, 32);   // (sliceHdr: where each stream's 10-byte header starts)
+    uint64_t* d_hlen = d_hoff + round_up(nchunks, 32);
+    uint8_t* d_heads = reinterpret_cast<uint8_t*>(d_hlen + round_up(nchunks, 32));
+    // (withHdr: a second launch gathers the 10 bytes in front of every stream behind the heads, for the same read-back)
+    auto gather = [&](const std::vector<uint64_t>& off, const std::vector<uint64_t>& len, std::vector<uint8_t>& out,
+                      bool withHdr) -> int {
       HIP_CHECK(hipMemcpyAsync(d_off, off.data(), nchunks * 8, hipMemcpyHostToDevice, st));
       HIP_CHECK(hipMemcpyAsync(d_len, len.data(), nchunks * 8, hipMemcpyHostToDevice, st));
       LAUNCH_K(k_gather_heads, dim3((nchunks + 63) / 64), dim3(64), 0, st, d_src, d_off, d_len, d_heads, nchunks);
-      out.resize((size_t)nchunks * 32);
+      std::vector<uint64_t> hoff, hlen;
+      if (withHdr) {
+        hoff.resize(nchunks);
+        hlen.assign(nchunks, 10);
+        for (uint32_t i = 0; i < nchunks; i++)
+          hoff[i] = off[i] - 10;
+        HIP_CHECK(hipMemcpyAsync(d_hoff, hoff.data(), nchunks * 8, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_hlen, hlen.data(), nchunks * 8, hipMemcpyHostToDevice, st));
+        LAUNCH_K(k_gather_heads, dim3((nchunks + 63) / 64), dim3(64), 0, st, d_src, d_hoff, d_hlen,
+                 d_heads + (size_t)nchunks * 32, nchunks);
+      }
+      out.resize((size_t)nchunks * (withHdr ? 64 : 32));
       HIP_CHECK(hipMemcpyAsync(out.data(), d_heads, out.size(), hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
       return 0;
     };
-    if (gather(selOff, selLen, heads))
+    if (gather(selOff, selLen, heads, sliceHdr != nullptr))
       return -1;
+    if (sliceHdr)   // {version, flags, u32 dimx, u32 dimy} of every stream of a slice batch: the dims must be the call's
+      for (uint32_t i = 0; i < nchunks; i++) {
+        uint32_t d2[2];
+        memcpy(d2, heads.data() + (size_t)(nchunks + i) * 32 + 2, 8);
+        if (d2[0] != sliceHdr[0] || d2[1] != sliceHdr[1]) {
+          fprintf(stderr, "[sperr_hip] slice %u of the batch: its header says %u x %u, the call %u x %u\n", i, d2[0], d2[1],
+                  sliceHdr[0], sliceHdr[1]);
+          return -1;
+        }
+      }
     outHead.resize(nchunks);
     tailOff.assign(nchunks, 0);
     tailLen.assign(nchunks, 0);
@@ -2889,7 +2983,7 @@ struct DecodeCall {
     }
     if (!anyTail)
       return 0;
-    if (gather(tailOff, tailLen, tails))
+    if (gather(tailOff, tailLen, tails, false))
       return -1;
     for (uint32_t i = 0; i < nchunks; i++) {
       if (tailLen[i] < 9)
@@ -3557,9 +3651,9 @@ template <typename T>
 int decompress_impl(Engine& E, const uint8_t* d_src, size_t /*src_len*/, T* d_dst, size_t dst_cap_vals,
                     const ContainerInfo& ci, hipStream_t st, const MultiRes* mr = nullptr,
                     bool slice = false, const BoxSel* box = nullptr,
-                    const std::vector<std::array<size_t, 6>>* list = nullptr)
+                    const std::vector<std::array<size_t, 6>>* list = nullptr, const uint32_t* sliceHdr = nullptr)
 {
-  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box, list};
+  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box, list, sliceHdr};
   return call.run(dst_cap_vals);
 }
 
@@ -4274,6 +4368,145 @@ int sperrhip_decompress_2d_dev(const void* d_src, size_t src_len, int output_flo
     return decompress_impl<double>(E, static_cast<const uint8_t*>(d_src), src_len,
                                    static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci, st,
                                    nullptr, true);
+  });
+}
+
+// ---- a batch of same-shape slices (the stacked view of DESIGN.md section 0c: N slices read as one volume of
+// (x, y, N) whose chunk s is slice s, one shape group on the 2D coder's forest) ------------------------------------
+// With SPERR_HIP_SLICE_MIXED=0, and for a shape the forest's list kernel does not take, slices go through k_speck2d's
+// quadtree walk, whose buffers (Engine::slice2d) are carved for one chunk: the batch calls then run the slices
+// through the single-slice path one after the other -- the same bytes, no gain in speed.
+size_t sperrhip_max_compressed_size_2d_batch(size_t nslice, size_t dimx, size_t dimy, int mode, double quality)
+{
+  const size_t one = sperrhip_max_compressed_size_2d(dimx, dimy, mode, quality);
+  if (nslice != 0 && one > SIZE_MAX / nslice)
+    return 0;
+  return nslice * one;
+}
+
+static bool slice_batch_side_by_side(Engine& E, size_t dimx, size_t dimy)
+{
+  if (!slice_forest_enabled())
+    return false;
+  ShapePlan* P = E.plan(dimx, dimy, 0);
+  return P && (P->ht.flags & spk::kTree2D) && use_mixed(*P);
+}
+
+int sperrhip_compress_2d_batch_dev(const void* d_src, int is_float, size_t nslice, size_t dimx, size_t dimy,
+                                   int mode, double quality, int out_inc_header,
+                                   void* d_dst, size_t dst_cap, size_t* offsets, void* hip_stream)
+{
+  return guarded("sperrhip_compress_2d_batch_dev", [&]() -> int {
+    if (quality <= 0.0)
+      return 2;
+    if (mode < 1 || mode > 3)
+      return 2;
+    if (!d_src || !d_dst || !offsets || nslice == 0 || dimx == 0 || dimy == 0)
+      return -1;
+    if (nslice > 0xffffffffull)   // (chunk origins of the stacked view are 32-bit)
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    const Dims vol{dimx, dimy, 1};
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int slice = out_inc_header ? 2 : 1;
+    uint8_t* dst = static_cast<uint8_t*>(d_dst);
+    if (nslice > 1 && !slice_batch_side_by_side(E, dimx, dimy)) {   // one after the other
+      offsets[0] = 0;
+      for (size_t s = 0; s < nslice; s++) {
+        size_t len = 0;
+        const size_t at = offsets[s], elems = s * dimx * dimy;
+        const int rc = is_float ? compress_impl<float>(E, static_cast<const float*>(d_src) + elems, vol, vol, mode, quality,
+                                                       dst + at, dst_cap - at, &len, st, slice)
+                                : compress_impl<double>(E, static_cast<const double*>(d_src) + elems, vol, vol, mode,
+                                                        quality, dst + at, dst_cap - at, &len, st, slice);
+        if (rc)
+          return rc;
+        offsets[s + 1] = at + len;
+      }
+      return 0;
+    }
+    if (is_float)
+      return compress_batch_impl<float>(E, static_cast<const float*>(d_src), nslice, vol, vol, mode, quality, dst,
+                                        dst_cap, offsets, st, slice);
+    return compress_batch_impl<double>(E, static_cast<const double*>(d_src), nslice, vol, vol, mode, quality, dst,
+                                       dst_cap, offsets, st, slice);
+  });
+}
+
+int sperrhip_decompress_2d_batch_dev(const void* d_src, const size_t* offsets, size_t nslice, int has_header,
+                                     int output_float, size_t dimx, size_t dimy,
+                                     void* d_dst, size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_decompress_2d_batch_dev", [&]() -> int {
+    if (!d_src || !offsets || !d_dst || nslice == 0 || dimx == 0 || dimy == 0)
+      return -1;
+    if (nslice > 0xffffffffull || dimx > 0xffffffffull || dimy > 0xffffffffull)
+      return -1;
+    const size_t H = has_header ? 10 : 0, esz = output_float ? sizeof(float) : sizeof(double);
+    if (dimx > SIZE_MAX / dimy || dimx * dimy > SIZE_MAX / 8 / nslice)
+      return -1;
+    const size_t per = dimx * dimy;
+    if (per * nslice > dst_cap_bytes / esz)
+      return -1;
+    ContainerInfo all;
+    all.vol = {dimx, dimy, nslice};
+    all.chunk = {dimx, dimy, 1};
+    all.nvals = per * nslice;
+    all.is_float = output_float != 0;
+    std::vector<std::array<size_t, 6>> list(nslice);
+    for (size_t s = 0; s < nslice; s++) {
+      if (offsets[s + 1] < offsets[s] || offsets[s + 1] - offsets[s] < H + 17)   // (as sperrhip_decompress_2d_dev)
+        return -1;
+      all.off.push_back(offsets[s] + H);
+      all.len.push_back(offsets[s + 1] - offsets[s] - H);
+      list[s] = {0, dimx, 0, dimy, s, 1};
+    }
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    const uint32_t hdrDims[2] = {(uint32_t)dimx, (uint32_t)dimy};
+    if (nslice > 1 && !slice_batch_side_by_side(E, dimx, dimy)) {   // one after the other
+      if (has_header) {   // every header first: a refusal leaves d_dst as it was
+        std::vector<uint8_t> hd(nslice * 10);
+        for (size_t s = 0; s < nslice; s++)
+          HIP_CHECK(hipMemcpyAsync(hd.data() + s * 10, src + offsets[s], 10, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (size_t s = 0; s < nslice; s++) {
+          uint32_t d2[2];
+          memcpy(d2, hd.data() + s * 10 + 2, 8);
+          if (d2[0] != hdrDims[0] || d2[1] != hdrDims[1])
+            return -1;
+        }
+      }
+      for (size_t s = 0; s < nslice; s++) {
+        ContainerInfo ci;
+        ci.vol = {dimx, dimy, 1};
+        ci.nvals = per;
+        ci.chunk = ci.vol;
+        ci.is_float = output_float != 0;
+        ci.off = {0};
+        ci.len = {all.len[s]};
+        const uint8_t* one = src + all.off[s];
+        const int rc = output_float ? decompress_impl<float>(E, one, all.len[s], static_cast<float*>(d_dst) + s * per, per,
+                                                             ci, st, nullptr, true)
+                                    : decompress_impl<double>(E, one, all.len[s], static_cast<double*>(d_dst) + s * per,
+                                                              per, ci, st, nullptr, true);
+        if (rc)
+          return rc;
+      }
+      return 0;
+    }
+    if (output_float)
+      return decompress_impl<float>(E, src, 0, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), all, st,
+                                    nullptr, true, nullptr, &list, has_header ? hdrDims : nullptr);
+    return decompress_impl<double>(E, src, 0, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), all, st,
+                                   nullptr, true, nullptr, &list, has_header ? hdrDims : nullptr);
   });
 }
 
