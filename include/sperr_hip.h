@@ -271,9 +271,7 @@ int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size
  * calls return -1 for nslice == 0, a zero dim, a NULL pointer, an output that is too small, decreasing
  * offsets, a stream sperrhip_decompress_2d_dev would refuse (shorter than 17 bytes) and, with
  * has_header, a header whose dims differ from the arguments'; a refusal found before decoding starts
- * leaves d_dst as it was, and compression never writes past dst_cap.  With SPERR_HIP_SLICE_MIXED=0 (the
- * quadtree walk of the 2D coder, whose buffers hold one slice) the batch calls run the slices through
- * the single-slice path one after the other: the same bytes, no gain in speed. */
+ * leaves d_dst as it was, and compression never writes past dst_cap. */
 /* Upper bound for sperrhip_compress_2d_batch_dev: nslice times sperrhip_max_compressed_size_2d; 0 for
  * nslice == 0 or if the product overflows size_t.  Host only. */
 size_t sperrhip_max_compressed_size_2d_batch(size_t nslice, size_t dimx, size_t dimy, int mode, double quality);

@@ -32,7 +32,6 @@
 #include "speck_enc.h"
 #include "speck_tree_host.hpp"
 #include "outlier.h"
-#include "speck2d.h"
 #include "xform.h"
 
 // The decoder runs the shape groups of a volume side by side on up to eight streams; the ROCm
@@ -535,7 +534,6 @@ struct Engine {
   void* pweHost = nullptr;                 // pinned: the outlier stage's first read-back (a copy into pageable memory
   size_t pweHostBytes = 0;                 //   would hold the host until the stream gets there: compress_impl)
   hipEvent_t liveEv[kSubStreams][kLiveSlots] = {};
-  DevBuf slice2d;                           // 2D slices: lists and masks of the 2D coder
   DevBuf wideScratch;                       // 64-bit retry of a batch whose coder arrays lay over the chunk buffer
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
@@ -658,7 +656,7 @@ struct Engine {
       kv.second->tables.drop();
     plans.clear();
     planOrder.clear();
-    for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &slice2d, &wideScratch})
+    for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch})
       b->drop();
     for (auto& b : outlDec)
       b.drop();
@@ -674,7 +672,7 @@ struct Engine {
   size_t device_bytes() const
   {
     size_t n = 0;
-    for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &slice2d, &wideScratch})
+    for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch})
       n += b->n;
     for (const auto& b : outlDec)
       n += b.n;
@@ -1811,46 +1809,9 @@ int pwe_stage_finish(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs
   return 0;
 }
 
-// SPERR_HIP_SLICE_MIXED=0: slices are coded by k_speck2d's quadtree walk (one workgroup) instead of
-// the kernels of the 3D coder on the 2D coder's forest
-bool slice_forest_enabled()
-{
-  static const bool on = !(getenv("SPERR_HIP_SLICE_MIXED") && atoi(getenv("SPERR_HIP_SLICE_MIXED")) == 0);
-  return on;
-}
-
 // ---- 2D slices (sperr_comp_2d / sperr_decomp_2d, src/SPERR_C_API.cpp:7-134): a slice is a
-// one-chunk batch of dims (x, y, 1) -- its transform plan already is dwt2d -- coded by the 2D
-// coder of speck2d.hip instead of the 3D one
-int carve_slice2d(Engine& E, const ShapePlan& P, Speck2dBufs& sb)
-{
-  memset(&sb, 0, sizeof(sb));
-  sb.dx = P.dims[0];
-  sb.dy = P.dims[1];
-  sb.N = P.N;
-  sb.nw = (P.N + 63) / 64;
-  sb.nxforms = (uint32_t)spk::num_of_xforms(std::min(P.dims[0], P.dims[1]));
-  sb.nlists = (uint32_t)spk::num_of_partitions(std::max(P.dims[0], P.dims[1])) + 1;
-  if (sb.dx > 0xffffu || sb.dy > 0xffffu || sb.nlists > (uint32_t)kS2MaxLevels)
-    return -1;
-  const size_t entries = speck2d_list_entries(sb);
-  const size_t words = round_up((size_t)sb.nw + 2, 32);
-  const size_t bytes = round_up(entries * 8, 256) + round_up(entries, 256) + 2 * words * 8 +
-                       round_up((size_t)P.N * 4, 256) + 1024 + 4096;
-  if (E.slice2d.ensure(bytes))
-    return -1;
-  Arena A;
-  A.base = static_cast<char*>(E.slice2d.p);
-  A.cap = E.slice2d.n;
-  sb.runs = A.take<uint64_t>(entries);
-  sb.sval = A.take<int8_t>(entries);
-  sb.lip = A.take<uint64_t>(words);
-  sb.lsp = A.take<uint64_t>(words);
-  sb.fresh = A.take<uint32_t>(P.N);
-  sb.prep = A.take<int32_t>(256);
-  return (sb.runs && sb.sval && sb.lip && sb.lsp && sb.fresh && sb.prep) ? 0 : -1;
-}
-
+// one-chunk batch of dims (x, y, 1) -- its transform plan already is dwt2d -- coded by the 3D coder's
+// kernels on the 2D coder's forest (the plan of key (x, y, 0))
 // optional 10-byte header {version, flags, u32 dimx, u32 dimy} (SPERR_C_API.cpp:45-83), then the
 // chunk stream and its outlier stream
 __global__ void k_slice_header(uint8_t* dst, const uint64_t* lens, const uint64_t* lens2,
@@ -1902,9 +1863,8 @@ struct EncodeCall {
     std::vector<CoderState> hc;
     std::vector<ChunkGeom> hg;
     std::vector<uint32_t> hid;
-    bool orgAligned = true, quadWalk = false;   // (quadWalk: a slice whose plan is no 2D forest, SPERR_HIP_SLICE_MIXED=0)
+    bool orgAligned = true;
     EncPlanHost ph;
-    Speck2dBufs sb;
   };
   Engine& E;
   const T* d_src;
@@ -1940,8 +1900,8 @@ struct EncodeCall {
   std::vector<uint64_t> bases;   // (a batch: where each container starts, then the total)
   bool ok = false;
   ~EncodeCall() { if (!ok) drain_after_error(E, st); }
-  // (a slice is coded on the 2D coder's forest, the plan with z extent 0; SPERR_HIP_SLICE_MIXED=0: k_speck2d's walk)
-  ShapePlan* plan_of(const GKey& d) { return E.plan(d[0], d[1], slice && slice_forest_enabled() ? 0 : d[2]); }
+  // (a slice is coded on the 2D coder's forest, the plan with z extent 0)
+  ShapePlan* plan_of(const GKey& d) { return E.plan(d[0], d[1], slice ? 0 : d[2]); }
   int run(const Dims& chunkPref)
   {
     for (int a = 0; a < 3; a++)  // SPERR3D_OMP_C.cpp:23-30
@@ -2188,7 +2148,6 @@ struct EncodeCall {
   {
     const ShapePlan& P = *b.P;
     EncBuffers& e = b.bb.eb;
-    b.quadWalk = slice && !(P.ht.flags & spk::kTree2D);
     EncPlanHost& ph = b.ph = EncPlanHost{P.d_initLIS, P.d_initLen, P.d_depthBlocks, P.depthBlockOff, P.ht.nsets};
     // (the census of the pixel passes on a stream of its own beside the pyramid's upper levels: the
     //  decoder's outlier streams and events are idle during a compression call)
@@ -2197,35 +2156,20 @@ struct EncodeCall {
     ph.evJoin = E.evOutl[gi % kSubStreams];
     // the planes that can hold work are asked of the device before the plane loop is enqueued (speck_enc.h;
     // the decoder's pinned words and events are idle during a compression call)
-    if (!b.quadWalk) {
-      ph.d_bound = A.take<uint32_t>(64);
-      // (a pinned word pair and an event per GROUP: groups gi and gi + kSubStreams share a stream, and every head
-      //  is enqueued before any plane loop reads its bounds back -- a ragged volume has up to 4 parts + 7 border
-      //  shapes = 11 groups.  Past kSubStreams * kLiveSlots / 2 groups: all planes are launched)
-      const uint32_t lane = gi % kSubStreams, turn = gi / kSubStreams;
-      if (turn < (uint32_t)kLiveSlots / 2) {
-        ph.h_bound = E.liveHost[lane] + 2 * turn;
-        ph.evBound = E.liveEv[lane][turn];
-      }
-      if (!ph.d_bound)
-        ph.h_bound = nullptr;
+    ph.d_bound = A.take<uint32_t>(64);
+    // (a pinned word pair and an event per GROUP: groups gi and gi + kSubStreams share a stream, and every head
+    //  is enqueued before any plane loop reads its bounds back -- a ragged volume has up to 4 parts + 7 border
+    //  shapes = 11 groups.  Past kSubStreams * kLiveSlots / 2 groups: all planes are launched)
+    const uint32_t lane = gi % kSubStreams, turn = gi / kSubStreams;
+    if (turn < (uint32_t)kLiveSlots / 2) {
+      ph.h_bound = E.liveHost[lane] + 2 * turn;
+      ph.evBound = E.liveEv[lane][turn];
     }
-    if (b.quadWalk) {
-      Speck2dBufs& sb = b.sb;
-      if (carve_slice2d(E, P, sb))
-        return -1;
-      sb.coef = b.bb.coef32;
-      sb.sign = const_cast<uint64_t*>(e.sign);
-      sb.msb = b.bb.msb;
-      sb.stream = e.stream;
-      sb.streamWords = e.streamStride;
-      sb.cst = e.cst;
-      if (launch_speck2d_encode(b.ss, sb, b.raw_budget, rate, false))
-        return -1;
-    }
-    else if (sideBySide && ph.h_bound
-                 ? launch_speck_encode_head(b.ss, e, ph, b.raw_budget, rate, false)   // (its planes: late_planes)
-                 : launch_speck_encode(b.ss, e, ph, b.raw_budget, rate, false))
+    if (!ph.d_bound)
+      ph.h_bound = nullptr;
+    if (sideBySide && ph.h_bound
+            ? launch_speck_encode_head(b.ss, e, ph, b.raw_budget, rate, false)   // (its planes: late_planes)
+            : launch_speck_encode(b.ss, e, ph, b.raw_budget, rate, false))
       return -1;
     b.wblocks = (uint32_t)std::min<size_t>(4096, (e.streamStride * 8 + kThreads - 1) / kThreads);
     if (!(sideBySide && ph.h_bound))
@@ -2258,12 +2202,7 @@ struct EncodeCall {
     EncBuffers ew = e;
     ew.coef = bb.vals;
     ew.coefStride = bb.valsStride;
-    if (b.quadWalk) {
-      b.sb.coef = bb.vals;
-      if (launch_speck2d_encode(b.ss, b.sb, b.raw_budget, rate, true))
-        return -1;
-    }
-    else if (launch_speck_encode(b.ss, ew, ph, b.raw_budget, rate, true))
+    if (launch_speck_encode(b.ss, ew, ph, b.raw_budget, rate, true))
       return -1;
     write_slots(b, 1);
     return 0;
@@ -2530,12 +2469,15 @@ bool use_tables(const ShapePlan& P)
 // lists that mix set shapes (any chunk extent that is not a power of two, every slice): k_lis_mx (speck_mx.hip:
 // rows keyed by shape class, several workgroups per chunk, only the walk serial).  SPERR_HIP_LIS_MIXED=0, and trees
 // the class machinery does not take (more than 254 classes, 48 roots, 352 grids): k_lis_walk, the serial walk.
+// The switch does not apply to the 2D coder's forest: only k_lis_mx has the type-I phase a slice needs, and every
+// slice's forest fits it (tests/test_slice_forest_host.py).
 // (k_lis_mixed, the one-workgroup-per-chunk kernel of rounds 2-3 whose formulation k_lis_mx took over, was removed
 // at the end of round 4.)
 bool use_mixed(const ShapePlan& P)
 {
   static const bool mixEnv = !(getenv("SPERR_HIP_LIS_MIXED") && atoi(getenv("SPERR_HIP_LIS_MIXED")) == 0);
-  if (!mixEnv || use_tables(P) || P.ht.cls.empty() || P.ht.roots.size() > 48 || P.ht.grids.size() > 352 ||
+  const bool twoD = (P.ht.flags & spk::kTree2D) != 0;
+  if ((!twoD && !mixEnv) || use_tables(P) || P.ht.cls.empty() || P.ht.roots.size() > 48 || P.ht.grids.size() > 352 ||
       P.ht.mxSlot.size() != P.ht.cls.size())
     return false;
   return 2 * kMxS + 256 <= kMxRing && ((kMxS + kMxM) >> 6) + 5 <= 64 && kMxM >= 192 &&
@@ -3006,11 +2948,13 @@ struct DecodeCall {
   // fed), so the groups share one budget of workgroups (SPERR_HIP_MX_WGS; with more workgroups than CUs the chunks
   // launched last wait for the first ones to END: 1000^3 in 256^3 chunks, 37 such chunks at 8 workgroups each,
   // decoded no faster than with one workgroup per chunk)
+  // (a slice is decoded on the 2D coder's forest, the plan with z extent 0)
+  ShapePlan* plan_of(const Dims& d) { return E.plan(d[0], d[1], slice ? 0 : d[2]); }
   void count_mx_groups()
   {
     size_t nmx = 0;
     for (auto& h : groups) {
-      ShapePlan* Q = (slice && slice_forest_enabled()) ? E.plan(h.first[0], h.first[1], 0) : E.plan(h.first[0], h.first[1], h.first[2]);
+      ShapePlan* Q = plan_of(h.first);
       if (Q && use_mixed(*Q))
         nmx += h.second.size();
     }
@@ -3027,12 +2971,9 @@ struct DecodeCall {
   // (groups of 32 and more chunks of a shape the table kernels take keep the sub-batch scheme)
   static bool deferrable(const ShapePlan& P, size_t nchunksOfShape) { return nchunksOfShape < 32 || !use_tables(P); }
   // Refinement bit planes (speck_dec.h, DecBuffers::refPlanes): as many as the chunks of a group with 32-bit
-  // coefficients have planes (byte 17 of a chunk: src/SPECK_INT.cpp:284-308); not for a slice that goes through
-  // the quadtree walk of speck2d.hip, which updates coefficients itself
+  // coefficients have planes (byte 17 of a chunk: src/SPECK_INT.cpp:284-308)
   uint32_t ref_planes_of(const ShapePlan& P, const std::vector<Ref>& refs) const
   {
-    if (slice && !(P.ht.flags & spk::kTree2D))
-      return 0;
     uint32_t n = 0;
     for (const Ref& r : refs) {
       const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
@@ -3090,17 +3031,14 @@ struct DecodeCall {
   int decode_group(const Dims& shape, const std::vector<Ref>& refs, int pass)
   {
     // a slice is decoded by the kernels of the 3D decoder on the 2D coder's forest (k_lis_mx and its
-    // type-I phase); SPERR_HIP_SLICE_MIXED=0: by k_speck2d_decode, one workgroup walking the quadtree
-    ShapePlan* P = nullptr;
-    if (slice && slice_forest_enabled()) {
-      P = E.plan(shape[0], shape[1], 0);
-      if (P && !use_mixed(*P))
-        P = nullptr;
-    }
-    if (!P)
-      P = E.plan(shape[0], shape[1], shape[2]);
+    // type-I phase)
+    ShapePlan* P = plan_of(shape);
     if (!P)
       return -1;
+    if (slice && !use_mixed(*P)) {   // (no slice has such a forest, DESIGN.md section 4c: k_lis_walk has no type-I phase)
+      fprintf(stderr, "[sperr_hip] slice of %u x %u: its forest does not fit k_lis_mx\n", P->dims[0], P->dims[1]);
+      return -1;
+    }
     Batch b{&refs, P};
     b.deferG = deferOK && deferrable(*P, refs.size());
     if (b.deferG != (pass == 1))
@@ -3374,8 +3312,7 @@ struct DecodeCall {
     DecPlanHost ph = dec_plan_host(P);
     ph.skipFinish = true;   // launch_inv_quantize / the dequantising inverse passes complete the coefficients
     ph.mxGroups = mxGroupsCall;
-    const bool quadWalk = slice && !(P.ht.flags & spk::kTree2D);
-    if (!ph.tables && !ph.mixed && !quadWalk) {
+    if (!ph.tables && !ph.mixed) {
       // (a tree neither the table kernels nor k_lis_mx take -- more than 288 / 352 grids or 48 roots: chunks of
       //  2^30 samples and more -- decodes correctly, through one serial wavefront per chunk: say so, once)
       static std::atomic<bool> warned{false};
@@ -3428,24 +3365,6 @@ struct DecodeCall {
       }
       else
         HIP_CHECK(hipMemsetAsync(bb.coef32, 0, d.coefStride * nb * 4, ss));
-      if (quadWalk) {   // header + stream words by the 3D launcher (no planes), then the 2D coder
-        DecPlanHost ph2 = ph;
-        ph2.tables = ph2.l0 = ph2.l1 = ph2.mixed = false;
-        Speck2dBufs sb;
-        if (launch_speck_decode(ss, dw, ph2, d_src, bb.chunkOff, bb.chunkLen, wide != 0, 0) || carve_slice2d(E, P, sb))
-          return -1;
-        sb.coef = dw.coef;
-        sb.sign = d.sign;
-        sb.stream = d.stream;
-        sb.streamWords = d.streamStride;
-        sb.cst = d.cst;
-        sb.dst = d.st;
-        if (launch_speck2d_decode(ss, sb, wide != 0) ||
-            launch_inv_quantize(ss, wide != 0, dw.coef, dw.coefStride, d.sign, d.signStride, nb, P.N, bb.vals,
-                                bb.valsStride, d.cst))
-          return -1;
-        continue;
-      }
       // the header kernel must run even when no plane does (constant / all-zero chunks)
       if (launch_speck_decode(ss, dw, ph, d_src, bb.chunkOff, bb.chunkLen, wide != 0, wide ? S.maxWide : S.maxNarrow))
         return -1;
@@ -4373,23 +4292,12 @@ int sperrhip_decompress_2d_dev(const void* d_src, size_t src_len, int output_flo
 
 // ---- a batch of same-shape slices (the stacked view of DESIGN.md section 0c: N slices read as one volume of
 // (x, y, N) whose chunk s is slice s, one shape group on the 2D coder's forest) ------------------------------------
-// With SPERR_HIP_SLICE_MIXED=0, and for a shape the forest's list kernel does not take, slices go through k_speck2d's
-// quadtree walk, whose buffers (Engine::slice2d) are carved for one chunk: the batch calls then run the slices
-// through the single-slice path one after the other -- the same bytes, no gain in speed.
 size_t sperrhip_max_compressed_size_2d_batch(size_t nslice, size_t dimx, size_t dimy, int mode, double quality)
 {
   const size_t one = sperrhip_max_compressed_size_2d(dimx, dimy, mode, quality);
   if (nslice != 0 && one > SIZE_MAX / nslice)
     return 0;
   return nslice * one;
-}
-
-static bool slice_batch_side_by_side(Engine& E, size_t dimx, size_t dimy)
-{
-  if (!slice_forest_enabled())
-    return false;
-  ShapePlan* P = E.plan(dimx, dimy, 0);
-  return P && (P->ht.flags & spk::kTree2D) && use_mixed(*P);
 }
 
 int sperrhip_compress_2d_batch_dev(const void* d_src, int is_float, size_t nslice, size_t dimx, size_t dimy,
@@ -4413,21 +4321,6 @@ int sperrhip_compress_2d_batch_dev(const void* d_src, int is_float, size_t nslic
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const int slice = out_inc_header ? 2 : 1;
     uint8_t* dst = static_cast<uint8_t*>(d_dst);
-    if (nslice > 1 && !slice_batch_side_by_side(E, dimx, dimy)) {   // one after the other
-      offsets[0] = 0;
-      for (size_t s = 0; s < nslice; s++) {
-        size_t len = 0;
-        const size_t at = offsets[s], elems = s * dimx * dimy;
-        const int rc = is_float ? compress_impl<float>(E, static_cast<const float*>(d_src) + elems, vol, vol, mode, quality,
-                                                       dst + at, dst_cap - at, &len, st, slice)
-                                : compress_impl<double>(E, static_cast<const double*>(d_src) + elems, vol, vol, mode,
-                                                        quality, dst + at, dst_cap - at, &len, st, slice);
-        if (rc)
-          return rc;
-        offsets[s + 1] = at + len;
-      }
-      return 0;
-    }
     if (is_float)
       return compress_batch_impl<float>(E, static_cast<const float*>(d_src), nslice, vol, vol, mode, quality, dst,
                                         dst_cap, offsets, st, slice);
@@ -4471,37 +4364,6 @@ int sperrhip_decompress_2d_batch_dev(const void* d_src, const size_t* offsets, s
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const uint8_t* src = static_cast<const uint8_t*>(d_src);
     const uint32_t hdrDims[2] = {(uint32_t)dimx, (uint32_t)dimy};
-    if (nslice > 1 && !slice_batch_side_by_side(E, dimx, dimy)) {   // one after the other
-      if (has_header) {   // every header first: a refusal leaves d_dst as it was
-        std::vector<uint8_t> hd(nslice * 10);
-        for (size_t s = 0; s < nslice; s++)
-          HIP_CHECK(hipMemcpyAsync(hd.data() + s * 10, src + offsets[s], 10, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        for (size_t s = 0; s < nslice; s++) {
-          uint32_t d2[2];
-          memcpy(d2, hd.data() + s * 10 + 2, 8);
-          if (d2[0] != hdrDims[0] || d2[1] != hdrDims[1])
-            return -1;
-        }
-      }
-      for (size_t s = 0; s < nslice; s++) {
-        ContainerInfo ci;
-        ci.vol = {dimx, dimy, 1};
-        ci.nvals = per;
-        ci.chunk = ci.vol;
-        ci.is_float = output_float != 0;
-        ci.off = {0};
-        ci.len = {all.len[s]};
-        const uint8_t* one = src + all.off[s];
-        const int rc = output_float ? decompress_impl<float>(E, one, all.len[s], static_cast<float*>(d_dst) + s * per, per,
-                                                             ci, st, nullptr, true)
-                                    : decompress_impl<double>(E, one, all.len[s], static_cast<double*>(d_dst) + s * per,
-                                                              per, ci, st, nullptr, true);
-        if (rc)
-          return rc;
-      }
-      return 0;
-    }
     if (output_float)
       return decompress_impl<float>(E, src, 0, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), all, st,
                                     nullptr, true, nullptr, &list, has_header ? hdrDims : nullptr);

@@ -997,32 +997,6 @@ def test_2d_slice_decoder_on_the_shared_forest(eng, oracle, shape):
             assert np.array_equal(bits(got), bits(oracle.decomp_2d(s, shape, False))), (shape, mode, cut)
 
 
-def test_2d_quadtree_walk_decoder_in_a_fresh_process(oracle):
-    """`SPERR_HIP_SLICE_MIXED=0` (read once per process) codes slices with k_speck2d's quadtree walk, which
-    also decodes the slices the shared forest does not take: the same stream, the same values."""
-    import subprocess
-    import sys
-    import tempfile
-    shape = (121, 96)
-    img = turbulence((1,) + shape)[0]
-    want = oracle.comp_2d(img, 2, 90.0, False)
-    ref = oracle.decomp_2d(want, shape, True)
-    with tempfile.TemporaryDirectory() as td:
-        np.save(os.path.join(td, "c.npy"), np.frombuffer(want, dtype=np.uint8))
-        np.save(os.path.join(td, "r.npy"), ref)
-        np.save(os.path.join(td, "i.npy"), img)
-        code = ("import sys, numpy as np, torch; sys.path.insert(0, %r); from sperr_amd.api import SperrHip; "
-                "e = SperrHip(); c = torch.from_numpy(np.load(%r)).cuda(); r = np.load(%r); "
-                "d = e.decompress_2d(c, %r, True).cpu().numpy(); "
-                "s = e.compress_2d(torch.from_numpy(np.load(%r)).cuda(), 90.0, mode=2, header=False); "
-                "ok = np.array_equal(d.view(np.uint32), r.view(np.uint32)) and torch.equal(s, c); "
-                "sys.exit(0 if ok else 3)"
-                % (os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), os.path.join(td, "c.npy"),
-                   os.path.join(td, "r.npy"), shape, os.path.join(td, "i.npy")))
-        env = dict(os.environ, SPERR_HIP_SLICE_MIXED="0")
-        assert subprocess.run([sys.executable, "-c", code], env=env, timeout=300).returncode == 0
-
-
 @pytest.mark.parametrize("shape,chunks", [((64, 64, 64), (16, 16, 16)), ((48, 80, 160), (16, 16, 16)),
                                           ((70, 96, 96), (16, 24, 16))])
 @pytest.mark.parametrize("bpp", [0.8, 4.0, 20.0])

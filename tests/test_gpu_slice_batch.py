@@ -6,7 +6,7 @@ alone, and slice s of a batch decode bit for bit the oracle's (sperr_decomp_2d) 
 stream s.  Nothing is compared against the batch itself, and no tolerance is involved.  The cases walk the three
 modes in both precisions with and without the 10-byte header, a real 999 x 999 field, truncated and mixed streams in
 one decode, the 64-bit retry of some slices of a batch, a group that runs as several batches of 256 chunks, the launch
-counts, the refusals, the Python conveniences and the one-after-the-other path of SPERR_HIP_SLICE_MIXED=0."""
+counts, the refusals and the Python conveniences."""
 import ctypes as C
 import os
 
@@ -313,31 +313,3 @@ def test_python_inputs(eng, oracle):
         assert one.shape == (1,) + shape
         assert np.array_equal(bits(one[0]), bits(eng.decompress_2d(body, shape, False).cpu().numpy()))
         assert np.array_equal(bits(one[0]), bits(oracle.decomp_2d(host(body), shape, False)))
-
-
-def test_quadtree_walk_fallback_in_a_fresh_process(oracle):
-    """`SPERR_HIP_SLICE_MIXED=0` (read once per process): the batch calls run the slices one after the other through
-    k_speck2d's quadtree walk -- the same streams, the same values"""
-    import subprocess
-    import sys
-    import tempfile
-    shape = (37, 50)
-    imgs = np.stack([turbulence((1,) + shape, seed=200 + s)[0] for s in range(4)])
-    wants = [oracle.comp_2d(a, 1, 2.0, True) for a in imgs]
-    ref = np.stack([oracle.decomp_2d(w[10:], shape, True) for w in wants])
-    with tempfile.TemporaryDirectory() as td:
-        np.save(os.path.join(td, "i.npy"), imgs)
-        np.save(os.path.join(td, "r.npy"), ref)
-        np.save(os.path.join(td, "c.npy"), np.frombuffer(b"".join(wants), dtype=np.uint8))
-        code = ("import sys, numpy as np, torch; sys.path.insert(0, %r); from sperr_amd.api import SperrHip; "
-                "e = SperrHip(); i = torch.from_numpy(np.load(%r)).cuda(); r = np.load(%r); "
-                "c = torch.from_numpy(np.load(%r)).cuda(); "
-                "p = e.compress_2d_batch(i, 2.0, header=True); "
-                "d = e.decompress_2d_batch(p, %r, True, header=True).cpu().numpy(); "
-                "ok = torch.equal(torch.cat(p), c) and len(p) == 4 and "
-                "np.array_equal(d.view(np.uint32), r.view(np.uint32)); "
-                "sys.exit(0 if ok else 3)"
-                % (os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), os.path.join(td, "i.npy"),
-                   os.path.join(td, "r.npy"), os.path.join(td, "c.npy"), shape))
-        env = dict(os.environ, SPERR_HIP_SLICE_MIXED="0")
-        assert subprocess.run([sys.executable, "-c", code], env=env, timeout=300).returncode == 0
