@@ -72,6 +72,7 @@ int main(int argc, char** argv)
   size_t omp = 0, ftype = 0, dims[3] = {0, 0, 0}, chunks[3] = {256, 256, 256};
   // (SIZE_MAX: no --box_dims given; the parser makes --box_origin and --box_dims come together)
   size_t box_origin[3] = {0, 0, 0}, box_dims[3] = {SIZE_MAX, SIZE_MAX, SIZE_MAX};
+  size_t level = SIZE_MAX;   // (SIZE_MAX: no --level given)
   double pwe = 0.0, psnr = 0.0, bpp = 0.0;
 
   cli::Parser app("3D SPERR compression and decompression (MI355X)\n");
@@ -95,6 +96,14 @@ int main(int argc, char** argv)
   {
     cli::Option& o = app.counts("--box_dims", box_dims, 3, "Dimensions of the box to decode (with --box_origin).", go);
     o.needs = {"-d", "--box_origin"};
+    o.excludes = {"--decomp_lowres_f", "--decomp_lowres_d"};
+  }
+  // (this tool's addition: decode one level of the hierarchy alone, whole or a box of it)
+  {
+    cli::Option& o = app.count("--level", level, "Decode only this level of the lower resolutions (0: the coarsest):\n"
+                               "--decomp_f / --decomp_d hold the level; with --box_origin and\n"
+                               "--box_dims, the box in that level's coordinates.", go);
+    o.needs = {"-d"};
     o.excludes = {"--decomp_lowres_f", "--decomp_lowres_d"};
   }
   app.flag("--print_stats", print_stats, "Print statistics measuring the compression quality.", go).needs = {"-c"};
@@ -196,6 +205,18 @@ int main(int argc, char** argv)
                std::log2(s.sigma / s.rmse) - rate);
       }
     }
+  }
+  else if (level != SIZE_MAX) {
+    const bool boxed = box_dims[0] != SIZE_MAX || box_dims[1] != SIZE_MAX || box_dims[2] != SIZE_MAX;
+    Freed lev;
+    size_t od[3] = {0, 0, 0};
+    if (sperrhip_decomp_3d_level(input.data(), input.size(), 0, level, boxed ? box_origin : nullptr,
+                                 boxed ? box_dims : nullptr, od, &lev.p) != 0) {
+      printf("Decompression failed!\n");
+      return 1;
+    }
+    if (!cli::write_volume(static_cast<const double*>(lev.p), od[0] * od[1] * od[2], decomp_f64, decomp_f32, "data"))
+      return 1;
   }
   else if (box_dims[0] != SIZE_MAX || box_dims[1] != SIZE_MAX || box_dims[2] != SIZE_MAX) {
     Freed box;

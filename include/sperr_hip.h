@@ -236,6 +236,28 @@ int sperrhip_decompress_box_dev(const void* d_src, size_t src_len, int output_fl
 int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float,
                            const size_t box_lo[3], const size_t box_dims[3], void** dst);
 
+/* ---- one level of a 3D container's hierarchy, whole or a box of it ---------------------------- */
+/* Level `level` of the hierarchy (0 <= level < nlev, coarsest first as sperrhip_multires_levels orders
+ * them), or the box [lo, lo + dims) of it given in that level's coordinates: bit for bit that level of
+ * sperrhip_decompress_multires_dev cut to the box, as doubles, or as floats each narrowed once (round
+ * to nearest).  Only the chunks the box meets are read, only the inverse passes of the levels coarser
+ * than `level` run, and no outlier stream is looked at (a level is taken before the correctors are
+ * added); nothing of the full volume's size is allocated.  Any container kind that has levels decodes
+ * this way.  The calls return -1 without writing to the output when the container has no such level
+ * (chunks that are not dyadic or do not tile the volume have none), when an extent is 0, when
+ * lo + dims leaves the level, when only one of box_lo / box_dims is NULL, when the output is too
+ * small, or when the container is refused as sperrhip_decompress_dev refuses it. */
+/* box_lo and box_dims both NULL: the whole level.  Output: box_dims (or the level's dims) values, x fastest. */
+int sperrhip_decompress_level_dev(const void* d_src, size_t src_len, int output_float, size_t level,
+                                  const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
+                                  size_t dst_cap_bytes, void* hip_stream);   /* 0 ok, -1 */
+/* host container -> malloc'd host level or box (*dst must be NULL, free() it); out_dims receives its
+ * dims.  The chosen chunks' bytes travel to the calling thread's device, packed.  Returns 0 ok,
+ * 1 *dst not NULL, -1 error. */
+int sperrhip_decomp_3d_level(const void* src, size_t src_len, int output_float, size_t level,
+                             const size_t box_lo[3], const size_t box_dims[3], size_t out_dims[3],
+                             void** dst);
+
 /* ---- a batch of same-shape volumes, one container each ----------------------------------------- */
 /* N volumes of the same dims in one call: the chunks of every volume are coded together (a batch is
  * more chunks for the same shape groups), and each volume gets a container of its own.  Container v

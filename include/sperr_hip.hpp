@@ -176,6 +176,17 @@ class SPERR3D_OMP_D {
     std::free(dst);
     return RTNType::Good;
   }
+  // (this library's addition) one level of the hierarchy alone, coarsest first as view_hierarchy() orders them, whole
+  // or the box [lo, lo + dims) of it in the level's coordinates (sperrhip_decomp_3d_level): only the chunks it meets
+  // are read and only the level's part of the inverse transform runs; view_decoded_data() then holds it, x fastest
+  auto decompress_level(const void* bitstream, size_t level) -> RTNType
+  {
+    return level_impl(bitstream, level, nullptr, nullptr);
+  }
+  auto decompress_level(const void* bitstream, size_t level, dims_type lo, dims_type dims) -> RTNType
+  {
+    return level_impl(bitstream, level, lo.data(), dims.data());
+  }
   auto view_decoded_data() const -> const vecd_type& { return m_vol; }
   auto release_decoded_data() -> vecd_type&& { return std::move(m_vol); }
   auto view_hierarchy() const -> const std::vector<vecd_type>& { return m_hierarchy; }
@@ -184,6 +195,20 @@ class SPERR3D_OMP_D {
   auto get_chunk_dims() const -> dims_type { return m_chunk_dims; }
 
  private:
+  auto level_impl(const void* bitstream, size_t level, const size_t* lo, const size_t* dims) -> RTNType
+  {
+    if (bitstream == nullptr || m_ptr == nullptr || bitstream != m_ptr)
+      return RTNType::Error;
+    void* dst = nullptr;
+    size_t od[3] = {0, 0, 0};
+    m_hierarchy.clear();
+    if (sperrhip_decomp_3d_level(m_ptr, m_len, 0, level, lo, dims, od, &dst) != 0)
+      return RTNType::Error;
+    const auto* d = static_cast<const double*>(dst);
+    m_vol.assign(d, d + od[0] * od[1] * od[2]);
+    std::free(dst);
+    return RTNType::Good;
+  }
   dims_type m_dims = {0, 0, 0}, m_chunk_dims = {0, 0, 0};
   const uint8_t* m_ptr = nullptr;
   size_t m_len = 0;

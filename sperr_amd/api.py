@@ -36,6 +36,7 @@ EXPORTS = [
     "sperrhip_box_chunks", "sperrhip_decompress_box_dev", "sperrhip_decomp_3d_box",
     "sperrhip_max_compressed_size_batch", "sperrhip_compress_batch_dev", "sperrhip_decompress_batch_dev",
     "sperrhip_max_compressed_size_2d_batch", "sperrhip_compress_2d_batch_dev", "sperrhip_decompress_2d_batch_dev",
+    "sperrhip_decompress_level_dev", "sperrhip_decomp_3d_level",
 ]
 
 
@@ -133,6 +134,11 @@ def load_library():
     lib.sperrhip_decompress_box_dev.argtypes = [_vp, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, _vp]
     lib.sperrhip_decomp_3d_box.restype = C.c_int
     lib.sperrhip_decomp_3d_box.argtypes = [_vp, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_vp)]
+    lib.sperrhip_decompress_level_dev.restype = C.c_int
+    lib.sperrhip_decompress_level_dev.argtypes = [_vp, _sz, C.c_int, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, _vp]
+    lib.sperrhip_decomp_3d_level.restype = C.c_int
+    lib.sperrhip_decomp_3d_level.argtypes = [_vp, _sz, C.c_int, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz),
+                                             C.POINTER(_vp)]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -249,6 +255,40 @@ class SperrHip:
                                                    out.numel() * out.element_size(), self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decompress_box_dev returned {rtn}")
+        return out
+
+    @staticmethod
+    def _box_args(box_lo_xyz, box_dims_xyz):
+        if (box_lo_xyz is None) != (box_dims_xyz is None):
+            raise ValueError("give both box_lo_xyz and box_dims_xyz, or neither")
+        if box_lo_xyz is None:
+            return None, None
+        return (_sz * 3)(*box_lo_xyz), (_sz * 3)(*box_dims_xyz)
+
+    def decompress_level(self, container, level, box_lo_xyz=None, box_dims_xyz=None, output_float=False, out=None):
+        """Level `level` of a device container's hierarchy (coarsest first, as multires_levels orders them), whole or
+        the box [lo, lo + dims) of it (x, y, z order, the level's coordinates): only the chunks it meets are read and
+        only the level's part of the inverse transform runs.  A cuda tensor shaped (z, y, x) -- `out` when given."""
+        torch = self.torch
+        assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
+        dt = torch.float32 if output_float else torch.float64
+        lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
+        if out is None:
+            if dims is None:
+                shape, _, chunks = self.parse_header(container)
+                lv = self.multires_levels(shape, chunks)
+                if not 0 <= level < len(lv):
+                    raise SperrHipError(f"the container has {len(lv)} levels, level {level} was asked for")
+                zyx = lv[level]
+            else:
+                zyx = tuple(int(d) for d in reversed(box_dims_xyz))
+            out = torch.empty(zyx, dtype=dt, device=container.device)
+        assert out.dtype == dt and out.is_contiguous() and out.is_cuda
+        rtn = self.lib.sperrhip_decompress_level_dev(container.data_ptr(), container.numel(), int(output_float),
+                                                     level, lo, dims, out.data_ptr(),
+                                                     out.numel() * out.element_size(), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_level_dev returned {rtn}")
         return out
 
     def max_compressed_size_batch(self, nvol, shape_zyx, chunks_xyz, quality, mode=1):
@@ -402,6 +442,23 @@ class SperrHip:
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decomp_3d_box returned {rtn}")
         dx, dy, dz = (int(d) for d in box_dims_xyz)
+        dt = np.float32 if output_float else np.float64
+        out = np.frombuffer(C.string_at(dst.value, dx * dy * dz * np.dtype(dt).itemsize), dtype=dt).copy()
+        self._libc.free(dst)
+        return out.reshape(dz, dy, dx)
+
+    def decomp_3d_level(self, stream, level, box_lo_xyz=None, box_dims_xyz=None, output_float=False):
+        """Level `level` of a host container's hierarchy (bytes or a uint8 array, pageable or pinned), whole or the
+        box [lo, lo + dims) of it in the level's coordinates, as a numpy array shaped (z, y, x)."""
+        buf = stream if isinstance(stream, np.ndarray) else np.frombuffer(stream, dtype=np.uint8)
+        lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
+        dst = _vp(None)
+        od = (_sz * 3)()
+        rtn = self.lib.sperrhip_decomp_3d_level(buf.ctypes.data, buf.size, int(output_float), level, lo, dims, od,
+                                                C.byref(dst))
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decomp_3d_level returned {rtn}")
+        dx, dy, dz = int(od[0]), int(od[1]), int(od[2])
         dt = np.float32 if output_float else np.float64
         out = np.frombuffer(C.string_at(dst.value, dx * dy * dz * np.dtype(dt).itemsize), dtype=dt).copy()
         self._libc.free(dst)

@@ -2717,6 +2717,104 @@ k_sub_volume(const double* vals, size_t valsStride, const CoderState* cst, const
   }
 }
 
+// One level of the hierarchy alone (sperrhip_decompress_level_dev): level h, coarsest first, and the box
+// [lo, lo + dims) of it in the level's coordinates.  The level is the grid of the chunks' corners of resolution
+// cres[h], so the chunks the box meets are box_chunks of the level's dims with cres[h] as the chunk size
+struct LevelSel {
+  size_t h = 0;
+  MultiRes m;
+  Dims lo, dims;
+  bool crop = false;   // the box is not the whole level
+  std::vector<uint32_t> ids;
+};
+
+// The coarsest level's corner: no inverse pass runs before it is read, so nothing has dequantised it (LiftFuse mode 2
+// does that as a pass loads).  k_inv_quantize for the corner box [0, s) of every chunk with 32-bit coefficients, into
+// the chunk buffer with rows of bx and slices of by rows; one sample per lane, nothing outside the corner is touched.
+// The arithmetic is k_lift_axis's fetch: q * double(c) * (+-1.0), a coefficient never refined completed from the
+// decoder's masks, or the word k_ref_assemble left complete with its sign in bit 31 (coef_scheme)
+__global__ void __launch_bounds__(kThreads)
+k_dequant_corner(double* vals, size_t valsStride, uint32_t bx, uint32_t by, uint32_t cx, uint32_t cy, uint32_t sx,
+                 uint32_t sy, uint32_t sz, const CoderState* cst, const DecState* dst, const uint32_t* coef,
+                 size_t coefStride, const uint64_t* sign, size_t signStride, const uint64_t* sigNew,
+                 const uint64_t* sigOld, size_t maskStride, int coefSigned)
+{
+  const uint32_t c = blockIdx.y;
+  const CoderState& cs = cst[c];
+  if (cs.is_const || cs.wide)   // (64-bit coefficients: k_inv_quantize has converted the chunk buffer)
+    return;
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= sx * sy * sz)
+    return;
+  const uint32_t x = i % sx, r = i / sx;
+  const uint32_t y = r % sy, z = r / sy;
+  const size_t idx = ((size_t)z * cy + y) * cx + x;
+  const double q = cs.q;
+  const int scheme = coefSigned != 0 ? coef_scheme(dst[c]) : 0;
+  uint32_t v = coef[c * coefStride + idx];
+  double out;
+  if (scheme)
+    out = q * (double)coef_scheme_mag(v, scheme == 2) * ((v >> 31) ? -1.0 : 1.0);
+  else {
+    const uint32_t lastPl = (uint32_t)dst[c].lastPlane;
+    const uint32_t initNew = (1u << lastPl) + (1u << lastPl) - (1u << lastPl) / 2 - 1;
+    const uint32_t initOld = lastPl < 31 ? (2u << lastPl) + (2u << lastPl) - (2u << lastPl) / 2 - 1 : 0u;
+    const uint32_t w = (uint32_t)(idx >> 6), sh = (uint32_t)(idx & 63);
+    const uint64_t sgw = sign[c * signStride + w];
+    const uint32_t mn = (uint32_t)(sigNew[c * maskStride + w] >> sh) & 1u;
+    const uint32_t mo = (uint32_t)(sigOld[c * maskStride + w] >> sh) & 1u;
+    const uint32_t fill = mn ? initNew : (mo ? initOld : 0u);
+    v = v ? v : fill;
+    out = q * (double)v * (((sgw >> sh) & 1ull) ? 1.0 : -1.0);
+  }
+  vals[c * valsStride + ((size_t)z * by + y) * bx + x] = out;
+}
+
+// The writer of one level (k_sub_volume's sibling): the corner [0, s) of every chunk, read with the buffer's row
+// strides (bx, by), mean added (a constant chunk: the mean alone), narrowed once when OT is float, stored at the
+// chunk's place in the level -- or, kCrop, the chunk's window of the box (CropGeom in the level's coordinates; `vd`
+// holds the output's dims either way).  One sample per lane, x fastest; a workgroup covers kThreads consecutive
+// samples of the corner, whole rows or pieces of one, and returns before it loads when none of its rows is in the window
+template <typename OT, bool kCrop>
+__global__ void __launch_bounds__(kThreads)
+k_level_write(const double* vals, size_t valsStride, const CoderState* cst, const GeomOf<kCrop>* geom, uint32_t bx,
+              uint32_t by, uint32_t cdx, uint32_t cdy, uint32_t cdz, uint32_t sx, uint32_t sy, uint32_t sz,
+              VolDesc vd, OT* out)
+{
+  const uint32_t c = blockIdx.y;
+  const uint32_t n = sx * sy * sz, i0 = blockIdx.x * kThreads;
+  const GeomOf<kCrop> g = geom[c];
+  if constexpr (kCrop) {   // (uniform) rows r = z * sy + y of this workgroup: r0 .. r1
+    const uint32_t r0 = i0 / sx, r1 = (min(i0 + (uint32_t)kThreads, n) - 1) / sx;
+    const uint32_t z0 = r0 / sy, y0 = r0 % sy, z1 = r1 / sy, y1 = r1 % sy;
+    auto zin = [&](uint32_t z) { return z >= g.lo[2] && z < g.hi[2]; };
+    auto ymeet = [&](uint32_t a, uint32_t b) { return a < g.hi[1] && b >= g.lo[1]; };   // [a, b] meets [lo, hi)
+    bool any = zin(z0) && ymeet(y0, z1 > z0 ? sy - 1 : y1);
+    any = any || (z1 > z0 && zin(z1) && ymeet(0, y1));
+    any = any || (max(z0 + 1, g.lo[2]) < min(z1, g.hi[2]));   // a whole slice in between
+    if (!any)
+      return;
+  }
+  const uint32_t i = i0 + threadIdx.x;
+  if (i >= n)
+    return;
+  const uint32_t x = i % sx, r = i / sx;
+  const uint32_t y = r % sy, z = r / sy;
+  size_t o;
+  if constexpr (kCrop) {
+    if (x < g.lo[0] || x >= g.hi[0] || y < g.lo[1] || y >= g.hi[1] || z < g.lo[2] || z >= g.hi[2])
+      return;
+    o = ((size_t)((int64_t)g.rel[2] + z) * vd.dims[1] + (size_t)((int64_t)g.rel[1] + y)) * vd.dims[0] +
+        (size_t)((int64_t)g.rel[0] + x);
+  }
+  else
+    o = (((size_t)(g.org[2] / cdz) * sz + z) * vd.dims[1] + (size_t)(g.org[1] / cdy) * sy + y) * vd.dims[0] +
+        (size_t)(g.org[0] / cdx) * sx + x;
+  const CoderState& cs = cst[c];
+  const double v = cs.is_const ? cs.mean : vals[c * valsStride + ((size_t)z * by + y) * bx + x] + cs.mean;
+  out[o] = (OT)v;
+}
+
 // a sub-box of the volume to decode (sperrhip_decompress_box_dev): [lo, lo + dims), and the chunks it
 // meets (box_chunks, chunk_volume order)
 struct BoxSel {
@@ -2748,7 +2846,8 @@ DecPlanHost dec_plan_host(const ShapePlan& P)
 
 // One decompression call (decompress_impl), stage by stage.  slice: `ci` describes one chunk of dims (x, y, 1) whose
 // stream starts at d_src (2D coder); with `list`, a batch of slices: chunk s of dims (x, y, 1) at (0, 0, s).  box: only
-// the chunks the box meets are read and decoded, and d_dst is the box (not with mr or slice)
+// the chunks the box meets are read and decoded, and d_dst is the box (not with mr or slice).  lvl: one level of the
+// hierarchy alone, or a box of it (LevelSel, enqueue_level)
 template <typename T>
 struct DecodeCall {
   struct Ref {
@@ -2803,8 +2902,16 @@ struct DecodeCall {
   // a batch of slices whose streams carry the 10-byte header (sperrhip_decompress_2d_batch_dev): ci.off points behind
   // each header; {dimx, dimy} that every header has to name (null: no headers)
   const uint32_t* sliceHdr = nullptr;
+  // one level of the hierarchy alone (sperrhip_decompress_level_dev): only the chunks its box meets are read, the
+  // inverse passes stop at the level, no outlier stream is looked at, and d_dst is the level or the box of it (not
+  // with mr, slice, box or list)
+  const LevelSel* lvl = nullptr;
   // the output: the volume, or the box (its chunks write their windows: CropGeom, the kCrop writers)
-  const VolDesc vd = box ? VolDesc{{box->dims[0], box->dims[1], box->dims[2]}} : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
+  const VolDesc vd = box ? VolDesc{{box->dims[0], box->dims[1], box->dims[2]}}
+                     : lvl ? VolDesc{{lvl->dims[0], lvl->dims[1], lvl->dims[2]}}
+                           : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
+  // the chunks' windows travel to the device (DecBatchBufs::crop)
+  bool cropped() const { return box != nullptr || (lvl && lvl->crop); }
   // The chunks of this call, slot by slot: slot i is container chunk sel[i] (all of them in order, or the
   // box's).  Heads, outlier heads and batches are per slot; offsets and lengths come from the container.
   std::vector<uint32_t> sel;
@@ -2831,11 +2938,15 @@ struct DecodeCall {
     const auto chunks = list ? *list : chunk_volume(ci.vol, ci.chunk);
     if ((box && (mr || slice)) || (list && mr))   // (a list of slices: sperrhip_decompress_2d_batch_dev)
       return -1;
-    sel = box ? box->ids : std::vector<uint32_t>(chunks.size());
-    if (!box)
+    if (lvl && (box || mr || slice || list || lvl->h >= lvl->m.nlev))
+      return -1;
+    sel = box ? box->ids : lvl ? lvl->ids : std::vector<uint32_t>(chunks.size());
+    if (!box && !lvl)
       std::iota(sel.begin(), sel.end(), 0u);
     const uint32_t nchunks = (uint32_t)sel.size();
-    const size_t outVals = box ? box->dims[0] * box->dims[1] * box->dims[2] : ci.nvals;
+    const size_t outVals = box ? box->dims[0] * box->dims[1] * box->dims[2]
+                           : lvl ? lvl->dims[0] * lvl->dims[1] * lvl->dims[2]
+                                 : ci.nvals;
     if (outVals == 0 || outVals > dst_cap_vals || nchunks == 0)
       return -1;
     for (uint32_t i = 0; i < nchunks; i++) {
@@ -2910,6 +3021,8 @@ struct DecodeCall {
     tailOff.assign(nchunks, 0);
     tailLen.assign(nchunks, 0);
     bool anyTail = false;
+    if (lvl)   // (a level is taken before the outlier correctors are added, src/SPECK_FLT.cpp:568-603: no stream of them is read)
+      return 0;
     for (uint32_t i = 0; i < nchunks; i++) {
       const uint8_t* hd = heads.data() + (size_t)i * 32;
       if (selLen[i] < 26 || (hd[0] & 0x01))
@@ -3002,6 +3115,9 @@ struct DecodeCall {
         cbox[a] = std::max(cbox[a], P.fwd[k].region[a]);
     for (int a = 0; a < 3; a++)
       cbox[a] = std::max(cbox[a], 1u);
+    if (lvl)   // (a chunk with one level of transform has no coarser pass: the box still holds the level's corner)
+      for (int a = 0; a < 3; a++)
+        cbox[a] = std::max(cbox[a], lvl->m.cres[lvl->h][a]);
     return (size_t)cbox[0] * cbox[1] * cbox[2];
   }
   // room for all the small groups at once, if the memory is there
@@ -3019,7 +3135,7 @@ struct DecodeCall {
       for (auto& r : h.second)
         mp = std::max<uint64_t>(mp, ci.len[r.gid]);
       uint32_t qbox[3];
-      sum += round_up(h.second.size() * dec_bytes_per_chunk(*Q, mp, compact_box(*Q, h.second, qbox), ref_planes_of(*Q, h.second), box != nullptr) + (1 << 20), 4096);
+      sum += round_up(h.second.size() * dec_bytes_per_chunk(*Q, mp, compact_box(*Q, h.second, qbox), ref_planes_of(*Q, h.second), cropped()) + (1 << 20), 4096);
     }
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
@@ -3052,7 +3168,7 @@ struct DecodeCall {
     // the inverse passes dequantise on the way (not for the resolution hierarchy, whose coarsest
     // level is read before any pass has run)
     b.fuseDq = plan_fusable(*P) && !mr && !slice;
-    const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, box != nullptr);
+    const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, cropped());
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const size_t budgetBytes = arena_budget(E.arena.n, fr);
@@ -3175,7 +3291,7 @@ struct DecodeCall {
       S.nb = (nbAll - done + (nsub - q) - 1) / (nsub - q);
       S.first = b0 + done;
       done += S.nb;
-      if (S.nb && !carve_dec(A, *b.P, S.nb, b.maxPayload, S.bb, b.compactElems, b.refNPlanes, box != nullptr))
+      if (S.nb && !carve_dec(A, *b.P, S.nb, b.maxPayload, S.bb, b.compactElems, b.refNPlanes, cropped()))
         return -1;
       if (S.nb && b.compactElems)
         g_dbg_counter[2]++;
@@ -3305,6 +3421,18 @@ struct DecodeCall {
         }
       HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
     }
+    else if (cropped()) {   // a level's box: the same in the level's coordinates, where a chunk is its corner of cres[h]
+      S.hc.resize(nb);
+      for (uint32_t i = 0; i < nb; i++)
+        for (int a = 0; a < 3; a++) {
+          const size_t s = lvl->m.cres[lvl->h][a], o = S.hg[i].org[a] / b.P->dims[a] * s;
+          const size_t lo = lvl->lo[a], hi = lvl->lo[a] + lvl->dims[a];
+          S.hc[i].rel[a] = (int32_t)((int64_t)o - (int64_t)lo);
+          S.hc[i].lo[a] = (uint32_t)(lo > o ? lo - o : 0);
+          S.hc[i].hi[a] = (uint32_t)std::min<size_t>(hi - o, s);
+        }
+      HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
+    }
     HIP_CHECK(hipMemcpyAsync(bb.chunkOff, S.ho.data(), nb * 8, hipMemcpyHostToDevice, ss));
     HIP_CHECK(hipMemcpyAsync(bb.chunkLen, S.hl.data(), nb * 8, hipMemcpyHostToDevice, ss));
     HIP_CHECK(hipMemsetAsync(d.cst, 0, nb * sizeof(CoderState), ss));
@@ -3376,11 +3504,35 @@ struct DecodeCall {
     }
     return 0;
   }
+  // LiftFuse of inverse pass k: the pass dequantises the samples no coarser level produces as it loads them, where
+  // the group allows it, and works in the compact buffer where the group has one
+  void pass_dequant(const Batch& b, const DecBatchBufs& bb, size_t k, LiftFuse& lf) const
+  {
+    const DecBuffers& d = bb.db;
+    if (b.fuseDq && pass_fuse(*b.P, k, lf.inner) > 0) {
+      lf.mode = 2;
+      lf.coef = bb.coef32;
+      lf.coefStride = d.coefStride;
+      lf.sign = d.sign;
+      lf.signStride = d.signStride;
+      lf.sigNew = d.sigNew;
+      lf.sigOld = d.sigOld;
+      lf.maskStride = d.maskPixStride;
+      lf.dst = d.st;
+      lf.coefSigned = d.refPlanes ? 1 : 0;
+    }
+    if (b.compactElems) {
+      lf.bufx = b.cbox[0];
+      lf.bufy = b.cbox[1];
+    }
+  }
   // The inverse transform.  Its last pass covers the whole chunk: it adds the mean, narrows and scatters --
   // unless outlier correctors have to be added to the transformed values first (src/SPECK_FLT.cpp:573-590), in
   // which case every pass stays in the chunk buffer
   int enqueue_inverse(const Batch& b, SubHost& S, uint32_t q, hipStream_t ss)
   {
+    if (lvl)
+      return enqueue_level(b, S, ss);
     const ShapePlan& P = *b.P;
     const uint32_t nb = S.nb;
     const uint32_t* cd = P.dims;
@@ -3430,22 +3582,7 @@ struct DecodeCall {
       return 0;
     };
     auto dequant_fuse = [&](size_t k, LiftFuse& lf) {
-      if (b.fuseDq && pass_fuse(P, k, lf.inner) > 0) {
-        lf.mode = 2;
-        lf.coef = bb.coef32;
-        lf.coefStride = d.coefStride;
-        lf.sign = d.sign;
-        lf.signStride = d.signStride;
-        lf.sigNew = d.sigNew;
-        lf.sigOld = d.sigOld;
-        lf.maskStride = d.maskPixStride;
-        lf.dst = d.st;
-        lf.coefSigned = d.refPlanes ? 1 : 0;
-      }
-      if (b.compactElems) {
-        lf.bufx = b.cbox[0];
-        lf.bufy = b.cbox[1];
-      }
+      pass_dequant(b, bb, k, lf);
       if (fbrick) {
         lf.bufx = bbox[0];
         lf.bufy = bbox[1];
@@ -3497,6 +3634,45 @@ struct DecodeCall {
     if ((P.fwd.empty() || S.outliers) &&
         launch_scatter<T>(ss, d_dst, vd, bb.geom, nb, cd, bb.vals, bb.valsStride, d.cst, bb.crop))
       return -1;
+    return 0;
+  }
+  // One level alone: the passes of the levels coarser than it, in the compact buffer or the chunk buffer as the group
+  // has it (compact_box, fuseDq), then the writer.  The coarsest level has no pass: its corner is dequantised by a
+  // kernel of its own where the passes would have (chunks with 64-bit coefficients: k_inv_quantize has).  The finest
+  // level's kernels and the scatter pass are never reached
+  int enqueue_level(const Batch& b, SubHost& S, hipStream_t ss)
+  {
+    const ShapePlan& P = *b.P;
+    const uint32_t nb = S.nb;
+    const uint32_t* cd = P.dims;
+    DecBatchBufs& bb = S.bb;
+    DecBuffers& d = bb.db;
+    const size_t h = lvl->h, nlev = lvl->m.nlev;
+    if (P.fwd.size() != 3 * nlev)   // (a level of the transform is the three passes z y x of a dyadic chunk)
+      return -1;
+    const uint32_t bx = b.compactElems ? b.cbox[0] : cd[0], by = b.compactElems ? b.cbox[1] : cd[1];
+    const auto& r = lvl->m.cres[h];
+    if (b.compactElems && (r[0] > b.cbox[0] || r[1] > b.cbox[1] || r[2] > b.cbox[2]))
+      return -1;
+    for (size_t k = P.fwd.size(); k-- > 3 * (nlev - h);) {
+      const LiftPass& ps = P.fwd[k];
+      LiftFuse lf;
+      pass_dequant(b, bb, k, lf);
+      if (launch_lift(ss, false, bb.vals, bb.valsStride, nb, cd, ps.axis, ps.region, d.cst, 0, d_dst, vd, bb.geom, &lf))
+        return -1;
+    }
+    const uint32_t blocks = (r[0] * r[1] * r[2] + kThreads - 1) / kThreads;
+    if (h == 0 && b.fuseDq)
+      LAUNCH_K(k_dequant_corner, dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, bx, by, cd[0], cd[1],
+               r[0], r[1], r[2], d.cst, d.st, bb.coef32, d.coefStride, d.sign, d.signStride, d.sigNew, d.sigOld,
+               d.maskPixStride, d.refPlanes ? 1 : 0);
+    if (lvl->crop)
+      LAUNCH_K((k_level_write<T, true>), dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, d.cst, bb.crop,
+               bx, by, cd[0], cd[1], cd[2], r[0], r[1], r[2], vd, d_dst);
+    else
+      LAUNCH_K((k_level_write<T, false>), dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, d.cst, bb.geom,
+               bx, by, cd[0], cd[1], cd[2], r[0], r[1], r[2], vd, d_dst);
+    HIP_CHECK(hipGetLastError());
     return 0;
   }
   // read-backs only after every sub-batch is enqueued: a device-to-host copy into pageable
@@ -3570,9 +3746,10 @@ template <typename T>
 int decompress_impl(Engine& E, const uint8_t* d_src, size_t /*src_len*/, T* d_dst, size_t dst_cap_vals,
                     const ContainerInfo& ci, hipStream_t st, const MultiRes* mr = nullptr,
                     bool slice = false, const BoxSel* box = nullptr,
-                    const std::vector<std::array<size_t, 6>>* list = nullptr, const uint32_t* sliceHdr = nullptr)
+                    const std::vector<std::array<size_t, 6>>* list = nullptr, const uint32_t* sliceHdr = nullptr,
+                    const LevelSel* lvl = nullptr)
 {
-  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box, list, sliceHdr};
+  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box, list, sliceHdr, lvl};
   return call.run(dst_cap_vals);
 }
 
@@ -3706,6 +3883,93 @@ int decompress_box(Engine& E, const uint8_t* d_src, size_t src_len, int output_f
                                   st, nullptr, false, box);
   return decompress_impl<double>(E, d_src, src_len, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
                                  st, nullptr, false, box);
+}
+
+// Level `level` of the container `ci` describes, whole (lo and dims null) or the box [lo, lo + dims) of it: the chunks
+// it meets; -1 when the container has no such level, the box is empty or leaves the level
+int level_select(const ContainerInfo& ci, size_t level, const size_t* lo, const size_t* dims, LevelSel& s)
+{
+  multires_levels(ci.vol, ci.chunk, s.m);
+  if (level >= s.m.nlev || (lo == nullptr) != (dims == nullptr))
+    return -1;
+  s.h = level;
+  Dims ld, cr;
+  for (int a = 0; a < 3; a++) {
+    cr[a] = s.m.cres[level][a];
+    ld[a] = cr[a] * s.m.grid[a];
+    s.lo[a] = lo ? lo[a] : 0;
+    s.dims[a] = dims ? dims[a] : ld[a];
+    if (s.dims[a] > (size_t)INT32_MAX)
+      return -1;
+  }
+  s.crop = !(s.lo == Dims{0, 0, 0} && s.dims == ld);
+  return box_chunks(ld, cr, s.lo, s.dims, s.ids) ? 0 : -1;
+}
+
+// the level or its box into d_dst (x fastest); the caller has checked that d_dst holds it
+int decompress_level(Engine& E, const uint8_t* d_src, size_t src_len, int output_float, const ContainerInfo& ci,
+                     const LevelSel& s, void* d_dst, size_t dst_cap_bytes, hipStream_t st)
+{
+  if (output_float)
+    return decompress_impl<float>(E, d_src, src_len, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci,
+                                  st, nullptr, false, nullptr, nullptr, nullptr, &s);
+  return decompress_impl<double>(E, d_src, src_len, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
+                                 st, nullptr, false, nullptr, nullptr, nullptr, &s);
+}
+
+// The host entry points of a sub-box and of a level: the streams of the chunks `ids` of the host container at `h`
+// travel to the calling thread's device packed, in their order (one copy per run of chunks that lie back to back in
+// the container), `decode` runs the device path on that buffer -- `packed` is `ci` with those chunks' offsets
+// pointing into it -- and the result comes back in one copy, into a malloc'd buffer
+template <typename F>
+int decode_packed_host(const uint8_t* h, const ContainerInfo& ci, const std::vector<uint32_t>& ids, size_t outBytes,
+                       void** dst, F&& decode)
+{
+  ContainerInfo packed = ci;
+  size_t total = 0;
+  for (uint32_t id : ids) {
+    packed.off[id] = total;
+    total += ci.len[id];
+  }
+  void *d_in = nullptr, *d_out = nullptr;
+  auto release = [&]() {
+    if (d_in)
+      (void)hipFree(d_in);
+    if (d_out)
+      (void)hipFree(d_out);
+  };
+  if (hipMalloc(&d_in, std::max<size_t>(total, 1)) != hipSuccess || hipMalloc(&d_out, outBytes) != hipSuccess) {
+    (void)hipGetLastError();
+    fprintf(stderr, "[sperr_hip] device allocation failed\n");
+    release();
+    return -1;
+  }
+  int rtn = 0;
+  for (size_t i = 0; rtn == 0 && i < ids.size();) {
+    size_t j = i + 1;
+    while (j < ids.size() && ci.off[ids[j]] == ci.off[ids[j - 1]] + ci.len[ids[j - 1]])
+      j++;
+    const size_t bytes = ci.off[ids[j - 1]] + ci.len[ids[j - 1]] - ci.off[ids[i]];
+    if (bytes && hipMemcpy(static_cast<uint8_t*>(d_in) + packed.off[ids[i]], h + ci.off[ids[i]], bytes,
+                           hipMemcpyHostToDevice) != hipSuccess)
+      rtn = -1;
+    i = j;
+  }
+  if (rtn == 0) {
+    Lease L;
+    rtn = L.e ? decode(*L.e, static_cast<const uint8_t*>(d_in), total, packed, d_out) : -1;
+  }
+  if (rtn == 0) {
+    void* buf = malloc(outBytes);
+    if (buf && hipMemcpy(buf, d_out, outBytes, hipMemcpyDeviceToHost) == hipSuccess)
+      *dst = buf;
+    else {
+      free(buf);
+      rtn = -1;
+    }
+  }
+  release();
+  return rtn;
 }
 
 }  // namespace sperrhip
@@ -4074,6 +4338,32 @@ int sperrhip_decompress_box_dev(const void* d_src, size_t src_len, int output_fl
       return -1;
     return decompress_box(E, static_cast<const uint8_t*>(d_src), src_len, output_float, ci, b, d_dst,
                           dst_cap_bytes, st);
+  });
+}
+
+int sperrhip_decompress_level_dev(const void* d_src, size_t src_len, int output_float, size_t level,
+                                  const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
+                                  size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_decompress_level_dev", [&]() -> int {
+    if (!d_src || !d_dst)
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    ContainerInfo ci;
+    if (read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st))
+      return -1;
+    LevelSel s;
+    if (level_select(ci, level, box_lo, box_dims, s))
+      return -1;
+    const size_t esz = output_float ? sizeof(float) : sizeof(double);
+    if (dst_cap_bytes / esz < s.dims[0] * s.dims[1] * s.dims[2])
+      return -1;
+    return decompress_level(E, static_cast<const uint8_t*>(d_src), src_len, output_float, ci, s, d_dst,
+                            dst_cap_bytes, st);
   });
 }
 
@@ -4844,9 +5134,8 @@ int sperrhip_decomp_3d_multires(const void* src, size_t src_len, int output_floa
   });
 }
 
-// host container in, malloc'd host box out: only the chunks the box meets travel to the device (packed,
-// one copy per run of consecutive chunks), are decoded there by the device path on the calling thread's
-// device and stream 0, and the box comes back in one copy
+// host container in, malloc'd host box out: only the chunks the box meets travel to the device (decode_packed_host),
+// are decoded there by the device path on the calling thread's device and stream 0, and the box comes back in one copy
 int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float, const size_t box_lo[3],
                            const size_t box_dims[3], void** dst)
 {
@@ -4864,54 +5153,38 @@ int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float, co
       return -1;
     const size_t esz = output_float ? sizeof(float) : sizeof(double);
     const size_t outBytes = b.dims[0] * b.dims[1] * b.dims[2] * esz;
-    // the chosen chunks' streams, packed in their order: the offsets of `packed` point into that buffer
-    ContainerInfo packed = ci;
-    size_t total = 0;
-    for (uint32_t id : b.ids) {
-      packed.off[id] = total;
-      total += ci.len[id];
-    }
-    void *d_in = nullptr, *d_out = nullptr;
-    auto release = [&]() {
-      if (d_in)
-        (void)hipFree(d_in);
-      if (d_out)
-        (void)hipFree(d_out);
-    };
-    if (hipMalloc(&d_in, std::max<size_t>(total, 1)) != hipSuccess || hipMalloc(&d_out, outBytes) != hipSuccess) {
-      (void)hipGetLastError();
-      fprintf(stderr, "[sperr_hip] device allocation failed\n");
-      release();
+    return decode_packed_host(static_cast<const uint8_t*>(src), ci, b.ids, outBytes, dst,
+                              [&](Engine& E, const uint8_t* d_in, size_t total, const ContainerInfo& packed, void* d_out) {
+                                return decompress_box(E, d_in, total, output_float, packed, b, d_out, outBytes, nullptr);
+                              });
+  });
+}
+
+// host container in, malloc'd host level (or box of it) out, the same way
+int sperrhip_decomp_3d_level(const void* src, size_t src_len, int output_float, size_t level, const size_t box_lo[3],
+                             const size_t box_dims[3], size_t out_dims[3], void** dst)
+{
+  return guarded("sperrhip_decomp_3d_level", [&]() -> int {
+    if (!dst || *dst != nullptr)
+      return 1;
+    if (!src || !out_dims)
       return -1;
-    }
-    const uint8_t* h = static_cast<const uint8_t*>(src);
-    int rtn = 0;
-    for (size_t i = 0; rtn == 0 && i < b.ids.size();) {   // runs of chunks that lie back to back in the container
-      size_t j = i + 1;
-      while (j < b.ids.size() && ci.off[b.ids[j]] == ci.off[b.ids[j - 1]] + ci.len[b.ids[j - 1]])
-        j++;
-      const size_t bytes = ci.off[b.ids[j - 1]] + ci.len[b.ids[j - 1]] - ci.off[b.ids[i]];
-      if (bytes && hipMemcpy(static_cast<uint8_t*>(d_in) + packed.off[b.ids[i]], h + ci.off[b.ids[i]], bytes,
-                             hipMemcpyHostToDevice) != hipSuccess)
-        rtn = -1;
-      i = j;
-    }
-    if (rtn == 0) {
-      Lease L;
-      rtn = L.e ? decompress_box(*L.e, static_cast<const uint8_t*>(d_in), total, output_float, packed, b, d_out,
-                                 outBytes, nullptr)
-                : -1;
-    }
-    if (rtn == 0) {
-      void* buf = malloc(outBytes);
-      if (buf && hipMemcpy(buf, d_out, outBytes, hipMemcpyDeviceToHost) == hipSuccess)
-        *dst = buf;
-      else {
-        free(buf);
-        rtn = -1;
-      }
-    }
-    release();
+    ContainerInfo ci;
+    size_t need = 0;
+    if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
+      return -1;
+    LevelSel s;
+    if (level_select(ci, level, box_lo, box_dims, s))
+      return -1;
+    const size_t esz = output_float ? sizeof(float) : sizeof(double);
+    const size_t outBytes = s.dims[0] * s.dims[1] * s.dims[2] * esz;
+    const int rtn = decode_packed_host(static_cast<const uint8_t*>(src), ci, s.ids, outBytes, dst,
+                                       [&](Engine& E, const uint8_t* d_in, size_t total, const ContainerInfo& packed, void* d_out) {
+                                         return decompress_level(E, d_in, total, output_float, packed, s, d_out, outBytes, nullptr);
+                                       });
+    if (rtn == 0)
+      for (int a = 0; a < 3; a++)
+        out_dims[a] = s.dims[a];
     return rtn;
   });
 }
