@@ -201,7 +201,7 @@ struct DevBuf {
   }
 };
 
-std::atomic<unsigned long long> g_dbg_counter[3];   // sperrhip_debug_counter
+std::atomic<unsigned long long> g_dbg_counter[4];   // sperrhip_debug_counter (0..2, and [3] as counter 7)
 
 struct Arena {
   char* base = nullptr;
@@ -281,6 +281,7 @@ struct ShapePlan {
   const uint8_t* d_slotLevel = nullptr;
   const spk::LevelClass* d_levelClass = nullptr;
   const uint32_t* d_wordLeaf = nullptr;   // nullptr: no raster word lies over leaf-word grids
+  const FusedRoot* d_fusedRoots = nullptr;   // non-null: the encoder's 32-bit pass can take k_head_fused (fused_head_roots)
   const uint8_t* d_mxSlot = nullptr;      // k_lis_mx: column of every shape class
   const uint8_t* d_mxLevelGroup = nullptr;
   int l0Level = -1;                       // LIS level of 2x2x2 leaf sets that k_lis_l0 can decode
@@ -295,6 +296,34 @@ struct ShapePlan {
 };
 bool use_tables(const ShapePlan& P);   // (defined with the decoder's plan logic below)
 
+
+// The encoder's fused head (k_head_fused, speck_enc.hip) wants workgroups that own whole pixel tiles AND whole leaf sets:
+// an all-octree forest (cubic power-of-two roots) whose every deepest grid is one pyramid_leaf4 takes (leaf4_block) with
+// even y and z origins, rows that are a power of two with at least two of them in a pixel tile, slices that are whole
+// tiles and come in pairs.  Returns the kernel's root table, empty when the shape does not qualify (256^3, 128^3 and
+// 64^3 chunks do; a chunk with an axis that is no power of two, or under 64 samples a side, does not).
+std::vector<FusedRoot> fused_head_roots(const spk::HostTree& h)
+{
+  std::vector<FusedRoot> out;
+  const uint32_t dx = h.dims[0], dy = h.dims[1], dz = h.dims[2];
+  if (!(h.flags & spk::kTreeAllOct) || (h.flags & spk::kTree2D) || h.roots.empty() || h.roots.size() > (size_t)spk::kMaxRoots)
+    return out;
+  if ((dx & (dx - 1)) != 0 || dx < 8 || dx > (uint32_t)kPixTile / 2 || ((size_t)dx * dy) % kPixTile != 0 || dz % 2 != 0)
+    return out;
+  uint64_t covered = 0;
+  for (const spk::Root& r : h.roots) {
+    const spk::Grid& g = h.grids[r.gridFirst + r.Dmax - 1];
+    const uint32_t side = r.len[0];
+    if (!(g.kind & spk::kGridOct) || g.e[0] < 2 || g.e[1] != g.e[0] || g.e[2] != g.e[0] || r.org[0] % 8 != 0 ||
+        r.org[1] % 2 != 0 || r.org[2] % 2 != 0 || r.len[1] != side || r.len[2] != side || side != (2u << g.e[0]))
+      return std::vector<FusedRoot>();
+    out.push_back(FusedRoot{(uint32_t)r.org[0] | ((uint32_t)r.org[1] << 16), (uint32_t)r.org[2] | (side << 16), g.nodeOff, g.e[0]});
+    covered += (uint64_t)side * side * side;
+  }
+  if (covered != (uint64_t)dx * dy * dz)   // (the roots are disjoint boxes: every sample has a leaf parent)
+    return std::vector<FusedRoot>();
+  return out;
+}
 
 struct Blob {  // host-side staging of all tables of a plan, uploaded in one copy
   std::vector<char> bytes;
@@ -410,6 +439,8 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
                oLC = blob.add(h.levelClass), oWL = blob.add(wordLeaf), oCls = blob.add(h.cls),
                oGC = blob.add(h.gridCls), oIR = blob.add(h.iRoots),
                oMS = blob.add(h.mxSlot), oMG = blob.add(h.mxLevelGroup);
+  const std::vector<FusedRoot> fusedRoots = twoD ? std::vector<FusedRoot>() : fused_head_roots(h);
+  const size_t oFR = blob.add(fusedRoots);
   P.maxK = 0;
   for (const auto& lc : h.levelClass)
     P.maxK = std::max<int>(P.maxK, lc.K);
@@ -471,6 +502,7 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
   P.d_slotLevel = reinterpret_cast<const uint8_t*>(base + oSL);
   P.d_levelClass = reinterpret_cast<const spk::LevelClass*>(base + oLC);
   P.d_wordLeaf = wordLeaf.empty() ? nullptr : reinterpret_cast<const uint32_t*>(base + oWL);
+  P.d_fusedRoots = fusedRoots.empty() ? nullptr : reinterpret_cast<const FusedRoot*>(base + oFR);
 
   // DWT pass list (src/CDF97.cpp:132-139,170-225,284-292,387-429); the inverse runs it backwards
   P.fwd.clear();
@@ -1121,12 +1153,15 @@ struct EncBatchBufs {
   int8_t* msb;
   size_t bytesPerChunk;
   bool aliased;        // the coder's node arrays, birth records and second list lie over `vals` (carve_enc_coder)
+  bool fusedHead;      // the 32-bit pass takes k_head_fused: M, E and leafDesc have memory of their own
   size_t coderBytes;   // ... and take this many bytes for the batch
 };
 
 // the arrays of the integer coder that nothing reads or writes before the quantiser is done: each from
 // `first` when it fits there, else from `second` (may be null)
-bool carve_enc_coder(Arena& first, Arena* second, const ShapePlan& P, uint32_t B, EncBuffers& e)
+// ownLeaf: M, E and leafDesc from `second` whatever room `first` has (the fused head writes them while other workgroups
+// still read the chunk buffer)
+bool carve_enc_coder(Arena& first, Arena* second, const ShapePlan& P, uint32_t B, EncBuffers& e, bool ownLeaf = false)
 {
   const size_t nn = P.dtree.nnodes;
 #define TAKE(dst, T, count)                            \
@@ -1143,13 +1178,28 @@ bool carve_enc_coder(Arena& first, Arena* second, const ShapePlan& P, uint32_t B
   TAKE(e.bornPacked, uint64_t, e.bornStride * B);
   TAKE(e.bornPosLev, uint64_t, e.bornStride * B);
   TAKE(e.lis[1], uint64_t, P.lisEntries * B);
-  TAKE(e.E, uint32_t, nn * B);
+  if (!(ownLeaf && second))
+    TAKE(e.E, uint32_t, nn * B);
   TAKE(e.bucket, uint32_t, nn * B);
   TAKE(e.koff, uint32_t, nn * B);
+  if (ownLeaf && second) {
+    e.E = second->take<uint32_t>(nn * B);
+    e.leafDesc = second->take<uint16_t>(nn * B);
+    e.M = second->take<int8_t>(nn * B);
+    return e.E && e.leafDesc && e.M;
+  }
   TAKE(e.leafDesc, uint16_t, nn * B);
   TAKE(e.M, int8_t, nn * B);
 #undef TAKE
   return true;
+}
+
+// Does the 32-bit pass of this shape take the fused head (SPERR_HIP_ENC_FUSED_HEAD=0: the three kernels, for A/B runs and
+// tests)?  Decides the memory layout (carve_enc) and the launches (EncodeCall::quantise) alike.
+bool enc_fused_head(const ShapePlan& P)
+{
+  static const bool on = !(getenv("SPERR_HIP_ENC_FUSED_HEAD") && atoi(getenv("SPERR_HIP_ENC_FUSED_HEAD")) == 0);
+  return on && P.d_fusedRoots != nullptr;
 }
 
 // carve the arrays of one batch out of the arena; returns false when it does not fit
@@ -1201,7 +1251,8 @@ bool carve_enc(Arena& A, const ShapePlan& P, uint32_t B, uint64_t raw_budget, En
     over.base = reinterpret_cast<char*>(o.vals);
     over.cap = alias ? Npad * B * sizeof(double) : 0;
     const size_t before = A.used;
-    if (!carve_enc_coder(over, &A, P, B, e))
+    o.fusedHead = enc_fused_head(P);
+    if (!carve_enc_coder(over, &A, P, B, e, o.fusedHead))
       return false;
     o.aliased = over.used != 0;
     o.coderBytes = over.used + (A.used - before);
@@ -1260,10 +1311,13 @@ size_t enc_bytes_per_chunk(const ShapePlan& P, uint64_t raw_budget, bool alias =
   return enc_bytes_for(P, 1, raw_budget, alias);
 }
 
-int reset_enc_pass(hipStream_t st, const EncBatchBufs& bb, uint32_t B)
+// (fusedHead: k_head_fused writes the birth plane of EVERY sample of every chunk that takes part in the pass, and whatever
+//  reads bplane -- k_pyramid, k_census, k_emit_pixels -- leaves the other chunks alone (EncState::active): no fill)
+int reset_enc_pass(hipStream_t st, const EncBatchBufs& bb, uint32_t B, bool fusedHead = false)
 {
   const EncBuffers& e = bb.eb;
-  HIP_CHECK(hipMemsetAsync(e.bplane, 0xff, e.pixStride * B, st));
+  if (!fusedHead)
+    HIP_CHECK(hipMemsetAsync(e.bplane, 0xff, e.pixStride * B, st));
   HIP_CHECK(hipMemsetAsync(e.M, 0xff, e.nodeStride * B, st));
   HIP_CHECK(hipMemsetAsync(e.mask, 0, std::max<size_t>(e.maskStride, 1) * B * sizeof(uint64_t), st));
   HIP_CHECK(hipMemsetAsync(e.stream, 0, e.streamStride * B * sizeof(uint64_t), st));
@@ -2137,6 +2191,15 @@ struct EncodeCall {
       return -1;
     if (mode == 3 && pwe_q_setup(b.ss, bb, nb, quality, hcKeep.emplace_back(), pweWide))
       return -1;
+    if (bb.fusedHead) {
+      // quantiser, leaf level of the pyramid and census in one kernel: the fills first (M, E and leafDesc, which the
+      // kernel writes, have memory of their own; what else lies over the chunk buffer is written after it)
+      if (reset_enc_pass(b.ss, bb, nb, true))
+        return -1;
+      const EncPlanHost ph{b.P->d_initLIS, b.P->d_initLen, b.P->d_depthBlocks, b.P->depthBlockOff, b.P->ht.nsets};
+      g_dbg_counter[3]++;
+      return launch_speck_encode_fused_head(b.ss, e, ph, b.raw_budget, bb.vals, bb.valsStride, b.P->d_fusedRoots);
+    }
     if (launch_quantize(b.ss, false, bb.vals, bb.valsStride, nb, b.P->N, bb.coef32, e.coefStride,
                         const_cast<uint64_t*>(e.sign), e.signStride, bb.msb, e.pixStride, e.cst))
       return -1;
@@ -2149,6 +2212,7 @@ struct EncodeCall {
     const ShapePlan& P = *b.P;
     EncBuffers& e = b.bb.eb;
     EncPlanHost& ph = b.ph = EncPlanHost{P.d_initLIS, P.d_initLen, P.d_depthBlocks, P.depthBlockOff, P.ht.nsets};
+    ph.fusedHead = b.bb.fusedHead;   // (quantise() has run k_head_fused)
     // (the census of the pixel passes on a stream of its own beside the pyramid's upper levels: the
     //  decoder's outlier streams and events are idle during a compression call)
     ph.side = E.sideQ[gi % kSubStreams];
@@ -4074,6 +4138,8 @@ unsigned long long sperrhip_debug_counter(int which)
   }
   if (which == 4 || which == 5)   // pinned staging / device bytes the farm's workers hold right now
     return farm_footprint(which == 4);
+  if (which == 7)   // batches whose 32-bit pass took the fused encoder head (k_head_fused)
+    return g_dbg_counter[3].load();
   return which >= 0 && which < 3 ? g_dbg_counter[which].load() : 0ull;
 }
 void sperrhip_debug_lis_stamps(int on, unsigned long long* out64)

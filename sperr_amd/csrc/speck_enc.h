@@ -80,6 +80,15 @@ struct EncBuffers {
   uint32_t iLevels;
 };
 
+// Fused head (k_head_fused): where a root's samples and leaf parents lie.  Every root of a qualifying shape is a cube of
+// `side` samples whose deepest grid has 2^e leaf parents per axis, flat ids from nodeOff on.
+struct FusedRoot {
+  uint32_t org01;      // org[0] | org[1] << 16
+  uint32_t org2side;   // org[2] | side << 16
+  uint32_t nodeOff;
+  uint32_t e;
+};
+
 struct EncPlanHost {
   const uint64_t* d_initLIS;
   const uint32_t* d_initLen;
@@ -101,6 +110,9 @@ struct EncPlanHost {
   uint32_t* d_bound = nullptr;
   uint32_t* h_bound = nullptr;
   hipEvent_t evBound = nullptr;
+  // launch_speck_encode_fused_head() has run for this batch's 32-bit pass: the states are initialised, the leaf parents'
+  // pyramid level and the census are done -- launch_speck_encode_head() does the rest (ignored by the 64-bit pass)
+  bool fusedHead = false;
 };
 
 int launch_speck_encode(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan,
@@ -110,6 +122,13 @@ int launch_speck_encode_head(hipStream_t stream, const EncBuffers& b, const EncP
                              uint64_t raw_budget, bool rate_mode, bool wide_pass);
 int launch_speck_encode_planes(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan,
                                uint64_t raw_budget, bool rate_mode, bool wide_pass);
+// The 32-bit pass of a shape whose workgroups can own whole pixel tiles and whole leaf parents (`roots`: one FusedRoot per
+// root of the tree, on the device; the engine decides per ShapePlan): k_enc_state_init, then ONE kernel that quantises the
+// fp64 coefficients (what launch_quantize does), builds the leaf parents' level of the pyramid and takes the census of the
+// pixel passes.  M must hold its 0xff fill and must not lie over `vals`.  Then launch_speck_encode_head() with
+// plan.fusedHead set.
+int launch_speck_encode_fused_head(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan, uint64_t raw_budget,
+                                   const double* vals, size_t valsStride, const FusedRoot* roots);
 
 }  // namespace sperrhip
 #endif

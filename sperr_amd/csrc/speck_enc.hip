@@ -5,11 +5,15 @@
 // traversal that appends one bit at a time.  Every bit it emits, and the position it lands on, is
 // a pure function of the msb of each coefficient and of each set's largest coefficient, so the
 // stream is produced here as count -> scan -> scatter (tests/model/speck_model.cpp is the CPU
-// model of exactly these kernels and is pinned bit-for-bit against the oracle):
+// model of these kernels' arrays and passes, one loop per kernel, and is pinned bit-for-bit against
+// the oracle; where two kernels here are one launch -- k_head_fused -- the model keeps its loops
+// apart: the arrays they fill, and every value in them, are the same):
 //
 //   k_pyramid        bottom-up: M[node] = msb of the set's largest coefficient, E[node] = bits the
 //                    set's split emits, bplane[pixel] = plane at which the pixel enters the LIP
 //   k_census/_scan   per pixel tile and plane: bits of the LIP scan and of the refinement pass
+//   k_head_fused     (64^3 .. 512^3 chunks, 32-bit pass) the quantiser, the leaf parents' level of k_pyramid and
+//                    k_census in one pass over the fp64 coefficients
 //   per plane p:
 //     k_list_count / k_list_scan / k_list_apply   positions of the LIS entries (list order is
 //                    part of the format), their '1' test bits, list compaction
@@ -408,7 +412,7 @@ __device__ __forceinline__ void pyramid_leaf4(const EncBuffers& b, uint32_t c, u
 constexpr int kNodePerMax = 8;
 template <bool ANY>
 __global__ void __launch_bounds__(kNodeBlock)
-k_pyramid(EncBuffers b, const uint32_t* depthBlocks, uint32_t nblk, uint32_t per)
+k_pyramid(EncBuffers b, const uint32_t* depthBlocks, uint32_t nblk, uint32_t per, int leafDone)
 {
   const uint32_t c = blockIdx.y;
   EncState& s = b.st[c];
@@ -426,7 +430,7 @@ k_pyramid(EncBuffers b, const uint32_t* depthBlocks, uint32_t nblk, uint32_t per
     if (bi >= nblk)
       break;
     const uint32_t blk = depthBlocks[bi];
-    if (leaf4_block(b.tree, blk))   // (uniform over the wavefront)
+    if (!leafDone && leaf4_block(b.tree, blk))   // (uniform over the wavefront; leafDone: k_head_fused has taken them)
       pyramid_leaf4(b, c, blk * kNodeBlock + lane * 4u, h);
   }
   // every other block: a node per thread
@@ -687,6 +691,215 @@ __global__ void __launch_bounds__(kThreads) k_census_scan(EncBuffers b)
       s.lipTot[p] = carry;
     else
       s.refTot[p] = carry;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_head_fused: quantiser + leaf parents' level of the pyramid + census, one pass over the fp64 coefficients
+// ------------------------------------------------------------------------------------------
+// What k_quantize4 (xform.hip), the deepest launches of k_pyramid (pyramid_leaf4) and k_census write, from one read of the
+// chunk buffer: the second and third of those passes only ever consumed the msb and sign the first had in registers.
+// A workgroup owns the same kPixTile samples -- whole rows -- of the slices z and z + 1: two pixel tiles, and every
+// 2x2x2 leaf set whose samples they hold.
+//   phase 1  streams the two tiles like k_quantize4 (four consecutive samples a thread, 32-byte loads, 16-byte stores of the
+//            magnitudes), and leaves the msb bytes and sign words in LDS as well as in memory;
+//   phase 2  a thread takes eight samples of x in two rows of both slices out of LDS -- four leaf parents in a row, as
+//            pyramid_leaf4 does -- and writes M, E, leafDesc and the birth planes; the samples' (msb, birth plane) go to the
+//            two tiles' histograms on the way, which k_census's scan over the bins then turns into pixCnt.
+// The shapes that qualify (all-octree trees of cubic roots at least eight samples wide on multiples of eight, rows that
+// divide kPixTile: the engine decides per ShapePlan) make every index below a shift; `roots` maps a sample group to the flat
+// id of its leaf parent.  M, E and leafDesc must not lie over `vals`: other workgroups are still reading it.
+__global__ void __launch_bounds__(kThreads)
+k_head_fused(EncBuffers b, const double* vals, size_t valsStride, uint32_t* coef, uint64_t* sign, int8_t* msb,
+             const FusedRoot* roots, int lgRow, int maxPlanes)
+{
+  static_assert(kThreads * 32 == 2 * kPixTile && kThreads * kPixPer == kPixTile, "two pixel tiles, 32 samples a thread");
+  static_assert(kMaxPlanes == 64, "one wavefront scans the bins");
+  const uint32_t c = blockIdx.y;
+  const CoderState& cs = b.cst[c];
+  if (cs.is_const)
+    return;
+  EncState& s = b.st[c];
+  const bool act = s.active != 0;   // (k_enc_state_init has run; a chunk that waits for the 64-bit pass is quantised only)
+  __shared__ uint32_t msbL[2 * kPixTile / 4];
+  __shared__ uint64_t signL[2 * kPixTile / 64];
+  __shared__ FusedRoot rootL[kMaxRoots];
+  // as k_census: bin q + 1 counts value q; [0]: msb, low half all samples, high half those that wait in the LIP; [1]: birth
+  __shared__ uint32_t hist[kThreads / 64][2][2][kMaxPlanes + 1];
+  __shared__ uint32_t h[kMaxPlanes];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < (kThreads / 64) * 2 * 2 * (kMaxPlanes + 1); i += kThreads)
+    (&hist[0][0][0][0])[i] = 0;
+  if (tid < kMaxPlanes)
+    h[tid] = 0;
+  const Tree& t = b.tree;
+  if (tid < t.nroots)
+    rootL[tid] = roots[tid];
+  const uint32_t sliceTiles = (t.dims[0] * t.dims[1]) / kPixTile;
+  const uint32_t zp = blockIdx.x / sliceTiles, jt = blockIdx.x % sliceTiles;
+  const uint32_t tileId[2] = {2u * zp * sliceTiles + jt, (2u * zp + 1u) * sliceTiles + jt};
+
+  // ---- phase 1: the quantiser (SPECK_FLT.cpp:345-368), exactly k_quantize4's arithmetic
+  const double inv = 1.0 / cs.q;
+  const uint32_t lane = tid & 63u;
+#pragma unroll
+  for (int it = 0; it < 8; it++) {
+    const uint32_t l = (uint32_t)(it >> 2) * kPixTile + ((uint32_t)(it & 3) * kThreads + tid) * 4u;   // in the two tiles
+    const uint32_t g = tileId[it >> 2] * kPixTile + (l & (kPixTile - 1u));                             // in the chunk
+    const double2* in = reinterpret_cast<const double2*>(vals + c * valsStride + g);
+    const double2 a = in[0], b2 = in[1];
+    const double v[4] = {a.x, a.y, b2.x, b2.y};
+    uint32_t mag[4], mb = 0, nn = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const long long ll = __double2ll_rn(v[e] * inv);
+      nn |= (ll >= 0 ? 1u : 0u) << e;
+      const unsigned long long m = (unsigned long long)(ll < 0 ? -ll : ll);
+      mag[e] = (uint32_t)m;
+      mb |= (uint32_t)(uint8_t)(m ? (int8_t)(63 - __clzll((long long)m)) : (int8_t)-1) << (8 * e);
+    }
+    *reinterpret_cast<uint4*>(coef + c * b.coefStride + g) = make_uint4(mag[0], mag[1], mag[2], mag[3]);
+    *reinterpret_cast<uint32_t*>(msb + c * b.pixStride + g) = mb;
+    msbL[l >> 2] = mb;
+    uint64_t word = (uint64_t)nn << (4 * (lane & 15u));   // 16 lanes x 4 bits = one sign word
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1)
+      word |= __shfl_xor(word, d, 64);
+    if ((lane & 15u) == 0) {
+      sign[c * b.signStride + (g >> 6)] = word;
+      signL[l >> 6] = word;
+    }
+  }
+  if (!act)
+    return;   // (uniform)
+  __syncthreads();
+
+  // ---- phase 2: four leaf parents a thread (pyramid_leaf4) and their 32 samples' census
+  const uint32_t dx = t.dims[0];
+  const uint32_t x = (tid & ((dx >> 3) - 1u)) * 8u, lrow = (tid >> (lgRow - 3)) * 2u;
+  const uint32_t y = jt * ((uint32_t)kPixTile >> lgRow) + lrow, z = 2u * zp;
+  uint32_t id0 = 0;
+  for (int r = (int)t.nroots - 1; r >= 0; r--) {   // (the large subbands come last)
+    const FusedRoot fr = rootL[r];
+    const uint32_t ox = x - (fr.org01 & 0xffffu), oy = y - (fr.org01 >> 16), oz = z - (fr.org2side & 0xffffu);
+    const uint32_t side = fr.org2side >> 16;
+    if (ox < side && oy < side && oz < side) {
+      id0 = fr.nodeOff + (((((oz >> 1) << fr.e) + (oy >> 1)) << fr.e) + (ox >> 1));
+      break;
+    }
+  }
+  uint2 rows[4];
+  uint32_t sg[4], lofs[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {   // row k: y + (k & 1), z + (k >> 1)
+    lofs[k] = (uint32_t)(k >> 1) * kPixTile + ((lrow + (uint32_t)(k & 1)) << lgRow) + x;
+    rows[k] = *reinterpret_cast<const uint2*>(&msbL[lofs[k] >> 2]);
+    sg[k] = reinterpret_cast<const uint8_t*>(signL)[lofs[k] >> 3];   // (eight samples of one sign word)
+  }
+  const uint32_t wave = tid >> 6;
+  uint32_t zeroM[2] = {0, 0}, zeroB[2] = {0, 0};
+  uint32_t mPack = 0, ePack[4], dPack[2] = {0, 0};
+  int mv[4];
+#pragma unroll
+  for (int n = 0; n < 4; n++) {
+    int km[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {   // child j = (x + (j & 1), y + ((j >> 1) & 1), z + (j >> 2))
+      const uint2 rw = rows[((j >> 1) & 1) + 2 * (j >> 2)];
+      const uint32_t byte = 2u * (uint32_t)n + (uint32_t)(j & 1);
+      km[j] = (int)(int8_t)(((byte < 4 ? rw.x : rw.y) >> (8u * (byte & 3u))) & 0xffu);
+    }
+    int m = -1;
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      m = max(m, km[j]);
+    uint32_t bits = 0, desc = 0;
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const bool coded = found || j != 7;
+      bits += coded ? 1u : 0u;
+      if (!coded || km[j] == m) {
+        found = true;
+        bits += 1u;
+      }
+      desc |= (uint32_t)(km[j] == m) << j;
+      desc |= ((sg[((j >> 1) & 1) + 2 * (j >> 2)] >> (2u * (uint32_t)n + (uint32_t)(j & 1))) & 1u) << (8 + j);
+    }
+    mv[n] = m;
+    mPack |= ((uint32_t)m & 0xffu) << (8 * n);
+    ePack[n] = m >= 0 ? bits : 0u;
+    dPack[n >> 1] |= (desc & 0xffffu) << (16 * (n & 1));
+    if (m >= 0)
+      atomicAdd(&h[m], 1u);
+    // census: children 0..3 lie in the first tile, 4..7 in the second; all eight are born on plane m.  The zero bins
+    // (most samples) are summed over the wavefront below; the four samples a tile has of this set share one birth atomic
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      if (km[j] < 0)
+        zeroM[j >> 2]++;
+      else
+        atomicAdd(&hist[wave][j >> 2][0][km[j] + 1], m > km[j] ? 0x10001u : 1u);
+    }
+    if (m < 0) {
+      zeroB[0] += 4;
+      zeroB[1] += 4;
+    }
+    else {
+      atomicAdd(&hist[wave][0][1][m + 1], 4u);
+      atomicAdd(&hist[wave][1][1][m + 1], 4u);
+    }
+  }
+  *reinterpret_cast<uint32_t*>(b.M + c * b.nodeStride + id0) = mPack;
+  *reinterpret_cast<uint4*>(b.E + c * b.nodeStride + id0) = make_uint4(ePack[0], ePack[1], ePack[2], ePack[3]);
+  *reinterpret_cast<uint2*>(b.leafDesc + c * b.nodeStride + id0) = make_uint2(dPack[0], dPack[1]);
+  // the samples' birth planes: their parent's msb, two samples a node
+  const uint32_t pairs[4] = {((uint32_t)mv[0] & 0xffu) * 0x0101u, ((uint32_t)mv[1] & 0xffu) * 0x0101u,
+                             ((uint32_t)mv[2] & 0xffu) * 0x0101u, ((uint32_t)mv[3] & 0xffu) * 0x0101u};
+  const uint2 bp = make_uint2(pairs[0] | (pairs[1] << 16), pairs[2] | (pairs[3] << 16));
+  int8_t* bplane = b.bplane + c * b.pixStride;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    *reinterpret_cast<uint2*>(bplane + tileId[k >> 1] * kPixTile + (lofs[k] & (kPixTile - 1u))) = bp;
+#pragma unroll
+  for (int tt = 0; tt < 2; tt++) {
+    uint32_t zz = zeroM[tt] | (zeroB[tt] << 16);   // both at most 1024 per wavefront and tile
+    for (int d = 32; d > 0; d >>= 1)
+      zz += __shfl_xor(zz, d, 64);
+    if (lane == 0) {
+      atomicAdd(&hist[wave][tt][0][0], zz & 0xffffu);
+      atomicAdd(&hist[wave][tt][1][0], zz >> 16);
+    }
+  }
+  __syncthreads();
+  if (tid < kMaxPlanes && h[tid])
+    atomicAdd(&s.bucketCnt[tid], h[tid]);
+  // the tiles' histograms (sum over the wavefronts), then their running sums over the bins: k_census's, a wavefront a tile
+  __shared__ uint32_t tot[2][2][kMaxPlanes + 1];
+  __shared__ uint64_t pre[2][kMaxPlanes + 1];
+  for (uint32_t i = tid; i < 2 * 2 * (kMaxPlanes + 1); i += kThreads) {
+    uint32_t v = 0;
+    for (int w = 0; w < kThreads / 64; w++)
+      v += (&hist[w][0][0][0])[i];   // (both 16-bit halves of [0] stay below 2^13)
+    (&tot[0][0][0])[i] = v;
+  }
+  __syncthreads();
+  if (tid < 128) {
+    const uint32_t tt = tid >> 6;
+    const uint64_t v = (uint64_t)(tot[tt][0][lane] & 0xffffu) | ((uint64_t)tot[tt][1][lane] << 32);
+    const uint64_t inc = wave_inclusive_scan<uint64_t>(v);
+    pre[tt][lane] = inc;
+    if (lane == 63)
+      pre[tt][64] = inc + ((uint64_t)(tot[tt][0][64] & 0xffffu) | ((uint64_t)tot[tt][1][64] << 32));
+  }
+  __syncthreads();
+  if (tid < 128 && (int)lane < maxPlanes) {
+    const uint32_t tt = tid >> 6, p = lane;
+    const uint32_t le_m = (uint32_t)pre[tt][p + 1], le_b = (uint32_t)(pre[tt][p + 1] >> 32);
+    const uint32_t all_m = (uint32_t)pre[tt][kMaxPlanes], eq = tot[tt][0][p + 1] >> 16;
+    uint32_t* cnt = b.pixCnt + c * b.pixCntStride + (tt ? tileId[1] : tileId[0]);
+    cnt[(size_t)(p * 2 + 0) * b.nPixTiles] = le_m - le_b + eq;   // LIP scan bits
+    cnt[(size_t)(p * 2 + 1) * b.nPixTiles] = all_m - le_m;       // refinement bits
   }
 }
 
@@ -1604,8 +1817,7 @@ static uint32_t node_blocks_per_group(uint32_t nb, uint32_t nc)
   return per;
 }
 
-int launch_speck_encode_head(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan,
-                             uint64_t raw_budget, bool rate_mode, bool wide_pass)
+static uint64_t coder_budget(uint64_t raw_budget)
 {
   uint64_t budget = ~0ull;
   if (raw_budget != 0) {  // SPECK_INT.cpp:48-58
@@ -1613,22 +1825,56 @@ int launch_speck_encode_head(hipStream_t stream, const EncBuffers& b, const EncP
     while (budget % 8)
       budget++;
   }
+  return budget;
+}
+
+int launch_speck_encode_fused_head(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan, uint64_t raw_budget,
+                                   const double* vals, size_t valsStride, const FusedRoot* roots)
+{
+  const uint32_t nc = b.nchunks;
+  int lgRow = 0;
+  while ((1u << lgRow) < b.tree.dims[0])
+    lgRow++;
+  // (what the engine has checked of the shape, as far as the kernel's indexing depends on it)
+  if ((1u << lgRow) != b.tree.dims[0] || lgRow < 3 || (kPixTile >> lgRow) < 2 || (b.tree.dims[1] << lgRow) % kPixTile != 0 ||
+      b.tree.dims[2] % 2 != 0 || b.tree.nroots > (uint32_t)kMaxRoots || b.nPixTiles % 2 != 0 ||
+      b.nPixTiles * (uint32_t)kPixTile != b.tree.nvals) {
+    fprintf(stderr, "[sperr_hip] the fused encoder head was asked for a shape it does not take\n");
+    return -1;
+  }
+  LAUNCH_K(k_enc_state_init, dim3((nc + 63) / 64), dim3(64), 0, stream, b, plan.d_initLIS, plan.d_initLen,
+           coder_budget(raw_budget), 0);
+  LAUNCH_K(k_head_fused, dim3(b.nPixTiles / 2, nc), dim3(kThreads), 0, stream, b, vals, valsStride,
+           const_cast<uint32_t*>(static_cast<const uint32_t*>(b.coef)), const_cast<uint64_t*>(b.sign),
+           const_cast<int8_t*>(b.msb), roots, lgRow, 32);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_speck_encode_head(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan,
+                             uint64_t raw_budget, bool rate_mode, bool wide_pass)
+{
+  const uint64_t budget = coder_budget(raw_budget);
   const uint32_t nc = b.nchunks;
   const dim3 perChunk((nc + 63) / 64);
-  LAUNCH_K(k_enc_state_init, perChunk, dim3(64), 0, stream, b, plan.d_initLIS,
-                     plan.d_initLen, budget, wide_pass ? 1 : 0);
+  // (fused: k_enc_state_init, the leaf parents' level of the pyramid and the census are k_head_fused's)
+  const bool fused = plan.fusedHead && !wide_pass;
+  if (!fused)
+    LAUNCH_K(k_enc_state_init, perChunk, dim3(64), 0, stream, b, plan.d_initLIS,
+                       plan.d_initLen, budget, wide_pass ? 1 : 0);
   const int maxPlanes = wide_pass ? kMaxPlanes : 32;
-  const bool sideCensus = plan.side && plan.evFork && plan.evJoin && b.tree.maxDepth >= 2;
+  const bool sideCensus = !fused && plan.side && plan.evFork && plan.evJoin && b.tree.maxDepth >= 2;
   for (int d = (int)b.tree.maxDepth - 1; d >= 0; d--) {
     const uint32_t nb = plan.depthBlockOff[d + 1] - plan.depthBlockOff[d];
-    if (nb) {
+    // (fused: every root's deepest grid is done, so nothing is left of the deepest depth)
+    if (nb && !(fused && d == (int)b.tree.maxDepth - 1)) {
       const uint32_t per = node_blocks_per_group(nb, nc);
       if (b.tree.flags & kTreeAllOct)
         LAUNCH_K(k_pyramid<false>, dim3((nb + per - 1) / per, nc), dim3(kNodeBlock), 0, stream, b,
-                 plan.d_depthBlocks + plan.depthBlockOff[d], nb, per);
+                 plan.d_depthBlocks + plan.depthBlockOff[d], nb, per, fused ? 1 : 0);
       else
         LAUNCH_K(k_pyramid<true>, dim3((nb + per - 1) / per, nc), dim3(kNodeBlock), 0, stream, b,
-                 plan.d_depthBlocks + plan.depthBlockOff[d], nb, per);
+                 plan.d_depthBlocks + plan.depthBlockOff[d], nb, per, 0);
     }
     if (sideCensus && d == 0) {
       // every sample's birth plane is known now (samples are born at any depth: the roots' trees differ in
@@ -1653,7 +1899,7 @@ int launch_speck_encode_head(hipStream_t stream, const EncBuffers& b, const EncP
     HIP_CHECK(hipEventRecord(plan.evJoin, plan.side));
     HIP_CHECK(hipStreamWaitEvent(stream, plan.evJoin, 0));
   }
-  else
+  else if (!fused)
     LAUNCH_K(k_census, dim3(b.nPixTiles, nc), dim3(kThreads), 0, stream, b, maxPlanes);
   LAUNCH_K(k_census_scan, dim3(maxPlanes * 2, nc), dim3(kThreads), 0, stream, b);
   if (plan.d_bound && plan.h_bound && plan.evBound) {
