@@ -1900,9 +1900,11 @@ void drain_after_error(Engine& E, hipStream_t st)
   E.pweLastStream = nullptr;
 }
 
-// One compression call (compress_impl), stage by stage.  slice: 0 = a 3D container; 1 / 2 = one 2D slice
-// without / with the 10-byte header.  mode 1: fixed rate, `quality` bits per value; mode 2: fixed PSNR and
-// mode 3: fixed point-wise error, every bit plane is coded
+// what a compression call makes: a 3D container, or one 2D slice without / with the 10-byte header
+enum class Coded { Container, Slice, SliceWithHeader };
+
+// One compression call (compress_impl), stage by stage.  mode 1: fixed rate, `quality` bits per value; mode 2: fixed
+// PSNR and mode 3: fixed point-wise error, every bit plane is coded
 template <typename T>
 struct EncodeCall {
   using GKey = std::array<size_t, 4>;   // chunk extents + part
@@ -1928,12 +1930,13 @@ struct EncodeCall {
   uint8_t* d_dst;
   size_t dst_cap;
   hipStream_t st;
-  const int slice;
+  const Coded what;
   // a batch (sperrhip_compress_batch_dev): nvol volumes of dims `vol` back to back in d_src, read as one volume of
   // (x, y, nvol z) -- the stacked view -- whose chunks are each volume's, and coded into nvol containers.  With
   // `slice` (sperrhip_compress_2d_batch_dev): nvol slices, chunk s of dims (x, y, 1) at (0, 0, s), one shape group on
   // the 2D coder's forest, coded into nvol streams (k_slice_batch_layout)
   const size_t nvol = 1;
+  const bool slice = what != Coded::Container;
   const bool rate = mode == 1;
   const double bpp = rate ? quality : 0.0;
   const VolDesc vd{{vol[0], vol[1], vol[2] * nvol}};
@@ -2314,14 +2317,14 @@ struct EncodeCall {
   {
     // (the header kernels write before any length is known to them: check its room here)
     const uint32_t cpv = (uint32_t)(nchunks / nvol);   // chunks per container
-    if (dst_cap < (slice ? (slice == 2 ? 10u : 0u) : ((cpv > 1 ? 20u : 14u) + 4ull * cpv) * nvol)) {
+    if (dst_cap < (slice ? (what == Coded::SliceWithHeader ? 10u : 0u) : ((cpv > 1 ? 20u : 14u) + 4ull * cpv) * nvol)) {
       fprintf(stderr, "[sperr_hip] output buffer too small for the container header (%zu bytes)\n", dst_cap);
       return -1;
     }
     if (nvol > 1 && slice)   // (a batch of slices: no length tables, a header per stream if any)
       LAUNCH_K(k_slice_batch_layout, dim3(1), dim3(kBatchThreads), 0, st, d_dst, (uint64_t)dst_cap, d_lens, d_lens2,
                d_offs, nchunks, (uint32_t)vol[0], (uint32_t)vol[1], std::is_same<T, float>::value ? 1 : 0,
-               slice == 2 ? 1 : 0, d_total);
+               what == Coded::SliceWithHeader ? 1 : 0, d_total);
     else if (nvol > 1)   // (one container: k_container_header, as before)
       LAUNCH_K(k_batch_container, dim3(1), dim3(kBatchThreads), 0, st, d_dst, (uint64_t)dst_cap, d_lens, d_lens2,
                d_offs, nchunks, cpv, (uint32_t)vol[0], (uint32_t)vol[1], (uint32_t)vol[2], (uint32_t)cdim[0],
@@ -2329,7 +2332,7 @@ struct EncodeCall {
     else if (slice)
       LAUNCH_K(k_slice_header, dim3(1), dim3(1), 0, st, d_dst, d_lens, d_lens2, d_offs,
                (uint32_t)vol[0], (uint32_t)vol[1], std::is_same<T, float>::value ? 1 : 0,
-               slice == 2 ? 1 : 0, d_total);
+               what == Coded::SliceWithHeader ? 1 : 0, d_total);
     else
       LAUNCH_K(k_container_header, dim3(1), dim3(1), 0, st, d_dst, d_lens, d_lens2, d_offs, nchunks,
                (uint32_t)vol[0], (uint32_t)vol[1], (uint32_t)vol[2], (uint32_t)cdim[0],
@@ -2364,9 +2367,9 @@ struct EncodeCall {
 
 template <typename T>
 int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkPref, int mode, double quality,
-                  uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st, int slice = 0)
+                  uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st, Coded what = Coded::Container)
 {
-  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, slice};
+  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, what};
   if (call.run(chunkPref))
     return -1;
   *dst_len = (size_t)call.total;
@@ -2377,9 +2380,10 @@ int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkP
 // [offsets[v], offsets[v + 1])
 template <typename T>
 int compress_batch_impl(Engine& E, const T* d_src, size_t nvol, const Dims& vol, const Dims& chunkPref, int mode,
-                        double quality, uint8_t* d_dst, size_t dst_cap, size_t* offsets, hipStream_t st, int slice = 0)
+                        double quality, uint8_t* d_dst, size_t dst_cap, size_t* offsets, hipStream_t st,
+                        Coded what = Coded::Container)
 {
-  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, slice, nvol};
+  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, what, nvol};
   if (call.run(chunkPref))
     return -1;
   if (nvol == 1) {
@@ -2781,16 +2785,53 @@ k_sub_volume(const double* vals, size_t valsStride, const CoderState* cst, const
   }
 }
 
-// One level of the hierarchy alone (sperrhip_decompress_level_dev): level h, coarsest first, and the box
-// [lo, lo + dims) of it in the level's coordinates.  The level is the grid of the chunks' corners of resolution
-// cres[h], so the chunks the box meets are box_chunks of the level's dims with cres[h] as the chunk size
-struct LevelSel {
+// A window of a call's output, [lo, lo + dims), and the chunks it meets (box_chunks, chunk_volume order).  Either a
+// box of the volume at full resolution (sperrhip_decompress_box_dev), or -- `level` -- a box of level h of the
+// hierarchy alone, coarsest first, in the level's coordinates (sperrhip_decompress_level_dev).  The level is the grid
+// of the chunks' corners of resolution cres[h], so the chunks its box meets are box_chunks of the level's dims with
+// cres[h] as the chunk size
+struct Window {
+  Dims lo, dims;
+  std::vector<uint32_t> ids;
+  bool crop = false;    // the window is not all of what it is a window of (window_select)
+  bool level = false;   // of level h of m; otherwise of the volume
   size_t h = 0;
   MultiRes m;
-  Dims lo, dims;
-  bool crop = false;   // the box is not the whole level
-  std::vector<uint32_t> ids;
+  // the chunk at `org` of dims `cd`, in the coordinates the window is given in: its origin and extent
+  void place(const uint32_t org[3], const uint32_t cd[3], size_t o[3], size_t ext[3]) const
+  {
+    for (int a = 0; a < 3; a++) {
+      ext[a] = level ? m.cres[h][a] : cd[a];
+      o[a] = level ? org[a] / cd[a] * ext[a] : org[a];
+    }
+  }
+  // what a chunk at `o` of extent `ext` (both as place() gives them) writes of the window, and where
+  CropGeom crop_geom(const size_t o[3], const size_t ext[3]) const
+  {
+    CropGeom g;
+    for (int a = 0; a < 3; a++) {
+      const size_t hi = lo[a] + dims[a];
+      g.rel[a] = (int32_t)((int64_t)o[a] - (int64_t)lo[a]);
+      g.lo[a] = (uint32_t)(lo[a] > o[a] ? lo[a] - o[a] : 0);
+      g.hi[a] = (uint32_t)std::min<size_t>(hi - o[a], ext[a]);
+    }
+    return g;
+  }
 };
+
+// The window [lo, lo + dims) of `full`, which chunks of `chunk` tile: false when it is empty, leaves `full`, or is too
+// long along an axis for a chunk's origin relative to it (CropGeom::rel).  One that is all of `full` crops nothing
+bool window_select(const Dims& full, const Dims& chunk, const size_t lo[3], const size_t dims[3], Window& w)
+{
+  for (int a = 0; a < 3; a++) {
+    if (dims[a] > (size_t)INT32_MAX)
+      return false;
+    w.lo[a] = lo[a];
+    w.dims[a] = dims[a];
+  }
+  w.crop = !(w.lo == Dims{0, 0, 0} && w.dims == full);
+  return box_chunks(full, chunk, w.lo, w.dims, w.ids);
+}
 
 // The coarsest level's corner: no inverse pass runs before it is read, so nothing has dequantised it (LiftFuse mode 2
 // does that as a pass loads).  k_inv_quantize for the corner box [0, s) of every chunk with 32-bit coefficients, into
@@ -2879,11 +2920,73 @@ k_level_write(const double* vals, size_t valsStride, const CoderState* cst, cons
   out[o] = (OT)v;
 }
 
-// a sub-box of the volume to decode (sperrhip_decompress_box_dev): [lo, lo + dims), and the chunks it
-// meets (box_chunks, chunk_volume order)
-struct BoxSel {
-  Dims lo, dims;
-  std::vector<uint32_t> ids;
+// What one decompression call decodes, and what it writes: everything DecodeCall needs to know beside the container
+// `ci` and the buffers.  The two halves are independent but for the pairs valid() excludes
+struct DecodeRequest {
+  using ChunkList = std::vector<std::array<size_t, 6>>;
+  // ---- the source: where the chunks come from
+  // a batch (sperrhip_decompress_batch_dev): the chunks of every container, z origins shifted into the stacked view
+  // that `ci` describes -- the volume (x, y, nvol z) and every chunk's absolute offset and length (null: the chunks
+  // of the one container, chunk_volume)
+  const ChunkList* stacked = nullptr;
+  // the chunks are slices, decoded on the 2D coder's forest: `ci` describes one chunk of dims (x, y, 1) whose stream
+  // starts at d_src, or with `stacked` a batch of them, chunk s of dims (x, y, 1) at (0, 0, s)
+  bool slices = false;
+  // a batch of slices whose streams carry the 10-byte header (sperrhip_decompress_2d_batch_dev): ci.off points behind
+  // each header; {dimx, dimy} that every header has to name (null: no headers)
+  const uint32_t* sliceHdr = nullptr;
+  // ---- the output: what d_dst receives
+  // null: the whole volume.  A box of it: only the chunks the box meets are read and decoded, and d_dst is the box.
+  // One level alone or a box of it: the same, the inverse passes stop at the level and no outlier stream is looked at
+  const Window* window = nullptr;
+  // beside the volume, every level of the hierarchy into levels->d_level (sperrhip_decompress_multires_dev)
+  const MultiRes* levels = nullptr;
+
+  // (a box that is the whole volume is no window: such a call is the whole-volume decode)
+  void set_window(const Window& w) { window = (w.level || w.crop) ? &w : nullptr; }
+
+  // every combination of source and output the decoder refuses
+  bool valid() const
+  {
+    if (window && slices)   // a window is cut along a container's chunk grid; a slice is one chunk
+      return false;
+    if (window && levels)   // the side outputs are whole levels: a box reads only some chunks, a level stops before the rest
+      return false;
+    if (stacked && levels)   // the stacked view is no volume with a hierarchy: each container has its own
+      return false;
+    if (level() && stacked)   // a level's grid of chunk corners is one container's
+      return false;
+    if (level() && level()->h >= level()->m.nlev)   // the container has no such level
+      return false;
+    return true;
+  }
+
+  // the level the inverse stops at (null: it runs to full resolution)
+  const Window* level() const { return window && window->level ? window : nullptr; }
+  // the chunks' windows travel to the device (DecBatchBufs::crop, the kCrop writers)
+  bool cropped() const { return window && window->crop; }
+  // (a level is taken before the outlier correctors are added, src/SPECK_FLT.cpp:568-603: no stream of them is read)
+  bool reads_outliers() const { return !level(); }
+  ChunkList chunks(const ContainerInfo& ci) const { return stacked ? *stacked : chunk_volume(ci.vol, ci.chunk); }
+  // The chunks of the call, slot by slot: slot i is chunk sel[i] of chunks() (all of them in order, or the window's)
+  std::vector<uint32_t> slots(size_t nchunks) const
+  {
+    if (window)
+      return window->ids;
+    std::vector<uint32_t> sel(nchunks);
+    std::iota(sel.begin(), sel.end(), 0u);
+    return sel;
+  }
+  // the output: the volume, or the window (its chunks write their pieces of it)
+  VolDesc out_desc(const ContainerInfo& ci) const
+  {
+    return window ? VolDesc{{window->dims[0], window->dims[1], window->dims[2]}}
+                  : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
+  }
+  size_t out_vals(const ContainerInfo& ci) const
+  {
+    return window ? window->dims[0] * window->dims[1] * window->dims[2] : ci.nvals;
+  }
 };
 
 // bytes carve_dec takes for one chunk
@@ -2908,10 +3011,8 @@ DecPlanHost dec_plan_host(const ShapePlan& P)
   return ph;
 }
 
-// One decompression call (decompress_impl), stage by stage.  slice: `ci` describes one chunk of dims (x, y, 1) whose
-// stream starts at d_src (2D coder); with `list`, a batch of slices: chunk s of dims (x, y, 1) at (0, 0, s).  box: only
-// the chunks the box meets are read and decoded, and d_dst is the box (not with mr or slice).  lvl: one level of the
-// hierarchy alone, or a box of it (LevelSel, enqueue_level)
+// One decompression call (decompress_impl), stage by stage.  What is decoded and where it goes is `req`'s to say
+// (DecodeRequest: its source and its output); no stage asks anything else
 template <typename T>
 struct DecodeCall {
   struct Ref {
@@ -2957,27 +3058,10 @@ struct DecodeCall {
   T* d_dst;
   const ContainerInfo& ci;
   hipStream_t st;
-  const MultiRes* mr;
-  const bool slice;
-  const BoxSel* box;
-  // a batch (sperrhip_decompress_batch_dev): the chunks of every container, z origins shifted into the stacked view
-  // that `ci` describes -- the volume (x, y, nvol z) and every chunk's absolute offset and length (null: chunk_volume)
-  const std::vector<std::array<size_t, 6>>* list = nullptr;
-  // a batch of slices whose streams carry the 10-byte header (sperrhip_decompress_2d_batch_dev): ci.off points behind
-  // each header; {dimx, dimy} that every header has to name (null: no headers)
-  const uint32_t* sliceHdr = nullptr;
-  // one level of the hierarchy alone (sperrhip_decompress_level_dev): only the chunks its box meets are read, the
-  // inverse passes stop at the level, no outlier stream is looked at, and d_dst is the level or the box of it (not
-  // with mr, slice, box or list)
-  const LevelSel* lvl = nullptr;
-  // the output: the volume, or the box (its chunks write their windows: CropGeom, the kCrop writers)
-  const VolDesc vd = box ? VolDesc{{box->dims[0], box->dims[1], box->dims[2]}}
-                     : lvl ? VolDesc{{lvl->dims[0], lvl->dims[1], lvl->dims[2]}}
-                           : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
-  // the chunks' windows travel to the device (DecBatchBufs::crop)
-  bool cropped() const { return box != nullptr || (lvl && lvl->crop); }
-  // The chunks of this call, slot by slot: slot i is container chunk sel[i] (all of them in order, or the
-  // box's).  Heads, outlier heads and batches are per slot; offsets and lengths come from the container.
+  const DecodeRequest& req;
+  const VolDesc vd = req.out_desc(ci);
+  // The chunks of this call, slot by slot (DecodeRequest::slots).  Heads, outlier heads and batches are per slot;
+  // offsets and lengths come from the container.
   std::vector<uint32_t> sel;
   std::vector<uint64_t> selOff, selLen, tailOff, tailLen;
   std::vector<uint8_t> heads, tails;
@@ -2999,18 +3083,12 @@ struct DecodeCall {
   ~DecodeCall() { if (!ok) drain_after_error(E, st); }
   int run(size_t dst_cap_vals)
   {
-    const auto chunks = list ? *list : chunk_volume(ci.vol, ci.chunk);
-    if ((box && (mr || slice)) || (list && mr))   // (a list of slices: sperrhip_decompress_2d_batch_dev)
+    if (!req.valid())
       return -1;
-    if (lvl && (box || mr || slice || list || lvl->h >= lvl->m.nlev))
-      return -1;
-    sel = box ? box->ids : lvl ? lvl->ids : std::vector<uint32_t>(chunks.size());
-    if (!box && !lvl)
-      std::iota(sel.begin(), sel.end(), 0u);
+    const auto chunks = req.chunks(ci);
+    sel = req.slots(chunks.size());
     const uint32_t nchunks = (uint32_t)sel.size();
-    const size_t outVals = box ? box->dims[0] * box->dims[1] * box->dims[2]
-                           : lvl ? lvl->dims[0] * lvl->dims[1] * lvl->dims[2]
-                                 : ci.nvals;
+    const size_t outVals = req.out_vals(ci);
     if (outVals == 0 || outVals > dst_cap_vals || nchunks == 0)
       return -1;
     for (uint32_t i = 0; i < nchunks; i++) {
@@ -3021,7 +3099,7 @@ struct DecodeCall {
     }
     if (read_heads())
       return -1;
-    deferOK = !anyOutlier && !mr && !slice && groups.size() > 1;
+    deferOK = !anyOutlier && !req.levels && !req.slices && groups.size() > 1;
     count_mx_groups();
     for (int pass = 0; pass < 2; pass++)
       for (auto& g : groups)
@@ -3044,7 +3122,7 @@ struct DecodeCall {
       return -1;
     uint64_t* d_off = reinterpret_cast<uint64_t*>(E.misc.p);
     uint64_t* d_len = d_off + round_up(nchunks, 32);
-    uint64_t* d_hoff = d_len + round_up(nchunks, 32);   // (sliceHdr: where each stream's 10-byte header starts)
+    uint64_t* d_hoff = d_len + round_up(nchunks, 32);   // (req.sliceHdr: where each stream's 10-byte header starts)
     uint64_t* d_hlen = d_hoff + round_up(nchunks, 32);
     uint8_t* d_heads = reinterpret_cast<uint8_t*>(d_hlen + round_up(nchunks, 32));
     // (withHdr: a second launch gathers the 10 bytes in front of every stream behind the heads, for the same read-back)
@@ -3069,9 +3147,9 @@ struct DecodeCall {
       HIP_CHECK(hipStreamSynchronize(st));
       return 0;
     };
-    if (gather(selOff, selLen, heads, sliceHdr != nullptr))
+    if (gather(selOff, selLen, heads, req.sliceHdr != nullptr))
       return -1;
-    if (sliceHdr)   // {version, flags, u32 dimx, u32 dimy} of every stream of a slice batch: the dims must be the call's
+    if (const uint32_t* sliceHdr = req.sliceHdr)   // {version, flags, u32 dimx, u32 dimy} of every stream of a slice batch: the dims must be the call's
       for (uint32_t i = 0; i < nchunks; i++) {
         uint32_t d2[2];
         memcpy(d2, heads.data() + (size_t)(nchunks + i) * 32 + 2, 8);
@@ -3085,7 +3163,7 @@ struct DecodeCall {
     tailOff.assign(nchunks, 0);
     tailLen.assign(nchunks, 0);
     bool anyTail = false;
-    if (lvl)   // (a level is taken before the outlier correctors are added, src/SPECK_FLT.cpp:568-603: no stream of them is read)
+    if (!req.reads_outliers())
       return 0;
     for (uint32_t i = 0; i < nchunks; i++) {
       const uint8_t* hd = heads.data() + (size_t)i * 32;
@@ -3126,7 +3204,7 @@ struct DecodeCall {
   // launched last wait for the first ones to END: 1000^3 in 256^3 chunks, 37 such chunks at 8 workgroups each,
   // decoded no faster than with one workgroup per chunk)
   // (a slice is decoded on the 2D coder's forest, the plan with z extent 0)
-  ShapePlan* plan_of(const Dims& d) { return E.plan(d[0], d[1], slice ? 0 : d[2]); }
+  ShapePlan* plan_of(const Dims& d) { return E.plan(d[0], d[1], req.slices ? 0 : d[2]); }
   void count_mx_groups()
   {
     size_t nmx = 0;
@@ -3167,7 +3245,7 @@ struct DecodeCall {
   size_t compact_box(const ShapePlan& P, const std::vector<Ref>& refs, uint32_t cbox[3]) const
   {
     cbox[0] = cbox[1] = cbox[2] = 0;
-    if (!fuse_xyz(P) || !plan_fusable(P) || mr || slice || anyOutlier || P.fwd.size() < 3)
+    if (!fuse_xyz(P) || !plan_fusable(P) || req.levels || req.slices || anyOutlier || P.fwd.size() < 3)
       return 0;
     for (const Ref& r : refs) {
       const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
@@ -3179,7 +3257,7 @@ struct DecodeCall {
         cbox[a] = std::max(cbox[a], P.fwd[k].region[a]);
     for (int a = 0; a < 3; a++)
       cbox[a] = std::max(cbox[a], 1u);
-    if (lvl)   // (a chunk with one level of transform has no coarser pass: the box still holds the level's corner)
+    if (const Window* lvl = req.level())   // (a chunk with one level of transform has no coarser pass: the box still holds the level's corner)
       for (int a = 0; a < 3; a++)
         cbox[a] = std::max(cbox[a], lvl->m.cres[lvl->h][a]);
     return (size_t)cbox[0] * cbox[1] * cbox[2];
@@ -3199,7 +3277,7 @@ struct DecodeCall {
       for (auto& r : h.second)
         mp = std::max<uint64_t>(mp, ci.len[r.gid]);
       uint32_t qbox[3];
-      sum += round_up(h.second.size() * dec_bytes_per_chunk(*Q, mp, compact_box(*Q, h.second, qbox), ref_planes_of(*Q, h.second), cropped()) + (1 << 20), 4096);
+      sum += round_up(h.second.size() * dec_bytes_per_chunk(*Q, mp, compact_box(*Q, h.second, qbox), ref_planes_of(*Q, h.second), req.cropped()) + (1 << 20), 4096);
     }
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
@@ -3215,7 +3293,7 @@ struct DecodeCall {
     ShapePlan* P = plan_of(shape);
     if (!P)
       return -1;
-    if (slice && !use_mixed(*P)) {   // (no slice has such a forest, DESIGN.md section 4c: k_lis_walk has no type-I phase)
+    if (req.slices && !use_mixed(*P)) {   // (no slice has such a forest, DESIGN.md section 4c: k_lis_walk has no type-I phase)
       fprintf(stderr, "[sperr_hip] slice of %u x %u: its forest does not fit k_lis_mx\n", P->dims[0], P->dims[1]);
       return -1;
     }
@@ -3231,8 +3309,8 @@ struct DecodeCall {
     b.refNPlanes = ref_planes_of(*P, refs);
     // the inverse passes dequantise on the way (not for the resolution hierarchy, whose coarsest
     // level is read before any pass has run)
-    b.fuseDq = plan_fusable(*P) && !mr && !slice;
-    const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, cropped());
+    b.fuseDq = plan_fusable(*P) && !req.levels && !req.slices;
+    const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, req.cropped());
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const size_t budgetBytes = arena_budget(E.arena.n, fr);
@@ -3355,7 +3433,7 @@ struct DecodeCall {
       S.nb = (nbAll - done + (nsub - q) - 1) / (nsub - q);
       S.first = b0 + done;
       done += S.nb;
-      if (S.nb && !carve_dec(A, *b.P, S.nb, b.maxPayload, S.bb, b.compactElems, b.refNPlanes, cropped()))
+      if (S.nb && !carve_dec(A, *b.P, S.nb, b.maxPayload, S.bb, b.compactElems, b.refNPlanes, req.cropped()))
         return -1;
       if (S.nb && b.compactElems)
         g_dbg_counter[2]++;
@@ -3474,27 +3552,13 @@ struct DecodeCall {
     DecBatchBufs& bb = S.bb;
     DecBuffers& d = bb.db;
     HIP_CHECK(hipMemcpyAsync(bb.geom, S.hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
-    if (box) {   // each chunk's window of the box and its origin relative to the box
+    if (req.cropped()) {   // each chunk's piece of the window and its origin relative to the window
       S.hc.resize(nb);
-      for (uint32_t i = 0; i < nb; i++)
-        for (int a = 0; a < 3; a++) {
-          const size_t o = S.hg[i].org[a], lo = box->lo[a], hi = box->lo[a] + box->dims[a];
-          S.hc[i].rel[a] = (int32_t)((int64_t)o - (int64_t)lo);
-          S.hc[i].lo[a] = (uint32_t)(lo > o ? lo - o : 0);
-          S.hc[i].hi[a] = (uint32_t)std::min<size_t>(hi - o, b.P->dims[a]);
-        }
-      HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
-    }
-    else if (cropped()) {   // a level's box: the same in the level's coordinates, where a chunk is its corner of cres[h]
-      S.hc.resize(nb);
-      for (uint32_t i = 0; i < nb; i++)
-        for (int a = 0; a < 3; a++) {
-          const size_t s = lvl->m.cres[lvl->h][a], o = S.hg[i].org[a] / b.P->dims[a] * s;
-          const size_t lo = lvl->lo[a], hi = lvl->lo[a] + lvl->dims[a];
-          S.hc[i].rel[a] = (int32_t)((int64_t)o - (int64_t)lo);
-          S.hc[i].lo[a] = (uint32_t)(lo > o ? lo - o : 0);
-          S.hc[i].hi[a] = (uint32_t)std::min<size_t>(hi - o, s);
-        }
+      for (uint32_t i = 0; i < nb; i++) {
+        size_t o[3], ext[3];
+        req.window->place(S.hg[i].org, P.dims, o, ext);
+        S.hc[i] = req.window->crop_geom(o, ext);
+      }
       HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
     }
     HIP_CHECK(hipMemcpyAsync(bb.chunkOff, S.ho.data(), nb * 8, hipMemcpyHostToDevice, ss));
@@ -3595,8 +3659,8 @@ struct DecodeCall {
   // which case every pass stays in the chunk buffer
   int enqueue_inverse(const Batch& b, SubHost& S, uint32_t q, hipStream_t ss)
   {
-    if (lvl)
-      return enqueue_level(b, S, ss);
+    if (const Window* lvl = req.level())
+      return enqueue_level(b, S, ss, *lvl);
     const ShapePlan& P = *b.P;
     const uint32_t nb = S.nb;
     const uint32_t* cd = P.dims;
@@ -3634,8 +3698,9 @@ struct DecodeCall {
       HIP_CHECK(hipMemcpyAsync(d_bricks, S.bricks.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
     }
     // a level of the inverse transform is 3 passes (z y x) of a dyadic chunk, 2 (y x) of a slice
-    const size_t perLevel = slice ? 2 : 3;
+    const size_t perLevel = req.slices ? 2 : 3;
     auto sub_volume = [&](size_t k) -> int {   // before pass k, the first of its level
+      const MultiRes* mr = req.levels;
       if (!mr || !mr->nlev)
         return 0;
       const size_t h = mr->nlev - (k / perLevel + 1);
@@ -3679,7 +3744,7 @@ struct DecodeCall {
       if (launch_lift_xyz(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst, io, d_dst, vd, bb.geom, &lf, bb.crop))
         return -1;
     }
-    if (fxy && slice && sub_volume(1))   // the finest level of a slice is the fused pair
+    if (fxy && req.slices && sub_volume(1))   // the finest level of a slice is the fused pair
       return -1;
     if (fxy && launch_lift_xy(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst, io, d_dst, vd, bb.geom, bb.crop))
       return -1;
@@ -3704,18 +3769,18 @@ struct DecodeCall {
   // has it (compact_box, fuseDq), then the writer.  The coarsest level has no pass: its corner is dequantised by a
   // kernel of its own where the passes would have (chunks with 64-bit coefficients: k_inv_quantize has).  The finest
   // level's kernels and the scatter pass are never reached
-  int enqueue_level(const Batch& b, SubHost& S, hipStream_t ss)
+  int enqueue_level(const Batch& b, SubHost& S, hipStream_t ss, const Window& lvl)
   {
     const ShapePlan& P = *b.P;
     const uint32_t nb = S.nb;
     const uint32_t* cd = P.dims;
     DecBatchBufs& bb = S.bb;
     DecBuffers& d = bb.db;
-    const size_t h = lvl->h, nlev = lvl->m.nlev;
+    const size_t h = lvl.h, nlev = lvl.m.nlev;
     if (P.fwd.size() != 3 * nlev)   // (a level of the transform is the three passes z y x of a dyadic chunk)
       return -1;
     const uint32_t bx = b.compactElems ? b.cbox[0] : cd[0], by = b.compactElems ? b.cbox[1] : cd[1];
-    const auto& r = lvl->m.cres[h];
+    const auto& r = lvl.m.cres[h];
     if (b.compactElems && (r[0] > b.cbox[0] || r[1] > b.cbox[1] || r[2] > b.cbox[2]))
       return -1;
     for (size_t k = P.fwd.size(); k-- > 3 * (nlev - h);) {
@@ -3730,7 +3795,7 @@ struct DecodeCall {
       LAUNCH_K(k_dequant_corner, dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, bx, by, cd[0], cd[1],
                r[0], r[1], r[2], d.cst, d.st, bb.coef32, d.coefStride, d.sign, d.signStride, d.sigNew, d.sigOld,
                d.maskPixStride, d.refPlanes ? 1 : 0);
-    if (lvl->crop)
+    if (lvl.crop)
       LAUNCH_K((k_level_write<T, true>), dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, d.cst, bb.crop,
                bx, by, cd[0], cd[1], cd[2], r[0], r[1], r[2], vd, d_dst);
     else
@@ -3807,13 +3872,10 @@ struct DecodeCall {
 };
 
 template <typename T>
-int decompress_impl(Engine& E, const uint8_t* d_src, size_t /*src_len*/, T* d_dst, size_t dst_cap_vals,
-                    const ContainerInfo& ci, hipStream_t st, const MultiRes* mr = nullptr,
-                    bool slice = false, const BoxSel* box = nullptr,
-                    const std::vector<std::array<size_t, 6>>* list = nullptr, const uint32_t* sliceHdr = nullptr,
-                    const LevelSel* lvl = nullptr)
+int decompress_impl(Engine& E, const uint8_t* d_src, T* d_dst, size_t dst_cap_vals, const ContainerInfo& ci,
+                    hipStream_t st, const DecodeRequest& req)
 {
-  DecodeCall<T> call{E, d_src, d_dst, ci, st, mr, slice, box, list, sliceHdr, lvl};
+  DecodeCall<T> call{E, d_src, d_dst, ci, st, req};
   return call.run(dst_cap_vals);
 }
 
@@ -3917,68 +3979,57 @@ int set_max_dyn_lds(const void* fn, int bytes)
   return 0;
 }
 
-// The box [lo, lo + dims) of a container's volume: the chunks it meets; -1 when it is empty, leaves the
-// volume, or is too long along an axis for a chunk's origin relative to it (CropGeom::rel)
-int box_select(const ContainerInfo& ci, const size_t lo[3], const size_t dims[3], BoxSel& b)
+// The box [lo, lo + dims) of a container's volume and the chunks it meets; -1 when window_select refuses it
+int box_select(const ContainerInfo& ci, const size_t lo[3], const size_t dims[3], Window& w)
 {
-  for (int a = 0; a < 3; a++) {
-    if (dims[a] > (size_t)INT32_MAX)
-      return -1;
-    b.lo[a] = lo[a];
-    b.dims[a] = dims[a];
-  }
-  return box_chunks(ci.vol, ci.chunk, b.lo, b.dims, b.ids) ? 0 : -1;
+  return window_select(ci.vol, ci.chunk, lo, dims, w) ? 0 : -1;
 }
 
-// a box that is the whole volume goes through the whole-volume decode
-bool box_is_volume(const ContainerInfo& ci, const BoxSel& b)
+// Level `level` of the container `ci` describes, whole (lo and dims null) or the box [lo, lo + dims) of it, and the
+// chunks it meets; -1 when the container has no such level or window_select refuses the box
+int level_select(const ContainerInfo& ci, size_t level, const size_t* lo, const size_t* dims, Window& w)
 {
-  return b.lo == Dims{0, 0, 0} && b.dims == ci.vol;
-}
-
-// the box `b` of the container at d_src (described by `ci`) into d_dst (x fastest); the caller has checked
-// that d_dst holds it
-int decompress_box(Engine& E, const uint8_t* d_src, size_t src_len, int output_float, const ContainerInfo& ci,
-                   const BoxSel& b, void* d_dst, size_t dst_cap_bytes, hipStream_t st)
-{
-  const BoxSel* box = box_is_volume(ci, b) ? nullptr : &b;
-  if (output_float)
-    return decompress_impl<float>(E, d_src, src_len, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci,
-                                  st, nullptr, false, box);
-  return decompress_impl<double>(E, d_src, src_len, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
-                                 st, nullptr, false, box);
-}
-
-// Level `level` of the container `ci` describes, whole (lo and dims null) or the box [lo, lo + dims) of it: the chunks
-// it meets; -1 when the container has no such level, the box is empty or leaves the level
-int level_select(const ContainerInfo& ci, size_t level, const size_t* lo, const size_t* dims, LevelSel& s)
-{
-  multires_levels(ci.vol, ci.chunk, s.m);
-  if (level >= s.m.nlev || (lo == nullptr) != (dims == nullptr))
+  multires_levels(ci.vol, ci.chunk, w.m);
+  if (level >= w.m.nlev || (lo == nullptr) != (dims == nullptr))
     return -1;
-  s.h = level;
+  w.level = true;
+  w.h = level;
+  const Dims zero{0, 0, 0};
   Dims ld, cr;
   for (int a = 0; a < 3; a++) {
-    cr[a] = s.m.cres[level][a];
-    ld[a] = cr[a] * s.m.grid[a];
-    s.lo[a] = lo ? lo[a] : 0;
-    s.dims[a] = dims ? dims[a] : ld[a];
-    if (s.dims[a] > (size_t)INT32_MAX)
-      return -1;
+    cr[a] = w.m.cres[level][a];
+    ld[a] = cr[a] * w.m.grid[a];
   }
-  s.crop = !(s.lo == Dims{0, 0, 0} && s.dims == ld);
-  return box_chunks(ld, cr, s.lo, s.dims, s.ids) ? 0 : -1;
+  return window_select(ld, cr, lo ? lo : zero.data(), dims ? dims : ld.data(), w) ? 0 : -1;
 }
 
-// the level or its box into d_dst (x fastest); the caller has checked that d_dst holds it
-int decompress_level(Engine& E, const uint8_t* d_src, size_t src_len, int output_float, const ContainerInfo& ci,
-                     const LevelSel& s, void* d_dst, size_t dst_cap_bytes, hipStream_t st)
+// f(float{}) or f(double{}): the element type an entry point's is_float / output_float names
+template <typename F>
+int with_elem(int is_float, F&& f)
 {
-  if (output_float)
-    return decompress_impl<float>(E, d_src, src_len, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci,
-                                  st, nullptr, false, nullptr, nullptr, nullptr, &s);
-  return decompress_impl<double>(E, d_src, src_len, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
-                                 st, nullptr, false, nullptr, nullptr, nullptr, &s);
+  return is_float ? f(float{}) : f(double{});
+}
+
+// `req` of the container at d_src (described by `ci`) into d_dst (x fastest), which holds dst_cap_bytes
+int decode_to(Engine& E, const void* d_src, int output_float, void* d_dst, size_t dst_cap_bytes,
+              const ContainerInfo& ci, hipStream_t st, const DecodeRequest& req)
+{
+  return with_elem(output_float, [&](auto t) {
+    using T = decltype(t);
+    return decompress_impl<T>(E, static_cast<const uint8_t*>(d_src), static_cast<T*>(d_dst), dst_cap_bytes / sizeof(T),
+                              ci, st, req);
+  });
+}
+
+// the window `w` of it, once d_dst is seen to hold the window
+int decode_window(Engine& E, const void* d_src, int output_float, void* d_dst, size_t dst_cap_bytes,
+                  const ContainerInfo& ci, hipStream_t st, const Window& w)
+{
+  if (dst_cap_bytes / (output_float ? sizeof(float) : sizeof(double)) < w.dims[0] * w.dims[1] * w.dims[2])
+    return -1;
+  DecodeRequest req;
+  req.set_window(w);
+  return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, ci, st, req);
 }
 
 // The host entry points of a sub-box and of a level: the streams of the chunks `ids` of the host container at `h`
@@ -4021,7 +4072,7 @@ int decode_packed_host(const uint8_t* h, const ContainerInfo& ci, const std::vec
   }
   if (rtn == 0) {
     Lease L;
-    rtn = L.e ? decode(*L.e, static_cast<const uint8_t*>(d_in), total, packed, d_out) : -1;
+    rtn = L.e ? decode(*L.e, d_in, packed, d_out) : -1;
   }
   if (rtn == 0) {
     void* buf = malloc(outBytes);
@@ -4030,6 +4081,59 @@ int decode_packed_host(const uint8_t* h, const ContainerInfo& ci, const std::vec
     else {
       free(buf);
       rtn = -1;
+    }
+  }
+  release();
+  return rtn;
+}
+
+// The host entry points of the hierarchy, the same way: the stream at `src` travels to the calling thread's device,
+// `decode` runs the device call on it -- d_out takes the outBytes of the volume (the slice), d_lv[h] the lvn[h]
+// doubles of level h -- and the volume and every level come back into malloc'd buffers
+template <typename F>
+int decode_multires_host(const void* src, size_t src_len, size_t outBytes, const std::vector<size_t>& lvn, void** dst,
+                         double** levels, F&& decode)
+{
+  std::vector<void*> dev;
+  auto release = [&]() {
+    for (void* p : dev)
+      (void)hipFree(p);
+  };
+  auto dalloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess)
+      return nullptr;
+    dev.push_back(p);
+    return p;
+  };
+  void* d_in = dalloc(src_len);
+  void* d_out = dalloc(outBytes);
+  std::vector<double*> d_lv(lvn.size(), nullptr);
+  bool ok = d_in && d_out;
+  for (size_t h = 0; ok && h < lvn.size(); h++) {
+    d_lv[h] = static_cast<double*>(dalloc(lvn[h] * 8));
+    ok = d_lv[h] != nullptr;
+  }
+  if (!ok) {
+    fprintf(stderr, "[sperr_hip] device allocation failed\n");
+    release();
+    return -1;
+  }
+  int rtn = -1;
+  if (hipMemcpy(d_in, src, src_len, hipMemcpyHostToDevice) == hipSuccess)
+    rtn = decode(d_in, d_out, d_lv.data());
+  if (rtn == 0) {
+    void* buf = malloc(outBytes);
+    if (buf && hipMemcpy(buf, d_out, outBytes, hipMemcpyDeviceToHost) == hipSuccess)
+      *dst = buf;
+    else {
+      free(buf);
+      rtn = -1;
+    }
+    for (size_t h = 0; rtn == 0 && h < lvn.size(); h++) {
+      levels[h] = static_cast<double*>(malloc(lvn[h] * 8));
+      if (!levels[h] || hipMemcpy(levels[h], d_lv[h], lvn[h] * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        rtn = -1;
     }
   }
   release();
@@ -4061,6 +4165,32 @@ static int guarded(const char* what, F&& body) noexcept
     fprintf(stderr, "[sperr_hip] %s: unknown exception\n", what);
   }
   return -1;
+}
+
+// what the device decode entry points begin with: an engine leased, the caller's stream, the container's header read
+struct DevDecode {
+  Lease L;
+  hipStream_t st;
+  ContainerInfo ci;
+  const bool ok;
+  DevDecode(const void* d_src, size_t src_len, void* hip_stream)
+      : st(static_cast<hipStream_t>(hip_stream)),
+        ok(L.e && read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st) == 0)
+  {
+  }
+};
+
+// a slice's stream (without the 10-byte header) described as a container of one chunk
+static ContainerInfo one_slice_info(size_t dimx, size_t dimy, size_t src_len, int output_float)
+{
+  ContainerInfo ci;
+  ci.vol = {dimx, dimy, 1};
+  ci.nvals = dimx * dimy;
+  ci.chunk = ci.vol;
+  ci.is_float = output_float != 0;
+  ci.off = {0};
+  ci.len = {src_len};
+  return ci;
 }
 
 extern "C" {
@@ -4230,11 +4360,10 @@ int sperrhip_compress_dev(const void* d_src, int is_float, size_t dimx, size_t d
     Engine& E = *L.e;
     const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (is_float)
-      return compress_impl<float>(E, static_cast<const float*>(d_src), vol, ch, mode, quality,
-                                  static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st);
-    return compress_impl<double>(E, static_cast<const double*>(d_src), vol, ch, mode, quality,
-                                 static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st);
+    return with_elem(is_float, [&](auto t) {
+      return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, ch, mode, quality,
+                           static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st);
+    });
   });
 }
 
@@ -4243,13 +4372,10 @@ int sperrhip_parse_header_dev(const void* d_src, size_t src_len, size_t* dimx, s
                               size_t* chunk_z)
 {
   return guarded("sperrhip_parse_header_dev", [&]() -> int {
-    Lease L;
-    if (!L.e)
+    DevDecode d(d_src, src_len, nullptr);
+    if (!d.ok)
       return -1;
-    Engine& E = *L.e;
-    ContainerInfo ci;
-    if (read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, nullptr))
-      return -1;
+    const ContainerInfo& ci = d.ci;
     *dimx = ci.vol[0];
     *dimy = ci.vol[1];
     *dimz = ci.vol[2];
@@ -4271,26 +4397,16 @@ int sperrhip_decompress_dev(const void* d_src, size_t src_len, int output_float,
   return guarded("sperrhip_decompress_dev", [&]() -> int {
     if (!d_src || !d_dst)
       return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ContainerInfo ci;
-    if (read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st))
+    DevDecode d(d_src, src_len, hip_stream);
+    if (!d.ok)
       return -1;
     if (dimx)
-      *dimx = ci.vol[0];
+      *dimx = d.ci.vol[0];
     if (dimy)
-      *dimy = ci.vol[1];
+      *dimy = d.ci.vol[1];
     if (dimz)
-      *dimz = ci.vol[2];
-    if (output_float)
-      return decompress_impl<float>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                    static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci, st);
-    return decompress_impl<double>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                   static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
-                                   st);
+      *dimz = d.ci.vol[2];
+    return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, DecodeRequest{});
   });
 }
 
@@ -4322,11 +4438,10 @@ int sperrhip_compress_batch_dev(const void* d_src, int is_float, size_t nvol, si
     Engine& E = *L.e;
     const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (is_float)
-      return compress_batch_impl<float>(E, static_cast<const float*>(d_src), nvol, vol, ch, mode, quality,
-                                        static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
-    return compress_batch_impl<double>(E, static_cast<const double*>(d_src), nvol, vol, ch, mode, quality,
-                                       static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
+    return with_elem(is_float, [&](auto t) {
+      return compress_batch_impl(E, static_cast<const decltype(t)*>(d_src), nvol, vol, ch, mode, quality,
+                                 static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
+    });
   });
 }
 
@@ -4355,11 +4470,9 @@ int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size
       *dimy = all.vol[1];
     if (dimz)
       *dimz = all.vol[2] / nvol;
-    if (output_float)
-      return decompress_impl<float>(E, src, 0, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), all, st,
-                                    nullptr, false, nullptr, &list);
-    return decompress_impl<double>(E, src, 0, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), all, st,
-                                   nullptr, false, nullptr, &list);
+    DecodeRequest req;
+    req.stacked = &list;
+    return decode_to(E, src, output_float, d_dst, dst_cap_bytes, all, st, req);
   });
 }
 
@@ -4388,22 +4501,11 @@ int sperrhip_decompress_box_dev(const void* d_src, size_t src_len, int output_fl
   return guarded("sperrhip_decompress_box_dev", [&]() -> int {
     if (!d_src || !d_dst || !box_lo || !box_dims)
       return -1;
-    Lease L;
-    if (!L.e)
+    DevDecode d(d_src, src_len, hip_stream);
+    Window w;
+    if (!d.ok || box_select(d.ci, box_lo, box_dims, w))
       return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ContainerInfo ci;
-    if (read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st))
-      return -1;
-    BoxSel b;
-    if (box_select(ci, box_lo, box_dims, b))
-      return -1;
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    if (dst_cap_bytes / esz < b.dims[0] * b.dims[1] * b.dims[2])
-      return -1;
-    return decompress_box(E, static_cast<const uint8_t*>(d_src), src_len, output_float, ci, b, d_dst,
-                          dst_cap_bytes, st);
+    return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w);
   });
 }
 
@@ -4414,22 +4516,11 @@ int sperrhip_decompress_level_dev(const void* d_src, size_t src_len, int output_
   return guarded("sperrhip_decompress_level_dev", [&]() -> int {
     if (!d_src || !d_dst)
       return -1;
-    Lease L;
-    if (!L.e)
+    DevDecode d(d_src, src_len, hip_stream);
+    Window w;
+    if (!d.ok || level_select(d.ci, level, box_lo, box_dims, w))
       return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ContainerInfo ci;
-    if (read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st))
-      return -1;
-    LevelSel s;
-    if (level_select(ci, level, box_lo, box_dims, s))
-      return -1;
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    if (dst_cap_bytes / esz < s.dims[0] * s.dims[1] * s.dims[2])
-      return -1;
-    return decompress_level(E, static_cast<const uint8_t*>(d_src), src_len, output_float, ci, s, d_dst,
-                            dst_cap_bytes, st);
+    return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w);
   });
 }
 
@@ -4461,16 +4552,11 @@ int sperrhip_decompress_multires_dev(const void* d_src, size_t src_len, int outp
   return guarded("sperrhip_decompress_multires_dev", [&]() -> int {
     if (!d_src || !d_dst || (nlev && !d_levels))
       return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ContainerInfo ci;
-    if (read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st))
+    DevDecode d(d_src, src_len, hip_stream);
+    if (!d.ok)
       return -1;
     MultiRes m;
-    multires_levels(ci.vol, ci.chunk, m);
+    multires_levels(d.ci.vol, d.ci.chunk, m);
     if (m.nlev != nlev)
       return -1;   // (sperrhip_multires_levels tells how many there are)
     for (size_t h = 0; h < nlev; h++) {
@@ -4478,13 +4564,9 @@ int sperrhip_decompress_multires_dev(const void* d_src, size_t src_len, int outp
         return -1;
       m.d_level[h] = d_levels[h];
     }
-    if (output_float)
-      return decompress_impl<float>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                    static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci, st,
-                                    &m);
-    return decompress_impl<double>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                   static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci,
-                                   st, &m);
+    DecodeRequest req;
+    req.levels = &m;
+    return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, req);
   });
 }
 
@@ -4608,12 +4690,11 @@ int sperrhip_compress_2d_dev(const void* d_src, int is_float, size_t dimx, size_
     Engine& E = *L.e;
     const Dims vol{dimx, dimy, 1};
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int slice = out_inc_header ? 2 : 1;
-    if (is_float)
-      return compress_impl<float>(E, static_cast<const float*>(d_src), vol, vol, mode, quality,
-                                  static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st, slice);
-    return compress_impl<double>(E, static_cast<const double*>(d_src), vol, vol, mode, quality,
-                                 static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st, slice);
+    const Coded what = out_inc_header ? Coded::SliceWithHeader : Coded::Slice;
+    return with_elem(is_float, [&](auto t) {
+      return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, vol, mode, quality,
+                           static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st, what);
+    });
   });
 }
 
@@ -4629,20 +4710,10 @@ int sperrhip_decompress_2d_dev(const void* d_src, size_t src_len, int output_flo
       return -1;
     Engine& E = *L.e;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ContainerInfo ci;
-    ci.vol = {dimx, dimy, 1};
-    ci.nvals = dimx * dimy;
-    ci.chunk = ci.vol;
-    ci.is_float = output_float != 0;
-    ci.off = {0};
-    ci.len = {src_len};
-    if (output_float)
-      return decompress_impl<float>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                    static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci, st,
-                                    nullptr, true);
-    return decompress_impl<double>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                   static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci, st,
-                                   nullptr, true);
+    DecodeRequest req;
+    req.slices = true;
+    return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, one_slice_info(dimx, dimy, src_len, output_float),
+                     st, req);
   });
 }
 
@@ -4675,13 +4746,11 @@ int sperrhip_compress_2d_batch_dev(const void* d_src, int is_float, size_t nslic
     Engine& E = *L.e;
     const Dims vol{dimx, dimy, 1};
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int slice = out_inc_header ? 2 : 1;
-    uint8_t* dst = static_cast<uint8_t*>(d_dst);
-    if (is_float)
-      return compress_batch_impl<float>(E, static_cast<const float*>(d_src), nslice, vol, vol, mode, quality, dst,
-                                        dst_cap, offsets, st, slice);
-    return compress_batch_impl<double>(E, static_cast<const double*>(d_src), nslice, vol, vol, mode, quality, dst,
-                                       dst_cap, offsets, st, slice);
+    const Coded what = out_inc_header ? Coded::SliceWithHeader : Coded::Slice;
+    return with_elem(is_float, [&](auto t) {
+      return compress_batch_impl(E, static_cast<const decltype(t)*>(d_src), nslice, vol, vol, mode, quality,
+                                 static_cast<uint8_t*>(d_dst), dst_cap, offsets, st, what);
+    });
   });
 }
 
@@ -4718,13 +4787,12 @@ int sperrhip_decompress_2d_batch_dev(const void* d_src, const size_t* offsets, s
       return -1;
     Engine& E = *L.e;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const uint8_t* src = static_cast<const uint8_t*>(d_src);
     const uint32_t hdrDims[2] = {(uint32_t)dimx, (uint32_t)dimy};
-    if (output_float)
-      return decompress_impl<float>(E, src, 0, static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), all, st,
-                                    nullptr, true, nullptr, &list, has_header ? hdrDims : nullptr);
-    return decompress_impl<double>(E, src, 0, static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), all, st,
-                                   nullptr, true, nullptr, &list, has_header ? hdrDims : nullptr);
+    DecodeRequest req;
+    req.stacked = &list;
+    req.slices = true;
+    req.sliceHdr = has_header ? hdrDims : nullptr;
+    return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, all, st, req);
   });
 }
 
@@ -5018,20 +5086,11 @@ int sperrhip_decompress_2d_multires_dev(const void* d_src, size_t src_len, int o
         return -1;
       m.d_level[h] = d_levels[h];
     }
-    ContainerInfo ci;
-    ci.vol = {dimx, dimy, 1};
-    ci.nvals = dimx * dimy;
-    ci.chunk = ci.vol;
-    ci.is_float = output_float != 0;
-    ci.off = {0};
-    ci.len = {src_len};
-    if (output_float)
-      return decompress_impl<float>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                    static_cast<float*>(d_dst), dst_cap_bytes / sizeof(float), ci, st, &m,
-                                    true);
-    return decompress_impl<double>(E, static_cast<const uint8_t*>(d_src), src_len,
-                                   static_cast<double*>(d_dst), dst_cap_bytes / sizeof(double), ci, st, &m,
-                                   true);
+    DecodeRequest req;
+    req.slices = true;
+    req.levels = &m;
+    return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, one_slice_info(dimx, dimy, src_len, output_float),
+                     st, req);
   });
 }
 
@@ -5044,54 +5103,14 @@ int sperrhip_decomp_2d_multires(const void* src, size_t src_len, int output_floa
     if (src_len < 17 || !nlev || !level_dims || !levels ||
         sperrhip_multires_levels_2d(dimx, dimy, nlev, level_dims))
       return -1;
-    const size_t n = dimx * dimy, esz = output_float ? 4 : 8;
-    std::vector<void*> dev;
-    auto release = [&]() {
-      for (void* p : dev)
-        (void)hipFree(p);
-    };
-    auto dalloc = [&](size_t bytes) -> void* {
-      void* p = nullptr;
-      if (hipMalloc(&p, bytes) != hipSuccess)
-        return nullptr;
-      dev.push_back(p);
-      return p;
-    };
-    void* d_in = dalloc(src_len);
-    void* d_out = dalloc(n * esz);
-    std::vector<double*> d_lv(*nlev, nullptr);
-    std::vector<size_t> lvn(*nlev, 0);
-    bool ok = d_in && d_out;
-    for (size_t h = 0; ok && h < *nlev; h++) {
+    const size_t outBytes = dimx * dimy * (output_float ? 4 : 8);
+    std::vector<size_t> lvn(*nlev);
+    for (size_t h = 0; h < *nlev; h++)
       lvn[h] = level_dims[2 * h] * level_dims[2 * h + 1];
-      d_lv[h] = static_cast<double*>(dalloc(lvn[h] * 8));
-      ok = d_lv[h] != nullptr;
-    }
-    if (!ok) {
-      fprintf(stderr, "[sperr_hip] device allocation failed\n");
-      release();
-      return -1;
-    }
-    int rtn = -1;
-    if (hipMemcpy(d_in, src, src_len, hipMemcpyHostToDevice) == hipSuccess)
-      rtn = sperrhip_decompress_2d_multires_dev(d_in, src_len, output_float, dimx, dimy, d_out, n * esz, *nlev,
-                                                d_lv.data(), nullptr);
-    if (rtn == 0) {
-      void* buf = malloc(n * esz);
-      if (buf && hipMemcpy(buf, d_out, n * esz, hipMemcpyDeviceToHost) == hipSuccess)
-        *dst = buf;
-      else {
-        free(buf);
-        rtn = -1;
-      }
-      for (size_t h = 0; rtn == 0 && h < *nlev; h++) {
-        levels[h] = static_cast<double*>(malloc(lvn[h] * 8));
-        if (!levels[h] || hipMemcpy(levels[h], d_lv[h], lvn[h] * 8, hipMemcpyDeviceToHost) != hipSuccess)
-          rtn = -1;
-      }
-    }
-    release();
-    return rtn;
+    return decode_multires_host(src, src_len, outBytes, lvn, dst, levels, [&](void* d_in, void* d_out, double** d_lv) {
+      return sperrhip_decompress_2d_multires_dev(d_in, src_len, output_float, dimx, dimy, d_out, outBytes, *nlev, d_lv,
+                                                 nullptr);
+    });
   });
 }
 
@@ -5143,59 +5162,19 @@ int sperrhip_decomp_3d_multires(const void* src, size_t src_len, int output_floa
     if (sperrhip_multires_levels(ci.vol[0], ci.vol[1], ci.vol[2], ci.chunk[0], ci.chunk[1], ci.chunk[2],
                                  nlev, level_dims))
       return -1;
-    const size_t n = ci.nvals;
-    const size_t esz = output_float ? 4 : 8;
-    std::vector<void*> dev;
-    auto release = [&]() {
-      for (void* p : dev)
-        (void)hipFree(p);
-    };
-    auto dalloc = [&](size_t bytes) -> void* {
-      void* p = nullptr;
-      if (hipMalloc(&p, bytes) != hipSuccess)
-        return nullptr;
-      dev.push_back(p);
-      return p;
-    };
-    void* d_in = dalloc(src_len);
-    void* d_out = dalloc(n * esz);
-    std::vector<double*> d_lv(*nlev, nullptr);
-    std::vector<size_t> lvn(*nlev, 0);
-    bool ok = d_in && d_out;
-    for (size_t h = 0; ok && h < *nlev; h++) {
+    const size_t outBytes = ci.nvals * (output_float ? 4 : 8);
+    std::vector<size_t> lvn(*nlev);
+    for (size_t h = 0; h < *nlev; h++)
       lvn[h] = level_dims[3 * h] * level_dims[3 * h + 1] * level_dims[3 * h + 2];
-      d_lv[h] = static_cast<double*>(dalloc(lvn[h] * 8));
-      ok = d_lv[h] != nullptr;
-    }
-    if (!ok) {
-      fprintf(stderr, "[sperr_hip] device allocation failed\n");
-      release();
-      return -1;
-    }
-    int rtn = -1;
-    if (hipMemcpy(d_in, src, src_len, hipMemcpyHostToDevice) == hipSuccess)
-      rtn = sperrhip_decompress_multires_dev(d_in, src_len, output_float, d_out, n * esz, *nlev,
-                                             d_lv.data(), nullptr);
+    const int rtn =
+        decode_multires_host(src, src_len, outBytes, lvn, dst, levels, [&](void* d_in, void* d_out, double** d_lv) {
+          return sperrhip_decompress_multires_dev(d_in, src_len, output_float, d_out, outBytes, *nlev, d_lv, nullptr);
+        });
     if (rtn == 0) {
-      void* buf = malloc(n * esz);
-      if (buf && hipMemcpy(buf, d_out, n * esz, hipMemcpyDeviceToHost) == hipSuccess)
-        *dst = buf;
-      else {
-        free(buf);
-        rtn = -1;
-      }
-      for (size_t h = 0; rtn == 0 && h < *nlev; h++) {
-        levels[h] = static_cast<double*>(malloc(lvn[h] * 8));
-        if (!levels[h] || hipMemcpy(levels[h], d_lv[h], lvn[h] * 8, hipMemcpyDeviceToHost) != hipSuccess)
-          rtn = -1;
-      }
-      if (rtn == 0) {
-        *dimx = ci.vol[0];
-        *dimy = ci.vol[1];
-        *dimz = ci.vol[2];
-      }
+      *dimx = ci.vol[0];
+      *dimy = ci.vol[1];
+      *dimz = ci.vol[2];
     }
-    release();
     return rtn;
   });
 }
@@ -5214,14 +5193,14 @@ int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float, co
     size_t need = 0;
     if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
       return -1;
-    BoxSel b;
-    if (box_select(ci, box_lo, box_dims, b))
+    Window w;
+    if (box_select(ci, box_lo, box_dims, w))
       return -1;
     const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    const size_t outBytes = b.dims[0] * b.dims[1] * b.dims[2] * esz;
-    return decode_packed_host(static_cast<const uint8_t*>(src), ci, b.ids, outBytes, dst,
-                              [&](Engine& E, const uint8_t* d_in, size_t total, const ContainerInfo& packed, void* d_out) {
-                                return decompress_box(E, d_in, total, output_float, packed, b, d_out, outBytes, nullptr);
+    const size_t outBytes = w.dims[0] * w.dims[1] * w.dims[2] * esz;
+    return decode_packed_host(static_cast<const uint8_t*>(src), ci, w.ids, outBytes, dst,
+                              [&](Engine& E, const void* d_in, const ContainerInfo& packed, void* d_out) {
+                                return decode_window(E, d_in, output_float, d_out, outBytes, packed, nullptr, w);
                               });
   });
 }
@@ -5239,18 +5218,18 @@ int sperrhip_decomp_3d_level(const void* src, size_t src_len, int output_float, 
     size_t need = 0;
     if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
       return -1;
-    LevelSel s;
-    if (level_select(ci, level, box_lo, box_dims, s))
+    Window w;
+    if (level_select(ci, level, box_lo, box_dims, w))
       return -1;
     const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    const size_t outBytes = s.dims[0] * s.dims[1] * s.dims[2] * esz;
-    const int rtn = decode_packed_host(static_cast<const uint8_t*>(src), ci, s.ids, outBytes, dst,
-                                       [&](Engine& E, const uint8_t* d_in, size_t total, const ContainerInfo& packed, void* d_out) {
-                                         return decompress_level(E, d_in, total, output_float, packed, s, d_out, outBytes, nullptr);
+    const size_t outBytes = w.dims[0] * w.dims[1] * w.dims[2] * esz;
+    const int rtn = decode_packed_host(static_cast<const uint8_t*>(src), ci, w.ids, outBytes, dst,
+                                       [&](Engine& E, const void* d_in, const ContainerInfo& packed, void* d_out) {
+                                         return decode_window(E, d_in, output_float, d_out, outBytes, packed, nullptr, w);
                                        });
     if (rtn == 0)
       for (int a = 0; a < 3; a++)
-        out_dims[a] = s.dims[a];
+        out_dims[a] = w.dims[a];
     return rtn;
   });
 }

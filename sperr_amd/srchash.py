@@ -9,7 +9,7 @@ import os
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# what compress_impl / decompress_impl of a regular 3D volume run: transform, encoder, decoder, engine + headers
+# what EncodeCall / DecodeCall (engine.hip) of a regular 3D volume run: transform, encoder, decoder, engine + headers
 BENCH_PATH_SOURCES = ["xform.hip", "speck_enc.hip", "speck_dec.hip", "engine.hip"]
 
 

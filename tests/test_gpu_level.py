@@ -343,6 +343,72 @@ def test_existing_calls_launch_what_they_launched(eng, oracle):
     assert got == PARENT_LAUNCHES
 
 
+# Launches of five more kinds of call, measured the same way with the library built from the parent commit
+# 7d7e4b1 ("Quantise, build the leaf pyramid level and take the census in one kernel"): a level and a box of a
+# level of that container, a batch of two such containers, and slices of 96 x 80 at 2 bits per value -- one,
+# and a batch of three with their headers.
+PARENT_LAUNCHES_MORE = {
+    "decompress_level_0": {
+        "(k_level_write<T, false>)": 4, "k_dec_count": 72, "k_dec_header": 4, "k_dec_live": 8,
+        "k_dec_load_words": 4, "k_dec_plane_end": 72, "k_dec_scan": 72, "k_dequant_corner": 4,
+        "k_gather_heads": 1, "k_leaf_apply": 72, "k_lip_apply<uint32_t>": 72, "k_lip_deposit": 72,
+        "k_lip_scan": 72, "k_lip_words": 72, "k_lis_compact": 72, "k_lis_hi<uint32_t>": 72, "k_lis_l0": 72,
+        "k_lis_l1": 72, "k_lis_l2": 72, "k_place_scan": 72, "k_place_scatter": 72, "k_ref_assemble": 4,
+        "k_ref_deposit": 72,
+    },
+    "decompress_level_last_box": {
+        "(k_level_write<T, true>)": 1, "(k_lift_axis<false, 0>)": 3, "k_dec_count": 18, "k_dec_header": 1,
+        "k_dec_live": 2, "k_dec_load_words": 1, "k_dec_plane_end": 18, "k_dec_scan": 18, "k_gather_heads": 1,
+        "k_leaf_apply": 18, "k_lip_apply<uint32_t>": 18, "k_lip_deposit": 18, "k_lip_scan": 18, "k_lip_words": 18,
+        "k_lis_compact": 18, "k_lis_hi<uint32_t>": 18, "k_lis_l0": 18, "k_lis_l1": 18, "k_lis_l2": 18,
+        "k_place_scan": 18, "k_place_scatter": 18, "k_ref_assemble": 1, "k_ref_deposit": 18,
+    },
+    "decompress_batch": {
+        "(k_lift_axis<false, 0>)": 12, "(k_lift_xyz_inv<2, true>)": 4, "k_dec_count": 72, "k_dec_header": 4,
+        "k_dec_live": 8, "k_dec_load_words": 4, "k_dec_plane_end": 72, "k_dec_scan": 72, "k_gather_bytes": 1,
+        "k_gather_heads": 2, "k_leaf_apply": 72, "k_lip_apply<uint32_t>": 72, "k_lip_deposit": 72,
+        "k_lip_scan": 72, "k_lip_words": 72, "k_lis_compact": 72, "k_lis_hi<uint32_t>": 72, "k_lis_l0": 72,
+        "k_lis_l1": 72, "k_lis_l2": 72, "k_place_scan": 72, "k_place_scatter": 72, "k_ref_assemble": 4,
+        "k_ref_deposit": 72,
+    },
+    "decompress_2d": {
+        "(k_lift_axis<false, 0>)": 6, "(k_lift_xy<false, 2>)": 1, "k_dec_count": 18, "k_dec_header": 1,
+        "k_dec_live": 2, "k_dec_load_words": 1, "k_dec_plane_end": 18, "k_dec_scan": 18, "k_gather_heads": 1,
+        "k_inv_quantize<uint32_t>": 1, "k_leaf_apply": 18, "k_lip_apply<uint32_t>": 18, "k_lip_deposit": 18,
+        "k_lip_scan": 18, "k_lip_words": 18, "k_lis_compact": 18, "k_lis_mx<false>": 18, "k_place_scan": 18,
+        "k_place_scatter": 18, "k_ref_assemble": 1, "k_ref_deposit": 18,
+    },
+    "decompress_2d_batch": {
+        "(k_lift_axis<false, 0>)": 6, "(k_lift_xy<false, 2>)": 1, "k_dec_count": 18, "k_dec_header": 1,
+        "k_dec_live": 2, "k_dec_load_words": 1, "k_dec_plane_end": 18, "k_dec_scan": 18, "k_gather_heads": 2,
+        "k_inv_quantize<uint32_t>": 1, "k_leaf_apply": 18, "k_lip_apply<uint32_t>": 18, "k_lip_deposit": 18,
+        "k_lip_scan": 18, "k_lip_words": 18, "k_lis_compact": 18, "k_lis_mx<false>": 18, "k_place_scan": 18,
+        "k_place_scatter": 18, "k_ref_assemble": 1, "k_ref_deposit": 18,
+    },
+}
+
+
+def test_more_calls_launch_what_they_launched(eng, oracle):
+    dev = [dev_of(oracle.comp_3d(turbulence((64, 64, 64), seed=s), (32, 32, 32), 1, 3.0)) for s in (42, 7)]
+    nlev = len(eng.multires_levels((64, 64, 64), (32, 32, 32)))
+    assert nlev > 0
+    imgs = [turbulence((1, 80, 96), seed=s)[0] for s in (1, 2, 3)]
+    one = dev_of(oracle.comp_2d(imgs[0], 1, 2.0, False))
+    three = [dev_of(oracle.comp_2d(img, 1, 2.0, True)) for img in imgs]
+    got = {
+        "decompress_level_0": profile_names(eng, lambda: eng.decompress_level(dev[0], 0)),
+        "decompress_level_last_box": profile_names(eng, lambda: eng.decompress_level(dev[0], nlev - 1, (1, 1, 1),
+                                                                                     (1, 1, 1))),
+        "decompress_batch": profile_names(eng, lambda: eng.decompress_batch(dev, output_float=False)),
+        "decompress_2d": profile_names(eng, lambda: eng.decompress_2d(one, (80, 96), output_float=False)),
+        "decompress_2d_batch": profile_names(eng, lambda: eng.decompress_2d_batch(three, (80, 96), output_float=False,
+                                                                                  header=True)),
+    }
+    for call, rep in got.items():
+        print(call, sum(rep.values()), rep)
+    assert got == PARENT_LAUNCHES_MORE
+
+
 # ---- refusals -------------------------------------------------------------------------------------------------------
 
 def test_level_refusals_leave_the_output_and_engine_alone(eng, oracle):

@@ -333,7 +333,7 @@ def test_retry_of_a_batch_whose_coder_arrays_lay_over_the_chunk_buffer(eng, orac
                                                  ((16, 48, 64), (16, 16, 16), 2, 70.0), ((20, 33, 47), (10, 11, 12), 1, 6.0)])
 def test_small_batches_decode_in_several_sub_batches(eng, oracle, shape, chunks, mode, q):
     """Round 3: a decompression call that has the device to itself cuts a batch of 4 to 55 equally shaped
-    chunks into two or four sub-batches that decode side by side (decompress_impl: streams, events and
+    chunks into two or four sub-batches that decode side by side (DecodeCall::pick_sub_batches: streams, events and
     workspace per sub-batch, outlier streams included); 32, 12, 12 and 24 chunks here, all three modes."""
     v = turbulence(shape)
     want = oracle.comp_3d(v, chunks[::-1], mode, q)
@@ -667,7 +667,7 @@ def test_long_rows_and_odd_tiles(eng, oracle, shape, chunks, dtype):
 
 def test_many_chunks_decode_in_sub_batches(eng, oracle):
     """48 chunks of one shape: the decoder splits the batch into sub-batches on separate streams
-    (engine.hip, decompress_impl); same values as the oracle."""
+    (engine.hip, DecodeCall::pick_sub_batches); same values as the oracle."""
     v = turbulence((192, 256, 256))
     want = oracle.comp_3d(v, (64, 64, 64), 1, 2.0, nthreads=8)
     got = eng.compress(cuda(v), (64, 64, 64), 2.0)
