@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "xform.h"
+#include "lift_window.h"
 #include "speck_dec.h"
 
 namespace sperrhip {
@@ -544,51 +545,7 @@ __device__ __forceinline__ uint32_t reflect_index(int q, int n)
   return (uint32_t)(q < n ? q : period - q);
 }
 
-// The lifting steps of QccWAVCDF97AnalysisSymmetric / SynthesisSymmetric (src/CDF97.cpp:598-666) on
-// 16 consecutive samples r[0..16) of the symmetrically extended signal, r[0] at an even position:
-// r[4..12) come out exactly as the whole-signal loops compute them -- a step reaches one sample to
-// each side, the extension is symmetric about the first and the last sample and a + b == b + a, so
-// the mirrored copies stay equal to the samples the reference's clamped indices refer to.
-template <bool FORWARD>
-__device__ __forceinline__ void lift16(double (&r)[16], const LiftConsts& K)
-{
-  if (FORWARD) {
-#pragma unroll
-    for (int k = 1; k <= 13; k += 2)
-      r[k] = fma(K.alpha, r[k - 1] + r[k + 1], r[k]);
-#pragma unroll
-    for (int k = 2; k <= 12; k += 2)
-      r[k] = fma(K.beta, r[k - 1] + r[k + 1], r[k]);
-#pragma unroll
-    for (int k = 3; k <= 11; k += 2)
-      r[k] = fma(K.gamma, r[k - 1] + r[k + 1], r[k]);
-#pragma unroll
-    for (int k = 4; k <= 10; k += 2)
-      r[k] = K.eps * fma(K.delta, r[k - 1] + r[k + 1], r[k]);
-#pragma unroll
-    for (int k = 5; k <= 11; k += 2)
-      r[k] = (-K.inv_eps) * r[k];
-  }
-  else {
-#pragma unroll
-    for (int k = 1; k <= 15; k += 2)
-      r[k] = (-K.eps) * r[k];
-#pragma unroll
-    for (int k = 2; k <= 14; k += 2) {
-      const double t = K.delta * (r[k - 1] + r[k + 1]);
-      r[k] = fma(r[k], K.inv_eps, -t);
-    }
-#pragma unroll
-    for (int k = 3; k <= 13; k += 2)
-      r[k] = fma(-K.gamma, r[k - 1] + r[k + 1], r[k]);
-#pragma unroll
-    for (int k = 4; k <= 12; k += 2)
-      r[k] = fma(-K.beta, r[k - 1] + r[k + 1], r[k]);
-#pragma unroll
-    for (int k = 5; k <= 11; k += 2)
-      r[k] = fma(-K.alpha, r[k - 1] + r[k + 1], r[k]);
-  }
-}
+// (lift16, lift_window: lift_window.h)
 
 // kCrop (inverse only): the tile's rows of the chunk's window go to the box; a tile without one returns
 template <bool FORWARD, int IO, bool kCrop = false>
@@ -856,6 +813,41 @@ constexpr int kXYZPosI = 6144 / kXYZThreadsI;   // inverse: kXYZStaged * cx <= 6
 #define XYZ_INV_GROUP 3
 #endif
 constexpr int kXYZGroupI = XYZ_INV_GROUP;       // positions whose loads are in flight together
+// samples a task of the y / x pass produces (window: that + 8), forward and inverse; A/B builds: tools/build_variant.sh
+#ifndef XYZ_FWD_YOUT
+#define XYZ_FWD_YOUT 4
+#endif
+#ifndef XYZ_FWD_XOUT
+#define XYZ_FWD_XOUT 8
+#endif
+#ifndef XYZ_INV_YOUT
+#define XYZ_INV_YOUT 4
+#endif
+#ifndef XYZ_INV_XOUT
+#define XYZ_INV_XOUT 4
+#endif
+#ifndef XYZ_INV_XSTORE
+#define XYZ_INV_XSTORE 1   // the inverse kernel's x pass writes the volume itself (0: back into LDS, rows stored from there)
+#endif
+// Timing only (tools/build_variant.sh; the results of such a build are wrong): parts of the two kernels switched off,
+// a sum of 1: global loads, 2: y and x passes, 4: global stores, 8: z pipelines -- 15 leaves staging and barriers.
+#ifndef XYZ_FWD_OFF
+#define XYZ_FWD_OFF 0
+#endif
+#ifndef XYZ_INV_OFF
+#define XYZ_INV_OFF 0
+#endif
+// part `bit` of a kernel is switched off.  A timing build asks a value of the launch as well, one that never has the
+// value asked for: what feeds the part stays needed and the rest of the kernel stays what it was.  Folds to false
+// in the product's build.
+template <int MASK>
+__device__ __forceinline__ bool xyz_off(int bit, uint32_t nseg)
+{
+  return (MASK & bit) != 0 && nseg != ~0u;
+}
+constexpr int kXYZOutFY = XYZ_FWD_YOUT, kXYZOutFX = XYZ_FWD_XOUT, kXYZOutIY = XYZ_INV_YOUT, kXYZOutIX = XYZ_INV_XOUT;
+constexpr bool xyz_out_ok(int n) { return n == 2 || n == 4 || n == 8; }   // (a row's and a tile's last window stays inside the aprons)
+static_assert(xyz_out_ok(kXYZOutFY) && xyz_out_ok(kXYZOutFX) && xyz_out_ok(kXYZOutIY) && xyz_out_ok(kXYZOutIX), "2, 4 or 8 outputs a task");
 constexpr int kXYZBoxSlots = 48;                // inverse, sign-in-word kernel: 256-byte rows of box samples on their way in (12 rows x 4)
 
 // LDS layout of a slice: kXYZStaged rows; row r holds row reflect_index(y0 - 4 + r, cy) of the slice
@@ -883,51 +875,93 @@ __device__ __forceinline__ void xyz_put(double* row, uint32_t x, uint32_t cx, do
 }
 
 // x pass: rows [jlo, jhi) of `src` (aprons filled) -> the same rows of `dst` (another buffer: no barrier
-// inside); aprons of dst are filled when `apron`
-template <bool FORWARD, int NT>
+// inside); a task produces NOUT samples of a row
+template <bool FORWARD, int NT, int NOUT>
 __device__ __forceinline__ void xyz_lift_x(const double* src, double* dst, uint32_t RS, uint32_t cx, uint32_t jlo,
                                            uint32_t jhi, uint32_t tid, const LiftConsts& K)
 {
-  const uint32_t nseg = (cx + kSeg - 1) / kSeg;
+  const uint32_t nseg = (cx + NOUT - 1) / NOUT;
   const uint32_t ntask = (jhi - jlo) * nseg;
 #pragma unroll 1
   for (uint32_t t = tid; t < ntask; t += NT) {
     // lanes of a wavefront take different rows: their addresses differ by the (odd) row stride
     const uint32_t rows = jhi - jlo, sg = t / rows, rb = jlo + (t - sg * rows);
-    const double* row = src + (size_t)rb * RS + sg * kSeg;
-    double r[16];
+    const double* row = src + (size_t)rb * RS + sg * NOUT;
+    double r[NOUT + 8];
 #pragma unroll
-    for (int k = 0; k < 16; k++)
+    for (int k = 0; k < NOUT + 8; k++)
       r[k] = row[k];
-    lift16<FORWARD>(r, K);
-    double* out = dst + (size_t)rb * RS + 4 + sg * kSeg;
+    lift_window<FORWARD, NOUT + 8>(r, K);
+    double* out = dst + (size_t)rb * RS + 4 + sg * NOUT;
 #pragma unroll
-    for (int k = 0; k < kSeg; k++)
-      if (sg * kSeg + k < cx)
+    for (int k = 0; k < NOUT; k++)
+      if (sg * NOUT + k < cx)
         out[k] = r[4 + k];
   }
 }
 
-// y pass: tile rows (LDS rows 4 .. 4 + nt) of `src` -> the same rows of `dst`
-template <bool FORWARD, bool APRON, int NT>
+// the inverse kernel's x pass with the volume as its destination: row rb of `src` is row rb - jlo of `vrows` (rows `vsy`
+// samples apart); what a task produces goes out as it is -- mean added, narrowed -- without another trip through LDS
+template <int NT, int NOUT, typename VT>
+__device__ __forceinline__ void xyz_lift_x_store(const double* src, VT* vrows, size_t vsy, uint32_t RS, uint32_t cx, uint32_t jlo,
+                                                 uint32_t jhi, uint32_t tid, const LiftConsts& K, double mean, bool noMean,
+                                                 bool doStore)
+{
+  const uint32_t nseg = (cx + NOUT - 1) / NOUT;
+  const uint32_t ntask = (jhi - jlo) * nseg;
+#pragma unroll 1
+  for (uint32_t t = tid; t < ntask; t += NT) {
+    const uint32_t rows = jhi - jlo, sg = t / rows, rb = t - sg * rows;   // (lanes take different rows, see xyz_lift_x)
+    const double* row = src + (size_t)(jlo + rb) * RS + sg * NOUT;
+    double r[NOUT + 8];
+#pragma unroll
+    for (int k = 0; k < NOUT + 8; k++)
+      r[k] = row[k];
+    lift_window<false, NOUT + 8>(r, K);
+    VT* out = vrows + (size_t)rb * vsy + sg * NOUT;
+    VT v[NOUT];
+#pragma unroll
+    for (int k = 0; k < NOUT; k++)
+      v[k] = (VT)(noMean ? r[4 + k] : r[4 + k] + mean);
+    if (!doStore)
+      continue;
+    if (sg * NOUT + NOUT <= cx) {   // (a whole segment: one store, aligned as a single sample is)
+      typedef VT Seg __attribute__((ext_vector_type(NOUT), aligned(sizeof(VT))));
+      Seg s;
+#pragma unroll
+      for (int k = 0; k < NOUT; k++)
+        s[k] = v[k];
+      *reinterpret_cast<Seg*>(out) = s;
+    }
+    else {
+#pragma unroll
+      for (int k = 0; k < NOUT; k++)
+        if (sg * NOUT + k < cx)
+          out[k] = v[k];
+    }
+  }
+}
+
+// y pass: tile rows (LDS rows 4 .. 4 + nt) of `src` -> the same rows of `dst`; a task produces NOUT samples of a column
+template <bool FORWARD, bool APRON, int NT, int NOUT>
 __device__ __forceinline__ void xyz_lift_y(const double* src, double* dst, uint32_t RS, uint32_t cx, uint32_t nt,
                                            uint32_t tid, const LiftConsts& K)
 {
-  const uint32_t nq = (nt + kSeg - 1) / kSeg;
+  const uint32_t nq = (nt + NOUT - 1) / NOUT;
   const uint32_t ntask = nq * cx;
 #pragma unroll 1
   for (uint32_t t = tid; t < ntask; t += NT) {
     const uint32_t q = t / cx, x = t - q * cx;   // lanes take consecutive columns
-    const double* top = src + (size_t)(q * kSeg) * RS + 4 + x;
-    double r[16];
+    const double* top = src + (size_t)(q * NOUT) * RS + 4 + x;
+    double r[NOUT + 8];
 #pragma unroll
-    for (int k = 0; k < 16; k++)
+    for (int k = 0; k < NOUT + 8; k++)
       r[k] = top[(size_t)k * RS];
-    lift16<FORWARD>(r, K);
+    lift_window<FORWARD, NOUT + 8>(r, K);
 #pragma unroll
-    for (int k = 0; k < kSeg; k++) {
-      if (q * kSeg + k < nt) {
-        double* row = dst + (size_t)(4 + q * kSeg + k) * RS;
+    for (int k = 0; k < NOUT; k++) {
+      if (q * NOUT + k < nt) {
+        double* row = dst + (size_t)(4 + q * NOUT + k) * RS;
         if (APRON)
           xyz_put(row, x, cx, r[4 + k]);
         else
@@ -1003,7 +1037,8 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
     sxe[k] = sxo[k] = d1p[k] = e1p[k] = d2p[k] = 0.0;
   double vmax = 0.0;
   auto emit = [&](int k, uint32_t zp, double v) {   // sample (ooff, zp) of the transformed chunk
-    buf[(size_t)zp * sliceN + ooff[k]] = v;
+    if (!xyz_off<XYZ_FWD_OFF>(4, nseg))
+      buf[(size_t)zp * sliceN + ooff[k]] = v;
     if (wantMax && (((outerMask >> k) & 1u) || zp >= in2))
       vmax = fmax(vmax, fabs(v));
   };
@@ -1012,9 +1047,15 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
   auto issue = [&](uint32_t z) {
     const VT* src = volc + (size_t)z * vsz;
 #pragma unroll
-    for (int k = 0; k < kXYZStageF; k++)
-      pre[k] = (tid + (uint32_t)k * kXYZThreadsF) < nstage
-                   ? src[(size_t)((pk[k] >> 12) & 0x7fffu) * vsy + (pk[k] & 0xfffu)] : (VT)0;
+    for (int k = 0; k < kXYZStageF; k++) {
+      if (xyz_off<XYZ_FWD_OFF>(1, nseg)) {   // (noise instead of the volume: the coder gets something to code)
+        pre[k] = (VT)(((pk[k] + z * 40503u) * 2654435761u) >> 20);
+      }
+      else {
+        pre[k] = (tid + (uint32_t)k * kXYZThreadsF) < nstage
+                     ? src[(size_t)((pk[k] >> 12) & 0x7fffu) * vsy + (pk[k] & 0xfffu)] : (VT)0;
+      }
+    }
   };
   issue(zFirst);
   for (uint32_t z = zFirst; z < zEnd; z++) {
@@ -1037,11 +1078,15 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
     if (z + 1 < zEnd)
       issue(z + 1);   // (in flight while this slice is lifted)
     XYZ_LDS_BARRIER();
-    xyz_lift_x<true, kXYZThreadsF>(A, B, RSv, cx, 0, kXYZStaged, tidv, K);
+    if (!xyz_off<XYZ_FWD_OFF>(2, nseg))
+      xyz_lift_x<true, kXYZThreadsF, kXYZOutFX>(A, B, RSv, cx, 0, kXYZStaged, tidv, K);
     XYZ_LDS_BARRIER();
-    xyz_lift_y<true, false, kXYZThreadsF>(B, A, RSv, cx, nt, tidv, K);
+    if (!xyz_off<XYZ_FWD_OFF>(2, nseg))
+      xyz_lift_y<true, false, kXYZThreadsF, kXYZOutFY>(B, A, RSv, cx, nt, tidv, K);
     XYZ_LDS_BARRIER();   // (A's tile rows: this slice after x and y; the next slice is staged into B)
     const uint32_t m = z >> 1;
+    if (xyz_off<XYZ_FWD_OFF>(8, nseg))
+      continue;
     if (z & 1) {
 #pragma unroll
       for (int k = 0; k < kXYZPosF; k++)
@@ -1160,7 +1205,8 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   const uint32_t bufx = F.bufx ? F.bufx : cx;                       // the chunk buffer may be compact:
   const size_t bufSlice = (size_t)bufx * (F.bufy ? F.bufy : cy);   // only the next level's box
   const double mean = st[c].mean;
-  const uint32_t lane = tid & 63u, wave = tid >> 6, nwaves = kXYZThreadsI / 64;
+  const uint32_t lane = tid & 63u, nwaves = kXYZThreadsI / 64;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (a scalar, and what is made of it)
 
   if (st[c].is_const != 0) {   // the chunk is its constant
     if constexpr (kCrop) {
@@ -1230,8 +1276,9 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     }
     return buf[(size_t)zp * bufSlice + drow * bufx + dcol];
   };
-  // The slice of z-inverted samples staged in X (all staged rows) -> y pass into Y, x pass back into
-  // X, volume.  X and Y swap from slice to slice: three barriers per slice.
+  // The slice of z-inverted samples staged in X (all staged rows) -> y pass into Y, x pass into the volume (kDirect,
+  // see finish_slice) or, the box variant, back into X and from there into the box: X and Y then swap from slice
+  // to slice, three barriers per slice.
   uint32_t flip = 0;
   // sample k of the slice that is finished next (its staging buffer is free: see finish_slice)
   auto stage = [&](int k, double v) {
@@ -1248,44 +1295,66 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   // rows of a finished slice (in staging buffer `which`) -> volume, mean added, narrowed
   auto store_rows = [&](uint32_t z, uint32_t which) {
     const double* X = sm + (which ? bufN : 0u);
+    // (the lane's addresses are made anew for every slice: computed once, ahead of the loop, they are spilled, and a
+    //  reload here waits for every load and store in flight)
+    uint32_t lanev = lane;
+    asm volatile("" : "+v"(lanev));
     if constexpr (kCrop) {   // (any x origin: one sample per lane)
       if (z - cg.lo[2] >= cg.hi[2] - cg.lo[2])
         return;
       for (uint32_t r = wy0 + wave; r < wy1; r += nwaves) {
         VT* dstrow = crop_row(z, r);
         const double* srow = X + (size_t)(kXYHalo + r) * RS + 4;
-        for (uint32_t x = cg.lo[0] + lane; x < cg.hi[0]; x += 64)
+        for (uint32_t x = cg.lo[0] + lanev; x < cg.hi[0]; x += 64)
           dstrow[x - cg.lo[0]] = (VT)(F.noMean ? srow[x] : srow[x] + mean);
       }
       return;
     }
+    if (xyz_off<XYZ_INV_OFF>(4, nseg))
+      return;
     for (uint32_t r = wave; r < nt; r += nwaves) {
       VT* dstrow = volc + (size_t)z * vsz + (size_t)(y0 + r) * vsy;
       const double* srow = X + (size_t)(kXYHalo + r) * RS + 4;
       if (F.noMean) {   // (uniform)
-        for (uint32_t x = lane; x < cx; x += 64)
+        for (uint32_t x = lanev; x < cx; x += 64)
           dstrow[x] = (VT)srow[x];
       }
       else
-        for (uint32_t x = lane; x < cx; x += 64)
+        for (uint32_t x = lanev; x < cx; x += 64)
           dstrow[x] = (VT)(srow[x] + mean);
     }
   };
+  // kDirect: the x pass writes the volume itself.  The slices are then all staged in the first buffer: its y pass has
+  // read it when the barrier in front of the x pass is behind a wavefront, and the second buffer, which the x pass
+  // reads, is written again only behind the next slice's first barrier.  Two barriers per slice.
+  constexpr bool kDirect = !kCrop && XYZ_INV_XSTORE != 0;
   auto finish_slice = [&](uint32_t z) {
     uint32_t RSv = RS, tidv = tid;   // (see k_lift_xyz_fwd)
     asm volatile("" : "+s"(RSv), "+v"(tidv));
     const uint32_t which = flip;
     double* X = sm + (flip ? bufN : 0u);
     double* Y = sm + (flip ? 0u : bufN);
-    flip ^= 1u;
+    if constexpr (!kDirect)
+      flip ^= 1u;
     XYZ_LDS_BARRIER();
-    xyz_lift_y<false, true, kXYZThreadsI>(X, Y, RSv, cx, nt, tidv, K);
+    if (!xyz_off<XYZ_INV_OFF>(2, nseg))
+      xyz_lift_y<false, true, kXYZThreadsI, kXYZOutIY>(X, Y, RSv, cx, nt, tidv, K);
     XYZ_LDS_BARRIER();
-    xyz_lift_x<false, kXYZThreadsI>(Y, X, RSv, cx, kXYHalo, kXYHalo + nt, tidv, K);
-    XYZ_LDS_BARRIER();
-    store_rows(z, which);
-    // (the next slice is staged into Y, which nobody reads any more; its y pass writes X only after
-    //  the barrier behind that staging, when every row above has been stored)
+    if constexpr (kDirect) {
+      if (!xyz_off<XYZ_INV_OFF>(2, nseg))
+        xyz_lift_x_store<kXYZThreadsI, kXYZOutIX>(Y, volc + (size_t)z * vsz + (size_t)y0 * vsy, vsy, RSv, cx, kXYHalo, kXYHalo + nt,
+                                                   tidv, K, mean, F.noMean != 0, !xyz_off<XYZ_INV_OFF>(4, nseg));
+      else   // (timing builds: the rows as they are)
+        store_rows(z, which ^ 1u);
+    }
+    else {
+      if (!xyz_off<XYZ_INV_OFF>(2, nseg))
+        xyz_lift_x<false, kXYZThreadsI, kXYZOutIX>(Y, X, RSv, cx, kXYHalo, kXYHalo + nt, tidv, K);
+      XYZ_LDS_BARRIER();
+      store_rows(z, which);
+      // (the next slice is staged into Y, which nobody reads any more; its y pass writes X only after
+      //  the barrier behind that staging, when every row above has been stored)
+    }
   };
 
   double o1p[kXYZPosI], e1p[kXYZPosI], o2p[kXYZPosI], e2p[kXYZPosI];
@@ -1373,19 +1442,15 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     XYZ_LDS_BARRIER();
     if (total <= (uint32_t)kXYZBoxSlots && reg == (1u << kXYZPosI) - 1u) {   // (all of the wavefront's positions or none)
       boxLds = reg;
-      boxSlot0 = before;
+      boxSlot0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
     }
   }
   uint32_t* myBox = boxRows + (size_t)boxSlot0 * 64;   // position k's row: myBox + k * 64
   auto pre_issue = [&](uint32_t m) {
-#pragma unroll
-    for (int k = 0; k < kXYZPosI; k++) {
-      uint32_t drow, dcol;
-      pos_off(k, drow, dcol);
-      const uint32_t off = drow * cx + dcol;
-      __builtin_amdgcn_global_load_lds(coef + ((size_t)m * sliceN + off), myPre + (k * 2) * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(coef + ((size_t)(ze + m) * sliceN + off), myPre + (k * 2 + 1) * 64, 4, 0, 0);
-    }
+    if (xyz_off<XYZ_INV_OFF>(1, nseg))
+      return;
+    // (the box rows first: what their addresses are made of may have to come back from scratch, and behind the
+    //  coefficients' loads that reload would wait for every one of them -- the memory counter retires in order)
     if (SG && boxLds != 0 && m < F.inner[2]) {   // (uniform)
 #pragma unroll
       for (int k = 0; k < kXYZPosI; k++) {
@@ -1395,6 +1460,14 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
         const uint32_t* src = reinterpret_cast<const uint32_t*>(buf + ((size_t)m * bufSlice + (size_t)drow * bufx + x0h)) + lane;
         __builtin_amdgcn_global_load_lds(src, myBox + k * 64, 4, 0, 0);
       }
+    }
+#pragma unroll
+    for (int k = 0; k < kXYZPosI; k++) {
+      uint32_t drow, dcol;
+      pos_off(k, drow, dcol);
+      const uint32_t off = drow * cx + dcol;
+      __builtin_amdgcn_global_load_lds(coef + ((size_t)m * sliceN + off), myPre + (k * 2) * 64, 4, 0, 0);
+      __builtin_amdgcn_global_load_lds(coef + ((size_t)(ze + m) * sliceN + off), myPre + (k * 2 + 1) * 64, 4, 0, 0);
     }
   };
   if (fastLoads && mFirst < mB)
@@ -1412,7 +1485,8 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
       // row: those whose rows are the even ones)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this pair's coefficients have landed in LDS (and its box rows)
       const bool boxWave = boxAny != 0 && m < F.inner[2];   // (uniform)
-      if (boxWave && boxLds != 0) {   // the box samples were prefetched with the coefficients
+      const bool zOn = !xyz_off<XYZ_INV_OFF>(8, nseg);
+      if (zOn && boxWave && boxLds != 0) {   // the box samples were prefetched with the coefficients
 #pragma unroll
         for (int k = 0; k < kXYZPosI; k++) {
           const double lo = sg_value(myPre[(k * 2) * 64 + lane]);
@@ -1421,7 +1495,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
           zstep(k, m, mine, true, (lane & 1u) ? lo : bxv, hi);   // (the even lanes are the ones in the box)
         }
       }
-      else {
+      else if (zOn) {
 #pragma unroll
       for (int g = 0; g < kXYZPosI; g += kXYZGroupI) {
         __builtin_amdgcn_sched_barrier(0);   // (kXYZGroupI positions' loads in flight at a time)
