@@ -2724,6 +2724,47 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   return true;
 }
 
+// What a decode call clears of the arrays carve_dec hands out, for nb chunks: once per call ...
+int reset_dec_call(const DecBuffers& d, uint32_t nb, hipStream_t ss)
+{
+  HIP_CHECK(hipMemsetAsync(d.cst, 0, nb * sizeof(CoderState), ss));
+  HIP_CHECK(hipMemsetAsync(d.st, 0, nb * sizeof(DecState), ss));
+  HIP_CHECK(hipMemsetAsync(d.mask, 0, std::max<size_t>(d.maskStride, 1) * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.l0Flags, 0, d.l0FlagStride * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.l0Tab, 0, d.l0FlagStride * 17 * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.l1Flags, 0, d.l0FlagStride * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.l2Flags, 0, d.l0FlagStride * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.hiFlags, 0, d.hiFlagStride * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.sigbits, 0, d.sigbitsStride * nb * 8, ss));
+  if (d.lisStamps)
+    HIP_CHECK(hipMemsetAsync(d.lisStamps, 0, 64 * 8 * nb, ss));
+  return 0;
+}
+
+// ... and before each width pass (wide: 64-bit magnitudes, which are decoded into the fp64 buffer; else the
+// refinement bit planes -- k_ref_assemble writes every coefficient, a plane's words are valid from wordTop down --
+// or the 32-bit coefficients)
+int reset_dec_pass(const DecBatchBufs& bb, uint32_t nb, bool wide, hipStream_t ss)
+{
+  const DecBuffers& d = bb.db;
+  HIP_CHECK(hipMemsetAsync(d.bornM, 0, d.maskPixStride * nb * 8, ss));
+  if (d.tileBorn)
+    HIP_CHECK(hipMemsetAsync(d.tileBorn, 0, d.tileStride * nb, ss));
+  HIP_CHECK(hipMemsetAsync(d.sigOld, 0, d.maskPixStride * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.sigNew, 0, d.maskPixStride * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.sign, 0xff, d.signStride * nb * 8, ss));
+  HIP_CHECK(hipMemsetAsync(d.leafState, 0, d.leafStateStride * nb * 2, ss));
+  HIP_CHECK(hipMemsetAsync(d.leafDirty, 0, d.leafDirtyStride * nb, ss));
+  HIP_CHECK(hipMemsetAsync(d.stream, 0, d.streamStride * nb * 8, ss));
+  if (wide)
+    HIP_CHECK(hipMemsetAsync(bb.vals, 0, bb.valsStride * nb * 8, ss));
+  else if (d.refPlanes)
+    HIP_CHECK(hipMemsetAsync(d.wordTop, 0, d.wordTopStride * nb, ss));
+  else
+    HIP_CHECK(hipMemsetAsync(bb.coef32, 0, d.coefStride * nb * 4, ss));
+  return 0;
+}
+
 // multi-resolution decoding (SPERR3D_OMP_D::decompress(p, true), src/SPERR3D_OMP_D.cpp:50-150):
 // the volume at every coarsened resolution of the chunks (src/sperr_helper.cpp:70-123), coarsest
 // first.  Only for dyadic chunks that tile the volume.
@@ -3563,8 +3604,6 @@ struct DecodeCall {
     }
     HIP_CHECK(hipMemcpyAsync(bb.chunkOff, S.ho.data(), nb * 8, hipMemcpyHostToDevice, ss));
     HIP_CHECK(hipMemcpyAsync(bb.chunkLen, S.hl.data(), nb * 8, hipMemcpyHostToDevice, ss));
-    HIP_CHECK(hipMemsetAsync(d.cst, 0, nb * sizeof(CoderState), ss));
-    HIP_CHECK(hipMemsetAsync(d.st, 0, nb * sizeof(DecState), ss));
     DecPlanHost ph = dec_plan_host(P);
     ph.skipFinish = true;   // launch_inv_quantize / the dequantising inverse passes complete the coefficients
     ph.mxGroups = mxGroupsCall;
@@ -3587,40 +3626,21 @@ struct DecodeCall {
     static const bool gpuWide = !(getenv("SPERR_HIP_LIS_GPUWIDE") && atoi(getenv("SPERR_HIP_LIS_GPUWIDE")) == 0);
     if (!gpuWide)
       ph.l0 = ph.l1 = ph.l2 = false;
-    HIP_CHECK(hipMemsetAsync(d.mask, 0, std::max<size_t>(d.maskStride, 1) * nb * 8, ss));
-    HIP_CHECK(hipMemsetAsync(d.l0Flags, 0, d.l0FlagStride * nb * 8, ss));
-    HIP_CHECK(hipMemsetAsync(d.l0Tab, 0, d.l0FlagStride * 17 * nb * 8, ss));
-    HIP_CHECK(hipMemsetAsync(d.l1Flags, 0, d.l0FlagStride * nb * 8, ss));
-    HIP_CHECK(hipMemsetAsync(d.l2Flags, 0, d.l0FlagStride * nb * 8, ss));
-    HIP_CHECK(hipMemsetAsync(d.hiFlags, 0, d.hiFlagStride * nb * 8, ss));
-    HIP_CHECK(hipMemsetAsync(d.sigbits, 0, d.sigbitsStride * nb * 8, ss));
-    if (d.lisStamps)
-      HIP_CHECK(hipMemsetAsync(d.lisStamps, 0, 64 * 8 * nb, ss));
+    if (reset_dec_call(d, nb, ss))
+      return -1;
     for (int wide = 1; wide >= 0; wide--) {
       if (wide && S.maxWide == 0)
         continue;
-      HIP_CHECK(hipMemsetAsync(d.bornM, 0, d.maskPixStride * nb * 8, ss));
-      if (d.tileBorn)
-        HIP_CHECK(hipMemsetAsync(d.tileBorn, 0, d.tileStride * nb, ss));
-      HIP_CHECK(hipMemsetAsync(d.sigOld, 0, d.maskPixStride * nb * 8, ss));
-      HIP_CHECK(hipMemsetAsync(d.sigNew, 0, d.maskPixStride * nb * 8, ss));
-      HIP_CHECK(hipMemsetAsync(d.sign, 0xff, d.signStride * nb * 8, ss));
-      HIP_CHECK(hipMemsetAsync(d.leafState, 0, d.leafStateStride * nb * 2, ss));
-      HIP_CHECK(hipMemsetAsync(d.leafDirty, 0, d.leafDirtyStride * nb, ss));
-      HIP_CHECK(hipMemsetAsync(d.stream, 0, d.streamStride * nb * 8, ss));
+      if (reset_dec_pass(bb, nb, wide != 0, ss))
+        return -1;
       DecBuffers dw = d;
       if (wide) {  // 64-bit magnitudes live in the fp64 buffer, converted in place afterwards
         dw.coef = bb.vals;
         dw.coefStride = bb.valsStride;
         dw.refPlanes = nullptr;
-        HIP_CHECK(hipMemsetAsync(bb.vals, 0, bb.valsStride * nb * 8, ss));
       }
-      else if (d.refPlanes) { // (k_ref_assemble writes every coefficient; a plane's words are valid from wordTop down)
-        HIP_CHECK(hipMemsetAsync(d.wordTop, 0, d.wordTopStride * nb, ss));
+      else if (d.refPlanes)
         dw.coefSigned = b.fuseDq ? 1u : 0u;   // (read by the dequantising inverse passes only: LiftFuse::coefSigned)
-      }
-      else
-        HIP_CHECK(hipMemsetAsync(bb.coef32, 0, d.coefStride * nb * 4, ss));
       // the header kernel must run even when no plane does (constant / all-zero chunks)
       if (launch_speck_decode(ss, dw, ph, d_src, bb.chunkOff, bb.chunkLen, wide != 0, wide ? S.maxWide : S.maxNarrow))
         return -1;
@@ -4938,35 +4958,14 @@ int sperrhip_speck3d_decode_dev(const void* d_stream, size_t stream_len, size_t 
     const uint64_t off = 0, len = 17 + stream_len;
     HIP_CHECK(hipMemcpyAsync(bb.chunkOff, &off, 8, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(bb.chunkLen, &len, 8, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(d.cst, 0, sizeof(CoderState), st));
-    HIP_CHECK(hipMemsetAsync(d.st, 0, sizeof(DecState), st));
-    HIP_CHECK(hipMemsetAsync(d.bornM, 0, d.maskPixStride * 8, st));
-    if (d.tileBorn)
-      HIP_CHECK(hipMemsetAsync(d.tileBorn, 0, d.tileStride, st));
-    HIP_CHECK(hipMemsetAsync(d.sigOld, 0, d.maskPixStride * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.sigNew, 0, d.maskPixStride * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.sign, 0xff, d.signStride * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.leafState, 0, d.leafStateStride * 2, st));
-    HIP_CHECK(hipMemsetAsync(d.leafDirty, 0, d.leafDirtyStride, st));
-    HIP_CHECK(hipMemsetAsync(d.stream, 0, d.streamStride * 8, st));
+    if (reset_dec_call(d, 1, st) || reset_dec_pass(bb, 1, wide, st))
+      return -1;
     const uint32_t n = P->N;
     if (wide) {
       d.coef = bb.vals;
       d.coefStride = bb.valsStride;
-      HIP_CHECK(hipMemsetAsync(bb.vals, 0, (size_t)n * 8, st));
     }
-    else if (d.refPlanes)
-      HIP_CHECK(hipMemsetAsync(d.wordTop, 0, d.wordTopStride, st));
-    else
-      HIP_CHECK(hipMemsetAsync(bb.coef32, 0, (size_t)n * 4, st));
     const DecPlanHost ph = dec_plan_host(*P);
-    HIP_CHECK(hipMemsetAsync(d.mask, 0, std::max<size_t>(d.maskStride, 1) * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.l0Flags, 0, d.l0FlagStride * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.l0Tab, 0, d.l0FlagStride * 17 * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.l1Flags, 0, d.l0FlagStride * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.l2Flags, 0, d.l0FlagStride * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.hiFlags, 0, d.hiFlagStride * 8, st));
-    HIP_CHECK(hipMemsetAsync(d.sigbits, 0, d.sigbitsStride * 8, st));
     if (launch_speck_decode(st, d, ph, wrap, bb.chunkOff, bb.chunkLen, wide, nbp))
       return -1;
     HIP_CHECK(hipMemcpyAsync(d_coef, d.coef, (size_t)n * (wide ? 8 : 4), hipMemcpyDeviceToDevice, st));

@@ -18,6 +18,7 @@
 // SPECK_INT.cpp:95-105); the loop stops where the reference's does.
 #include "speck_dec.h"
 #include "bit_words.h"
+#include "lis_chain.h"
 
 namespace sperrhip {
 
@@ -958,21 +959,17 @@ __global__ void __launch_bounds__(64) k_lis_walk(DecBuffers b, int p)
 }
 
 // ------------------------------------------------------------------------------------------
-// LIS phase, list of the smallest sets (2x2x2 leaf sets: class 0).  The sorting pass visits the
-// lists from the smallest sets to the largest (SPECK_INT.cpp:317-327), so this list's code starts
-// where the LIP scan ended and its entry count is known: the whole GPU decodes it before
-// k_lis_l1 / k_lis_hi take the other lists.  An entry is '0', or '1' followed by the <= 16 bits of its
-// eight pixels; nothing is born.  The stream is cut into blocks of kL0W bits handed out by a
-// ticket counter; each block
-//   * finds, for every bit position, the length of a token that would start there, and by pointer
-//     jumping where a chain of tokens entering at that position leaves the block, how many tokens
-//     it holds and how many of them are significant;
-//   * waits for its predecessor's look-back word (entry offset, entries and significant entries so
-//     far), publishes its own straight from those tables, and only then
-//   * marks the tokens really on the chain and lets every thread handle its share: insignificant
-//     entries are copied to the next list in order, significant ones become leaf events.
-// A block is handed out only after all earlier ones, so a waiting block always waits for a
-// workgroup that is running (or has seen the pass end).
+// LIS phase, the GPU-wide list kernels: k_lis_l0, k_lis_l1, k_lis_l2 decode the lists of the three smallest set
+// sizes, one after the other -- the sorting pass visits the lists from the smallest sets to the largest
+// (SPECK_INT.cpp:317-327), so the first list's code starts where the LIP scan ended and each next one's where the
+// list before it ended -- before k_lis_hi takes the other lists.  The scheme they share (blocks of the stream handed
+// out by a ticket counter, token chains by pointer jumping, a look-back word per block, marks) is described in
+// lis_chain.h, the token grammar in lis_token.h; each kernel below says what it adds.
+//
+// k_lis_l0: the list of the smallest sets (2x2x2 leaf sets: class 0).  An entry is '0', or '1' followed by the
+// <= 16 bits of its eight pixels; nothing is born.  Insignificant entries are copied to the next list in order,
+// significant ones become leaf events.  Its own: blocks of 8192 positions and 1024 threads at 64 registers, the
+// decoupled look-back through published memo tables, and the block's list entries staged in LDS.
 // ------------------------------------------------------------------------------------------
 // (k_lis_l0's tick counters cost registers the kernel does not have at two workgroups a compute unit: they are compiled
 //  in with -DSPERR_HIP_L0_STAMPS=1 only, for tools/hi_stamps.py)
@@ -985,12 +982,20 @@ constexpr int kL0Threads = 1024;
 // (k_lis_l1 with 512 threads: two workgroups of eight wavefronts a compute unit and 128 registers a thread, where 1024
 //  threads at 64 registers spilled 38 of them: 98.3 -> 100.8 GB/s of decompression at 64 chunks, round 5)
 constexpr int kL1Threads = 512;
-constexpr int kL0Sub = kL0W / 64;
 constexpr int kL0Stage = kL0W / 2;   // list entries of a block staged in LDS (hop64's 32 KB)
-constexpr uint32_t kL0None = 0xffffffffu;
 constexpr size_t kL0Smem = (size_t)(kL0W / 64 + 4) * 8 + (size_t)kL0W * (1 + 4 + 4);
 
-// chain summary: tokens << 21 | significant tokens << 14 | position reached (block-relative)
+// A leaf event: the 2x2x2 set at (cx, cy, cz) of grid g splits into its pixels, coded from position y
+__device__ __forceinline__ void leaf_event(const DecBuffers& b, uint64_t* leafEv, uint32_t slot, const LdsBits& bits, uint32_t y,
+                                           const Grid& g, uint32_t cx, uint32_t cy, uint32_t cz)
+{
+  uint32_t sigm, negm;
+  split8_pixels(bits.bits32(y), sigm, negm);
+  const uint32_t fid = g.nodeOff + (((cz << g.e[1]) + cy) << g.e[0]) + cx;
+  if (slot < b.leafCap)
+    leafEv[slot] = (uint64_t)fid | ((uint64_t)sigm << 32) | ((uint64_t)negm << 40);
+}
+
 __global__ void __launch_bounds__(kL0Threads) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_lis_l0(DecBuffers b, int p)
 {
@@ -1004,15 +1009,13 @@ k_lis_l0(DecBuffers b, int p)
     return;   // (k_lis_hi finds the list empty as well)
   extern __shared__ __attribute__((aligned(16))) char l0_smem[];
   uint64_t* wbits = reinterpret_cast<uint64_t*>(l0_smem);
-  const uint32_t* w32 = reinterpret_cast<const uint32_t*>(l0_smem);
   uint32_t* hop64 = reinterpret_cast<uint32_t*>(l0_smem + (size_t)(kL0W / 64 + 4) * 8);
   uint32_t* hopW = hop64 + kL0W;     // later: the marks of the tokens on the chain
   uint8_t* U = reinterpret_cast<uint8_t*>(hopW + kL0W);
   const uint64_t* stg64 = reinterpret_cast<const uint64_t*>(hop64);   // (later: the block's list entries)
   __shared__ uint32_t memoX[32], memoC[32], memoS[32];
-  __shared__ uint32_t entR[kL0W / 1024], entK[kL0W / 1024], entS[kL0W / 1024];
-  __shared__ uint32_t blkE[kL0Sub], blkK[kL0Sub], blkS[kL0Sub];
-  __shared__ uint32_t sh_ticket, sh_e, sh_rank, sh_sig, sh_last, sh_stop, sh_endpos, sh_endsig;
+  __shared__ ChainShared<kL0W> cs;
+  __shared__ uint32_t sh_lbT[64][17];   // X << 24 | tokens << 10 | significant tokens
 
   const int tid = threadIdx.x;
   const uint32_t lane = (uint32_t)tid & 63u, wave = (uint32_t)tid >> 6;
@@ -1024,90 +1027,26 @@ k_lis_l0(DecBuffers b, int p)
   uint64_t* keep = b.lis[nx] + c * b.lisStride + b.levelOff[L];
   uint64_t* leafEv = b.leafEv + c * b.leafStride;
   unsigned long long* flags = b.l0Flags + c * b.l0FlagStride;
-  unsigned long long* tabs = b.l0Tab ? b.l0Tab + c * b.l0FlagStride * 17 : nullptr;   // the blocks' published memo tables
-  __shared__ uint32_t sh_lbT[64][17];   // X << 24 | tokens << 10 | significant tokens
+  unsigned long long* tabs = b.l0Tab + c * b.l0FlagStride * 17;   // the blocks' published memo tables
   const unsigned long long tag = (unsigned long long)(p + 1) << 56;
 
   for (;;) {
-    if (tid == 0) {
-      const bool over = __hip_atomic_load(&s.l0PlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                        p + 1;
-      sh_ticket = over ? kL0None : atomicAdd(&s.l0Ticket, 1u);
-    }
-    __syncthreads();
-    const uint32_t i = sh_ticket;
-    if (i == kL0None || (size_t)i + 1 >= b.l0FlagStride)
+    const uint32_t i = chain_ticket(cs, &s.l0PlaneP1, &s.l0Ticket, p, b.l0FlagStride);
+    if (i == kL0None)
       break;
     const bool l0stamps = SPERR_HIP_L0_STAMPS && b.lisStamps != nullptr && tid == 0 && c == 0;
     uint64_t l0t[6] = {l0stamps ? __builtin_readcyclecounter() : 0, 0, 0, 0, 0, 0};
     const uint64_t a = phase0 + (uint64_t)i * kL0W;
-    const uint64_t w0 = a >> 6;
-    const uint32_t q0 = (uint32_t)(a & 63);
-    for (uint32_t k = tid; k < (uint32_t)(kL0W / 64 + 4); k += kL0Threads)
-      wbits[k] = w0 + k < nwordsAvail ? words[w0 + k] : 0ull;
-    __syncthreads();
-    auto bit_at = [&](uint32_t r) -> uint32_t {
-      const uint32_t q = r + q0;
-      return (w32[q >> 5] >> (q & 31)) & 1u;
-    };
-    auto bits32 = [&](uint32_t r) -> uint32_t {
-      const uint32_t q = r + q0, sh = q & 31;
-      const uint32_t lo = w32[q >> 5], hi = w32[(q >> 5) + 1];
-      return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-    };
+    const LdsBits bits = chain_load_words<kL0W / 64 + 4, kL0Threads>(wbits, words, a, nwordsAvail);
     // ---- token length at every position
-    for (uint32_t r = tid; r < (uint32_t)kL0W; r += kL0Threads) {
-      uint32_t len = 1;
-      if (bit_at(r)) {
-        const uint32_t v = bits32(r + 1);
-        uint32_t y = 0, found = 0;
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-          const uint32_t bit = (v >> y) & 1u;
-          found |= bit;
-          y += 1u + bit;
-        }
-        const uint32_t bit = found ? (v >> y) & 1u : 1u;
-        len = 1u + y + found + bit;
-      }
-      U[r] = (uint8_t)len;
-    }
+    for (uint32_t r = tid; r < (uint32_t)kL0W; r += kL0Threads)
+      U[r] = (uint8_t)(bits.bit_at(r) ? 1u + split8_len(bits.bits32(r + 1)) : 1u);
     __syncthreads();
-    // ---- chains inside 64-position sub-blocks (lane = position)
-    for (uint32_t sb = wave; sb < (uint32_t)kL0Sub; sb += kL0Threads / 64) {
-      const uint32_t r = sb * 64 + lane, hEnd = (sb + 1) * 64;
-      uint32_t v = (1u << 21) | (bit_at(r) << 14) | (r + U[r]);
-      bool inb = (v & 0x3fffu) < hEnd;
-      for (int it = 0; it < 6 && __any(inb); it++) {
-        const uint32_t o = __shfl(v, (v & 0x3fffu) & 63u, 64);
-        if (inb) {
-          v = (v & ~0x3fffu) + o;
-          inb = (v & 0x3fffu) < hEnd;
-        }
-      }
-      hop64[r] = v;
-      hopW[r] = v;
-    }
-    __syncthreads();
-    // ---- widen a copy to 1024-position blocks (in place: any version read is a valid summary)
-    for (uint32_t wide = 128; wide <= 1024; wide <<= 1) {
-      for (uint32_t r = tid; r < (uint32_t)kL0W; r += kL0Threads) {
-        const uint32_t v = hopW[r], e = v & 0x3fffu;
-        if (e < (uint32_t)kL0W && e / wide == r / wide)
-          hopW[r] = (v & ~0x3fffu) + hopW[e];
-      }
-      __syncthreads();
-    }
+    chain_hops<kL0W, kL0Threads>(bits, U, hop64, hopW);
     // ---- the whole block, for each of the 17 offsets a chain can enter at
     if (tid < 17) {
-      uint32_t r = tid, cnt = 0, sg = 0;
-      while (r < (uint32_t)kL0W) {
-        const uint32_t v = hopW[r];
-        cnt += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-      memoX[tid] = r - kL0W;
+      uint32_t cnt, sg;
+      memoX[tid] = chain_through<kL0W>(hopW, tid, cnt, sg);
       memoC[tid] = cnt;
       memoS[tid] = sg;
     }
@@ -1117,12 +1056,13 @@ k_lis_l0(DecBuffers b, int p)
     //      waited for its predecessor's state, applied its table and published -- a hand-over through L2 per block,
     //      about a microsecond each, the list's whole length in series (what bounded a batch of a few chunks).  Now
     //      a block PUBLISHES ITS TABLE as soon as it has it (tagged entries, no fence), and a block that looks back
-    //      takes the nearest state that is out (64 blocks back at most: as many workgroups as a chunk has) and
-    //      applies the tables of the blocks in between itself -- the decoupled look-back of a scan whose carry is a
-    //      function, not a sum.  Blocks that wait resolve together instead of one after the other.
+    //      takes the nearest state that is out (64 blocks back at most: as many workgroups as a chunk has; the
+    //      virtual block before the first always is) and applies the tables of the blocks in between itself -- the
+    //      decoupled look-back of a scan whose carry is a function, not a sum.  Blocks that wait resolve together
+    //      instead of one after the other.
     if (l0stamps)
       l0t[1] = __builtin_readcyclecounter();
-    if (b.l0Tab && tid < 17)
+    if (tid < 17)
       __hip_atomic_store(tabs + (size_t)i * 17 + tid,
                          tag | ((unsigned long long)memoX[tid] << 50) | ((unsigned long long)memoC[tid] << 25) |
                              (unsigned long long)memoS[tid],
@@ -1135,9 +1075,9 @@ k_lis_l0(DecBuffers b, int p)
         const int idx = (int)i - 1 - (int)lane;   // lane j looks at block i - 1 - j (-1: before the first block)
         for (;;) {
           unsigned long long f = 0;
-          if (idx >= 0 && (lane == 0 || b.l0Tab))
+          if (idx >= 0)
             f = __hip_atomic_load(flags + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const bool out = (idx >= 0 && (f >> 56) == (unsigned long long)(p + 1)) || (idx == -1 && b.l0Tab);
+          const bool out = (idx >= 0 && (f >> 56) == (unsigned long long)(p + 1)) || idx == -1;
           const uint64_t om = __ballot(out);
           bool done = false;
           if (om) {
@@ -1199,101 +1139,31 @@ k_lis_l0(DecBuffers b, int p)
           }
         }
       }
-      if (tid == 0) {
-      uint32_t last = 0;
-      if (!stop) {
-        if (rank + memoC[e] >= n) {   // the list ends inside this block
-          last = 1;
-          __hip_atomic_store(flags + i, tag | (1ull << 55), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&s.l0PlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        else
-          __hip_atomic_store(flags + i,
-                             tag | ((unsigned long long)memoX[e] << 50) |
-                                 ((unsigned long long)(rank + memoC[e]) << 25) |
-                                 (unsigned long long)(sg + memoS[e]),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      sh_e = e;
-      sh_rank = rank;
-      sh_sig = sg;
-      sh_last = last;
-      sh_stop = stop;
-      sh_endpos = 0;
-      sh_endsig = 0;
-      }
+      if (tid == 0)
+        lookback_publish<50, 25>(cs, &s.l0PlaneP1, flags + i, p, n, stop, e, rank, sg, memoX[e], memoC[e], memoS[e]);
     }
-    for (uint32_t k = tid; k < (uint32_t)kL0Sub; k += kL0Threads)
-      blkE[k] = kL0None;
-    if (tid < kL0W / 1024)
-      entR[tid] = kL0None;
+    chain_clear_entries<kL0W, kL0Threads>(cs);
     __syncthreads();
-    if (sh_stop)
+    if (cs.stop)
       break;
     if (l0stamps)
       l0t[2] = __builtin_readcyclecounter();
-    // ---- where the chain enters each 1024-block, then each sub-block
-    if (tid == 0) {
-      uint32_t r = sh_e, rk = 0, sg = 0;
-      while (r < (uint32_t)kL0W) {
-        entR[r >> 10] = r;
-        entK[r >> 10] = rk;
-        entS[r >> 10] = sg;
-        const uint32_t v = hopW[r];
-        rk += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-    }
-    __syncthreads();
-    if (tid < kL0W / 1024 && entR[tid] != kL0None) {
-      uint32_t r = entR[tid], rk = entK[tid], sg = entS[tid];
-      const uint32_t end = ((uint32_t)tid + 1) * 1024;
-      while (r < end) {
-        blkE[r >> 6] = r;
-        blkK[r >> 6] = rk;
-        blkS[r >> 6] = sg;
-        const uint32_t v = hop64[r];
-        rk += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-    }
-    __syncthreads();
+    chain_entries(cs, hop64, hopW);
     if (l0stamps)
       l0t[3] = __builtin_readcyclecounter();
-    const uint32_t rank0 = sh_rank, sig0 = sh_sig;
+    const uint32_t rank0 = cs.rank, sig0 = cs.sig;
     const uint32_t nloc = n - rank0;   // entries the list still holds at the start of the block
     // ---- the block's list entries are one stretch of the list: they travel from HBM straight into LDS (hop64 is
     //      free now: 4096 entries; global_load_lds, no register holds them) while the marks are worked out.  Fetched
     //      where each token is handled they were eight loads in series per thread, two thousand cycles each (the
     //      registers to have them in flight together this kernel does not have: profiles/r5_l01_phases.txt).
-    const uint32_t nstg = min(min(memoC[sh_e], nloc), (uint32_t)kL0Stage);
+    const uint32_t nstg = min(min(memoC[cs.e], nloc), (uint32_t)kL0Stage);
     {
       const uint32_t* list32 = reinterpret_cast<const uint32_t*>(list + rank0);
       for (uint32_t d0 = wave * 64u; d0 < 2u * nstg; d0 += (kL0Threads / 64) * 64u)
         __builtin_amdgcn_global_load_lds(list32 + min(d0 + lane, 2u * nstg - 1u), hop64 + d0, 4, 0, 0);
     }
-    // ---- marks: (1 + entries before the token) | significant entries before it << 16, block-local
-    for (uint32_t r = tid; r < (uint32_t)kL0W; r += kL0Threads)
-      hopW[r] = 0;
-    __syncthreads();
-    if (tid < kL0Sub && blkE[tid] != kL0None) {
-      uint32_t r = blkE[tid], rk = blkK[tid], sg = blkS[tid];
-      const uint32_t end = ((uint32_t)tid + 1) * 64;
-      bool did = false;
-      while (r < end && rk < nloc) {
-        hopW[r] = (rk + 1u) | (sg << 16);
-        rk++;
-        sg += bit_at(r);
-        r += U[r];
-        did = true;
-      }
-      if (did && rk == nloc) {   // this thread decoded the list's last entry
-        sh_endpos = r;
-        sh_endsig = sg;
-      }
-    }
+    chain_marks<kL0W, kL0Threads>(cs, bits, U, hopW, nloc);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the staged list entries have landed)
     __syncthreads();
     if (l0stamps)
@@ -1307,29 +1177,12 @@ k_lis_l0(DecBuffers b, int p)
       const uint32_t q = rank0 + (mk & 0xffffu) - 1u, sb = sig0 + (mk >> 16);
       const uint32_t li = (mk & 0xffffu) - 1u;
       const uint64_t ident = li < nstg ? stg64[li] : list[q];
-      if (!bit_at(r)) {
+      if (!bits.bit_at(r)) {
         keep[q - sb] = ident;
         continue;
       }
-      const uint32_t v = bits32(r + 1);
-      uint32_t yy = 0, found = 0, sigm = 0, negm = 0;
-#pragma unroll
-      for (int k = 0; k < 7; k++) {
-        const uint32_t bit = (v >> yy) & 1u, sgn = (v >> (yy + 1)) & 1u;
-        sigm |= bit << k;
-        negm |= (bit & (sgn ^ 1u)) << k;
-        found |= bit;
-        yy += 1u + bit;
-      }
-      const uint32_t bit = found ? (v >> yy) & 1u : 1u;
-      const uint32_t sgn = (v >> (yy + found)) & 1u;
-      sigm |= bit << 7;
-      negm |= (bit & (sgn ^ 1u)) << 7;
       const Node nd = unpack_node(ident);
-      const Grid g = t.grids[nd.grid];
-      const uint32_t fid = g.nodeOff + ((((uint32_t)nd.i[2] << g.e[1]) + nd.i[1]) << g.e[0]) + nd.i[0];
-      if (sb < b.leafCap)
-        leafEv[sb] = (uint64_t)fid | ((uint64_t)sigm << 32) | ((uint64_t)negm << 40);
+      leaf_event(b, leafEv, sb, bits, r + 1, t.grids[nd.grid], nd.i[0], nd.i[1], nd.i[2]);
     }
     if (l0stamps) {
       l0t[5] = __builtin_readcyclecounter();
@@ -1337,12 +1190,12 @@ k_lis_l0(DecBuffers b, int p)
       for (int k = 0; k < 5; k++)
         atomicAdd(reinterpret_cast<unsigned long long*>(b.lisStamps + 49 + k), l0t[k + 1] - l0t[k]);
     }
-    if (sh_last) {
+    if (cs.last) {
       if (tid == 0) {
-        s.l0End = a + sh_endpos;
-        s.l0Sig = sig0 + sh_endsig;
-        s.leafCount = sig0 + sh_endsig;
-        s.listLen[nx][L] = n - (sig0 + sh_endsig);
+        s.l0End = a + cs.endpos;
+        s.l0Sig = sig0 + cs.endsig;
+        s.leafCount = sig0 + cs.endsig;
+        s.listLen[nx][L] = n - (sig0 + cs.endsig);
       }
       break;
     }
@@ -1351,11 +1204,10 @@ k_lis_l0(DecBuffers b, int p)
 }
 
 // ------------------------------------------------------------------------------------------
-// LIS phase, the next list: 4x4x4 sets (class 1) whose children are the 2x2x2 leaf sets.  Same
-// scheme as k_lis_l0 with one more level inside a token: an entry is '0', or '1' followed by its
-// eight children, each '0' (the child joins the list of the smallest sets: a birth, recorded
-// with its stream position exactly like k_lis_hi does) or '1' + eight pixels (a leaf event).
-// A token takes at most 1 + 7 * 17 + 17 = 137 bits, so the tables of a block cover kL1Ahead
+// k_lis_l1, the next list: 4x4x4 sets (class 1) whose children are the 2x2x2 leaf sets.  One more level inside a
+// token: an entry is '0', or '1' followed by its eight children, each '0' (the child joins the list of the
+// smallest sets: a birth, recorded with its stream position exactly like k_lis_hi does) or '1' + eight pixels (a
+// leaf event).  A token takes at most 1 + 7 * 17 + 17 = 137 bits, so the tables of a block cover kL1Ahead
 // positions more than the block itself.  Births and leaf events get their slots per block: each
 // token reserves block-local slots while it is counted, the block reserves its range with one
 // atomic per counter, and a second sweep writes.
@@ -1364,7 +1216,6 @@ constexpr int kL1W = 4096;
 constexpr int kL1Ahead = 192;
 constexpr int kL1P = kL1W + kL1Ahead;           // positions with class-0 tables
 constexpr int kL1MaxTok = 137;
-constexpr int kL1Per = kL1W / kL1Threads;        // positions a thread looks at in a sweep
 constexpr int kL1QCap = kL1W / 2;               // children of a block's significant tokens: eight of each of kL1W / 16 tokens
 constexpr size_t kL1Smem = (size_t)(kL1P / 64 + 4) * 8 + (size_t)(kL1W + 4) * 4 + (size_t)kL1W * (4 + 1) +
                            (size_t)kL1P * 2;
@@ -1385,22 +1236,18 @@ k_lis_l1(DecBuffers b, int p)
     return;   // (k_lis_hi takes the list)
   extern __shared__ __attribute__((aligned(16))) char l1_smem[];
   uint64_t* wbits = reinterpret_cast<uint64_t*>(l1_smem);
-  const uint32_t* w32 = reinterpret_cast<const uint32_t*>(l1_smem);
   uint32_t* hop64 = reinterpret_cast<uint32_t*>(l1_smem + (size_t)(kL1P / 64 + 4) * 8);
   uint32_t* hopW = hop64 + kL1W + 4;     // later: the marks of the tokens on the chain
   uint8_t* U1 = reinterpret_cast<uint8_t*>(hopW + kL1W);   // token length at every position
   uint8_t* U0 = U1 + kL1W;           // coded class-0 item: 1, or 1 + T0 of the next position
   uint8_t* T0 = U0 + kL1P;           // split of a class-0 set that starts here
   __shared__ uint32_t memoX[kL1MaxTok + 1], memoC[kL1MaxTok + 1], memoS[kL1MaxTok + 1];
-  __shared__ uint32_t entR[kL1W / 1024], entK[kL1W / 1024], entS[kL1W / 1024];
-  __shared__ uint32_t blkE[kL1W / 64], blkK[kL1W / 64], blkS[kL1W / 64];
-  __shared__ uint32_t sh_ticket, sh_e, sh_rank, sh_sig, sh_last, sh_stop, sh_endpos, sh_endsig;
+  __shared__ ChainShared<kL1W> cs;
   __shared__ uint32_t sh_nb, sh_nl, sh_baseB, sh_baseL, sh_ntok;
   __shared__ uint16_t tokQ[kL1W / 16];   // the significant tokens of a block: 16 bits each and more
   __shared__ Grid sh_grids[kTabLdsGrids];   // (the launcher checks that the tree's grids fit)
 
   const int tid = threadIdx.x;
-  const uint32_t lane = (uint32_t)tid & 63u, wave = (uint32_t)tid >> 6;
   const Tree& t = b.tree;
   for (uint32_t k = tid; k < t.ngrids; k += kL1Threads)
     sh_grids[k] = t.grids[k];
@@ -1414,7 +1261,6 @@ k_lis_l1(DecBuffers b, int p)
   uint64_t* bornPacked = b.bornPacked + c * b.bornPitch;
   uint64_t* bornPosLev = b.bornPosLev + c * b.bornPitch;
   unsigned long long* flags = b.l1Flags + c * b.l0FlagStride;
-  const unsigned long long tag = (unsigned long long)(p + 1) << 56;
   const uint64_t maskBits = (uint64_t)b.maskWords * 64;
   const uint32_t bornLev = b.levelClass[L].lev[0];
   const uint32_t bornSlot = b.levelSlot[bornLev];
@@ -1422,256 +1268,60 @@ k_lis_l1(DecBuffers b, int p)
 
   for (;;) {
     if (tid == 0) {
-      const bool over = __hip_atomic_load(&s.l1PlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                        p + 1;
-      sh_ticket = over ? kL0None : atomicAdd(&s.l1Ticket, 1u);
       sh_nb = 0;
       sh_nl = 0;
       sh_ntok = 0;
     }
-    __syncthreads();
-    const uint32_t i = sh_ticket;
-    if (i == kL0None || (size_t)i + 1 >= b.l0FlagStride)
+    const uint32_t i = chain_ticket(cs, &s.l1PlaneP1, &s.l1Ticket, p, b.l0FlagStride);
+    if (i == kL0None)
       break;
     const bool l1stamps = b.lisStamps != nullptr && tid == 0 && c == 0;
     uint64_t l1t0 = l1stamps ? __builtin_readcyclecounter() : 0, l1t1 = 0, l1t2 = 0, l1t3 = 0, l1t4 = 0, l1t5 = 0;
     const uint64_t a = start0 + (uint64_t)i * kL1W;
-    const uint64_t w0 = a >> 6;
-    const uint32_t q0 = (uint32_t)(a & 63);
-    for (uint32_t k = tid; k < (uint32_t)(kL1P / 64 + 4); k += kL1Threads)
-      wbits[k] = w0 + k < nwordsAvail ? words[w0 + k] : 0ull;
-    __syncthreads();
-    auto bit_at = [&](uint32_t r) -> uint32_t {
-      const uint32_t q = r + q0;
-      return (w32[q >> 5] >> (q & 31)) & 1u;
-    };
-    auto bits32 = [&](uint32_t r) -> uint32_t {
-      const uint32_t q = r + q0, sh = q & 31;
-      const uint32_t lo = w32[q >> 5], hi = w32[(q >> 5) + 1];
-      return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-    };
+    const LdsBits bits = chain_load_words<kL1P / 64 + 4, kL1Threads>(wbits, words, a, nwordsAvail);
     // ---- class 0: split length, then the coded item
-    for (uint32_t r = tid; r < (uint32_t)kL1P; r += kL1Threads) {
-      const uint32_t v = bits32(r);
-      uint32_t y = 0, found = 0;
-#pragma unroll
-      for (int k = 0; k < 7; k++) {
-        const uint32_t bit = (v >> y) & 1u;
-        found |= bit;
-        y += 1u + bit;
-      }
-      const uint32_t bit = found ? (v >> y) & 1u : 1u;
-      T0[r] = (uint8_t)(y + found + bit);
-    }
+    for (uint32_t r = tid; r < (uint32_t)kL1P; r += kL1Threads)
+      T0[r] = (uint8_t)split8_len(bits.bits32(r));
     __syncthreads();
     for (uint32_t r = tid; r < (uint32_t)kL1P; r += kL1Threads)
-      U0[r] = (uint8_t)((bit_at(r) && r + 1 < (uint32_t)kL1P) ? 1u + T0[r + 1] : 1u);
+      U0[r] = (uint8_t)((bits.bit_at(r) && r + 1 < (uint32_t)kL1P) ? 1u + T0[r + 1] : 1u);
     __syncthreads();
     // ---- class 1: the token at every position of the block
-    for (uint32_t r = tid; r < (uint32_t)kL1W; r += kL1Threads) {
-      uint32_t len = 1;
-      if (bit_at(r)) {
-        uint32_t y = r + 1, found = 0;
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-          const uint32_t u = U0[y];
-          found |= u - 1u;
-          y += u;
-        }
-        y += found ? U0[y] : T0[y];
-        len = y - r;
-      }
-      U1[r] = (uint8_t)len;
-    }
+    for (uint32_t r = tid; r < (uint32_t)kL1W; r += kL1Threads)
+      U1[r] = (uint8_t)(bits.bit_at(r) ? 1u + parent_split_len(U0, T0, r + 1) : 1u);
     __syncthreads();
-    // ---- chains inside 64-position sub-blocks (lane = position)
-    for (uint32_t sb = wave; sb < (uint32_t)(kL1W / 64); sb += kL1Threads / 64) {
-      const uint32_t r = sb * 64 + lane, hEnd = (sb + 1) * 64;
-      uint32_t v = (1u << 21) | (bit_at(r) << 14) | (r + U1[r]);
-      bool inb = (v & 0x3fffu) < hEnd;
-      for (int it = 0; it < 6 && __any(inb); it++) {
-        const uint32_t o = __shfl(v, (v & 0x3fffu) & 63u, 64);
-        if (inb) {
-          v = (v & ~0x3fffu) + o;
-          inb = (v & 0x3fffu) < hEnd;
-        }
-      }
-      hop64[r] = v;
-      hopW[r] = v;
-    }
-    __syncthreads();
-    for (uint32_t wide = 128; wide <= 1024; wide <<= 1) {
-      for (uint32_t r = tid; r < (uint32_t)kL1W; r += kL1Threads) {
-        const uint32_t v = hopW[r], e = v & 0x3fffu;
-        if (e < (uint32_t)kL1W && e / wide == r / wide)
-          hopW[r] = (v & ~0x3fffu) + hopW[e];
-      }
-      __syncthreads();
-    }
+    chain_hops<kL1W, kL1Threads>(bits, U1, hop64, hopW);
     // ---- the whole block, for each offset a chain can enter at
     if (tid <= kL1MaxTok) {
-      uint32_t r = tid, cnt = 0, sg = 0;
-      while (r < (uint32_t)kL1W) {
-        const uint32_t v = hopW[r];
-        cnt += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-      memoX[tid] = r - kL1W;
+      uint32_t cnt, sg;
+      memoX[tid] = chain_through<kL1W>(hopW, tid, cnt, sg);
       memoC[tid] = cnt;
       memoS[tid] = sg;
     }
     __syncthreads();
-    // ---- look back, publish: tag | done << 55 | exit offset << 47 | entries << 23 | significant
+    // ---- look back, publish: exit offset << 47 | entries << 23 | significant
     if (l1stamps)
       l1t1 = __builtin_readcyclecounter();
     if (tid == 0) {
-      uint32_t e = 0, rank = 0, sg = 0, stop = 0, last = 0;
-      if (i > 0) {
-        unsigned long long f = 0;
-        uint32_t spins = 0;
-        uint64_t spinT0 = 0;
-        for (;;) {
-          f = __hip_atomic_load(flags + (i - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((f >> 56) == (unsigned long long)(p + 1))
-            break;
-          // (the end-of-pass marker is looked at now and then: the poll stays one load long)
-          if ((++spins & 15u) == 0 &&
-              __hip_atomic_load(&s.l1PlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1) {
-            stop = 1;
-            break;
-          }
-          if (spin_expired(spins, spinT0)) {   // (a minute of wall time: the device has stopped making progress)
-            s.error = kErrLookBackTimeout;
-            __hip_atomic_store(&s.l1PlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            stop = 1;
-            break;
-          }
-        }
-        if (!stop) {
-          if ((f >> 55) & 1ull)
-            stop = 1;
-          else {
-            e = (uint32_t)(f >> 47) & 0xffu;
-            rank = (uint32_t)(f >> 23) & 0xffffffu;
-            sg = (uint32_t)f & 0x7fffffu;
-          }
-        }
-      }
-      if (!stop) {
-        if (rank + memoC[e] >= n) {   // the list ends inside this block
-          last = 1;
-          __hip_atomic_store(flags + i, tag | (1ull << 55), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&s.l1PlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        else
-          __hip_atomic_store(flags + i,
-                             tag | ((unsigned long long)memoX[e] << 47) |
-                                 ((unsigned long long)(rank + memoC[e]) << 23) |
-                                 (unsigned long long)(sg + memoS[e]),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      sh_e = e;
-      sh_rank = rank;
-      sh_sig = sg;
-      sh_last = last;
-      sh_stop = stop;
-      sh_endpos = 0;
-      sh_endsig = 0;
+      uint32_t e = 0, rank = 0, sg = 0;
+      const bool stop = i > 0 && lookback_wait<47, 23>(s, &s.l1PlaneP1, flags + (i - 1), p, e, rank, sg);
+      lookback_publish<47, 23>(cs, &s.l1PlaneP1, flags + i, p, n, stop, e, rank, sg, memoX[e], memoC[e], memoS[e]);
       if (l1stamps)
         l1t2 = __builtin_readcyclecounter();
     }
-    for (uint32_t k = tid; k < (uint32_t)(kL1W / 64); k += kL1Threads)
-      blkE[k] = kL0None;
-    if (tid < kL1W / 1024)
-      entR[tid] = kL0None;
+    chain_clear_entries<kL1W, kL1Threads>(cs);
     __syncthreads();
-    if (sh_stop)
+    if (cs.stop)
       break;
-    // ---- where the chain enters each 1024-block, then each sub-block
-    if (tid == 0) {
-      uint32_t r = sh_e, rk = 0, sg = 0;
-      while (r < (uint32_t)kL1W) {
-        entR[r >> 10] = r;
-        entK[r >> 10] = rk;
-        entS[r >> 10] = sg;
-        const uint32_t v = hopW[r];
-        rk += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-    }
-    __syncthreads();
-    if (tid < kL1W / 1024 && entR[tid] != kL0None) {
-      uint32_t r = entR[tid], rk = entK[tid], sg = entS[tid];
-      const uint32_t end = ((uint32_t)tid + 1) * 1024;
-      while (r < end) {
-        blkE[r >> 6] = r;
-        blkK[r >> 6] = rk;
-        blkS[r >> 6] = sg;
-        const uint32_t v = hop64[r];
-        rk += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-    }
-    __syncthreads();
+    chain_entries(cs, hop64, hopW);
     if (l1stamps)
       l1t3 = __builtin_readcyclecounter();
-    // ---- marks: (1 + entries before the token) | significant entries before it << 16, block-local
-    for (uint32_t r = tid; r < (uint32_t)kL1W; r += kL1Threads)
-      hopW[r] = 0;
-    __syncthreads();
-    const uint32_t rank0 = sh_rank, sig0 = sh_sig;
-    const uint32_t nloc = n - rank0;
-    if (tid < kL1W / 64 && blkE[tid] != kL0None) {
-      uint32_t r = blkE[tid], rk = blkK[tid], sg = blkS[tid];
-      const uint32_t end = ((uint32_t)tid + 1) * 64;
-      bool did = false;
-      while (r < end && rk < nloc) {
-        hopW[r] = (rk + 1u) | (sg << 16);
-        rk++;
-        sg += bit_at(r);
-        r += U1[r];
-        did = true;
-      }
-      if (did && rk == nloc) {
-        sh_endpos = r;
-        sh_endsig = sg;
-      }
-    }
+    const uint32_t sig0 = cs.sig;
+    chain_marks<kL1W, kL1Threads>(cs, bits, U1, hopW, n - cs.rank);
     __syncthreads();
     if (l1stamps)
       l1t4 = __builtin_readcyclecounter();
-    // ---- first sweep: insignificant entries stay, significant ones leave their list entry in their own words of
-    //      hop64 (a significant token is 16 bits and more) and queue up.  The list entries of a thread's positions are
-    //      loaded before any is used.
-    {
-      uint32_t mk4[kL1Per];
-      uint64_t id4[kL1Per];
-#pragma unroll
-      for (int j = 0; j < kL1Per; j++)
-        mk4[j] = hopW[(uint32_t)tid + (uint32_t)j * kL1Threads];
-#pragma unroll
-      for (int j = 0; j < kL1Per; j++)
-        id4[j] = mk4[j] ? list[rank0 + (mk4[j] & 0xffffu) - 1u] : 0ull;
-#pragma unroll
-      for (int j = 0; j < kL1Per; j++) {
-        const uint32_t r = (uint32_t)tid + (uint32_t)j * kL1Threads;
-        const uint32_t mk = mk4[j];
-        if (mk == 0)
-          continue;
-        const uint32_t q = rank0 + (mk & 0xffffu) - 1u, sb = sig0 + (mk >> 16);
-        const uint64_t ident = id4[j];
-        if (!bit_at(r)) {
-          keep[q - sb] = ident;
-          continue;
-        }
-        hop64[r + 1] = (uint32_t)ident;
-        hop64[r + 2] = (uint32_t)(ident >> 32);
-        tokQ[atomicAdd(&sh_ntok, 1u)] = (uint16_t)r;
-      }
-    }
+    chain_sweep_list<kL1W, kL1Threads, kL1W / 16>(cs, bits, list, keep, hop64, hopW, tokQ, &sh_ntok);
     __syncthreads();
     // ---- the significant tokens, one per thread (a token every 40 positions or so: found where they lie, six lanes of
     //      a wavefront walked eight children each while the others waited -- 20 of a block's 67 thousand cycles):
@@ -1741,25 +1391,7 @@ k_lis_l1(DecBuffers b, int p)
       const bool coded = (desc >> 23) & 1u;
       const Node nd = unpack_node((uint64_t)hop64[r + 1] | ((uint64_t)hop64[r + 2] << 32));
       const uint32_t cx = 2u * nd.i[0] + (k & 1u), cy = 2u * nd.i[1] + ((k >> 1) & 1u), cz = 2u * nd.i[2] + (k >> 2);
-      const Grid g1 = sh_grids[nd.grid + 1];   // the grid of the children
-      const uint32_t slotL = sh_baseL + i2;
-      const uint32_t v = bits32(coded ? y + 1 : y);
-      uint32_t yy = 0, fnd = 0, sigm = 0, negm = 0;
-#pragma unroll
-      for (int j = 0; j < 7; j++) {
-        const uint32_t bit = (v >> yy) & 1u, sgn = (v >> (yy + 1)) & 1u;
-        sigm |= bit << j;
-        negm |= (bit & (sgn ^ 1u)) << j;
-        fnd |= bit;
-        yy += 1u + bit;
-      }
-      const uint32_t bit = fnd ? (v >> yy) & 1u : 1u;
-      const uint32_t sgn = (v >> (yy + fnd)) & 1u;
-      sigm |= bit << 7;
-      negm |= (bit & (sgn ^ 1u)) << 7;
-      const uint32_t fid = g1.nodeOff + (((cz << g1.e[1]) + cy) << g1.e[0]) + cx;
-      if (slotL < b.leafCap)
-        leafEv[slotL] = (uint64_t)fid | ((uint64_t)sigm << 32) | ((uint64_t)negm << 40);
+      leaf_event(b, leafEv, sh_baseL + i2, bits, coded ? y + 1 : y, sh_grids[nd.grid + 1], cx, cy, cz);   // (the grid of the children)
     }
     if (l1stamps) {
       const uint64_t now_ = __builtin_readcyclecounter();
@@ -1772,10 +1404,10 @@ k_lis_l1(DecBuffers b, int p)
       atomicAdd(reinterpret_cast<unsigned long long*>(b.lisStamps + 62), l1t5 - l1t4);
       atomicAdd(reinterpret_cast<unsigned long long*>(b.lisStamps + 63), now_ - l1t5);
     }
-    if (sh_last) {
+    if (cs.last) {
       if (tid == 0) {
-        s.l1End = a + sh_endpos;
-        s.listLen[nx][L] = n - (sig0 + sh_endsig);
+        s.l1End = a + cs.endpos;
+        s.listLen[nx][L] = n - (sig0 + cs.endsig);
       }
       break;
     }
@@ -1784,19 +1416,18 @@ k_lis_l1(DecBuffers b, int p)
 }
 
 // ------------------------------------------------------------------------------------------
-// LIS phase, the third list: 8x8x8 sets (class 2) whose children are the 4x4x4 sets (round 6).  The scheme of
-// k_lis_l0 / k_lis_l1 with one more level inside a token: an entry is '0', or '1' followed by its eight
+// k_lis_l2, the third list: 8x8x8 sets (class 2) whose children are the 4x4x4 sets (round 6).  One more level again:
+// an entry is '0', or '1' followed by its eight
 // children, each '0' (a birth into the 4x4x4 sets' list) or '1' + ITS eight children, each '0' (a birth into
-// the list of the smallest sets) or '1' + eight pixels (a leaf event); the last child of a set none of whose
-// siblings was significant carries no test bit (src/SPECK3D_INT.cpp:140-212).  A token takes at most
+// the list of the smallest sets) or '1' + eight pixels (a leaf event).  A token takes at most
 // 1 + 7 * 137 + 137 = 1097 bits, so a block's class-1 tables cover 1024 positions more than the block and its
 // class-0 tables 128 more than those; a chain can enter a block at 1098 offsets, which is the size of its memo
-// table.  Until round 6 this list was k_lis_hi's: in the heavy planes most of that kernel's bits (2.5 Mbit per
+// table -- one packed word per offset: three arrays of 1098 do not fit.  Until round 6 this list was k_lis_hi's:
+// in the heavy planes most of that kernel's bits (2.5 Mbit per
 // 256^3 chunk in plane 14 of the bench volume), decoded through its general machinery -- regions handed from
 // workgroup to workgroup over a chain of 15 K cycles each, class tables for any chain of classes, breadth-first
 // expansion through global queues.  Here a block's hand-over is one look-back word, as in k_lis_l1.
-//   sweep 1   the tokens on the chain: insignificant entries stay, significant ones leave their list entry in
-//             their own words of hop64 (a significant token is 24 bits and more) and queue up;
+//   sweep 1   (chain_sweep_list) the tokens on the chain; a significant token is 24 bits and more;
 //   sweep T   a significant token per thread: its children -- births counted, significant ones queued;
 //   sweep C   a significant child per thread: its children -- births and leaf events counted;
 //   the block reserves its birth and leaf-event slots with one atomic each, and sweeps T and C run again to write
@@ -1807,7 +1438,6 @@ constexpr int kL2W = 4096;
 constexpr int kL2MaxTok = 1097;
 constexpr int kL2P1 = kL2W + 1024;              // positions with class-1 tables
 constexpr int kL2P0 = kL2P1 + 128;              // positions with class-0 tables
-constexpr int kL2Per = kL2W / kL2Threads;
 constexpr int kL2TokCap = 256;                  // significant tokens that START in a block: 24 bits each and more
 constexpr int kL2ChildCap = 512;                // their significant children: 16 bits each and more inside 4096 + 1097
 constexpr size_t kL2Smem = (size_t)(kL2P0 / 64 + 4) * 8 + (size_t)(kL2W + 4) * 4 + (size_t)kL2W * (4 + 2) +
@@ -1828,7 +1458,6 @@ k_lis_l2(DecBuffers b, int p, uint32_t minEntries)
     return;   // (k_lis_hi takes the list)
   extern __shared__ __attribute__((aligned(16))) char l2_smem[];
   uint64_t* wbits = reinterpret_cast<uint64_t*>(l2_smem);
-  const uint32_t* w32 = reinterpret_cast<const uint32_t*>(l2_smem);
   uint32_t* hop64 = reinterpret_cast<uint32_t*>(l2_smem + (size_t)(kL2P0 / 64 + 4) * 8);
   uint32_t* hopW = hop64 + kL2W + 4;     // later: the marks of the tokens on the chain, then the queues
   uint16_t* U2 = reinterpret_cast<uint16_t*>(hopW + kL2W);   // token length at every position of the block
@@ -1837,16 +1466,13 @@ k_lis_l2(DecBuffers b, int p, uint32_t minEntries)
   uint8_t* U0 = T1 + kL2P1;          // the same for class 0
   uint8_t* T0 = U0 + kL2P0;
   __shared__ uint32_t memo[kL2MaxTok + 1];   // exit offset << 21 | entries << 8 | significant entries, per entry offset
-  __shared__ uint32_t entR[kL2W / 1024], entK[kL2W / 1024], entS[kL2W / 1024];
-  __shared__ uint32_t blkE[kL2W / 64], blkK[kL2W / 64], blkS[kL2W / 64];
-  __shared__ uint32_t sh_ticket, sh_e, sh_rank, sh_sig, sh_last, sh_stop, sh_endpos, sh_endsig;
+  __shared__ ChainShared<kL2W> cs;
   __shared__ uint32_t sh_nb, sh_nl, sh_nc, sh_baseB, sh_baseL, sh_ntok;
   __shared__ uint16_t tokQ[kL2TokCap];
   __shared__ uint32_t tokSlot[kL2TokCap];    // first birth slot of a token's children (block-local)
   __shared__ Grid sh_grids[kTabLdsGrids];    // (the launcher checks that the tree's grids fit)
 
   const int tid = threadIdx.x;
-  const uint32_t lane = (uint32_t)tid & 63u, wave = (uint32_t)tid >> 6;
   const Tree& t = b.tree;
   for (uint32_t k = tid; k < t.ngrids; k += kL2Threads)
     sh_grids[k] = t.grids[k];
@@ -1860,7 +1486,6 @@ k_lis_l2(DecBuffers b, int p, uint32_t minEntries)
   uint64_t* bornPacked = b.bornPacked + c * b.bornPitch;
   uint64_t* bornPosLev = b.bornPosLev + c * b.bornPitch;
   unsigned long long* flags = b.l2Flags + c * b.l0FlagStride;
-  const unsigned long long tag = (unsigned long long)(p + 1) << 56;
   const uint64_t maskBits = (uint64_t)b.maskWords * 64;
   const uint32_t lev1 = b.levelClass[L].lev[1], lev0 = b.levelClass[L].lev[0];
   const uint32_t slot1 = b.levelSlot[lev1], slot0 = b.levelSlot[lev0];
@@ -1869,261 +1494,58 @@ k_lis_l2(DecBuffers b, int p, uint32_t minEntries)
 
   for (;;) {
     if (tid == 0) {
-      const bool over = __hip_atomic_load(&s.l2PlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1;
-      sh_ticket = over ? kL0None : atomicAdd(&s.l2Ticket, 1u);
       sh_nb = 0;
       sh_nl = 0;
       sh_nc = 0;
       sh_ntok = 0;
     }
-    __syncthreads();
-    const uint32_t i = sh_ticket;
-    if (i == kL0None || (size_t)i + 1 >= b.l0FlagStride)
+    const uint32_t i = chain_ticket(cs, &s.l2PlaneP1, &s.l2Ticket, p, b.l0FlagStride);
+    if (i == kL0None)
       break;
     const uint64_t a = start0 + (uint64_t)i * kL2W;
-    const uint64_t w0 = a >> 6;
-    const uint32_t q0 = (uint32_t)(a & 63);
-    for (uint32_t k = tid; k < (uint32_t)(kL2P0 / 64 + 4); k += kL2Threads)
-      wbits[k] = w0 + k < nwordsAvail ? words[w0 + k] : 0ull;
-    __syncthreads();
-    auto bit_at = [&](uint32_t r) -> uint32_t {
-      const uint32_t q = r + q0;
-      return (w32[q >> 5] >> (q & 31)) & 1u;
-    };
-    auto bits32 = [&](uint32_t r) -> uint32_t {
-      const uint32_t q = r + q0, sh = q & 31;
-      const uint32_t lo = w32[q >> 5], hi = w32[(q >> 5) + 1];
-      return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-    };
+    const LdsBits bits = chain_load_words<kL2P0 / 64 + 4, kL2Threads>(wbits, words, a, nwordsAvail);
     // ---- class 0: split length, then the coded item
-    for (uint32_t r = tid; r < (uint32_t)kL2P0; r += kL2Threads) {
-      const uint32_t v = bits32(r);
-      uint32_t y = 0, found = 0;
-#pragma unroll
-      for (int k = 0; k < 7; k++) {
-        const uint32_t bit = (v >> y) & 1u;
-        found |= bit;
-        y += 1u + bit;
-      }
-      const uint32_t bit = found ? (v >> y) & 1u : 1u;
-      T0[r] = (uint8_t)(y + found + bit);
-    }
+    for (uint32_t r = tid; r < (uint32_t)kL2P0; r += kL2Threads)
+      T0[r] = (uint8_t)split8_len(bits.bits32(r));
     __syncthreads();
     for (uint32_t r = tid; r < (uint32_t)kL2P0; r += kL2Threads)
-      U0[r] = (uint8_t)((bit_at(r) && r + 1 < (uint32_t)kL2P0) ? 1u + T0[r + 1] : 1u);
+      U0[r] = (uint8_t)((bits.bit_at(r) && r + 1 < (uint32_t)kL2P0) ? 1u + T0[r + 1] : 1u);
     __syncthreads();
     // ---- class 1
-    for (uint32_t r = tid; r < (uint32_t)kL2P1; r += kL2Threads) {
-      uint32_t y = r, found = 0;
-#pragma unroll
-      for (int k = 0; k < 7; k++) {
-        const uint32_t u = U0[y];
-        found |= u - 1u;
-        y += u;
-      }
-      y += found ? U0[y] : T0[y];
-      T1[r] = (uint8_t)(y - r);
-    }
+    for (uint32_t r = tid; r < (uint32_t)kL2P1; r += kL2Threads)
+      T1[r] = (uint8_t)parent_split_len(U0, T0, r);
     __syncthreads();
     for (uint32_t r = tid; r < (uint32_t)kL2P1; r += kL2Threads)
-      U1[r] = (uint8_t)((bit_at(r) && r + 1 < (uint32_t)kL2P1) ? 1u + T1[r + 1] : 1u);
+      U1[r] = (uint8_t)((bits.bit_at(r) && r + 1 < (uint32_t)kL2P1) ? 1u + T1[r + 1] : 1u);
     __syncthreads();
     // ---- class 2: the token at every position of the block
-    for (uint32_t r = tid; r < (uint32_t)kL2W; r += kL2Threads) {
-      uint32_t len = 1;
-      if (bit_at(r)) {
-        uint32_t y = r + 1, found = 0;
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-          const uint32_t u = U1[y];
-          found |= u - 1u;
-          y += u;
-        }
-        y += found ? U1[y] : T1[y];
-        len = y - r;
-      }
-      U2[r] = (uint16_t)len;
-    }
+    for (uint32_t r = tid; r < (uint32_t)kL2W; r += kL2Threads)
+      U2[r] = (uint16_t)(bits.bit_at(r) ? 1u + parent_split_len(U1, T1, r + 1) : 1u);
     __syncthreads();
-    // ---- chains inside 64-position sub-blocks (lane = position)
-    for (uint32_t sb = wave; sb < (uint32_t)(kL2W / 64); sb += kL2Threads / 64) {
-      const uint32_t r = sb * 64 + lane, hEnd = (sb + 1) * 64;
-      uint32_t v = (1u << 21) | (bit_at(r) << 14) | (r + U2[r]);
-      bool inb = (v & 0x3fffu) < hEnd;
-      for (int it = 0; it < 6 && __any(inb); it++) {
-        const uint32_t o = __shfl(v, (v & 0x3fffu) & 63u, 64);
-        if (inb) {
-          v = (v & ~0x3fffu) + o;
-          inb = (v & 0x3fffu) < hEnd;
-        }
-      }
-      hop64[r] = v;
-      hopW[r] = v;
-    }
-    __syncthreads();
-    for (uint32_t wide = 128; wide <= 1024; wide <<= 1) {
-      for (uint32_t r = tid; r < (uint32_t)kL2W; r += kL2Threads) {
-        const uint32_t v = hopW[r], e = v & 0x3fffu;
-        if (e < (uint32_t)kL2W && e / wide == r / wide)
-          hopW[r] = (v & ~0x3fffu) + hopW[e];
-      }
-      __syncthreads();
-    }
+    chain_hops<kL2W, kL2Threads>(bits, U2, hop64, hopW);
     // ---- the whole block, for each offset a chain can enter at
     for (uint32_t e0 = tid; e0 <= (uint32_t)kL2MaxTok; e0 += kL2Threads) {
-      uint32_t r = e0, cnt = 0, sg = 0;
-      while (r < (uint32_t)kL2W) {
-        const uint32_t v = hopW[r];
-        cnt += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-      memo[e0] = ((r - kL2W) << 21) | (cnt << 8) | sg;   // (exit offset <= 1097, entries <= 4096, significant <= 171)
+      uint32_t cnt, sg;
+      const uint32_t x = chain_through<kL2W>(hopW, e0, cnt, sg);
+      memo[e0] = (x << 21) | (cnt << 8) | sg;   // (exit offset <= 1097, entries <= 4096, significant <= 171)
     }
     __syncthreads();
-    // ---- look back, publish: tag | done << 55 | exit offset << 44 | entries << 22 | significant
+    // ---- look back, publish: exit offset << 44 | entries << 22 | significant
     if (tid == 0) {
-      uint32_t e = 0, rank = 0, sg = 0, stop = 0, last = 0;
-      if (i > 0) {
-        unsigned long long f = 0;
-        uint32_t spins = 0;
-        uint64_t spinT0 = 0;
-        for (;;) {
-          f = __hip_atomic_load(flags + (i - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((f >> 56) == (unsigned long long)(p + 1))
-            break;
-          // (the end-of-pass marker is looked at now and then: the poll stays one load long)
-          if ((++spins & 15u) == 0 &&
-              __hip_atomic_load(&s.l2PlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1) {
-            stop = 1;
-            break;
-          }
-          if (spin_expired(spins, spinT0)) {   // (a minute of wall time: the device has stopped making progress)
-            s.error = kErrLookBackTimeout;
-            __hip_atomic_store(&s.l2PlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            stop = 1;
-            break;
-          }
-        }
-        if (!stop) {
-          if ((f >> 55) & 1ull)
-            stop = 1;
-          else {
-            e = (uint32_t)(f >> 44) & 0x7ffu;
-            rank = (uint32_t)(f >> 22) & 0x3fffffu;
-            sg = (uint32_t)f & 0x3fffffu;
-          }
-        }
-      }
-      if (!stop) {
-        const uint32_t m = memo[e], mc = (m >> 8) & 0x1fffu;
-        if (rank + mc >= n) {   // the list ends inside this block
-          last = 1;
-          __hip_atomic_store(flags + i, tag | (1ull << 55), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&s.l2PlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        else
-          __hip_atomic_store(flags + i,
-                             tag | ((unsigned long long)(m >> 21) << 44) |
-                                 ((unsigned long long)(rank + mc) << 22) |
-                                 (unsigned long long)(sg + (m & 0xffu)),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      sh_e = e;
-      sh_rank = rank;
-      sh_sig = sg;
-      sh_last = last;
-      sh_stop = stop;
-      sh_endpos = 0;
-      sh_endsig = 0;
+      uint32_t e = 0, rank = 0, sg = 0;
+      const bool stop = i > 0 && lookback_wait<44, 22>(s, &s.l2PlaneP1, flags + (i - 1), p, e, rank, sg);
+      const uint32_t m = memo[e];
+      lookback_publish<44, 22>(cs, &s.l2PlaneP1, flags + i, p, n, stop, e, rank, sg, m >> 21, (m >> 8) & 0x1fffu, m & 0xffu);
     }
-    for (uint32_t k = tid; k < (uint32_t)(kL2W / 64); k += kL2Threads)
-      blkE[k] = kL0None;
-    if (tid < kL2W / 1024)
-      entR[tid] = kL0None;
+    chain_clear_entries<kL2W, kL2Threads>(cs);
     __syncthreads();
-    if (sh_stop)
+    if (cs.stop)
       break;
-    // ---- where the chain enters each 1024-block, then each sub-block
-    if (tid == 0) {
-      uint32_t r = sh_e, rk = 0, sg = 0;
-      while (r < (uint32_t)kL2W) {
-        entR[r >> 10] = r;
-        entK[r >> 10] = rk;
-        entS[r >> 10] = sg;
-        const uint32_t v = hopW[r];
-        rk += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-    }
+    chain_entries(cs, hop64, hopW);
+    const uint32_t sig0 = cs.sig;
+    chain_marks<kL2W, kL2Threads>(cs, bits, U2, hopW, n - cs.rank);
     __syncthreads();
-    if (tid < kL2W / 1024 && entR[tid] != kL0None) {
-      uint32_t r = entR[tid], rk = entK[tid], sg = entS[tid];
-      const uint32_t end = ((uint32_t)tid + 1) * 1024;
-      while (r < end) {
-        blkE[r >> 6] = r;
-        blkK[r >> 6] = rk;
-        blkS[r >> 6] = sg;
-        const uint32_t v = hop64[r];
-        rk += v >> 21;
-        sg += (v >> 14) & 0x7fu;
-        r = v & 0x3fffu;
-      }
-    }
-    __syncthreads();
-    // ---- marks: (1 + entries before the token) | significant entries before it << 16, block-local
-    for (uint32_t r = tid; r < (uint32_t)kL2W; r += kL2Threads)
-      hopW[r] = 0;
-    __syncthreads();
-    const uint32_t rank0 = sh_rank, sig0 = sh_sig;
-    const uint32_t nloc = n - rank0;
-    if (tid < kL2W / 64 && blkE[tid] != kL0None) {
-      uint32_t r = blkE[tid], rk = blkK[tid], sg = blkS[tid];
-      const uint32_t end = ((uint32_t)tid + 1) * 64;
-      bool did = false;
-      while (r < end && rk < nloc) {
-        hopW[r] = (rk + 1u) | (sg << 16);
-        rk++;
-        sg += bit_at(r);
-        r += U2[r];
-        did = true;
-      }
-      if (did && rk == nloc) {
-        sh_endpos = r;
-        sh_endsig = sg;
-      }
-    }
-    __syncthreads();
-    // ---- sweep 1: insignificant entries stay, significant ones leave their list entry in hop64 and queue up
-    {
-      uint32_t mk4[kL2Per];
-      uint64_t id4[kL2Per];
-#pragma unroll
-      for (int j = 0; j < kL2Per; j++)
-        mk4[j] = hopW[(uint32_t)tid + (uint32_t)j * kL2Threads];
-#pragma unroll
-      for (int j = 0; j < kL2Per; j++)
-        id4[j] = mk4[j] ? list[rank0 + (mk4[j] & 0xffffu) - 1u] : 0ull;
-#pragma unroll
-      for (int j = 0; j < kL2Per; j++) {
-        const uint32_t r = (uint32_t)tid + (uint32_t)j * kL2Threads;
-        const uint32_t mk = mk4[j];
-        if (mk == 0)
-          continue;
-        const uint32_t q = rank0 + (mk & 0xffffu) - 1u, sb = sig0 + (mk >> 16);
-        const uint64_t ident = id4[j];
-        if (!bit_at(r)) {
-          keep[q - sb] = ident;
-          continue;
-        }
-        hop64[r + 1] = (uint32_t)ident;
-        hop64[r + 2] = (uint32_t)(ident >> 32);
-        const uint32_t ti = atomicAdd(&sh_ntok, 1u);
-        if (ti < (uint32_t)kL2TokCap)
-          tokQ[ti] = (uint16_t)r;
-      }
-    }
+    chain_sweep_list<kL2W, kL2Threads, kL2TokCap>(cs, bits, list, keep, hop64, hopW, tokQ, &sh_ntok);
     __syncthreads();
     // ---- sweeps T and C, twice: first counting (write == 0), then -- the block's slots reserved -- writing.
     //      QC (the marks' array: they are dead now): a significant child as
@@ -2234,24 +1656,7 @@ k_lis_l2(DecBuffers b, int p, uint32_t minEntries)
           }
           else if ((kinds >> j) & 1u) {   // splits into its pixels: a leaf event
             const bool coded = (offs[j] >> 8) & 1u;
-            const uint32_t v = bits32(coded ? yy0 + 1 : yy0);
-            uint32_t yy = 0, fnd = 0, sigm = 0, negm = 0;
-#pragma unroll
-            for (int q = 0; q < 7; q++) {
-              const uint32_t bit = (v >> yy) & 1u, sgn = (v >> (yy + 1)) & 1u;
-              sigm |= bit << q;
-              negm |= (bit & (sgn ^ 1u)) << q;
-              fnd |= bit;
-              yy += 1u + bit;
-            }
-            const uint32_t bit = fnd ? (v >> yy) & 1u : 1u;
-            const uint32_t sgn = (v >> (yy + fnd)) & 1u;
-            sigm |= bit << 7;
-            negm |= (bit & (sgn ^ 1u)) << 7;
-            const uint32_t fid = g2.nodeOff + (((cz << g2.e[1]) + cy) << g2.e[0]) + cx;
-            if (slotL < b.leafCap)
-              leafEv[slotL] = (uint64_t)fid | ((uint64_t)sigm << 32) | ((uint64_t)negm << 40);
-            slotL++;
+            leaf_event(b, leafEv, slotL++, bits, coded ? yy0 + 1 : yy0, g2, cx, cy, cz);
           }
         }
       }
@@ -2266,10 +1671,10 @@ k_lis_l2(DecBuffers b, int p, uint32_t minEntries)
     }
     if (sh_ntok > (uint32_t)kL2TokCap || sh_nc > (uint32_t)kL2ChildCap)   // (cannot be: see the constants)
       s.error = 1;
-    if (sh_last) {
+    if (cs.last) {
       if (tid == 0) {
-        s.l2End = a + sh_endpos;
-        s.listLen[nx][L] = n - (sig0 + sh_endsig);
+        s.l2End = a + cs.endpos;
+        s.listLen[nx][L] = n - (sig0 + cs.endsig);
       }
       break;
     }
@@ -2513,16 +1918,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
     return -1;
   };
 
-  uint32_t wq0 = 0;
-  auto bit_at = [&](uint32_t r) -> uint32_t {
-    const uint32_t q = r + wq0;
-    return (w32[q >> 5] >> (q & 31)) & 1u;
-  };
-  auto bits32 = [&](uint32_t r) -> uint32_t {
-    const uint32_t q = r + wq0, sh = q & 31;
-    const uint32_t lo = w32[q >> 5], hi = w32[(q >> 5) + 1];
-    return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-  };
+  LdsBits bits{w32, 0};   // (q0: bit offset of region position 0 inside wbits[0])
   uint64_t a = 0;   // absolute bit of window position 0
 
   // ---- tables of classes [j0, j1) of level `lv`'s chain (see the section comment above)
@@ -2533,18 +1929,10 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
       // it is known wherever it starts (r <= W), so the chain never has to walk into one
       if (r > W)
         return kTInf;
-      const uint32_t v = bits32(r);
+      const uint32_t v = bits.bits32(r);
       uint32_t y = 0, found = 0;
-      if (ar == 8) {
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-          const uint32_t bit = (v >> y) & 1u;
-          found |= bit;
-          y += 1u + bit;
-        }
-        const uint32_t bit = found ? (v >> y) & 1u : 1u;
-        y += found + bit;
-      }
+      if (ar == 8)
+        y = split8_len(v);
       else {
         for (int i = 0; i < ar; i++) {
           const uint32_t coded = found | (uint32_t)(i + 1 != ar);
@@ -2618,7 +2006,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
         const uint32_t r = r0 + lane;
         bool is = false;
         if (r < npos)
-          is = r <= zn || r >= W || bit_at(r - 1) != 0 || (bits32(r - zn) & zmask) == 0;
+          is = r <= zn || r >= W || bits.bit_at(r - 1) != 0 || (bits.bits32(r - zn) & zmask) == 0;
         const uint64_t m = __ballot(is);
         if (is)
           cand[wv * slice + ncand + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)r;
@@ -2627,7 +2015,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
       // every entry of every class once, two positions a store: T "leaves the window", U 1 behind a '0'
       for (uint32_t h = (uint32_t)tid; 2 * h < npos; h += kTabThreads) {
         const uint32_t r = 2 * h;
-        const uint32_t u0 = (r >= W || bit_at(r)) ? kTInf : 1u, u1 = (r + 1 >= W || bit_at(r + 1)) ? kTInf : 1u;
+        const uint32_t u0 = (r >= W || bits.bit_at(r)) ? kTInf : 1u, u1 = (r + 1 >= W || bits.bit_at(r + 1)) ? kTInf : 1u;
         const uint32_t u = u0 | (u1 << 16);
         for (int j = j0; j < j1; j++) {
           reinterpret_cast<uint32_t*>(Uu + (size_t)j * TS)[h] = u;
@@ -2654,7 +2042,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
               continue;
             if (Tj)
               Tj[r] = (uint16_t)tl[q];
-            if (r >= 1 && r - 1 < W && bit_at(r - 1))
+            if (r >= 1 && r - 1 < W && bits.bit_at(r - 1))
               Uj[r - 1] = (uint16_t)(tl[q] == kTInf ? kTInf : (0x8000u | (1u + tl[q])));
           }
         }
@@ -2668,7 +2056,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
       auto coded = [&](uint32_t q, uint32_t tl) -> uint16_t {   // U_j[q] given T_j[q + 1]
         if (q >= W)
           return (uint16_t)kTInf;
-        if (!bit_at(q))
+        if (!bits.bit_at(q))
           return (uint16_t)1;
         return (uint16_t)(tl == kTInf ? kTInf : (0x8000u | (1u + tl)));
       };
@@ -2697,12 +2085,12 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
     }
   };
   // all threads; pointer-jump table over the coded items of class `top`, from every position:
-  // hop[h] for h = r + wq0 (64-bit blocks are stream words): cnt << 16 | stop << 15 | exit
+  // hop[h] for h = r + bits.q0 (64-bit blocks are stream words): cnt << 16 | stop << 15 | exit
   auto build_hop = [&](uint32_t* hop, int top, uint32_t from = 0) {
     const uint16_t* Utop = Uu + (size_t)top * TS;
-    const uint32_t nblk = ((SR - 1 + wq0) >> 6) + 1;
-    const uint32_t blk0 = (min(from, SR - 1) + wq0) >> 6;   // the block position `from` lies in
-    const int32_t rbase = -(int32_t)wq0;
+    const uint32_t nblk = ((SR - 1 + bits.q0) >> 6) + 1;
+    const uint32_t blk0 = (min(from, SR - 1) + bits.q0) >> 6;   // the block position `from` lies in
+    const int32_t rbase = -(int32_t)bits.q0;
     const uint32_t wave = (uint32_t)tid >> 6;
     for (uint32_t bi = blk0 + wave; bi < nblk; bi += kTabThreads / 64) {
       const uint32_t h = bi * 64 + lane;
@@ -2848,22 +2236,10 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
         const bool isLeaf = have && cls == 0;
         uint32_t sigm = 0, negm = 0;
         if (isLeaf) {
-          const uint32_t v = bits32(y0);
+          const uint32_t v = bits.bits32(y0);
           uint32_t yy = 0, found = 0;
-          if (ar == 8) {
-#pragma unroll
-            for (int k = 0; k < 7; k++) {
-              const uint32_t bit = (v >> yy) & 1u, sgn = (v >> (yy + 1)) & 1u;
-              sigm |= bit << k;
-              negm |= (bit & (sgn ^ 1u)) << k;
-              found |= bit;
-              yy += 1u + bit;
-            }
-            const uint32_t bit = found ? (v >> yy) & 1u : 1u;
-            const uint32_t sgn = (v >> (yy + found)) & 1u;
-            sigm |= bit << 7;
-            negm |= (bit & (sgn ^ 1u)) << 7;
-          }
+          if (ar == 8)
+            split8_pixels(v, sigm, negm);
           else {
             for (int k = 0; k < ar; k++) {
               const uint32_t coded = found | (uint32_t)(k + 1 != ar);
@@ -2982,7 +2358,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
       W = SR + b.hiAhead;
       a = S0 + off;
     }
-    wq0 = (uint32_t)(a & 63);
+    bits.q0 = (uint32_t)(a & 63);
     {
       const uint64_t w0 = a >> 6;
       uint64_t any = 0;
@@ -3269,8 +2645,8 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
         uint32_t pendK = 0, pendRemaining = 0, pendE0 = 0, pendLOff = 0;
         auto emit_entries = [&](const uint32_t* hp, uint32_t K, uint32_t remaining, uint32_t e0, uint32_t lOff) {
           const uint16_t* Utop = Uu + (size_t)(K - 1) * TS;
-          const uint32_t nblk = ((SR - 1 + wq0) >> 6) + 1;
-          const int32_t rbase = -(int32_t)wq0;
+          const uint32_t nblk = ((SR - 1 + bits.q0) >> 6) + 1;
+          const int32_t rbase = -(int32_t)bits.q0;
           for (uint32_t kb = lane; kb < nblk; kb += 64) {  // P3: the blocks emit their entries
             const uint32_t eb = blkEB[kb];
             if (eb == 0xffffffffu)
@@ -3436,7 +2812,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
                 if (coded) {
                   // (children of a class without a table: their test bit decides, a significant one
                   //  is entered)
-                  const uint32_t u = cls < Kcap ? (uint32_t)Uu[(size_t)cls * TS + y] : (bit_at(y) ? (uint32_t)kTInf : 1u);
+                  const uint32_t u = cls < Kcap ? (uint32_t)Uu[(size_t)cls * TS + y] : (bits.bit_at(y) ? (uint32_t)kTInf : 1u);
                   if (u == 1) {
                     kind = 1;
                     at = y;
@@ -3517,7 +2893,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
               const uint32_t lOff = sh_lOff[clevel];
               while (rem > 0 && r < SR) {
                 const uint32_t lim = min(rem, SR - r);
-                const uint32_t v = bits32(r);
+                const uint32_t v = bits.bits32(r);
                 const uint32_t z = v ? (uint32_t)__ffs((int)v) - 1u : 32u;
                 if (z >= lim) {
                   e += lim;
@@ -3610,8 +2986,8 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
           const uint32_t pr = (uint32_t)(cpos - a);
           const uint32_t remaining = crem, e0 = ce;
           const uint32_t lOff = sh_lOff[clevel];
-          const uint32_t nblk = ((SR - 1 + wq0) >> 6) + 1;
-          const int32_t rbase = -(int32_t)wq0;
+          const uint32_t nblk = ((SR - 1 + bits.q0) >> 6) + 1;
+          const int32_t rbase = -(int32_t)bits.q0;
           for (uint32_t k = lane; k < nblk; k += 64)
             blkEB[k] = 0xffffffffu;
           HI_WAVE_SYNC();

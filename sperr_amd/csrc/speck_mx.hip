@@ -29,6 +29,7 @@
 // Old entries are compacted by k_lis_compact, which also sets the chunk's state after the phase.
 // tests/model/speck_model.cpp::model_speck3d_decode_mixed pins the formulation (rows, hops, walking into sets).
 #include "speck_dec.h"
+#include "lis_token.h"
 
 namespace sperrhip {
 
@@ -176,18 +177,9 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
   uint16_t* const ecls = reinterpret_cast<uint16_t*>(qmetaB + Q);   // ring [kMxRing]: class | column in the list's group << 8
   uint16_t* const cand = reinterpret_cast<uint16_t*>(qidB);         // [W] (the rows are built before anything is queued)
   uint64_t a = 0;     // stream position of the region's bit 0
-  uint32_t wq0 = 0;   // bit offset of region position 0 inside wbits[0]
+  LdsBits bits{w32, 0};   // (q0: bit offset of region position 0 inside wbits[0])
   __syncthreads();
 
-  auto bit_at = [&](uint32_t r) -> uint32_t {
-    const uint32_t q = r + wq0;
-    return (w32[q >> 5] >> (q & 31)) & 1u;
-  };
-  auto bits32 = [&](uint32_t r) -> uint32_t {  // 32 stream bits starting at r
-    const uint32_t q = r + wq0, sh = q & 31;
-    const uint32_t lo = w32[q >> 5], hi = w32[(q >> 5) + 1];
-    return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-  };
   auto pixel_event = [&](uint32_t ridx, bool sig, uint32_t signbit) {
     atomicOr(bornM + (ridx >> 6), 1ull << (ridx & 63));
     if (sig) {
@@ -277,7 +269,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
   // a significant leaf parent of nk samples whose split starts at y: ONE event word (node id,
   // significance and sign masks by child ordinal) that k_leaf_apply turns into mask updates
   auto leaf_event = [&](const Node& nd, uint32_t y, uint32_t nk) {
-    const uint32_t v = bits32(y);
+    const uint32_t v = bits.bits32(y);
     uint32_t yy = 0, found = 0, sigm = 0, negm = 0;
     for (uint32_t k = 0; k < nk; k++) {
       const uint32_t coded = found | (uint32_t)(k + 1 != nk);
@@ -314,28 +306,9 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
       uint32_t T0 = kTInf, T1 = kTInf, T2 = kTInf, T3 = kTInf, rest = 0xffffffffu;
       bool isCand = false;
       if (x < W) {
-        const uint32_t v = bits32(x);
-        // children 0..6 coded one after the other; the last child of 2 / 4 / 8 is coded only when
-        // an earlier one was significant
-        uint32_t y = 0, found = 0, t2 = 0, t4 = 0, t8 = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-          if (k == 1 || k == 3 || k == 7) {
-            const uint32_t bit = found ? (v >> y) & 1u : 1u;
-            const uint32_t tl = y + found + bit;
-            if (k == 1)
-              t2 = tl;
-            else if (k == 3)
-              t4 = tl;
-            else
-              t8 = tl;
-          }
-          if (k < 7) {
-            const uint32_t bit = (v >> y) & 1u;
-            found |= bit;
-            y += 1u + bit;
-          }
-        }
+        const uint32_t v = bits.bits32(x);
+        // (the last child of 2 / 4 / 8 is coded only when an earlier one was significant)
+        const uint32_t t2 = pixel_split_len<2>(v), t4 = pixel_split_len<4>(v), t8 = split8_len(v);
         T0 = 1u;
         T1 = x + t2 <= W ? t2 : kTInf;
         T2 = x + t4 <= W ? t4 : kTInf;
@@ -343,7 +316,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         rest = kTNone | (kTNone << 16);
         // (a region may begin anywhere: position 0 can be the start of a split whose test bit the
         //  region before holds)
-        isCand = x == 0 || bit_at(x - 1) != 0;
+        isCand = x == 0 || bits.bit_at(x - 1) != 0;
       }
       uint4* row = reinterpret_cast<uint4*>(Tr + (size_t)x * kMxCols);
       row[0] = make_uint4(T0 | (T1 << 16), T2 | (T3 << 16), rest, rest);
@@ -387,7 +360,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
             const uint32_t ccol = (uint32_t)(kc >> (8 * k)) & 0xffu;
             const uint32_t coded = found | (uint32_t)(k + 1 != nk);
             const uint32_t yy = min(y, W + 1);
-            const uint32_t bitv = coded ? bit_at(yy) : 1u;
+            const uint32_t bitv = coded ? bits.bit_at(yy) : 1u;
             const uint32_t s0 = yy + coded;
             uint32_t t = row_at(s0, ccol);
             if (t >= kTNone) {
@@ -464,7 +437,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
     }
     return y > W ? kTInf : y - x;
   };
-  auto chain_len = [&](uint32_t ci, uint32_t x) -> uint32_t { return chain_len_with(bit_at, ci, x); };
+  auto chain_len = [&](uint32_t ci, uint32_t x) -> uint32_t { return chain_len_with([&](uint32_t r) { return bits.bit_at(r); }, ci, x); };
 
   // ---- the walk through the region (first wavefront, every lane carrying the same walker state): from
   //      sh_pos on until an item starts at or past S, or the list ends (depth 0)
@@ -506,7 +479,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
       return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x06040200u) + 0x01010101u;
     };
     auto load_lrow = [&](uint32_t kk) {
-      const int32_t row = (int32_t)(kk * 64u + lane) - (int32_t)wq0 + 1;
+      const int32_t row = (int32_t)(kk * 64u + lane) - (int32_t)bits.q0 + 1;
       uint64_t va = ~0ull, vb = ~0ull;
       if (row >= 0 && row <= (int32_t)W + 2) {
         va = *reinterpret_cast<const uint64_t*>(Tr + (size_t)row * kMxCols + ga * 4u);
@@ -531,9 +504,9 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
     };
     // last stream word the tight loop takes: the one the region's last bit lies in, ALL of it -- the walk may leave a
     // region up to 63 bits late (a long split does that anyway; rows 1 .. S + 128 exist, entry classes to e + S + 128)
-    const uint32_t kkLast = (S + wq0 - 1u) >> 6;
+    const uint32_t kkLast = (S + bits.q0 - 1u) >> 6;
     // LDS address of lane's row entries for word 0 (+ word << 11: 64 rows of 32 bytes), then of the list's two column groups
-    const uint32_t adBase = (uint32_t)(size_t)Tr + (uint32_t)((int32_t)(lane + 1u) - (int32_t)wq0) * (uint32_t)(kMxCols * 2);
+    const uint32_t adBase = (uint32_t)(size_t)Tr + (uint32_t)((int32_t)(lane + 1u) - (int32_t)bits.q0) * (uint32_t)(kMxCols * 2);
     const uint32_t adBaseA = adBase + ga * 8u, adBaseB = adBase + gb * 8u;
     auto rl32 = [&](uint32_t v, uint32_t idx) -> uint32_t {
       return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)idx);
@@ -544,7 +517,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
     // (a stream bit out of the words in the lane registers: two v_readlane instead of an LDS round trip -- the walk
     //  into a set and the lengths worked out on the chain read a bit per child)
     auto bit_w = [&](uint32_t rr) -> uint32_t {
-      const uint32_t q = rr + wq0;
+      const uint32_t q = rr + bits.q0;
       return (uint32_t)(rl64(sw0, (q >> 6) & 63u) >> (q & 63u)) & 1u;
     };
     auto chain_len_w = [&](uint32_t ci, uint32_t x) -> uint32_t { return chain_len_with(bit_w, ci, x); };
@@ -566,7 +539,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
           depth = 0;
           break;
         }
-        const uint32_t q = r + wq0, k = q >> 6, o = q & 63u;
+        const uint32_t q = r + bits.q0, k = q >> 6, o = q & 63u;
         if (k != curK) {
           curK = k;
           m = rl64(sw0, k & 63u);
@@ -784,7 +757,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
 #undef MX_HOP
 #undef MX_HOP_TEST
 #undef MX_HOP_END
-          r = kk * 64u + oo - wq0;
+          r = kk * 64u + oo - bits.q0;
           rem = eEnd - e;
           if (kStamps)
             wk_tight += __builtin_readcyclecounter() - tt0;
@@ -797,7 +770,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
             m = rl64(sw0, kk);
           curK = kk;   // (an unusual entry lies in the word just walked: m and lrow are that word's)
         }
-        const uint32_t q2 = r + wq0, o2 = q2 & 63u;   // (same word: the tight loop stops inside it)
+        const uint32_t q2 = r + bits.q0, o2 = q2 & 63u;   // (same word: the tight loop stops inside it)
         const uint64_t tt = m >> o2;
         const uint32_t z = min(min(tt ? (uint32_t)__ffsll((long long)tt) - 1u : 64u - o2, rem), S - r);
         if (z) {
@@ -1055,7 +1028,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         uint64_t cm = sh_recM[ri][0], im = sh_recM[ri][1];
         uint32_t slot = atomicAdd(&sh_qn[0], (uint32_t)__popcll(cm));
         // (the ordinal mask's bits are ordinals mod 64: turned so that bit 0 is the word's first ordinal)
-        const uint32_t e0 = sh_recE[ri], rk = sh_recK[ri], pb = (rk & 0xffu) * 64u + 1u - wq0, r6 = (rk >> 8) & 63u;
+        const uint32_t e0 = sh_recE[ri], rk = sh_recK[ri], pb = (rk & 0xffu) * 64u + 1u - bits.q0, r6 = (rk >> 8) & 63u;
         im = r6 ? (im >> r6) | (im << (64u - r6)) : im;
         while (cm && im) {
           const uint32_t pbit = (uint32_t)__builtin_ctzll(cm), ebit = (uint32_t)__builtin_ctzll(im);
@@ -1109,10 +1082,10 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         for (uint32_t k = 0; k < nk; k++) {
           const uint32_t coded = found | (uint32_t)(k + 1 != nk);
           const uint32_t col = (uint32_t)(kc >> (8 * k)) & 0xffu;
-          const uint32_t bit = coded ? bit_at(y) : 1u;
+          const uint32_t bit = coded ? bits.bit_at(y) : 1u;
           const uint32_t start = y + coded;
           if (col == 0) {   // a single sample: its sign follows
-            pixel_event(kid_pixel_raster(b.tree, nd, kb, k), bit != 0, bit ? bit_at(start) : 1u);
+            pixel_event(kid_pixel_raster(b.tree, nd, kb, k), bit != 0, bit ? bits.bit_at(start) : 1u);
             found |= bit;
             y = start + bit;
             continue;
@@ -1211,7 +1184,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
     if (((size_t)i + 1) * kMxWordsPerRegion > b.hiFlagStride)
       break;
     a = phase0 + (uint64_t)i * S;
-    wq0 = (uint32_t)(a & 63);
+    bits.q0 = (uint32_t)(a & 63);
     {
       const uint64_t w0 = a >> 6;
       for (uint32_t k = tid; k < kWords; k += kMxThreads) {
@@ -1539,7 +1512,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
           else {
             uint32_t bit = 1;
             if (__builtin_amdgcn_readfirstlane(sh_iNeed)) {
-              bit = bit_at(r);
+              bit = bits.bit_at(r);
               r += 1;
             }
             if (lane == 0)
@@ -1575,7 +1548,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
             continue;
           }
           // the subband is tested like a list of one entry
-          const uint32_t bit = bit_at(r);
+          const uint32_t bit = bits.bit_at(r);
           if (!bit) {
             if (lane == 0) {
               record_born(iPart, a + r, root);

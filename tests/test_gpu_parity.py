@@ -752,6 +752,31 @@ def test_streams_that_end_anywhere_in_the_list_kernels(eng, oracle):
         assert np.array_equal(bits(got), bits(oracle.decomp_3d(want, True))), bpp
 
 
+def test_two_chunks_through_the_block_parallel_list_kernels(eng, oracle):
+    """128 x 128 x 256 in two chunks of 128^3 -- the smallest chunk whose list of 8^3 sets (4096 of them) passes
+    k_lis_l2's threshold of 512 entries; two chunks, so the tickets and the look-back words and tables of k_lis_l0 /
+    _l1 / _l2 are taken at a chunk's offset -- at 1 and at 4 bits per sample, and the 4-bit container cut to half of
+    each chunk's payload (sperr_trunc_3d): every decoded value's bits against the reference's.  A list kernel that
+    gives up early hands its list to k_lis_hi, which decodes the same bits, so the decoder's tick counters are
+    switched on as well: word 56 counts the blocks k_lis_l1 handled for the first chunk."""
+    import ctypes as C
+    v = turbulence((256, 128, 128), seed=5)
+    full = oracle.comp_3d(v, (128, 128, 128), 1, 4.0)
+    eng.lib.sperrhip_debug_lis_stamps.argtypes = [C.c_int, C.c_void_p]
+    out = (C.c_ulonglong * 64)()
+    for name, want in [("1 bpp", oracle.comp_3d(v, (128, 128, 128), 1, 1.0)), ("half of 4 bpp", oracle.trunc_3d(full, 50)),
+                       ("4 bpp", full)]:
+        dev = cuda(np.frombuffer(want, dtype=np.uint8))
+        eng.lib.sperrhip_debug_lis_stamps(1, None)
+        try:
+            got = eng.decompress(dev, True).cpu().numpy()
+        finally:
+            eng.lib.sperrhip_debug_lis_stamps(0, out)
+        assert np.array_equal(bits(got), bits(oracle.decomp_3d(want, True))), name
+    print("k_lis_l1 handled %d blocks of the first chunk at 4 bpp" % out[56])
+    assert out[56] != 0
+
+
 def test_256_cube_chunk_pwe(eng, oracle):
     """One 256^3 fp32 chunk in point-wise error mode (the chunk shape of BASELINE configs 3 and 5 with
     config 5's mode): outlier stream included, byte-identical to the oracle; decoded floats
