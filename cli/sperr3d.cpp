@@ -73,6 +73,7 @@ int main(int argc, char** argv)
   // (SIZE_MAX: no --box_dims given; the parser makes --box_origin and --box_dims come together)
   size_t box_origin[3] = {0, 0, 0}, box_dims[3] = {SIZE_MAX, SIZE_MAX, SIZE_MAX};
   size_t level = SIZE_MAX;   // (SIZE_MAX: no --level given)
+  size_t pct = 0;            // (0: no --pct given; 0 and 100 and above all mean the whole streams)
   double pwe = 0.0, psnr = 0.0, bpp = 0.0;
 
   cli::Parser app("3D SPERR compression and decompression (MI355X)\n");
@@ -103,6 +104,15 @@ int main(int argc, char** argv)
     cli::Option& o = app.count("--level", level, "Decode only this level of the lower resolutions (0: the coarsest):\n"
                                "--decomp_f / --decomp_d hold the level; with --box_origin and\n"
                                "--box_dims, the box in that level's coordinates.", go);
+    o.needs = {"-d"};
+    o.excludes = {"--decomp_lowres_f", "--decomp_lowres_d"};
+  }
+  // (this tool's addition: decode a portion of every chunk's stream -- what decoding sperr3d_trunc's output gives,
+  //  without making it; the value is checked as sperr3d_trunc checks its --pct)
+  {
+    cli::Option& o = app.count("--pct", pct, "Percentage (1--100) of every chunk's bitstream to decode:\n"
+                               "--decomp_f / --decomp_d hold what the truncated bitstream decodes to.\n"
+                               "Composes with --box_origin, --box_dims and --level.", go);
     o.needs = {"-d"};
     o.excludes = {"--decomp_lowres_f", "--decomp_lowres_d"};
   }
@@ -205,6 +215,19 @@ int main(int argc, char** argv)
                std::log2(s.sigma / s.rmse) - rate);
       }
     }
+  }
+  else if (pct != 0) {
+    const bool boxed = box_dims[0] != SIZE_MAX || box_dims[1] != SIZE_MAX || box_dims[2] != SIZE_MAX;
+    Freed part;
+    size_t od[3] = {0, 0, 0};
+    if (sperrhip_decomp_3d_portion(input.data(), input.size(), (unsigned)std::min<size_t>(pct, 100), 0,
+                                   level != SIZE_MAX ? &level : nullptr, boxed ? box_origin : nullptr,
+                                   boxed ? box_dims : nullptr, od, &part.p) != 0) {
+      printf("Decompression failed!\n");
+      return 1;
+    }
+    if (!cli::write_volume(static_cast<const double*>(part.p), od[0] * od[1] * od[2], decomp_f64, decomp_f32, "data"))
+      return 1;
   }
   else if (level != SIZE_MAX) {
     const bool boxed = box_dims[0] != SIZE_MAX || box_dims[1] != SIZE_MAX || box_dims[2] != SIZE_MAX;

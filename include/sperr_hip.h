@@ -48,7 +48,9 @@ int sperr_decomp_3d(const void* src, size_t src_len, int output_float, size_t nt
 void sperr_parse_header(const void* src, size_t* dimx, size_t* dimy, size_t* dimz, int* is_float);
 
 /* include/SPERR_C_API.h:138-156 : keep `pct` percent of every chunk stream (progressive access);
- * the result decodes with sperr_decomp_3d.  Host only.  Returns 0 ok, 1 *dst not NULL, -1 other. */
+ * the result decodes with sperr_decomp_3d.  Host only: sperrhip_trunc_dev does the same to a container in device
+ * memory, and sperrhip_decompress_portion_dev decodes a portion without making one.  Returns 0 ok, 1 *dst not NULL,
+ * -1 other. */
 int sperr_trunc_3d(const void* src, size_t src_len, unsigned pct, void** dst, size_t* dst_len);
 
 /* ---- chunk farm: the same on an explicit list of devices -----------------------------------
@@ -257,6 +259,41 @@ int sperrhip_decompress_level_dev(const void* d_src, size_t src_len, int output_
 int sperrhip_decomp_3d_level(const void* src, size_t src_len, int output_float, size_t level,
                              const size_t box_lo[3], const size_t box_dims[3], size_t out_dims[3],
                              void** dst);
+
+/* ---- a portion of a 3D container: decoding at a fraction of the bit rate, truncating on the device -- */
+/* SPERR streams are embedded: the first `pct` percent of every chunk's stream decode to a coarser version of the
+ * same field (the reference's src/SPERR3D_Stream_Tools.cpp:134-226, utilities/sperr3d_trunc.cpp).  How many bytes
+ * of a chunk stream of chunk_len bytes a portion keeps: all of them when pct is 0 or >= 100 or chunk_len <= 64,
+ * else max(64, floor(pct / 100 * chunk_len)) (SPERR3D_Stream_Tools.cpp:170-195).  Host only. */
+size_t sperrhip_portion_len(size_t chunk_len, unsigned pct);
+/* The volume (level == NULL, no box), the box [lo, lo + dims) of it (level == NULL), or level *level of the hierarchy
+ * whole or a box of it (box_lo and box_dims NULL or not as for sperrhip_decompress_level_dev), decoded from the first
+ * `pct` percent of every chunk stream: bit for bit what sperrhip_decompress_dev / _box_dev / _level_dev give for
+ * sperr_trunc_3d(container, pct), but no truncated container is made -- no byte behind a kept prefix is read and the
+ * decoder's workspace follows the kept lengths.  pct 0 or >= 100: the whole streams, exactly as those calls.  They
+ * return -1 without writing to the output where those calls do, and when only one of box_lo / box_dims is NULL. */
+int sperrhip_decompress_portion_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
+                                    const size_t* level, const size_t box_lo[3], const size_t box_dims[3],
+                                    void* d_dst, size_t dst_cap_bytes, void* hip_stream);      /* 0 ok, -1 */
+/* host container -> malloc'd host volume, box or level (*dst must be NULL, free() it); out_dims (may be NULL) receives
+ * its dims.  Only the kept prefixes of the chosen chunks travel to the calling thread's device, one copy per chunk.
+ * Returns 0 ok, 1 *dst not NULL, -1 error. */
+int sperrhip_decomp_3d_portion(const void* src, size_t src_len, unsigned pct, int output_float,
+                               const size_t* level, const size_t box_lo[3], const size_t box_dims[3],
+                               size_t out_dims[3], void** dst);
+/* sperr_trunc_3d of a container in device memory into device memory: d_dst receives byte for byte what
+ * sperr_trunc_3d makes of it, *dst_len its length.  One kernel launch moves all bytes; the ranges may have any
+ * alignment.  Returns 0 ok; 1 when d_dst is NULL or dst_cap is too small -- nothing is written and *dst_len holds the
+ * size needed (src_len always suffices); -1 for a NULL d_src or dst_len, a container sperrhip_decompress_dev would
+ * refuse, or source and destination ranges that overlap. */
+int sperrhip_trunc_dev(const void* d_src, size_t src_len, unsigned pct, void* d_dst, size_t dst_cap,
+                       size_t* dst_len, void* hip_stream);
+/* nvol containers, container v at [offsets[v], offsets[v+1]) of d_src (host array), each truncated as above and
+ * written back to back: container v of the result is [out_offsets[v], out_offsets[v+1]) of d_dst (host array of
+ * nvol + 1 entries; out_offsets[nvol] is the size needed when 1 is returned).  The containers need not describe the
+ * same volume.  Return codes as sperrhip_trunc_dev; -1 also for nvol == 0 and decreasing offsets. */
+int sperrhip_trunc_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, unsigned pct,
+                             void* d_dst, size_t dst_cap, size_t* out_offsets, void* hip_stream);
 
 /* ---- a batch of same-shape volumes, one container each ----------------------------------------- */
 /* N volumes of the same dims in one call: the chunks of every volume are coded together (a batch is

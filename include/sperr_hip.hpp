@@ -162,30 +162,28 @@ class SPERR3D_OMP_D {
     return RTNType::Good;
   }
   // (this library's addition) only the box [lo, lo + dims) of the volume, decoded from the chunks it
-  // meets (sperrhip_decomp_3d_box); view_decoded_data() then holds the box, x fastest
-  auto decompress_box(const void* bitstream, dims_type lo, dims_type dims) -> RTNType
+  // meets (sperrhip_decomp_3d_box); view_decoded_data() then holds the box, x fastest.  pct (here and below): decode
+  // the first pct percent of every chunk stream only, what decoding progressive_truncate(.., pct) gives (0: all)
+  auto decompress_box(const void* bitstream, dims_type lo, dims_type dims, unsigned pct = 0) -> RTNType
   {
-    if (bitstream == nullptr || m_ptr == nullptr || bitstream != m_ptr)
-      return RTNType::Error;
-    void* dst = nullptr;
-    m_hierarchy.clear();
-    if (sperrhip_decomp_3d_box(m_ptr, m_len, 0, lo.data(), dims.data(), &dst) != 0)
-      return RTNType::Error;
-    const auto* d = static_cast<const double*>(dst);
-    m_vol.assign(d, d + dims[0] * dims[1] * dims[2]);
-    std::free(dst);
-    return RTNType::Good;
+    return window_impl(bitstream, pct, nullptr, lo.data(), dims.data());
   }
   // (this library's addition) one level of the hierarchy alone, coarsest first as view_hierarchy() orders them, whole
   // or the box [lo, lo + dims) of it in the level's coordinates (sperrhip_decomp_3d_level): only the chunks it meets
   // are read and only the level's part of the inverse transform runs; view_decoded_data() then holds it, x fastest
-  auto decompress_level(const void* bitstream, size_t level) -> RTNType
+  auto decompress_level(const void* bitstream, size_t level, unsigned pct = 0) -> RTNType
   {
-    return level_impl(bitstream, level, nullptr, nullptr);
+    return window_impl(bitstream, pct, &level, nullptr, nullptr);
   }
-  auto decompress_level(const void* bitstream, size_t level, dims_type lo, dims_type dims) -> RTNType
+  auto decompress_level(const void* bitstream, size_t level, dims_type lo, dims_type dims, unsigned pct = 0) -> RTNType
   {
-    return level_impl(bitstream, level, lo.data(), dims.data());
+    return window_impl(bitstream, pct, &level, lo.data(), dims.data());
+  }
+  // (this library's addition) the volume from the first pct percent of every chunk stream
+  // (sperrhip_decomp_3d_portion): only those bytes travel to the device
+  auto decompress_portion(const void* bitstream, unsigned pct) -> RTNType
+  {
+    return window_impl(bitstream, pct, nullptr, nullptr, nullptr, true);
   }
   auto view_decoded_data() const -> const vecd_type& { return m_vol; }
   auto release_decoded_data() -> vecd_type&& { return std::move(m_vol); }
@@ -195,14 +193,26 @@ class SPERR3D_OMP_D {
   auto get_chunk_dims() const -> dims_type { return m_chunk_dims; }
 
  private:
-  auto level_impl(const void* bitstream, size_t level, const size_t* lo, const size_t* dims) -> RTNType
+  // a box (level null), a level or a box of one; `portion`: through sperrhip_decomp_3d_portion whatever pct is
+  auto window_impl(const void* bitstream, unsigned pct, const size_t* level, const size_t* lo, const size_t* dims,
+                   bool portion = false) -> RTNType
   {
     if (bitstream == nullptr || m_ptr == nullptr || bitstream != m_ptr)
       return RTNType::Error;
     void* dst = nullptr;
     size_t od[3] = {0, 0, 0};
     m_hierarchy.clear();
-    if (sperrhip_decomp_3d_level(m_ptr, m_len, 0, level, lo, dims, od, &dst) != 0)
+    int rtn;
+    if (portion || pct != 0)
+      rtn = sperrhip_decomp_3d_portion(m_ptr, m_len, pct, 0, level, lo, dims, od, &dst);
+    else if (level)
+      rtn = sperrhip_decomp_3d_level(m_ptr, m_len, 0, *level, lo, dims, od, &dst);
+    else {
+      rtn = sperrhip_decomp_3d_box(m_ptr, m_len, 0, lo, dims, &dst);
+      for (int a = 0; a < 3; a++)
+        od[a] = dims[a];
+    }
+    if (rtn != 0)
       return RTNType::Error;
     const auto* d = static_cast<const double*>(dst);
     m_vol.assign(d, d + od[0] * od[1] * od[2]);
@@ -444,6 +454,14 @@ class SPERR3D_Stream_Tools {
       std::free(dst);
     }
     return out;
+  }
+  // (this library's addition) the same on a container in device memory, into device memory (sperrhip_trunc_dev):
+  // the bytes written to d_out, which holds `cap` (stream_len always suffices); 0 on failure
+  auto progressive_truncate_dev(const void* d_stream, size_t stream_len, unsigned pct, void* d_out, size_t cap) const
+      -> size_t
+  {
+    size_t len = 0;
+    return sperrhip_trunc_dev(d_stream, stream_len, pct, d_out, cap, &len, nullptr) == 0 ? len : 0;
   }
   auto progressive_read(const std::string& filename, unsigned pct) const -> vec8_type
   {

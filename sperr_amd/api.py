@@ -37,6 +37,8 @@ EXPORTS = [
     "sperrhip_max_compressed_size_batch", "sperrhip_compress_batch_dev", "sperrhip_decompress_batch_dev",
     "sperrhip_max_compressed_size_2d_batch", "sperrhip_compress_2d_batch_dev", "sperrhip_decompress_2d_batch_dev",
     "sperrhip_decompress_level_dev", "sperrhip_decomp_3d_level",
+    "sperrhip_portion_len", "sperrhip_decompress_portion_dev", "sperrhip_decomp_3d_portion",
+    "sperrhip_trunc_dev", "sperrhip_trunc_batch_dev",
 ]
 
 
@@ -139,6 +141,18 @@ def load_library():
     lib.sperrhip_decomp_3d_level.restype = C.c_int
     lib.sperrhip_decomp_3d_level.argtypes = [_vp, _sz, C.c_int, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz),
                                              C.POINTER(_vp)]
+    lib.sperrhip_portion_len.restype = _sz
+    lib.sperrhip_portion_len.argtypes = [_sz, C.c_uint]
+    lib.sperrhip_decompress_portion_dev.restype = C.c_int
+    lib.sperrhip_decompress_portion_dev.argtypes = [_vp, _sz, C.c_uint, C.c_int, C.POINTER(_sz), C.POINTER(_sz),
+                                                    C.POINTER(_sz), _vp, _sz, _vp]
+    lib.sperrhip_decomp_3d_portion.restype = C.c_int
+    lib.sperrhip_decomp_3d_portion.argtypes = [_vp, _sz, C.c_uint, C.c_int, C.POINTER(_sz), C.POINTER(_sz),
+                                               C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_vp)]
+    lib.sperrhip_trunc_dev.restype = C.c_int
+    lib.sperrhip_trunc_dev.argtypes = [_vp, _sz, C.c_uint, _vp, _sz, C.POINTER(_sz), _vp]
+    lib.sperrhip_trunc_batch_dev.restype = C.c_int
+    lib.sperrhip_trunc_batch_dev.argtypes = [_vp, C.POINTER(_sz), _sz, C.c_uint, _vp, _sz, C.POINTER(_sz), _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -223,7 +237,21 @@ class SperrHip:
         return (d[2].value, d[1].value, d[0].value), bool(isf.value), \
                (d[3].value, d[4].value, d[5].value)
 
-    def decompress(self, container, output_float=True, out=None, shape_zyx=None):
+    def _portion_dev(self, container, pct, output_float, level, lo, dims, out):
+        """sperrhip_decompress_portion_dev into `out`: the decode `level` / `lo` / `dims` name, of the first `pct`
+        percent of every chunk stream"""
+        rtn = self.lib.sperrhip_decompress_portion_dev(container.data_ptr(), container.numel(), int(pct),
+                                                       int(output_float), None if level is None else C.byref(_sz(level)),
+                                                       lo, dims, out.data_ptr(), out.numel() * out.element_size(),
+                                                       self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_portion_dev returned {rtn}")
+        return out
+
+    def decompress(self, container, output_float=True, out=None, shape_zyx=None, pct=0):
+        """The volume of a device container, a cuda tensor shaped (z, y, x) -- `out` when given.  pct (here and in
+        decompress_box / decompress_level): decode the first pct percent of every chunk stream only, bit for bit the
+        decode of truncate(container, pct) without making it; 0: everything."""
         torch = self.torch
         assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
         if shape_zyx is None:
@@ -232,6 +260,8 @@ class SperrHip:
         if out is None:
             out = torch.empty(shape_zyx, dtype=dt, device=container.device)
         assert out.dtype == dt and out.is_contiguous()
+        if pct:
+            return self._portion_dev(container, pct, output_float, None, None, None, out)
         dx, dy, dz = _sz(0), _sz(0), _sz(0)
         rtn = self.lib.sperrhip_decompress_dev(container.data_ptr(), container.numel(),
                                                int(output_float), out.data_ptr(),
@@ -241,7 +271,7 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_decompress_dev returned {rtn}")
         return out
 
-    def decompress_box(self, container, box_lo_xyz, box_dims_xyz, output_float=True, out=None):
+    def decompress_box(self, container, box_lo_xyz, box_dims_xyz, output_float=True, out=None, pct=0):
         """The box [lo, lo + dims) (x, y, z order) of a device container's volume, decoded from the chunks it
         meets only; a cuda tensor shaped (dims z, dims y, dims x) -- `out` when given."""
         torch = self.torch
@@ -250,6 +280,9 @@ class SperrHip:
         if out is None:
             out = torch.empty(tuple(int(d) for d in reversed(box_dims_xyz)), dtype=dt, device=container.device)
         assert out.dtype == dt and out.is_contiguous() and out.is_cuda
+        if pct:
+            return self._portion_dev(container, pct, output_float, None, (_sz * 3)(*box_lo_xyz),
+                                     (_sz * 3)(*box_dims_xyz), out)
         rtn = self.lib.sperrhip_decompress_box_dev(container.data_ptr(), container.numel(), int(output_float),
                                                    (_sz * 3)(*box_lo_xyz), (_sz * 3)(*box_dims_xyz), out.data_ptr(),
                                                    out.numel() * out.element_size(), self._stream())
@@ -265,7 +298,8 @@ class SperrHip:
             return None, None
         return (_sz * 3)(*box_lo_xyz), (_sz * 3)(*box_dims_xyz)
 
-    def decompress_level(self, container, level, box_lo_xyz=None, box_dims_xyz=None, output_float=False, out=None):
+    def decompress_level(self, container, level, box_lo_xyz=None, box_dims_xyz=None, output_float=False, out=None,
+                         pct=0):
         """Level `level` of a device container's hierarchy (coarsest first, as multires_levels orders them), whole or
         the box [lo, lo + dims) of it (x, y, z order, the level's coordinates): only the chunks it meets are read and
         only the level's part of the inverse transform runs.  A cuda tensor shaped (z, y, x) -- `out` when given."""
@@ -284,12 +318,52 @@ class SperrHip:
                 zyx = tuple(int(d) for d in reversed(box_dims_xyz))
             out = torch.empty(zyx, dtype=dt, device=container.device)
         assert out.dtype == dt and out.is_contiguous() and out.is_cuda
+        if pct:
+            return self._portion_dev(container, pct, output_float, level, lo, dims, out)
         rtn = self.lib.sperrhip_decompress_level_dev(container.data_ptr(), container.numel(), int(output_float),
                                                      level, lo, dims, out.data_ptr(),
                                                      out.numel() * out.element_size(), self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decompress_level_dev returned {rtn}")
         return out
+
+    def truncate(self, container, pct, out=None):
+        """sperr_trunc_3d of a device container on the device: a cuda uint8 view (of `out` when it is large enough) of
+        the container that keeps the first pct percent of every chunk stream."""
+        torch = self.torch
+        assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
+        if out is None or out.numel() < container.numel():
+            out = torch.empty(container.numel(), dtype=torch.uint8, device=container.device)
+        n = _sz(0)
+        rtn = self.lib.sperrhip_trunc_dev(container.data_ptr(), container.numel(), int(pct), out.data_ptr(),
+                                          out.numel(), C.byref(n), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_trunc_dev returned {rtn}")
+        return out[:n.value]
+
+    def truncate_batch(self, containers, pct, out=None):
+        """truncate() of every container of a list in one call and one kernel launch: cuda uint8 views into one
+        buffer (`out` when it is large enough), in order.  The containers are concatenated first unless they already
+        lie back to back in one buffer."""
+        torch = self.torch
+        assert len(containers) > 0
+        for c in containers:
+            assert c.is_cuda and c.dtype == torch.uint8 and c.dim() == 1 and c.is_contiguous()
+        nvol = len(containers)
+        packed = all(b.data_ptr() == a.data_ptr() + a.numel() and
+                     b.untyped_storage().data_ptr() == a.untyped_storage().data_ptr()
+                     for a, b in zip(containers, containers[1:]))
+        src = containers[0] if packed else torch.cat(list(containers))
+        offs, outs = (_sz * (nvol + 1))(), (_sz * (nvol + 1))()
+        for v, c in enumerate(containers):
+            offs[v + 1] = offs[v] + c.numel()
+        if out is None or out.numel() < offs[nvol]:
+            out = torch.empty(offs[nvol], dtype=torch.uint8, device=src.device)
+        rtn = self.lib.sperrhip_trunc_batch_dev(src.data_ptr(), offs, nvol, int(pct), out.data_ptr(), out.numel(),
+                                                outs, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_trunc_batch_dev returned {rtn}")
+        return [out[outs[v]:outs[v + 1]] for v in range(nvol)]
 
     def max_compressed_size_batch(self, nvol, shape_zyx, chunks_xyz, quality, mode=1):
         dz, dy, dx = shape_zyx
@@ -458,6 +532,25 @@ class SperrHip:
                                                 C.byref(dst))
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decomp_3d_level returned {rtn}")
+        dx, dy, dz = int(od[0]), int(od[1]), int(od[2])
+        dt = np.float32 if output_float else np.float64
+        out = np.frombuffer(C.string_at(dst.value, dx * dy * dz * np.dtype(dt).itemsize), dtype=dt).copy()
+        self._libc.free(dst)
+        return out.reshape(dz, dy, dx)
+
+    def decomp_3d_portion(self, stream, pct, level=None, box_lo_xyz=None, box_dims_xyz=None, output_float=True):
+        """The volume (no level, no box), a box of it, a level of the hierarchy or a box of one, of a host container
+        (bytes or a uint8 array), decoded from the first pct percent of every chunk stream: only those bytes of the
+        chosen chunks travel to the device.  A numpy array shaped (z, y, x)."""
+        buf = stream if isinstance(stream, np.ndarray) else np.frombuffer(stream, dtype=np.uint8)
+        lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
+        dst = _vp(None)
+        od = (_sz * 3)()
+        rtn = self.lib.sperrhip_decomp_3d_portion(buf.ctypes.data, buf.size, int(pct), int(output_float),
+                                                  None if level is None else C.byref(_sz(level)), lo, dims, od,
+                                                  C.byref(dst))
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decomp_3d_portion returned {rtn}")
         dx, dy, dz = int(od[0]), int(od[1]), int(od[2])
         dt = np.float32 if output_float else np.float64
         out = np.frombuffer(C.string_at(dst.value, dx * dy * dz * np.dtype(dt).itemsize), dtype=dt).copy()

@@ -238,6 +238,7 @@ using hostc::box_chunks;
 using hostc::chunk_volume;
 using hostc::ContainerInfo;
 using hostc::parse_container_host;
+using hostc::keep_portion;
 
 // src/Conditioner.cpp:137-163
 uint32_t condi_num_strides(size_t len)
@@ -1131,6 +1132,49 @@ __global__ void k_gather_heads(const uint8_t* container, const uint64_t* offs, c
     return;
   for (int i = 0; i < 32; i++)
     heads[c * 32 + i] = (i < 26 && (uint64_t)i < lens[c]) ? container[offs[c] + i] : 0;
+}
+
+// sperrhip_trunc_dev / sperrhip_trunc_batch_dev: the output of a truncation -- for every container its header, then the
+// kept prefix of every chunk stream -- is one run of bytes cut into `n` pieces: piece i is the bytes
+// [outOff[i], outOff[i + 1]) of dst and comes from the device address srcAddr[i] (a container's leading bytes and a
+// chunk's stream in the source, a rewritten length table in the call's upload).  The work is split by OUTPUT BYTES:
+// workgroup b moves the bytes [b kTruncSlice, (b + 1) kTruncSlice) and finds the pieces under them by binary search,
+// so 64 streams of 2 MB and 70 000 of 100 bytes load the device alike and the grid has one dimension.  A slice
+// under few pieces is copied piece by piece by the whole workgroup, one under many (short streams) wave by wave.
+// Pieces of no bytes share their start with the next one and are passed over.  Any alignment on either side
+constexpr uint32_t kTruncSlice = 8192;
+__global__ void __launch_bounds__(kThreads)
+k_trunc_container(uint8_t* dst, const uint64_t* srcAddr, const uint64_t* outOff, uint32_t n, uint64_t total)
+{
+  const uint64_t lo = (uint64_t)blockIdx.x * kTruncSlice;
+  if (lo >= total)
+    return;
+  const uint64_t hi = min(lo + kTruncSlice, total);
+  uint32_t a = 0, e = n;   // outOff[a] <= lo < outOff[e]  (outOff[0] = 0, outOff[n] = total)
+  while (e - a > 1) {
+    const uint32_t m = a + (e - a) / 2;
+    if (outOff[m] <= lo)
+      a = m;
+    else
+      e = m;
+  }
+  uint32_t f = a, g = n;   // outOff[f] < hi <= outOff[g]: the pieces a .. g - 1 have bytes in the slice
+  while (g - f > 1) {
+    const uint32_t m = f + (g - f) / 2;
+    if (outOff[m] < hi)
+      f = m;
+    else
+      g = m;
+  }
+  constexpr uint32_t kWaves = kThreads / 64;
+  const bool byWave = g - a >= 2 * kWaves;
+  const uint32_t first = byWave ? a + (threadIdx.x >> 6) : a, step = byWave ? kWaves : 1u;
+  const uint64_t tid = byWave ? (threadIdx.x & 63u) : threadIdx.x, nthr = byWave ? 64u : (uint32_t)kThreads;
+  for (uint32_t i = first; i < g; i += step) {
+    const uint64_t at = outOff[i], s = max(at, lo), t = min(outOff[i + 1], hi);
+    if (t > s)
+      copy_bytes_wide(dst + s, reinterpret_cast<const uint8_t*>(srcAddr[i]) + (s - at), t - s, tid, nthr);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2428,13 +2472,12 @@ int read_container_info(const uint8_t* d_src, size_t src_len, ContainerInfo& ci,
   return r == 0 ? 0 : -1;
 }
 
-// The containers of a batch (sperrhip_decompress_batch_dev), container v at [offs[v], offs[v + 1]) of d_src: every
-// header's prefix in one gather and one read-back, then the full headers of those with more to read in a second, each
-// parsed by parse_container_host.  All of them must describe the same volume.  `all` becomes the stacked view,
-// (x, y, nvol z) with every chunk's absolute offset and length; `list` its chunks (each container's chunk_volume, z
-// origins shifted by v z).  No container base is assumed aligned: the gathers read bytes
-int read_batch_info(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, ContainerInfo& all,
-                    std::vector<std::array<size_t, 6>>& list, hipStream_t st)
+// The headers of the containers of a batch, container v at [offs[v], offs[v + 1]) of d_src: every header's prefix in
+// one gather and one read-back, then the full headers of those with more to read in a second, each parsed by
+// parse_container_host into ci[v] (offsets relative to the container).  heads: 32 bytes per container, its first 26
+// (or fewer) and zeros.  No container base is assumed aligned: the gathers read bytes
+int read_batch_headers(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, std::vector<ContainerInfo>& ci,
+                       std::vector<uint8_t>& heads, hipStream_t st)
 {
   if (nvol == 0 || nvol > 0xffffffffull)
     return -1;
@@ -2453,13 +2496,13 @@ int read_batch_info(Engine& E, const uint8_t* d_src, const size_t* offs, size_t 
   uint64_t* d_len = d_off + arr / 8;
   uint64_t* d_at = d_len + arr / 8;
   uint8_t* d_bytes = reinterpret_cast<uint8_t*>(d_at + arr / 8);
-  std::vector<uint8_t> heads(nvol * 32);
+  heads.assign(nvol * 32, 0);
   HIP_CHECK(hipMemcpyAsync(d_off, off.data(), nvol * 8, hipMemcpyHostToDevice, st));
   HIP_CHECK(hipMemcpyAsync(d_len, len.data(), nvol * 8, hipMemcpyHostToDevice, st));
   LAUNCH_K(k_gather_heads, dim3((n + 63) / 64), dim3(64), 0, st, d_src, d_off, d_len, d_bytes, n);
   HIP_CHECK(hipMemcpyAsync(heads.data(), d_bytes, heads.size(), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  std::vector<ContainerInfo> ci(nvol);
+  ci.assign(nvol, ContainerInfo{});
   for (size_t v = 0; v < nvol; v++) {
     size_t nd = 0;
     const int r = parse_container_host(heads.data() + v * 32, std::min<uint64_t>(len[v], 26), len[v], ci[v], &nd);
@@ -2489,6 +2532,19 @@ int read_batch_info(Engine& E, const uint8_t* d_src, const size_t* offs, size_t 
         return -1;
     }
   }
+  return 0;
+}
+
+// The containers of a batch (sperrhip_decompress_batch_dev) as one: all of them must describe the same volume.  `all`
+// becomes the stacked view, (x, y, nvol z) with every chunk's absolute offset and length; `list` its chunks (each
+// container's chunk_volume, z origins shifted by v z)
+int read_batch_info(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, ContainerInfo& all,
+                    std::vector<std::array<size_t, 6>>& list, hipStream_t st)
+{
+  std::vector<ContainerInfo> ci;
+  std::vector<uint8_t> heads;
+  if (read_batch_headers(E, d_src, offs, nvol, ci, heads, st))
+    return -1;
   const Dims vol = ci[0].vol;
   for (size_t v = 1; v < nvol; v++)
     if (ci[v].vol != vol)
@@ -2509,10 +2565,84 @@ int read_batch_info(Engine& E, const uint8_t* d_src, const size_t* offs, size_t 
       auto c = per[i];
       c[4] += v * vol[2];
       list.push_back(c);
-      all.off.push_back(off[v] + ci[v].off[i]);
+      all.off.push_back(offs[v] + ci[v].off[i]);
       all.len.push_back(ci[v].len[i]);
     }
   }
+  return 0;
+}
+
+// sperrhip_trunc_dev / sperrhip_trunc_batch_dev: the containers at [offs[v], offs[v + 1]) of d_src, each as
+// hostc::truncate_container writes it, back to back into d_dst.  The host has every length table (read_batch_headers):
+// it works out the kept lengths, where every piece of the output comes from and where it goes, writes the new headers
+// -- the leading bytes with the portion flag, the table of kept lengths -- and uploads all that; one launch of
+// k_trunc_container then moves every byte, the headers' included.  outOffs: nvol + 1 entries
+int trunc_impl(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, unsigned pct, uint8_t* d_dst,
+               size_t dst_cap, size_t* outOffs, hipStream_t st)
+{
+  std::vector<ContainerInfo> ci;
+  std::vector<uint8_t> heads;
+  if (read_batch_headers(E, d_src, offs, nvol, ci, heads, st))
+    return -1;
+  const bool whole = pct == 0 || pct >= 100;
+  size_t npieces = 0, hdrBytes = 0;
+  for (const ContainerInfo& c : ci) {
+    npieces += 1 + c.len.size();
+    hdrBytes += (c.multi ? 20 : 14) + 4 * c.len.size();
+  }
+  if (npieces >= 0xffffffffull)
+    return -1;
+  // the upload: the source addresses, the output offsets, then the new headers
+  const size_t addrBytes = round_up(npieces * 8, 256), offBytes = round_up((npieces + 1) * 8, 256);
+  if (E.misc.ensure(addrBytes + offBytes + hdrBytes + 256))
+    return -1;
+  uint8_t* d_up = static_cast<uint8_t*>(E.misc.p);
+  std::vector<uint8_t> up(addrBytes + offBytes + hdrBytes, 0);
+  uint64_t* srcAddr = reinterpret_cast<uint64_t*>(up.data());
+  uint64_t* outOff = reinterpret_cast<uint64_t*>(up.data() + addrBytes);
+  uint8_t* hdr = up.data() + addrBytes + offBytes;
+  size_t k = 0, hat = 0;
+  uint64_t out = 0;
+  for (size_t v = 0; v < nvol; v++) {
+    const ContainerInfo& c = ci[v];
+    const size_t pos = c.multi ? 20 : 14, hlen = pos + 4 * c.len.size();
+    uint8_t* h = hdr + hat;
+    memcpy(h, heads.data() + v * 32, pos);
+    if (!whole) {
+      h[0] = 0;       // SPERR_VERSION_MAJOR
+      h[1] |= 0x80;   // the portion flag (hostc::truncate_container)
+    }
+    outOffs[v] = (size_t)out;
+    srcAddr[k] = reinterpret_cast<uint64_t>(d_up + addrBytes + offBytes + hat);
+    outOff[k++] = out;
+    out += hlen;
+    for (size_t i = 0; i < c.len.size(); i++) {
+      const uint32_t keep = (uint32_t)hostc::portion_len((size_t)c.len[i], pct);
+      memcpy(h + pos + 4 * i, &keep, 4);
+      srcAddr[k] = reinterpret_cast<uint64_t>(d_src + offs[v] + c.off[i]);
+      outOff[k++] = out;
+      out += keep;
+    }
+    hat += hlen;
+  }
+  outOff[k] = out;
+  outOffs[nvol] = (size_t)out;
+  if (!d_dst || out > dst_cap)
+    return 1;
+  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src) + offs[0], s1 = reinterpret_cast<uintptr_t>(d_src) + offs[nvol];
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(d_dst), d1 = d0 + out;
+  if (s0 < d1 && d0 < s1)
+    return -1;
+  const uint64_t nblocks = (out + kTruncSlice - 1) / kTruncSlice;
+  if (nblocks > 0x7fffffffull)
+    return -1;
+  HIP_CHECK(hipMemcpyAsync(d_up, up.data(), up.size(), hipMemcpyHostToDevice, st));
+  LAUNCH_K(k_trunc_container, dim3((uint32_t)nblocks), dim3(kThreads), 0, st, d_dst,
+           reinterpret_cast<const uint64_t*>(d_up), reinterpret_cast<const uint64_t*>(d_up + addrBytes), (uint32_t)npieces,
+           out);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));   // (also: `up` may go only once the copy has read it)
+  E.prof.collect();
   return 0;
 }
 
@@ -5231,6 +5361,105 @@ int sperrhip_decomp_3d_level(const void* src, size_t src_len, int output_float, 
         out_dims[a] = w.dims[a];
     return rtn;
   });
+}
+
+// ---- a portion: decoding, and truncating on the device ------------------------------------------
+size_t sperrhip_portion_len(size_t chunk_len, unsigned pct)
+{
+  return hostc::portion_len(chunk_len, pct);
+}
+
+// The decodes of sperrhip_decompress_dev / _box_dev / _level_dev of the first `pct` percent of every chunk stream: the
+// call's own ContainerInfo takes the kept lengths (keep_portion) and the existing path runs on it, so nothing behind
+// a kept prefix is read, the workspace follows the kept lengths and no copy of the container is made
+int sperrhip_decompress_portion_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
+                                    const size_t* level, const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
+                                    size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_decompress_portion_dev", [&]() -> int {
+    if (!d_src || !d_dst || (box_lo == nullptr) != (box_dims == nullptr))
+      return -1;
+    DevDecode d(d_src, src_len, hip_stream);
+    if (!d.ok)
+      return -1;
+    keep_portion(d.ci, pct);
+    if (!level && !box_lo)
+      return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, DecodeRequest{});
+    Window w;
+    if (level ? level_select(d.ci, *level, box_lo, box_dims, w) : box_select(d.ci, box_lo, box_dims, w))
+      return -1;
+    return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w);
+  });
+}
+
+// host container in, malloc'd host volume, box or level out: only the kept prefixes of the chosen chunks travel to the
+// device (decode_packed_host; the prefixes do not lie back to back, so each is a copy of its own)
+int sperrhip_decomp_3d_portion(const void* src, size_t src_len, unsigned pct, int output_float, const size_t* level,
+                               const size_t box_lo[3], const size_t box_dims[3], size_t out_dims[3], void** dst)
+{
+  return guarded("sperrhip_decomp_3d_portion", [&]() -> int {
+    if (!dst || *dst != nullptr)
+      return 1;
+    if (!src || (box_lo == nullptr) != (box_dims == nullptr))
+      return -1;
+    ContainerInfo ci;
+    size_t need = 0;
+    if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
+      return -1;
+    keep_portion(ci, pct);
+    const size_t esz = output_float ? sizeof(float) : sizeof(double);
+    const bool all = !level && !box_lo;
+    Window w;
+    std::vector<uint32_t> every;
+    if (all) {
+      if (ci.len.size() > 0xffffffffull)
+        return -1;
+      every.resize(ci.len.size());
+      for (size_t i = 0; i < every.size(); i++)
+        every[i] = (uint32_t)i;
+    }
+    else if (level ? level_select(ci, *level, box_lo, box_dims, w) : box_select(ci, box_lo, box_dims, w))
+      return -1;
+    const Dims od = all ? ci.vol : w.dims;
+    const size_t outBytes = od[0] * od[1] * od[2] * esz;
+    const int rtn = decode_packed_host(
+        static_cast<const uint8_t*>(src), ci, all ? every : w.ids, outBytes, dst,
+        [&](Engine& E, const void* d_in, const ContainerInfo& packed, void* d_out) {
+          return all ? decode_to(E, d_in, output_float, d_out, outBytes, packed, nullptr, DecodeRequest{})
+                     : decode_window(E, d_in, output_float, d_out, outBytes, packed, nullptr, w);
+        });
+    if (rtn == 0 && out_dims)
+      for (int a = 0; a < 3; a++)
+        out_dims[a] = od[a];
+    return rtn;
+  });
+}
+
+int sperrhip_trunc_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, unsigned pct, void* d_dst,
+                             size_t dst_cap, size_t* out_offsets, void* hip_stream)
+{
+  return guarded("sperrhip_trunc_batch_dev", [&]() -> int {
+    if (!d_src || !offsets || !out_offsets || nvol == 0)
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    return trunc_impl(*L.e, static_cast<const uint8_t*>(d_src), offsets, nvol, pct, static_cast<uint8_t*>(d_dst),
+                      dst_cap, out_offsets, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int sperrhip_trunc_dev(const void* d_src, size_t src_len, unsigned pct, void* d_dst, size_t dst_cap, size_t* dst_len,
+                       void* hip_stream)
+{
+  if (!dst_len)
+    return -1;
+  const size_t offs[2] = {0, src_len};
+  size_t out[2] = {0, 0};
+  const int rtn = sperrhip_trunc_batch_dev(d_src, offs, 1, pct, d_dst, dst_cap, out, hip_stream);
+  if (rtn >= 0)
+    *dst_len = out[1];
+  return rtn;
 }
 
 }  // extern "C"

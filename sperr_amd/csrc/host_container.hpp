@@ -165,6 +165,27 @@ inline int parse_container_host(const uint8_t* h, size_t hlen, size_t total_len,
   return 0;
 }
 
+// src/SPERR3D_Stream_Tools.cpp:170-195: how many bytes of a chunk stream of `len` bytes a portion of `pct` percent
+// keeps -- all of them for pct 0 or >= 100 and for streams of at most 64 bytes (include/SPERR3D_Stream_Tools.h:54),
+// else pct percent of them, rounded down, and at least 64.  The one statement of the rule: truncate_container, the
+// device truncation and the portion decodes all size a chunk with it.
+constexpr size_t kMinChunkBytes = 64;
+inline size_t portion_len(size_t len, unsigned pct)
+{
+  if (pct == 0 || pct >= 100 || len <= kMinChunkBytes)
+    return len;
+  return std::max(kMinChunkBytes, (size_t)((double)pct / 100.0 * (double)len));
+}
+
+// A container read as its portion of `pct` percent without making one: every chunk's length becomes the kept length,
+// its offset stays where the whole stream starts.  A decoder that takes its lengths from `ci` then reads no byte
+// behind a kept prefix and pads with zeros, as it does for a truncated container.
+inline void keep_portion(ContainerInfo& ci, unsigned pct)
+{
+  for (auto& l : ci.len)
+    l = portion_len((size_t)l, pct);
+}
+
 // include/SPERR_C_API.h:138-156, src/SPERR_C_API.cpp:260-280,
 // src/SPERR3D_Stream_Tools.cpp:134-226: host-side byte surgery, no GPU involved.  Every chunk
 // stream keeps `pct` percent of its bytes (at least 64, at most what it has), the container is
@@ -195,7 +216,6 @@ inline int truncate_container(const uint8_t* src, size_t src_len, unsigned pct, 
   if (src_len < pos || nchunks > (src_len - pos) / 4)
     return -1;
   const size_t hlen = pos + 4 * nchunks;
-  constexpr size_t kMinChunkBytes = 64;   // include/SPERR3D_Stream_Tools.h:54
   const bool whole = pct == 0 || pct >= 100;
   std::vector<size_t> off(nchunks), len(nchunks);
   size_t at = hlen, total = hlen, far = 0;
@@ -204,9 +224,7 @@ inline int truncate_container(const uint8_t* src, size_t src_len, unsigned pct, 
     memcpy(&l, h + pos + 4 * i, 4);
     off[i] = at;
     at += l;
-    len[i] = l;
-    if (!whole && l > kMinChunkBytes)
-      len[i] = std::max(kMinChunkBytes, (size_t)((double)pct / 100.0 * (double)l));
+    len[i] = portion_len(l, pct);
     total += len[i];
     far = std::max(far, off[i] + len[i]);
   }
