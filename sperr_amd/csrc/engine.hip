@@ -29,6 +29,7 @@
 #include "engine_internal.h"
 #include "host_container.hpp"
 #include "speck_dec.h"
+#include "dequant.h"
 #include "speck_enc.h"
 #include "speck_tree_host.hpp"
 #include "outlier.h"
@@ -1652,6 +1653,17 @@ struct PweStage {
   std::vector<ChunkGeom> bricks;
   HostMarks hm;
 };
+// The encoder's own coefficients, for its reconstruction of what the decoder will see: complete, so no masks and no
+// decoder state.  wide: the 64-bit ones, which live in the fp64 buffer and are converted in place
+static DequantSrc enc_dequant_src(const EncBatchBufs& bb, bool wide)
+{
+  DequantSrc s;
+  s.coef = wide ? static_cast<const void*>(bb.vals) : bb.coef32;
+  s.coefStride = wide ? bb.valsStride : bb.eb.coefStride;
+  s.sign = bb.eb.sign;
+  s.signStride = bb.eb.signStride;
+  return s;
+}
 template <typename T>
 int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb,
                     const T* d_src, VolDesc vd, const uint32_t cd[3], double tol, bool anyWide, PweStage& S)
@@ -1693,10 +1705,7 @@ int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs&
     auto fuse = [&](size_t k, LiftFuse& lf) {
       if (pass_fuse(P, k, lf.inner) > 0) {
         lf.mode = 2;
-        lf.coef = bb.coef32;
-        lf.coefStride = e.coefStride;
-        lf.sign = e.sign;
-        lf.signStride = e.signStride;
+        lf.src = enc_dequant_src(bb, false);
       }
       lf.bufx = cbox[0];
       lf.bufy = cbox[1];
@@ -1716,10 +1725,8 @@ int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs&
       return -1;
   }
   else {
-    if (launch_inv_quantize(st, false, bb.coef32, e.coefStride, e.sign, e.signStride, nb, P.N, bb.vals,
-                            bb.valsStride, e.cst) ||
-        launch_inv_quantize(st, true, bb.vals, bb.valsStride, e.sign, e.signStride, nb, P.N, bb.vals,
-                            bb.valsStride, e.cst))
+    if (launch_inv_quantize(st, false, enc_dequant_src(bb, false), nb, P.N, bb.vals, bb.valsStride, e.cst) ||
+        launch_inv_quantize(st, true, enc_dequant_src(bb, true), nb, P.N, bb.vals, bb.valsStride, e.cst))
       return -1;
     for (size_t k = P.fwd.size(); k-- > 0;) {
       const LiftPass& ps = P.fwd[k];
@@ -3005,15 +3012,13 @@ bool window_select(const Dims& full, const Dims& chunk, const size_t lo[3], cons
 }
 
 // The coarsest level's corner: no inverse pass runs before it is read, so nothing has dequantised it (LiftFuse mode 2
-// does that as a pass loads).  k_inv_quantize for the corner box [0, s) of every chunk with 32-bit coefficients, into
+// does that as a pass loads).  The samples of the corner box [0, s) of every chunk with 32-bit coefficients, into
 // the chunk buffer with rows of bx and slices of by rows; one sample per lane, nothing outside the corner is touched.
-// The arithmetic is k_lift_axis's fetch: q * double(c) * (+-1.0), a coefficient never refined completed from the
-// decoder's masks, or the word k_ref_assemble left complete with its sign in bit 31 (coef_scheme)
+// The arithmetic is dequant.h's: dequant_masks, or dequant_signed where k_ref_assemble left the word complete with
+// its sign in bit 31
 __global__ void __launch_bounds__(kThreads)
 k_dequant_corner(double* vals, size_t valsStride, uint32_t bx, uint32_t by, uint32_t cx, uint32_t cy, uint32_t sx,
-                 uint32_t sy, uint32_t sz, const CoderState* cst, const DecState* dst, const uint32_t* coef,
-                 size_t coefStride, const uint64_t* sign, size_t signStride, const uint64_t* sigNew,
-                 const uint64_t* sigOld, size_t maskStride, int coefSigned)
+                 uint32_t sy, uint32_t sz, const CoderState* cst, DequantSrc Q)
 {
   const uint32_t c = blockIdx.y;
   const CoderState& cs = cst[c];
@@ -3025,23 +3030,16 @@ k_dequant_corner(double* vals, size_t valsStride, uint32_t bx, uint32_t by, uint
   const uint32_t x = i % sx, r = i / sx;
   const uint32_t y = r % sy, z = r / sy;
   const size_t idx = ((size_t)z * cy + y) * cx + x;
-  const double q = cs.q;
-  const int scheme = coefSigned != 0 ? coef_scheme(dst[c]) : 0;
-  uint32_t v = coef[c * coefStride + idx];
+  const DequantRule<uint32_t> rule = dequant_rule<uint32_t>(cs.q, true, Q.dst + c, Q.coefSigned != 0);   // (the decoder's: masks and state are there)
+  const uint32_t v = Q.coefs<uint32_t>(c)[idx];
   double out;
-  if (scheme)
-    out = q * (double)coef_scheme_mag(v, scheme == 2) * ((v >> 31) ? -1.0 : 1.0);
+  if (rule.scheme)
+    out = dequant_signed(rule, v);
   else {
-    const uint32_t lastPl = (uint32_t)dst[c].lastPlane;
-    const uint32_t initNew = (1u << lastPl) + (1u << lastPl) - (1u << lastPl) / 2 - 1;
-    const uint32_t initOld = lastPl < 31 ? (2u << lastPl) + (2u << lastPl) - (2u << lastPl) / 2 - 1 : 0u;
     const uint32_t w = (uint32_t)(idx >> 6), sh = (uint32_t)(idx & 63);
-    const uint64_t sgw = sign[c * signStride + w];
-    const uint32_t mn = (uint32_t)(sigNew[c * maskStride + w] >> sh) & 1u;
-    const uint32_t mo = (uint32_t)(sigOld[c * maskStride + w] >> sh) & 1u;
-    const uint32_t fill = mn ? initNew : (mo ? initOld : 0u);
-    v = v ? v : fill;
-    out = q * (double)v * (((sgw >> sh) & 1ull) ? 1.0 : -1.0);
+    const uint64_t sgw = Q.sign[c * Q.signStride + w];
+    const uint64_t mnw = Q.sigNew[c * Q.maskStride + w], mow = Q.sigOld[c * Q.maskStride + w];
+    out = dequant_masks(rule, v, mnw, mow, sgw, sh);
   }
   vals[c * valsStride + ((size_t)z * by + y) * bx + x] = out;
 }
@@ -3769,35 +3767,44 @@ struct DecodeCall {
         dw.coefStride = bb.valsStride;
         dw.refPlanes = nullptr;
       }
-      else if (d.refPlanes)
-        dw.coefSigned = b.fuseDq ? 1u : 0u;   // (read by the dequantising inverse passes only: LiftFuse::coefSigned)
+      else   // (read by the dequantising inverse passes only: DequantSrc::coefSigned)
+        dw.coefSigned = packed_signs(b, bb, false) ? 1u : 0u;
       // the header kernel must run even when no plane does (constant / all-zero chunks)
       if (launch_speck_decode(ss, dw, ph, d_src, bb.chunkOff, bb.chunkLen, wide != 0, wide ? S.maxWide : S.maxNarrow))
         return -1;
       // (32-bit coefficients are dequantised by the inverse passes as they load them, LiftFuse)
       if ((wide || !b.fuseDq) &&
-          launch_inv_quantize(ss, wide != 0, dw.coef, dw.coefStride, d.sign, d.signStride, nb, P.N, bb.vals,
-                              bb.valsStride, d.cst, d.sigNew, d.sigOld, d.maskPixStride, d.st))
+          launch_inv_quantize(ss, wide != 0, dequant_src(b, bb, wide != 0), nb, P.N, bb.vals, bb.valsStride, d.cst))
         return -1;
     }
     return 0;
   }
+  // Where the decoder left a sub-batch's coefficients, with the masks and the state that complete them.  wide: the
+  // 64-bit ones, which live in the fp64 buffer and are converted in place.  The 32-bit words carry their sign exactly
+  // where enqueue_lists asked k_ref_assemble for it (DecBuffers::coefSigned)
+  DequantSrc dequant_src(const Batch& b, const DecBatchBufs& bb, bool wide) const
+  {
+    const DecBuffers& d = bb.db;
+    DequantSrc s;
+    s.coef = wide ? static_cast<const void*>(bb.vals) : bb.coef32;
+    s.coefStride = wide ? bb.valsStride : d.coefStride;
+    s.sign = d.sign;
+    s.signStride = d.signStride;
+    s.sigNew = d.sigNew;
+    s.sigOld = d.sigOld;
+    s.maskStride = d.maskPixStride;
+    s.dst = d.st;
+    s.coefSigned = packed_signs(b, bb, wide) ? 1 : 0;
+    return s;
+  }
+  static bool packed_signs(const Batch& b, const DecBatchBufs& bb, bool wide) { return !wide && bb.db.refPlanes && b.fuseDq; }
   // LiftFuse of inverse pass k: the pass dequantises the samples no coarser level produces as it loads them, where
   // the group allows it, and works in the compact buffer where the group has one
   void pass_dequant(const Batch& b, const DecBatchBufs& bb, size_t k, LiftFuse& lf) const
   {
-    const DecBuffers& d = bb.db;
     if (b.fuseDq && pass_fuse(*b.P, k, lf.inner) > 0) {
       lf.mode = 2;
-      lf.coef = bb.coef32;
-      lf.coefStride = d.coefStride;
-      lf.sign = d.sign;
-      lf.signStride = d.signStride;
-      lf.sigNew = d.sigNew;
-      lf.sigOld = d.sigOld;
-      lf.maskStride = d.maskPixStride;
-      lf.dst = d.st;
-      lf.coefSigned = d.refPlanes ? 1 : 0;
+      lf.src = dequant_src(b, bb, false);
     }
     if (b.compactElems) {
       lf.bufx = b.cbox[0];
@@ -3943,8 +3950,7 @@ struct DecodeCall {
     const uint32_t blocks = (r[0] * r[1] * r[2] + kThreads - 1) / kThreads;
     if (h == 0 && b.fuseDq)
       LAUNCH_K(k_dequant_corner, dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, bx, by, cd[0], cd[1],
-               r[0], r[1], r[2], d.cst, d.st, bb.coef32, d.coefStride, d.sign, d.signStride, d.sigNew, d.sigOld,
-               d.maskPixStride, d.refPlanes ? 1 : 0);
+               r[0], r[1], r[2], d.cst, dequant_src(b, bb, false));
     if (lvl.crop)
       LAUNCH_K((k_level_write<T, true>), dim3(blocks, nb), dim3(kThreads), 0, ss, bb.vals, bb.valsStride, d.cst, bb.crop,
                bx, by, cd[0], cd[1], cd[2], r[0], r[1], r[2], vd, d_dst);

@@ -17,6 +17,7 @@
 // Bits past the available length read as zero (the reference zero-pads a truncated stream,
 // SPECK_INT.cpp:95-105); the loop stops where the reference's does.
 #include "speck_dec.h"
+#include "dequant.h"
 #include "bit_words.h"
 #include "lis_chain.h"
 
@@ -701,8 +702,7 @@ __global__ void __launch_bounds__(64) k_lis_walk(DecBuffers b, int p)
   unsigned long long* sigNew = reinterpret_cast<unsigned long long*>(b.sigNew + c * b.maskPixStride);
   CT* coef = reinterpret_cast<CT*>(b.coef) + c * b.coefStride;
   unsigned long long* sign = reinterpret_cast<unsigned long long*>(b.sign + c * b.signStride);
-  const CT thr = (CT)1 << p;
-  const CT init = thr + thr - thr / 2 - 1;
+  const CT init = never_refined<CT>(p);
   const uint32_t cur = s.cur, nx = cur ^ 1u;
   for (uint32_t l = lane; l < t.nlevels; l += 64)
     nextLen[l] = 0;
@@ -3582,7 +3582,7 @@ __global__ void __launch_bounds__(kThreads) k_ref_assemble(DecBuffers b)
   const uint64_t* sigNew = b.sigNew + c * b.maskPixStride;
   const uint64_t* refMask = b.refMask + c * b.maskPixStride;
   const uint8_t* wordTop = b.wordTop + c * b.wordTopStride;
-  // the sign in bit 31 for the dequantising inverse passes where the chunk allows it (coef_scheme, speck_dec.h)
+  // the sign in bit 31 for the dequantising inverse passes where the chunk allows it (coef_scheme, dequant.h)
   const int scheme = b.coefSigned != 0 ? coef_scheme(s) : 0;
   const uint64_t* sign = b.sign + c * b.signStride;
   for (uint32_t w0 = wave * kW; w0 + kW <= nw; w0 += nwave * kW) {
@@ -3675,8 +3675,8 @@ __global__ void __launch_bounds__(kThreads) k_ref_assemble(DecBuffers b)
             q = refPlane + 1;
         }
         v = m ? m + (q >= 1 ? (1u << (q - 1)) - 1u : 0u) : 0u;
-        if (scheme)   // (a set bit of the sign array is "positive", SPECK_INT.cpp:174-175)
-          v = (scheme == 2 ? v >> 1 : v) | (((sg[u] >> lane) & 1ull) ? 0u : 0x80000000u);
+        if (scheme)   // (a branch the whole chunk takes or not; without it, a select more per coefficient)
+          v = coef_scheme_pack(v, ((sg[u] >> lane) & 1ull) != 0, scheme);
       }
       coef[(size_t)w * 64 + lane] = v;
     }
@@ -3708,10 +3708,8 @@ __global__ void __launch_bounds__(kThreads) k_dec_fold(DecBuffers b)
   }
 }
 
-// After the last plane: coefficients that became significant but were never refined still hold 0.
-// Those found during the last decoded plane `pl` (sigNew) get 1.5 * 2^pl - 1, those found on the
-// plane before (sigOld, untouched by a complete refinement pass) 1.5 * 2^(pl+1) - 1
-// (SPECK_INT.cpp:216-220,462-468).
+// After the last plane: coefficients that became significant but were never refined still hold 0 and are completed
+// (rule 1 of dequant.h) -- unless the caller's inverse quantiser does it on its way (DecPlanHost::skipFinish).
 template <typename CT>
 __global__ void __launch_bounds__(kThreads) k_dec_finish(DecBuffers b)
 {
@@ -3731,9 +3729,7 @@ __global__ void __launch_bounds__(kThreads) k_dec_finish(DecBuffers b)
   CT* coef = reinterpret_cast<CT*>(b.coef) + c * b.coefStride;
   if (coef[i] != 0)
     return;
-  const int pl = s.lastPlane + (isNew ? 0 : 1);
-  const CT thr = (CT)1 << pl;
-  coef[i] = thr + thr - thr / 2 - 1;
+  coef[i] = never_refined<CT>(s.lastPlane + (isNew ? 0 : 1));
 }
 
 __global__ void k_dec_plane_end(DecBuffers b, int p)

@@ -37,21 +37,38 @@ int launch_scatter(hipStream_t stream, T* vol, VolDesc vd, const ChunkGeom* geom
 //                     whole chunk is written and read again.  Chunks with 64-bit coefficients keep
 //                     theirs in the fp64 buffer (converted in place beforehand) and are read as ever.
 struct DecState;
-struct LiftFuse {
-  int mode = 0;
-  uint32_t inner[3] = {0, 0, 0};
-  const uint32_t* coef = nullptr;
+
+// Where the integer coefficients of a batch's chunks are, for every kernel that makes samples of them (dequant.h):
+// chunk c's arrays start c strides in
+struct DequantSrc {
+  // uint32_t magnitudes -- or, the 64-bit pass, uint64_t ones in the fp64 buffer that is converted in place: the
+  // caller knows which (coefs<CT>)
+  const void* coef = nullptr;
   size_t coefStride = 0;
-  const uint64_t* sign = nullptr;
+  const uint64_t* sign = nullptr;     // a set bit: positive
   size_t signStride = 0;
+  // the decoder's significance masks and state, to complete the coefficients that were never refined (the decoder
+  // is told to skip its own finishing pass, DecPlanHost::skipFinish); all null: nothing to complete (the encoder's
+  // reconstruction of its own coefficients)
   const uint64_t* sigNew = nullptr;
   const uint64_t* sigOld = nullptr;
   size_t maskStride = 0;
   const DecState* dst = nullptr;
   // 1: k_ref_assemble has written the coefficients complete (never-refined ones included) and, chunk by chunk where
-  // coef_scheme(dst[c]) allows it, with the sign in bit 31 (speck_dec.h): the sign and mask words are not read at all then.
-  // q * double(magnitude), sign flipped = q * double(magnitude) * (+-1.0) bit for bit (a zero is positive either way)
+  // coef_scheme(dst[c]) allows it, with the sign in bit 31 (dequant.h): the sign and mask words are not read at all then
   int coefSigned = 0;
+
+  __host__ __device__ bool has_masks() const { return sigNew != nullptr && dst != nullptr; }
+  template <typename CT>
+  __host__ __device__ const CT* coefs(uint32_t c) const { return static_cast<const CT*>(coef) + c * coefStride; }
+};
+
+struct LiftFuse {
+  int mode = 0;
+  uint32_t inner[3] = {0, 0, 0};
+  // mode 2.  (no_unique_address: noMean lies in the padding at src's end, as it did when src's fields were LiftFuse's own
+  // -- k_lift_xyz_inv spills three to seven more scalar registers when the kernel's argument block is laid out otherwise)
+  [[no_unique_address]] DequantSrc src;
   // k_lift_xyz_inv: do not add the chunk's mean to what it writes (the encoder's point-wise error stage compares in the
   // conditioned domain, src/SPECK_FLT.cpp:461-486)
   int noMean = 0;
@@ -60,6 +77,7 @@ struct LiftFuse {
   // arrays keep the chunk's dims
   uint32_t bufx = 0, bufy = 0;
 };
+static_assert(sizeof(LiftFuse) == 96 && __builtin_offsetof(LiftFuse, noMean) == 84, "the argument block of the lifting kernels");
 
 // io: 0 in place; 1 / 2: the pass also reads (forward) or writes (inverse) the float / double
 // volume through the chunk map -- only valid for a pass whose region is the whole chunk
@@ -79,7 +97,7 @@ int launch_lift_xy(hipStream_t stream, bool forward, double* vals, size_t valsSt
 // The x, y AND z pass of the finest level in one kernel (k_lift_xyz_fwd / _inv): the z direction is
 // a sliding window of per-position lifting pipelines in registers.  Forward: volume -> vals, with
 // the largest magnitude collected when fuse->mode == 1; inverse: (coefficients dequantised on the
-// way when fuse->mode == 2, never-refined ones already completed by k_dec_finish) -> volume.  Only
+// way when fuse->mode == 2, never-refined ones completed from the decoder's masks: dequant.h) -> volume.  Only
 // for chunks whose first three passes are the full-size x, y and z ones and whose rows fit.
 bool lift_xyz_applicable(const uint32_t cdims[3]);
 int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsStride, uint32_t nchunks,
@@ -116,13 +134,10 @@ int launch_quantize(hipStream_t stream, bool wide, const double* vals, size_t va
                     uint32_t nchunks, uint32_t n, void* coef, size_t coefStride, uint64_t* sign,
                     size_t signStride, int8_t* msb, size_t msbStride, const CoderState* st);
 
-// sigNew / sigOld / dst: the decoder's significance masks and state, to complete the coefficients
-// that were never refined (then launch_speck_decode is told to skip its own finishing pass)
-int launch_inv_quantize(hipStream_t stream, bool wide, const void* coef, size_t coefStride,
-                        const uint64_t* sign, size_t signStride, uint32_t nchunks, uint32_t n,
-                        double* vals, size_t valsStride, const CoderState* st,
-                        const uint64_t* sigNew = nullptr, const uint64_t* sigOld = nullptr,
-                        size_t maskStride = 0, const DecState* dst = nullptr);
+// every chunk with 32-bit (wide: 64-bit) coefficients, whole: src.coef holds magnitudes of that width, never packed
+// words (src.coefSigned is not looked at)
+int launch_inv_quantize(hipStream_t stream, bool wide, const DequantSrc& src, uint32_t nchunks, uint32_t n,
+                        double* vals, size_t valsStride, const CoderState* st);
 
 }  // namespace sperrhip
 

@@ -13,7 +13,7 @@
 
 #include "xform.h"
 #include "lift_window.h"
-#include "speck_dec.h"
+#include "dequant.h"
 
 namespace sperrhip {
 
@@ -330,32 +330,24 @@ k_lift_axis(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, int axis,
     return !(xyz[0] < F.inner[0] && xyz[1] < F.inner[1] && xyz[2] < F.inner[2]);
   };
   const bool dequant = !FORWARD && F.mode == 2 && !st[c].wide;
-  const double fq = dequant ? st[c].q : 0.0;
-  // value of a coefficient that became significant on the last decoded plane / the one before and
-  // was never refined (k_inv_quantize)
-  const uint32_t lastPl = (dequant && F.dst) ? (uint32_t)F.dst[c].lastPlane : 0u;
-  const int scheme = (dequant && F.coefSigned != 0 && F.dst) ? coef_scheme(F.dst[c]) : 0;
-  const uint32_t initNew = (1u << lastPl) + (1u << lastPl) - (1u << lastPl) / 2 - 1;
-  const uint32_t initOld = lastPl < 31 ? (2u << lastPl) + (2u << lastPl) - (2u << lastPl) / 2 - 1 : 0u;
+  const DequantSrc& Q = F.src;
+  const bool haveMasks = dequant && Q.has_masks();
+  const DequantRule<uint32_t> rule =
+      dequant_rule<uint32_t>(dequant ? st[c].q : 0.0, haveMasks, haveMasks ? Q.dst + c : nullptr, Q.coefSigned != 0);
   auto fetch = [&](uint32_t l, uint32_t p) -> LT {
     if (IO != 0 && FORWARD)
       return (LT)vol[vbase + l * vsu + p * vsl];
     if (!FORWARD && dequant) {
       size_t idx;
-      if (outside_inner(l, p, idx)) {   // k_inv_quantize for this one sample; the loads are independent
-        if (scheme) {   // (the sign in bit 31, the value complete: LiftFuse::coefSigned)
-          const uint32_t sv = F.coef[c * F.coefStride + idx];
-          return (LT)(fq * (double)coef_scheme_mag(sv, scheme == 2) * ((sv >> 31) ? -1.0 : 1.0));
-        }
+      if (outside_inner(l, p, idx)) {   // this one sample from its coefficient (dequant.h); the loads are independent
+        const uint32_t v = Q.coefs<uint32_t>(c)[idx];
+        if (rule.scheme)   // (the sign in bit 31, the value complete: DequantSrc::coefSigned)
+          return (LT)dequant_signed(rule, v);
         const uint32_t w = (uint32_t)(idx >> 6), sh = (uint32_t)(idx & 63);
-        uint32_t v = F.coef[c * F.coefStride + idx];
-        const uint64_t sgw = F.sign[c * F.signStride + w];
-        const uint64_t mnw = F.sigNew ? F.sigNew[c * F.maskStride + w] : 0ull;
-        const uint64_t mow = F.sigNew ? F.sigOld[c * F.maskStride + w] : 0ull;
-        const uint32_t mn = (uint32_t)(mnw >> sh) & 1u, mo = (uint32_t)(mow >> sh) & 1u;
-        const uint32_t fill = mn ? initNew : (mo ? initOld : 0u);
-        v = v ? v : fill;
-        return (LT)(fq * (double)v * (((sgw >> sh) & 1ull) ? 1.0 : -1.0));
+        const uint64_t sgw = Q.sign[c * Q.signStride + w];
+        const uint64_t mnw = haveMasks ? Q.sigNew[c * Q.maskStride + w] : 0ull;
+        const uint64_t mow = haveMasks ? Q.sigOld[c * Q.maskStride + w] : 0ull;
+        return (LT)dequant_masks(rule, v, mnw, mow, sgw, sh);
       }
     }
     return (LT)tile[l * su + p * sl];
@@ -1156,7 +1148,7 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
   }
 }
 
-// SG: the coefficients carry their sign where the chunk allows it (LiftFuse::coefSigned, coef_scheme), a kernel of its own -- with both fast paths in
+// SG: the coefficients carry their sign where the chunk allows it (DequantSrc::coefSigned, coef_scheme), a kernel of its own -- with both fast paths in
 // one function the register allocator spilled inside the slice loop (88 registers against 38) and the kernel took 5.4 ms
 // instead of 3.7
 // kCrop: the rows of the chunk's window go to the box; a tile with no row in the window returns at once
@@ -1238,25 +1230,21 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   }
   const bool dequant = F.mode == 2 && !st[c].wide;
   const double fq = dequant ? st[c].q : 0.0;
-  const uint32_t* coef = F.coef + c * F.coefStride;
-  const uint64_t* sign = F.sign + c * F.signStride;
-  // a coefficient that became significant on the last decoded plane / the one before and was never
-  // refined still holds 0: its value comes from the decoder's masks (k_inv_quantize, k_lift_axis)
-  const bool haveMasks = dequant && F.sigNew != nullptr && F.dst != nullptr;
-  const uint64_t* mNew = haveMasks ? F.sigNew + c * F.maskStride : sign;
-  const uint64_t* mOld = haveMasks ? F.sigOld + c * F.maskStride : sign;
-  const uint32_t lastPl = haveMasks ? (uint32_t)F.dst[c].lastPlane : 0u;
-  const uint32_t initNew = haveMasks ? (1u << lastPl) + (1u << lastPl) - (1u << lastPl) / 2 - 1 : 0u;
-  const uint32_t initOld = (haveMasks && lastPl < 31) ? (2u << lastPl) + (2u << lastPl) - (2u << lastPl) / 2 - 1 : 0u;
-  // the sign in bit 31, the value complete (k_ref_assemble, LiftFuse::coefSigned): neither the sign nor the mask words are read
-  const int scheme = (SG && dequant && F.dst) ? coef_scheme(F.dst[c]) : 0;   // (0: this chunk keeps magnitudes and masks)
-  const bool two = scheme == 2;
-  auto sg_value = [&](uint32_t sv) -> double {
-    double d = fq * (double)coef_scheme_mag(sv, two);
-    return __hiloint2double(__double2hiint(d) ^ (int)(sv & 0x80000000u), __double2loint(d));   // * -1.0, exactly
-  };
-  // sample (dcol, drow, zp): straight from the decoder (q * double(c) * (+-1.0), src/SPECK_FLT.cpp:373-399)
-  // unless a coarser level's passes have produced it
+  const DequantSrc& Q = F.src;
+  const uint32_t* coef = Q.coefs<uint32_t>(c);
+  const uint64_t* sign = Q.sign + c * Q.signStride;
+  // a coefficient that became significant on the last decoded plane / the one before and was never refined still
+  // holds 0: its value comes from the decoder's masks.  (Without masks the rule completes nothing: the mask words
+  // read are the sign's then, whatever they hold.)
+  const bool haveMasks = dequant && Q.has_masks();
+  const uint64_t* mNew = haveMasks ? Q.sigNew + c * Q.maskStride : sign;
+  const uint64_t* mOld = haveMasks ? Q.sigOld + c * Q.maskStride : sign;
+  // SG: the sign in bit 31, the value complete (k_ref_assemble, DequantSrc::coefSigned): neither the sign nor the mask
+  // words are read (scheme 0: this chunk keeps magnitudes and masks)
+  const DequantRule<uint32_t> rule = dequant_rule<uint32_t>(fq, haveMasks, haveMasks ? Q.dst + c : nullptr, SG);
+  const int scheme = rule.scheme;
+  auto sg_value = [&](uint32_t sv) -> double { return dequant_signed(rule, sv); };
+  // sample (dcol, drow, zp): straight from the decoder (dequant.h) unless a coarser level's passes have produced it
   auto fetch = [&](int k, uint32_t zp) -> double {
     const uint32_t y = (pk[k] >> 12) & 0x7fffu, x = pk[k] & 0xfffu;
     const uint32_t drow = (y & 1) ? ye + (y >> 1) : (y >> 1), dcol = (x & 1) ? xe + (x >> 1) : (x >> 1);
@@ -1267,12 +1255,10 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     if (dequant && !inBox) {
       if (SG && scheme)
         return sg_value(coef[idx]);
-      uint32_t v = coef[idx];
+      const uint32_t v = coef[idx];
       const uint32_t sh = (uint32_t)(idx & 63);
       const uint64_t sgw = sign[idx >> 6], mnw = mNew[idx >> 6], mow = mOld[idx >> 6];   // (independent loads)
-      const uint32_t fill = ((mnw >> sh) & 1ull) ? initNew : (((mow >> sh) & 1ull) ? initOld : 0u);
-      v = v ? v : fill;
-      return fq * (double)v * (((sgw >> sh) & 1ull) ? 1.0 : -1.0);
+      return dequant_masks(rule, v, mnw, mow, sgw, sh);
     }
     return buf[(size_t)zp * bufSlice + drow * bufx + dcol];
   };
@@ -1563,9 +1549,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
         for (int j = 0; j < NV; j++) {
           if (g + j / 2 >= kXYZPosI)
             continue;
-          const uint32_t fill = ((mnw[j] >> shv[j]) & 1u) ? initNew : (((mow[j] >> shv[j]) & 1u) ? initOld : 0u);
-          const uint32_t v = cv[j] ? cv[j] : fill;
-          const double dq = fq * (double)v * (((sgw[j] >> shv[j]) & 1u) ? 1.0 : -1.0);
+          const double dq = dequant_masks(rule, cv[j], mnw[j], mow[j], sgw[j], shv[j]);
           val[j] = ((j & 1) == 0 && ((boxm >> j) & 1u)) ? bx[j / 2] : dq;
         }
 #pragma unroll
@@ -1832,15 +1816,12 @@ k_quantize4(const double* vals, size_t valsStride, uint32_t n, uint32_t* coef, s
     sign[c * signStride + (i >> 6)] = word;
 }
 
-// SPECK_FLT.cpp:373-399 : (q * c) * (+-1.0), left to right.  When the decoder's masks are given,
-// the coefficients that became significant but were never refined are completed here instead of
-// in a pass of their own (k_dec_finish, speck_dec.hip: 1.5 * 2^plane - 1, SPECK_INT.cpp:462-468).
+// Every sample of a chunk from its coefficient (dequant.h), four per lane.  When the decoder's masks are given, the
+// coefficients that became significant but were never refined are completed here instead of in a pass of their own
+// (k_dec_finish, speck_dec.hip).
 template <typename CT>
 __global__ void __launch_bounds__(kThreads)
-k_inv_quantize(const CT* coef, size_t coefStride, const uint64_t* sign, size_t signStride,
-               uint32_t n, double* vals, size_t valsStride, const CoderState* st, int wide_pass,
-               const uint64_t* sigNew, const uint64_t* sigOld, size_t maskStride,
-               const DecState* dst)
+k_inv_quantize(DequantSrc Q, uint32_t n, double* vals, size_t valsStride, const CoderState* st, int wide_pass)
 {
   const uint32_t c = blockIdx.y;
   const CoderState& s = st[c];
@@ -1849,7 +1830,7 @@ k_inv_quantize(const CT* coef, size_t coefStride, const uint64_t* sign, size_t s
   const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;   // four samples of one mask word
   if (i0 >= n)
     return;
-  const CT* in = coef + c * coefStride + i0;
+  const CT* in = Q.coefs<CT>(c) + i0;
   double* out = vals + c * valsStride + i0;
   CT v[4];
   const uint32_t cnt = min(4u, n - i0);
@@ -1868,24 +1849,23 @@ k_inv_quantize(const CT* coef, size_t coefStride, const uint64_t* sign, size_t s
     for (uint32_t k = 0; k < 4; k++)
       v[k] = k < cnt ? in[k] : (CT)1;
   const uint32_t w = i0 >> 6, sh = i0 & 63;
-  if (sigNew != nullptr && (v[0] == 0 || v[1] == 0 || v[2] == 0 || v[3] == 0)) {
-    const uint32_t mn = (uint32_t)(sigNew[c * maskStride + w] >> sh) & 15u;
-    const uint32_t mo = (uint32_t)(sigOld[c * maskStride + w] >> sh) & 15u;
+  // (the mask words and the decoder's state are read only where a coefficient is 0: few are)
+  if (Q.has_masks() && (v[0] == 0 || v[1] == 0 || v[2] == 0 || v[3] == 0)) {
+    const uint32_t mn = (uint32_t)(Q.sigNew[c * Q.maskStride + w] >> sh) & 15u;
+    const uint32_t mo = (uint32_t)(Q.sigOld[c * Q.maskStride + w] >> sh) & 15u;
     if (mn | mo) {
-      const int pl = dst[c].lastPlane;
+      const int pl = Q.dst[c].lastPlane;   // (few lanes get here: the threshold per element, not a DequantRule)
 #pragma unroll
       for (int k = 0; k < 4; k++)
-        if (v[k] == 0 && ((mn | mo) >> k) & 1u) {
-          const CT thr = (CT)1 << (pl + (((mn >> k) & 1u) ? 0 : 1));
-          v[k] = thr + thr - thr / 2 - 1;
-        }
+        if (v[k] == 0 && ((mn | mo) >> k) & 1u)
+          v[k] = never_refined<CT>(pl + (((mn >> k) & 1u) ? 0 : 1));
     }
   }
-  const uint32_t sg = (uint32_t)(sign[c * signStride + w] >> sh);
+  const uint32_t sg = (uint32_t)(Q.sign[c * Q.signStride + w] >> sh);
   double r[4];
 #pragma unroll
   for (int k = 0; k < 4; k++)
-    r[k] = s.q * (double)v[k] * (((sg >> k) & 1u) ? 1.0 : -1.0);
+    r[k] = dequant_value(s.q, v[k], ((sg >> k) & 1u) != 0);
   if (cnt == 4) {
     *reinterpret_cast<double2*>(out) = make_double2(r[0], r[1]);
     *reinterpret_cast<double2*>(out + 2) = make_double2(r[2], r[3]);
@@ -2124,7 +2104,7 @@ int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsS
                cdims[2], K, st, volume, vd, geom, wantMax, F.inner[0], F.inner[1], F.inner[2], nseg);
   }
   else {
-    const bool sg = F.mode == 2 && F.coefSigned != 0;
+    const bool sg = F.mode == 2 && F.src.coefSigned != 0;
 #define XYZ_INV_LAUNCH(io_, sg_)                                                                                    \
   LAUNCH_K((k_lift_xyz_inv<io_, sg_>), grid, dim3(kXYZThreadsI), smem, stream, vals, valsStride, cdims[0], cdims[1], \
            cdims[2], K, st, volume, vd, geom, F, nseg)
@@ -2285,21 +2265,14 @@ int launch_quantize(hipStream_t stream, bool wide, const double* vals, size_t va
   return 0;
 }
 
-int launch_inv_quantize(hipStream_t stream, bool wide, const void* coef, size_t coefStride,
-                        const uint64_t* sign, size_t signStride, uint32_t nchunks, uint32_t n,
-                        double* vals, size_t valsStride, const CoderState* st,
-                        const uint64_t* sigNew, const uint64_t* sigOld, size_t maskStride,
-                        const DecState* dst)
+int launch_inv_quantize(hipStream_t stream, bool wide, const DequantSrc& src, uint32_t nchunks, uint32_t n,
+                        double* vals, size_t valsStride, const CoderState* st)
 {
   dim3 grid((n + kThreads * 4 - 1) / (kThreads * 4), nchunks);
   if (wide)
-    LAUNCH_K(k_inv_quantize<uint64_t>, grid, dim3(kThreads), 0, stream,
-                       (const uint64_t*)coef, coefStride, sign, signStride, n, vals, valsStride,
-                       st, 1, sigNew, sigOld, maskStride, dst);
+    LAUNCH_K(k_inv_quantize<uint64_t>, grid, dim3(kThreads), 0, stream, src, n, vals, valsStride, st, 1);
   else
-    LAUNCH_K(k_inv_quantize<uint32_t>, grid, dim3(kThreads), 0, stream,
-                       (const uint32_t*)coef, coefStride, sign, signStride, n, vals, valsStride,
-                       st, 0, sigNew, sigOld, maskStride, dst);
+    LAUNCH_K(k_inv_quantize<uint32_t>, grid, dim3(kThreads), 0, stream, src, n, vals, valsStride, st, 0);
   HIP_CHECK(hipGetLastError());
   return 0;
 }

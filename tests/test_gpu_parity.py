@@ -280,7 +280,7 @@ def test_high_precision_retry(eng, oracle):
 @pytest.mark.parametrize("bpp", [2.0, 9.0, 14.0, 16.0, 17.0, 18.0, 18.5, 19.0, 19.5, 20.0, 24.0, 29.5])
 def test_decoded_coefficients_hand_over_schemes(eng, oracle, bpp):
     """k_ref_assemble hands the inverse passes the sign inside the coefficient word where the chunk allows it
-    (coef_scheme, speck_dec.h): fixed-rate chunks have 32 planes (src/SPECK_FLT.cpp:282-290), so which scheme a chunk
+    (coef_scheme, dequant.h): fixed-rate chunks have 32 planes (src/SPECK_FLT.cpp:282-290), so which scheme a chunk
     takes depends on the plane its stream runs out on -- from plane 2 up the low bit makes room, below it the
     magnitudes stay as they are and the masks are read.  A sweep of rates down to the last planes, two chunk shapes
     (the fused x-y-z inverse kernel and the per-axis passes)."""
