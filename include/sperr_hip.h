@@ -295,6 +295,21 @@ int sperrhip_trunc_dev(const void* d_src, size_t src_len, unsigned pct, void* d_
 int sperrhip_trunc_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, unsigned pct,
                              void* d_dst, size_t dst_cap, size_t* out_offsets, void* hip_stream);
 
+/* ---- quality figures of a reconstruction, both arrays in device memory ------------------------- */
+/* out[8] = {rmse, linfty, psnr, min, max, mean, var, mse}: calc_stats<T> then calc_mean_var<T> of the
+ * reference (min, max, mean and var are the original's), each a T widened to double, with the reference's
+ * blocked, strictly sequential sums in T -- the bits a host run of the reference gives; psnr goes through
+ * the host's log10.  Identical arrays: rmse 0, linfty 0, psnr +inf, mse 0.  The arrays hold n values of
+ * float (is_float != 0) or double at any alignment of that type; values are finite (NaNs are the caller's
+ * problem, as in the reference) and the sign of a zero min or max is not pinned.  One host wait, at the
+ * end.  0 ok; -1 (out untouched, nothing launched) for n == 0 or a NULL pointer. */
+int sperrhip_quality_dev(const void* d_orig, const void* d_recon, int is_float, size_t n,
+                         double* out, void* hip_stream);
+/* nvol arrays of n values back to back in each buffer; out[nvol*8]; volume v's figures are bit for
+ * bit those of the single call on its slice.  One host wait for the batch; -1 also for nvol == 0. */
+int sperrhip_quality_batch_dev(const void* d_orig, const void* d_recon, int is_float, size_t nvol,
+                               size_t n, double* out, void* hip_stream);
+
 /* ---- a batch of same-shape volumes, one container each ----------------------------------------- */
 /* N volumes of the same dims in one call: the chunks of every volume are coded together (a batch is
  * more chunks for the same shape groups), and each volume gets a container of its own.  Container v

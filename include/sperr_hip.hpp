@@ -502,6 +502,18 @@ class SPERR3D_Stream_Tools {
   }
 };
 
+// (this library's addition) calc_stats<T> then calc_mean_var<T> of two arrays of n values in device memory
+// (sperrhip_quality_dev): {rmse, linfty, psnr, min, max, mean, var, mse}, each a T widened to double.
+// RTNType::Good, or RTNType::Error (out untouched) for n == 0, a null pointer or no device.
+template <typename T>
+inline auto quality_dev(const T* d_orig, const T* d_recon, size_t n, std::array<double, 8>& out,
+                        void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const int rtn = sperrhip_quality_dev(d_orig, d_recon, sizeof(T) == 4, n, out.data(), hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
 }  // namespace sperr
 
 #endif

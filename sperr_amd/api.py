@@ -5,6 +5,7 @@ path is the C-ABI library declared in include/sperr_hip.h.  There is no CPU fall
 works anywhere, but every call needs a GPU and raises if the library is missing or a call fails.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -39,11 +40,32 @@ EXPORTS = [
     "sperrhip_decompress_level_dev", "sperrhip_decomp_3d_level",
     "sperrhip_portion_len", "sperrhip_decompress_portion_dev", "sperrhip_decomp_3d_portion",
     "sperrhip_trunc_dev", "sperrhip_trunc_batch_dev",
+    "sperrhip_quality_dev", "sperrhip_quality_batch_dev",
 ]
 
 
 class SperrHipError(RuntimeError):
     pass
+
+
+class Quality:
+    """The figures of one reconstruction against its original (SperrHip.quality): rmse, linfty, psnr, mse, and
+    the original's min, max, mean, var and sigma = sqrt(var); with the compressed size known also bitrate and
+    accuracy_gain (None otherwise).  Values of the arrays' type widened to float."""
+    __slots__ = ("rmse", "linfty", "psnr", "min", "max", "mean", "var", "mse", "sigma", "bitrate", "accuracy_gain")
+
+    def __init__(self, figs, n, nbytes=None):
+        self.rmse, self.linfty, self.psnr, self.min, self.max, self.mean, self.var, self.mse = figs
+        self.sigma = math.sqrt(self.var)
+        self.bitrate = self.accuracy_gain = None
+        if nbytes is not None:
+            # as the reference's tool prints them (utilities/sperr3d.cpp:380-382), in double
+            self.bitrate = 8.0 * nbytes / n
+            with np.errstate(divide="ignore"):
+                self.accuracy_gain = float(np.log2(np.float64(self.sigma) / np.float64(self.rmse))) - self.bitrate
+
+    def __repr__(self):
+        return "Quality(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
 
 
 def host_cpus(lib):
@@ -153,6 +175,10 @@ def load_library():
     lib.sperrhip_trunc_dev.argtypes = [_vp, _sz, C.c_uint, _vp, _sz, C.POINTER(_sz), _vp]
     lib.sperrhip_trunc_batch_dev.restype = C.c_int
     lib.sperrhip_trunc_batch_dev.argtypes = [_vp, C.POINTER(_sz), _sz, C.c_uint, _vp, _sz, C.POINTER(_sz), _vp]
+    lib.sperrhip_quality_dev.restype = C.c_int
+    lib.sperrhip_quality_dev.argtypes = [_vp, _vp, C.c_int, _sz, C.POINTER(C.c_double), _vp]
+    lib.sperrhip_quality_batch_dev.restype = C.c_int
+    lib.sperrhip_quality_batch_dev.argtypes = [_vp, _vp, C.c_int, _sz, _sz, C.POINTER(C.c_double), _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -417,6 +443,39 @@ class SperrHip:
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decompress_batch_dev returned {rtn}")
         return out
+
+    # ---- quality figures of a reconstruction ---------------------------------------------------
+    def _quality_args(self, orig, recon):
+        torch = self.torch
+        assert orig.is_cuda and recon.is_cuda and orig.is_contiguous() and recon.is_contiguous()
+        assert orig.dtype == recon.dtype and orig.dtype in (torch.float32, torch.float64)
+        assert orig.numel() == recon.numel() and orig.numel() > 0
+
+    def quality(self, orig, recon, nbytes=None):
+        """The reference's figures (calc_stats, calc_mean_var) of `recon` against `orig`, computed where they are:
+        contiguous cuda tensors of one dtype (float32 / float64) and numel, any shape.  A Quality record; `nbytes`
+        (the compressed size) adds bitrate and accuracy_gain."""
+        self._quality_args(orig, recon)
+        out = (C.c_double * 8)()
+        rtn = self.lib.sperrhip_quality_dev(orig.data_ptr(), recon.data_ptr(), int(orig.dtype == self.torch.float32),
+                                            orig.numel(), out, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_quality_dev returned {rtn}")
+        return Quality(out[:8], orig.numel(), nbytes)
+
+    def quality_batch(self, origs, recons):
+        """quality() of every pair of a batch in one call: stacked tensors (N, ...), as compress_batch takes and
+        decompress_batch returns them.  A list of N Quality records."""
+        self._quality_args(origs, recons)
+        assert origs.dim() >= 2 and origs.shape[0] == recons.shape[0]
+        nvol = origs.shape[0]
+        n = origs.numel() // nvol
+        out = (C.c_double * (8 * nvol))()
+        rtn = self.lib.sperrhip_quality_batch_dev(origs.data_ptr(), recons.data_ptr(),
+                                                  int(origs.dtype == self.torch.float32), nvol, n, out, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_quality_batch_dev returned {rtn}")
+        return [Quality(out[8 * v:8 * v + 8], n) for v in range(nvol)]
 
     # ---- stage access ----------------------------------------------------------------------
     def dwt3d(self, vals, inverse=False):

@@ -33,6 +33,7 @@
 #include "speck_enc.h"
 #include "speck_tree_host.hpp"
 #include "outlier.h"
+#include "quality.h"
 #include "xform.h"
 
 // The decoder runs the shape groups of a volume side by side on up to eight streams; the ROCm
@@ -5466,6 +5467,32 @@ int sperrhip_trunc_dev(const void* d_src, size_t src_len, unsigned pct, void* d_
   if (rtn >= 0)
     *dst_len = out[1];
   return rtn;
+}
+
+// the figures of nvol reconstructions against their originals (quality.hip); the partials' workspace is the
+// leased engine's arena, like every other call's
+int sperrhip_quality_batch_dev(const void* d_orig, const void* d_recon, int is_float, size_t nvol, size_t n,
+                               double* out, void* hip_stream)
+{
+  return guarded("sperrhip_quality_batch_dev", [&]() -> int {
+    if (!d_orig || !d_recon || !out || nvol == 0 || n == 0)
+      return -1;
+    const size_t need = quality_workspace_bytes(nvol, n, is_float);
+    if (need == 0)
+      return -1;
+    Lease L;
+    if (!L.e || L.e->arena.ensure(need))
+      return -1;
+    const int rtn = quality_run(d_orig, d_recon, is_float, nvol, n, L.e->arena.p, out, hip_stream);
+    L.e->prof.collect();
+    return rtn;
+  });
+}
+
+int sperrhip_quality_dev(const void* d_orig, const void* d_recon, int is_float, size_t n, double* out,
+                         void* hip_stream)
+{
+  return sperrhip_quality_batch_dev(d_orig, d_recon, is_float, 1, n, out, hip_stream);
 }
 
 }  // extern "C"
