@@ -26,6 +26,7 @@
 // Bits past the budget are dropped, but whole passes are still counted so that the header's
 // total_bits equals the reference's (the bit count at the end of the pass that crossed it).
 #include "speck_enc.h"
+#include "pix_planes.h"
 
 namespace sperrhip {
 
@@ -552,6 +553,24 @@ __device__ __forceinline__ void load_pix(const int8_t* a, uint32_t i0, uint32_t 
   else
     for (int k = 0; k < kPixPer; k++)
       v[k] = (i0 + k < n) ? a[i0 + k] : -1;
+}
+
+// the same 16 bytes as they lie in memory (byte k of the four words: value k); 0xff, that is -1, past the end
+__device__ __forceinline__ void load_pix_packed(const int8_t* a, uint32_t i0, uint32_t n, uint32_t (&w)[4])
+{
+  static_assert(kPixPer == 16, "one 16-byte load per thread");
+  if (i0 + kPixPer <= n) {
+    const uint4 q = *reinterpret_cast<const uint4*>(a + i0);
+    w[0] = q.x;
+    w[1] = q.y;
+    w[2] = q.z;
+    w[3] = q.w;
+  }
+  else {
+    w[0] = w[1] = w[2] = w[3] = 0;
+    for (int k = 0; k < kPixPer; k++)
+      w[k >> 2] |= (uint32_t)((i0 + k < n) ? (uint8_t)a[i0 + k] : 0xffu) << ((k & 3) * 8);
+  }
 }
 
 // Bits each plane's LIP scan and refinement pass take inside one tile.  A sample with msb m that
@@ -1522,72 +1541,139 @@ __global__ void __launch_bounds__(kThreads) k_born_place(EncBuffers b, int p)
 // Each tile's bits of one (plane, phase) are contiguous in the stream: stage them in LDS and OR
 // whole words out.
 // ------------------------------------------------------------------------------------------
+// (timing experiments only, tools/build_variant.sh: parts of the kernel switched off -- 1: the coefficient and sign loads
+//  (hashed noise below the birth plane instead), 2: the threads' bits of a plane, 4: the block scan, 8: deposit and flush.
+//  Any of them writes a stream that is not the coder's.)
+#ifndef EMIT_PIX_OFF
+#define EMIT_PIX_OFF 0
+#endif
 template <typename CT>
-__global__ void __launch_bounds__(kThreads) k_emit_pixels(EncBuffers b)
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(sizeof(CT) == 4 ? 7 : 4, 8)))
+k_emit_pixels(EncBuffers b)
 {
+  constexpr bool kPlanes = sizeof(CT) == 4;   // 32 planes of 16 samples are 16 registers: the 32-bit pass holds plane masks
   const uint32_t c = blockIdx.y;
   const EncState& s = b.st[c];
   if (!s.active || s.nbp == 0)
     return;
   constexpr int kWords = kPixTile * 2 / 64 + 2;
   __shared__ unsigned long long lipw[kWords], refw[kWords];
-  __shared__ uint32_t sm[kThreads / 64 + 1];
   const uint32_t n = b.tree.nvals;
   const uint32_t tile = blockIdx.x;
   const uint32_t i0 = tile * kPixTile + threadIdx.x * kPixPer;
-  int m[kPixPer], bp[kPixPer];
-  load_pix(b.bplane + c * b.pixStride, i0, n, bp);
+  // The thread's 16 samples BIT-SLICED (round 3): bit k of B[j] = bit j of birth plane + 1 of sample k.  "Born above
+  // plane p" for all 16 samples is then a dozen logic operations on 16-bit masks per plane instead of a chain of
+  // compares, shifts and adds per sample and plane.
+  constexpr int kBirthBits = kPlanes ? 6 : 7;   // birth plane + 1 is at most 32 in the 32-bit pass
+  uint32_t B[kBirthBits];
   int bpmax = -1;   // no sample of the thread is in the LIP or significant at planes >= bpmax
+  {
+    // (the 16 bytes stay packed: + 1 in every byte, -1 -> 0 without a carry, and a multiplication gathers bit j of a
+    //  word's four bytes -- a quarter of the operations of 16 samples taken apart one by one)
+    uint32_t w[4];
+    load_pix_packed(b.bplane + c * b.pixStride, i0, n, w);
 #pragma unroll
-  for (int k = 0; k < kPixPer; k++)
-    bpmax = max(bpmax, bp[k]);
+    for (int k = 0; k < kPixPer; k++)
+      bpmax = max(bpmax, (int)(int8_t)(w[k >> 2] >> ((k & 3) * 8)));
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      w[i] = ((w[i] & 0x7f7f7f7fu) + 0x01010101u) & 0x7f7f7f7fu;
+#pragma unroll
+    for (int j = 0; j < kBirthBits; j++) {
+      B[j] = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        B[j] |= ((((w[i] >> j) & 0x01010101u) * 0x01020408u) >> 24 & 15u) << (4 * i);
+    }
+  }
   // A sample born at plane b gives LIP bits on planes below b and refinement bits below its msb <= b: nothing at all
   // when b is not above the last plane coded.  Such a thread -- at 2 bits per sample half of them: the fine subbands
-  // whose sets never split inside the budget -- loads neither its coefficients nor their msbs (round 5, second
-  // session: 5 of the 6 bytes a sample costs here).
+  // whose sets never split inside the budget -- loads no coefficients (round 5, second session).  Nobody loads the msb
+  // bytes: a sample's msb is that of the magnitude the thread has in hand (k_quantize, k_head_fused: 63 - clz, -1 of a
+  // zero), and the 32-bit pass does not even form it -- see below.
   const bool live = bpmax > s.plast;
-  CT cf[kPixPer];
   uint32_t sg = 0;
   const CT* coef = reinterpret_cast<const CT*>(b.coef) + c * b.coefStride;
   const uint64_t* sign = b.sign + c * b.signStride;
+  // 32-bit pass: the magnitudes TRANSPOSED (pix_planes.h) -- P holds plane j in its low and plane j + 16 in its high
+  // half, bit k: sample k.  Bit pl of the 16 magnitudes, which the refinement pass writes, is then a register's half, not
+  // 16 shifts; the samples whose msb is above / at the plane follow from the planes above it (pix_msb_step) in three
+  // operations, where the bit-sliced msb + 1 took a comparison of seven masks; and the magnitudes themselves, 16
+  // registers that lived through the whole plane loop for the sake of those shifts, are gone once P is built.
+  // 64-bit pass (64 planes would be 32 registers): the magnitudes and the bit-sliced msb + 1, as before.
+  uint32_t P[kPlanes ? 16 : 1];
+  CT cf[kPlanes ? 1 : kPixPer];
+  uint32_t M[kPlanes ? 1 : 7];
+  if constexpr (kPlanes) {
 #pragma unroll
-  for (int k = 0; k < kPixPer; k++) {
-    m[k] = -1;
-    cf[k] = (CT)0;
+    for (int k = 0; k < 16; k++)
+      P[k] = 0;
+    if (live) {
+#if EMIT_PIX_OFF & 1
+#pragma unroll
+      for (int k = 0; k < kPixPer; k++) {
+        const uint32_t h = (i0 + k) * 2654435761u, top = (B[0] >> k & 1u) | (B[1] >> k & 1u) << 1 | (B[2] >> k & 1u) << 2 |
+                                                         (B[3] >> k & 1u) << 3 | (B[4] >> k & 1u) << 4 | (B[5] >> k & 1u) << 5;
+        P[k] = top ? (h >> 7) & (0xffffffffu >> (32u - min(top, 32u))) : 0u;
+      }
+      sg = i0 * 40503u;
+#else
+      if (i0 < n)   // kPixPer divides 64: the signs of the thread's samples sit in one word
+        sg = (uint32_t)(sign[i0 >> 6] >> (i0 & 63));
+      if (i0 + kPixPer <= n) {   // (chunk buffers start on 256 bytes and their stride is a multiple of 64 samples)
+#pragma unroll
+        for (int k = 0; k < kPixPer; k += 4) {
+          const uint4 q = *reinterpret_cast<const uint4*>(coef + i0 + k);
+          P[k] = q.x;
+          P[k + 1] = q.y;
+          P[k + 2] = q.z;
+          P[k + 3] = q.w;
+        }
+      }
+      else {
+#pragma unroll
+        for (int k = 0; k < kPixPer; k++)
+          P[k] = (i0 + k < n) ? coef[i0 + k] : 0u;
+      }
+#endif
+      pix_transpose16(P);
+    }
+    else
+      bpmax = -1;   // (takes no part in the plane loop)
   }
-  if (live) {
-    load_pix(b.msb + c * b.pixStride, i0, n, m);
-    if (i0 < n)   // kPixPer divides 64: the signs of the thread's samples sit in one word
-      sg = (uint32_t)(sign[i0 >> 6] >> (i0 & 63));
-#pragma unroll
-    for (int k = 0; k < kPixPer; k++)
-      cf[k] = (i0 + k < n) ? coef[i0 + k] : (CT)0;
-  }
-  else
-    bpmax = -1;   // (takes no part in the plane loop)
-  // The thread's 16 samples BIT-SLICED (round 3): bit k of M[j] / B[j] = bit j of msb + 1 / birth plane + 1
-  // of sample k.  "msb above plane p", "msb equal to p", "born above p" for all 16 samples are then a
-  // dozen logic operations on 16-bit masks per plane instead of a chain of compares, shifts and
-  // adds per sample and plane.  (Measured on MI355X, 64 chunks of 256^3: the kernel takes 2.3 ms to
-  // load its samples and 3.7 ms for the plane loop; two planes per round, plain stores for the
-  // stream words a tile owns, LDS-only barriers and this took the loop from 4.1 ms -- what it waits
-  // for is the block scan and the three barriers of a round at four workgroups per CU.)
-  uint32_t M[7], B[7];
-#pragma unroll
-  for (int j = 0; j < 7; j++) {
-    M[j] = B[j] = 0;
+  else {
+    int m[kPixPer];
 #pragma unroll
     for (int k = 0; k < kPixPer; k++) {
-      M[j] |= (((uint32_t)(m[k] + 1) >> j) & 1u) << k;
-      B[j] |= (((uint32_t)(bp[k] + 1) >> j) & 1u) << k;
+      m[k] = -1;
+      cf[k] = (CT)0;
+    }
+    if (live) {
+      if (i0 < n)
+        sg = (uint32_t)(sign[i0 >> 6] >> (i0 & 63));
+#pragma unroll
+      for (int k = 0; k < kPixPer; k++) {
+        cf[k] = (i0 + k < n) ? coef[i0 + k] : (CT)0;
+        m[k] = cf[k] ? 63 - __clzll((long long)cf[k]) : -1;
+      }
+    }
+    else
+      bpmax = -1;
+#pragma unroll
+    for (int j = 0; j < 7; j++) {
+      M[j] = 0;
+#pragma unroll
+      for (int k = 0; k < kPixPer; k++)
+        M[j] |= (((uint32_t)(m[k] + 1) >> j) & 1u) << k;
     }
   }
-  // masks of the samples whose value (given bit-sliced in X) is above / equal to t - 1, t in 1 .. 64
-  auto above_equal = [](const uint32_t (&X)[7], uint32_t t, uint32_t& gt, uint32_t& eq) {
+  // masks of the samples whose value (given bit-sliced in X) is above / equal to t - 1, t in 1 .. 2^NB
+  auto above_equal = [](const auto& X, uint32_t t, uint32_t& gt, uint32_t& eq) {
+    constexpr int NB = (int)(sizeof(X) / sizeof(X[0]));
     gt = 0;
     eq = 0xffffu;
 #pragma unroll
-    for (int j = 6; j >= 0; j--) {
+    for (int j = NB - 1; j >= 0; j--) {
       if ((t >> j) & 1u)   // (uniform)
         eq &= X[j];
       else {
@@ -1596,58 +1682,28 @@ __global__ void __launch_bounds__(kThreads) k_emit_pixels(EncBuffers b)
       }
     }
   };
-  // bits of `val` at the set positions of `mask`, packed (16-bit pext, a nibble at a time through a table)
-  __shared__ uint8_t pextLut[16][16];
-  {
-    const uint32_t mk = threadIdx.x >> 4, vl = threadIdx.x & 15u;
-    uint32_t r = 0, o = 0;
-    for (int i = 0; i < 4; i++)
-      if ((mk >> i) & 1u) {
-        r |= ((vl >> i) & 1u) << o;
-        o++;
-      }
-    pextLut[mk][vl] = (uint8_t)r;   // (kThreads == 256: one entry per thread)
-  }
-  static_assert(kThreads == 256, "one pext table entry per thread");
-  auto pext16 = [&](uint32_t val, uint32_t mask) -> uint32_t {
-    uint32_t r = 0, sh = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint32_t mn = (mask >> (4 * i)) & 15u;
-      r |= (uint32_t)pextLut[mn][(val >> (4 * i)) & 15u] << sh;
-      sh += (uint32_t)__popc(mn);
-    }
-    return r;
-  };
-  // the LIP scan's and the refinement pass's bits of the thread's samples on plane pl
-  auto plane_bits = [&](int pl, bool withRef, uint32_t& lbits, uint32_t& lval, uint32_t& rbits, uint32_t& rval) {
-    uint32_t gtM, eqM, gtB, eqB;
-    above_equal(M, (uint32_t)pl + 1u, gtM, eqM);
+  // the nibble tables of pix_planes.h: 16-bit pext, and the LIP tokens with a sign behind every '1'
+  __shared__ uint8_t pextLut[256], signLut[256];
+  pextLut[threadIdx.x] = pix_pext_entry(threadIdx.x >> 4, threadIdx.x & 15u);   // (kThreads == 256: one entry per thread)
+  signLut[threadIdx.x] = pix_sign_entry(threadIdx.x >> 4, threadIdx.x & 15u);
+  static_assert(kThreads == 256, "one table entry per thread");
+  // The LIP scan's and the refinement pass's bits of the thread's samples on plane pl, given the samples whose msb is
+  // above the plane (gtM) and at it (eqM) and the plane's bits of the magnitudes (cbit).
+  auto plane_bits = [&](int pl, uint32_t gtM, uint32_t eqM, uint32_t cbit, bool withRef, uint32_t& lbits, uint32_t& lval,
+                        uint32_t& rbits, uint32_t& rval) {
+    uint32_t gtB, eqB;
     above_equal(B, (uint32_t)pl + 1u, gtB, eqB);
     const uint32_t inLip = gtB & ~gtM;        // born above the plane, msb not above it: one '0' or '1' + sign
     lbits = lval = rbits = rval = 0;
     if (inLip) {
-      const uint32_t nl = (uint32_t)__popc(inLip);
-      uint32_t tok = pext16(eqM, inLip);      // token i is '1' (found significant) ...
-      uint32_t sgn = pext16(sg, inLip);       // ... and then its sign follows
-      lbits = nl;
-      lval = tok;
-      // a sign bit behind every '1', from the last token down (what lies below stays where it is)
-      for (uint32_t rest = tok; rest;) {
-        const uint32_t i = 31u - (uint32_t)__clz((int)rest);   // token index
-        rest &= ~(1u << i);
-        const uint32_t low = lval & ((2u << i) - 1u);             // tokens 0 .. i as they stand
-        lval = low | (((sgn >> i) & 1u) << (i + 1)) | ((lval >> (i + 1)) << (i + 2));
-        lbits++;
-      }
+      const uint32_t tok = pix_pext16(pextLut, eqM, inLip);   // token i is '1' (found significant) ...
+      lbits = (uint32_t)__popc(inLip) + (uint32_t)__popc(tok);
+      if (tok)                                                // ... and then its sign follows
+        lval = pix_sign_expand(signLut, tok, pix_pext16(pextLut, sg, inLip));
     }
     if (withRef && gtM) {
-      uint32_t cbit = 0;   // bit pl of the samples' magnitudes
-#pragma unroll
-      for (int k = 0; k < kPixPer; k++)
-        cbit |= (uint32_t)((cf[k] >> pl) & 1) << k;
       rbits = (uint32_t)__popc(gtM);
-      rval = pext16(cbit, gtM);
+      rval = pix_pext16(pextLut, cbit, gtM);
     }
   };
   const uint32_t* cnt = b.pixCnt + c * b.pixCntStride;
@@ -1673,29 +1729,78 @@ __global__ void __launch_bounds__(kThreads) k_emit_pixels(EncBuffers b)
   __shared__ uint64_t sm64[kThreads / 64 + 1];
   __syncthreads();
   // Two planes per round (round 3): their four bit counts share one block scan, which halves the
-  // barriers per plane.
+  // barriers per plane.  (Measured on MI355X, 64 chunks of 256^3, before the plane masks: the kernel took 2.3 ms to load
+  // its samples and 3.7 ms for the plane loop; two planes per round, plain stores for the stream words a tile owns and
+  // LDS-only barriers had taken the loop from 4.1 ms -- at the five workgroups per CU its 94 registers allowed.  With the
+  // plane masks: 72 registers, seven workgroups per CU, 3.9 ms a step in all, of which 0.5 ms to load and transpose and
+  // 2.9 ms the threads' bits of a plane with their deposit; profiles/emit_pixels_ab.txt, DESIGN.md sections 3 and 5.)
+  auto uni32 = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  auto uni64 = [&](uint64_t v) { return (uint64_t)uni32((uint32_t)v) | ((uint64_t)uni32((uint32_t)(v >> 32)) << 32); };
+  uint32_t gt = 0;   // (32-bit pass) the samples whose msb is above the round's first plane: none above the chunk's top plane
   for (int p = nbp - 1; p >= plast; p -= 2) {
     const int q = p - 1;                       // the round's second plane, if there is one
     const bool two = q >= plast;
-    const uint32_t nlipA = tcnt[p * 2], nrefA = tcnt[p * 2 + 1];
-    const uint32_t nlipB = two ? tcnt[q * 2] : 0u, nrefB = two ? tcnt[q * 2 + 1] : 0u;
+    uint32_t gtA = 0, eqA = 0, cA = 0, gtB2 = 0, eqB2 = 0, cB = 0;
+    if constexpr (kPlanes) {
+      // (every round, also the ones the tile skips: gt runs down the planes)
+      cA = pix_plane(P, p);
+      cB = pix_plane(P, q);   // (q = -1 behind the last plane: some plane, not used)
+      gtA = gt;
+      pix_msb_step(cA, gt, eqA);
+      gtB2 = gt;
+      pix_msb_step(cB, gt, eqB2);
+    }
+    // (what every lane reads from the same LDS address belongs in scalar registers: twelve vector registers otherwise)
+    const uint32_t nlipA = uni32(tcnt[p * 2]), nrefA = uni32(tcnt[p * 2 + 1]);
+    const uint32_t nlipB = two ? uni32(tcnt[q * 2]) : 0u, nrefB = two ? uni32(tcnt[q * 2 + 1]) : 0u;
     if ((nlipA | nrefA | nlipB | nrefB) == 0)
       continue;  // uniform across the block
     uint32_t lbA = 0, lvA = 0, rbA = 0, rvA = 0, lbB = 0, lvB = 0, rbB = 0, rvB = 0;   // at most 2 and 1 bits per sample
+#if !(EMIT_PIX_OFF & 2)
     if (q < bpmax) {   // (a sample takes part from its birth plane on: most threads hold none yet)
-      plane_bits(p, nrefA != 0, lbA, lvA, rbA, rvA);
-      if (two)
-        plane_bits(q, nrefB != 0, lbB, lvB, rbB, rvB);
+      // (the loop's own values of B and sg: left to itself the compiler keeps every ~B[j] and the four nibbles of sg in
+      //  registers of their own across the whole loop, ten registers for five operations a plane)
+#pragma unroll
+      for (int j = 0; j < kBirthBits; j++)
+        asm volatile("" : "+v"(B[j]));
+      asm volatile("" : "+v"(sg));
+      if constexpr (!kPlanes) {
+        above_equal(M, (uint32_t)p + 1u, gtA, eqA);
+        if (nrefA && gtA) {
+#pragma unroll
+          for (int k = 0; k < kPixPer; k++)
+            cA |= (uint32_t)((cf[k] >> p) & 1) << k;
+        }
+      }
+      plane_bits(p, gtA, eqA, cA, nrefA != 0, lbA, lvA, rbA, rvA);
+      if (two) {
+        if constexpr (!kPlanes) {
+          above_equal(M, (uint32_t)q + 1u, gtB2, eqB2);
+          if (nrefB && gtB2) {
+#pragma unroll
+            for (int k = 0; k < kPixPer; k++)
+              cB |= (uint32_t)((cf[k] >> q) & 1) << k;
+          }
+        }
+        plane_bits(q, gtB2, eqB2, cB, nrefB != 0, lbB, lvB, rbB, rvB);
+      }
     }
+#endif
     if (!nrefA)
       rbA = 0;
     if (!nrefB)
       rbB = 0;
     uint64_t total;
+#if EMIT_PIX_OFF & 4
+    const uint64_t ex = (uint64_t)threadIdx.x * 0x0010002000100020ull;
+    total = 0;
+#else
     const uint64_t ex = block_exclusive_scan_lds<uint64_t>((uint64_t)lbA | ((uint64_t)rbA << 16) | ((uint64_t)lbB << 32) |
                                                            ((uint64_t)rbB << 48), sm64, &total);
-    const uint64_t lipBaseA = tbase[p * 2], refBaseA = tbase[p * 2 + 1];
-    const uint64_t lipBaseB = two ? tbase[q * 2] : 0ull, refBaseB = two ? tbase[q * 2 + 1] : 0ull;
+#endif
+    const uint64_t lipBaseA = uni64(tbase[p * 2]), refBaseA = uni64(tbase[p * 2 + 1]);
+    const uint64_t lipBaseB = two ? uni64(tbase[q * 2]) : 0ull, refBaseB = two ? uni64(tbase[q * 2 + 1]) : 0ull;
+#if !(EMIT_PIX_OFF & 8)
     auto deposit = [&](unsigned long long* w, uint32_t val, uint32_t nbits, uint32_t at) {
       atomicOr(&w[at >> 6], (unsigned long long)val << (at & 63));
       if ((at & 63) + nbits > 64)
@@ -1741,6 +1846,10 @@ __global__ void __launch_bounds__(kThreads) k_emit_pixels(EncBuffers b)
       flush(refw2, refBaseB, nrefB);
     }
     LDS_ONLY_BARRIER();   // (not __syncthreads(): that would wait for the words on their way to the stream)
+#else
+    if (total == 0x123456789ull + lipBaseA + refBaseA + lipBaseB + refBaseB + ex + lvA + rvA + lvB + rvB)   // (keeps what was computed alive)
+      stream[0] = ex;
+#endif
   }
 }
 
