@@ -448,7 +448,7 @@ int orc_quantize(const double* vals, size_t n, double q, uint64_t* coeffs, uint6
     if (!(a <= maxabs))
       maxabs = a; /* NaN would stick; the reference returns FE_Invalid in that case */
   }
-  if (!(maxabs / q < 9.2e18)) /* llrint would raise FE_INVALID (SPECK_FLT.cpp:323-327) */
+  if (!(maxabs / q < 0x1p63)) /* llrint would raise FE_INVALID (SPECK_FLT.cpp:323-327): from 2^63 on */
     return 7;                 /* RTNType::FE_Invalid (include/sperr_helper.h:54-64) */
   const long long maxll = llrint(maxabs / q);
   *width = maxll <= 0xff ? 1 : maxll <= 0xffff ? 2 : maxll <= 0xffffffffLL ? 4 : 8;
@@ -1719,7 +1719,7 @@ int orc_speck2d_decode(const uint8_t* stream, size_t len, size_t dx, size_t dy, 
 /* ------------------------------------------------------------------------------------------ */
 
 /* src/Outlier_Coder.cpp:71-129,179-197 : errors in units of the tolerance, rounded to nearest;
- * pos[] ascending.  Returns 1 on a bad list (an error within the tolerance). */
+ * pos[] ascending.  Returns 1 on a bad list (an error within the tolerance), 7 where the reference refuses. */
 int orc_outlier_encode(const uint64_t* pos, const double* err, size_t count, size_t n, double tol,
                        uint8_t** stream, size_t* stream_len)
 {
@@ -1728,6 +1728,12 @@ int orc_outlier_encode(const uint64_t* pos, const double* err, size_t count, siz
   for (size_t k = 0; k < count; k++)
     if (pos[k] >= n || fabs(err[k]) <= tol)
       return 1;
+  double maxerr = 0.0; /* the reference sizes its integers by llrint of the largest ERROR, not of error / tol,  */
+  for (size_t k = 0; k < count; k++) /* and refuses when that raises FE_INVALID (Outlier_Coder.cpp:82-91) */
+    if (!(fabs(err[k]) <= maxerr))
+      maxerr = fabs(err[k]);
+  if (!(maxerr < 0x1p63))
+    return 7; /* RTNType::FE_Invalid */
   uint64_t* coef = (uint64_t*)calloc(n, sizeof(uint64_t));
   uint64_t* sign = (uint64_t*)malloc(((n + 63) / 64) * 8);
   memset(sign, 0xff, ((n + 63) / 64) * 8);

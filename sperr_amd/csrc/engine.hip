@@ -1563,8 +1563,8 @@ int psnr_q_search(hipStream_t st, const ShapePlan& P, EncBatchBufs& bb, uint32_t
     if (c.is_const)
       continue;
     const double m = c.maxabs / c.q;
-    if (!(m < 9.3e18))
-      return -1;   // llrint would raise FE_INVALID (SPECK_FLT.cpp:325-327)
+    if (!(m < 0x1p63))
+      return -1;   // llrint would raise FE_INVALID (SPECK_FLT.cpp:323-327): exactly from 2^63 on, and for a NaN
     c.need_retry = std::llrint(m) > (long long)0xffffffffll ? 1u : 0u;
   }
   HIP_CHECK(hipMemcpyAsync(e.cst, hc.data(), nb * sizeof(CoderState), hipMemcpyHostToDevice, st));
@@ -1606,8 +1606,8 @@ int pwe_q_setup(hipStream_t st, EncBatchBufs& bb, uint32_t nb, double tol, std::
       continue;
     c.q = 1.5 * tol;
     const double m = c.maxabs / c.q;
-    if (!(m < 9.3e18))
-      return -1;   // llrint would raise FE_INVALID (SPECK_FLT.cpp:325-327)
+    if (!(m < 0x1p63))
+      return -1;   // llrint would raise FE_INVALID (SPECK_FLT.cpp:323-327): exactly from 2^63 on, and for a NaN
     c.need_retry = std::llrint(m) > (long long)0xffffffffll ? 1u : 0u;
     if (anyWide && c.need_retry)
       *anyWide = true;   // (this mode chooses the width before coding: nothing else sets the flag, k_enc_finalize)
@@ -1800,8 +1800,8 @@ int pwe_stage_finish(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs
     // from the largest magnitude (Outlier_Coder.cpp:82-100); magnitudes wrap to that width
     double maxerr;
     memcpy(&maxerr, &o.maxErrKey, 8);
-    if (!(maxerr < 9.2e18))
-      return -1;
+    if (!(maxerr < 0x1p63))
+      return -1;   // llrint would raise FE_INVALID (Outlier_Coder.cpp:88-91): the reference refuses the chunk
     const long long mi = std::llrint(maxerr);
     o.widthMask = mi <= 0xffll ? 0xffull : mi <= 0xffffll ? 0xffffull : mi <= 0xffffffffll ? 0xffffffffull : ~0ull;
   }

@@ -4,8 +4,11 @@ recorded from it (tests/refbits.py, tests/golden/ref_digests.json)."""
 import numpy as np
 import pytest
 
-from fields import ramp_field, smooth_field
+from fields import (COEF_BUDGETS, COEF_PATTERNS, COEF_SHAPES, VALUE_DOMAIN_CASES, VD_SHAPE, cached_value_domain_fields,
+                    coefficient_pattern, ramp_field, smooth_field, value_domain_plane, value_domain_refused,
+                    value_domain_settings)
 from refbits import same
+from sperr_amd.farm import split_container
 from sperr_amd.synth import turbulence
 
 SHAPES = [(17, 17, 17), (32, 32, 32), (23, 45, 70), (41, 64, 64), (9, 40, 48), (64, 64, 64)]
@@ -224,3 +227,87 @@ def test_integer_len_rule_matches_the_reference(oracle, ref):
         assert same(0, rc) and same(rule, w0) and same(rule, w1)
         seen.add(rule)
     assert seen == {1, 2, 4, 8}
+
+
+# ---- value domains (tests/fields.py: value_domain_fields, coefficient_pattern) -----------------------------------
+
+
+def chunk_planes(container):
+    """byte 17 of every chunk stream that has one (a constant chunk's stream is its 17-byte conditioner header)"""
+    return [p[17] for p in split_container(container)[3] if len(p) > 17]
+
+
+@pytest.mark.parametrize("name,dtype", VALUE_DOMAIN_CASES)
+def test_value_domain_containers_bit_exact(oracle, ref, name, dtype):
+    """One-signed, offset, scaled, subnormal, sparse, discontinuous and mixed-range volumes, as one chunk and in 16^3
+    chunks, three rates, two PSNR targets and two tolerances: the container, both decodes, and in mode 3 the
+    tolerance on the reference's fp64 decode.  No PSNR target or tolerance reaches the regime of more than 53 bit
+    planes, where the oracle is not pinned to the reference."""
+    v = cached_value_domain_fields(VD_SHAPE, dtype)[name]
+    v64 = v.astype(np.float64)
+    for chunks in (v.shape[::-1], (16, 16, 16)):
+        for mode, q in value_domain_settings(name, v):
+            so = oracle.comp_3d(v, chunks, mode, q)
+            assert same(so, ref.get(lambda r: r.comp_3d(v, chunks, mode, q))), (chunks, mode, q)
+            if mode != 1:   # (a rate that 32 planes cannot fill makes the reference itself re-quantise for 53 or 54)
+                assert max(chunk_planes(so), default=0) <= 53, (chunks, mode, q)
+            dec = oracle.decomp_3d(so, False)
+            assert same(bits(dec), ref.get(lambda r: r.decomp_3d(so, False))), (chunks, mode, q)
+            assert same(bits(oracle.decomp_3d(so, True)), ref.get(lambda r: r.decomp_3d(so, True))), (chunks, mode, q)
+            if mode == 3:   # (dec has the bits of the reference's fp64 decode: asserted just above)
+                assert np.abs(dec - v64).max() <= q, (chunks, q)
+        for mode, q in value_domain_refused(name, v):   # (the reference does not survive its own refusal here)
+            assert refuses(lambda: oracle.comp_3d(v, chunks, mode, q)), (chunks, mode, q)
+
+
+def refuses(call):
+    try:
+        call()
+    except RuntimeError:
+        return True
+    return False
+
+
+@pytest.mark.parametrize("name,dtype", VALUE_DOMAIN_CASES)
+def test_value_domain_2d_slices_bit_exact(oracle, ref, name, dtype):
+    img, settings, refused = value_domain_plane(name, dtype)
+    for mode, q in refused:   # (sperr_comp_2d hands the refusal back as an error code)
+        assert refuses(lambda: oracle.comp_2d(img, mode, q, False))
+        assert same(True, ref.get(lambda r: refuses(lambda: r.comp_2d(img, mode, q, False))))
+    for mode, q in settings:
+        for hdr in (False, True):
+            got = oracle.comp_2d(img, mode, q, hdr)
+            assert same(got, ref.get(lambda r: r.comp_2d(img, mode, q, hdr))), (mode, q, hdr)
+        body = got[10:]
+        assert mode == 1 or len(body) == 17 or body[17] <= 53
+        for as_float in (True, False):
+            assert same(bits(oracle.decomp_2d(body, img.shape, as_float)),
+                        ref.get(lambda r: r.decomp_2d(body, img.shape, as_float))), (mode, q, as_float)
+
+
+@pytest.mark.parametrize("pattern", COEF_PATTERNS)
+def test_value_domain_speck_patterns_bit_exact(oracle, ref, pattern):
+    """The SPECK stage on the extremes of occupancy: every coefficient significant on the first plane (32 and 53 bits
+    deep), one coefficient in the whole array (first, last), one bit per coefficient, a geometric fall-off."""
+    for shape in COEF_SHAPES:
+        coef, sign, _ = coefficient_pattern(pattern, shape)
+
+        def sign_bits(words):   # the signs of the nonzero coefficients only
+            return (words[idx >> 6] >> (idx & 63).astype(np.uint64)) & np.uint64(1)
+
+        for budget in COEF_BUDGETS:
+            so = oracle.speck3d_encode(coef, sign, budget)
+            assert same(so, ref.get(lambda r: r.speck3d_encode(coef, sign, budget, width=8))), (shape, budget)
+            for cut in (len(so), 9 + (len(so) - 9) // 2, 9 + (len(so) - 9) // 7):
+                co, sgo = oracle.speck3d_decode(so[:cut], shape)
+                idx = np.nonzero(co.reshape(-1) != 0)[0]
+
+                def ref_decode(r):
+                    c, s = r.speck3d_decode(so[:cut], shape)
+                    return c, sign_bits(s)
+
+                cr, br = ref.get(ref_decode)
+                assert same(co, cr), (shape, budget, cut)
+                assert same(sign_bits(sgo), br), (shape, budget, cut)
+                if budget == 0 and cut == len(so):   # the whole stream gives the coefficients back
+                    assert np.array_equal(co, coef) and np.array_equal(sign_bits(sgo), sign_bits(sign)), shape
