@@ -296,8 +296,10 @@ struct ShapePlan {
   uint64_t maxPhaseBits = 0;
   size_t lisEntries = 0;
   std::vector<LiftPass> fwd;
+  bool level2 = false;   // passes 3 to 5 -- the second level -- run as one launch each way (plan_level2)
 };
 bool use_tables(const ShapePlan& P);   // (defined with the decoder's plan logic below)
+bool plan_level2(const ShapePlan& P);  // (defined with the transform's plan logic below)
 
 
 // The encoder's fused head (k_head_fused, speck_enc.hip) wants workgroups that own whole pixel tiles AND whole leaf sets:
@@ -529,6 +531,7 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
       P.fwd.push_back({1, {approx(dx, lev), approx(dy, lev), (uint32_t)dz}});
     }
   }
+  P.level2 = plan_level2(P);
   return 0;
 }
 
@@ -1432,12 +1435,58 @@ bool plan_fusable(const ShapePlan& P)
   return true;
 }
 
+// Can the SECOND level of this shape run as one launch each way (k_lift2_fwd / k_lift2_inv, xform.h) instead of three
+// per-axis passes?  Passes 3, 4 and 5 have to be x, y and z of one region -- the low halves the fused finest-level kernel
+// leaves --, the region has to fit the sliding-window kernels with rows of at most 128 samples, and the passes have to
+// nest (plan_fusable: the kernels tell the box's samples from the others by LiftFuse::inner).
+static bool level2_fits(const ShapePlan& P)
+{
+  if (!fuse_xyz(P) || !plan_fusable(P) || P.fwd.size() < 6)
+    return false;
+  for (int k = 3; k < 6; k++) {
+    if (P.fwd[k].axis != k - 3)
+      return false;
+    for (int a = 0; a < 3; a++)
+      if (P.fwd[k].region[a] != P.dims[a] - P.dims[a] / 2)
+        return false;
+  }
+  uint32_t inner[3];
+  if (pass_fuse(P, 2, inner) <= 0 || inner[0] != P.fwd[3].region[0] || inner[1] != P.fwd[3].region[1] ||
+      inner[2] != P.fwd[3].region[2])
+    return false;
+  return lift2_applicable(P.fwd[3].region);
+}
+// Does it?  Decided once, when the plan is made: the encoder's launches (float_stages) and the decoder's memory layout
+// and launches (decode_group, enqueue_inverse) follow it.  By default only where the region has at least kLevel2Floor
+// samples along every axis, in both directions alike, because that is where it was measured to gain
+// (profiles/level2_fused_ab.txt): at 128^3 (256^3 chunks) decompression gains 1.8 % run against run; at 64^3, 32^3 and
+// 16^3 (128^3, 64^3, 32^3 chunks, 64 and 512 of them) compress and decompress times with and without it lie inside
+// each other's spread -- the launch is no slower there, the march through the slices costs what the three launches
+// cost -- with one exception, 512 chunks of 32^3, which decode 3 to 4 % faster with it.  A gain that cannot be told
+// from the spread is not taken: the small shapes keep the launches they had, which tests/test_gpu_level.py pins launch
+// by launch for 32^3 chunks (with the launch on, those tables would have to change: 12 k_lift_axis<false, 0> become 4
+// k_lift2_inv<true>; the 32^3 decode gain above is what that would buy).  Nothing between 64 and 128 was measured; the
+// floor sits midway.
+// SPERR_HIP_XYZ_LEVEL2=0: the three passes everywhere, for A/B runs and tests; =2: the launch wherever it fits, for the
+// same (the tests put every shape the kernels can go wrong at through them this way).  Read whenever a plan is made:
+// sperrhip_release() drops the plans.
+constexpr uint32_t kLevel2Floor = 96;
+bool plan_level2(const ShapePlan& P)
+{
+  const char* env = getenv("SPERR_HIP_XYZ_LEVEL2");
+  const int sw = env ? atoi(env) : 1;
+  if (sw == 0 || !level2_fits(P))
+    return false;
+  const uint32_t* r = P.fwd[3].region;
+  return sw == 2 || std::min(r[0], std::min(r[1], r[2])) >= kLevel2Floor;
+}
+
 // conditioner + forward transform of one batch: volume -> bb.vals (mean, constness, largest magnitude
 // in CoderState).  Run once per batch -- and once more before a 64-bit retry when the coder's arrays
 // lay over the chunk buffer (carve_enc): the same launches on the same input give the same bits.
 template <typename T>
 int float_stages(hipStream_t ss, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb, const uint32_t cd[3],
-                 const T* d_src, VolDesc vd, bool orgAligned, bool wantRange)
+                 const T* d_src, VolDesc vd, bool orgAligned, bool wantRange, bool level2 = true)
 {
   EncBuffers& e = bb.eb;
   // the first lifting pass covers the whole chunk: it reads the volume itself (gather, widen,
@@ -1455,10 +1504,27 @@ int float_stages(hipStream_t ss, const ShapePlan& P, EncBatchBufs& bb, uint32_t 
     LiftFuse lf;
     if (fuseMax && pass_fuse(P, 2, lf.inner) > 0)
       lf.mode = 1;
+    // The second level fused (plan_level2): the finest-level kernel writes the next level's box compact into the 32-bit
+    // coefficient array, which only the quantiser writes, after the transform (one sample in eight, 8 of the array's 32 bytes for them); the
+    // level-2 launch reads it and writes the corner of the chunk buffer.  (Not in front of the 64-bit retry: the
+    // chunks that keep their 32-bit coefficients keep them there.)
+    const bool l2 = level2 && P.level2;
+    double* box = l2 ? reinterpret_cast<double*>(bb.coef32) : nullptr;
+    const size_t boxStride = e.coefStride / 2;
+    if (l2 && (e.coefStride % 2 != 0 || (size_t)lf.inner[0] * lf.inner[1] * lf.inner[2] > boxStride))
+      return -1;
     if (launch_lift_xyz(ss, true, bb.vals, bb.valsStride, nb, cd, e.cst, io, const_cast<T*>(d_src), vd,
-                        bb.geom, &lf))
+                        bb.geom, &lf, nullptr, box, boxStride))
       return -1;
     k0 = 3;
+    if (l2) {
+      LiftFuse l5;
+      if (pass_fuse(P, 5, l5.inner) > 0)
+        l5.mode = 1;
+      if (launch_lift2_fwd(ss, box, boxStride, bb.vals, bb.valsStride, nb, cd, P.fwd[3].region, e.cst, &l5))
+        return -1;
+      k0 = 6;
+    }
   }
   else if (fuse_xy(P)) {   // the full-size x and y passes in one kernel, straight from the volume
     if (launch_lift_xy(ss, true, bb.vals, bb.valsStride, nb, cd, e.cst, io, const_cast<T*>(d_src), vd,
@@ -1503,7 +1569,7 @@ int wide_retry_prepare(hipStream_t ss, Engine& E, const ShapePlan& P, EncBatchBu
   if (unalias_coder(ss, E, P, bb, nb))
     return -1;
   g_dbg_counter[0]++;
-  return float_stages<T>(ss, P, bb, nb, cd, d_src, vd, orgAligned, wantRange);
+  return float_stages<T>(ss, P, bb, nb, cd, d_src, vd, orgAligned, wantRange, false);
 }
 
 // PSNR mode (src/SPECK_FLT.cpp:268-279,431-435): per chunk q = 2 sqrt(3 t), t = range^2 10^(-psnr/10),
@@ -2698,6 +2764,7 @@ struct DecBatchBufs {
   uint64_t *chunkOff, *chunkLen;
   double* vals;
   size_t valsStride;
+  double* vals2;    // a second compact box of the same layout: the fused second level writes it (null: no such launch)
   uint32_t* coef32;
   uint32_t* live;   // chunks that still decode (DecPlanHost::d_live)
 };
@@ -2705,8 +2772,9 @@ struct DecBatchBufs {
 // valsElems: fp64 samples per chunk of the chunk buffer (0: the whole chunk; compact_box() otherwise)
 // refNPlanes: refinement bit planes per chunk (DecBuffers::refPlanes; 0: the coefficients are updated plane by plane)
 // crop: a sub-box is decoded (DecBatchBufs::crop)
+// box2: the second level runs fused (Batch::level2): a second compact box
 bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadBytes, DecBatchBufs& o,
-               size_t valsElems = 0, uint32_t refNPlanes = 0, bool crop = false)
+               size_t valsElems = 0, uint32_t refNPlanes = 0, bool crop = false, bool box2 = false)
 {
   const size_t N = P.N, Npad = round_up(N, 512);   // (512: k_ref_assemble takes eight mask words per round)
   DecBuffers& d = o.db;
@@ -2732,6 +2800,10 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   TAKE(o.live, uint32_t, 64);
   o.valsStride = valsElems ? round_up(valsElems, 256) : Npad;
   TAKE(o.vals, double, o.valsStride * B);
+  o.vals2 = nullptr;
+  if (box2 && valsElems) {
+    TAKE(o.vals2, double, o.valsStride * B);
+  }
   d.coefStride = Npad;
   TAKE(o.coef32, uint32_t, Npad * B);
   d.coef = o.coef32;
@@ -3160,13 +3232,14 @@ struct DecodeRequest {
 };
 
 // bytes carve_dec takes for one chunk
-size_t dec_bytes_per_chunk(const ShapePlan& P, uint64_t maxPayload, size_t valsElems, uint32_t refNPlanes, bool crop)
+size_t dec_bytes_per_chunk(const ShapePlan& P, uint64_t maxPayload, size_t valsElems, uint32_t refNPlanes, bool crop,
+                           bool box2 = false)
 {
   Arena probe;
   probe.base = reinterpret_cast<char*>(uintptr_t(4096));  // size probe only
   probe.cap = ~size_t(0) / 2;
   DecBatchBufs tmp;
-  carve_dec(probe, P, 1, maxPayload, tmp, valsElems, refNPlanes, crop);
+  carve_dec(probe, P, 1, maxPayload, tmp, valsElems, refNPlanes, crop, box2);
   return probe.used;
 }
 
@@ -3218,6 +3291,7 @@ struct DecodeCall {
     uint32_t cbox[3], refNPlanes, nsub = 1;
     uint64_t maxPayload = 0;
     size_t compactElems;
+    bool level2 = false;   // passes 5, 4 and 3 as one launch into a second compact box (level2_of)
     bool deferG, fuseDq;
     hipStream_t deferStream = nullptr;
     std::vector<SubHost>* subs = nullptr;
@@ -3432,6 +3506,9 @@ struct DecodeCall {
         cbox[a] = std::max(cbox[a], lvl->m.cres[lvl->h][a]);
     return (size_t)cbox[0] * cbox[1] * cbox[2];
   }
+  // The second level of a group runs as one launch (plan_level2) where the group works in the compact box, whose every
+  // pass dequantises on the way; a single level's decode (enqueue_level) never reaches that launch
+  bool level2_of(const ShapePlan& P, size_t compactElems) const { return P.level2 && compactElems != 0 && !req.level(); }
   // room for all the small groups at once, if the memory is there
   int size_deferred()
   {
@@ -3447,7 +3524,8 @@ struct DecodeCall {
       for (auto& r : h.second)
         mp = std::max<uint64_t>(mp, ci.len[r.gid]);
       uint32_t qbox[3];
-      sum += round_up(h.second.size() * dec_bytes_per_chunk(*Q, mp, compact_box(*Q, h.second, qbox), ref_planes_of(*Q, h.second), req.cropped()) + (1 << 20), 4096);
+      const size_t qelems = compact_box(*Q, h.second, qbox);
+      sum += round_up(h.second.size() * dec_bytes_per_chunk(*Q, mp, qelems, ref_planes_of(*Q, h.second), req.cropped(), level2_of(*Q, qelems)) + (1 << 20), 4096);
     }
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
@@ -3480,7 +3558,8 @@ struct DecodeCall {
     // the inverse passes dequantise on the way (not for the resolution hierarchy, whose coarsest
     // level is read before any pass has run)
     b.fuseDq = plan_fusable(*P) && !req.levels && !req.slices;
-    const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, req.cropped());
+    b.level2 = level2_of(*P, b.compactElems) && b.fuseDq;
+    const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, req.cropped(), b.level2);
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const size_t budgetBytes = arena_budget(E.arena.n, fr);
@@ -3603,7 +3682,7 @@ struct DecodeCall {
       S.nb = (nbAll - done + (nsub - q) - 1) / (nsub - q);
       S.first = b0 + done;
       done += S.nb;
-      if (S.nb && !carve_dec(A, *b.P, S.nb, b.maxPayload, S.bb, b.compactElems, b.refNPlanes, req.cropped()))
+      if (S.nb && !carve_dec(A, *b.P, S.nb, b.maxPayload, S.bb, b.compactElems, b.refNPlanes, req.cropped(), b.level2))
         return -1;
       if (S.nb && b.compactElems)
         g_dbg_counter[2]++;
@@ -3875,7 +3954,10 @@ struct DecodeCall {
         lf.bufy = bbox[1];
       }
     };
-    for (size_t k = P.fwd.size(); k-- > ((fxyz || fbrick) ? 3u : fxy ? 2u : 0u);) {
+    // (the second level fused: its three passes are one launch from the compact box into a second one, which the
+    //  finest level then reads -- in place a tile's outputs would land in rows other tiles still read)
+    const bool l2 = b.level2 && fxyz && bb.vals2 != nullptr;
+    for (size_t k = P.fwd.size(); k-- > (l2 ? 6u : (fxyz || fbrick) ? 3u : fxy ? 2u : 0u);) {
       const LiftPass& ps = P.fwd[k];
       if (k % perLevel == perLevel - 1 && sub_volume(k))
         return -1;
@@ -3897,9 +3979,15 @@ struct DecodeCall {
     if (fxyz) {   // the finest level: z, y and x pass in one kernel, into the volume
       if (sub_volume(2))
         return -1;
+      if (l2) {
+        LiftFuse l5;
+        dequant_fuse(5, l5);
+        if (launch_lift2_inv(ss, bb.vals, bb.valsStride, bb.vals2, bb.valsStride, nb, cd, P.fwd[3].region, d.cst, &l5))
+          return -1;
+      }
       LiftFuse lf;
       dequant_fuse(2, lf);
-      if (launch_lift_xyz(ss, false, bb.vals, bb.valsStride, nb, cd, d.cst, io, d_dst, vd, bb.geom, &lf, bb.crop))
+      if (launch_lift_xyz(ss, false, l2 ? bb.vals2 : bb.vals, bb.valsStride, nb, cd, d.cst, io, d_dst, vd, bb.geom, &lf, bb.crop))
         return -1;
     }
     if (fxy && req.slices && sub_volume(1))   // the finest level of a slice is the fused pair

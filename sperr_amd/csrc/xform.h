@@ -102,7 +102,27 @@ int launch_lift_xy(hipStream_t stream, bool forward, double* vals, size_t valsSt
 bool lift_xyz_applicable(const uint32_t cdims[3]);
 int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsStride, uint32_t nchunks,
                     const uint32_t cdims[3], CoderState* st, int io, void* volume, VolDesc vd,
-                    const ChunkGeom* geom, const LiftFuse* fuse, const CropGeom* crop = nullptr);
+                    const ChunkGeom* geom, const LiftFuse* fuse, const CropGeom* crop = nullptr,
+                    double* box = nullptr, size_t boxStride = 0);
+
+// The SECOND level's x, y and z pass in one launch of the same sliding-window code (k_lift2_fwd / k_lift2_inv), between
+// compact boxes: a box holds `region` -- the finest level's low-low-low octant -- as rows of region[0] samples,
+// region[1] rows a slice, chunk c's `boxStride` samples in.  Neither launch can work in place (a tile's outputs land in
+// rows other tiles still read).
+//   forward: launch_lift_xyz(..., box, boxStride) has written the octant into `box` instead of `vals`; this launch reads
+//            it, nothing subtracted, and writes the corner of `vals` at the chunk's strides, collecting the largest
+//            magnitude outside fuse->inner when fuse->mode == 1.
+//   inverse: the samples inside fuse->inner come from `box` (rows of fuse->bufx samples), every other one from the
+//            coefficients, addressed at the chunk's strides (fuse->mode == 2: dequant.h); the region goes to `out`, no
+//            mean added, where launch_lift_xyz(inverse) takes it as its `vals` with fuse->bufx / bufy = region.
+// Only for regions that pass lift_xyz_applicable and whose rows are at most 128 samples.
+bool lift2_applicable(const uint32_t region[3]);
+int launch_lift2_fwd(hipStream_t stream, const double* box, size_t boxStride, double* vals, size_t valsStride,
+                     uint32_t nchunks, const uint32_t cdims[3], const uint32_t region[3], CoderState* st,
+                     const LiftFuse* fuse);
+int launch_lift2_inv(hipStream_t stream, const double* box, size_t boxStride, double* out, size_t outStride,
+                     uint32_t nchunks, const uint32_t cdims[3], const uint32_t region[3], const CoderState* st,
+                     const LiftFuse* fuse);
 
 // have_max: CoderState::maxabs is already there (the lifting passes collected it)
 int launch_maxabs_q(hipStream_t stream, const double* vals, size_t valsStride, uint32_t nchunks,

@@ -963,17 +963,19 @@ __device__ __forceinline__ void xyz_lift_y(const double* src, double* dst, uint3
   }
 }
 
-template <int IO>
-__global__ void __launch_bounds__(kXYZThreadsF) __attribute__((amdgpu_waves_per_eu(kXYZThreadsF / 256, kXYZThreadsF / 256)))
-k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz, LiftConsts K,
-               CoderState* st, const void* volume, VolDesc vd, const ChunkGeom* geom, int wantMax,
-               uint32_t in0, uint32_t in1, uint32_t in2, uint32_t nseg)
+// The body of the forward kernels: one chunk's tile (and segment) of a workgroup.  `volc`: the chunk's samples, rows vsy
+// and slices vsz apart, `mean` subtracted on the way in; `buf`: where the transformed chunk goes, rows `orow` and slices
+// `sliceN` samples apart.  NPOS / NSTG: z pipelines / staged samples per thread (kXYZRows * cx <= NPOS * threads,
+// kXYZStaged * cx <= NSTG * threads).
+// `box` (not null: the finest level with the second level fused, k_lift2_fwd): the samples of the next level's box --
+// low along x, y and z -- go there instead, rows of in0 samples and in1 rows a slice; L2: the second level itself, which has
+// no box of its own.
+template <typename VT, int NPOS, int NSTG, bool L2>
+__device__ __forceinline__ void xyz_fwd_body(double* buf, const uint32_t orow, const size_t sliceN, uint32_t cx, uint32_t cy,
+                                             uint32_t cz, const LiftConsts& K, CoderState* stc, const VT* volc, const size_t vsy,
+                                             const size_t vsz, const double mean, int wantMax, uint32_t in0, uint32_t in1,
+                                             uint32_t in2, uint32_t nseg, double* box)
 {
-  static_assert(IO == 1 || IO == 2, "float or double volume");
-  using VT = typename std::conditional<IO == 1, float, double>::type;
-  const uint32_t c = blockIdx.y;
-  if (st[c].is_const != 0)
-    return;
   const uint32_t tid = threadIdx.x;
   // A small batch has too few tiles for the device: the slices are then dealt to `nseg` workgroups
   // per tile.  Segment g emits what the even slices 2m, m in [mA, mB), complete (the last one also
@@ -992,54 +994,55 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
   double* sm = reinterpret_cast<double*>(dyn_smem);
   const uint32_t bufN = (uint32_t)kXYZStaged * RS;
   const uint32_t xe = cx - cx / 2, ye = cy - cy / 2, ze = cz - cz / 2;
-  const VT* vol = reinterpret_cast<const VT*>(volume);
-  const size_t vsy = vd.dims[0], vsz = (size_t)vd.dims[0] * vd.dims[1];
-  const VT* volc = vol + ((size_t)geom[c].org[2] * vsz + (size_t)geom[c].org[1] * vsy + geom[c].org[0]);
-  double* buf = vals + c * valsStride;
-  const size_t sliceN = (size_t)cx * cy;
-  const double mean = st[c].mean;
+  const size_t boxSlice = (size_t)in0 * in1;
 
   // staging map: value k of this thread is sample x of LDS row j = row ysrc of the slice:
   // j << 27 | ysrc << 12 | x
   const uint32_t nstage = (uint32_t)kXYZStaged * cx;
-  uint32_t pk[kXYZStageF];
+  uint32_t pk[NSTG];
 #pragma unroll
-  for (int k = 0; k < kXYZStageF; k++) {
+  for (int k = 0; k < NSTG; k++) {
     const uint32_t q = tid + (uint32_t)k * kXYZThreadsF;
     const uint32_t j = q / cx, x = q - j * cx;
     pk[k] = (j << 27) | (reflect_index((int)y0 - kXYHalo + (int)j, (int)cy) << 12) | x;
   }
   // z pipelines: position k of this thread is (row y0 + row, column col) of the tile
   const uint32_t npos = nt * cx;
-  uint32_t srow[kXYZPosF], ooff[kXYZPosF];   // (LDS row << 16 | column), offset in a slice of the chunk buffer
+  uint32_t srow[NPOS], ooff[NPOS];   // (LDS row << 16 | column), offset in a slice of the chunk buffer
+  uint32_t boff[L2 ? 1 : NPOS];          // ... and in a slice of the box
   uint32_t outerMask = 0;   // bit k: position k lies outside the next level's box along x or y
 #pragma unroll
-  for (int k = 0; k < kXYZPosF; k++) {
+  for (int k = 0; k < NPOS; k++) {
     const uint32_t q = tid + (uint32_t)k * kXYZThreadsF;
     const uint32_t row = q / cx, col = q - row * cx, y = y0 + row;
     srow[k] = ((row + kXYHalo) << 16) | col;
     const uint32_t drow = (y & 1) ? ye + (y >> 1) : (y >> 1), dcol = (col & 1) ? xe + (col >> 1) : (col >> 1);
-    ooff[k] = drow * cx + dcol;
+    ooff[k] = drow * orow + dcol;
+    if constexpr (!L2)
+      boff[k] = drow * in0 + dcol;
     if (!(dcol < in0 && drow < in1))
       outerMask |= 1u << k;
   }
-  double sxe[kXYZPosF], sxo[kXYZPosF], d1p[kXYZPosF], e1p[kXYZPosF], d2p[kXYZPosF];
+  double sxe[NPOS], sxo[NPOS], d1p[NPOS], e1p[NPOS], d2p[NPOS];
 #pragma unroll
-  for (int k = 0; k < kXYZPosF; k++)
+  for (int k = 0; k < NPOS; k++)
     sxe[k] = sxo[k] = d1p[k] = e1p[k] = d2p[k] = 0.0;
   double vmax = 0.0;
   auto emit = [&](int k, uint32_t zp, double v) {   // sample (ooff, zp) of the transformed chunk
-    if (!xyz_off<XYZ_FWD_OFF>(4, nseg))
-      buf[(size_t)zp * sliceN + ooff[k]] = v;
+    bool toBox = false;
+    if constexpr (!L2)
+      toBox = box != nullptr && zp < in2 && !((outerMask >> k) & 1u);
+    if (!xyz_off<XYZ_FWD_OFF>(4, nseg))   // (one store, its address chosen)
+      *(toBox ? box + ((size_t)zp * boxSlice + boff[L2 ? 0 : k]) : buf + ((size_t)zp * sliceN + ooff[k])) = v;
     if (wantMax && (((outerMask >> k) & 1u) || zp >= in2))
       vmax = fmax(vmax, fabs(v));
   };
 
-  VT pre[kXYZStageF];
+  VT pre[NSTG];
   auto issue = [&](uint32_t z) {
     const VT* src = volc + (size_t)z * vsz;
 #pragma unroll
-    for (int k = 0; k < kXYZStageF; k++) {
+    for (int k = 0; k < NSTG; k++) {
       if (xyz_off<XYZ_FWD_OFF>(1, nseg)) {   // (noise instead of the volume: the coder gets something to code)
         pre[k] = (VT)(((pk[k] + z * 40503u) * 2654435761u) >> 20);
       }
@@ -1056,15 +1059,20 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
     uint32_t RSv = RS, tidv = tid;
     asm volatile("" : "+s"(RSv), "+v"(tidv));
 #pragma unroll
-    for (int k = 0; k < kXYZStageF; k++)
+    for (int k = 0; k < NSTG; k++)
       asm volatile("" : "+v"(pk[k]));
 #pragma unroll
-    for (int k = 0; k < kXYZPosF; k++)
+    for (int k = 0; k < NPOS; k++)
       asm volatile("" : "+v"(srow[k]), "+v"(ooff[k]));
+    if constexpr (!L2) {
+#pragma unroll
+      for (int k = 0; k < NPOS; k++)
+        asm volatile("" : "+v"(boff[k]));
+    }
     double* A = sm + ((z & 1) ? bufN : 0u);
     double* B = sm + ((z & 1) ? 0u : bufN);
 #pragma unroll
-    for (int k = 0; k < kXYZStageF; k++)
+    for (int k = 0; k < NSTG; k++)
       if ((tid + (uint32_t)k * kXYZThreadsF) < nstage)
         xyz_put(A + (pk[k] >> 27) * RSv, pk[k] & 0xfffu, cx, (double)pre[k] - mean);
     if (z + 1 < zEnd)
@@ -1081,13 +1089,13 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
       continue;
     if (z & 1) {
 #pragma unroll
-      for (int k = 0; k < kXYZPosF; k++)
+      for (int k = 0; k < NPOS; k++)
         if ((tid + (uint32_t)k * kXYZThreadsF) < npos)
           sxo[k] = A[(srow[k] >> 16) * RSv + 4 + (srow[k] & 0xffffu)];
     }
     else {
 #pragma unroll
-      for (int k = 0; k < kXYZPosF; k++) {
+      for (int k = 0; k < NPOS; k++) {
         if ((tid + (uint32_t)k * kXYZThreadsF) >= npos)
           continue;
         const double v = A[(srow[k] >> 16) * RSv + 4 + (srow[k] & 0xffffu)];
@@ -1112,7 +1120,7 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
   }
   // ---- the end of the lines: the samples still in the pipelines (the last segment's to emit)
 #pragma unroll
-  for (int k = 0; k < kXYZPosF; k++) {
+  for (int k = 0; k < NPOS; k++) {
     if ((tid + (uint32_t)k * kXYZThreadsF) >= npos || seg + 1 != nseg)
       continue;
     if ((cz & 1) == 0) {   // the last sample is odd: x[2M+1], M = cz / 2 - 1
@@ -1143,21 +1151,67 @@ k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32
     for (int d = 32; d > 0; d >>= 1)
       vmax = fmax(vmax, __shfl_xor(vmax, d, 64));
     if ((tid & 63) == 0 && vmax > 0.0)
-      atomicMax(reinterpret_cast<unsigned long long*>(&st[c].maxabs),
+      atomicMax(reinterpret_cast<unsigned long long*>(&stc->maxabs),
                 (unsigned long long)__double_as_longlong(vmax));
   }
+}
+
+// box (not null): the next level's box goes there, chunk c's boxStride samples in, and not to `vals` (xyz_fwd_body)
+template <int IO>
+__global__ void __launch_bounds__(kXYZThreadsF) __attribute__((amdgpu_waves_per_eu(kXYZThreadsF / 256, kXYZThreadsF / 256)))
+k_lift_xyz_fwd(double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz, LiftConsts K,
+               CoderState* st, const void* volume, VolDesc vd, const ChunkGeom* geom, int wantMax,
+               uint32_t in0, uint32_t in1, uint32_t in2, uint32_t nseg, double* box, size_t boxStride)
+{
+  static_assert(IO == 1 || IO == 2, "float or double volume");
+  using VT = typename std::conditional<IO == 1, float, double>::type;
+  const uint32_t c = blockIdx.y;
+  if (st[c].is_const != 0)
+    return;
+  const VT* vol = reinterpret_cast<const VT*>(volume);
+  const size_t vsy = vd.dims[0], vsz = (size_t)vd.dims[0] * vd.dims[1];
+  const VT* volc = vol + ((size_t)geom[c].org[2] * vsz + (size_t)geom[c].org[1] * vsy + geom[c].org[0]);
+  xyz_fwd_body<VT, kXYZPosF, kXYZStageF, false>(vals + c * valsStride, cx, (size_t)cx * cy, cx, cy, cz, K, st + c, volc, vsy, vsz,
+                                                 st[c].mean, wantMax, in0, in1, in2, nseg, box ? box + c * boxStride : nullptr);
+}
+
+// The SECOND level's three passes in one launch of the same sliding-window code: the box the finest-level kernel
+// has written (rows of cx samples, cy rows a slice: read like a volume of doubles, nothing subtracted) -> the corner of
+// the chunk buffer, at the chunk's strides `orow` / `oslice`.  Rows of at most 128 samples: half the z pipelines per
+// thread, and no scratch.
+constexpr int kL2MaxRow = 128;
+constexpr int kL2PosF = (kXYZRows * kL2MaxRow + kXYZThreadsF - 1) / kXYZThreadsF;
+constexpr int kL2StageF = (kXYZStaged * kL2MaxRow + kXYZThreadsF - 1) / kXYZThreadsF;
+constexpr int kL2PosI = (kXYZStaged * kL2MaxRow + kXYZThreadsI - 1) / kXYZThreadsI;
+__global__ void __launch_bounds__(kXYZThreadsF) __attribute__((amdgpu_waves_per_eu(kXYZThreadsF / 256, kXYZThreadsF / 256)))
+k_lift2_fwd(const double* box, size_t boxStride, double* vals, size_t valsStride, uint32_t orow, size_t oslice, uint32_t cx,
+            uint32_t cy, uint32_t cz, LiftConsts K, CoderState* st, int wantMax, uint32_t in0, uint32_t in1, uint32_t in2,
+            uint32_t nseg)
+{
+  const uint32_t c = blockIdx.y;
+  if (st[c].is_const != 0)
+    return;
+  xyz_fwd_body<double, kL2PosF, kL2StageF, true>(vals + c * valsStride, orow, oslice, cx, cy, cz, K, st + c, box + c * boxStride,
+                                                  (size_t)cx, (size_t)cx * cy, 0.0, wantMax, in0, in1, in2, nseg, nullptr);
 }
 
 // SG: the coefficients carry their sign where the chunk allows it (DequantSrc::coefSigned, coef_scheme), a kernel of its own -- with both fast paths in
 // one function the register allocator spilled inside the slice loop (88 registers against 38) and the kernel took 5.4 ms
 // instead of 3.7
 // kCrop: the rows of the chunk's window go to the box; a tile with no row in the window returns at once
-template <int IO, bool SG, bool kCrop = false>
-__global__ void __launch_bounds__(kXYZThreadsI) __attribute__((amdgpu_waves_per_eu(kXYZThreadsI / 256, kXYZThreadsI / 256)))
-k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz, LiftConsts K,
-               const CoderState* st, void* volume, VolDesc vd, const GeomOf<kCrop>* geom, LiftFuse F, uint32_t nseg)
+// The body of the inverse kernels.  NPOS: positions per thread (kXYZStaged * cx <= NPOS * threads).
+// L2: the second level (k_lift2_inv) -- `volume` is the chunk's own output box (rows and slices as `vd` says, no chunk
+// map, nothing written for a constant chunk), and the coefficient, sign and mask arrays, which keep the CHUNK's dims, have
+// rows of `qrowL2` samples and slices of `qsliceL2`; otherwise they are the region's, cx and cx * cy.
+template <int IO, bool SG, bool kCrop, int NPOS, bool L2>
+__device__ __forceinline__ void xyz_inv_body(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz,
+                                             const LiftConsts& K, const CoderState* st, void* volume, const VolDesc& vd,
+                                             const GeomOf<kCrop>* geom, const LiftFuse& F, uint32_t nseg, uint32_t qrowL2,
+                                             size_t qsliceL2)
 {
   static_assert(IO == 1 || IO == 2, "float or double volume");
+  static_assert(!L2 || (IO == 2 && !kCrop), "the second level writes doubles into a box");
+  constexpr int NGRP = NPOS < kXYZGroupI ? NPOS : kXYZGroupI;   // positions whose loads are in flight together
   using VT = typename std::conditional<IO == 1, float, double>::type;
   const uint32_t c = blockIdx.y;
   const uint32_t tid = threadIdx.x;
@@ -1187,19 +1241,21 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
       return;
     wy1 -= y0;
   }
-  else
+  else if constexpr (!L2)
     volc = vol + ((size_t)geom[c].org[2] * vsz + (size_t)geom[c].org[1] * vsy + geom[c].org[0]);
   // crop variant: row y0 + r of slice z -> the box row that holds its window, x = wx0 at its start
   auto crop_row = [&](uint32_t z, uint32_t r) -> VT* { return vol + crop_addr(cg, vd, cg.lo[0], y0 + r, z); };
   (void)crop_row;
   const double* buf = vals + c * valsStride;
-  const size_t sliceN = (size_t)cx * cy;
+  const uint32_t qrow = L2 ? qrowL2 : cx;                    // the coefficient arrays' rows and slices
+  const size_t sliceN = L2 ? qsliceL2 : (size_t)cx * cy;
   const uint32_t bufx = F.bufx ? F.bufx : cx;                       // the chunk buffer may be compact:
   const size_t bufSlice = (size_t)bufx * (F.bufy ? F.bufy : cy);   // only the next level's box
   const double mean = st[c].mean;
   const uint32_t lane = tid & 63u, nwaves = kXYZThreadsI / 64;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (a scalar, and what is made of it)
 
+  if constexpr (!L2) {   // (k_lift2_inv has returned for a constant chunk)
   if (st[c].is_const != 0) {   // the chunk is its constant
     if constexpr (kCrop) {
       const uint32_t w = cg.hi[0] - cg.lo[0], nr = wy1 - wy0;
@@ -1213,14 +1269,15 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
         volc[(size_t)z * vsz + (size_t)(y0 + k / cx) * vsy + k % cx] = (VT)mean;
     return;
   }
+  }
 
   // position k of this thread: sample x of LDS row j = row ysrc of a slice (j << 27 | ysrc << 12 | x);
   // in the transformed chunk that is sample (dcol, drow): low | high halves along x and y
   const uint32_t npos = (uint32_t)kXYZStaged * cx;
-  uint32_t pk[kXYZPosI];
+  uint32_t pk[NPOS];
   uint32_t innerMask = 0;   // bit k: inside the next level's box along x and y
 #pragma unroll
-  for (int k = 0; k < kXYZPosI; k++) {
+  for (int k = 0; k < NPOS; k++) {
     const uint32_t q = tid + (uint32_t)k * kXYZThreadsI;
     const uint32_t j = q / cx, x = q - j * cx, y = reflect_index((int)y0 - kXYHalo + (int)j, (int)cy);
     const uint32_t drow = (y & 1) ? ye + (y >> 1) : (y >> 1), dcol = (x & 1) ? xe + (x >> 1) : (x >> 1);
@@ -1248,7 +1305,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   auto fetch = [&](int k, uint32_t zp) -> double {
     const uint32_t y = (pk[k] >> 12) & 0x7fffu, x = pk[k] & 0xfffu;
     const uint32_t drow = (y & 1) ? ye + (y >> 1) : (y >> 1), dcol = (x & 1) ? xe + (x >> 1) : (x >> 1);
-    const size_t idx = (size_t)zp * sliceN + drow * cx + dcol;
+    const size_t idx = (size_t)zp * sliceN + drow * qrow + dcol;
     const bool inBox = ((innerMask >> k) & 1u) && zp < F.inner[2];
     if (!dequant && !inBox && F.bufx)
       return 0.0;   // (a compact buffer holds the box only; the host asks for one only when every chunk dequantises here)
@@ -1272,9 +1329,9 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     asm volatile("" : "+v"(p));   // (keeps the LDS address from being computed ahead and spilled)
     (sm + (flip ? bufN : 0u))[(p >> 27) * RS + 4 + (p & 0xfffu)] = v;
   };
-  auto stage_all = [&](const double (&v)[kXYZPosI]) {
+  auto stage_all = [&](const double (&v)[NPOS]) {
 #pragma unroll
-    for (int k = 0; k < kXYZPosI; k++)
+    for (int k = 0; k < NPOS; k++)
       if ((tid + (uint32_t)k * kXYZThreadsI) < npos)
         stage(k, v[k]);
   };
@@ -1343,9 +1400,9 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     }
   };
 
-  double o1p[kXYZPosI], e1p[kXYZPosI], o2p[kXYZPosI], e2p[kXYZPosI];
+  double o1p[NPOS], e1p[NPOS], o2p[NPOS], e2p[NPOS];
 #pragma unroll
-  for (int k = 0; k < kXYZPosI; k++)
+  for (int k = 0; k < NPOS; k++)
     o1p[k] = e1p[k] = o2p[k] = e2p[k] = 0.0;
   const uint32_t npairs = cz / 2;
   // one pair (low[m], high[m]) of position k enters its pipeline; slice 2m-3's sample is staged
@@ -1376,20 +1433,20 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   //    without any branch -- a lane that does not need one reads a harmless address --, three positions'
   //    worth at a time: two round trips per pair.
   // The arithmetic per sample is what it was.
-  uint32_t* myPre = reinterpret_cast<uint32_t*>(sm + 2 * (size_t)bufN) + (size_t)wave * (kXYZPosI * 2 * 64);
+  uint32_t* myPre = reinterpret_cast<uint32_t*>(sm + 2 * (size_t)bufN) + (size_t)wave * (NPOS * 2 * 64);
   const uint32_t* sign32 = reinterpret_cast<const uint32_t*>(sign);
   const uint32_t* mNew32 = reinterpret_cast<const uint32_t*>(mNew);
   const uint32_t* mOld32 = reinterpret_cast<const uint32_t*>(mOld);
   uint32_t activeMask = 0;
 #pragma unroll
-  for (int k = 0; k < kXYZPosI; k++)
+  for (int k = 0; k < NPOS; k++)
     if ((tid + (uint32_t)k * kXYZThreadsI) < npos)
       activeMask |= 1u << k;
     else
       pk[k] = pk[0];   // (a valid position: its loads are harmless, nothing of it is staged)
   uint32_t boxAny = 0;   // bit k: some lane of this wavefront has position k inside the coarser levels' box (along x and y)
 #pragma unroll
-  for (int k = 0; k < kXYZPosI; k++)
+  for (int k = 0; k < NPOS; k++)
     boxAny |= __ballot((innerMask >> k) & 1u) != 0ull ? 1u << k : 0u;
   boxAny = (uint32_t)__builtin_amdgcn_readfirstlane((int)boxAny);
   auto pos_off = [&](int k, uint32_t& drow, uint32_t& dcol) {
@@ -1405,11 +1462,11 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   // and lane 2 i reads double i.  Two load round trips per pair in half the wavefronts, with the other half waiting
   // for them at the barrier, before.  A slot per (wavefront, position) that has a box row: 12 rows x cx / 64 <= 48.
   uint32_t boxLds = 0, boxSlot0 = 0;   // (wave-uniform) bit k: position k's box samples come through LDS; the wavefront's first slot
-  uint32_t* boxRows = reinterpret_cast<uint32_t*>(sm + 2 * (size_t)bufN) + (size_t)nwaves * (kXYZPosI * 2 * 64);
+  uint32_t* boxRows = reinterpret_cast<uint32_t*>(sm + 2 * (size_t)bufN) + (size_t)nwaves * (NPOS * 2 * 64);
   if (SG && fastLoads) {
     uint32_t reg = 0;
 #pragma unroll
-    for (int k = 0; k < kXYZPosI; k++) {
+    for (int k = 0; k < NPOS; k++) {
       const uint64_t inb = __ballot((innerMask >> k) & 1u), act = __ballot((activeMask >> k) & 1u);
       if (inb == 0x5555555555555555ull && act == ~0ull && (cx & 63u) == 0)
         reg |= 1u << k;
@@ -1426,7 +1483,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
       total += v;
     }
     XYZ_LDS_BARRIER();
-    if (total <= (uint32_t)kXYZBoxSlots && reg == (1u << kXYZPosI) - 1u) {   // (all of the wavefront's positions or none)
+    if (total <= (uint32_t)kXYZBoxSlots && reg == (1u << NPOS) - 1u) {   // (all of the wavefront's positions or none)
       boxLds = reg;
       boxSlot0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
     }
@@ -1439,7 +1496,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     //  coefficients' loads that reload would wait for every one of them -- the memory counter retires in order)
     if (SG && boxLds != 0 && m < F.inner[2]) {   // (uniform)
 #pragma unroll
-      for (int k = 0; k < kXYZPosI; k++) {
+      for (int k = 0; k < NPOS; k++) {
         uint32_t drow, dcol;
         pos_off(k, drow, dcol);
         const uint32_t x0h = ((pk[k] & 0xfffu) - lane) >> 1;   // the box column of the wavefront's first lane
@@ -1448,10 +1505,10 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
       }
     }
 #pragma unroll
-    for (int k = 0; k < kXYZPosI; k++) {
+    for (int k = 0; k < NPOS; k++) {
       uint32_t drow, dcol;
       pos_off(k, drow, dcol);
-      const uint32_t off = drow * cx + dcol;
+      const uint32_t off = drow * qrow + dcol;
       __builtin_amdgcn_global_load_lds(coef + ((size_t)m * sliceN + off), myPre + (k * 2) * 64, 4, 0, 0);
       __builtin_amdgcn_global_load_lds(coef + ((size_t)(ze + m) * sliceN + off), myPre + (k * 2 + 1) * 64, 4, 0, 0);
     }
@@ -1462,7 +1519,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   for (uint32_t m = mFirst; m < mB; m++) {
     const bool mine = m >= mA;   // (else: the segment's run-up)
 #pragma unroll
-    for (int k = 0; k < kXYZPosI; k++)
+    for (int k = 0; k < NPOS; k++)
       asm volatile("" : "+v"(pk[k]));
 #if XYZ_INV_PREFETCH == 2
     if (SG && fastLoads) {
@@ -1474,7 +1531,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
       const bool zOn = !xyz_off<XYZ_INV_OFF>(8, nseg);
       if (zOn && boxWave && boxLds != 0) {   // the box samples were prefetched with the coefficients
 #pragma unroll
-        for (int k = 0; k < kXYZPosI; k++) {
+        for (int k = 0; k < NPOS; k++) {
           const double lo = sg_value(myPre[(k * 2) * 64 + lane]);
           const double hi = sg_value(myPre[(k * 2 + 1) * 64 + lane]);
           const double bxv = reinterpret_cast<const double*>(myBox + k * 64)[lane >> 1];
@@ -1483,15 +1540,15 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
       }
       else if (zOn) {
 #pragma unroll
-      for (int g = 0; g < kXYZPosI; g += kXYZGroupI) {
-        __builtin_amdgcn_sched_barrier(0);   // (kXYZGroupI positions' loads in flight at a time)
-        double bx[kXYZGroupI];
+      for (int g = 0; g < NPOS; g += NGRP) {
+        __builtin_amdgcn_sched_barrier(0);   // (NGRP positions' loads in flight at a time)
+        double bx[NGRP];
         uint32_t boxm = 0;
         if (boxWave) {
 #pragma unroll
-          for (int kk = 0; kk < kXYZGroupI; kk++) {
+          for (int kk = 0; kk < NGRP; kk++) {
             const int k = g + kk;
-            if (k >= kXYZPosI)
+            if (k >= NPOS)
               continue;
             uint32_t drow, dcol;
             pos_off(k, drow, dcol);
@@ -1501,9 +1558,9 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
           }
         }
 #pragma unroll
-        for (int kk = 0; kk < kXYZGroupI; kk++) {
+        for (int kk = 0; kk < NGRP; kk++) {
           const int k = g + kk;
-          if (k >= kXYZPosI)
+          if (k >= NPOS)
             continue;
           const double lo = sg_value(myPre[(k * 2) * 64 + lane]);
           const double hi = sg_value(myPre[(k * 2 + 1) * 64 + lane]);
@@ -1519,20 +1576,20 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     else if (!SG && fastLoads) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this pair's coefficients have landed in LDS
 #pragma unroll
-      for (int g = 0; g < kXYZPosI; g += kXYZGroupI) {
-        __builtin_amdgcn_sched_barrier(0);   // (kXYZGroupI positions' loads in flight at a time)
-        constexpr int NV = 2 * kXYZGroupI;
+      for (int g = 0; g < NPOS; g += NGRP) {
+        __builtin_amdgcn_sched_barrier(0);   // (NGRP positions' loads in flight at a time)
+        constexpr int NV = 2 * NGRP;
         uint32_t sgw[NV], mnw[NV], mow[NV], cv[NV], shv[NV], boxm = 0;
-        double bx[kXYZGroupI];   // (only a low-half sample can lie in the box: fastLoads)
+        double bx[NGRP];   // (only a low-half sample can lie in the box: fastLoads)
 #pragma unroll
         for (int j = 0; j < NV; j++) {
           const int k = g + j / 2;
-          if (k >= kXYZPosI)
+          if (k >= NPOS)
             continue;
           const uint32_t zp = (j & 1) ? ze + m : m;
           uint32_t drow, dcol;
           pos_off(k, drow, dcol);
-          const size_t idx = (size_t)zp * sliceN + drow * cx + dcol;
+          const size_t idx = (size_t)zp * sliceN + drow * qrow + dcol;
           sgw[j] = sign32[idx >> 5];
           mnw[j] = mNew32[idx >> 5];
           mow[j] = mOld32[idx >> 5];
@@ -1547,14 +1604,14 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
         double val[NV];
 #pragma unroll
         for (int j = 0; j < NV; j++) {
-          if (g + j / 2 >= kXYZPosI)
+          if (g + j / 2 >= NPOS)
             continue;
           const double dq = dequant_masks(rule, cv[j], mnw[j], mow[j], sgw[j], shv[j]);
           val[j] = ((j & 1) == 0 && ((boxm >> j) & 1u)) ? bx[j / 2] : dq;
         }
 #pragma unroll
-        for (int kk = 0; kk < kXYZGroupI; kk++)
-          if (g + kk < kXYZPosI)
+        for (int kk = 0; kk < NGRP; kk++)
+          if (g + kk < NPOS)
             zstep(g + kk, m, mine, ((activeMask >> (g + kk)) & 1u) != 0, val[2 * kk], val[2 * kk + 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -1566,7 +1623,7 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
 #endif
     {
 #pragma unroll
-      for (int k = 0; k < kXYZPosI; k++) {
+      for (int k = 0; k < NPOS; k++) {
         if ((k % 3) == 0)
           __builtin_amdgcn_sched_barrier(0);   // (four positions' loads in flight at a time, not all twelve)
         if ((tid + (uint32_t)k * kXYZThreadsI) >= npos)
@@ -1587,9 +1644,9 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     return;
   if ((cz & 1) == 0) {   // pairs 0 .. M, M = cz / 2 - 1
     const uint32_t M = npairs - 1;
-    double outC[kXYZPosI];
+    double outC[NPOS];
 #pragma unroll
-    for (int k = 0; k < kXYZPosI; k++) {
+    for (int k = 0; k < NPOS; k++) {
       outC[k] = 0.0;
       if ((tid + (uint32_t)k * kXYZThreadsI) >= npos)
         continue;
@@ -1607,9 +1664,9 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
   }
   else {                 // pairs 0 .. M-1 and the lone even sample low[M], M = cz / 2
     const uint32_t M = npairs;
-    double outC[kXYZPosI], outD[kXYZPosI];
+    double outC[NPOS], outD[NPOS];
 #pragma unroll
-    for (int k = 0; k < kXYZPosI; k++) {
+    for (int k = 0; k < NPOS; k++) {
       outC[k] = outD[k] = 0.0;
       if ((tid + (uint32_t)k * kXYZThreadsI) >= npos)
         continue;
@@ -1632,6 +1689,29 @@ k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, 
     stage_all(outD);
     finish_slice(2 * M);
   }
+}
+
+template <int IO, bool SG, bool kCrop = false>
+__global__ void __launch_bounds__(kXYZThreadsI) __attribute__((amdgpu_waves_per_eu(kXYZThreadsI / 256, kXYZThreadsI / 256)))
+k_lift_xyz_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz, LiftConsts K,
+               const CoderState* st, void* volume, VolDesc vd, const GeomOf<kCrop>* geom, LiftFuse F, uint32_t nseg)
+{
+  xyz_inv_body<IO, SG, kCrop, kXYZPosI, false>(vals, valsStride, cx, cy, cz, K, st, volume, vd, geom, F, nseg, 0u, 0);
+}
+
+// The second level, inverse: the region (cx, cy, cz) of every chunk from the box the coarser levels worked in (F.bufx /
+// F.bufy, the samples inside F.inner) and the coefficients (at the chunk's strides qrow / qslice) into `out`, a box of
+// its own with rows of cx samples, chunk c's outStride samples in; no mean added.  See k_lift2_fwd.
+template <bool SG>
+__global__ void __launch_bounds__(kXYZThreadsI) __attribute__((amdgpu_waves_per_eu(kXYZThreadsI / 256, kXYZThreadsI / 256)))
+k_lift2_inv(const double* vals, size_t valsStride, uint32_t cx, uint32_t cy, uint32_t cz, LiftConsts K, const CoderState* st,
+            double* out, size_t outStride, LiftFuse F, uint32_t nseg, uint32_t qrow, size_t qslice)
+{
+  if (st[blockIdx.y].is_const != 0)
+    return;
+  const VolDesc vd{{cx, cy, cz}};
+  xyz_inv_body<2, SG, false, kL2PosI, true>(vals, valsStride, cx, cy, cz, K, st, out + blockIdx.y * outStride, vd, nullptr, F, nseg,
+                                            qrow, qslice);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2064,11 +2144,22 @@ bool lift_xyz_applicable(const uint32_t cdims[3])
          (size_t)kXYZRows * cdims[0] <= (size_t)kXYZPosF * kXYZThreadsF && cdims[0] < 4096 && cdims[1] < 32768;
 }
 
+// a batch with fewer tiles than two per CU: the slices of a tile are dealt to several workgroups
+static uint32_t xyz_segments(uint32_t ntile, uint32_t nchunks, uint32_t cz)
+{
+  uint32_t nseg = 1;
+  while (nseg < 4 && (size_t)ntile * nchunks * nseg < 512 && cz / (2 * nseg) >= 24)
+    nseg *= 2;
+  return nseg;
+}
+
 int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsStride, uint32_t nchunks,
                     const uint32_t cdims[3], CoderState* st, int io, void* volume, VolDesc vd,
-                    const ChunkGeom* geom, const LiftFuse* fuse, const CropGeom* crop)
+                    const ChunkGeom* geom, const LiftFuse* fuse, const CropGeom* crop, double* box, size_t boxStride)
 {
   if (!lift_xyz_applicable(cdims) || (io != 1 && io != 2) || (crop && forward))
+    return -1;
+  if (box && !forward)
     return -1;
   const LiftFuse F = fuse ? *fuse : LiftFuse{};
   size_t smem = 2 * (size_t)kXYZStaged * xyz_row_stride(cdims[0]) * sizeof(double);   // two staging buffers
@@ -2087,21 +2178,18 @@ int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsS
       if (set_max_dyn_lds(f, 160 * 1024))
         return -1;
   }
-  // a batch with fewer tiles than two per CU: the slices of a tile are dealt to several workgroups
   const uint32_t ntile = (cdims[1] + kXYZRows - 1) / kXYZRows;
-  uint32_t nseg = 1;
-  while (nseg < 4 && (size_t)ntile * nchunks * nseg < 512 && cdims[2] / (2 * nseg) >= 24)
-    nseg *= 2;
+  const uint32_t nseg = xyz_segments(ntile, nchunks, cdims[2]);
   const dim3 grid(ntile * nseg, nchunks);
   const LiftConsts K = lift_consts();
   if (forward) {
     const int wantMax = F.mode == 1 ? 1 : 0;
     if (io == 1)
       LAUNCH_K((k_lift_xyz_fwd<1>), grid, dim3(kXYZThreadsF), smem, stream, vals, valsStride, cdims[0], cdims[1],
-               cdims[2], K, st, volume, vd, geom, wantMax, F.inner[0], F.inner[1], F.inner[2], nseg);
+               cdims[2], K, st, volume, vd, geom, wantMax, F.inner[0], F.inner[1], F.inner[2], nseg, box, boxStride);
     else
       LAUNCH_K((k_lift_xyz_fwd<2>), grid, dim3(kXYZThreadsF), smem, stream, vals, valsStride, cdims[0], cdims[1],
-               cdims[2], K, st, volume, vd, geom, wantMax, F.inner[0], F.inner[1], F.inner[2], nseg);
+               cdims[2], K, st, volume, vd, geom, wantMax, F.inner[0], F.inner[1], F.inner[2], nseg, box, boxStride);
   }
   else {
     const bool sg = F.mode == 2 && F.src.coefSigned != 0;
@@ -2136,6 +2224,70 @@ int launch_lift_xyz(hipStream_t stream, bool forward, double* vals, size_t valsS
 #undef XYZ_INV_LAUNCH
 #undef XYZ_CROP_LAUNCH
   }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+bool lift2_applicable(const uint32_t region[3])
+{
+  return lift_xyz_applicable(region) && region[0] <= (uint32_t)kL2MaxRow;
+}
+
+// segments per tile of a level-2 launch (SPERR_HIP_L2_NSEG, diagnostics build: 1, 2 or 4 whatever the rule says)
+static uint32_t lift2_segments(uint32_t ntile, uint32_t nchunks, uint32_t cz)
+{
+  static const int forced = tune_getenv("SPERR_HIP_L2_NSEG") ? atoi(tune_getenv("SPERR_HIP_L2_NSEG")) : 0;
+  if ((forced == 1 || forced == 2 || forced == 4) && cz / (2 * (uint32_t)forced) >= 8)
+    return (uint32_t)forced;
+  return xyz_segments(ntile, nchunks, cz);
+}
+
+int launch_lift2_fwd(hipStream_t stream, const double* box, size_t boxStride, double* vals, size_t valsStride,
+                     uint32_t nchunks, const uint32_t cdims[3], const uint32_t region[3], CoderState* st,
+                     const LiftFuse* fuse)
+{
+  if (!lift2_applicable(region) || !box || region[0] > cdims[0] || region[1] > cdims[1] || region[2] > cdims[2])
+    return -1;
+  const LiftFuse F = fuse ? *fuse : LiftFuse{};
+  const size_t smem = 2 * (size_t)kXYZStaged * xyz_row_stride(region[0]) * sizeof(double);   // two staging buffers
+  if (set_max_dyn_lds(reinterpret_cast<const void*>(&k_lift2_fwd), 160 * 1024))
+    return -1;
+  const uint32_t ntile = (region[1] + kXYZRows - 1) / kXYZRows;
+  const uint32_t nseg = lift2_segments(ntile, nchunks, region[2]);
+  LAUNCH_K(k_lift2_fwd, dim3(ntile * nseg, nchunks), dim3(kXYZThreadsF), smem, stream, box, boxStride, vals, valsStride,
+           cdims[0], (size_t)cdims[0] * cdims[1], region[0], region[1], region[2], lift_consts(), st, F.mode == 1 ? 1 : 0,
+           F.inner[0], F.inner[1], F.inner[2], nseg);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_lift2_inv(hipStream_t stream, const double* box, size_t boxStride, double* out, size_t outStride,
+                     uint32_t nchunks, const uint32_t cdims[3], const uint32_t region[3], const CoderState* st,
+                     const LiftFuse* fuse)
+{
+  // (every sample outside fuse->inner comes from the coefficients: there is no fp64 copy of the region to read them from)
+  if (!lift2_applicable(region) || !box || !out || !fuse || fuse->mode != 2 || region[0] > cdims[0] ||
+      region[1] > cdims[1] || region[2] > cdims[2] || outStride < (size_t)region[0] * region[1] * region[2])
+    return -1;
+  LiftFuse F = *fuse;
+  F.noMean = 1;
+  size_t smem = 2 * (size_t)kXYZStaged * xyz_row_stride(region[0]) * sizeof(double);   // two staging buffers
+#if XYZ_INV_PREFETCH == 2
+  smem += (size_t)kXYZThreadsI * kL2PosI * 2 * sizeof(uint32_t) + (size_t)kXYZBoxSlots * 64 * sizeof(uint32_t);   // (see launch_lift_xyz)
+#endif
+  if (set_max_dyn_lds(reinterpret_cast<const void*>(&k_lift2_inv<false>), 160 * 1024) ||
+      set_max_dyn_lds(reinterpret_cast<const void*>(&k_lift2_inv<true>), 160 * 1024))
+    return -1;
+  const uint32_t ntile = (region[1] + kXYZRows - 1) / kXYZRows;
+  const uint32_t nseg = lift2_segments(ntile, nchunks, region[2]);
+  const dim3 grid(ntile * nseg, nchunks);
+  const LiftConsts K = lift_consts();
+  if (F.src.coefSigned != 0)
+    LAUNCH_K((k_lift2_inv<true>), grid, dim3(kXYZThreadsI), smem, stream, box, boxStride, region[0], region[1], region[2], K,
+             st, out, outStride, F, nseg, cdims[0], (size_t)cdims[0] * cdims[1]);
+  else
+    LAUNCH_K((k_lift2_inv<false>), grid, dim3(kXYZThreadsI), smem, stream, box, boxStride, region[0], region[1], region[2], K,
+             st, out, outStride, F, nseg, cdims[0], (size_t)cdims[0] * cdims[1]);
   HIP_CHECK(hipGetLastError());
   return 0;
 }
