@@ -265,6 +265,26 @@ struct LiftPass {
   uint32_t region[3];
 };
 
+// How a chunk shape's transform runs.  Decided once, when the plan is made (plan_schedule, below): the encoder's
+// launches (float_stages, pwe_stage_begin) and the decoder's memory layout and launches (compact_box, decode_group,
+// enqueue_inverse) read it, and nothing else asks the pass list these questions.
+struct LiftSchedule {
+  enum Head { kNoHead, kHeadXY, kHeadXYZ };
+  Head head = kNoHead;     // the finest level's full-size passes that one kernel runs, straight from / into the volume
+  bool fusable = false;    // the passes can collect the largest coefficient / dequantise on the way (plan_fusable)
+  bool brick = false;      // x-y-z head, fusable, at least three passes: the coarser levels can work in a compact box
+  bool level2 = false;     // passes 3 to 5 -- the second level -- run as one launch each way (plan_level2)
+  uint32_t coarseBox[3] = {1, 1, 1};   // the box the coarser levels work in: the largest region of the passes k >= 3
+  struct Pass {   // what pass_fuse_rule says of a pass: -1, 0 or 1, and the box of the later passes
+    int fuse;
+    uint32_t inner[3];
+  };
+  std::vector<Pass> pass;
+  // The passes, counted from the finest, that fused launches run instead of the per-axis kernel: the forward walk's
+  // per-axis loop starts there and the inverse walk's stops there
+  static size_t fused_passes(Head head, bool level2) { return level2 ? 6 : head == kHeadXYZ ? 3 : head == kHeadXY ? 2 : 0; }
+};
+
 struct ShapePlan {
   uint32_t dims[3];
   uint32_t N = 0;
@@ -296,11 +316,9 @@ struct ShapePlan {
   uint64_t maxPhaseBits = 0;
   size_t lisEntries = 0;
   std::vector<LiftPass> fwd;
-  bool level2 = false;   // passes 3 to 5 -- the second level -- run as one launch each way (plan_level2)
+  LiftSchedule schedule;   // which kernels run the passes (plan_schedule)
+  DecPlanHost dec{};       // the list kernels the shape's decoder takes (plan_list_kernels); per-call fields at their defaults
 };
-bool use_tables(const ShapePlan& P);   // (defined with the decoder's plan logic below)
-bool plan_level2(const ShapePlan& P);  // (defined with the transform's plan logic below)
-
 
 // The encoder's fused head (k_head_fused, speck_enc.hip) wants workgroups that own whole pixel tiles AND whole leaf sets:
 // an all-octree forest (cubic power-of-two roots) whose every deepest grid is one pyramid_leaf4 takes (leaf4_block) with
@@ -343,6 +361,182 @@ struct Blob {  // host-side staging of all tables of a plan, uploaded in one cop
   }
 };
 
+// ---- the rules of a shape's kernel choices: build_plan asks them once and keeps the answers (ShapePlan::schedule, ::dec) ----
+// the transform starts with the full-size x pass followed by the full-size y pass (every dyadic
+// shape; wavelet-packet shapes start along z), and the rows fit the fused kernel's LDS tile
+static bool fuse_xy(const ShapePlan& P)
+{
+  if (P.fwd.size() < 2 || P.fwd[0].axis != 0 || P.fwd[1].axis != 1)
+    return false;
+  for (int a = 0; a < 3; a++)
+    if (P.fwd[0].region[a] != P.dims[a] || P.fwd[1].region[a] != P.dims[a])
+      return false;
+  return lift_xy_applicable(P.dims);
+}
+
+// ... and the full-size z pass follows (every dyadic shape): all three in one kernel
+static bool fuse_xyz(const ShapePlan& P)
+{
+  if (!fuse_xy(P) || P.fwd.size() < 3 || P.fwd[2].axis != 2)
+    return false;
+  for (int a = 0; a < 3; a++)
+    if (P.fwd[2].region[a] != P.dims[a])
+      return false;
+  return lift_xyz_applicable(P.dims);
+}
+
+// LiftFuse of pass k (xform.h): the samples of its region that no LATER pass of the forward order
+// touches.  The later passes' regions are boxes at the origin; when one of them contains all the
+// others (dyadic plans: the next pass; wavelet-packet plans: the full-size x pass for every z pass)
+// the samples are those outside it.  Returns 0 when there are none, 1 when there are (inner = that
+// box), -1 when the later regions are not nested (no plan of build_plan is like that).
+static int pass_fuse_rule(const ShapePlan& P, size_t k, uint32_t inner[3])
+{
+  const LiftPass& ps = P.fwd[k];
+  inner[0] = inner[1] = inner[2] = 0;
+  for (size_t j = k + 1; j < P.fwd.size(); j++)
+    for (int a = 0; a < 3; a++)
+      inner[a] = std::max(inner[a], P.fwd[j].region[a]);
+  bool nested = k + 1 >= P.fwd.size();
+  for (size_t j = k + 1; j < P.fwd.size(); j++)
+    nested = nested || (P.fwd[j].region[0] == inner[0] && P.fwd[j].region[1] == inner[1] &&
+                        P.fwd[j].region[2] == inner[2]);
+  if (!nested)
+    return -1;
+  bool covers = true;
+  for (int a = 0; a < 3; a++)
+    covers = covers && inner[a] >= ps.region[a];
+  return covers ? 0 : 1;
+}
+// ... as the plan keeps it (LiftSchedule::pass)
+int pass_fuse(const ShapePlan& P, size_t k, uint32_t inner[3])
+{
+  std::copy_n(P.schedule.pass[k].inner, 3, inner);
+  return P.schedule.pass[k].fuse;
+}
+
+// Can the lifting passes collect the largest coefficient / dequantise on the way?  Not when the
+// fused x-y kernel of the finest level would have to (slices: their next pass is a coarser level).
+static bool plan_fusable(const ShapePlan& P)
+{
+  if (P.fwd.empty())
+    return false;
+  for (const LiftSchedule::Pass& ps : P.schedule.pass)
+    if (ps.fuse < 0)
+      return false;
+  if (P.schedule.head != LiftSchedule::kNoHead && (P.schedule.pass[0].fuse != 0 || P.schedule.pass[1].fuse != 0))
+    return false;
+  return true;
+}
+
+// Can the SECOND level of this shape run as one launch each way (k_lift2_fwd / k_lift2_inv, xform.h) instead of three
+// per-axis passes?  Passes 3, 4 and 5 have to be x, y and z of one region -- the low halves the fused finest-level kernel
+// leaves --, the region has to fit the sliding-window kernels with rows of at most 128 samples, and the passes have to
+// nest (plan_fusable: the kernels tell the box's samples from the others by LiftFuse::inner).
+static bool level2_fits(const ShapePlan& P)
+{
+  if (!P.schedule.brick || P.fwd.size() < 6)
+    return false;
+  for (int k = 3; k < 6; k++) {
+    if (P.fwd[k].axis != k - 3)
+      return false;
+    for (int a = 0; a < 3; a++)
+      if (P.fwd[k].region[a] != P.dims[a] - P.dims[a] / 2)
+        return false;
+  }
+  const LiftSchedule::Pass& z = P.schedule.pass[2];
+  if (z.fuse <= 0 || z.inner[0] != P.fwd[3].region[0] || z.inner[1] != P.fwd[3].region[1] ||
+      z.inner[2] != P.fwd[3].region[2])
+    return false;
+  return lift2_applicable(P.fwd[3].region);
+}
+// Does it?  Decided once, when the plan is made: the encoder's launches (float_stages) and the decoder's memory layout
+// and launches (decode_group, enqueue_inverse) follow it.  By default only where the region has at least kLevel2Floor
+// samples along every axis, in both directions alike, because that is where it was measured to gain
+// (profiles/level2_fused_ab.txt): at 128^3 (256^3 chunks) decompression gains 1.8 % run against run; at 64^3, 32^3 and
+// 16^3 (128^3, 64^3, 32^3 chunks, 64 and 512 of them) compress and decompress times with and without it lie inside
+// each other's spread -- the launch is no slower there, the march through the slices costs what the three launches
+// cost -- with one exception, 512 chunks of 32^3, which decode 3 to 4 % faster with it.  A gain that cannot be told
+// from the spread is not taken: the small shapes keep the launches they had, which tests/test_gpu_level.py pins launch
+// by launch for 32^3 chunks (with the launch on, those tables would have to change: 12 k_lift_axis<false, 0> become 4
+// k_lift2_inv<true>; the 32^3 decode gain above is what that would buy).  Nothing between 64 and 128 was measured; the
+// floor sits midway.
+// SPERR_HIP_XYZ_LEVEL2=0: the three passes everywhere, for A/B runs and tests; =2: the launch wherever it fits, for the
+// same (the tests put every shape the kernels can go wrong at through them this way).  Read whenever a plan is made:
+// sperrhip_release() drops the plans.
+constexpr uint32_t kLevel2Floor = 96;
+static bool plan_level2(const ShapePlan& P)
+{
+  const char* env = getenv("SPERR_HIP_XYZ_LEVEL2");
+  const int sw = env ? atoi(env) : 1;
+  if (sw == 0 || !level2_fits(P))
+    return false;
+  const uint32_t* r = P.fwd[3].region;
+  return sw == 2 || std::min(r[0], std::min(r[1], r[2])) >= kLevel2Floor;
+}
+
+// The schedule of the pass list P.fwd, each answer from the ones before it
+static void plan_schedule(ShapePlan& P)
+{
+  LiftSchedule& S = P.schedule;
+  S = LiftSchedule{};
+  S.pass.resize(P.fwd.size());
+  for (size_t k = 0; k < P.fwd.size(); k++)
+    S.pass[k].fuse = pass_fuse_rule(P, k, S.pass[k].inner);
+  S.head = fuse_xyz(P) ? LiftSchedule::kHeadXYZ : fuse_xy(P) ? LiftSchedule::kHeadXY : LiftSchedule::kNoHead;
+  S.fusable = plan_fusable(P);
+  S.brick = S.head == LiftSchedule::kHeadXYZ && S.fusable && P.fwd.size() >= 3;
+  for (size_t k = 3; k < P.fwd.size(); k++)   // (a chunk with one level of transform has no coarser pass: 1 x 1 x 1)
+    for (int a = 0; a < 3; a++)
+      S.coarseBox[a] = std::max(S.coarseBox[a], P.fwd[k].region[a]);
+  S.level2 = plan_level2(P);
+}
+
+// the lists of the larger sets GPU-wide (k_lis_hi); SPERR_HIP_LIS_HI=0 and regular trees whose geometry
+// tables do not fit the kernel's LDS go to k_lis_mx, which takes any shape (k_lis_tables, one workgroup
+// per chunk, was the table kernel of rounds 1-3: removed in round 4)
+constexpr int kHiMaxK = 9;   // longest class chain k_lis_hi takes (chunk dims up to 1024)
+static bool use_lis_hi(const ShapePlan& P, bool tables)
+{
+  static const bool hiEnv = !(getenv("SPERR_HIP_LIS_HI") && atoi(getenv("SPERR_HIP_LIS_HI")) == 0);
+  return hiEnv && tables && P.ht.grids.size() <= 288 && P.ht.roots.size() <= 48 &&
+         P.maxK >= 1 && P.maxK <= kHiMaxK;
+}
+// every LIS level is regular and the table kernels (k_lis_l0 / _l1 / _hi) can take the shape
+static bool use_tables(const ShapePlan& P)
+{
+  if (!P.ht.allRegular || P.maxK < 1)
+    return false;
+  return use_lis_hi(P, true);
+}
+// lists that mix set shapes (any chunk extent that is not a power of two, every slice): k_lis_mx (speck_mx.hip:
+// rows keyed by shape class, several workgroups per chunk, only the walk serial).  SPERR_HIP_LIS_MIXED=0, and trees
+// the class machinery does not take (more than 254 classes, 48 roots, 352 grids): k_lis_walk, the serial walk.
+// The switch does not apply to the 2D coder's forest: only k_lis_mx has the type-I phase a slice needs, and every
+// slice's forest fits it (DESIGN.md section 4c, tests/test_slice_forest_host.py).
+// (k_lis_mixed, the one-workgroup-per-chunk kernel of rounds 2-3 whose formulation k_lis_mx took over, was removed
+// at the end of round 4.)
+static bool use_mixed(const ShapePlan& P, bool tables)
+{
+  static const bool mixEnv = !(getenv("SPERR_HIP_LIS_MIXED") && atoi(getenv("SPERR_HIP_LIS_MIXED")) == 0);
+  const bool twoD = (P.ht.flags & spk::kTree2D) != 0;
+  if ((!twoD && !mixEnv) || tables || P.ht.cls.empty() || P.ht.roots.size() > 48 || P.ht.grids.size() > 352 ||
+      P.ht.mxSlot.size() != P.ht.cls.size())
+    return false;
+  return 2 * kMxS + 256 <= kMxRing && ((kMxS + kMxM) >> 6) + 5 <= 64 && kMxM >= 192 &&
+         mx_smem_bytes(kMxS, kMxM, kMxQ) <= 138u * 1024u;   // (k_lis_mx has 21 KB of static LDS)
+}
+// the list kernels a chunk shape takes, once its tree, its tables and its list levels are there
+static DecPlanHost plan_list_kernels(const ShapePlan& P, bool tables)
+{
+  DecPlanHost ph{P.d_initLIS, P.d_initLen, tables, P.l0Level >= 0 && P.ht.grids.size() <= 288,
+                 P.l1Level >= 0 && P.ht.grids.size() <= 288, P.maxK};
+  ph.l2 = ph.l1 && P.l2Level >= 0;
+  ph.hi = use_lis_hi(P, ph.tables);   // the lists of the larger sets GPU-wide
+  ph.mixed = use_mixed(P, tables);
+  return ph;
+}
+
 // twoD: the plan of a slice's DECODER, with the forest of the 2D coder (spk::kTree2D)
 int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
 {
@@ -362,7 +556,8 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
   P.maxK = 0;
   for (const auto& lc : P.ht.levelClass)
     P.maxK = std::max<int>(P.maxK, lc.K);
-  if (!use_tables(P))
+  const bool tables = use_tables(P);
+  if (!tables)
     spk::build_mx_columns(P.ht);
   const spk::HostTree& h = P.ht;
   const uint32_t nlev = h.nlevels;
@@ -446,9 +641,6 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
                oMS = blob.add(h.mxSlot), oMG = blob.add(h.mxLevelGroup);
   const std::vector<FusedRoot> fusedRoots = twoD ? std::vector<FusedRoot>() : fused_head_roots(h);
   const size_t oFR = blob.add(fusedRoots);
-  P.maxK = 0;
-  for (const auto& lc : h.levelClass)
-    P.maxK = std::max<int>(P.maxK, lc.K);
   P.l0Level = -1;   // the first non-empty list the sorting pass visits, when it holds 2x2x2 sets
   for (uint32_t l = nlev; l-- > 0;) {
     if (cap[l] == 0)
@@ -531,7 +723,8 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
       P.fwd.push_back({1, {approx(dx, lev), approx(dy, lev), (uint32_t)dz}});
     }
   }
-  P.level2 = plan_level2(P);
+  plan_schedule(P);
+  P.dec = plan_list_kernels(P, tables);
   return 0;
 }
 
@@ -1373,114 +1566,6 @@ int reset_enc_pass(hipStream_t st, const EncBatchBufs& bb, uint32_t B, bool fuse
   return 0;
 }
 
-// the transform starts with the full-size x pass followed by the full-size y pass (every dyadic
-// shape; wavelet-packet shapes start along z), and the rows fit the fused kernel's LDS tile
-bool fuse_xy(const ShapePlan& P)
-{
-  if (P.fwd.size() < 2 || P.fwd[0].axis != 0 || P.fwd[1].axis != 1)
-    return false;
-  for (int a = 0; a < 3; a++)
-    if (P.fwd[0].region[a] != P.dims[a] || P.fwd[1].region[a] != P.dims[a])
-      return false;
-  return lift_xy_applicable(P.dims);
-}
-
-// ... and the full-size z pass follows (every dyadic shape): all three in one kernel
-bool fuse_xyz(const ShapePlan& P)
-{
-  if (!fuse_xy(P) || P.fwd.size() < 3 || P.fwd[2].axis != 2)
-    return false;
-  for (int a = 0; a < 3; a++)
-    if (P.fwd[2].region[a] != P.dims[a])
-      return false;
-  return lift_xyz_applicable(P.dims);
-}
-
-// LiftFuse of pass k (xform.h): the samples of its region that no LATER pass of the forward order
-// touches.  The later passes' regions are boxes at the origin; when one of them contains all the
-// others (dyadic plans: the next pass; wavelet-packet plans: the full-size x pass for every z pass)
-// the samples are those outside it.  Returns 0 when there are none, 1 when there are (inner = that
-// box), -1 when the later regions are not nested (no plan of build_plan is like that).
-int pass_fuse(const ShapePlan& P, size_t k, uint32_t inner[3])
-{
-  const LiftPass& ps = P.fwd[k];
-  inner[0] = inner[1] = inner[2] = 0;
-  for (size_t j = k + 1; j < P.fwd.size(); j++)
-    for (int a = 0; a < 3; a++)
-      inner[a] = std::max(inner[a], P.fwd[j].region[a]);
-  bool nested = k + 1 >= P.fwd.size();
-  for (size_t j = k + 1; j < P.fwd.size(); j++)
-    nested = nested || (P.fwd[j].region[0] == inner[0] && P.fwd[j].region[1] == inner[1] &&
-                        P.fwd[j].region[2] == inner[2]);
-  if (!nested)
-    return -1;
-  bool covers = true;
-  for (int a = 0; a < 3; a++)
-    covers = covers && inner[a] >= ps.region[a];
-  return covers ? 0 : 1;
-}
-
-// Can the lifting passes collect the largest coefficient / dequantise on the way?  Not when the
-// fused x-y kernel of the finest level would have to (slices: their next pass is a coarser level).
-bool plan_fusable(const ShapePlan& P)
-{
-  if (P.fwd.empty())
-    return false;
-  uint32_t inner[3];
-  for (size_t k = 0; k < P.fwd.size(); k++)
-    if (pass_fuse(P, k, inner) < 0)
-      return false;
-  if (fuse_xy(P) && (pass_fuse(P, 0, inner) != 0 || pass_fuse(P, 1, inner) != 0))
-    return false;
-  return true;
-}
-
-// Can the SECOND level of this shape run as one launch each way (k_lift2_fwd / k_lift2_inv, xform.h) instead of three
-// per-axis passes?  Passes 3, 4 and 5 have to be x, y and z of one region -- the low halves the fused finest-level kernel
-// leaves --, the region has to fit the sliding-window kernels with rows of at most 128 samples, and the passes have to
-// nest (plan_fusable: the kernels tell the box's samples from the others by LiftFuse::inner).
-static bool level2_fits(const ShapePlan& P)
-{
-  if (!fuse_xyz(P) || !plan_fusable(P) || P.fwd.size() < 6)
-    return false;
-  for (int k = 3; k < 6; k++) {
-    if (P.fwd[k].axis != k - 3)
-      return false;
-    for (int a = 0; a < 3; a++)
-      if (P.fwd[k].region[a] != P.dims[a] - P.dims[a] / 2)
-        return false;
-  }
-  uint32_t inner[3];
-  if (pass_fuse(P, 2, inner) <= 0 || inner[0] != P.fwd[3].region[0] || inner[1] != P.fwd[3].region[1] ||
-      inner[2] != P.fwd[3].region[2])
-    return false;
-  return lift2_applicable(P.fwd[3].region);
-}
-// Does it?  Decided once, when the plan is made: the encoder's launches (float_stages) and the decoder's memory layout
-// and launches (decode_group, enqueue_inverse) follow it.  By default only where the region has at least kLevel2Floor
-// samples along every axis, in both directions alike, because that is where it was measured to gain
-// (profiles/level2_fused_ab.txt): at 128^3 (256^3 chunks) decompression gains 1.8 % run against run; at 64^3, 32^3 and
-// 16^3 (128^3, 64^3, 32^3 chunks, 64 and 512 of them) compress and decompress times with and without it lie inside
-// each other's spread -- the launch is no slower there, the march through the slices costs what the three launches
-// cost -- with one exception, 512 chunks of 32^3, which decode 3 to 4 % faster with it.  A gain that cannot be told
-// from the spread is not taken: the small shapes keep the launches they had, which tests/test_gpu_level.py pins launch
-// by launch for 32^3 chunks (with the launch on, those tables would have to change: 12 k_lift_axis<false, 0> become 4
-// k_lift2_inv<true>; the 32^3 decode gain above is what that would buy).  Nothing between 64 and 128 was measured; the
-// floor sits midway.
-// SPERR_HIP_XYZ_LEVEL2=0: the three passes everywhere, for A/B runs and tests; =2: the launch wherever it fits, for the
-// same (the tests put every shape the kernels can go wrong at through them this way).  Read whenever a plan is made:
-// sperrhip_release() drops the plans.
-constexpr uint32_t kLevel2Floor = 96;
-bool plan_level2(const ShapePlan& P)
-{
-  const char* env = getenv("SPERR_HIP_XYZ_LEVEL2");
-  const int sw = env ? atoi(env) : 1;
-  if (sw == 0 || !level2_fits(P))
-    return false;
-  const uint32_t* r = P.fwd[3].region;
-  return sw == 2 || std::min(r[0], std::min(r[1], r[2])) >= kLevel2Floor;
-}
-
 // conditioner + forward transform of one batch: volume -> bb.vals (mean, constness, largest magnitude
 // in CoderState).  Run once per batch -- and once more before a 64-bit retry when the coder's arrays
 // lay over the chunk buffer (carve_enc): the same launches on the same input give the same bits.
@@ -1496,19 +1581,22 @@ int float_stages(hipStream_t ss, const ShapePlan& P, EncBatchBufs& bb, uint32_t 
   if (launch_condition<T>(ss, d_src, vd, bb.geom, nb, cd, P.nstrides, bb.strideMean, bb.strideMeanStride,
                           bb.vals, bb.valsStride, e.cst, !fuse, wantRange, orgAligned))
     return -1;
-  size_t k0 = 0;
-  // the passes after which samples have their final value also collect the largest magnitude
+  // The forward walk: the head, the second level as one launch where the schedule has it, then pass by pass.
+  // The passes after which samples have their final value also collect the largest magnitude
   // (src/SPECK_FLT.cpp:282-301): no pass over the coefficients of its own
-  const bool fuseMax = plan_fusable(P);
-  if (fuse_xyz(P)) {   // the three full-size passes in one kernel, straight from the volume
-    LiftFuse lf;
-    if (fuseMax && pass_fuse(P, 2, lf.inner) > 0)
+  const LiftSchedule& sch = P.schedule;
+  auto collect_max = [&](size_t k, LiftFuse& lf) {
+    if (sch.fusable && pass_fuse(P, k, lf.inner) > 0)
       lf.mode = 1;
+  };
+  const bool l2 = level2 && sch.level2;
+  if (sch.head == LiftSchedule::kHeadXYZ) {   // the three full-size passes in one kernel, straight from the volume
+    LiftFuse lf;
+    collect_max(2, lf);
     // The second level fused (plan_level2): the finest-level kernel writes the next level's box compact into the 32-bit
     // coefficient array, which only the quantiser writes, after the transform (one sample in eight, 8 of the array's 32 bytes for them); the
     // level-2 launch reads it and writes the corner of the chunk buffer.  (Not in front of the 64-bit retry: the
     // chunks that keep their 32-bit coefficients keep them there.)
-    const bool l2 = level2 && P.level2;
     double* box = l2 ? reinterpret_cast<double*>(bb.coef32) : nullptr;
     const size_t boxStride = e.coefStride / 2;
     if (l2 && (e.coefStride % 2 != 0 || (size_t)lf.inner[0] * lf.inner[1] * lf.inner[2] > boxStride))
@@ -1516,27 +1604,22 @@ int float_stages(hipStream_t ss, const ShapePlan& P, EncBatchBufs& bb, uint32_t 
     if (launch_lift_xyz(ss, true, bb.vals, bb.valsStride, nb, cd, e.cst, io, const_cast<T*>(d_src), vd,
                         bb.geom, &lf, nullptr, box, boxStride))
       return -1;
-    k0 = 3;
     if (l2) {
       LiftFuse l5;
-      if (pass_fuse(P, 5, l5.inner) > 0)
-        l5.mode = 1;
+      collect_max(5, l5);
       if (launch_lift2_fwd(ss, box, boxStride, bb.vals, bb.valsStride, nb, cd, P.fwd[3].region, e.cst, &l5))
         return -1;
-      k0 = 6;
     }
   }
-  else if (fuse_xy(P)) {   // the full-size x and y passes in one kernel, straight from the volume
+  else if (sch.head == LiftSchedule::kHeadXY) {   // the full-size x and y passes in one kernel, straight from the volume
     if (launch_lift_xy(ss, true, bb.vals, bb.valsStride, nb, cd, e.cst, io, const_cast<T*>(d_src), vd,
                        bb.geom))
       return -1;
-    k0 = 2;
   }
-  for (size_t k = k0; k < P.fwd.size(); k++) {
+  for (size_t k = LiftSchedule::fused_passes(sch.head, l2); k < P.fwd.size(); k++) {
     const LiftPass& ps = P.fwd[k];
     LiftFuse lf;
-    if (fuseMax && pass_fuse(P, k, lf.inner) > 0)
-      lf.mode = 1;
+    collect_max(k, lf);
     if (launch_lift(ss, true, bb.vals, bb.valsStride, nb, cd, ps.axis, ps.region, e.cst, k == 0 ? io : 0,
                     const_cast<T*>(d_src), vd, bb.geom, &lf))
       return -1;
@@ -1717,7 +1800,7 @@ void speck1d_level_offsets(OutlierBufs& ob, uint32_t N, uint64_t most)
 struct PweStage {
   OutlierBufs ob;
   std::vector<OutlierChunk> hoc;
-  std::vector<ChunkGeom> bricks;
+  std::vector<ChunkGeom> bricks;   // (enqueue_brick_inverse; lives until the stage's next wait for the stream)
   HostMarks hm;
 };
 // The encoder's own coefficients, for its reconstruction of what the decoder will see: complete, so no masks and no
@@ -1731,6 +1814,58 @@ static DequantSrc enc_dequant_src(const EncBatchBufs& bb, bool wide)
   s.signStride = bb.eb.signStride;
   return s;
 }
+// The brick inverse: what a decoder reconstructs of a batch, in the conditioned domain, as doubles in the chunk buffer
+// -- for the encoder's point-wise error stage and for the decoder's outlier correctors, which both need the values
+// before the mean is added.  By the decoder's own fused kernels: the coarser levels (passes k >= 3) in a compact
+// buffer of their box, dequantising as they load (LiftFuse mode 2), the finest level by k_lift_xyz_inv writing doubles
+// into the chunk buffer as if it were a volume of bricks (a chunk's offset rides in org[0], hence the 32-bit guard; no
+// mean added) -- instead of an inverse quantiser pass and fifteen per-axis passes over the whole chunk (14.9 of the
+// 56 ms a 1024^3 volume took to compress in PWE mode; 12.7 ms for 64 chunks of 256^3 with correctors to decode).
+// Never the second level as one launch: the box is one buffer, and k_lift2_inv cannot work in place.
+// A caller adds its own conditions to brick_inverse_fits: no chunk of the batch may have 64-bit coefficients.
+bool brick_inverse_fits(const ShapePlan& P, uint32_t nb, size_t valsStride)
+{
+  return P.schedule.brick && (uint64_t)nb * valsStride <= 0xffffffffull;
+}
+// box: the engine's buffer for the coarser levels' box and the bricks; bricks: the host copy of the latter, which has
+// to live until the stream has taken it
+int enqueue_brick_inverse(hipStream_t st, const ShapePlan& P, DevBuf& box, std::vector<ChunkGeom>& bricks, uint32_t nb,
+                          double* vals, size_t valsStride, CoderState* cst, const ChunkGeom* geom, const DequantSrc& src)
+{
+  const uint32_t* cd = P.dims;
+  const uint32_t* cbox = P.schedule.coarseBox;
+  const size_t boxStride = round_up((size_t)cbox[0] * cbox[1] * cbox[2], 64);
+  const size_t geomOff = round_up((size_t)nb * boxStride * 8, 256);
+  if (box.ensure(geomOff + (size_t)nb * sizeof(ChunkGeom) + 256))
+    return -1;
+  double* boxVals = static_cast<double*>(box.p);
+  ChunkGeom* d_bricks = reinterpret_cast<ChunkGeom*>(static_cast<char*>(box.p) + geomOff);
+  bricks.assign(nb, ChunkGeom{});
+  for (uint32_t i = 0; i < nb; i++)
+    bricks[i].org[0] = (uint32_t)((size_t)i * valsStride);
+  HIP_CHECK(hipMemcpyAsync(d_bricks, bricks.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, st));
+  auto fuse = [&](size_t k, LiftFuse& lf) {
+    if (pass_fuse(P, k, lf.inner) > 0) {
+      lf.mode = 2;
+      lf.src = src;
+    }
+    lf.bufx = cbox[0];
+    lf.bufy = cbox[1];
+  };
+  for (size_t k = P.fwd.size(); k-- > 3;) {
+    const LiftPass& ps = P.fwd[k];
+    LiftFuse lf;
+    fuse(k, lf);
+    if (launch_lift(st, false, boxVals, boxStride, nb, cd, ps.axis, ps.region, cst, 0, nullptr, VolDesc{}, geom, &lf))
+      return -1;
+  }
+  LiftFuse lf;
+  fuse(2, lf);
+  lf.noMean = 1;
+  const VolDesc brickVol{{cd[0], cd[1], cd[2]}};   // (rows of cx samples, slices of cx * cy: a brick)
+  return launch_lift_xyz(st, false, boxVals, boxStride, nb, cd, cst, 2, vals, brickVol, d_bricks, &lf);
+}
+
 template <typename T>
 int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb,
                     const T* d_src, VolDesc vd, const uint32_t cd[3], double tol, bool anyWide, PweStage& S)
@@ -1739,56 +1874,16 @@ int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs&
   HostMarks& hm = S.hm;
   OutlierBufs& ob = S.ob;
   std::vector<OutlierChunk>& hoc = S.hoc;
-  std::vector<ChunkGeom>& bricks = S.bricks;
   if (E.pweLastStream) {   // (a second batch of one call: the first one's stage is not waited for at its end any more)
     HIP_CHECK(hipStreamSynchronize(E.pweLastStream));
     E.pweLastStream = nullptr;
   }
   hm.mark("(3D coder done)", st);
-  // What the decoder will reconstruct, in the conditioned domain (src/SPECK_FLT.cpp:461-486).  Round 5: by the decoder's
-  // own kernels where the plan allows it -- the coarser levels in a compact buffer of their box, dequantising as they
-  // load (LiftFuse mode 2), the finest level by k_lift_xyz_inv writing doubles into the chunk buffer as if it were a
-  // volume of bricks (a chunk's offset rides in org[0]; no mean added) -- instead of an inverse quantiser pass and
-  // fifteen per-axis passes over the whole chunk (14.9 of the 56 ms a 1024^3 volume took to compress in this mode).
-  bricks.assign(nb, ChunkGeom{});   // (lives until the stage's next wait for the stream)
-  const bool fused = !anyWide && fuse_xyz(P) && plan_fusable(P) && P.fwd.size() >= 3 &&
-                     (uint64_t)nb * bb.valsStride <= 0xffffffffull;
-  if (fused) {
-    uint32_t cbox[3] = {1, 1, 1};
-    for (size_t k = 3; k < P.fwd.size(); k++)
-      for (int a = 0; a < 3; a++)
-        cbox[a] = std::max(cbox[a], P.fwd[k].region[a]);
-    const size_t cstride = round_up((size_t)cbox[0] * cbox[1] * cbox[2], 64);
-    const size_t geomOff = round_up((size_t)nb * cstride * 8, 256);
-    if (E.pweBox.ensure(geomOff + (size_t)nb * sizeof(ChunkGeom) + 256))
-      return -1;
-    double* cvals = static_cast<double*>(E.pweBox.p);
-    ChunkGeom* d_bricks = reinterpret_cast<ChunkGeom*>(static_cast<char*>(E.pweBox.p) + geomOff);
-    for (uint32_t i = 0; i < nb; i++) {
-      bricks[i].org[0] = (uint32_t)((size_t)i * bb.valsStride);
-      bricks[i].org[1] = bricks[i].org[2] = 0;
-    }
-    HIP_CHECK(hipMemcpyAsync(d_bricks, bricks.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, st));
-    auto fuse = [&](size_t k, LiftFuse& lf) {
-      if (pass_fuse(P, k, lf.inner) > 0) {
-        lf.mode = 2;
-        lf.src = enc_dequant_src(bb, false);
-      }
-      lf.bufx = cbox[0];
-      lf.bufy = cbox[1];
-    };
-    for (size_t k = P.fwd.size(); k-- > 3;) {
-      const LiftPass& ps = P.fwd[k];
-      LiftFuse lf;
-      fuse(k, lf);
-      if (launch_lift(st, false, cvals, cstride, nb, cd, ps.axis, ps.region, e.cst, 0, nullptr, vd, bb.geom, &lf))
-        return -1;
-    }
-    LiftFuse lf;
-    fuse(2, lf);
-    lf.noMean = 1;
-    const VolDesc brickVol{{cd[0], cd[1], cd[2]}};   // (rows of cx samples, slices of cx * cy: a brick)
-    if (launch_lift_xyz(st, false, cvals, cstride, nb, cd, e.cst, 2, bb.vals, brickVol, d_bricks, &lf))
+  // What the decoder will reconstruct, in the conditioned domain (src/SPECK_FLT.cpp:461-486): by the brick inverse
+  // where the plan allows it and no chunk has 64-bit coefficients, else by an inverse quantiser pass and the per-axis
+  // passes over the whole chunk
+  if (!anyWide && brick_inverse_fits(P, nb, bb.valsStride)) {
+    if (enqueue_brick_inverse(st, P, E.pweBox, S.bricks, nb, bb.vals, bb.valsStride, e.cst, bb.geom, enc_dequant_src(bb, false)))
       return -1;
   }
   else {
@@ -2306,7 +2401,7 @@ struct EncodeCall {
     HIP_CHECK(hipMemsetAsync(e.cst, 0, nb * sizeof(CoderState), b.ss));
     if (float_stages<T>(b.ss, *b.P, bb, nb, b.P->dims, d_src, vd, b.orgAligned, mode == 2))
       return -1;
-    if (launch_maxabs_q(b.ss, bb.vals, bb.valsStride, nb, b.P->N, e.cst, plan_fusable(*b.P)))
+    if (launch_maxabs_q(b.ss, bb.vals, bb.valsStride, nb, b.P->N, e.cst, b.P->schedule.fusable))
       return -1;
     if (mode == 2 && psnr_q_search(b.ss, *b.P, bb, nb, quality, hcKeep.emplace_back(), hcKeep.emplace_back()))
       return -1;
@@ -2720,41 +2815,7 @@ int trunc_impl(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol,
   return 0;
 }
 
-// the lists of the larger sets GPU-wide (k_lis_hi); SPERR_HIP_LIS_HI=0 and regular trees whose geometry
-// tables do not fit the kernel's LDS go to k_lis_mx, which takes any shape (k_lis_tables, one workgroup
-// per chunk, was the table kernel of rounds 1-3: removed in round 4)
 bool g_lis_stamps_on = false;
-constexpr int kHiMaxK = 9;   // longest class chain k_lis_hi takes (chunk dims up to 1024)
-bool use_lis_hi(const ShapePlan& P, bool tables)
-{
-  static const bool hiEnv = !(getenv("SPERR_HIP_LIS_HI") && atoi(getenv("SPERR_HIP_LIS_HI")) == 0);
-  return hiEnv && tables && P.ht.grids.size() <= 288 && P.ht.roots.size() <= 48 &&
-         P.maxK >= 1 && P.maxK <= kHiMaxK;
-}
-// every LIS level is regular and the table kernels (k_lis_l0 / _l1 / _hi) can take the shape
-bool use_tables(const ShapePlan& P)
-{
-  if (!P.ht.allRegular || P.maxK < 1)
-    return false;
-  return use_lis_hi(P, true);
-}
-// lists that mix set shapes (any chunk extent that is not a power of two, every slice): k_lis_mx (speck_mx.hip:
-// rows keyed by shape class, several workgroups per chunk, only the walk serial).  SPERR_HIP_LIS_MIXED=0, and trees
-// the class machinery does not take (more than 254 classes, 48 roots, 352 grids): k_lis_walk, the serial walk.
-// The switch does not apply to the 2D coder's forest: only k_lis_mx has the type-I phase a slice needs, and every
-// slice's forest fits it (DESIGN.md section 4c, tests/test_slice_forest_host.py).
-// (k_lis_mixed, the one-workgroup-per-chunk kernel of rounds 2-3 whose formulation k_lis_mx took over, was removed
-// at the end of round 4.)
-bool use_mixed(const ShapePlan& P)
-{
-  static const bool mixEnv = !(getenv("SPERR_HIP_LIS_MIXED") && atoi(getenv("SPERR_HIP_LIS_MIXED")) == 0);
-  const bool twoD = (P.ht.flags & spk::kTree2D) != 0;
-  if ((!twoD && !mixEnv) || use_tables(P) || P.ht.cls.empty() || P.ht.roots.size() > 48 || P.ht.grids.size() > 352 ||
-      P.ht.mxSlot.size() != P.ht.cls.size())
-    return false;
-  return 2 * kMxS + 256 <= kMxRing && ((kMxS + kMxM) >> 6) + 5 <= 64 && kMxM >= 192 &&
-         mx_smem_bytes(kMxS, kMxM, kMxQ) <= 138u * 1024u;   // (k_lis_mx has 21 KB of static LDS)
-}
 std::vector<uint64_t> g_lis_stamps_host;   // chunk 0 of the last decoded batch
 
 struct DecBatchBufs {
@@ -2843,7 +2904,7 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
     //  k_lis_walk set mask bits themselves)
     uint8_t* tb = nullptr;
     TAKE(tb, uint8_t, d.tileStride * B);
-    d.tileBorn = use_tables(P) ? tb : nullptr;
+    d.tileBorn = P.dec.tables ? tb : nullptr;
   }
   d.lipResStride = Npad / 64 + 2;
   TAKE(d.lipSig, uint64_t, d.lipResStride * B);
@@ -2906,7 +2967,7 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   d.mxM = kMxM;
   d.mxQ = kMxQ;
   d.mxSmemBytes = mx_smem_bytes(kMxS, kMxM, kMxQ);
-  if (use_mixed(P))   // (k_lis_mx keeps its look-back words in the same array: kMxWordsPerRegion per region of mxS bits)
+  if (P.dec.mixed)   // (k_lis_mx keeps its look-back words in the same array: kMxWordsPerRegion per region of mxS bits)
     d.hiFlagStride = std::max<size_t>(d.hiFlagStride, ((d.streamStride * 64 + N) / kMxS + 4) * kMxWordsPerRegion);
   TAKE(d.hiFlags, unsigned long long, d.hiFlagStride * B);
   d.iRoots = P.d_iRoots;
@@ -3243,16 +3304,8 @@ size_t dec_bytes_per_chunk(const ShapePlan& P, uint64_t maxPayload, size_t valsE
   return probe.used;
 }
 
-// the list kernels a chunk shape takes
-DecPlanHost dec_plan_host(const ShapePlan& P)
-{
-  DecPlanHost ph{P.d_initLIS, P.d_initLen, use_tables(P), P.l0Level >= 0 && P.ht.grids.size() <= 288,
-                 P.l1Level >= 0 && P.ht.grids.size() <= 288, P.maxK};
-  ph.l2 = ph.l1 && P.l2Level >= 0;
-  ph.hi = use_lis_hi(P, ph.tables);   // the lists of the larger sets GPU-wide
-  ph.mixed = use_mixed(P);
-  return ph;
-}
+// the list kernels a chunk shape takes: the plan's copy, for the caller to complete with what its call decides
+const DecPlanHost& dec_plan_host(const ShapePlan& P) { return P.dec; }
 
 // One decompression call (decompress_impl), stage by stage.  What is decoded and where it goes is `req`'s to say
 // (DecodeRequest: its source and its output); no stage asks anything else
@@ -3454,7 +3507,7 @@ struct DecodeCall {
     size_t nmx = 0;
     for (auto& h : groups) {
       ShapePlan* Q = plan_of(h.first);
-      if (Q && use_mixed(*Q))
+      if (Q && Q->dec.mixed)
         nmx += h.second.size();
     }
     static const uint32_t mxBudget = getenv("SPERR_HIP_MX_WGS") ? (uint32_t)atoi(getenv("SPERR_HIP_MX_WGS")) : 208u;
@@ -3468,7 +3521,7 @@ struct DecodeCall {
       mxGroupsCall = std::min<uint32_t>(8u, std::max<uint32_t>(2u, (uint32_t)(mxBudget / (nmx * sharers))));
   }
   // (groups of 32 and more chunks of a shape the table kernels take keep the sub-batch scheme)
-  static bool deferrable(const ShapePlan& P, size_t nchunksOfShape) { return nchunksOfShape < 32 || !use_tables(P); }
+  static bool deferrable(const ShapePlan& P, size_t nchunksOfShape) { return nchunksOfShape < 32 || !P.dec.tables; }
   // Refinement bit planes (speck_dec.h, DecBuffers::refPlanes): as many as the chunks of a group with 32-bit
   // coefficients have planes (byte 17 of a chunk: src/SPECK_INT.cpp:284-308)
   uint32_t ref_planes_of(const ShapePlan& P, const std::vector<Ref>& refs) const
@@ -3489,18 +3542,15 @@ struct DecodeCall {
   size_t compact_box(const ShapePlan& P, const std::vector<Ref>& refs, uint32_t cbox[3]) const
   {
     cbox[0] = cbox[1] = cbox[2] = 0;
-    if (!fuse_xyz(P) || !plan_fusable(P) || req.levels || req.slices || anyOutlier || P.fwd.size() < 3)
+    if (!P.schedule.brick || req.levels || req.slices || anyOutlier)
       return 0;
     for (const Ref& r : refs) {
       const uint8_t* hd = heads.data() + (size_t)r.slot * 32;
       if (ci.len[r.gid] >= 26 && !(hd[0] & 0x01) && hd[17] > 32)
         return 0;   // a chunk with 64-bit coefficients
     }
-    for (size_t k = 3; k < P.fwd.size(); k++)
-      for (int a = 0; a < 3; a++)
-        cbox[a] = std::max(cbox[a], P.fwd[k].region[a]);
     for (int a = 0; a < 3; a++)
-      cbox[a] = std::max(cbox[a], 1u);
+      cbox[a] = P.schedule.coarseBox[a];
     if (const Window* lvl = req.level())   // (a chunk with one level of transform has no coarser pass: the box still holds the level's corner)
       for (int a = 0; a < 3; a++)
         cbox[a] = std::max(cbox[a], lvl->m.cres[lvl->h][a]);
@@ -3508,7 +3558,7 @@ struct DecodeCall {
   }
   // The second level of a group runs as one launch (plan_level2) where the group works in the compact box, whose every
   // pass dequantises on the way; a single level's decode (enqueue_level) never reaches that launch
-  bool level2_of(const ShapePlan& P, size_t compactElems) const { return P.level2 && compactElems != 0 && !req.level(); }
+  bool level2_of(const ShapePlan& P, size_t compactElems) const { return P.schedule.level2 && compactElems != 0 && !req.level(); }
   // room for all the small groups at once, if the memory is there
   int size_deferred()
   {
@@ -3541,7 +3591,7 @@ struct DecodeCall {
     ShapePlan* P = plan_of(shape);
     if (!P)
       return -1;
-    if (req.slices && !use_mixed(*P)) {   // (no slice has such a forest, DESIGN.md section 4c: k_lis_walk has no type-I phase)
+    if (req.slices && !P->dec.mixed) {   // (no slice has such a forest, DESIGN.md section 4c: k_lis_walk has no type-I phase)
       fprintf(stderr, "[sperr_hip] slice of %u x %u: its forest does not fit k_lis_mx\n", P->dims[0], P->dims[1]);
       return -1;
     }
@@ -3557,7 +3607,7 @@ struct DecodeCall {
     b.refNPlanes = ref_planes_of(*P, refs);
     // the inverse passes dequantise on the way (not for the resolution hierarchy, whose coarsest
     // level is read before any pass has run)
-    b.fuseDq = plan_fusable(*P) && !req.levels && !req.slices;
+    b.fuseDq = P->schedule.fusable && !req.levels && !req.slices;
     b.level2 = level2_of(*P, b.compactElems) && b.fuseDq;
     const size_t per = dec_bytes_per_chunk(*P, b.maxPayload, b.compactElems, b.refNPlanes, req.cropped(), b.level2);
     size_t fr = 0, tot = 0;
@@ -3598,7 +3648,7 @@ struct DecodeCall {
       //  eight normal-priority hardware queues -- one of which the caller's stream has -- put two groups on one
       //  queue, one behind the other.  The regular chunks take the 1D decoder's idle high-priority stream: a queue
       //  pool of its own, 1000^3 in 256^3 chunks 178 -> see DESIGN.md section 9)
-      b.deferStream = (mxGroupsCall != 0 && use_tables(*b.P)) ? E.outlQ[1] : E.sub[deferNext++ % kSubStreams];
+      b.deferStream = (mxGroupsCall != 0 && b.P->dec.tables) ? E.outlQ[1] : E.sub[deferNext++ % kSubStreams];
       deferOff += round_up(needBytes, 4096);
     }
     if (pick_sub_batches(b, A, b0, nbAll))
@@ -3904,36 +3954,15 @@ struct DecodeCall {
     DecBatchBufs& bb = S.bb;
     DecBuffers& d = bb.db;
     const int io = std::is_same<T, float>::value ? 1 : 2;
-    const bool fxyz = fuse_xyz(P) && !S.outliers;
-    const bool fxy = fuse_xy(P) && !S.outliers && !fxyz;
-    // With outlier correctors the transformed values have to stay doubles a little longer -- but they can still
-    // come from the fused kernels (round 5): the coarser levels in a compact buffer of their box, the finest level
-    // by k_lift_xyz_inv writing doubles, no mean added, into the chunk buffer as if it were a volume of bricks (a
-    // chunk's offset rides in org[0]); the correctors and the scatter pass follow as before.  (Fifteen per-axis
-    // passes over the whole chunk before: 12.7 ms for 64 chunks of 256^3.)
-    const bool fbrick = S.outliers && fuse_xyz(P) && b.fuseDq && S.maxWide == 0 && P.fwd.size() >= 3 &&
-                        b.compactElems == 0 && (uint64_t)nb * bb.valsStride <= 0xffffffffull;
-    uint32_t bbox[3] = {1, 1, 1};
-    double* boxVals = nullptr;
-    size_t boxStride = 0;
-    ChunkGeom* d_bricks = nullptr;
-    if (fbrick) {
-      for (size_t k = 3; k < P.fwd.size(); k++)
-        for (int a = 0; a < 3; a++)
-          bbox[a] = std::max(bbox[a], P.fwd[k].region[a]);
-      boxStride = round_up((size_t)bbox[0] * bbox[1] * bbox[2], 64);
-      const size_t geomOff = round_up((size_t)nb * boxStride * 8, 256);
-      if (E.decBox[q].ensure(geomOff + (size_t)nb * sizeof(ChunkGeom) + 256))
-        return -1;
-      boxVals = static_cast<double*>(E.decBox[q].p);
-      d_bricks = reinterpret_cast<ChunkGeom*>(static_cast<char*>(E.decBox[q].p) + geomOff);
-      S.bricks.resize(nb);
-      for (uint32_t i = 0; i < nb; i++) {
-        S.bricks[i].org[0] = (uint32_t)((size_t)i * bb.valsStride);
-        S.bricks[i].org[1] = S.bricks[i].org[2] = 0;
-      }
-      HIP_CHECK(hipMemcpyAsync(d_bricks, S.bricks.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
-    }
+    // The inverse walk: the per-axis passes from the coarsest down to where the fused launches take over, then the
+    // second level as one launch where the batch has it, then the head.
+    // With outlier correctors the transformed values have to stay doubles a little longer, so no head writes the
+    // volume -- but they can still come from the fused kernels: the brick inverse, where the group dequantises on the
+    // way, has 32-bit coefficients only and no compact buffer.  The correctors and the scatter pass follow either way
+    const bool fbrick = S.outliers && b.fuseDq && S.maxWide == 0 && b.compactElems == 0 &&
+                        brick_inverse_fits(P, nb, bb.valsStride);
+    const LiftSchedule::Head head = S.outliers ? LiftSchedule::kNoHead : P.schedule.head;
+    const bool fxyz = head == LiftSchedule::kHeadXYZ, fxy = head == LiftSchedule::kHeadXY;
     // a level of the inverse transform is 3 passes (z y x) of a dyadic chunk, 2 (y x) of a slice
     const size_t perLevel = req.slices ? 2 : 3;
     auto sub_volume = [&](size_t k) -> int {   // before pass k, the first of its level
@@ -3947,46 +3976,37 @@ struct DecodeCall {
                cd[0], cd[1], cd[0], cd[1], cd[2], r[0], r[1], r[2], mr->grid[0], mr->grid[1], mr->d_level[h]);
       return 0;
     };
-    auto dequant_fuse = [&](size_t k, LiftFuse& lf) {
-      pass_dequant(b, bb, k, lf);
-      if (fbrick) {
-        lf.bufx = bbox[0];
-        lf.bufy = bbox[1];
-      }
-    };
     // (the second level fused: its three passes are one launch from the compact box into a second one, which the
     //  finest level then reads -- in place a tile's outputs would land in rows other tiles still read)
     const bool l2 = b.level2 && fxyz && bb.vals2 != nullptr;
-    for (size_t k = P.fwd.size(); k-- > (l2 ? 6u : (fxyz || fbrick) ? 3u : fxy ? 2u : 0u);) {
-      const LiftPass& ps = P.fwd[k];
-      if (k % perLevel == perLevel - 1 && sub_volume(k))
-        return -1;
-      LiftFuse lf;
-      dequant_fuse(k, lf);
-      const bool last = k == 0 && !S.outliers;   // (the pass that writes the volume / the box)
-      if (launch_lift(ss, false, fbrick ? boxVals : bb.vals, fbrick ? boxStride : bb.valsStride, nb, cd, ps.axis,
-                      ps.region, d.cst, last ? io : 0, d_dst, vd, bb.geom, &lf, last ? bb.crop : nullptr))
+    if (fbrick) {   // every pass, into the chunk buffer, as doubles
+      if (enqueue_brick_inverse(ss, P, E.decBox[q], S.bricks, nb, bb.vals, bb.valsStride, d.cst, bb.geom,
+                                dequant_src(b, bb, false)))
         return -1;
     }
-    if (fbrick) {   // the finest level into the chunk buffer, as doubles
-      LiftFuse lf;
-      dequant_fuse(2, lf);
-      lf.noMean = 1;
-      const VolDesc brickVol{{cd[0], cd[1], cd[2]}};
-      if (launch_lift_xyz(ss, false, boxVals, boxStride, nb, cd, d.cst, 2, bb.vals, brickVol, d_bricks, &lf))
-        return -1;
-    }
+    else
+      for (size_t k = P.fwd.size(); k-- > LiftSchedule::fused_passes(head, l2);) {
+        const LiftPass& ps = P.fwd[k];
+        if (k % perLevel == perLevel - 1 && sub_volume(k))
+          return -1;
+        LiftFuse lf;
+        pass_dequant(b, bb, k, lf);
+        const bool last = k == 0 && !S.outliers;   // (the pass that writes the volume / the box)
+        if (launch_lift(ss, false, bb.vals, bb.valsStride, nb, cd, ps.axis, ps.region, d.cst, last ? io : 0, d_dst, vd,
+                        bb.geom, &lf, last ? bb.crop : nullptr))
+          return -1;
+      }
     if (fxyz) {   // the finest level: z, y and x pass in one kernel, into the volume
       if (sub_volume(2))
         return -1;
       if (l2) {
         LiftFuse l5;
-        dequant_fuse(5, l5);
+        pass_dequant(b, bb, 5, l5);
         if (launch_lift2_inv(ss, bb.vals, bb.valsStride, bb.vals2, bb.valsStride, nb, cd, P.fwd[3].region, d.cst, &l5))
           return -1;
       }
       LiftFuse lf;
-      dequant_fuse(2, lf);
+      pass_dequant(b, bb, 2, lf);
       if (launch_lift_xyz(ss, false, l2 ? bb.vals2 : bb.vals, bb.valsStride, nb, cd, d.cst, io, d_dst, vd, bb.geom, &lf, bb.crop))
         return -1;
     }

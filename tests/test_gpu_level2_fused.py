@@ -13,7 +13,7 @@ the level-2 region has at least 96 samples along every axis (plan_level2, engine
 drops that floor, so that the kernels meet every shape of this file.  The default is checked as well: the same
 containers and decodes, the new kernels exactly where `by_default()` says.
 
-`level2()` restates level2_fits (engine.hip): a dyadic plan whose finest level is fused (test_gpu_xyz_passes.fused), a second level
+`level2()` restates level2_fits (engine.hip, one of the rules behind ShapePlan::schedule): a dyadic plan whose finest level is fused (test_gpu_xyz_passes.fused), a second level
 on every axis -- an axis of n samples is halved while n >= 9, so the level-2 region has at least 9 samples a side and a
 chunk 16 samples a side has no second level at all --, and region rows of at most 128 samples.
 

@@ -6,7 +6,7 @@ Everything is compared against the CPU oracle, never against the library itself:
 through the outliers it finds), a decoded volume bit for bit as fp32 and as fp64 (the inverse kernel, IO 1 and 2).
 
 The fused kernels run only for chunks whose transform is dyadic with full-size x, y and z passes first (fuse_xyz,
-engine.hip); every other shape takes the per-axis kernels.  `fused()` below restates that rule, and FUSED / UNFUSED say
+engine.hip: ShapePlan::schedule.head); every other shape takes the per-axis kernels.  `fused()` below restates that rule, and FUSED / UNFUSED say
 for every shape of this file which path it is meant to take: a shape edited off its path fails test_shapes_take_the_path_meant.
 
 The cases are the corners of the passes' task arithmetic: row lengths 2 (too short for these kernels: the other path has
@@ -67,7 +67,7 @@ def xforms(n):
 
 
 def fused(ch):
-    """fuse_xyz (engine.hip): a dyadic plan (can_use_dyadic), every axis transformed, 24 staged rows within 6144 samples"""
+    """fuse_xyz (engine.hip; the plan keeps its answer as schedule.head): a dyadic plan (can_use_dyadic), every axis transformed, 24 staged rows within 6144 samples"""
     xy, z = xforms(min(ch[0], ch[1])), xforms(ch[2])
     return min(ch) >= 9 and 24 * ch[0] <= 6144 and (xy == z or (xy >= 5 and z >= 5))
 

@@ -1,7 +1,7 @@
 """CPU: no slice has a forest that k_lis_mx cannot decode.  A slice is decoded on the 2D coder's forest
 (spk::build_tree(x, y, 1, twoD), the plan of key (x, y, 0)) by k_lis_mx, the only list kernel with the type-I phase:
 there is no other 2D decoder to fall back to.  tests/cpp/slice_forest_check.cpp builds the forest of every shape
-below and checks what use_mixed() and use_tables() (engine.hip) test: classes exist (at most 254, or build_classes
+below and checks what use_mixed() and use_tables() (engine.hip, the rules behind ShapePlan::dec) test: classes exist (at most 254, or build_classes
 gives up and leaves none), at most 48 roots and 352 grids, a column entry per class, and never `allRegular`.
 DESIGN.md section 4c argues why these counts stay bounded as the extents grow; this pins the finite part."""
 import os
