@@ -526,6 +526,27 @@ static bool use_mixed(const ShapePlan& P, bool tables)
   return 2 * kMxS + 256 <= kMxRing && ((kMxS + kMxM) >> 6) + 5 <= 64 && kMxM >= 192 &&
          mx_smem_bytes(kMxS, kMxM, kMxQ) <= 138u * 1024u;   // (k_lis_mx has 21 KB of static LDS)
 }
+// The decoder's sweep from a plane's refinement to the next plane's census as one launch, and the plane's end with the
+// next scan as another (k_pix_turn, k_dec_turn, speck_dec.hip: 14 launches a plane instead of 16, a mask word's second
+// sigOld load and the read-modify-write of its plane word gone)?  Decided once, when the plan is made; the launcher
+// takes it where the refinement goes through bit planes (32-bit coefficients).  By default only for chunks of at least
+// kPixTurnFloor decoder tiles (256 mask words = 16384 samples each: 64 tiles = 1 Mi samples), which is where it was
+// measured (profiles/pix_turn_ab.txt, 256^3 chunks: 1024 tiles).  Below that a plane's sweeps are a handful of workgroups,
+// and tests/test_gpu_level.py and tests/test_gpu_lift_schedule.py pin the decoder's launches one by one for chunks of 32^3,
+// 16^3, 2 x 23 x 20, 512 x 20 x 20 and for slices: at most 13 tiles.  Nothing between 13 and 64 tiles is pinned or measured.
+// SPERR_HIP_PIX_TURN=0: the four kernels everywhere, for A/B runs and tests; =2: the sweep wherever it fits, for the same.
+// Read whenever a plan is made: sperrhip_release() drops the plans.
+constexpr uint32_t kPixTurnFloor = 64;
+static bool plan_pix_turn(const ShapePlan& P)
+{
+  const char* env = getenv("SPERR_HIP_PIX_TURN");
+  const int sw = env ? atoi(env) : 1;
+  if (sw == 0)
+    return false;
+  const size_t decTiles = (round_up((size_t)P.N, 512) / 64 + kThreads - 1) / kThreads;   // DecBuffers::nPixTiles
+  return sw == 2 || decTiles >= kPixTurnFloor;
+}
+
 // the list kernels a chunk shape takes, once its tree, its tables and its list levels are there
 static DecPlanHost plan_list_kernels(const ShapePlan& P, bool tables)
 {
@@ -534,6 +555,7 @@ static DecPlanHost plan_list_kernels(const ShapePlan& P, bool tables)
   ph.l2 = ph.l1 && P.l2Level >= 0;
   ph.hi = use_lis_hi(P, ph.tables);   // the lists of the larger sets GPU-wide
   ph.mixed = use_mixed(P, tables);
+  ph.pixTurn = plan_pix_turn(P);
   return ph;
 }
 

@@ -204,6 +204,8 @@ struct DecPlanHost {
                                //   whose k_lis_mx workgroups hold most CUs (1000^3 in 256^3 chunks: 150 -> 146 ms with 4)
   uint32_t mxGroups = 0;       // workgroups per chunk of k_lis_mx (0: the launcher's own choice by the batch's size) --
                                //   the caller knows how many such chunks of OTHER shapes decode beside this batch
+  bool pixTurn = false;        // a plane's refinement and the next plane's census as one tile sweep, its end and the next
+                               //   scan as one launch (k_pix_turn, k_dec_turn): where the refinement goes through bit planes
   bool skipFinish = false;     // the caller's inverse quantiser completes the coefficients
   // Fixed-rate streams run out of bits many planes above plane 0, and the launches of a plane that
   // holds no work still cost about 0.1 ms per batch.  With d_live set (kLiveSlots device words) the

@@ -12,7 +12,9 @@
 //   LIS phase    (k_lis_l0/_l1/_hi; k_lis_mx, speck_mx.hip, for lists that mix set shapes)  what each bit means depends
 //                on every earlier bit of the phase: one workgroup per chunk; chunks run
 //                concurrently;
-//   refinement   (k_ref_apply2)  the j-th significant pixel in raster order takes bit j.
+//   refinement   (k_ref_apply2; k_ref_deposit with bit planes)  the j-th significant pixel in raster order takes bit j;
+//   turn         (k_pix_turn, k_dec_turn where the plan says so)  a plane's refinement and the next plane's census
+//                (k_dec_count) as one tile sweep, the plane's end and the next scan (k_dec_scan) as one launch.
 //
 // Bits past the available length read as zero (the reference zero-pads a truncated stream,
 // SPECK_INT.cpp:95-105); the loop stops where the reference's does.
@@ -139,17 +141,10 @@ constexpr int kDecTileWords = kThreads;
 // `tag`: only when a leaf of the word's 32-leaf block split on plane tag - 1 (k_leaf_apply leaves
 // 1 + the plane in leafDirty): what earlier planes did to the block was folded when they ended, and
 // a block's 64 bytes of states are not worth reading again on every plane (0: whatever its tag).
-__device__ __forceinline__ bool leaf_word(const DecBuffers& b, uint32_t c, uint32_t wi,
-                                          uint64_t& born, uint64_t& sig, uint64_t& neg, uint32_t tag)
+// the states of the 32 leaves under a mask word, `wl` its entry of wordLeaf (not 0xffffffff): leaf_word below
+__device__ __forceinline__ bool leaf_states(const DecBuffers& b, uint32_t c, uint32_t wl,
+                                            uint64_t& born, uint64_t& sig, uint64_t& neg)
 {
-  born = sig = neg = 0;
-  if (b.wordLeaf == nullptr)
-    return false;
-  const uint32_t wl = b.wordLeaf[wi];
-  if (wl == 0xffffffffu)
-    return false;
-  if (tag && b.leafDirty[c * b.leafDirtyStride + (wl >> 5)] != (uint8_t)tag)
-    return false;
   const uint32_t sel = (wl & 3u) * 2u;
   const uint4* q = reinterpret_cast<const uint4*>(b.leafState + c * b.leafStateStride + (wl & ~31u));
   uint32_t v[16];
@@ -181,6 +176,20 @@ __device__ __forceinline__ bool leaf_word(const DecBuffers& b, uint32_t c, uint3
   sig = (uint64_t)si[0] | ((uint64_t)si[1] << 32);
   neg = (uint64_t)ne[0] | ((uint64_t)ne[1] << 32);
   return true;
+}
+
+__device__ __forceinline__ bool leaf_word(const DecBuffers& b, uint32_t c, uint32_t wi,
+                                          uint64_t& born, uint64_t& sig, uint64_t& neg, uint32_t tag)
+{
+  born = sig = neg = 0;
+  if (b.wordLeaf == nullptr)
+    return false;
+  const uint32_t wl = b.wordLeaf[wi];
+  if (wl == 0xffffffffu)
+    return false;
+  if (tag && b.leafDirty[c * b.leafDirtyStride + (wl >> 5)] != (uint8_t)tag)
+    return false;
+  return leaf_states(b, c, wl, born, sig, neg);
 }
 
 // merges last plane's new significances (sigNew and the leaf states), then counts LIP candidates
@@ -314,12 +323,10 @@ __global__ void __launch_bounds__(kThreads) k_dec_count(DecBuffers b, int p)
   }
 }
 
-__global__ void __launch_bounds__(kThreads) k_dec_scan(DecBuffers b, int p)
+// offsets of the tiles' candidates, their totals, and the plane's counters back to zero: one workgroup per chunk
+// (k_dec_scan, and k_dec_turn after the end of the plane before)
+__device__ __forceinline__ void dec_scan_chunk(const DecBuffers& b, DecState& s, uint32_t c, uint64_t* sm)
 {
-  const uint32_t c = blockIdx.x;
-  DecState& s = b.st[c];
-  DEC_ACTIVE_OR_RETURN(s, p);
-  __shared__ uint64_t sm[kThreads / 64 + 1];
   uint32_t* tl = b.tileLip + c * b.tileStride;
   uint32_t* tr = b.tileRef + c * b.tileStride;
   uint32_t* ol = b.tileLipOff + c * b.tileStride;
@@ -350,6 +357,15 @@ __global__ void __launch_bounds__(kThreads) k_dec_scan(DecBuffers b, int p)
     for (int g = 0; g < 8; g++)
       s.hiBornCnt[g] = s.hiLeafCnt[g] = 0;
   }
+}
+
+__global__ void __launch_bounds__(kThreads) k_dec_scan(DecBuffers b, int p)
+{
+  const uint32_t c = blockIdx.x;
+  DecState& s = b.st[c];
+  DEC_ACTIVE_OR_RETURN(s, p);
+  __shared__ uint64_t sm[kThreads / 64 + 1];
+  dec_scan_chunk(b, s, c, sm);
 }
 
 // The k-th LIP candidate in raster order owns token k of the scan: take the results k_lip_apply
@@ -3547,6 +3563,256 @@ __global__ void __launch_bounds__(kThreads) k_ref_deposit(DecBuffers b, int p)
   }
 }
 
+// what k_pix_turn's thread knows of its mask word before it works on it
+struct PixWord {
+  uint64_t sig, fresh, born;
+  uint32_t wl;       // the word's entry of wordLeaf; 0xffffffff: no leaves to fold (none mapped, no word here, no census)
+  uint32_t refOff;   // tileRefOff of the tile
+};
+// ... of the first tile in `todo` (bit q: tile tile0 + q * gridDim.x); nothing is loaded when there is none
+__device__ __forceinline__ PixWord pix_word_load(const DecBuffers& b, uint32_t c, uint32_t tile0, uint32_t todo,
+                                                 uint32_t refTiles, uint32_t countTiles, uint32_t nw)
+{
+  PixWord w{0ull, 0ull, 0ull, 0xffffffffu, 0u};
+  if (todo == 0)
+    return w;
+  const uint32_t q = (uint32_t)__ffs((int)todo) - 1u;
+  const uint32_t tile = tile0 + q * gridDim.x;
+  const uint32_t wi = tile * kDecTileWords + threadIdx.x;
+  if ((refTiles >> q) & 1u)
+    w.refOff = b.tileRefOff[c * b.tileStride + tile];
+  if (wi < nw) {
+    w.sig = b.sigOld[c * b.maskPixStride + wi];
+    if ((countTiles >> q) & 1u) {
+      w.fresh = b.sigNew[c * b.maskPixStride + wi];
+      w.born = b.bornM[c * b.maskPixStride + wi];
+      if (b.wordLeaf != nullptr)
+        w.wl = b.wordLeaf[wi];
+    }
+  }
+  return w;
+}
+
+// One sweep over the mask words from plane p's refinement to plane p - 1's census: k_ref_deposit(p), then -- where the
+// chunk goes on, which is what k_dec_plane_end(p) is about to decide from the same DecState -- k_dec_count(p - 1).  Both
+// are "thread = mask word wi of the tile", both read sigOld[wi], and the second read plane p's word back to OR the '1's
+// of the samples found on plane p into it: here the word's refinement bits wait in a register for them, and the word is
+// stored once.  The grid, the stride over tiles and the test for kAhead tiles at once are k_dec_count's; a tile is taken
+// when it has refinement candidates (tileRef, read before the tile's new counts are stored) or when k_dec_count would
+// take it.  The kernel only reads DecState and is tile-local: k_dec_turn does the chunk's bookkeeping after it.
+// A chunk whose first plane is p - 1 (p >= nbp) has no refinement half; the launch before the first plane is all census.
+__global__ void __launch_bounds__(kThreads, 5) k_pix_turn(DecBuffers b, int p)
+{
+  const uint32_t c = blockIdx.y;
+  const DecState& s = b.st[c];
+  if (!s.active || s.done)
+    return;
+  const bool inPlane = p < s.nbp;
+  const uint64_t avail = s.avail, pos0 = s.pos;
+  const uint32_t nRef = s.nRef;
+  const bool refOn = inPlane && (uint32_t)p < b.refNPlanes;
+  const bool endsHere = inPlane && (p == 0 || (uint64_t)nRef >= avail - pos0);   // k_dec_plane_end(p): done
+  const bool countOn = !endsHere && p - 1 >= 0 && p - 1 < s.nbp;
+  if (!refOn && !countOn)
+    return;
+  const bool partial = inPlane && pos0 + (uint64_t)nRef > avail;   // the stream ends inside this pass
+  // (two rows each, taken in turn: a row is written again only after the barrier of the other row's use, which no
+  //  wavefront passes before every wavefront has read what it needs of this one -- one barrier per scan or reduction)
+  __shared__ uint32_t smRef[2][kThreads / 64];
+  __shared__ uint32_t smCnt[2][kThreads / 64];
+  __shared__ uint32_t smBorn[2][kThreads / 64];
+  uint32_t refRow = 0, cntRow = 0;
+  __shared__ uint32_t sh_need[2];   // (one per parity of the round: a wavefront that has not read its answer yet is at most one round back)
+  const uint32_t nw = (b.tree.nvals + 63) / 64;
+  const uint64_t* words = b.stream + c * b.streamStride;
+  constexpr uint32_t kAhead = 8;
+  const bool skipTest = b.tileBorn != nullptr && b.wordLeaf != nullptr;
+  uint32_t round = 0;
+  for (uint32_t tile0 = blockIdx.x; tile0 < b.nPixTiles; tile0 += gridDim.x * kAhead, round ^= 1u) {
+    uint32_t needMask = 0, refMaskT = 0;   // tiles of the round whose census / whose refinement runs
+    if (refOn) {
+#pragma unroll
+      for (uint32_t q = 0; q < kAhead; q++) {
+        const uint32_t tile = tile0 + q * gridDim.x;
+        if (tile < b.nPixTiles && b.tileRef[c * b.tileStride + tile] != 0)   // (uniform: the whole workgroup reads the same word)
+          refMaskT |= 1u << q;
+      }
+    }
+    if (countOn && skipTest) {   // k_dec_count's test, leaves that split on plane p
+      if (threadIdx.x == 0)
+        sh_need[round] = 0;
+      uint32_t wl[kAhead], tb[kAhead];
+#pragma unroll
+      for (uint32_t q = 0; q < kAhead; q++) {
+        const uint32_t tile = tile0 + q * gridDim.x;
+        const uint32_t wi = tile * kDecTileWords + threadIdx.x;
+        tb[q] = tile < b.nPixTiles ? (uint32_t)b.tileBorn[c * b.tileStride + tile] : 0u;
+        wl[q] = (tile < b.nPixTiles && wi < nw) ? b.wordLeaf[wi] : 0xfffffffeu;   // (..fe: no word here)
+      }
+      uint32_t mine = 0;
+#pragma unroll
+      for (uint32_t q = 0; q < kAhead; q++) {
+        const uint32_t tile = tile0 + q * gridDim.x;
+        if (tile >= b.nPixTiles)
+          continue;
+        bool need = tb[q] != 0;
+        if (!need && wl[q] != 0xfffffffeu)
+          need = wl[q] == 0xffffffffu || b.leafDirty[c * b.leafDirtyStride + (wl[q] >> 5)] == (uint8_t)(p + 1);
+        mine |= need ? 1u << q : 0u;
+      }
+      __syncthreads();
+      if (mine)
+        atomicOr(&sh_need[round], mine);
+      __syncthreads();
+      needMask = sh_need[round];
+    }
+    else if (countOn)
+      needMask = (1u << kAhead) - 1u;
+    // the tiles of the round that are swept; the others, where the census is on, count nothing
+    uint32_t todo = 0;
+    for (uint32_t q = 0; q < kAhead; q++) {
+      const uint32_t tile = tile0 + q * gridDim.x;
+      if (tile >= b.nPixTiles)
+        break;
+      if (countOn && !((needMask >> q) & 1u) && threadIdx.x == 0) {
+        b.tileLip[c * b.tileStride + tile] = 0;
+        b.tileRef[c * b.tileStride + tile] = 0;
+      }
+      todo |= (((refMaskT | needMask) >> q) & 1u) << q;
+    }
+    // A tile is a chain of round trips to memory -- the masks, the leaves' dirty byte, their states, the stream word
+    // behind the rank scan -- and a workgroup walks a dozen tiles one after the other: the masks, the tile's offset and
+    // the word's leaf entry of the NEXT tile are loaded while this one is worked on, its dirty byte once the entry is
+    // there, and the stream word and the leaf states of a tile are asked for together.
+    PixWord nx = pix_word_load(b, c, tile0, todo, refMaskT, needMask, nw);
+    uint32_t nxDirty = 0;
+    if (nx.wl != 0xffffffffu)
+      nxDirty = b.leafDirty[c * b.leafDirtyStride + (nx.wl >> 5)];
+    while (todo) {
+      const uint32_t q = (uint32_t)__ffs((int)todo) - 1u;
+      todo &= todo - 1u;
+      const uint32_t tile = tile0 + q * gridDim.x;
+      const uint32_t wi = tile * kDecTileWords + threadIdx.x;
+      const bool doRef = (refMaskT >> q) & 1u, doCount = (needMask >> q) & 1u;
+      const bool in = wi < nw;
+      const PixWord cur = nx;
+      const uint32_t curDirty = nxDirty;
+      nx = pix_word_load(b, c, tile0, todo, refMaskT, needMask, nw);
+      uint64_t sig = cur.sig;
+      // ---- plane p's refinement bits of the word: k_ref_deposit, the store left for below
+      uint32_t cnt = 0, n = 0;
+      uint64_t at = 0;
+      if (doRef) {   // (the rank scan with one barrier: the sums of consecutive scans alternate between two rows)
+        cnt = (uint32_t)__popcll(sig);
+        const uint32_t inc = wave_inclusive_scan(cnt);
+        if ((threadIdx.x & 63u) == 63u)
+          smRef[refRow][threadIdx.x >> 6] = inc;
+        LDS_ONLY_BARRIER();
+        uint32_t base = 0;
+        for (uint32_t w = 0; w < (threadIdx.x >> 6); w++)
+          base += smRef[refRow][w];
+        refRow ^= 1u;
+        at = pos0 + (uint64_t)cur.refOff + base + inc - cnt;
+        // the pass stops the moment the stream is exhausted (SPECK_INT.cpp:388-389)
+        n = (cnt == 0 || at >= avail) ? 0u : (uint32_t)min((uint64_t)cnt, avail - at);
+      }
+      const bool hasRef = cnt != 0;
+      uint64_t w0 = 0, w1 = 0;   // get64(words, at), its two loads here and the shift below
+      if (n) {
+        w0 = words[at >> 6];
+        w1 = words[(at >> 6) + 1];   // (the stream has two words of slack)
+      }
+      if (nx.wl != 0xffffffffu)
+        nxDirty = b.leafDirty[c * b.leafDirtyStride + (nx.wl >> 5)];
+      uint64_t lb = 0, ls = 0, ln = 0;
+      bool leafHit = false;
+      if (cur.wl != 0xffffffffu && curDirty == (uint32_t)(uint8_t)(p + 1) && cur.born != ~0ull)   // leaves that split on plane p (born: see k_dec_count)
+        leafHit = leaf_states(b, c, cur.wl, lb, ls, ln);
+      uint64_t res = 0, got = 0;   // the bits under the mask; the candidates that did get one
+      if (n) {
+        const int sh = (int)(at & 63);
+        const uint64_t bits = sh ? (w0 >> sh) | (w1 << (64 - sh)) : w0;
+        res = n < 64 ? bits & ((1ull << n) - 1) : bits;   // candidate k of the word is the k-th set bit of the mask
+        got = n < 64 ? (1ull << n) - 1 : ~0ull;
+        if (cnt != 64)   // (64: every sample of the word is a candidate, the bits as they come)
+          spread_under_mask(sig, res, got);
+      }
+      uint64_t* pw = b.refPlanes + c * b.refPlaneStride + ref_plane_word((uint32_t)p, wi);
+      if (!doCount) {
+        if (hasRef) {
+          *pw = res;   // (always: the word is valid from the plane of its first significant sample on)
+          if (partial)
+            b.refMask[c * b.maskPixStride + wi] = got;   // the candidates that did get a bit
+        }
+        continue;
+      }
+      // ---- the fold of plane p's finds and the census for plane p - 1: k_dec_count(p - 1)
+      uint32_t v = 0;
+      bool anyBorn = false;
+      if (in) {
+        const uint64_t fresh = cur.fresh;
+        uint64_t born = cur.born;
+        if (leafHit) {
+          if (lb & ~born) {
+            born |= lb;
+            b.bornM[c * b.maskPixStride + wi] = born;
+          }
+          if (ln) {
+            const uint64_t sg = b.sign[c * b.signStride + wi];
+            if (sg & ln)
+              b.sign[c * b.signStride + wi] = sg & ~ln;
+          }
+        }
+        uint64_t found = 0;
+        if (fresh | (ls & ~sig)) {
+          found = (fresh | ls) & ~sig;   // found on plane p: bit p of their magnitudes
+          if ((uint32_t)p >= b.refNPlanes)
+            found = 0;
+        }
+        // the word of plane p, once: the refinement bits of the older samples and the '1's of the new ones
+        if (hasRef || found) {
+          *pw = res | found;
+          if (!sig)
+            b.wordTop[c * b.wordTopStride + wi] = (uint8_t)(p + 1);
+        }
+        if (fresh | (ls & ~sig)) {
+          sig |= fresh | ls;
+          b.sigOld[c * b.maskPixStride + wi] = sig;
+        }
+        if (fresh)
+          b.sigNew[c * b.maskPixStride + wi] = 0;
+        const uint64_t lip = born & ~sig;
+        v = (uint32_t)__popcll(lip) | ((uint32_t)__popcll(sig) << 16);
+        anyBorn = born != 0;
+      }
+      // the tile's two counts (256 words x 64 bits: both sums fit in 15 bits, one reduction of the packed pair) and
+      // whether any of its samples is born, through one barrier that waits for LDS only: the stores above stay in flight
+      uint32_t r = v;
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1)
+        r += (uint32_t)__shfl_xor((int)r, d, 64);
+      const bool waveBorn = __ballot(anyBorn ? 1 : 0) != 0ull;
+      if ((threadIdx.x & 63u) == 0u) {
+        smCnt[cntRow][threadIdx.x >> 6] = r;
+        smBorn[cntRow][threadIdx.x >> 6] = waveBorn ? 1u : 0u;
+      }
+      LDS_ONLY_BARRIER();
+      if (threadIdx.x == 0) {
+        uint32_t tot = 0, anyB = 0;
+        for (int w = 0; w < kThreads / 64; w++) {
+          tot += smCnt[cntRow][w];
+          anyB |= smBorn[cntRow][w];
+        }
+        b.tileLip[c * b.tileStride + tile] = tot & 0xffffu;
+        b.tileRef[c * b.tileStride + tile] = tot >> 16;
+        if (b.tileBorn != nullptr && anyB)
+          b.tileBorn[c * b.tileStride + tile] = 1;
+      }
+      cntRow ^= 1u;
+    }
+  }
+}
+
 // Every coefficient, once: magnitude bits (the '1' of the plane p0 a sample was found on, the refinement
 // bits below it) + 2^(q-1) - 1, q = the lowest plane the sample was refined on, p0 itself when none
 // (1.5 * 2^p0 - 1, src/SPECK_INT.cpp:462-468; plane 0 adds the bare bit, :440-447).  A wavefront takes
@@ -3732,6 +3998,17 @@ __global__ void __launch_bounds__(kThreads) k_dec_finish(DecBuffers b)
   coef[i] = never_refined<CT>(s.lastPlane + (isNew ? 0 : 1));
 }
 
+// the refinement pass of plane p has taken its bits: the position after it, and whether the chunk ends here
+__device__ __forceinline__ void dec_plane_end_chunk(DecState& s, int p)
+{
+  const uint64_t room = s.avail - s.pos;
+  s.refPlaneP1 = p + 1;
+  s.refPartial = (uint64_t)s.nRef > room ? 1u : 0u;
+  s.pos += min((uint64_t)s.nRef, room);
+  if (s.pos >= s.avail || p == 0)  // SPECK_INT.cpp:204-205
+    s.done = 1;
+}
+
 __global__ void k_dec_plane_end(DecBuffers b, int p)
 {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3739,12 +4016,32 @@ __global__ void k_dec_plane_end(DecBuffers b, int p)
     return;
   DecState& s = b.st[c];
   DEC_ACTIVE_OR_RETURN(s, p);
-  const uint64_t room = s.avail - s.pos;
-  s.refPlaneP1 = p + 1;
-  s.refPartial = (uint64_t)s.nRef > room ? 1u : 0u;
-  s.pos += min((uint64_t)s.nRef, room);
-  if (s.pos >= s.avail || p == 0)  // SPECK_INT.cpp:204-205
-    s.done = 1;
+  dec_plane_end_chunk(s, p);
+}
+
+// The decoder's counterpart of the encoder's k_plane_turn, one workgroup per chunk: the end of plane pEnd (k_dec_plane_end;
+// a pEnd that is no plane of the chunk -- the launcher passes maxPlanes before the first -- ends nothing), then the scan of
+// plane pBegin (k_dec_scan; < 0: none) with the position the end has just advanced.  Whether the chunk goes on is handed
+// from thread 0 to the others through LDS, not read back from DecState.
+__global__ void __launch_bounds__(kThreads) k_dec_turn(DecBuffers b, int pEnd, int pBegin)
+{
+  const uint32_t c = blockIdx.x;
+  DecState& s = b.st[c];
+  __shared__ uint64_t sm[kThreads / 64 + 1];
+  __shared__ int sh_on;
+  if (threadIdx.x == 0) {
+    int on = 0;
+    if (s.active && !s.done) {
+      if (pEnd < s.nbp)
+        dec_plane_end_chunk(s, pEnd);
+      on = (!s.done && pBegin >= 0 && pBegin < s.nbp) ? 1 : 0;
+    }
+    sh_on = on;
+  }
+  LDS_ONLY_BARRIER();   // (thread 0's stores to DecState need not land before the others go on: they read none of them)
+  if (!sh_on)
+    return;
+  dec_scan_chunk(b, s, c, sm);
 }
 
 // chunks of the batch that still have planes to decode
@@ -3832,10 +4129,20 @@ int launch_speck_decode(hipStream_t stream, const DecBuffers& b, const DecPlanHo
     else                                        \
       LAUNCH_K(kern<uint64_t>, __VA_ARGS__);    \
   } while (0)
+  // One sweep from a plane's refinement to the next plane's census (k_pix_turn, k_dec_turn) where the shape's plan says
+  // so and the refinement goes through bit planes; the 64-bit pass and k_ref_apply2 keep the four kernels
+  const bool pixTurn = plan.pixTurn && b.refPlanes != nullptr && !wide_pass;
+  // the turn from plane p to plane p - 1 (p == maxPlanes: into the first plane)
+  auto turn = [&](int p) {
+    LAUNCH_K(k_pix_turn, dim3(tileGrid, nc), dim3(kThreads), 0, stream, b, p);
+    LAUNCH_K(k_dec_turn, dim3(nc), dim3(kThreads), 0, stream, b, p, p - 1);
+  };
   auto plane = [&](auto ct, int p) -> int {
     using CT = decltype(ct);
-    LAUNCH_K(k_dec_count, dim3(tileGrid, nc), dim3(kThreads), 0, stream, b, p);
-    LAUNCH_K(k_dec_scan, dim3(nc), dim3(kThreads), 0, stream, b, p);
+    if (!pixTurn) {
+      LAUNCH_K(k_dec_count, dim3(tileGrid, nc), dim3(kThreads), 0, stream, b, p);
+      LAUNCH_K(k_dec_scan, dim3(nc), dim3(kThreads), 0, stream, b, p);
+    }
     LAUNCH_K(k_lip_words, dim3(tokSegGrid, nc), dim3(kThreads), 0, stream, b, p);
     LAUNCH_K(k_lip_scan, dim3(nc), dim3(kThreads), 0, stream, b, p);
     LAUNCH_CT(k_lip_apply, dim3(tokGrid, nc), dim3(kThreads), 0, stream, b, p);
@@ -3866,17 +4173,23 @@ int launch_speck_decode(hipStream_t stream, const DecBuffers& b, const DecPlanHo
       }
       LAUNCH_K(k_leaf_apply, dim3(capped_blocks(1024, nc, kGridCap / gdiv), nc), dim3(kThreads), 0, stream, b, p);
     }
-    if (b.refPlanes && sizeof(CT) == 4)
-      LAUNCH_K(k_ref_deposit, dim3(tileGrid, nc), dim3(kThreads), 0, stream, b, p);
-    else
-      LAUNCH_CT(k_ref_apply2, dim3(tileGrid, nc), dim3(kThreads), 0, stream, b, p);
+    if (pixTurn)
+      turn(p);
+    else {
+      if (b.refPlanes && sizeof(CT) == 4)
+        LAUNCH_K(k_ref_deposit, dim3(tileGrid, nc), dim3(kThreads), 0, stream, b, p);
+      else
+        LAUNCH_CT(k_ref_apply2, dim3(tileGrid, nc), dim3(kThreads), 0, stream, b, p);
+      LAUNCH_K(k_dec_plane_end, perChunk, dim3(64), 0, stream, b, p);
+    }
     return 0;
   };
 #undef LAUNCH_CT
+  if (pixTurn && maxPlanes > 0)   // (no plane: nothing to turn into)
+    turn(maxPlanes);
   for (int p = maxPlanes - 1; p >= 0; p--) {
     if (wide_pass ? plane(uint64_t{}, p) : plane(uint32_t{}, p))
       return -1;
-    LAUNCH_K(k_dec_plane_end, perChunk, dim3(64), 0, stream, b, p);
     // Have the chunks run out of bits?  Asked after 16 planes and then after every second one, and
     // answered ONE QUESTION LATE: the host waits for the answer to the previous question while the
     // planes launched since are still queued, so the device never runs dry (a wait for the stream

@@ -5,7 +5,7 @@
     python tools/plane_table.py gpurun_out/prof_r4/trace/run_kernel_trace.csv
 
 Takes the last decompression of the trace (its k_dec_header .. k_lift_xyz_inv), one hardware queue = one sub-batch,
-and prints per kernel the summed duration and per plane (a plane starts at k_dec_count) the kernels' durations in
+and prints per kernel the summed duration and per plane (a plane starts at k_pix_turn or k_dec_count) the kernels' durations in
 microseconds.  Under the profiler consecutive kernels of a queue follow each other without gaps, so a duration
 includes the wait for the kernel before it; the sub-batches' overlap is not what it is without the profiler."""
 import collections
@@ -41,12 +41,12 @@ for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0]):
     print("%-20s %8.3f ms %4d launches" % (k, v[0] / 1e6, v[1]))
 planes, cur = [], None
 for r in l:
-    if r[3] == "k_dec_count":
+    if r[3] in ("k_pix_turn", "k_dec_count"):
         cur = collections.OrderedDict()
         planes.append(cur)
     if cur is not None:
         cur[r[3]] = cur.get(r[3], 0) + (r[1] - r[0]) / 1e3
-names = ["k_dec_count", "k_lip_words", "k_lip_apply", "k_lip_deposit", "k_lis_l0", "k_lis_l1", "k_lis_hi", "k_lis_compact",
+names = ["k_pix_turn", "k_dec_turn", "k_dec_count", "k_lip_words", "k_lip_apply", "k_lip_deposit", "k_lis_l0", "k_lis_l1", "k_lis_hi", "k_lis_compact",
          "k_place_scan", "k_place_scatter", "k_leaf_apply", "k_ref_apply2"]
 print("plane " + " ".join(n[2:].rjust(13) for n in names) + "     total (us; the last row includes what follows the planes)")
 for i, pl in enumerate(planes):

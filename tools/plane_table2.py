@@ -5,7 +5,7 @@
     python tools/plane_table2.py <run_kernel_trace.csv> [queue-rank]
 
 One hardware queue = one sub-batch; prints the sub-batch whose queue ends last (or the queue-rank-th).  A plane starts
-at k_dec_count (or k_plane_small); durations in microseconds; `gap` = time between the end of a kernel and the start of
+at k_pix_turn or k_dec_count (or k_plane_small); durations in microseconds; `gap` = time between the end of a kernel and the start of
 the next one on the same queue, summed per plane."""
 import collections
 import csv
@@ -48,7 +48,7 @@ for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0]):
     print("%-20s %8.3f ms %4d launches" % (k, v[0] / 1e6, v[1]))
 planes, cur, prev_end = [], None, None
 for r in l:
-    if r[3] in ("k_dec_count", "k_plane_small", "k_small_pre"):
+    if r[3] in ("k_pix_turn", "k_dec_count", "k_plane_small", "k_small_pre"):
         cur = collections.OrderedDict()
         cur["_start"] = (r[0] - t0) / 1e3
         planes.append(cur)
@@ -57,8 +57,8 @@ for r in l:
         if prev_end is not None:
             cur["gap"] = cur.get("gap", 0) + max(0, r[0] - prev_end) / 1e3
     prev_end = r[1]
-names = ["k_plane_small", "k_small_pre", "k_small_post", "k_dec_count", "k_lip_words", "k_lip_scan", "k_lip_apply", "k_lip_deposit", "k_lis_l0", "k_lis_l1", "k_lis_l2",
-         "k_lis_hi", "k_lis_compact", "k_place_scan", "k_place_scatter", "k_leaf_apply", "k_ref_apply2", "k_ref_deposit", "gap"]
+names = ["k_plane_small", "k_small_pre", "k_small_post", "k_pix_turn", "k_dec_turn", "k_dec_count", "k_dec_scan", "k_lip_words", "k_lip_scan", "k_lip_apply", "k_lip_deposit", "k_lis_l0", "k_lis_l1", "k_lis_l2",
+         "k_lis_hi", "k_lis_compact", "k_place_scan", "k_place_scatter", "k_leaf_apply", "k_ref_apply2", "k_ref_deposit", "k_dec_plane_end", "gap"]
 names = [n for n in names if any(n in pl for pl in planes)]
 print("plane  start " + " ".join(n.replace("k_", "")[:9].rjust(9) for n in names) + "     total")
 for i, pl in enumerate(planes):
