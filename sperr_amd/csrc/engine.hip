@@ -2952,13 +2952,13 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   d.prefStride = (size_t)P.nSlots * d.prefWords;
   TAKE(d.maskPrefix, uint32_t, std::max<size_t>(d.prefStride, 1) * B);
   d.bornStride = P.ht.nsets + 8;
-  d.hiGroupsMax = 8;
+  d.hiGroupsMax = kRegionGroups;
   // (a segment that fills up sends the rest to the shared part, which holds the worst case: eight
   //  segments of a twelfth of it each were never seen to fill up at 2 to 4.5 bits per sample; round 6: a
   //  sixteenth -- a set is born once, so a plane's births are a fraction of the sets, and the lists of the three
   //  smallest set sizes, whose kernels claim slots of the shared part, hold most of them: 9.7 MB less per 256^3 chunk)
-  d.bornSeg = (uint32_t)((P.ht.nsets + 8) / 16 + 64);
-  d.bornPitch = d.bornStride + (size_t)d.bornSeg * d.hiGroupsMax;
+  d.bornSeg = region_seg_slots(P.ht.nsets);
+  d.bornPitch = born_array(d).pitch();
   TAKE(d.bornPacked, uint64_t, d.bornPitch * B);
   TAKE(d.bornPosLev, uint64_t, d.bornPitch * B);
   d.lisStamps = nullptr;
@@ -2995,8 +2995,8 @@ bool carve_dec(Arena& A, const ShapePlan& P, uint32_t B, uint64_t maxPayloadByte
   d.iRoots = P.d_iRoots;
   d.iLevels = P.ht.iLevels;
   d.leafCap = P.ht.nsets + 8;
-  d.leafSeg = (uint32_t)((P.ht.nsets + 8) / 16 + 64);
-  d.leafStride = d.leafCap + (size_t)d.leafSeg * d.hiGroupsMax;
+  d.leafSeg = region_seg_slots(P.ht.nsets);
+  d.leafStride = leaf_array(d).pitch();
   TAKE(d.leafEv, uint64_t, d.leafStride * B);
   d.sigbitsStride = P.lisEntries / 64 + 4;
   TAKE(d.sigbits, uint64_t, d.sigbitsStride * B);
@@ -3540,7 +3540,7 @@ struct DecodeCall {
     if (hipGetDevice(&devNow) == hipSuccess)
       sharers = std::max<size_t>(1, g_pool.busy_on(devNow));
     if (nmx)
-      mxGroupsCall = std::min<uint32_t>(8u, std::max<uint32_t>(2u, (uint32_t)(mxBudget / (nmx * sharers))));
+      mxGroupsCall = std::min<uint32_t>(kRegionGroups, std::max<uint32_t>(2u, (uint32_t)(mxBudget / (nmx * sharers))));
   }
   // (groups of 32 and more chunks of a shape the table kernels take keep the sub-batch scheme)
   static bool deferrable(const ShapePlan& P, size_t nchunksOfShape) { return nchunksOfShape < 32 || !P.dec.tables; }

@@ -23,7 +23,7 @@
 //
 // A block is handed out only after all earlier ones, so a waiting block always waits for a workgroup that is running
 // (or has seen the pass end).  A wait also ends when the pass's end marker is set, and after a minute of wall time
-// (spin_expired: DecState::error = kErrLookBackTimeout).
+// (LookBackWait, lis_region.h: DecState::error = kErrLookBackTimeout).
 #ifndef SPERR_AMD_LIS_CHAIN_H
 #define SPERR_AMD_LIS_CHAIN_H
 
@@ -126,20 +126,18 @@ __device__ __forceinline__ bool lookback_wait(DecState& s, int32_t* planeP1, con
                                               uint32_t& rank, uint32_t& sg)
 {
   unsigned long long f = 0;
-  uint32_t spins = 0;
-  uint64_t spinT0 = 0;
+  LookBackWait wait;
   for (;;) {
     f = __hip_atomic_load(prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((f >> 56) == (unsigned long long)(p + 1))
       break;
-    // (the end-of-pass marker is looked at now and then: the poll stays one load long)
-    if ((++spins & 15u) == 0 && __hip_atomic_load(planeP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1)
-      return true;
-    if (spin_expired(spins, spinT0)) {   // (a minute of wall time: the device has stopped making progress)
-      s.error = kErrLookBackTimeout;
-      __hip_atomic_store(planeP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return true;
-    }
+    // (no sleep between polls: the rest of the workgroup stands at the barrier behind this wait)
+    const WaitStep ws = wait.step(planeP1, p, false);
+    if (ws == kWaitOn)
+      continue;
+    if (ws == kWaitExpired)
+      lookback_give_up(&s.error, planeP1, p);
+    return true;
   }
   if ((f >> 55) & 1ull)
     return true;

@@ -56,6 +56,51 @@ __host__ __device__ __forceinline__ void split8_pixels(uint32_t v, uint32_t& sig
   negm |= (bit & (sgn ^ 1u)) << 7;
 }
 
+// A leaf parent whose number of pixels n (1 .. 8) is known only at run time (k_lis_hi's class 0 of a tree that is not
+// an octree, every leaf parent of k_lis_mx): the bits its split takes ...
+__host__ __device__ __forceinline__ uint32_t pixel_split_len_n(uint32_t v, uint32_t n)
+{
+  uint32_t y = 0, found = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t coded = found | (uint32_t)(k + 1 != n);
+    const uint32_t bit = coded ? (v >> y) & 1u : 1u;
+    y += coded;
+    found |= bit;
+    y += bit;
+  }
+  return y;
+}
+
+// ... and the split decoded, masks by child ordinal as split8_pixels gives them
+__host__ __device__ __forceinline__ void split_pixels_n(uint32_t v, uint32_t n, uint32_t& sigm, uint32_t& negm)
+{
+  uint32_t y = 0, found = 0;
+  sigm = 0;
+  negm = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t coded = found | (uint32_t)(k + 1 != n);
+    const uint32_t bit = coded ? (v >> y) & 1u : 1u;
+    y += coded;
+    const uint32_t sgn = (v >> y) & 1u;
+    sigm |= bit << k;
+    negm |= (bit & (sgn ^ 1u)) << k;
+    found |= bit;
+    y += bit;
+  }
+}
+
+// The leaf-event word a significant leaf parent leaves for k_leaf_apply: its flat node id, and the two masks.
+__host__ __device__ __forceinline__ uint64_t leaf_event_pack(uint32_t flatId, uint32_t sigm, uint32_t negm)
+{
+  return (uint64_t)flatId | ((uint64_t)sigm << 32) | ((uint64_t)negm << 40);
+}
+__host__ __device__ __forceinline__ void leaf_event_unpack(uint64_t ev, uint32_t& flatId, uint32_t& sigm, uint32_t& negm)
+{
+  flatId = (uint32_t)ev;
+  sigm = (uint32_t)(ev >> 32) & 0xffu;
+  negm = (uint32_t)(ev >> 40) & 0xffu;
+}
+
 // Bits the split of a set of eight child sets takes when it starts at position y, from the tables of the children's
 // class: U[x] = bits of a coded child at x (1: its test bit is '0'; else 1 + its split), T[x] = bits of a child's
 // split that starts at x (the last child's when it has no test bit).

@@ -3,6 +3,7 @@
 #define SPERR_AMD_SPECK_DEC_H
 
 #include "common.h"
+#include "lis_region.h"
 
 namespace sperrhip {
 
@@ -44,8 +45,8 @@ struct DecState {
   uint32_t hiCompactDone;        // workgroups of k_lis_compact that have finished (the last one ends the phase)
   uint64_t hiEnd;                // first bit after the phase
   uint64_t mxHint;               // k_lis_mx: (plane + 1) << 57 | list level << 48 | region << 28 | entries left, as the chain last published
-  uint32_t hiBornCnt[8];         // births / leaf events in the workgroups' own segments
-  uint32_t hiLeafCnt[8];
+  uint32_t hiBornCnt[kRegionGroups];   // births / leaf events in the workgroups' own segments (lis_region.h)
+  uint32_t hiLeafCnt[kRegionGroups];
   uint32_t bornCount;            // sets born / leaf events written so far by the GPU-wide passes
   uint32_t leafCount;            //   of the current plane (bornCount: all births once the list kernels end)
   uint64_t lisPhaseBits;         // bits of the plane's LIS phase covered by the birth masks
@@ -173,7 +174,7 @@ struct DecBuffers {
   uint32_t hiK;                // classes the LDS tables have room for
   uint32_t hiSmemBytes;        // dynamic LDS given to k_lis_hi
   uint32_t hiHop2;             // the next class's pointer-jump table is built ahead of the chain (the host sets 0: on demand)
-  uint32_t hiGroupsMax;        // workgroups per chunk the queues are sized for (<= 8)
+  uint32_t hiGroupsMax;        // workgroups per chunk the queues are sized for (<= kRegionGroups)
   uint32_t hiExtra;            // classes built speculatively beyond the hinted list's own
   uint32_t hiCand;             // class tables only where a split can start (build_tables, round 6; the host sets 1)
   uint32_t hiAhead;            // bits of a region's tables past the region's end: items that start in
@@ -189,6 +190,16 @@ struct DecBuffers {
   uint32_t mxQ;                   // items per expansion queue
   uint32_t mxSmemBytes;
 };
+
+// the chunk's two segmented arrays (lis_region.h): births (bornPacked / bornPosLev) and leaf events (leafEv)
+__host__ __device__ inline SegArray born_array(const DecBuffers& b)
+{
+  return SegArray{(uint32_t)b.bornStride, b.bornSeg, b.hiGroupsMax};
+}
+__host__ __device__ inline SegArray leaf_array(const DecBuffers& b)
+{
+  return SegArray{b.leafCap, b.leafSeg, b.hiGroupsMax};
+}
 
 struct DecPlanHost {
   const uint64_t* d_initLIS;

@@ -354,7 +354,7 @@ __device__ __forceinline__ void dec_scan_chunk(const DecBuffers& b, DecState& s,
     s.hiCompactDone = 0;
     s.bornCount = 0;
     s.leafCount = 0;
-    for (int g = 0; g < 8; g++)
+    for (uint32_t g = 0; g < kRegionGroups; g++)
       s.hiBornCnt[g] = s.hiLeafCnt[g] = 0;
   }
 }
@@ -1086,8 +1086,7 @@ k_lis_l0(DecBuffers b, int p)
     if (tid < 64) {
       uint32_t e = 0, rank = 0, sg = 0, stop = 0;
       if (i > 0) {
-        uint32_t spins = 0;
-        uint64_t spinT0 = 0;
+        LookBackWait wait;
         const int idx = (int)i - 1 - (int)lane;   // lane j looks at block i - 1 - j (-1: before the first block)
         for (;;) {
           unsigned long long f = 0;
@@ -1139,20 +1138,14 @@ k_lis_l0(DecBuffers b, int p)
           }
           if (done)
             break;
-          // (the end-of-pass marker is looked at now and then: the poll stays one round of loads long)
-          if ((++spins & 15u) == 0 &&
-              __hip_atomic_load(&s.l0PlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1) {
-            stop = 1;
-            break;
-          }
-          if (spin_expired(spins, spinT0)) {   // (a minute of wall time: the device has stopped making progress)
-            if (lane == 0) {
-              s.error = kErrLookBackTimeout;
-              __hip_atomic_store(&s.l0PlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            stop = 1;
-            break;
-          }
+          // (no sleep between polls: the rest of the workgroup stands at the barrier behind this wait)
+          const WaitStep ws = wait.step(&s.l0PlaneP1, p, false);
+          if (ws == kWaitOn)
+            continue;
+          if (ws == kWaitExpired && lane == 0)
+            lookback_give_up(&s.error, &s.l0PlaneP1, p);
+          stop = 1;
+          break;
         }
       }
       if (tid == 0)
@@ -1783,22 +1776,12 @@ __device__ __forceinline__ uint32_t reg_child_raster(const Tree& t, const Node& 
 // wavefront and round.  Old entries are compacted afterwards by k_lis_compact; k_lis_hi_end sets
 // the chunk's state for the placement kernels.
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kHiTagShift = 57;
-constexpr unsigned long long kHiPayloadMask = (1ull << kHiTagShift) - 1ull;
+constexpr unsigned long long kHiPayloadMask = (1ull << kRegionTagShift) - 1ull;
 constexpr int kHiFrames = 10;   // list level + the sets being walked into (chains of up to 9 classes)
 #ifndef HI_FIRST_REGION
 #define HI_FIRST_REGION 1024
 #endif
 constexpr uint32_t kHiFirstRegion = HI_FIRST_REGION;   // bits of a phase's first region; the next ones double up to the full size
-
-// Lanes of ONE wavefront that talk through LDS: the hardware keeps a wavefront's LDS traffic in
-// order, but the compiler reasons per thread (it may forward a lane's own earlier store to its
-// later load and never look at memory), so every hand-over between lanes needs a fence.
-#define HI_WAVE_SYNC()                                        \
-  do {                                                        \
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");    \
-    __builtin_amdgcn_wave_barrier();                          \
-  } while (0)
 
 template <typename CT>
 __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
@@ -1898,7 +1881,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
   uint64_t* leafEv = b.leafEv + c * b.leafStride;
   const uint64_t* lisCur = b.lis[cur] + c * b.lisStride;
   unsigned long long* flags = b.hiFlags + c * b.hiFlagStride;
-  const unsigned long long tag = (unsigned long long)(p + 1) << kHiTagShift;
+  const unsigned long long tag = (unsigned long long)(p + 1) << kRegionTagShift;
   const bool l0done = b.l0Level >= 0 && s.l0PlaneP1 == p + 1;
   const bool l1done = b.l1Level >= 0 && s.l1PlaneP1 == p + 1;
   const bool l2done = b.l2Level >= 0 && s.l2PlaneP1 == p + 1;
@@ -1946,19 +1929,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
       if (r > W)
         return kTInf;
       const uint32_t v = bits.bits32(r);
-      uint32_t y = 0, found = 0;
-      if (ar == 8)
-        y = split8_len(v);
-      else {
-        for (int i = 0; i < ar; i++) {
-          const uint32_t coded = found | (uint32_t)(i + 1 != ar);
-          const uint32_t bit = coded ? (v >> y) & 1u : 1u;
-          y += coded;
-          found |= bit;
-          y += bit;
-        }
-      }
-      return y;
+      return ar == 8 ? split8_len(v) : pixel_split_len_n(v, (uint32_t)ar);
     }
     const uint16_t* Up = Uu + (size_t)(j - 1) * TS;
     const uint16_t* Tp = Tt + (size_t)(j - 1) * TS;
@@ -2187,38 +2158,17 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
     return true;
   };
 
-  // births and leaf events of the expansion go to a segment of the chunk's arrays that is this
-  // workgroup's alone (an LDS counter; the shared part, with its global counter, takes what does
-  // not fit)
-  const uint32_t segB0 = (uint32_t)b.bornStride + blockIdx.x * b.bornSeg;
-  const uint32_t segL0 = b.leafCap + blockIdx.x * b.leafSeg;
-  auto born_slots = [&](uint32_t n) -> uint32_t {
-    if (n == 0)
-      return 0;
-    const uint32_t k = atomicAdd(&sh_segBorn, n);
-    if (k + n <= b.bornSeg)
-      return segB0 + k;
-    atomicMin(&sh_segBornEnd, k);        // the segment is full from here on
-    return atomicAdd(&s.bornCount, n);   // (slots at or past bornStride are dropped by write_born)
-  };
-  auto leaf_slot = [&]() -> uint32_t {
-    const uint32_t k = atomicAdd(&sh_segLeaf, 1u);
-    if (k < b.leafSeg)
-      return segL0 + k;
-    const uint32_t g = atomicAdd(&s.leafCount, 1u);
-    return g < b.leafCap ? g : 0xffffffffu;
-  };
-  auto write_born = [&](uint32_t slot, uint32_t lev, uint64_t abs, uint64_t packed) {
+  // this workgroup's segments of the chunk's birth and leaf-event arrays (lis_region.h)
+  const SegArray bornA = born_array(b), leafA = leaf_array(b);
+  const SegGroup bornG = seg_group(bornA, blockIdx.x), leafG = seg_group(leafA, blockIdx.x);
+  // a set of level `lev` born insignificant at stream position abs (lev: from the host's LevelClass tables, a list level)
+  auto record_born = [&](uint32_t lev, uint64_t abs, uint64_t packed) {
     const uint64_t rel = abs - phase0;
-    if (!(slot < b.bornStride || (slot >= segB0 && slot < segB0 + b.bornSeg)))
-      return;   // (only a damaged stream asks for more slots than there are sets)
-    bornPacked[slot] = packed;
-    bornPosLev[slot] = ((uint64_t)lev << 48) | rel;
-    atomic_or64(b.mask + c * b.maskStride + (size_t)sh_lslot[lev] * b.maskWords + (rel >> 6),
-                1ull << (rel & 63));
-  };
-  auto born_counts = [&](uint32_t lev, uint64_t abs) -> bool {   // is this birth recorded at all
-    return sh_lslot[lev] != 0xff && abs - phase0 < maskBits;
+    if (!region_birth_counts(sh_lslot[lev], rel, maskBits))
+      return;
+    const uint32_t slot = region_claim_births(bornG, &sh_segBorn, &sh_segBornEnd, &s.bornCount, 1u);
+    region_write_birth(bornG, slot, bornPacked, bornPosLev,
+                       b.mask + c * b.maskStride + (size_t)sh_lslot[lev] * b.maskWords, lev, rel, packed);
   };
 
   // all threads: expand what the queue holds, breadth first (tables of level sh_tabLevel's chain)
@@ -2253,21 +2203,10 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
         uint32_t sigm = 0, negm = 0;
         if (isLeaf) {
           const uint32_t v = bits.bits32(y0);
-          uint32_t yy = 0, found = 0;
           if (ar == 8)
             split8_pixels(v, sigm, negm);
-          else {
-            for (int k = 0; k < ar; k++) {
-              const uint32_t coded = found | (uint32_t)(k + 1 != ar);
-              const uint32_t bit = coded ? (v >> yy) & 1u : 1u;
-              yy += coded;
-              const uint32_t sgn = (v >> yy) & 1u;
-              sigm |= bit << k;
-              negm |= (bit & (sgn ^ 1u)) << k;
-              found |= bit;
-              yy += bit;
-            }
-          }
+          else
+            split_pixels_n(v, (uint32_t)ar, sigm, negm);
         }
         // ---- other sets: children from the tables
         const bool isSet = have && cls > 0;
@@ -2275,9 +2214,9 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
         const uint32_t kidLev = isSet ? C.lev[cls - 1] : 0u;
         if (isLeaf) {
           const uint32_t fid = g.nodeOff + ((((uint32_t)nd.i[2] << g.e[1]) + nd.i[1]) << g.e[0]) + nd.i[0];
-          const uint32_t slotL = leaf_slot();
-          if (slotL != 0xffffffffu)
-            leafEv[slotL] = (uint64_t)fid | ((uint64_t)sigm << 32) | ((uint64_t)negm << 40);
+          const uint32_t slotL = region_claim_leaf(leafG, &sh_segLeaf, &s.leafCount);
+          if (slotL != kSegNoSlot)
+            leafEv[slotL] = leaf_event_pack(fid, sigm, negm);
         }
         if (isSet) {
           const Root rt = sh_roots[g.root];
@@ -2305,8 +2244,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
             if (coded) {
               const uint32_t u = Up[y];
               if (!(u & 0x8000u)) {
-                if (born_counts(kidLev, a + y))
-                  write_born(born_slots(1u), kidLev, a + y, kid);
+                record_born(kidLev, a + y, kid);
                 y += 1;
                 continue;
               }
@@ -2342,8 +2280,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
   for (;;) {
     // ---- ticket
     if (tid == 0) {
-      const bool over = __hip_atomic_load(&s.hiPlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1;
-      sh_ticket = over ? kL0None : atomicAdd(&s.hiTicket, 1u);
+      sh_ticket = region_ticket(&s.hiPlaneP1, &s.hiTicket, p);
       sh_any = 0;
       sh_over = 0;
       sh_nlog = 0;
@@ -2356,7 +2293,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
     }
     __syncthreads();
     const uint32_t i = sh_ticket;
-    if (i == kL0None || ((size_t)i + 1) * 4 > b.hiFlagStride)
+    if (i == kRegionNoTicket || ((size_t)i + 1) * 4 > b.hiFlagStride)
       break;
     // diagnostics (thread 0, when b.lisStamps != nullptr): ticks per part of a region
     const bool stamps = b.lisStamps != nullptr && tid == 0;
@@ -2515,28 +2452,25 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
           if (lane < 4) {
             unsigned long long f = 0;
             if (i > 0) {
-              uint32_t spins = 0;
-        uint64_t spinT0 = 0;
+              LookBackWait wait;
               for (;;) {
                 f = __hip_atomic_load(flags + (size_t)(i - 1) * 4 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((f >> kHiTagShift) == (unsigned long long)(p + 1))
+                if ((f >> kRegionTagShift) == (unsigned long long)(p + 1))
                   break;
-                if ((++spins & 15u) == 0 &&
-                    __hip_atomic_load(&s.hiPlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1) {
-                  f = tag | (1ull << 56);   // the phase is over
-                  break;
-                }
-                if (spin_expired(spins, spinT0)) {   // (a minute of wall time: the device has stopped making progress)
-                  s.error = kErrLookBackTimeout;
-                  __hip_atomic_store(&s.hiPlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                  f = tag | (1ull << 56);
-                  break;
-                }
+                // (no sleep between polls: the chain is the serial path, and the workgroup's other wavefronts stand at
+                //  the barrier behind it)
+                const WaitStep ws = wait.step(&s.hiPlaneP1, p, false);
+                if (ws == kWaitOn)
+                  continue;
+                if (ws == kWaitExpired)
+                  lookback_give_up(&s.error, &s.hiPlaneP1, p);
+                f = tag | (1ull << 56);   // the phase is over
+                break;
               }
             }
             sh_in[lane] = f;
           }
-          HI_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           if (lane == 0) {
             if (b.lisStamps)
               sh_t2 = __builtin_readcyclecounter();
@@ -2590,7 +2524,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
             sh_stop = stop;
             sh_haveState = 1;
           }
-          HI_WAVE_SYNC();
+          WAVE_LDS_SYNC();
         }
         // (LDS traffic of one wavefront is in order: what lane 0 wrote above is what the lanes read)
         uint64_t tmark = b.lisStamps ? __builtin_readcyclecounter() : 0;
@@ -2613,7 +2547,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
               }
               sh_parInit = 1;
             }
-            HI_WAVE_SYNC();
+            WAVE_LDS_SYNC();
           }
           const uint32_t nlog = sh_nlog;
           for (uint32_t j = 0; j < nlog; j++) {
@@ -2624,7 +2558,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
                 sh_par[1] = lisCur[ei];
                 atomic_or64(sigbits + (ei >> 6), 1ull << (ei & 63));
               }
-              HI_WAVE_SYNC();
+              WAVE_LDS_SYNC();
               continue;
             }
             const uint32_t fi = (hdr >> 4) & 15u, firstOrd = (hdr >> 8) & 15u, done = (hdr >> 12) & 15u;
@@ -2636,8 +2570,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
                 const uint64_t kid = reg_child_packed(t, unpack_node(sh_par[fi]), firstOrd + lane);
                 if (kind == 1) {
                   const uint32_t lev = sh_lc[lv].lev[cls];
-                  if (born_counts(lev, a + at))
-                    write_born(born_slots(1u), lev, a + at, kid);
+                  record_born(lev, a + at, kid);
                 }
                 else if (kind == 2) {
                   const uint32_t slot = atomicAdd(&sh_qn[0], 1u);
@@ -2650,11 +2583,11 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
                   sh_par[fi + 1] = kid;
               }
             }
-            HI_WAVE_SYNC();
+            WAVE_LDS_SYNC();
           }
           if (lane == 0)
             sh_nlog = 0;
-          HI_WAVE_SYNC();
+          WAVE_LDS_SYNC();
         };
         bool pend = false;
         const uint32_t* pendHp = nullptr;
@@ -2888,7 +2821,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
                 if (enter)
                   sh_fr[depth] = (uint32_t)C.arity[cls] | ((uint32_t)(cls - 1) << 24);
               }
-              HI_WAVE_SYNC();
+              WAVE_LDS_SYNC();
               r = y;
               if (enter)
                 depth++;
@@ -2939,7 +2872,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
             ce = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);
             crem = (uint32_t)__builtin_amdgcn_readfirstlane((int)rem);
             cdepth = (uint32_t)__builtin_amdgcn_readfirstlane((int)depth);
-            HI_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             HI_T(2);
             continue;
           }
@@ -2988,7 +2921,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
             ce = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);
             crem = (uint32_t)__builtin_amdgcn_readfirstlane((int)rem);
             cdepth = (uint32_t)__builtin_amdgcn_readfirstlane((int)depth);
-            HI_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             HI_T(2);
             continue;
           }
@@ -2996,7 +2929,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
           if (pend) {   // (this pass rewrites the blocks' entry points)
             emit_entries(pendHp, pendK, pendRemaining, pendE0, pendLOff);
             pend = false;
-            HI_WAVE_SYNC();
+            WAVE_LDS_SYNC();
           }
           const uint32_t* hp = sh_hopTop[0] == K - 1 ? hop : hop2;
           const uint32_t pr = (uint32_t)(cpos - a);
@@ -3006,7 +2939,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
           const int32_t rbase = -(int32_t)bits.q0;
           for (uint32_t k = lane; k < nblk; k += 64)
             blkEB[k] = 0xffffffffu;
-          HI_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           if (lane == 0) {  // P2: walk the blocks
             uint32_t r = pr, total = 0, stopped = 0, newr = 0xffffffffu;
             while (true) {
@@ -3034,7 +2967,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
             sh_stopped = stopped;
             sh_newr = newr;
           }
-          HI_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           HI_T(3);
           if (sh_newr == 0xffffffffu) {   // the list ends inside the region: where, P3 finds out
             emit_entries(hp, (uint32_t)K, remaining, e0, lOff);
@@ -3047,7 +2980,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
             pendE0 = e0;
             pendLOff = lOff;
           }
-          HI_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           HI_T(4);
           if (sh_nlog >= (uint32_t)kHiLogCap)   // (room for the entry P4 may enter)
             hi_replay();
@@ -3083,7 +3016,7 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
             cpos = a + r;
             cdepth = depth;
           }
-          HI_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           HI_T(5);
         }
       }
@@ -3143,10 +3076,8 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_hi(DecBuffers b, int p)
     __syncthreads();   // LDS is reused by the next region
   }
   __syncthreads();
-  if (tid == 0 && blockIdx.x < 8) {
-    s.hiBornCnt[blockIdx.x] = min(min(sh_segBorn, sh_segBornEnd), b.bornSeg);
-    s.hiLeafCnt[blockIdx.x] = min(sh_segLeaf, b.leafSeg);
-  }
+  if (tid == 0 && blockIdx.x < kRegionGroups)
+    region_publish_counts(bornA, leafA, blockIdx.x, sh_segBorn, sh_segBornEnd, sh_segLeaf, s.hiBornCnt, s.hiLeafCnt);
 }
 
 // Old entries of the lists k_lis_hi decoded that stayed insignificant keep their order
@@ -3249,8 +3180,8 @@ __global__ void __launch_bounds__(kTabThreads) k_lis_compact(DecBuffers b, int p
       const uint64_t end = s.hiEnd;
       s.cur = nx;
       s.pos = end;
-      s.nLeafEv = min(s.leafCount, b.leafCap);
-      s.bornCount = min(s.bornCount, (uint32_t)b.bornStride);
+      s.nLeafEv = leaf_array(b).shared_count(s.leafCount);
+      s.bornCount = born_array(b).shared_count(s.bornCount);
       s.lisPhaseBits = min(end - phase0, maskBits);
       s.lastPlane = p;
       if (end >= s.avail)  // SPECK_INT.cpp:200-201
@@ -3307,20 +3238,11 @@ __global__ void __launch_bounds__(kThreads) k_place_scatter(DecBuffers b, int p)
   const uint32_t cur = s.cur;   // (the list kernels have already made the next lists current)
   const uint64_t* bornPacked = b.bornPacked + c * b.bornPitch;
   const uint64_t* bornPosLev = b.bornPosLev + c * b.bornPitch;
-  // the shared part, then the segments the workgroups of k_lis_hi filled
-  uint32_t segEnd[9];
-  segEnd[0] = s.bornCount;
-  for (int g = 0; g < 8; g++)
-    segEnd[g + 1] = segEnd[g] + (g < (int)b.hiGroupsMax ? s.hiBornCnt[g] : 0u);
-  for (uint32_t kk = blockIdx.x * blockDim.x + threadIdx.x; kk < segEnd[8];
-       kk += gridDim.x * blockDim.x) {
-    uint32_t k = kk;
-    if (kk >= segEnd[0]) {
-      int g = 0;
-      while (kk >= segEnd[g + 1])
-        g++;
-      k = (uint32_t)b.bornStride + (uint32_t)g * b.bornSeg + (kk - segEnd[g]);
-    }
+  // the shared part, then the segments the workgroups of the region kernel filled
+  const SegArray bornA = born_array(b);
+  const SegRanks ranks = bornA.ranks(s.bornCount, s.hiBornCnt);
+  for (uint32_t kk = blockIdx.x * blockDim.x + threadIdx.x; kk < ranks.total(); kk += gridDim.x * blockDim.x) {
+    const uint32_t k = bornA.slot_of_rank(ranks, kk);
     const uint64_t pl = bornPosLev[k];
     const uint32_t lev = (uint32_t)(pl >> 48);
     const uint64_t rel = pl & ((1ull << 48) - 1);
@@ -3353,32 +3275,23 @@ __global__ void __launch_bounds__(kThreads) k_leaf_apply(DecBuffers b, int p)
       for (uint32_t slot = 0; slot < b.nSlots; slot++)
         s.listLen[s.cur][b.slotLevel[slot]] += s.slotBorn[slot];
   }
-  uint32_t segEnd[9];
-  segEnd[0] = s.nLeafEv;
-  for (int g = 0; g < 8; g++)
-    segEnd[g + 1] = segEnd[g] + (g < (int)b.hiGroupsMax ? s.hiLeafCnt[g] : 0u);
-  const uint32_t n = segEnd[8];
+  const SegArray leafA = leaf_array(b);
+  const SegRanks ranks = leafA.ranks(s.nLeafEv, s.hiLeafCnt);
+  const uint32_t n = ranks.total();
   const Tree& t = b.tree;
   unsigned long long* bornM = reinterpret_cast<unsigned long long*>(b.bornM + c * b.maskPixStride);
   unsigned long long* sigNew = reinterpret_cast<unsigned long long*>(b.sigNew + c * b.maskPixStride);
   unsigned long long* sign = reinterpret_cast<unsigned long long*>(b.sign + c * b.signStride);
   const uint64_t* leafEv = b.leafEv + c * b.leafStride;
   for (uint32_t kk = blockIdx.x * blockDim.x + threadIdx.x; kk < n; kk += gridDim.x * blockDim.x) {
-    uint32_t k = kk;
-    if (kk >= segEnd[0]) {
-      int g = 0;
-      while (kk >= segEnd[g + 1])
-        g++;
-      k = b.leafCap + (uint32_t)g * b.leafSeg + (kk - segEnd[g]);
-    }
-    const uint64_t ev = leafEv[k];
-    const uint32_t sigm = (uint32_t)(ev >> 32) & 0xffu, negm = (uint32_t)(ev >> 40) & 0xffu;
+    uint32_t fid, sigm, negm;
+    leaf_event_unpack(leafEv[leafA.slot_of_rank(ranks, kk)], fid, sigm, negm);
     Node nd;
-    node_from_flat(t, (uint32_t)ev, nd);
+    node_from_flat(t, fid, nd);
     const Grid g = t.grids[nd.grid];
     if (g.kind & kGridLeafWord) {   // folded into the masks by k_dec_count / k_dec_fold
-      b.leafState[c * b.leafStateStride + (uint32_t)ev] = (uint16_t)(sigm | (negm << 8));
-      b.leafDirty[c * b.leafDirtyStride + ((uint32_t)ev >> 5)] = (uint8_t)(p + 1);   // (every writer stores the same value)
+      b.leafState[c * b.leafStateStride + fid] = (uint16_t)(sigm | (negm << 8));
+      b.leafDirty[c * b.leafDirtyStride + (fid >> 5)] = (uint8_t)(p + 1);   // (every writer stores the same value)
       continue;
     }
     if (!(g.kind & kGridOct)) {   // any shape (events of k_lis_mx): the existing children by ordinal
@@ -4106,11 +4019,12 @@ int launch_speck_decode(hipStream_t stream, const DecBuffers& b, const DecPlanHo
   // bookkeeping went to one lane per level: 96 / 128 / 160 / 192 / 256 give 73.4 / 77.5 / 78.5 / 77.9 / 75.5)
   static const uint32_t hiTotal = tune_getenv("SPERR_HIP_HI_WGS") ? (uint32_t)atoi(tune_getenv("SPERR_HIP_HI_WGS")) : 128u;   // (round 6: 128 -- with three sub-batches side by side
                                                                                   //  96 / 112 / 128 / 144 / 160 workgroups a sub-batch: 119.2 / 118.8 / 118.5 to 119.5 / 117.3 / 115.9 to 116.7 GB/s)
-  const uint32_t hiGroups = std::min<uint32_t>(std::max<uint32_t>(1, b.hiGroupsMax), std::max<uint32_t>(1, hiTotal / nc));
+  const uint32_t hiGroups = std::min<uint32_t>(std::min<uint32_t>(kRegionGroups, std::max<uint32_t>(1, b.hiGroupsMax)),
+                                               std::max<uint32_t>(1, hiTotal / nc));
   // workgroups per chunk of k_lis_mx: the walk of a chunk is serial, the rows and the expansion of its regions are
   // what the other workgroups are for (SPERR_HIP_MX_WGS: the total over the batch's chunks)
   static const uint32_t mxTotal = getenv("SPERR_HIP_MX_WGS") ? (uint32_t)atoi(getenv("SPERR_HIP_MX_WGS")) : 208u;
-  const uint32_t mxGroups = std::min<uint32_t>(std::min<uint32_t>(8u, std::max<uint32_t>(1, b.hiGroupsMax)),
+  const uint32_t mxGroups = std::min<uint32_t>(std::min<uint32_t>(kRegionGroups, std::max<uint32_t>(1, b.hiGroupsMax)),
                                                plan.mxGroups ? plan.mxGroups : std::max<uint32_t>(1, mxTotal / nc));
   if (plan.mixed && prepare_lis_mx(b))
     return -1;

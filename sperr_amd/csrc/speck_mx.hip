@@ -42,10 +42,8 @@ constexpr int kMxCols = 16;
 constexpr int kMxColsAll = 17;   // + one column of its own array (`Tx`): the heaviest class the sixteen leave out, up to four steps up
 constexpr int kMxLdsRoots = 48, kMxLdsGrids = 352;   // (host: use_mixed checks that the tree fits)
 constexpr uint32_t kTInf = 0xffffu, kTNone = 0xfffeu;
-constexpr uint32_t kMxTagShift = 57;
 constexpr unsigned long long kMxOver = 1ull << 56;
 constexpr int kMxFrames = kMaxDepth + 2;
-constexpr uint32_t kNoTicket = 0xffffffffu;
 constexpr int kMxPreWaves = 4;   // wavefronts that fill the ring of entry classes while the region waits for its turn
 constexpr int kMxRecs = 160;   // per-word records a region's walk can leave (one per word and reload of entry classes)
 
@@ -67,13 +65,6 @@ struct MxCtx {
 #define MX_ACTIVE_OR_RETURN(s, p)                                \
   if (!(s).active || (s).done || (int)(p) >= (s).nbp)            \
     return;
-
-// lanes of ONE wavefront that talk through LDS (see HI_WAVE_SYNC in speck_dec.hip)
-#define MX_WAVE_SYNC()                                        \
-  do {                                                        \
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");    \
-    __builtin_amdgcn_wave_barrier();                          \
-  } while (0)
 
 template <bool kStamps>
 __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
@@ -160,7 +151,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
   uint64_t* leafEv = b.leafEv + c * b.leafStride;
   const uint64_t* lisCur = b.lis[cur] + c * b.lisStride;
   unsigned long long* flags = b.hiFlags + c * b.hiFlagStride;
-  const unsigned long long tag = (unsigned long long)(p + 1) << kMxTagShift;
+  const unsigned long long tag = (unsigned long long)(p + 1) << kRegionTagShift;
 
   const uint32_t S = b.mxS, W = b.mxS + b.mxM, Q = b.mxQ;
   const uint32_t kWords = ((W >> 6) + 5u) & ~1u;
@@ -188,34 +179,21 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         atomicAnd(sign + (ridx >> 6), ~(1ull << (ridx & 63)));
     }
   };
-  // births and leaf events go to a segment of the chunk's arrays that is this workgroup's alone (an LDS
-  // counter; the shared part, with its global counter, takes what does not fit) -- k_lis_hi's scheme
-  const uint32_t segB0 = (uint32_t)b.bornStride + blockIdx.x * b.bornSeg;
-  const uint32_t segL0 = b.leafCap + blockIdx.x * b.leafSeg;
+  // this workgroup's segments of the chunk's birth and leaf-event arrays (lis_region.h)
+  const SegArray bornA = born_array(b), leafA = leaf_array(b);
+  const SegGroup bornG = seg_group(bornA, blockIdx.x), leafG = seg_group(leafA, blockIdx.x);
   auto born_slots = [&](uint32_t n) -> uint32_t {
-    const uint32_t k = atomicAdd(&sh_segBorn, n);
-    if (k + n <= b.bornSeg)
-      return segB0 + k;
-    atomicMin(&sh_segBornEnd, k);        // the segment is full from here on
-    return atomicAdd(&s.bornCount, n);   // (slots at or past bornStride are dropped by write_born)
-  };
-  auto leaf_slot = [&]() -> uint32_t {
-    const uint32_t k = atomicAdd(&sh_segLeaf, 1u);
-    if (k < b.leafSeg)
-      return segL0 + k;
-    const uint32_t g = atomicAdd(&s.leafCount, 1u);
-    return g < b.leafCap ? g : 0xffffffffu;
+    return region_claim_births(bornG, &sh_segBorn, &sh_segBornEnd, &s.bornCount, n);
   };
   auto write_born = [&](uint32_t slot, uint32_t lev, uint64_t rel, uint64_t packed) {
-    if (!(slot < b.bornStride || (slot >= segB0 && slot < segB0 + b.bornSeg)))
-      return;   // (only a damaged stream asks for more slots than there are sets)
-    bornPacked[slot] = packed;
-    bornPosLev[slot] = ((uint64_t)lev << 48) | rel;
-    atomic_or64(b.mask + c * b.maskStride + (size_t)sh_levelSlot[lev] * b.maskWords + (rel >> 6),
-                1ull << (rel & 63));
+    region_write_birth(bornG, slot, bornPacked, bornPosLev,
+                       b.mask + c * b.maskStride + (size_t)sh_levelSlot[lev] * b.maskWords, lev, rel, packed);
   };
-  auto born_counts = [&](uint32_t lev, uint64_t rel) -> bool {   // is this birth recorded at all
-    return lev < (uint32_t)kMaxLevels && sh_levelSlot[lev] != 0xff && rel < maskBits;
+  // is a birth at bit rel of the phase recorded at all.  (lev < kMaxLevels: this kernel works a child's level out
+  // from the node it reads -- kid_box_l, the type-I set's part level -- and a damaged stream can leave it any node;
+  // k_lis_hi's levels come from the host's tables and need no such test.)
+  auto born_counts = [&](uint32_t lev, uint64_t rel) -> bool {
+    return lev < (uint32_t)kMaxLevels && region_birth_counts(sh_levelSlot[lev], rel, maskBits);
   };
   // a set born insignificant at stream position abs
   auto record_born = [&](uint32_t lev, uint64_t abs, uint64_t packed) {
@@ -269,23 +247,13 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
   // a significant leaf parent of nk samples whose split starts at y: ONE event word (node id,
   // significance and sign masks by child ordinal) that k_leaf_apply turns into mask updates
   auto leaf_event = [&](const Node& nd, uint32_t y, uint32_t nk) {
-    const uint32_t v = bits.bits32(y);
-    uint32_t yy = 0, found = 0, sigm = 0, negm = 0;
-    for (uint32_t k = 0; k < nk; k++) {
-      const uint32_t coded = found | (uint32_t)(k + 1 != nk);
-      const uint32_t bit = coded ? (v >> yy) & 1u : 1u;
-      yy += coded;
-      const uint32_t sgn = (v >> yy) & 1u;
-      sigm |= bit << k;
-      negm |= (bit & (sgn ^ 1u)) << k;
-      found |= bit;
-      yy += bit;
-    }
+    uint32_t sigm, negm;
+    split_pixels_n(bits.bits32(y), nk, sigm, negm);
     const Grid& g = sh_grids[nd.grid];
     const uint32_t fid = g.nodeOff + ((((uint32_t)nd.i[2] << g.e[1]) + nd.i[1]) << g.e[0]) + nd.i[0];
-    const uint32_t slot = leaf_slot();
-    if (slot != 0xffffffffu)
-      leafEv[slot] = (uint64_t)fid | ((uint64_t)sigm << 32) | ((uint64_t)negm << 40);
+    const uint32_t slot = region_claim_leaf(leafG, &sh_segLeaf, &s.leafCount);
+    if (slot != kSegNoSlot)
+      leafEv[slot] = leaf_event_pack(fid, sigm, negm);
   };
   // the next list after level `l` (exclusive) that holds entries
   auto next_level = [&](int l) -> int {
@@ -449,7 +417,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
   auto walk = [&]() {
     const uint64_t wk0 = kStamps ? __builtin_readcyclecounter() : 0;
     // (read here, off the end of the walk: what the state words 4 and 5 hold while a list is walked)
-    const unsigned long long pubBase = sh_base & ((1ull << kMxTagShift) - 1ull);
+    const unsigned long long pubBase = sh_base & ((1ull << kRegionTagShift) - 1ull);
     const unsigned long long pubI = (unsigned long long)sh_iJ | ((unsigned long long)sh_iPart << 2) |
                                     ((unsigned long long)sh_iCounter << 8) | ((unsigned long long)sh_iNeed << 10);
     uint32_t r = __builtin_amdgcn_readfirstlane((uint32_t)(sh_pos - a)), e = __builtin_amdgcn_readfirstlane(sh_e),
@@ -833,7 +801,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
             nc.found = 0;
             sh_base = packed;
           }
-          MX_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           depth = 2;
           r += 1;
         }
@@ -962,12 +930,12 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         r = S;
       }
       else if (halted) {
-        MX_WAVE_SYNC();
+        WAVE_LDS_SYNC();
         break;
       }
       else
         depth--;
-      MX_WAVE_SYNC();
+      WAVE_LDS_SYNC();
       if (kStamps)
         wk_into += __builtin_readcyclecounter() - ti0;
     }
@@ -1009,7 +977,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
       if (qn > Q)
         s.error = 1;   // (only a damaged stream packs that many sets into a region)
     }
-    MX_WAVE_SYNC();
+    WAVE_LDS_SYNC();
     if (kStamps) {
       wk_total += __builtin_readcyclecounter() - wk0;
       wk_epi += __builtin_readcyclecounter() - we0;
@@ -1124,8 +1092,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
   for (;;) {
     // ---- ticket
     if (tid == 0) {
-      const bool over = __hip_atomic_load(&s.hiPlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1;
-      sh_ticket = over ? kNoTicket : atomicAdd(&s.hiTicket, 1u);
+      sh_ticket = region_ticket(&s.hiPlaneP1, &s.hiTicket, p);
       // Which columns this region's rows need: sets of at most so many steps above the leaf parents.  The lists come
       // smallest sets first, so most regions lie in the lists of the leaf parents and of the sets made of those, whose
       // rows need no or few chains of look-ups.  The chain leaves a hint behind (list level, region, entries left of
@@ -1136,7 +1103,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
                                                           __HIP_MEMORY_SCOPE_AGENT);
         int lv = -1;
         uint32_t left = 0, at = 0;
-        if ((hint >> kMxTagShift) == (unsigned long long)(p + 1)) {
+        if ((hint >> kRegionTagShift) == (unsigned long long)(p + 1)) {
           lv = (int)((hint >> 48) & 63u);
           at = (uint32_t)(hint >> 28) & 0xfffffu;
           left = (uint32_t)hint & 0xfffffffu;
@@ -1177,7 +1144,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
     }
     __syncthreads();
     const uint32_t i = sh_ticket;
-    if (i == kNoTicket)
+    if (i == kRegionNoTicket)
       break;
     // (tickets are taken ahead of the chain: one past the flags is past the stream and all its padding, no
     //  phase gets there)
@@ -1207,21 +1174,19 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         unsigned long long f = 0;
         bool have = false;
         if (i >= 2) {
-          uint32_t spins = 0;
-          uint64_t spinT0 = 0;
+          LookBackWait wait;
           for (;;) {
             if (lane < 2)
               f = __hip_atomic_load(flags + (size_t)(i - 2) * kMxWordsPerRegion + lane, __ATOMIC_RELAXED,
                                     __HIP_MEMORY_SCOPE_AGENT);
-            have = __ballot(lane < 2 && (f >> kMxTagShift) == (unsigned long long)(p + 1)) == 3ull;
+            have = __ballot(lane < 2 && (f >> kRegionTagShift) == (unsigned long long)(p + 1)) == 3ull;
             if (have)
               break;
-            if ((++spins & 15u) == 0 &&
-                __hip_atomic_load(&s.hiPlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1)
+            // (this kernel's waits sleep between polls, as they were written and timed.  An expired wait is given up
+            //  SILENTLY here: the ring is only a prefetch, and the look-back below, which the chain cannot do without,
+            //  meets the same dead device and raises the error.)
+            if (wait.step(&s.hiPlaneP1, p, true) != kWaitOn)
               break;
-            if (spin_expired(spins, spinT0))
-              break;   // (the look-back below gives up loudly)
-            __builtin_amdgcn_s_sleep(1);
           }
         }
         const unsigned long long f0 = __shfl(f, 0, 64), f1 = __shfl(f, 1, 64);
@@ -1238,7 +1203,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
           sh_preHi = hi;
           __hip_atomic_store(&sh_go, (have && hi > lo) ? 2u : 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        MX_WAVE_SYNC();
+        WAVE_LDS_SYNC();
       }
     }
     // (four wavefronts put the classes into the ring: one alone takes longer than the region before this one walks)
@@ -1268,30 +1233,25 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
       if (lane < 7) {
         unsigned long long f = 0;
         if (i > 0) {
-          uint32_t spins = 0;
-          uint64_t spinT0 = 0;
+          LookBackWait wait;
           for (;;) {
             f = __hip_atomic_load(flags + (size_t)(i - 1) * kMxWordsPerRegion + lane, __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_AGENT);
-            if ((f >> kMxTagShift) == (unsigned long long)(p + 1))
+            if ((f >> kRegionTagShift) == (unsigned long long)(p + 1))
               break;
-            if ((++spins & 15u) == 0 &&
-                __hip_atomic_load(&s.hiPlaneP1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p + 1) {
-              sh_abort = 1;   // the phase is over
-              break;
-            }
-            if (spin_expired(spins, spinT0)) {   // (a minute of wall time: the device has stopped making progress)
-              s.error = kErrLookBackTimeout;
-              __hip_atomic_store(&s.hiPlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              sh_abort = 1;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
+            // (with a sleep between polls, like the wait above)
+            const WaitStep ws = wait.step(&s.hiPlaneP1, p, true);
+            if (ws == kWaitOn)
+              continue;
+            if (ws == kWaitExpired)
+              lookback_give_up(&s.error, &s.hiPlaneP1, p);
+            sh_abort = 1;   // the phase is over
+            break;
           }
         }
         sh_in[lane] = f;
       }
-      MX_WAVE_SYNC();
+      WAVE_LDS_SYNC();
       if (kStamps && lane == 0)
         sh_tk[1] = __builtin_readcyclecounter();
       if (kStamps)
@@ -1325,7 +1285,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         mode = (uint32_t)(f0 >> 51) & 3u;
         e = (uint32_t)f1;
         rem = (uint32_t)uni(sh_in[6]);
-        base = uni(sh_in[4]) & ((1ull << kMxTagShift) - 1ull);
+        base = uni(sh_in[4]) & ((1ull << kRegionTagShift) - 1ull);
         iJ = (uint32_t)f5 & 3u;
         iPart = (uint32_t)(f5 >> 2) & 63u;
         iCounter = (uint32_t)(f5 >> 8) & 3u;
@@ -1402,7 +1362,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
         if (pre)
           sh_ringHi = sh_preHi;
       }
-      MX_WAVE_SYNC();
+      WAVE_LDS_SYNC();
       if (kStamps && wk_seen)
         wk_dec += __builtin_readcyclecounter() - wk_seen;
     }
@@ -1428,7 +1388,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
       }
       if (wave != 0)
         continue;
-      MX_WAVE_SYNC();   // (what thread 0 wrote above is this wavefront's own LDS traffic)
+      WAVE_LDS_SYNC();   // (what thread 0 wrote above is this wavefront's own LDS traffic)
       // ---- first wavefront: on until the region ends, the phase ends, or a new list needs its classes
       for (;;) {
         uint32_t mode = __builtin_amdgcn_readfirstlane(sh_mode);
@@ -1446,7 +1406,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
               sh_depth = 1;
               sh_needFill = 1;
             }
-            MX_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             if (r < S)
               break;   // (all hands: the new list's classes)
           }
@@ -1455,7 +1415,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
               sh_mode = kModeITest;
               sh_depth = 1;
             }
-            MX_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             continue;
           }
           else
@@ -1485,7 +1445,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
           else if (lane == 3)
             f |= fr1;
           else if (lane == 4)
-            f |= sh_base & ((1ull << kMxTagShift) - 1ull);
+            f |= sh_base & ((1ull << kRegionTagShift) - 1ull);
           else if (lane == 5)
             f |= (unsigned long long)sh_iJ | ((unsigned long long)sh_iPart << 2) |
                  ((unsigned long long)sh_iCounter << 8) | ((unsigned long long)sh_iNeed << 10);
@@ -1501,7 +1461,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
                                    (unsigned long long)(sh_mode == kModeList ? min(sh_rem, 0xfffffffu) : 0u),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
-          MX_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           break;
         }
         if (!over && mode == kModeITest) {
@@ -1524,7 +1484,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
               sh_iCounter = 0;
               sh_mode = kModeISub;
             }
-            MX_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             if (!over)
               continue;
           }
@@ -1537,14 +1497,14 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
               sh_iNeed = sh_iCounter != 0 ? 1u : 0u;
               sh_mode = kModeITest;
             }
-            MX_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             continue;
           }
           const uint64_t root = b.iRoots[(size_t)(b.iLevels - iPart) * 3 + iJ];
           if (lane == 0)
             sh_iJ = iJ + 1u;
           if (root == ~0ull) {   // (an empty subband)
-            MX_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             continue;
           }
           // the subband is tested like a list of one entry
@@ -1554,7 +1514,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
               record_born(iPart, a + r, root);
               sh_pos = a + r + 1u;
             }
-            MX_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             continue;
           }
           const Node rn = unpack_node(root);
@@ -1574,7 +1534,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
               sh_iCounter = sh_iCounter + 1u;
               sh_pos = a + r + 1u + tl;
             }
-            MX_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             continue;
           }
           KidBox kb;
@@ -1594,7 +1554,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
             sh_e = 0;
             sh_mode = kModeISubWalk;
           }
-          MX_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           continue;
         }
         if (over) {
@@ -1611,7 +1571,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
             __hip_atomic_store(&s.hiPlaneP1, p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             sh_stop = 2;
           }
-          MX_WAVE_SYNC();
+          WAVE_LDS_SYNC();
           break;
         }
         // ---- list entries, or the children of the sets being walked into
@@ -1627,7 +1587,7 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
             sh_depth = 1;
             sh_mode = kModeISub;
           }
-          MX_WAVE_SYNC();
+          WAVE_LDS_SYNC();
         }
       }
     }
@@ -1675,10 +1635,8 @@ __global__ void __launch_bounds__(kMxThreads) k_lis_mx(DecBuffers b, int p)
     __syncthreads();   // LDS is reused by the next region
   }
   __syncthreads();
-  if (tid == 0 && blockIdx.x < 8) {
-    s.hiBornCnt[blockIdx.x] = min(min(sh_segBorn, sh_segBornEnd), b.bornSeg);
-    s.hiLeafCnt[blockIdx.x] = min(sh_segLeaf, b.leafSeg);
-  }
+  if (tid == 0 && blockIdx.x < kRegionGroups)
+    region_publish_counts(bornA, leafA, blockIdx.x, sh_segBorn, sh_segBornEnd, sh_segLeaf, s.hiBornCnt, s.hiLeafCnt);
 }
 
 }  // namespace

@@ -964,6 +964,35 @@ def test_list_kernel_choices_in_a_fresh_process(oracle, knobs):
         assert subprocess.run([sys.executable, "-c", code], env=env, timeout=300).returncode == 0, knobs
 
 
+def test_one_workgroup_per_chunk_decodes_every_list_in_a_fresh_process(oracle):
+    """`SPERR_HIP_LIS_GPUWIDE=0` with more chunks than k_lis_hi has workgroups to share out: 96^3 in 216 chunks of 16^3
+    decode as three sub-batches of 72, and 128 workgroups over 72 chunks leave each chunk ONE, which takes every region
+    of every list itself -- each look-back finds the state its own workgroup published, and all births and leaf events
+    of a chunk go through one group's segment.  At 6 bpp and cut to 37 % of every chunk (sperr_trunc_3d), against the
+    oracle's bits.  Whether a segment fills up here, so that claims spill to the shared part, is not known:
+    tests/test_lis_region_host.py is what covers the arithmetic of a full segment."""
+    import subprocess
+    import sys
+    import tempfile
+    v = turbulence((96, 96, 96))
+    want = oracle.comp_3d(v, (16, 16, 16), 1, 6.0)
+    part = oracle.trunc_3d(want, 37)
+    assert len(part) < len(want)
+    with tempfile.TemporaryDirectory() as td:
+        for name, c in (("whole", want), ("part", part)):
+            np.save(os.path.join(td, name + ".c.npy"), np.frombuffer(c, dtype=np.uint8))
+            np.save(os.path.join(td, name + ".r.npy"), oracle.decomp_3d(c, True))
+        code = ("import sys, os, numpy as np, torch; sys.path.insert(0, %r); from sperr_amd.api import SperrHip; td = %r; "
+                "L = lambda n: np.load(os.path.join(td, n)); e = SperrHip(); ok = True\n"
+                "for name in ('whole', 'part'):\n"
+                "    d = e.decompress(torch.from_numpy(L(name + '.c.npy')).cuda(), True).cpu().numpy()\n"
+                "    ok = ok and np.array_equal(d.view(np.uint32), L(name + '.r.npy').view(np.uint32))\n"
+                "sys.exit(0 if ok else 3)"
+                % (os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), td))
+        env = dict(os.environ, SPERR_HIP_LIS_GPUWIDE="0")
+        assert subprocess.run([sys.executable, "-c", code], env=env, timeout=300).returncode == 0
+
+
 @pytest.mark.parametrize("knobs", [{"SPERR_HIP_MX_WGS": "1"}, {"SPERR_HIP_MX_WGS": "3"}, {"SPERR_HIP_MX_WGS": "4096"}])
 def test_mixed_shape_decoders_in_a_fresh_process(oracle, knobs):
     """Chunks whose lists mix set shapes decode through k_lis_mx (round 4: fixed regions of the stream handed out to

@@ -1,13 +1,14 @@
 """CPU (hipcc cross-compiles gfx950 here): registers, spills, scratch and static LDS of the decoder's list kernels
-(k_lis_l0, k_lis_l1, k_lis_l2, k_lis_hi: sperr_amd/csrc/speck_dec.hip), read from the code object metadata of the ISA the
-compiler emits with the Makefile's flags.  Only the metadata block is read.
+(k_lis_l0, k_lis_l1, k_lis_l2, k_lis_hi: sperr_amd/csrc/speck_dec.hip; k_lis_mx: speck_mx.hip), read from the code object
+metadata of the ISA the compiler emits with the Makefile's flags.  Only the metadata block is read.
 
 The three block-parallel kernels are built from shared phases (lis_chain.h, lis_token.h).  Their occupancy is set by
 attribute -- two workgroups of 1024 threads a compute unit for k_lis_l0: 64 VGPRs a thread, not one more; two of 512
 for the others: 128 -- and k_lis_l0 sat at exactly 64 with two of them spilled before the phases were shared.  The
 ceilings below are the figures of the kernels as they were written out one by one (measured at the commit before the
 skeleton, with the same flags), so that a change to a shared phase cannot cost one of the kernels registers, scratch or
-LDS silently."""
+LDS silently.  The two region kernels (k_lis_hi, k_lis_mx) share their protocol half the same way (lis_region.h);
+k_lis_mx's ceilings are its figures at the commit before that header, plain and with stamps."""
 import os
 import re
 import shutil
@@ -16,7 +17,8 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "sperr_amd", "csrc", "speck_dec.hip")
+CSRC = os.path.join(ROOT, "sperr_amd", "csrc")
+SRCS = {"speck_dec.hip": 25, "speck_mx.hip": 2}   # file: kernels it holds at least
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wno-unused-value", "--cuda-device-only"]
 
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
@@ -29,6 +31,8 @@ CEILING = {
     "k_lis_l2E": (128, 0, 0, 10256),
     "k_lis_hiIjE": (128, 0, 16, 11376),
     "k_lis_hiImE": (128, 0, 16, 11376),
+    "k_lis_mxILb0E": (126, 0, 0, 20912),
+    "k_lis_mxILb1E": (128, 19, 84, 20928),
 }
 
 
@@ -44,11 +48,16 @@ def kernel_meta(s_text):
 
 @pytest.fixture(scope="module")
 def meta(tmp_path_factory):
-    s_path = str(tmp_path_factory.mktemp("lis_codeobj") / "speck_dec.s")
-    r = subprocess.run(["hipcc", *FLAGS, "-S", SRC, "-o", s_path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    m = kernel_meta(open(s_path).read())
-    assert len(m) >= 25, sorted(m)
+    tmp = tmp_path_factory.mktemp("lis_codeobj")
+    procs = {src: subprocess.Popen(["hipcc", *FLAGS, "-S", os.path.join(CSRC, src), "-o", str(tmp / (src + ".s"))],
+                                   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for src in SRCS}
+    m = {}
+    for src, proc in procs.items():
+        out = proc.communicate()[0]
+        assert proc.returncode == 0, out[-3000:]
+        one_file = kernel_meta(open(tmp / (src + ".s")).read())
+        assert len(one_file) >= SRCS[src], sorted(one_file)
+        m.update(one_file)
     return m
 
 

@@ -25,20 +25,8 @@ CSRC = os.path.join(ROOT, "sperr_amd", "csrc")
 
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
 
-PROGRAM = r"""
-#include <cstdio>
-#include <cstdint>
-#include <vector>
-#include "lis_token.h"
-using namespace sperrhip;
-
-static uint64_t rng = 0x9e3779b97f4a7c15ull;
-static uint64_t next64()
-{
-  rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
-  return rng;
-}
-
+# (tests/test_lis_region_host.py parses with it as well)
+PARSE = r"""
 // ---- the bit-by-bit parse
 struct Parse {
   const uint32_t* w;
@@ -78,7 +66,23 @@ struct Parse {
     }
   }
 };
+"""
 
+PROGRAM = r"""
+#include <cstdio>
+#include <cstdint>
+#include <vector>
+#include "lis_token.h"
+using namespace sperrhip;
+
+static uint64_t rng = 0x9e3779b97f4a7c15ull;
+static uint64_t next64()
+{
+  rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
+  return rng;
+}
+
+""" + PARSE + r"""
 static long check_pixels()
 {
   long bad = 0;
