@@ -310,6 +310,38 @@ int sperrhip_quality_dev(const void* d_orig, const void* d_recon, int is_float, 
 int sperrhip_quality_batch_dev(const void* d_orig, const void* d_recon, int is_float, size_t nvol,
                                size_t n, double* out, void* hip_stream);
 
+/* ---- strided views of device arrays -------------------------------------------------------------
+ * The interior of an array with ghost cells, a slice of a larger tensor: a volume of dims (dimx, dimy, dimz), x
+ * fastest with unit x stride, given by the device address of its first element and two pitches in elements --
+ * pitch_y from one row to the next, pitch_z from one slice to the next.  A view is valid when pitch_y >= dimx,
+ * pitch_z >= pitch_y * dimy, pitch_z is a multiple of pitch_y and nothing overflows size_t; it reaches
+ * (dimz-1)*pitch_z + (dimy-1)*pitch_y + dimx elements from its first one, its extent.  The first element needs the
+ * alignment of its type only.  The dense volume is the view {dimx, dimx*dimy}.  No packed copy is made anywhere.
+ * The three calls return -1 before anything is written for a view that is not valid, for a NULL pointer, and for an
+ * output whose capacity -- in bytes, counted from the view's first element -- is below the view's extent. */
+typedef struct sperrhip_view {
+  size_t pitch_y, pitch_z;
+} sperrhip_view;
+/* sperrhip_compress_dev of the view `view` of d_src (its first element): the container is byte for byte the one
+ * sperrhip_compress_dev makes of the packed copy.  Same modes and return codes. */
+int sperrhip_compress_view_dev(const void* d_src, const sperrhip_view* view, int is_float, size_t dimx, size_t dimy,
+                               size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
+                               void* d_dst, size_t dst_cap, size_t* dst_len, void* hip_stream);
+/* The volume of a container (box_lo and box_dims NULL) or the box [lo, lo + dims) of it, from the first `pct` percent
+ * of every chunk stream (0 or >= 100: all of them), into the view `view` of d_dst whose dims are the volume's or the
+ * box's: bit for bit what sperrhip_decompress_dev / _box_dev / _portion_dev write densely.  Elements of the
+ * destination that lie outside the view are not written.  dst_cap_bytes counts from d_dst.  0 ok, -1 error (also
+ * when only one of box_lo / box_dims is NULL). */
+int sperrhip_decompress_view_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
+                                 const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
+                                 const sperrhip_view* view, size_t dst_cap_bytes, void* hip_stream);
+/* sperrhip_quality_dev of two arrays of dims (dimx, dimy, dimz) read through views; either view may be NULL, which
+ * means dense, and the two may differ.  out[8] is bit for bit what sperrhip_quality_dev gives for the two packed
+ * copies.  Three kernels, one copy and one host wait, as there.  dimx and dimy stay below 2^31. */
+int sperrhip_quality_view_dev(const void* d_orig, const sperrhip_view* view_orig, const void* d_recon,
+                              const sperrhip_view* view_recon, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                              double* out, void* hip_stream);
+
 /* ---- a batch of same-shape volumes, one container each ----------------------------------------- */
 /* N volumes of the same dims in one call: the chunks of every volume are coded together (a batch is
  * more chunks for the same shape groups), and each volume gets a container of its own.  Container v

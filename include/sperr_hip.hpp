@@ -514,6 +514,60 @@ inline auto quality_dev(const T* d_orig, const T* d_recon, size_t n, std::array<
   return rtn == 0 ? RTNType::Good : RTNType::Error;
 }
 
+// (this library's addition) Strided views of device arrays (sperrhip_view: the interior of an array with ghost cells,
+// a slice of a larger one): a volume of `dims`, x fastest with unit x stride, rows pitch_y and slices pitch_z elements
+// apart from its first element.  The calls below are the device-pointer calls with such a view in place of a packed
+// array; no packed copy is made.  RTNType::Error (nothing written) for a view that is not valid, a null pointer, or an
+// output that does not hold the view.
+using view_type = sperrhip_view;
+
+// the dense view of a volume
+inline auto dense_view(dims_type dims) -> view_type { return view_type{dims[0], dims[0] * dims[1]}; }
+
+// quality_dev of two arrays of `dims` read through views; a null view means dense (sperrhip_quality_view_dev)
+template <typename T>
+inline auto quality_view_dev(const T* d_orig, const view_type* view_orig, const T* d_recon,
+                             const view_type* view_recon, dims_type dims, std::array<double, 8>& out,
+                             void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const int rtn = sperrhip_quality_view_dev(d_orig, view_orig, d_recon, view_recon, sizeof(T) == 4, dims[0], dims[1],
+                                            dims[2], out.data(), hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
+// A view of a device volume into a container in device memory of `cap` bytes (sperrhip_compress_view_dev); `len`
+// receives the container's length.  `mode` and `quality` as SPERR3D_OMP_C's setters name them.
+template <typename T>
+inline auto compress_view_dev(const T* d_src, const view_type& view, dims_type dims, dims_type chunks, CompMode mode,
+                              double quality, void* d_out, size_t cap, size_t& len, void* hip_stream = nullptr)
+    -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const int m = mode == CompMode::Rate ? 1 : mode == CompMode::PSNR ? 2 : mode == CompMode::PWE ? 3 : 0;
+  if (m == 0)
+    return RTNType::CompModeUnknown;
+  const int rtn = sperrhip_compress_view_dev(d_src, &view, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0],
+                                             chunks[1], chunks[2], m, quality, d_out, cap, &len, hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
+// The volume of a device container, or with `box_lo` / `box_dims` (both or neither) a box of it, from the first `pct`
+// percent of every chunk stream (0: all), into a view of `cap_bytes` of device memory at d_out
+// (sperrhip_decompress_view_dev).  Nothing outside the view is written.
+template <typename T>
+inline auto decompress_view_dev(const void* d_stream, size_t stream_len, T* d_out, const view_type& view,
+                                size_t cap_bytes, const dims_type* box_lo = nullptr,
+                                const dims_type* box_dims = nullptr, unsigned pct = 0, void* hip_stream = nullptr)
+    -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const int rtn = sperrhip_decompress_view_dev(d_stream, stream_len, pct, sizeof(T) == 4,
+                                               box_lo ? box_lo->data() : nullptr, box_dims ? box_dims->data() : nullptr,
+                                               d_out, &view, cap_bytes, hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
 }  // namespace sperr
 
 #endif

@@ -41,11 +41,17 @@ EXPORTS = [
     "sperrhip_portion_len", "sperrhip_decompress_portion_dev", "sperrhip_decomp_3d_portion",
     "sperrhip_trunc_dev", "sperrhip_trunc_batch_dev",
     "sperrhip_quality_dev", "sperrhip_quality_batch_dev",
+    "sperrhip_compress_view_dev", "sperrhip_decompress_view_dev", "sperrhip_quality_view_dev",
 ]
 
 
 class SperrHipError(RuntimeError):
     pass
+
+
+class View(C.Structure):
+    """sperrhip_view: the pitches of a strided view in elements (include/sperr_hip.h)"""
+    _fields_ = [("pitch_y", _sz), ("pitch_z", _sz)]
 
 
 class Quality:
@@ -179,6 +185,15 @@ def load_library():
     lib.sperrhip_quality_dev.argtypes = [_vp, _vp, C.c_int, _sz, C.POINTER(C.c_double), _vp]
     lib.sperrhip_quality_batch_dev.restype = C.c_int
     lib.sperrhip_quality_batch_dev.argtypes = [_vp, _vp, C.c_int, _sz, _sz, C.POINTER(C.c_double), _vp]
+    lib.sperrhip_compress_view_dev.restype = C.c_int
+    lib.sperrhip_compress_view_dev.argtypes = [_vp, C.POINTER(View), C.c_int, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int,
+                                               C.c_double, _vp, _sz, C.POINTER(_sz), _vp]
+    lib.sperrhip_decompress_view_dev.restype = C.c_int
+    lib.sperrhip_decompress_view_dev.argtypes = [_vp, _sz, C.c_uint, C.c_int, C.POINTER(_sz), C.POINTER(_sz), _vp,
+                                                 C.POINTER(View), _sz, _vp]
+    lib.sperrhip_quality_view_dev.restype = C.c_int
+    lib.sperrhip_quality_view_dev.argtypes = [_vp, C.POINTER(View), _vp, C.POINTER(View), C.c_int, _sz, _sz, _sz,
+                                              C.POINTER(C.c_double), _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -226,24 +241,77 @@ class SperrHip:
     def _stream(self):
         return _vp(self.torch.cuda.current_stream().cuda_stream)
 
+    # ---- strided views ---------------------------------------------------------------------
+    @staticmethod
+    def view_of(t):
+        """The sperrhip_view of a 3-D cuda tensor (z, y, x) that is a strided view of a larger one -- the interior
+        of an array with ghost cells, one member of a stacked buffer: unit x stride, rows stride(1) and slices
+        stride(0) elements apart, the slice pitch a multiple of the row pitch.  data_ptr() is its first element.
+        Raises SperrHipError for anything else (an x stride other than 1, a negative or overlapping stride, a slice
+        pitch that is no multiple of the row pitch): nothing is ever copied silently."""
+        if t.dim() != 3:
+            raise SperrHipError(f"a view is a 3-D tensor (z, y, x), not {t.dim()}-D")
+        dz, dy, dx = (int(d) for d in t.shape)
+        sz, sy, sx = (int(v) for v in t.stride())
+        if min(dz, dy, dx) < 1:
+            raise SperrHipError("a view has no empty dimension")
+        if dx > 1 and sx != 1:
+            raise SperrHipError(f"a view has unit x stride, this tensor has {sx}")
+        # (the stride of a dimension of size 1 says nothing: take the tightest pitch that fits)
+        if dy == 1:
+            sy = sz if dz > 1 and sz >= dx else dx
+        if dz == 1:
+            sz = sy * dy
+        if sy < dx or sz < sy * dy or sz % sy != 0:
+            raise SperrHipError(f"strides {tuple(t.stride())} of shape {tuple(t.shape)} are no view: the row pitch must "
+                                "be at least x, the slice pitch at least y rows and a multiple of the row pitch")
+        return View(sy, sz)
+
+    @staticmethod
+    def _no_view(t, what):
+        if not t.is_contiguous():
+            raise SperrHipError(f"{what} takes contiguous tensors only, no strided views")
+
+    @staticmethod
+    def _room_bytes(t):
+        """bytes from the tensor's first element to the end of its storage"""
+        return t.untyped_storage().nbytes() - t.storage_offset() * t.element_size()
+
+    def _decompress_view(self, container, pct, output_float, lo, dims, out):
+        rtn = self.lib.sperrhip_decompress_view_dev(container.data_ptr(), container.numel(), int(pct),
+                                                    int(output_float), lo, dims, out.data_ptr(),
+                                                    C.byref(self.view_of(out)), self._room_bytes(out), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_view_dev returned {rtn}")
+        return out
+
     # ---- device-resident API -------------------------------------------------------------
     def max_compressed_size(self, shape_zyx, chunks_xyz, quality, mode=1):
         dz, dy, dx = shape_zyx
         return self.lib.sperrhip_max_compressed_size(dx, dy, dz, *chunks_xyz, mode, quality)
 
     def compress(self, vol, chunks_xyz, bpp, out=None, mode=1):
-        """vol: cuda tensor float32/float64 shaped (z, y, x). Returns a cuda uint8 tensor view of
+        """vol: cuda tensor float32/float64 shaped (z, y, x), contiguous or a strided view (view_of) of a larger
+        tensor, which is read where it lies.  Returns a cuda uint8 tensor view of
         the container (a slice of `out` when given).  mode 1: `bpp` is the bit rate; mode 2: it is
         the target PSNR in dB; mode 3: the point-wise error tolerance (the reference's modes,
         include/SPERR_C_API.h:95-99)."""
         torch = self.torch
-        assert vol.is_cuda and vol.is_contiguous() and vol.dim() == 3
+        assert vol.is_cuda and vol.dim() == 3
         assert vol.dtype in (torch.float32, torch.float64)
+        view = None if vol.is_contiguous() else self.view_of(vol)
         dz, dy, dx = vol.shape
         cap = self.max_compressed_size(vol.shape, chunks_xyz, bpp, mode)
         if out is None or out.numel() < cap:
             out = torch.empty(cap, dtype=torch.uint8, device=vol.device)
         n = _sz(0)
+        if view is not None:
+            rtn = self.lib.sperrhip_compress_view_dev(vol.data_ptr(), C.byref(view), int(vol.dtype == torch.float32),
+                                                      dx, dy, dz, *chunks_xyz, mode, float(bpp), out.data_ptr(),
+                                                      out.numel(), C.byref(n), self._stream())
+            if rtn != 0:
+                raise SperrHipError(f"sperrhip_compress_view_dev returned {rtn}")
+            return out[:n.value]
         rtn = self.lib.sperrhip_compress_dev(vol.data_ptr(), int(vol.dtype == torch.float32), dx,
                                              dy, dz, *chunks_xyz, mode, float(bpp), out.data_ptr(),
                                              out.numel(), C.byref(n), self._stream())
@@ -275,7 +343,8 @@ class SperrHip:
         return out
 
     def decompress(self, container, output_float=True, out=None, shape_zyx=None, pct=0):
-        """The volume of a device container, a cuda tensor shaped (z, y, x) -- `out` when given.  pct (here and in
+        """The volume of a device container, a cuda tensor shaped (z, y, x) -- `out` when given, which may be a
+        strided view (view_of) of a larger tensor: the volume is written into it and nothing around it.  pct (here and in
         decompress_box / decompress_level): decode the first pct percent of every chunk stream only, bit for bit the
         decode of truncate(container, pct) without making it; 0: everything."""
         torch = self.torch
@@ -285,6 +354,11 @@ class SperrHip:
         dt = torch.float32 if output_float else torch.float64
         if out is None:
             out = torch.empty(shape_zyx, dtype=dt, device=container.device)
+        if not out.is_contiguous():
+            assert out.dtype == dt and out.is_cuda
+            if tuple(out.shape) != tuple(shape_zyx):
+                raise SperrHipError(f"the view is {tuple(out.shape)}, the volume {tuple(shape_zyx)}")
+            return self._decompress_view(container, pct, output_float, None, None, out)
         assert out.dtype == dt and out.is_contiguous()
         if pct:
             return self._portion_dev(container, pct, output_float, None, None, None, out)
@@ -299,12 +373,19 @@ class SperrHip:
 
     def decompress_box(self, container, box_lo_xyz, box_dims_xyz, output_float=True, out=None, pct=0):
         """The box [lo, lo + dims) (x, y, z order) of a device container's volume, decoded from the chunks it
-        meets only; a cuda tensor shaped (dims z, dims y, dims x) -- `out` when given."""
+        meets only; a cuda tensor shaped (dims z, dims y, dims x) -- `out` when given, which may be a strided view
+        (view_of) of a larger tensor."""
         torch = self.torch
         assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
         dt = torch.float32 if output_float else torch.float64
         if out is None:
             out = torch.empty(tuple(int(d) for d in reversed(box_dims_xyz)), dtype=dt, device=container.device)
+        if not out.is_contiguous():
+            assert out.dtype == dt and out.is_cuda
+            if tuple(out.shape) != tuple(int(d) for d in reversed(box_dims_xyz)):
+                raise SperrHipError(f"the view is {tuple(out.shape)}, the box (x, y, z) {tuple(box_dims_xyz)}")
+            return self._decompress_view(container, pct, output_float, (_sz * 3)(*box_lo_xyz),
+                                         (_sz * 3)(*box_dims_xyz), out)
         assert out.dtype == dt and out.is_contiguous() and out.is_cuda
         if pct:
             return self._portion_dev(container, pct, output_float, None, (_sz * 3)(*box_lo_xyz),
@@ -331,6 +412,8 @@ class SperrHip:
         only the level's part of the inverse transform runs.  A cuda tensor shaped (z, y, x) -- `out` when given."""
         torch = self.torch
         assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
+        if out is not None:
+            self._no_view(out, "decompress_level")
         dt = torch.float32 if output_float else torch.float64
         lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
         if out is None:
@@ -399,6 +482,7 @@ class SperrHip:
         """vols: contiguous cuda tensor float32/float64 shaped (N, z, y, x).  Returns N cuda uint8 tensors, views into
         one buffer (`out` when it is large enough) in order: container v is what compress() makes of vols[v]."""
         torch = self.torch
+        self._no_view(vols, "compress_batch")
         assert vols.is_cuda and vols.is_contiguous() and vols.dim() == 4
         assert vols.dtype in (torch.float32, torch.float64)
         nvol, dz, dy, dx = vols.shape
@@ -453,14 +537,34 @@ class SperrHip:
 
     def quality(self, orig, recon, nbytes=None):
         """The reference's figures (calc_stats, calc_mean_var) of `recon` against `orig`, computed where they are:
-        contiguous cuda tensors of one dtype (float32 / float64) and numel, any shape.  A Quality record; `nbytes`
-        (the compressed size) adds bitrate and accuracy_gain."""
+        contiguous cuda tensors of one dtype (float32 / float64) and numel, any shape -- or, when either is a strided
+        view (view_of), two 3-D tensors of one shape (z, y, x), each contiguous or a view, with the figures of their
+        packed copies.  A Quality record; `nbytes` (the compressed size) adds bitrate and accuracy_gain."""
+        if not (orig.is_contiguous() and recon.is_contiguous()):
+            return self._quality_view(orig, recon, nbytes)
         self._quality_args(orig, recon)
         out = (C.c_double * 8)()
         rtn = self.lib.sperrhip_quality_dev(orig.data_ptr(), recon.data_ptr(), int(orig.dtype == self.torch.float32),
                                             orig.numel(), out, self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_quality_dev returned {rtn}")
+        return Quality(out[:8], orig.numel(), nbytes)
+
+    def _quality_view(self, orig, recon, nbytes):
+        torch = self.torch
+        assert orig.is_cuda and recon.is_cuda
+        assert orig.dtype == recon.dtype and orig.dtype in (torch.float32, torch.float64)
+        if orig.dim() != 3 or tuple(orig.shape) != tuple(recon.shape):
+            raise SperrHipError(f"with a view, both tensors are (z, y, x) of one shape: {tuple(orig.shape)} and "
+                                f"{tuple(recon.shape)}")
+        vo = None if orig.is_contiguous() else C.byref(self.view_of(orig))
+        vr = None if recon.is_contiguous() else C.byref(self.view_of(recon))
+        dz, dy, dx = orig.shape
+        out = (C.c_double * 8)()
+        rtn = self.lib.sperrhip_quality_view_dev(orig.data_ptr(), vo, recon.data_ptr(), vr,
+                                                 int(orig.dtype == torch.float32), dx, dy, dz, out, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_quality_view_dev returned {rtn}")
         return Quality(out[:8], orig.numel(), nbytes)
 
     def quality_batch(self, origs, recons):
@@ -698,6 +802,7 @@ class SperrHip:
     def compress_2d(self, img, quality, mode=1, header=False):
         """img: cuda tensor float32/float64 (y, x). Returns a cuda uint8 tensor (sperr_comp_2d)."""
         torch = self.torch
+        self._no_view(img, "compress_2d")
         assert img.is_cuda and img.is_contiguous() and img.dim() == 2
         dy, dx = img.shape
         self.lib.sperrhip_max_compressed_size_2d.restype = _sz

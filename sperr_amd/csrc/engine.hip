@@ -34,6 +34,7 @@
 #include "speck_tree_host.hpp"
 #include "outlier.h"
 #include "quality.h"
+#include "view.h"
 #include "xform.h"
 
 // The decoder runs the shape groups of a volume side by side on up to eight streams; the ROCm
@@ -2138,6 +2139,10 @@ void drain_after_error(Engine& E, hipStream_t st)
 // what a compression call makes: a 3D container, or one 2D slice without / with the 10-byte header
 enum class Coded { Container, Slice, SliceWithHeader };
 
+// How the kernels see a valid view (view.h) of a volume of dimz slices: their address is (z * rows + y) * pitch + x,
+// so the first two entries are pitches rather than extents; nothing on the device reads the third
+inline VolDesc view_desc(const ViewPitch& p, size_t dimz) { return VolDesc{{p.y, p.z / p.y, dimz}}; }
+
 // One compression call (compress_impl), stage by stage.  mode 1: fixed rate, `quality` bits per value; mode 2: fixed
 // PSNR and mode 3: fixed point-wise error, every bit plane is coded
 template <typename T>
@@ -2171,10 +2176,14 @@ struct EncodeCall {
   // `slice` (sperrhip_compress_2d_batch_dev): nvol slices, chunk s of dims (x, y, 1) at (0, 0, s), one shape group on
   // the 2D coder's forest, coded into nvol streams (k_slice_batch_layout)
   const size_t nvol = 1;
+  // d_src is the first element of a strided view of the volume (sperrhip_compress_view_dev; valid, one volume):
+  // every reader of the volume takes rows and slices from `vd`, `vol` stays what the chunks, the header and the
+  // size checks see
+  const ViewPitch* srcView = nullptr;
   const bool slice = what != Coded::Container;
   const bool rate = mode == 1;
   const double bpp = rate ? quality : 0.0;
-  const VolDesc vd{{vol[0], vol[1], vol[2] * nvol}};
+  const VolDesc vd = srcView ? view_desc(*srcView, vol[2]) : VolDesc{{vol[0], vol[1], vol[2] * nvol}};
   Dims cdim;
   uint32_t nchunks = 0;
   std::map<GKey, std::vector<ChunkRef>> groups;
@@ -2602,9 +2611,10 @@ struct EncodeCall {
 
 template <typename T>
 int compress_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkPref, int mode, double quality,
-                  uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st, Coded what = Coded::Container)
+                  uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st, Coded what = Coded::Container,
+                  const ViewPitch* srcView = nullptr)
 {
-  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, what};
+  EncodeCall<T> call{E, d_src, vol, mode, quality, d_dst, dst_cap, st, what, 1, srcView};
   if (call.run(chunkPref))
     return -1;
   *dst_len = (size_t)call.total;
@@ -3266,6 +3276,9 @@ struct DecodeRequest {
   const Window* window = nullptr;
   // beside the volume, every level of the hierarchy into levels->d_level (sperrhip_decompress_multires_dev)
   const MultiRes* levels = nullptr;
+  // d_dst is the first element of a strided view (view.h; valid for the output's dims) of a larger array: the volume
+  // or the box goes there, and nothing outside the view is written (sperrhip_decompress_view_dev).  null: dense
+  const ViewPitch* outView = nullptr;
 
   // (a box that is the whole volume is no window: such a call is the whole-volume decode)
   void set_window(const Window& w) { window = (w.level || w.crop) ? &w : nullptr; }
@@ -3282,6 +3295,8 @@ struct DecodeRequest {
     if (level() && stacked)   // a level's grid of chunk corners is one container's
       return false;
     if (level() && level()->h >= level()->m.nlev)   // the container has no such level
+      return false;
+    if (outView && (stacked || slices || levels || level()))   // a view holds one volume or a box of it at full resolution
       return false;
     return true;
   }
@@ -3303,13 +3318,21 @@ struct DecodeRequest {
     return sel;
   }
   // the output: the volume, or the window (its chunks write their pieces of it)
+  // (the non-crop writers place a chunk by its origin in the volume, the crop writers by its origin relative to the
+  //  box: with a view only the pitches differ)
   VolDesc out_desc(const ContainerInfo& ci) const
   {
-    return window ? VolDesc{{window->dims[0], window->dims[1], window->dims[2]}}
-                  : VolDesc{{ci.vol[0], ci.vol[1], ci.vol[2]}};
+    const Dims& d = window ? window->dims : ci.vol;
+    return outView ? view_desc(*outView, d[2]) : VolDesc{{d[0], d[1], d[2]}};
   }
+  // values d_dst has to hold: the output's, or with a view its extent (0: the view is not valid for the output)
   size_t out_vals(const ContainerInfo& ci) const
   {
+    if (outView) {
+      const Dims& d = window ? window->dims : ci.vol;
+      size_t e = 0;
+      return view_extent(d[0], d[1], d[2], *outView, &e) ? e : 0;
+    }
     return window ? window->dims[0] * window->dims[1] * window->dims[2] : ci.nvals;
   }
 };
@@ -4310,12 +4333,15 @@ int decode_to(Engine& E, const void* d_src, int output_float, void* d_dst, size_
 
 // the window `w` of it, once d_dst is seen to hold the window
 int decode_window(Engine& E, const void* d_src, int output_float, void* d_dst, size_t dst_cap_bytes,
-                  const ContainerInfo& ci, hipStream_t st, const Window& w)
+                  const ContainerInfo& ci, hipStream_t st, const Window& w, const ViewPitch* outView = nullptr)
 {
-  if (dst_cap_bytes / (output_float ? sizeof(float) : sizeof(double)) < w.dims[0] * w.dims[1] * w.dims[2])
+  const size_t esz = output_float ? sizeof(float) : sizeof(double);
+  if (outView ? !view_fits(w.dims[0], w.dims[1], w.dims[2], *outView, esz, dst_cap_bytes)
+              : dst_cap_bytes / esz < w.dims[0] * w.dims[1] * w.dims[2])
     return -1;
   DecodeRequest req;
   req.set_window(w);
+  req.outView = outView;
   return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, ci, st, req);
 }
 
@@ -4650,6 +4676,33 @@ int sperrhip_compress_dev(const void* d_src, int is_float, size_t dimx, size_t d
     return with_elem(is_float, [&](auto t) {
       return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, ch, mode, quality,
                            static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st);
+    });
+  });
+}
+
+int sperrhip_compress_view_dev(const void* d_src, const sperrhip_view* view, int is_float, size_t dimx, size_t dimy,
+                               size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
+                               void* d_dst, size_t dst_cap, size_t* dst_len, void* hip_stream)
+{
+  return guarded("sperrhip_compress_view_dev", [&]() -> int {
+    if (quality <= 0.0)
+      return 2;
+    if (mode < 1 || mode > 3)
+      return 2;
+    if (!d_src || !view || !d_dst || !dst_len)
+      return -1;
+    const ViewPitch pitch{view->pitch_y, view->pitch_z};
+    if (!view_valid(dimx, dimy, dimz, pitch))
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return with_elem(is_float, [&](auto t) {
+      return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, ch, mode, quality,
+                           static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st, Coded::Container, &pitch);
     });
   });
 }
@@ -5529,6 +5582,35 @@ int sperrhip_decompress_portion_dev(const void* d_src, size_t src_len, unsigned 
   });
 }
 
+// The volume or a box of it, of the first `pct` percent of every chunk stream, into a strided view of d_dst: the
+// request names the view, and every writer takes its pitches from DecodeRequest::out_desc
+int sperrhip_decompress_view_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
+                                 const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
+                                 const sperrhip_view* view, size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_decompress_view_dev", [&]() -> int {
+    if (!d_src || !d_dst || !view || (box_lo == nullptr) != (box_dims == nullptr))
+      return -1;
+    const ViewPitch pitch{view->pitch_y, view->pitch_z};
+    DevDecode d(d_src, src_len, hip_stream);
+    if (!d.ok)
+      return -1;
+    keep_portion(d.ci, pct);
+    if (box_lo) {
+      Window w;
+      if (box_select(d.ci, box_lo, box_dims, w))
+        return -1;
+      return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w, &pitch);
+    }
+    if (!view_fits(d.ci.vol[0], d.ci.vol[1], d.ci.vol[2], pitch, output_float ? sizeof(float) : sizeof(double),
+                   dst_cap_bytes))
+      return -1;
+    DecodeRequest req;
+    req.outView = &pitch;
+    return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, req);
+  });
+}
+
 // host container in, malloc'd host volume, box or level out: only the kept prefixes of the chosen chunks travel to the
 // device (decode_packed_host; the prefixes do not lie back to back, so each is a copy of its own)
 int sperrhip_decomp_3d_portion(const void* src, size_t src_len, unsigned pct, int output_float, const size_t* level,
@@ -5623,6 +5705,31 @@ int sperrhip_quality_dev(const void* d_orig, const void* d_recon, int is_float, 
                          void* hip_stream)
 {
   return sperrhip_quality_batch_dev(d_orig, d_recon, is_float, 1, n, out, hip_stream);
+}
+
+// the same of two arrays read through strided views (a NULL view: dense), by the view form of the rows kernel
+int sperrhip_quality_view_dev(const void* d_orig, const sperrhip_view* view_orig, const void* d_recon,
+                              const sperrhip_view* view_recon, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                              double* out, void* hip_stream)
+{
+  return guarded("sperrhip_quality_view_dev", [&]() -> int {
+    if (!d_orig || !d_recon || !out)
+      return -1;
+    const size_t need = quality_view_workspace_bytes(dimx, dimy, dimz, is_float);
+    if (need == 0)
+      return -1;
+    const ViewPitch dense = view_dense(dimx, dimy);   // (its products fit: the workspace's size has multiplied them)
+    const ViewPitch po = view_orig ? ViewPitch{view_orig->pitch_y, view_orig->pitch_z} : dense;
+    const ViewPitch pr = view_recon ? ViewPitch{view_recon->pitch_y, view_recon->pitch_z} : dense;
+    if (!view_valid(dimx, dimy, dimz, po) || !view_valid(dimx, dimy, dimz, pr))
+      return -1;
+    Lease L;
+    if (!L.e || L.e->arena.ensure(need))
+      return -1;
+    const int rtn = quality_view_run(d_orig, po, d_recon, pr, is_float, dimx, dimy, dimz, L.e->arena.p, out, hip_stream);
+    L.e->prof.collect();
+    return rtn;
+  });
 }
 
 }  // extern "C"

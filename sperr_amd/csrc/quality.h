@@ -14,6 +14,8 @@
 #include <cstddef>
 #include <limits>
 
+#include "view.h"
+
 namespace sperrhip {
 
 constexpr size_t kQualSqBlock = 8192;     // calc_stats: stride_size
@@ -77,6 +79,13 @@ size_t quality_workspace_bytes(size_t nvol, size_t n, int is_float);
 // the end.  0 ok, -1 a HIP error (out untouched).
 int quality_run(const void* d_orig, const void* d_recon, int is_float, size_t nvol, size_t n, void* ws,
                 double* out, void* hip_stream);
+
+// The same for one pair of arrays read through strided views (view.h) of dims (dimx, dimy, dimz), each from its
+// first element: the figures are bit for bit those of quality_run on packed copies.  dimx and dimy stay below
+// kViewCursorMaxDim.  The workspace's size is 0 for dims that are refused; -1 also for a view that is not valid.
+size_t quality_view_workspace_bytes(size_t dimx, size_t dimy, size_t dimz, int is_float);
+int quality_view_run(const void* d_orig, ViewPitch p_orig, const void* d_recon, ViewPitch p_recon, int is_float,
+                     size_t dimx, size_t dimy, size_t dimz, void* ws, double* out, void* hip_stream);
 
 }  // namespace sperrhip
 

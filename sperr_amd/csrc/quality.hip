@@ -12,11 +12,17 @@
 //   k_quality_mean<T>          per array: the row sums of a in order -> mean; max d, min, max, differ over its rows
 //   k_quality_rows<T, true>    a, mean -> per row: sum of (a - mean) * (a - mean)
 //
+// k_quality_rows<T, kVar, true> is the same kernel over two strided views (view.h) of one shape: the rows are those
+// of the views' own linear order, so every sum has the addends and the order of the dense kernel on packed copies;
+// only the addresses the values are loaded from differ.
+//
 // The sums over the rows' squared differences and variance partials are not needed on the device: the host adds them
 // in order after the call's one read-back (quality_finish).
 #include "common.h"
 #include "quality.h"
+#include "view.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace sperrhip {
@@ -54,10 +60,37 @@ struct QualWs {
   T* stats;      // [rows][4]: max d, min, max, differ
 };
 
-template <typename T, bool kVar>
+// how the view form walks its two arrays (they share the dims; the pitches may differ); the dense form takes none
+struct QualViews {
+  ViewWalk a, b;
+};
+struct QualNoViews {};
+
+// A thread's pack of a view: the 16 bytes at the cursor when they lie in one x-row of the view and in the row of
+// 16384 (`e` is the pack's place in it, `len` its length), else value by value with the carry into the next x-row and
+// slice; +0 past the row's end, where nothing is read.  Consecutive lanes stand on consecutive elements, so within an
+// x-row their addresses are consecutive too.
+template <typename T>
+__device__ __forceinline__ void qual_load_view(QualPack<T>& p, const T* __restrict__ base, const ViewCursor& c,
+                                               const ViewWalk& w, uint32_t e, uint32_t len)
+{
+  constexpr uint32_t V = 16 / sizeof(T);
+  if (e + V <= len && c.x + V <= w.dimx) {
+    __builtin_memcpy(&p, base + c.row + c.x, 16);
+    return;
+  }
+  ViewCursor k = c;
+#pragma unroll
+  for (uint32_t j = 0; j < V; j++) {
+    p.v[j] = e + j < len ? base[k.row + k.x] : T(0);
+    view_next(k, w);
+  }
+}
+
+template <typename T, bool kVar, bool kView = false>
 __global__ void __launch_bounds__(kQualThreads)
 k_quality_rows(const T* __restrict__ a, const T* __restrict__ b, uint64_t n, uint64_t nrow, uint64_t totalRows,
-               QualWs<T> ws)
+               QualWs<T> ws, typename std::conditional<kView, QualViews, QualNoViews>::type vw)
 {
   constexpr int V = 16 / sizeof(T);                        // values per pack
   constexpr int PPR = kQualSeg / V;                        // packs per row and segment
@@ -78,6 +111,7 @@ k_quality_rows(const T* __restrict__ a, const T* __restrict__ b, uint64_t n, uin
   const T* pb[NP];
   uint32_t len[NP];
   T mean[NP];
+  ViewCursor ca[kView ? NP : 1], cb[kView ? NP : 1];   // (kView: where this thread's next pack of each row starts)
 #pragma unroll
   for (int i = 0; i < NP; i++) {
     const uint32_t rr = t / PPR + i * RSTEP;
@@ -86,15 +120,24 @@ k_quality_rows(const T* __restrict__ a, const T* __restrict__ b, uint64_t n, uin
     pa[i] = a;
     pb[i] = b;
     mean[i] = 0;
+    if constexpr (kView)
+      ca[i] = cb[i] = ViewCursor{0, 0, 0};
     if (g < totalRows) {
       const uint64_t v = g / nrow, r = g - v * nrow;
       const uint64_t start = r * kQualMvBlock;               // <= n: the last row is the tail
       const uint64_t left = n - start;
       len[i] = (uint32_t)(left < kQualMvBlock ? left : kQualMvBlock);
-      pa[i] = a + v * n + start;
-      if (!kVar)
-        pb[i] = b + v * n + start;
-      else
+      if constexpr (kView) {   // (one array each: v is 0.  The row's only 64-bit divisions)
+        ca[i] = view_cursor(start + col, vw.a);
+        if (!kVar)
+          cb[i] = view_cursor(start + col, vw.b);
+      }
+      else {
+        pa[i] = a + v * n + start;
+        if (!kVar)
+          pb[i] = b + v * n + start;
+      }
+      if (kVar)
         mean[i] = ws.hdr[v * 8];
     }
     if (t % PPR == 0)
@@ -107,12 +150,21 @@ k_quality_rows(const T* __restrict__ a, const T* __restrict__ b, uint64_t n, uin
     maxLen = max(maxLen, shLen[r]);
 
   QualPack<T> x[NP], y[NP];
-  // the packs of segment `seg`; what lies past a row's end reads as +0
+  // the packs of segment `seg`; what lies past a row's end reads as +0.  (kView: the segments are asked for in order,
+  // and the cursors move on to the same columns of the next one)
   auto load_seg = [&](uint32_t seg) {
 #pragma unroll
     for (int i = 0; i < NP; i++) {
       const uint32_t e = seg + col;
-      if (e + V <= len[i]) {
+      if constexpr (kView) {
+        qual_load_view(x[i], a, ca[i], vw.a, e, len[i]);
+        view_advance(ca[i], vw.a, kQualSeg);
+        if (!kVar) {
+          qual_load_view(y[i], b, cb[i], vw.b, e, len[i]);
+          view_advance(cb[i], vw.b, kQualSeg);
+        }
+      }
+      else if (e + V <= len[i]) {
         __builtin_memcpy(&x[i], pa[i] + e, 16);
         if (!kVar)
           __builtin_memcpy(&y[i], pb[i] + e, 16);
@@ -347,9 +399,10 @@ QualLayout qual_layout(size_t nvol, size_t n, size_t esz)
   return L;
 }
 
+// `vw`: a and b are one array each, read through these views (null: nvol dense arrays back to back)
 template <typename T>
 int quality_run_t(const T* a, const T* b, size_t nvol, size_t n, char* base, const QualLayout& L, double* out,
-                  hipStream_t st)
+                  hipStream_t st, const QualViews* vw = nullptr)
 {
   QualWs<T> ws;
   ws.hdr = reinterpret_cast<T*>(base + L.hdr);
@@ -360,13 +413,21 @@ int quality_run_t(const T* a, const T* b, size_t nvol, size_t n, char* base, con
   const uint32_t blocks = (uint32_t)((L.total + kQualRows - 1) / kQualRows);
   // (LAUNCH_K with names of their own: the template arguments would end up in the profile's kernel names)
   prof_begin("k_quality_rows", st);
-  hipLaunchKernelGGL((k_quality_rows<T, false>), dim3(blocks), dim3(kQualThreads), 0, st, a, b, (uint64_t)n,
-                     (uint64_t)L.rows, (uint64_t)L.total, ws);
+  if (vw)
+    hipLaunchKernelGGL((k_quality_rows<T, false, true>), dim3(blocks), dim3(kQualThreads), 0, st, a, b, (uint64_t)n,
+                       (uint64_t)L.rows, (uint64_t)L.total, ws, *vw);
+  else
+    hipLaunchKernelGGL((k_quality_rows<T, false>), dim3(blocks), dim3(kQualThreads), 0, st, a, b, (uint64_t)n,
+                       (uint64_t)L.rows, (uint64_t)L.total, ws, QualNoViews{});
   prof_end(st);
   LAUNCH_K(k_quality_mean<T>, dim3((uint32_t)nvol), dim3(kQualThreads), 0, st, (uint64_t)n, (uint64_t)L.rows, ws);
   prof_begin("k_quality_rows_var", st);
-  hipLaunchKernelGGL((k_quality_rows<T, true>), dim3(blocks), dim3(kQualThreads), 0, st, a, a, (uint64_t)n,
-                     (uint64_t)L.rows, (uint64_t)L.total, ws);
+  if (vw)
+    hipLaunchKernelGGL((k_quality_rows<T, true, true>), dim3(blocks), dim3(kQualThreads), 0, st, a, a, (uint64_t)n,
+                       (uint64_t)L.rows, (uint64_t)L.total, ws, *vw);
+  else
+    hipLaunchKernelGGL((k_quality_rows<T, true>), dim3(blocks), dim3(kQualThreads), 0, st, a, a, (uint64_t)n,
+                       (uint64_t)L.rows, (uint64_t)L.total, ws, QualNoViews{});
   prof_end(st);
   HIP_CHECK(hipGetLastError());
   std::vector<char> host(L.back);
@@ -408,6 +469,39 @@ int quality_run(const void* d_orig, const void* d_recon, int is_float, size_t nv
                          static_cast<char*>(ws), L, out, st);
   return quality_run_t(static_cast<const double*>(d_orig), static_cast<const double*>(d_recon), nvol, n,
                        static_cast<char*>(ws), L, out, st);
+}
+
+// the values of a view of these dims, for the workspace and the rows; 0: none, too many, or a dim ViewCursor cannot hold
+static size_t qual_view_vals(size_t dimx, size_t dimy, size_t dimz)
+{
+  size_t n = 0;
+  if (dimx == 0 || dimy == 0 || dimz == 0 || dimx >= kViewCursorMaxDim || dimy >= kViewCursorMaxDim)
+    return 0;
+  if (!view_mul(dimx, dimy, &n) || !view_mul(n, dimz, &n))
+    return 0;
+  return n;
+}
+
+size_t quality_view_workspace_bytes(size_t dimx, size_t dimy, size_t dimz, int is_float)
+{
+  return quality_workspace_bytes(1, qual_view_vals(dimx, dimy, dimz), is_float);
+}
+
+int quality_view_run(const void* d_orig, ViewPitch p_orig, const void* d_recon, ViewPitch p_recon, int is_float,
+                     size_t dimx, size_t dimy, size_t dimz, void* ws, double* out, void* hip_stream)
+{
+  const size_t n = qual_view_vals(dimx, dimy, dimz);
+  const QualLayout L = qual_layout(1, n, is_float ? sizeof(float) : sizeof(double));
+  if (!L.ok || !d_orig || !d_recon || !ws || !out || !view_valid(dimx, dimy, dimz, p_orig) ||
+      !view_valid(dimx, dimy, dimz, p_recon))
+    return -1;
+  const QualViews vw{view_walk(dimx, dimy, p_orig), view_walk(dimx, dimy, p_recon)};
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (is_float)
+    return quality_run_t(static_cast<const float*>(d_orig), static_cast<const float*>(d_recon), 1, n,
+                         static_cast<char*>(ws), L, out, st, &vw);
+  return quality_run_t(static_cast<const double*>(d_orig), static_cast<const double*>(d_recon), 1, n,
+                       static_cast<char*>(ws), L, out, st, &vw);
 }
 
 }  // namespace sperrhip
