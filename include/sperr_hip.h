@@ -158,7 +158,19 @@ int sperrhip_speck3d_encode_dev(const void* d_coef, int width, const uint64_t* d
                                 size_t dimy, size_t dimz, size_t budget_bits, void* d_dst,
                                 size_t dst_cap, size_t* dst_len, void* hip_stream);
 
-/* Inverse of the above: d_coef (width 4 if the header says <= 32 planes, else 8) and d_sign are
+/* The outlier coder of point-wise error mode (mode 3) on its own: d_orig (floats when is_float,
+ * else doubles) and d_recon (doubles) hold nchunks chunks of dimx*dimy*dimz samples stacked along
+ * z; every sample whose error d_orig - d_recon is beyond tol is an outlier, and chunk c's outlier
+ * stream -- what follows its SPECK stream in a container -- is written to d_dst behind chunk
+ * c - 1's; lens[c] (host memory) receives its length, 0 for a chunk without outliers.  It runs the
+ * stage sperrhip_compress_dev runs behind its own reconstruction, with a mean of 0 and no constant
+ * chunk.  Returns 0 ok, 2 for bad arguments, -1 otherwise: an output that is too small, or an
+ * error of 2^63 and more, which the reference refuses (src/Outlier_Coder.cpp:88-91). */
+int sperrhip_outlier_encode_dev(const void* d_orig, int is_float, const double* d_recon,
+                                size_t dimx, size_t dimy, size_t dimz, size_t nchunks, double tol,
+                                void* d_dst, size_t dst_cap, size_t* lens, void* hip_stream);
+
+/* Inverse of sperrhip_speck3d_encode_dev: d_coef (width 4 if the header says <= 32 planes, else 8) and d_sign are
  * outputs. *width_out receives the width that was written. */
 int sperrhip_speck3d_decode_dev(const void* d_stream, size_t stream_len, size_t dimx, size_t dimy,
                                 size_t dimz, void* d_coef, uint64_t* d_sign, int* width_out,

@@ -37,9 +37,25 @@ def build_ref():
     return have_ref()
 
 
+# the newest functions of ref_probe.cpp that Ref binds: a prebuilt probe from before them (one carried along where the
+# reference's sources are not present to rebuild it) is no reference build for this tree
+_PROBE_NEEDS = (b"refp_outlier_encode", b"refp_outlier_decode_apply")
+
+
+def have_ref_library():
+    """oracle/_ref holds the reference's own library (what needs nothing of the probe asks this)"""
+    return os.path.exists(os.path.join(HERE, "_ref", "libSPERR_ref.so"))
+
+
 def have_ref():
-    return all(os.path.exists(os.path.join(HERE, "_ref", f))
-               for f in ("libSPERR_ref.so", "libref_probe.so"))
+    """oracle/_ref holds the reference build AND a probe that exports what Ref binds.  A stale probe counts as no
+    reference build: the tests then compare with the recorded digests (tests/refbits.py) instead of failing to load."""
+    paths = [os.path.join(HERE, "_ref", f) for f in ("libSPERR_ref.so", "libref_probe.so")]
+    if not all(os.path.exists(p) for p in paths):
+        return False
+    with open(paths[1], "rb") as f:
+        image = f.read()
+    return all(name in image for name in _PROBE_NEEDS)
 
 
 def pack_mask(bools):
@@ -178,7 +194,42 @@ class _CApiMixin:
         return out.reshape(dz.value, dy.value, dx.value)
 
 
-class Oracle(_CApiMixin):
+class OutlierRefused(RuntimeError):
+    """the outlier coder's return code (7: a raw error of 2^63 or more, src/Outlier_Coder.cpp:88-91)"""
+
+    def __init__(self, what, code):
+        super().__init__(f"{what} returned {code}")
+        self.code = code
+
+
+class _OutlierMixin:
+    """Outlier_Coder as a primitive: `_oenc` / `_odec` are set by the class that mixes this in."""
+
+    def outlier_encode(self, pos, err, n, tol):
+        """pos: ascending positions < n; err: their float64 errors, each beyond tol. Returns the stream."""
+        p = np.ascontiguousarray(pos, dtype=np.uint64)
+        e = np.ascontiguousarray(err, dtype=np.float64)
+        assert p.size == e.size
+        out, ln = _vp(None), _sz(0)
+        rtn = self._oenc(p.ctypes.data, e.ctypes.data, p.size, n, tol, C.byref(out), C.byref(ln))
+        if rtn:
+            raise OutlierRefused("outlier_encode", rtn)
+        s = C.string_at(out.value, ln.value)
+        self._libc.free(out)
+        return s
+
+    def outlier_decode_apply(self, stream, n, tol, vals):
+        """Returns vals (float64[n]) with the stream's correctors added."""
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        v = np.array(vals, dtype=np.float64, order="C").reshape(-1)
+        assert v.size == n
+        rtn = self._odec(buf.ctypes.data, buf.size, n, tol, v.ctypes.data)
+        if rtn:
+            raise OutlierRefused("outlier_decode_apply", rtn)
+        return v
+
+
+class Oracle(_CApiMixin, _OutlierMixin):
     """The plain-C restatement (oracle/sperr_oracle.c)."""
 
     def __init__(self):
@@ -188,6 +239,7 @@ class Oracle(_CApiMixin):
         self._trunc = L.orc_trunc_3d
         self._comp2, self._decomp2 = L.orc_comp_2d, L.orc_decomp_2d
         self._decomp2mr = L.orc_decomp_2d_multi_res
+        self._oenc, self._odec = L.orc_outlier_encode, L.orc_outlier_decode_apply
         self._wire()
         L.orc_dwt3d.argtypes = [_vp, _vp]
         L.orc_idwt3d.argtypes = [_vp, _vp]
@@ -208,6 +260,10 @@ class Oracle(_CApiMixin):
         L.orc_speck1d_encode.restype = C.c_int
         L.orc_speck1d_decode.argtypes = [_vp, _sz, _sz, _vp, _vp]
         L.orc_speck1d_decode.restype = C.c_int
+        L.orc_outlier_encode.argtypes = [_vp, _vp, _sz, _sz, C.c_double, C.POINTER(_vp), C.POINTER(_sz)]
+        L.orc_outlier_encode.restype = C.c_int
+        L.orc_outlier_decode_apply.argtypes = [_vp, _sz, _sz, C.c_double, _vp]
+        L.orc_outlier_decode_apply.restype = C.c_int
         L.orc_chunk_compress_rate.argtypes = [_vp, _vp, C.c_double, C.POINTER(_vp), C.POINTER(_sz)]
         L.orc_chunk_compress_rate.restype = C.c_int
         L.orc_chunk_decompress.argtypes = [_vp, _sz, _vp, _vp]
@@ -355,7 +411,7 @@ class Oracle(_CApiMixin):
         return out
 
 
-class Ref(_CApiMixin):
+class Ref(_CApiMixin, _OutlierMixin):
     """The real reference (oracle/_ref, built from /root/reference by oracle/Makefile)."""
 
     def __init__(self):
@@ -367,6 +423,7 @@ class Ref(_CApiMixin):
         self._trunc = self.lib.sperr_trunc_3d
         self._comp2, self._decomp2 = self.lib.sperr_comp_2d, self.lib.sperr_decomp_2d
         self._decomp2mr = self.probe.refp_decomp_2d_multi_res
+        self._oenc, self._odec = self.probe.refp_outlier_encode, self.probe.refp_outlier_decode_apply
         self._wire()
         P = self.probe
         P.refp_dwt3d.argtypes = [_vp, _sz, _sz, _sz]
@@ -382,6 +439,10 @@ class Ref(_CApiMixin):
         P.refp_speck1d_encode.restype = C.c_int
         P.refp_speck1d_decode.argtypes = [_vp, _sz, _sz, _vp, _vp]
         P.refp_speck1d_decode.restype = C.c_int
+        P.refp_outlier_encode.argtypes = [_vp, _vp, _sz, _sz, C.c_double, C.POINTER(_vp), C.POINTER(_sz)]
+        P.refp_outlier_encode.restype = C.c_int
+        P.refp_outlier_decode_apply.argtypes = [_vp, _sz, _sz, C.c_double, _vp]
+        P.refp_outlier_decode_apply.restype = C.c_int
         P.refp_chunk_compress_rate.argtypes = [_vp, _sz, _sz, _sz, C.c_double, C.POINTER(_vp),
                                                C.POINTER(_sz)]
         P.refp_chunk_compress_rate.restype = C.c_int

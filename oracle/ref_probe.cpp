@@ -10,6 +10,7 @@
 
 #include "CDF97.h"
 #include "Conditioner.h"
+#include "Outlier_Coder.h"
 #include "SPECK1D_INT_DEC.h"
 #include "SPECK1D_INT_ENC.h"
 #include "SPECK2D_FLT.h"
@@ -160,6 +161,44 @@ int refp_speck1d_decode(const uint8_t* stream, size_t len, size_t n, uint64_t* c
   if (planes <= 32)
     return decode_as<uint32_t, sperr::SPECK1D_INT_DEC<uint32_t>>(stream, len, dims, coeffs, signs);
   return decode_as<uint64_t, sperr::SPECK1D_INT_DEC<uint64_t>>(stream, len, dims, coeffs, signs);
+}
+
+// the outlier list through Outlier_Coder itself (integer width from the largest raw error, the
+// quantisation, SPECK1D_INT_ENC); returns its RTNType, *out is malloc'd when that is Good
+int refp_outlier_encode(const uint64_t* pos, const double* err, size_t count, size_t n, double tol,
+                        uint8_t** out, size_t* out_len)
+{
+  sperr::Outlier_Coder oc;
+  oc.set_length(n);
+  oc.set_tolerance(tol);
+  for (size_t k = 0; k < count; k++)
+    oc.add_outlier(sperr::Outlier(pos[k], err[k]));
+  const auto rtn = oc.encode();
+  if (rtn != sperr::RTNType::Good)
+    return static_cast<int>(rtn);
+  std::vector<uint8_t> s;
+  oc.append_encoded_bitstream(s);
+  *out = static_cast<uint8_t*>(std::malloc(s.size()));
+  std::memcpy(*out, s.data(), s.size());
+  *out_len = s.size();
+  return 0;
+}
+
+// Outlier_Coder::decode, its correctors added to vals[] (what SPECK_FLT::decompress does with them)
+int refp_outlier_decode_apply(const uint8_t* stream, size_t len, size_t n, double tol, double* vals)
+{
+  sperr::Outlier_Coder oc;
+  oc.set_length(n);
+  oc.set_tolerance(tol);
+  auto rtn = oc.use_bitstream(stream, len);
+  if (rtn != sperr::RTNType::Good)
+    return static_cast<int>(rtn);
+  rtn = oc.decode();
+  if (rtn != sperr::RTNType::Good)
+    return static_cast<int>(rtn);
+  for (const auto& o : oc.view_outlier_list())
+    vals[o.pos] += o.err;
+  return 0;
 }
 
 // one chunk through the reference's SPECK3D_FLT in fixed-rate mode; *out is malloc'd

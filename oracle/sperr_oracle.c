@@ -1734,6 +1734,12 @@ int orc_outlier_encode(const uint64_t* pos, const double* err, size_t count, siz
       maxerr = fabs(err[k]);
   if (!(maxerr < 0x1p63))
     return 7; /* RTNType::FE_Invalid */
+  /* the magnitudes are stored into integers of that width (:93-100,200): a magnitude of error / tol
+   * beyond it wraps, and one that wraps to zero is no coefficient; if all do, the coder writes
+   * {0 planes, 0 bits} (src/SPECK_INT.cpp:128-135) */
+  const long long maxint = llrint(maxerr);
+  const uint64_t width_mask = maxint <= 0xff ? 0xffu : maxint <= 0xffff ? 0xffffu
+                              : maxint <= 0xffffffffll ? 0xffffffffu : ~(uint64_t)0;
   uint64_t* coef = (uint64_t*)calloc(n, sizeof(uint64_t));
   uint64_t* sign = (uint64_t*)malloc(((n + 63) / 64) * 8);
   memset(sign, 0xff, ((n + 63) / 64) * 8);
@@ -1744,7 +1750,7 @@ int orc_outlier_encode(const uint64_t* pos, const double* err, size_t count, siz
       mask_set(sign, pos[k]);
     else
       mask_clr(sign, pos[k]);
-    coef[pos[k]] = (uint64_t)(ll < 0 ? -ll : ll);
+    coef[pos[k]] = (ll < 0 ? -(uint64_t)ll : (uint64_t)ll) & width_mask;
   }
   const int rtn = orc_speck1d_encode(coef, sign, n, stream, stream_len);
   free(coef);

@@ -24,7 +24,7 @@ EXPORTS = [
     "sperr_comp_3d", "sperr_decomp_3d", "sperr_parse_header", "sperr_trunc_3d",
     "sperrhip_max_compressed_size", "sperrhip_compress_dev", "sperrhip_decompress_dev",
     "sperrhip_parse_header_dev", "sperrhip_dwt3d_dev", "sperrhip_speck3d_encode_dev",
-    "sperrhip_speck3d_decode_dev", "sperrhip_profile_enable", "sperrhip_profile_reset",
+    "sperrhip_speck3d_decode_dev", "sperrhip_outlier_encode_dev", "sperrhip_profile_enable", "sperrhip_profile_reset",
     "sperrhip_profile_get", "sperrhip_profile_get2", "sperrhip_profile_only",
     "sperrhip_multires_levels", "sperrhip_decompress_multires_dev", "sperrhip_decomp_3d_multires",
     "sperr_comp_2d", "sperr_decomp_2d", "sperrhip_max_compressed_size_2d", "sperrhip_compress_2d_dev",
@@ -205,6 +205,9 @@ def load_library():
     lib.sperrhip_speck3d_decode_dev.restype = C.c_int
     lib.sperrhip_speck3d_decode_dev.argtypes = [_vp, _sz, _sz, _sz, _sz, _vp, _vp,
                                                 C.POINTER(C.c_int), _vp]
+    lib.sperrhip_outlier_encode_dev.restype = C.c_int
+    lib.sperrhip_outlier_encode_dev.argtypes = [_vp, C.c_int, _vp, _sz, _sz, _sz, _sz, C.c_double, _vp, _sz,
+                                                C.POINTER(_sz), _vp]
     lib.sperrhip_profile_enable.argtypes = [C.c_int]
     lib.sperrhip_profile_only.argtypes = [C.c_char_p]
     lib.sperrhip_profile_get2.restype = C.c_int
@@ -630,6 +633,28 @@ class SperrHip:
         else:
             c = raw.view(np.uint64)
         return c.reshape(shape_zyx), sign.cpu().numpy().view(np.uint64)
+
+    def outlier_encode(self, orig, recon, chunk_shape_zyx, tol):
+        """orig: cuda float32 / float64 tensor, recon: cuda float64 tensor, both nchunks chunks of chunk_shape_zyx
+        stacked along z.  Returns the chunks' outlier streams as a list of bytes (b"": no sample beyond tol)."""
+        torch = self.torch
+        assert orig.is_cuda and recon.is_cuda and orig.is_contiguous() and recon.is_contiguous()
+        assert orig.dtype in (torch.float32, torch.float64) and recon.dtype == torch.float64
+        dz, dy, dx = chunk_shape_zyx
+        n = dz * dy * dx
+        assert orig.numel() == recon.numel() and orig.numel() % n == 0 and orig.numel() > 0
+        nch = orig.numel() // n
+        cap = nch * (9 + 33 * n + 64)   # (at most 4 * 64 + 1 bits a sample: pwe_stage_finish's dense bound)
+        out = torch.empty(cap, dtype=torch.uint8, device=orig.device)
+        lens = (_sz * nch)()
+        rtn = self.lib.sperrhip_outlier_encode_dev(orig.data_ptr(), int(orig.dtype == torch.float32), recon.data_ptr(),
+                                                   dx, dy, dz, nch, float(tol), out.data_ptr(), cap, lens,
+                                                   self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_outlier_encode_dev returned {rtn}")
+        host = out[:sum(lens)].cpu().numpy().tobytes()
+        offs = np.concatenate([[0], np.cumsum(list(lens))]).astype(np.int64)
+        return [host[offs[c]:offs[c + 1]] for c in range(nch)]
 
     # ---- reference-compatible host API (include/sperr_hip.h) ------------------------------
     def comp_3d(self, vol, chunks_xyz, mode, quality, nthreads=0):

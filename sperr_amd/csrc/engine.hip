@@ -1889,18 +1889,14 @@ int enqueue_brick_inverse(hipStream_t st, const ShapePlan& P, DevBuf& box, std::
   return launch_lift_xyz(st, false, boxVals, boxStride, nb, cd, cst, 2, vals, brickVol, d_bricks, &lf);
 }
 
-template <typename T>
-int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb,
-                    const T* d_src, VolDesc vd, const uint32_t cd[3], double tol, bool anyWide, PweStage& S)
+// `begin` itself in two parts: what the decoder will reconstruct (pwe_recon_begin), and the first pass over it and the
+// input (pwe_scan_begin) -- which with pwe_stage_finish is the whole outlier coder, and is where
+// sperrhip_outlier_encode_dev enters with a reconstruction of the caller's.
+int pwe_recon_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb, VolDesc vd,
+                    const uint32_t cd[3], bool anyWide, PweStage& S)
 {
   EncBuffers& e = bb.eb;
   HostMarks& hm = S.hm;
-  OutlierBufs& ob = S.ob;
-  std::vector<OutlierChunk>& hoc = S.hoc;
-  if (E.pweLastStream) {   // (a second batch of one call: the first one's stage is not waited for at its end any more)
-    HIP_CHECK(hipStreamSynchronize(E.pweLastStream));
-    E.pweLastStream = nullptr;
-  }
   hm.mark("(3D coder done)", st);
   // What the decoder will reconstruct, in the conditioned domain (src/SPECK_FLT.cpp:461-486): by the brick inverse
   // where the plan allows it and no chunk has 64-bit coefficients, else by an inverse quantiser pass and the per-axis
@@ -1921,6 +1917,16 @@ int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs&
     }
   }
   hm.mark("inverse path", st);
+  return 0;
+}
+
+template <typename T>
+int pwe_scan_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb,
+                   const T* d_src, VolDesc vd, const uint32_t cd[3], double tol, PweStage& S)
+{
+  EncBuffers& e = bb.eb;
+  OutlierBufs& ob = S.ob;
+  std::vector<OutlierChunk>& hoc = S.hoc;
   memset(&ob, 0, sizeof(ob));
   ob.nchunks = nb;
   ob.N = P.N;
@@ -1961,6 +1967,17 @@ int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs&
     HIP_CHECK(hipMemcpyAsync(E.pweHost, ob.oc, bytes, hipMemcpyDeviceToHost, st));
   }
   return 0;
+}
+
+template <typename T>
+int pwe_stage_begin(hipStream_t st, Engine& E, const ShapePlan& P, EncBatchBufs& bb, uint32_t nb,
+                    const T* d_src, VolDesc vd, const uint32_t cd[3], double tol, bool anyWide, PweStage& S)
+{
+  if (E.pweLastStream) {   // (a second batch of one call: the first one's stage is not waited for at its end any more)
+    HIP_CHECK(hipStreamSynchronize(E.pweLastStream));
+    E.pweLastStream = nullptr;
+  }
+  return pwe_recon_begin(st, E, P, bb, nb, vd, cd, anyWide, S) || pwe_scan_begin<T>(st, E, P, bb, nb, d_src, vd, cd, tol, S);
 }
 
 template <typename T>
@@ -2134,6 +2151,70 @@ void drain_after_error(Engine& E, hipStream_t st)
         (void)hipStreamSynchronize(s);
   (void)hipGetLastError();
   E.pweLastStream = nullptr;
+}
+
+// The outlier stage of point-wise error mode on a reconstruction of the caller's: the batch is the nchunks chunks of
+// a volume (x, y, z * nchunks) cut along z, its chunk buffer holds d_recon, and from there on it is what compress runs
+// -- pwe_scan_begin, pwe_stage_finish -- with every chunk's mean 0 and none constant.
+template <typename T>
+int outlier_encode_impl(Engine& E, hipStream_t st, const ShapePlan& P, const T* d_orig, const double* d_recon,
+                               uint32_t nb, double tol, uint8_t* d_dst, size_t dst_cap, size_t* lens)
+{
+  const size_t N = P.N;
+  if (E.arena.ensure(enc_bytes_for(P, nb, 0, false) + 4096) || E.misc.ensure(round_up((size_t)nb * 8, 256) + 256))
+    return -1;
+  Arena A;
+  A.base = static_cast<char*>(E.arena.p);
+  A.cap = E.arena.n;
+  EncBatchBufs bb;
+  if (!carve_enc(A, P, nb, 0, bb, false))
+    return -1;
+  const uint32_t cd[3] = {P.dims[0], P.dims[1], P.dims[2]};
+  const VolDesc vd{{cd[0], cd[1], (uint64_t)cd[2] * nb}};
+  std::vector<CoderState> hcs(nb);
+  std::vector<ChunkGeom> hg(nb);
+  std::vector<uint32_t> hid(nb);
+  memset(hcs.data(), 0, nb * sizeof(CoderState));
+  for (uint32_t i = 0; i < nb; i++) {
+    hg[i].org[0] = hg[i].org[1] = 0;
+    hg[i].org[2] = i * cd[2];
+    hid[i] = i;
+  }
+  uint64_t* d_lens2 = static_cast<uint64_t*>(E.misc.p);
+  std::vector<uint64_t> hl(nb, 0);
+  PweStage S;
+  PweKeepList keep;
+  auto run = [&]() -> int {
+    HIP_CHECK(hipMemcpyAsync(bb.eb.cst, hcs.data(), nb * sizeof(CoderState), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(bb.geom, hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(bb.gids, hid.data(), nb * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpy2DAsync(bb.vals, bb.valsStride * 8, d_recon, N * 8, N * 8, nb, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemsetAsync(d_lens2, 0, (size_t)nb * 8, st));
+    if (pwe_scan_begin<T>(st, E, P, bb, nb, d_orig, vd, cd, tol, S) ||
+        pwe_stage_finish<T>(st, E, P, bb, nb, d_orig, vd, cd, tol, d_lens2, keep, S))
+      return -1;
+    HIP_CHECK(hipMemcpyAsync(hl.data(), d_lens2, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    size_t pos = 0;
+    for (uint32_t i = 0; i < nb; i++) {
+      lens[i] = (size_t)hl[i];
+      if (!hl[i])
+        continue;
+      if (keep.empty() || hl[i] > dst_cap - std::min(pos, dst_cap))
+        return -1;
+      HIP_CHECK(hipMemcpyAsync(d_dst + pos, keep.back().slots + keep.back().off2[i], hl[i], hipMemcpyDeviceToDevice, st));
+      pos += hl[i];
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    return 0;
+  };
+  const int rtn = run();
+  if (rtn)
+    drain_after_error(E, st);   // (queued copies read and write the vectors above)
+  E.pweLastStream = nullptr;
+  E.prof.collect();
+  return rtn;
 }
 
 // what a compression call makes: a 3D container, or one 2D slice without / with the 10-byte header
@@ -5234,6 +5315,31 @@ int sperrhip_speck3d_encode_dev(const void* d_coef, int width, const uint64_t* d
       return -1;
     *dst_len = (size_t)len;
     return 0;
+  });
+}
+
+int sperrhip_outlier_encode_dev(const void* d_orig, int is_float, const double* d_recon, size_t dimx, size_t dimy,
+                                size_t dimz, size_t nchunks, double tol, void* d_dst, size_t dst_cap, size_t* lens,
+                                void* hip_stream)
+{
+  return guarded("sperrhip_outlier_encode_dev", [&]() -> int {
+    if (!d_orig || !d_recon || !lens || !(tol > 0.0) || nchunks == 0 || dimx == 0 || dimy == 0 || dimz == 0)
+      return 2;
+    if (nchunks > 0xffffffffull / dimz)   // (a chunk's origin along z is a uint32)
+      return 2;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    ShapePlan* P = E.plan(dimx, dimy, dimz);
+    if (!P)
+      return -1;
+    uint8_t* dst = static_cast<uint8_t*>(d_dst);
+    return is_float ? outlier_encode_impl<float>(E, st, *P, static_cast<const float*>(d_orig), d_recon, (uint32_t)nchunks,
+                                                 tol, dst, dst_cap, lens)
+                    : outlier_encode_impl<double>(E, st, *P, static_cast<const double*>(d_orig), d_recon,
+                                                  (uint32_t)nchunks, tol, dst, dst_cap, lens);
   });
 }
 

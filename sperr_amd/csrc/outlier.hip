@@ -797,10 +797,18 @@ k_speck1d(OutlierBufs b)
   };
 
   // (runs of a single value on a list -- arrays of fewer than four values -- keep the serial walk: a
-  //  descent with a stack of the right halves that still wait for their test bit)
+  //  descent with a stack of the right halves that still wait for their test bit.
+  //  A run of one value splits into that value and an EMPTY right half (src/SPECK1D_INT.cpp:36-56): the empty half gets
+  //  its test bit, a '0', and is then no set -- the reference drops it at the plane's end (m_clean_LIS), before anything
+  //  tests it again, so it never goes on a list here.  Only the array's own halves can be such runs, in an array of
+  //  two or three values.)
   auto expand_serial = [&](uint32_t ns, uint32_t nl, uint32_t nlev) {
     uint32_t sp = 0;
     while (true) {
+      if (nl == 0) {   // (a damaged stream set the bit of an empty half: nothing lies below it)
+        err = 2;
+        return;
+      }
       const uint32_t h0 = nl - nl / 2, r0 = nl / 2;
       bool atPixel = false;
       if (get()) {
@@ -852,7 +860,7 @@ k_speck1d(OutlierBufs b)
         }
         if (rl == 1)
           lip_set(rs);
-        else
+        else if (rl > 1)
           list_push(rlev, rs, rl);
       }
       if (!down)
@@ -1220,7 +1228,8 @@ k_speck1d(OutlierBufs b)
               }
               else {
                 wrlane(vT, f, nstate);
-                list_push(flev + 1, cs, cl);
+                if (cl)   // (the empty right half of a run of one value is no set: see expand_serial)
+                  list_push(flev + 1, cs, cl);
               }
             }
           }

@@ -135,5 +135,39 @@ def main():
                    "cases": cases, "cases_2d": cases2d}, f, indent=1)
 
 
+def outlier_streams():
+    """tests/golden/outlier_streams.npz: what the reference's Outlier_Coder (and, for the 64-plane case no error list
+    can express, its SPECK1D_INT_ENC) writes for the case table of tests/outlier_cases.py up to GOLDEN_MAX_N, and the
+    SHA-256 of what its decoder adds to a hashed base array.  Data only: uint8 arrays.
+
+        python tests/golden/make_golden.py outlier
+    """
+    import outlier_cases as oc
+    ref = Ref()
+    out = {}
+    for name, n in oc.coder_cases(max_n=oc.GOLDEN_MAX_N):
+        coef, sign = oc.coder_case(name, n)
+        if name == "top_bit":
+            stream = ref.speck1d_encode(coef, sign)
+        else:
+            stream = ref.outlier_encode(*oc.outlier_list(oc.errors_of(coef, sign, 1.0), 1.0), n, 1.0)
+        dec = ref.outlier_decode_apply(stream, n, oc.GOLDEN_TOL, oc.golden_base(n))
+        out[f"coder/{name}/{n}"] = np.frombuffer(stream, dtype=np.uint8)
+        out[f"decoded/{name}/{n}"] = np.frombuffer(hashlib.sha256(dec.tobytes()).digest(), dtype=np.uint8)
+        print(name, n, len(stream), stream[0])
+    for name, n, tol, err in oc.encoder_cases():
+        assert n <= oc.GOLDEN_MAX_N
+        stream = ref.outlier_encode(*oc.outlier_list(err, tol), n, tol)
+        dec = ref.outlier_decode_apply(stream, n, tol, oc.golden_base(n))
+        out[f"encoder/{name}"] = np.frombuffer(stream, dtype=np.uint8)
+        out[f"decoded/{name}"] = np.frombuffer(hashlib.sha256(dec.tobytes()).digest(), dtype=np.uint8)
+        print(name, n, len(stream), stream[0])
+    np.savez_compressed(os.path.join(HERE, "outlier_streams.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["outlier"]:
+        outlier_streams()
+    else:
+        main()
+        outlier_streams()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from fields import smooth_field
+from outlier_cases import outlier_start
 from sperr_amd import api
 from sperr_amd.synth import turbulence
 
@@ -180,16 +181,6 @@ def chunk_table(container, nch):
     lens = np.frombuffer(container, dtype=np.uint32, count=nch, offset=20)
     offs = 20 + 4 * nch + np.concatenate([[0], np.cumsum(lens.astype(np.int64))[:-1]])
     return [int(o) for o in offs], [int(n) for n in lens]
-
-
-def outlier_start(chunk):
-    """where the outlier stream of a chunk's stream starts (the bytes behind its SPECK stream), or None:
-    {17 bytes of conditioner header, u8 planes, u64 total_bits, payload} (src/SPECK_FLT.cpp:88-103)"""
-    if len(chunk) < 26 or chunk[0] & 0x01:
-        return None
-    tb = int(np.frombuffer(chunk, dtype=np.uint64, count=1, offset=18)[0])
-    speck = min(9 + (tb + 7) // 8, len(chunk) - 17)
-    return 17 + speck if 17 + speck + 9 <= len(chunk) else None
 
 
 @pytest.mark.parametrize("mode,q", [(1, 2.0), (3, 1e-3)])

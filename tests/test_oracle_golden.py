@@ -133,3 +133,29 @@ def test_dwt_roundtrip(oracle):
         a = smooth_field(shape)
         back = oracle.idwt3d(oracle.dwt3d(a.astype(np.float64)))
         assert np.max(np.abs(back - a)) <= 1e-11 * np.max(np.abs(a))
+
+
+def test_oracle_matches_golden_outlier_streams(oracle):
+    """The outlier coder as a primitive against the reference's recorded streams (tests/golden/outlier_streams.npz,
+    the case table of tests/outlier_cases.py up to GOLDEN_MAX_N): up to 64 bit planes, the integer widths 8 to 64
+    with their wraps, the ties and the tolerance's boundary -- the same bytes, and the same decoded bits."""
+    import outlier_cases as oc
+    gold = np.load(os.path.join(GOLD, "outlier_streams.npz"))
+    seen = set()
+    for name, n in oc.coder_cases(max_n=oc.GOLDEN_MAX_N):
+        coef, sign = oc.coder_case(name, n)
+        want = gold[f"coder/{name}/{n}"].tobytes()
+        assert oracle.speck1d_encode(coef, sign) == want, (name, n)
+        if name != "top_bit":
+            assert oracle.outlier_encode(*oc.outlier_list(oc.errors_of(coef, sign, 1.0), 1.0), n, 1.0) == want, (name, n)
+        dec = oracle.outlier_decode_apply(want, n, oc.GOLDEN_TOL, oc.golden_base(n))
+        assert hashlib.sha256(dec.tobytes()).digest() == gold[f"decoded/{name}/{n}"].tobytes(), (name, n)
+        seen.add(f"coder/{name}/{n}")
+    for name, n, tol, err in oc.encoder_cases():
+        want = gold[f"encoder/{name}"].tobytes()
+        assert oracle.outlier_encode(*oc.outlier_list(err, tol), n, tol) == want, name
+        dec = oracle.outlier_decode_apply(want, n, tol, oc.golden_base(n))
+        assert hashlib.sha256(dec.tobytes()).digest() == gold[f"decoded/{name}"].tobytes(), name
+        seen.add(f"encoder/{name}")
+    assert seen == {k for k in gold.files if not k.startswith("decoded/")}
+    assert max(gold[k][0] for k in seen) == 64

@@ -311,3 +311,68 @@ def test_value_domain_speck_patterns_bit_exact(oracle, ref, pattern):
                 assert same(sign_bits(sgo), br), (shape, budget, cut)
                 if budget == 0 and cut == len(so):   # the whole stream gives the coefficients back
                     assert np.array_equal(co, coef) and np.array_equal(sign_bits(sgo), sign_bits(sign)), shape
+
+
+# ---- the outlier coder as a primitive (tests/outlier_cases.py) -----------------------------------------------------
+
+
+def refusal_code(call):
+    """the return code an outlier coder refuses with, 0 if it does not"""
+    from oracle.pyoracle import OutlierRefused
+    try:
+        call()
+    except OutlierRefused as e:
+        return e.code
+    return 0
+
+
+def test_outlier_coder_bit_exact(oracle, ref):
+    """Outlier_Coder (src/Outlier_Coder.cpp) itself against the oracle's orc_outlier_encode / _decode_apply: the table's
+    coder cases up to 64 bit planes, and the encoder cases in which the reference's integer width, picked from the
+    largest raw error, wraps the magnitudes of error / tolerance -- some or all of them to zero --, the ties of llrint,
+    the tolerance's boundary and the refusal from a raw error of 2^63 on.  Same stream byte for byte, same bits from
+    both decoders."""
+    import outlier_cases as oc
+    widths, wrapped = set(), set()
+    for name, n in oc.coder_cases():
+        coef, sign = oc.coder_case(name, n)
+        stream = oracle.speck1d_encode(coef, sign)
+        assert same(stream, ref.get(lambda r: r.speck1d_encode(coef, sign))), (name, n)
+        if name != "top_bit":   # (an error of 2^63 tolerances needs a raw error the coder refuses or cannot hold)
+            pos, err = oc.outlier_list(oc.errors_of(coef, sign, 1.0), 1.0)
+            assert oracle.outlier_encode(pos, err, n, 1.0) == stream, (name, n)
+            assert same(stream, ref.get(lambda r: r.outlier_encode(pos, err, n, 1.0))), (name, n)
+        tol, base = oc.GOLDEN_TOL, oc.golden_base(n)
+        got = oracle.outlier_decode_apply(stream, n, tol, base)
+        assert same(bits(got), ref.get(lambda r: r.outlier_decode_apply(stream, n, tol, base))), (name, n)
+        assert np.array_equal(got, base + oc.corrector(coef, sign, tol)), (name, n)
+    for name, n, tol, err in oc.encoder_cases():
+        pos, e = oc.outlier_list(err, tol)
+        stream = oracle.outlier_encode(pos, e, n, tol)
+        assert same(stream, ref.get(lambda r: r.outlier_encode(pos, e, n, tol))), name
+        base = np.zeros(n)
+        got = oracle.outlier_decode_apply(stream, n, tol, base)
+        assert same(bits(got), ref.get(lambda r: r.outlier_decode_apply(stream, n, tol, base))), name
+        raw = int(np.rint(np.abs(e).max()))
+        width = 8 if raw <= 0xff else 16 if raw <= 0xffff else 32 if raw <= 0xffffffff else 64
+        widths.add(width)
+        if np.abs(e / tol).max() >= 2.0 ** width:
+            wrapped.add(width)
+            assert stream[0] <= width, name
+    assert widths == {8, 16, 32, 64} and wrapped == {8, 16, 32}
+    zero = dict((c[0], c) for c in oc.encoder_cases())["all_wrap_to_zero"]
+    assert oracle.outlier_encode(*oc.outlier_list(zero[3], zero[2]), zero[1], zero[2]) == bytes(9)
+    ex = dict((c[0], c) for c in oc.encoder_cases())["wrap_example"]
+    assert oracle.outlier_encode(*oc.outlier_list(ex[3], ex[2]), ex[1], ex[2]).hex() == \
+        "086800000000000000af2c0080000cc0000480000000"
+    # refusals: a raw error of 2^63 (FE_INVALID, code 7); an error within the tolerance in the list; an empty list
+    name, n, tol, p, e = oc.REFUSED_ENCODER_CASE
+    assert refusal_code(lambda: oracle.outlier_encode([p], [e], n, tol)) == 7
+    assert same(7, ref.get(lambda r: refusal_code(lambda: r.outlier_encode([p], [e], n, tol))))
+    assert refusal_code(lambda: oracle.outlier_encode([p], [-e], n, tol)) == 7
+    assert same(7, ref.get(lambda r: refusal_code(lambda: r.outlier_encode([p], [-e], n, tol))))
+    below = np.nextafter(e, 0.0)
+    assert same(oracle.outlier_encode([p], [below], n, tol), ref.get(lambda r: r.outlier_encode([p], [below], n, tol)))
+    for plist, elist in (([3], [0.125]), ([3, 4], [1.0, 0.125]), ([], [])):
+        assert refusal_code(lambda: oracle.outlier_encode(plist, elist, 65, 0.125)) != 0
+        assert same(True, ref.get(lambda r: refusal_code(lambda: r.outlier_encode(plist, elist, 65, 0.125)) != 0))

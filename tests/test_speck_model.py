@@ -322,6 +322,50 @@ def test_model_1d_coder_paths(oracle, model, n, k, top):
             assert np.array_equal(unpack_mask(s3, n)[coef > 0], sign[coef > 0])
 
 
+def _table_cases():
+    import outlier_cases as oc
+    # (the model states the formulations for arrays of four values and more, as k_speck1d uses them; below that the
+    #  kernel keeps a serial walk, which the GPU tests compare with the oracle)
+    return [(name, n) for name, n in oc.coder_cases() if n >= 4]
+
+
+@pytest.mark.parametrize("name,n", _table_cases())
+def test_model_1d_coder_table(oracle, model, name, n):
+    """The same three formulations on the case table of tests/outlier_cases.py: up to 64 bit planes, every position
+    found, one value per plane, the first and the last position, runs across word boundaries."""
+    import outlier_cases as oc
+    from oracle.pyoracle import pack_mask, unpack_mask
+    lib = model
+    lib.model_speck1d_encode.argtypes = [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_sz)]
+    lib.model_speck1d_encode.restype = C.c_int
+    lib.model_speck1d_decode.argtypes = [_vp, _sz, _sz, _vp, _vp]
+    lib.model_speck1d_decode.restype = C.c_int
+    lib.model_speck1d_decode_batched.argtypes = [_vp, _sz, _sz, _vp, _vp, C.c_uint32]
+    lib.model_speck1d_decode_batched.restype = C.c_int
+    coef, sign = oc.coder_case(name, n)
+    want = oracle.speck1d_encode(coef, sign)
+    assert want[0] == int(coef.max()).bit_length()
+    sm = pack_mask(sign)
+    out, ln = _vp(None), _sz(0)
+    assert lib.model_speck1d_encode(coef.ctypes.data, sm.ctypes.data, n, C.byref(out), C.byref(ln)) == 0
+    got = C.string_at(out.value, ln.value)
+    C.CDLL(None).free(out)
+    assert got == want
+    buf = np.frombuffer(want, dtype=np.uint8)
+    c2 = np.zeros(n, dtype=np.uint64)
+    s2 = np.zeros((n + 63) // 64, dtype=np.uint64)
+    assert lib.model_speck1d_decode(buf.ctypes.data, buf.size, n, c2.ctypes.data, s2.ctypes.data) == 0
+    assert np.array_equal(c2, coef)
+    assert np.array_equal(unpack_mask(s2, n)[coef > 0], sign[coef > 0])
+    for batch in (64, 3):
+        c3 = np.zeros(n, dtype=np.uint64)
+        s3 = np.zeros((n + 63) // 64, dtype=np.uint64)
+        assert lib.model_speck1d_decode_batched(buf.ctypes.data, buf.size, n, c3.ctypes.data, s3.ctypes.data,
+                                                batch) == 0
+        assert np.array_equal(c3, coef), batch
+        assert np.array_equal(unpack_mask(s3, n)[coef > 0], sign[coef > 0])
+
+
 def test_model_bit_words(model):
     """The word-level steps of the decoder's pixel passes (sperr_amd/csrc/bit_words.h: bits spread under / gathered
     from under a mask with parallel-suffix steps, a word's LIP token starts with one addition) against bit-by-bit
