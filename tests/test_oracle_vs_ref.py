@@ -313,6 +313,38 @@ def test_value_domain_speck_patterns_bit_exact(oracle, ref, pattern):
                     assert np.array_equal(co, coef) and np.array_equal(sign_bits(sgo), sign_bits(sign)), shape
 
 
+# ---- coefficient patterns aligned to the set tree (tests/coef_cases.py) ---------------------------------------------
+
+
+def _coef_cases():
+    import coef_cases as cc
+    return pytest.mark.parametrize("name,shape", cc.ALL_CASES, ids=cc.CASE_IDS)
+
+
+@_coef_cases()
+def test_tree_aligned_patterns_bit_exact(oracle, ref, name, shape):
+    """The SPECK stage at 128^3 (and at 100 x 128 x 128, whose lists mix set shapes) on patterns that keep the lists
+    of the 2^3, 4^3 and 8^3 sets thousands of entries long and choose what their tokens are: the oracle's stream, and
+    its decode of the whole stream and of the stream cut to 1/2 and to 1/7 of its payload, against the reference's."""
+    import coef_cases as cc
+    coef, sign, _ = cc.case(name, shape)
+    so = oracle.speck3d_encode(coef, sign, 0)
+    assert same(so, ref.get(lambda r: r.speck3d_encode(coef, sign, 0, width=8)))
+    for cut in cc.stream_cuts(so):
+        co, sgo = oracle.speck3d_decode(so[:cut], shape)
+        idx = np.nonzero(co.reshape(-1) != 0)[0]
+
+        def ref_decode(r):   # the reference's coefficients and the signs of the nonzero ones
+            c, s = r.speck3d_decode(so[:cut], shape)
+            return c, cc.sign_bits(s, idx)
+
+        cr, br = ref.get(ref_decode)
+        assert same(co, cr), cut
+        assert same(cc.sign_bits(sgo, idx), br), cut
+        if cut == len(so):   # the whole stream gives the coefficients back
+            assert np.array_equal(co, coef) and np.array_equal(cc.sign_bits(sgo, idx), cc.sign_bits(sign, idx))
+
+
 # ---- the outlier coder as a primitive (tests/outlier_cases.py) -----------------------------------------------------
 
 

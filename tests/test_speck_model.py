@@ -97,6 +97,28 @@ def test_model_decoder_matches_oracle(oracle, model, shape, budget):
         assert np.array_equal(s0, s1)
 
 
+def _coef_cases():
+    import coef_cases as cc
+    return pytest.mark.parametrize("name,shape", cc.ALL_CASES, ids=cc.CASE_IDS)
+
+
+@_coef_cases()
+def test_model_on_tree_aligned_patterns(oracle, model, name, shape):
+    """The count -> scan -> scatter encoder and the decoder of the model on the case table of tests/coef_cases.py:
+    128^3 patterns that keep the lists of the small sets thousands of entries long, all '0', half '1' or all '1'."""
+    import coef_cases as cc
+    coef, sign, _ = cc.case(name, shape)
+    want = oracle.speck3d_encode(coef, sign, 0)
+    assert model_encode(model, coef, sign, 0) == want
+    assert model_encode(model, coef, sign, 200000) == oracle.speck3d_encode(coef, sign, 200000)
+    if hasattr(model, "model_speck3d_decode"):
+        for cut in cc.stream_cuts(want):
+            c0, s0 = oracle.speck3d_decode(want[:cut], shape)
+            c1, s1 = model_decode(model, want[:cut], shape)
+            assert np.array_equal(c0, c1), cut
+            assert np.array_equal(s0, s1), cut
+
+
 def model_decode_par(lib, stream, shape, window):
     dz, dy, dx = shape
     buf = np.frombuffer(stream, dtype=np.uint8)
