@@ -153,7 +153,9 @@ int sperrhip_dwt3d_dev(double* d_vals, size_t dimx, size_t dimy, size_t dimz, in
 
 /* SPECK3D-encode one chunk of already quantised coefficients.  width is 4 or 8 (bytes per
  * magnitude); d_sign holds (n+63)/64 words, bit i set = non-negative.  budget_bits 0 = unlimited.
- * The 9-byte-header stream is written to d_dst; *dst_len receives its length. */
+ * The 9-byte-header stream is written to d_dst; *dst_len receives its length.
+ * dimz = 0 means a dimx x dimy slice through the 2D coder (SPECK2D_INT: the quadtree forest and the type-I set), with
+ * n = dimx * dimy coefficients; dimz = 1 is a one-sample-thick chunk of the 3D coder, whose stream differs. */
 int sperrhip_speck3d_encode_dev(const void* d_coef, int width, const uint64_t* d_sign, size_t dimx,
                                 size_t dimy, size_t dimz, size_t budget_bits, void* d_dst,
                                 size_t dst_cap, size_t* dst_len, void* hip_stream);
@@ -171,7 +173,7 @@ int sperrhip_outlier_encode_dev(const void* d_orig, int is_float, const double* 
                                 void* d_dst, size_t dst_cap, size_t* lens, void* hip_stream);
 
 /* Inverse of sperrhip_speck3d_encode_dev: d_coef (width 4 if the header says <= 32 planes, else 8) and d_sign are
- * outputs. *width_out receives the width that was written. */
+ * outputs. *width_out receives the width that was written.  dimz = 0, as there: the stream of a dimx x dimy slice. */
 int sperrhip_speck3d_decode_dev(const void* d_stream, size_t stream_len, size_t dimx, size_t dimy,
                                 size_t dimz, void* d_coef, uint64_t* d_sign, int* width_out,
                                 void* hip_stream);

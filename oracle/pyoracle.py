@@ -39,7 +39,7 @@ def build_ref():
 
 # the newest functions of ref_probe.cpp that Ref binds: a prebuilt probe from before them (one carried along where the
 # reference's sources are not present to rebuild it) is no reference build for this tree
-_PROBE_NEEDS = (b"refp_outlier_encode", b"refp_outlier_decode_apply")
+_PROBE_NEEDS = (b"refp_outlier_encode", b"refp_outlier_decode_apply", b"refp_speck2d_encode", b"refp_speck2d_decode")
 
 
 def have_ref_library():
@@ -253,6 +253,10 @@ class Oracle(_CApiMixin, _OutlierMixin):
         L.orc_speck3d_encode.restype = C.c_int
         L.orc_speck3d_decode.argtypes = [_vp, _sz, _vp, _vp, _vp]
         L.orc_speck3d_decode.restype = C.c_int
+        L.orc_speck2d_encode.argtypes = [_vp, _vp, _sz, _sz, _sz, C.POINTER(_vp), C.POINTER(_sz)]
+        L.orc_speck2d_encode.restype = C.c_int
+        L.orc_speck2d_decode.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp]
+        L.orc_speck2d_decode.restype = C.c_int
         L.orc_decomp_3d_multi_res.restype = C.c_int
         L.orc_decomp_3d_multi_res.argtypes = [_vp, _sz, _sz, C.POINTER(_sz), C.POINTER(_sz),
                                               C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _vp, _vp]
@@ -336,6 +340,29 @@ class Oracle(_CApiMixin, _OutlierMixin):
         sign = np.zeros((coef.size + 63) // 64, dtype=np.uint64)
         self.lib.orc_speck3d_decode(buf.ctypes.data, buf.size, self._dims((dx, dy, dz)),
                                     coef.ctypes.data, sign.ctypes.data)
+        return coef, sign
+
+    def speck2d_encode(self, coef_yx, sign_words, budget_bits=0):
+        """coef_yx: uint64 (y, x); sign_words: uint64 words. Returns the 9-byte-header stream of the 2D coder."""
+        c = np.ascontiguousarray(coef_yx, dtype=np.uint64)
+        dy, dx = c.shape
+        out, n = _vp(None), _sz(0)
+        rtn = self.lib.orc_speck2d_encode(c.ctypes.data, sign_words.ctypes.data, dx, dy, budget_bits,
+                                          C.byref(out), C.byref(n))
+        if rtn:
+            raise RuntimeError(f"orc_speck2d_encode returned {rtn}")
+        s = C.string_at(out.value, n.value)
+        self._libc.free(out)
+        return s
+
+    def speck2d_decode(self, stream, shape_yx):
+        dy, dx = shape_yx
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        coef = np.zeros(shape_yx, dtype=np.uint64)
+        sign = np.zeros((coef.size + 63) // 64, dtype=np.uint64)
+        rtn = self.lib.orc_speck2d_decode(buf.ctypes.data, buf.size, dx, dy, coef.ctypes.data, sign.ctypes.data)
+        if rtn:
+            raise RuntimeError(f"orc_speck2d_decode returned {rtn}")
         return coef, sign
 
     def decomp_3d_multi_res(self, stream, nthreads=1):
@@ -435,6 +462,10 @@ class Ref(_CApiMixin, _OutlierMixin):
         P.refp_speck3d_encode.restype = C.c_int
         P.refp_speck3d_decode.argtypes = [_vp, _sz, _sz, _sz, _sz, _vp, _vp]
         P.refp_speck3d_decode.restype = C.c_int
+        P.refp_speck2d_encode.argtypes = [_vp, _vp, _sz, _sz, _sz, C.c_int, C.POINTER(_vp), C.POINTER(_sz)]
+        P.refp_speck2d_encode.restype = C.c_int
+        P.refp_speck2d_decode.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp]
+        P.refp_speck2d_decode.restype = C.c_int
         P.refp_speck1d_encode.argtypes = [_vp, _vp, _sz, C.c_int, C.POINTER(_vp), C.POINTER(_sz)]
         P.refp_speck1d_encode.restype = C.c_int
         P.refp_speck1d_decode.argtypes = [_vp, _sz, _sz, _vp, _vp]
@@ -489,6 +520,28 @@ class Ref(_CApiMixin, _OutlierMixin):
         sign = np.zeros((coef.size + 63) // 64, dtype=np.uint64)
         self.probe.refp_speck3d_decode(buf.ctypes.data, buf.size, dx, dy, dz, coef.ctypes.data,
                                        sign.ctypes.data)
+        return coef, sign
+
+    def speck2d_encode(self, coef_yx, sign_words, budget_bits=0, width=8):
+        c = np.ascontiguousarray(coef_yx, dtype=np.uint64)
+        dy, dx = c.shape
+        out, n = _vp(None), _sz(0)
+        rtn = self.probe.refp_speck2d_encode(c.ctypes.data, sign_words.ctypes.data, dx, dy, budget_bits, width,
+                                             C.byref(out), C.byref(n))
+        if rtn:
+            raise RuntimeError(f"refp_speck2d_encode returned {rtn}")
+        s = C.string_at(out.value, n.value)
+        self._libc.free(out)
+        return s
+
+    def speck2d_decode(self, stream, shape_yx):
+        dy, dx = shape_yx
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        coef = np.zeros(shape_yx, dtype=np.uint64)
+        sign = np.zeros((coef.size + 63) // 64, dtype=np.uint64)
+        rtn = self.probe.refp_speck2d_decode(buf.ctypes.data, buf.size, dx, dy, coef.ctypes.data, sign.ctypes.data)
+        if rtn:
+            raise RuntimeError(f"refp_speck2d_decode returned {rtn}")
         return coef, sign
 
     def decomp_3d_multi_res(self, stream, nthreads=1):

@@ -14,6 +14,8 @@
 #include "SPECK1D_INT_DEC.h"
 #include "SPECK1D_INT_ENC.h"
 #include "SPECK2D_FLT.h"
+#include "SPECK2D_INT_DEC.h"
+#include "SPECK2D_INT_ENC.h"
 #include "SPECK3D_FLT.h"
 #include "SPERR3D_OMP_D.h"
 #include "SPECK3D_INT_DEC.h"
@@ -126,6 +128,41 @@ int refp_speck3d_decode(const uint8_t* stream, size_t len, size_t dx, size_t dy,
   if (planes <= 32)
     return decode_as<uint32_t>(stream, len, dims, coeffs, signs);
   return decode_as<uint64_t>(stream, len, dims, coeffs, signs);
+}
+
+// the coder of a slice (SPECK2D_INT_ENC / _DEC over dims {dx, dy, 1}), the widths as in the 3D probe
+int refp_speck2d_encode(const uint64_t* coeffs, const uint64_t* signs, size_t dx, size_t dy, size_t budget,
+                        int width, uint8_t** out, size_t* out_len)
+{
+  std::vector<uint8_t> s;
+  const sperr::dims_type dims = {dx, dy, 1};
+  int rtn = 1;
+  switch (width) {
+    case 1: rtn = encode_as<uint8_t, sperr::SPECK2D_INT_ENC<uint8_t>>(coeffs, signs, dims, budget, s); break;
+    case 2: rtn = encode_as<uint16_t, sperr::SPECK2D_INT_ENC<uint16_t>>(coeffs, signs, dims, budget, s); break;
+    case 4: rtn = encode_as<uint32_t, sperr::SPECK2D_INT_ENC<uint32_t>>(coeffs, signs, dims, budget, s); break;
+    case 8: rtn = encode_as<uint64_t, sperr::SPECK2D_INT_ENC<uint64_t>>(coeffs, signs, dims, budget, s); break;
+  }
+  if (rtn)
+    return rtn;
+  *out = static_cast<uint8_t*>(std::malloc(s.size()));
+  std::memcpy(*out, s.data(), s.size());
+  *out_len = s.size();
+  return 0;
+}
+
+int refp_speck2d_decode(const uint8_t* stream, size_t len, size_t dx, size_t dy, uint64_t* coeffs,
+                        uint64_t* signs)
+{
+  const sperr::dims_type dims = {dx, dy, 1};
+  const auto planes = sperr::speck_int_get_num_bitplanes(stream);
+  if (planes <= 8)
+    return decode_as<uint8_t, sperr::SPECK2D_INT_DEC<uint8_t>>(stream, len, dims, coeffs, signs);
+  if (planes <= 16)
+    return decode_as<uint16_t, sperr::SPECK2D_INT_DEC<uint16_t>>(stream, len, dims, coeffs, signs);
+  if (planes <= 32)
+    return decode_as<uint32_t, sperr::SPECK2D_INT_DEC<uint32_t>>(stream, len, dims, coeffs, signs);
+  return decode_as<uint64_t, sperr::SPECK2D_INT_DEC<uint64_t>>(stream, len, dims, coeffs, signs);
 }
 
 // the coder of the outlier list (SPECK1D_INT_ENC / _DEC over a length-n array, no bit budget)

@@ -595,13 +595,16 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_dwt3d_dev returned {rtn}")
         return vals
 
-    def speck3d_encode(self, coef, sign, budget_bits=0):
+    def speck3d_encode(self, coef, sign, budget_bits=0, _slice=False):
         """coef: cuda int32 (uint32 bits) or int64 (uint64 bits) tensor (z, y, x); sign: cuda int64
         tensor of (n+63)//64 words. Returns the stream as bytes."""
         torch = self.torch
         assert coef.is_cuda and coef.is_contiguous() and sign.is_cuda
         width = coef.element_size()
-        dz, dy, dx = coef.shape
+        if _slice:   # dimz = 0 asks the entry for the plan of a dx x dy slice
+            dz, (dy, dx) = 0, coef.shape
+        else:
+            dz, dy, dx = coef.shape
         n = coef.numel()
         cap = 9 + (budget_bits + 7) // 8 + 64 if budget_bits else 9 + 70 * n // 8 + 4096
         out = torch.empty(cap, dtype=torch.uint8, device=coef.device)
@@ -613,11 +616,26 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_speck3d_encode_dev returned {rtn}")
         return bytes(out[:ln.value].cpu().numpy())
 
-    def speck3d_decode(self, stream, shape_zyx):
+    def speck2d_encode(self, coef, sign, budget_bits=0):
+        """The 2D coder (the quadtree forest and the type-I set of a slice) on its own.  coef: cuda int32 (uint32
+        bits) or int64 (uint64 bits) tensor (y, x); sign as in speck3d_encode.  Returns the stream as bytes."""
+        assert coef.dim() == 2
+        return self.speck3d_encode(coef, sign, budget_bits, _slice=True)
+
+    def speck2d_decode(self, stream, shape_yx):
+        """Returns (coef uint64 numpy (y, x), sign uint64 numpy words) of a 2D coder's stream."""
+        dy, dx = shape_yx
+        c, s = self.speck3d_decode(stream, (1, dy, dx), _slice=True)
+        return c.reshape(dy, dx), s
+
+    def speck3d_decode(self, stream, shape_zyx, _slice=False):
         """Returns (coef uint64 numpy (z,y,x), sign uint64 numpy words)."""
         torch = self.torch
         dz, dy, dx = shape_zyx
         n = dz * dy * dx
+        if _slice:   # dimz = 0 asks the entry for the plan of a dx x dy slice
+            assert dz == 1
+            dz = 0
         s = torch.from_numpy(np.frombuffer(stream, dtype=np.uint8).copy()).cuda()
         coef = torch.zeros(n, dtype=torch.int64, device="cuda")
         sign = torch.zeros((n + 63) // 64, dtype=torch.int64, device="cuda")

@@ -2073,6 +2073,8 @@ static int xy_rows(uint32_t cx, uint32_t cy)
   if (rows > maxRows)
     rows = maxRows;
   int R = (rows - 2 * kXYHalo) & ~1;
+  if (R <= 0)   // (rows of 1088 samples and more leave no tile: a negative R must not pass for a large one below)
+    return 0;
   if ((uint32_t)R > cy)
     R = (int)((cy + 1) & ~1u);
   return R >= 8 ? R : 0;

@@ -32,6 +32,7 @@ from sperr_amd.farm import build_container, split_container
 
 SHAPE = (128, 128, 128)
 MX_SHAPE = (100, 128, 128)   # not dyadic along z: the lists mix set shapes, k_lis_mx decodes them
+MX_CUBE = (100, 100, 100)    # no axis dyadic: the sets change shape along all three
 TIERS = (26, 14, 3)
 WIDE_TIERS = (52, 40, 33)
 _U = np.uint64
@@ -113,7 +114,9 @@ _EXTREMES = ("all_one", "dense_top32", "last_only", "first_only")
 CASES = ("last_only", "first_only", "all_one", "checker8", "stagger8_one", "tiers8_all", "tiers4_one", "checker2",
          "tiers2_all", "front4", "dense_top32", "wide_tiers8_all", "wide_stagger4_one")   # the cheapest first
 MX_CASES = ("checker8", "tiers4_one", "stagger8_one")   # at MX_SHAPE
-ALL_CASES = [(name, SHAPE) for name in CASES] + [(name, MX_SHAPE) for name in MX_CASES]
+MX_CUBE_CASES = ("checker8", "tiers4_one")   # at MX_CUBE
+ALL_CASES = ([(name, SHAPE) for name in CASES] + [(name, MX_SHAPE) for name in MX_CASES]
+             + [(name, MX_CUBE) for name in MX_CUBE_CASES])
 CASE_IDS = ["%s-%dx%dx%d" % ((name,) + shape) for name, shape in ALL_CASES]
 
 

@@ -105,11 +105,15 @@ def test_stage_parity(eng, oracle, name):
     assert not any("k_lis_mx" in n for n in launched)
 
 
-@pytest.mark.parametrize("name", cc.MX_CASES)
-def test_stage_parity_where_the_lists_mix_set_shapes(eng, oracle, name):
+MX_PARAMS = ([pytest.param(name, cc.MX_SHAPE, id=name) for name in cc.MX_CASES]
+             + [pytest.param(name, cc.MX_CUBE, id="%s-%dx%dx%d" % ((name,) + cc.MX_CUBE)) for name in cc.MX_CUBE_CASES])
+
+
+@pytest.mark.parametrize("name,shape", MX_PARAMS)
+def test_stage_parity_where_the_lists_mix_set_shapes(eng, oracle, name, shape):
     """The same at 100 x 128 x 128: the boxes are no longer the coder's sets along z, the lists mix set shapes, and the
-    launch profile says k_lis_mx decoded them."""
-    launched = stage_parity(eng, oracle, name, cc.MX_SHAPE)
+    launch profile says k_lis_mx decoded them.  At 100 x 100 x 100 no axis is dyadic."""
+    launched = stage_parity(eng, oracle, name, shape)
     assert any("k_lis_mx" in n for n in launched), sorted(launched)
     assert not any("k_lis_l0" in n or "k_lis_hi" in n for n in launched)
 

@@ -345,6 +345,35 @@ def test_tree_aligned_patterns_bit_exact(oracle, ref, name, shape):
             assert np.array_equal(co, coef) and np.array_equal(cc.sign_bits(sgo, idx), cc.sign_bits(sign, idx))
 
 
+def _slice_cases():
+    import slice_cases as sc
+    return pytest.mark.parametrize("name,shape", sc.ALL_CASES, ids=sc.CASE_IDS)
+
+
+@_slice_cases()
+def test_slice_patterns_bit_exact(oracle, ref, name, shape):
+    """The 2D coder on the case table of tests/slice_cases.py (patterns aligned to the quadtree forest, and patterns
+    that choose what the type-I set does on every plane): the oracle's stream, and its decode of the whole stream and
+    of the stream cut to 1/2 and to 1/7 of its payload, against the reference's SPECK2D_INT_ENC / _DEC."""
+    import slice_cases as sc
+    coef, sign, _ = sc.case(name, shape)
+    so = oracle.speck2d_encode(coef, sign, 0)
+    assert same(so, ref.get(lambda r: r.speck2d_encode(coef, sign, 0, width=8)))
+    for cut in sc.stream_cuts(so):
+        co, sgo = oracle.speck2d_decode(so[:cut], shape)
+        idx = np.nonzero(co.reshape(-1) != 0)[0]
+
+        def ref_decode(r):   # the reference's coefficients and the signs of the nonzero ones
+            c, s = r.speck2d_decode(so[:cut], shape)
+            return c, sc.sign_bits(s, idx)
+
+        cr, br = ref.get(ref_decode)
+        assert same(co, cr), cut
+        assert same(sc.sign_bits(sgo, idx), br), cut
+        if cut == len(so):   # the whole stream gives the coefficients back
+            assert np.array_equal(co, coef) and np.array_equal(sc.sign_bits(sgo, idx), sc.sign_bits(sign, idx))
+
+
 # ---- the outlier coder as a primitive (tests/outlier_cases.py) -----------------------------------------------------
 
 

@@ -273,6 +273,46 @@ def test_model_2d_decoder_on_the_mixed_machinery(oracle, model, shape, window, h
                 assert np.array_equal(s0, s1)
 
 
+def _slice_model_cases():
+    import slice_cases as sc
+    return pytest.mark.parametrize("name,shape", sc.MODEL_CASES, ids=sc.MODEL_IDS)
+
+
+@_slice_model_cases()
+def test_model_2d_decoder_on_slice_patterns(oracle, model, name, shape):
+    """model_speck2d_decode_mixed, the CPU statement of k_lis_mx's formulation, on the type-I cases and the 2^2 box
+    cases of tests/slice_cases.py at 64 x 64 and 37 x 50: the stream whole, cut to 1/2 and 1/7 of its payload, cut
+    one byte into the case's long plane and, where the set releases a level there, cut in the middle of that plane's
+    type-I phase -- with the window / hmax pairs of the test above, against the oracle's decoder."""
+    import slice_cases as sc
+    lib = model
+    lib.model_speck2d_decode_mixed.argtypes = [_vp, _sz, _vp, _vp, _vp, C.c_int, C.c_int]
+    lib.model_speck2d_decode_mixed.restype = C.c_int
+    dy, dx = shape
+    coef, sign, _ = sc.case(name, shape)
+
+    def enc(c, s):
+        return oracle.speck2d_encode(c, s, 0)
+
+    stream = enc(coef, sign)
+    p = sc.long_plane(name, shape)
+    cuts = sc.stream_cuts(stream) + (sc.cut_into_plane(enc, coef, sign, p),)
+    if name in sc.PHASE_CASES:
+        cuts += (sc.cut_into_i_phase(enc, coef, sign, p)[0],)
+    for cut in cuts:
+        s = stream[:cut]
+        c0, s0 = oracle.speck2d_decode(s, shape)
+        buf = np.frombuffer(s, dtype=np.uint8)
+        for window, hmax in [(200, 1), (4096, 2), (64, 0)]:
+            c1 = np.zeros(shape, dtype=np.uint64)
+            s1 = np.zeros((c1.size + 63) // 64, dtype=np.uint64)
+            assert lib.model_speck2d_decode_mixed(buf.ctypes.data, buf.size, (_sz * 3)(dx, dy, 1),
+                                                  c1.ctypes.data, s1.ctypes.data, window, hmax) == 0
+            assert np.array_equal(c0, c1), (cut, window, hmax)
+            assert np.array_equal(s0, s1), (cut, window, hmax)
+    assert np.array_equal(oracle.speck2d_decode(stream, shape)[0], coef)
+
+
 @pytest.mark.parametrize("shape", [(16, 16), (17, 23), (64, 64), (99, 100), (40, 9), (128, 96), (9, 9), (200, 33), (8, 8), (5, 300)])
 @pytest.mark.parametrize("budget", [0, 1500, 40000])
 def test_model_2d_encoder_on_the_shared_forest(oracle, model, shape, budget):
