@@ -356,6 +356,56 @@ int sperrhip_quality_view_dev(const void* d_orig, const sperrhip_view* view_orig
                               const sperrhip_view* view_recon, int is_float, size_t dimx, size_t dimy, size_t dimz,
                               double* out, void* hip_stream);
 
+/* ---- interleaved fields of a device array ---------------------------------------------------------
+ * An array that keeps several variables per sample, the variables innermost -- a solver's (z, y, x, nvar), a detector's
+ * (y, x, channel), a channels-last tensor -- compressed to and decoded from one container per field without a packed
+ * copy of the caller's making.  The layout is three numbers in elements: stride_x from one sample to the next along x
+ * (the record's width), pitch_y from row to row, pitch_z from slice to slice.  A call names nfields consecutive fields;
+ * its data pointer is the device address of the FIRST SELECTED field at (0, 0, 0), and field f of sample (x, y, z)
+ * lies z*pitch_z + y*pitch_y + x*stride_x + f elements from it.  A layout is valid when the dims are not empty,
+ * 1 <= nfields <= stride_x, pitch_y >= dimx*stride_x, pitch_z >= pitch_y*dimy (pitch_z need not be a multiple of
+ * pitch_y) and nothing overflows size_t; it reaches (dimz-1)*pitch_z + (dimy-1)*pitch_y + (dimx-1)*stride_x + nfields
+ * elements, its extent.  A NULL layout means the dense interleave {nfields, dimx*nfields, dimx*dimy*nfields}.  The
+ * first element needs the alignment of its type only.  As in the batch calls nfields * dimz <= 2^32 - 1; dimx, dimy
+ * and stride_x stay below 2^31.
+ * The calls stage: one kernel gathers the selected fields into stacked volumes in a buffer the library owns (it grows
+ * on demand and goes back with sperrhip_release), or scatters them from it, and the batch code runs on that buffer.
+ * Every call returns -1 before anything is launched or written for a layout that is not valid or a NULL pointer. */
+typedef struct sperrhip_fields {
+  size_t stride_x, pitch_y, pitch_z;
+} sperrhip_fields;
+/* nfields containers back to back in d_dst, container f at [offsets[f], offsets[f + 1]) (offsets: nfields + 1
+ * entries): byte for byte what sperrhip_compress_dev makes of the packed copy of field f.  All modes, both
+ * precisions; dst_cap at least sperrhip_max_compressed_size_batch(nfields, ...); the return codes of
+ * sperrhip_compress_batch_dev. */
+int sperrhip_compress_fields_dev(const void* d_src, const sperrhip_fields* layout, size_t nfields, int is_float,
+                                 size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z,
+                                 int mode, double quality, void* d_dst, size_t dst_cap, size_t* offsets,
+                                 void* hip_stream);
+/* nfields containers (as sperrhip_decompress_batch_dev takes them: any mode, rate, truncation, chunking and coded
+ * precision each) whose dims all equal (dimx, dimy, dimz), decoded into the nfields fields of d_dst that `layout`
+ * names: field f holds bit for bit what sperrhip_decompress_dev makes of container f.  Only selected fields of samples
+ * inside the dims are written; other fields, paddings and halos keep their bytes.  dst_cap_bytes counts from d_dst and
+ * must hold the extent.  The decode goes to the library's buffer first, so after ANY refusal or decoder error -- a
+ * damaged stream found mid-decode included -- d_dst is as it was.  0 ok, -1 error. */
+int sperrhip_decompress_fields_dev(const void* d_src, const size_t* offsets, size_t nfields, int output_float,
+                                   size_t dimx, size_t dimy, size_t dimz, void* d_dst, const sperrhip_fields* layout,
+                                   size_t dst_cap_bytes, void* hip_stream);
+/* out[8 * nfields]: field f's eight figures are bit for bit sperrhip_quality_dev of the packed copies of field f of
+ * the two arrays, which may have different layouts. */
+int sperrhip_quality_fields_dev(const void* d_orig, const sperrhip_fields* layout_orig, const void* d_recon,
+                                const sperrhip_fields* layout_recon, size_t nfields, int is_float, size_t dimx,
+                                size_t dimy, size_t dimz, double* out, void* hip_stream);
+/* Stage access: the two kernels alone, between an interleaved array and the caller's own stacked buffer (nfields
+ * dense volumes back to back, what the batch calls take and return).  The gather's d_dst holds nfields*dimx*dimy*dimz
+ * elements within dst_cap_bytes; the scatter's d_dst holds the layout's extent within dst_cap_bytes and is written
+ * only at selected fields.  Both wait for the stream.  0 ok, -1 error. */
+int sperrhip_fields_gather_dev(const void* d_src, const sperrhip_fields* layout, size_t nfields, int is_float,
+                               size_t dimx, size_t dimy, size_t dimz, void* d_dst, size_t dst_cap_bytes,
+                               void* hip_stream);
+int sperrhip_fields_scatter_dev(const void* d_src, size_t nfields, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                                void* d_dst, const sperrhip_fields* layout, size_t dst_cap_bytes, void* hip_stream);
+
 /* ---- a batch of same-shape volumes, one container each ----------------------------------------- */
 /* N volumes of the same dims in one call: the chunks of every volume are coded together (a batch is
  * more chunks for the same shape groups), and each volume gets a container of its own.  Container v

@@ -568,6 +568,65 @@ inline auto decompress_view_dev(const void* d_stream, size_t stream_len, T* d_ou
   return rtn == 0 ? RTNType::Good : RTNType::Error;
 }
 
+// (this library's addition) Interleaved fields of a device array (sperrhip_fields: a solver's (z, y, x, nvar), a
+// channels-last tensor): `nfields` consecutive fields from the data pointer, the first selected field at (0, 0, 0);
+// samples stride_x, rows pitch_y and slices pitch_z elements apart.  A null layout means the dense interleave of
+// nfields.  One container per field, each what the device-pointer calls make of the packed copy of that field.
+// RTNType::Error (nothing written) for a layout that is not valid, a null pointer, or an output that does not hold it.
+using fields_type = sperrhip_fields;
+
+// the dense interleave of nfields fields of a volume
+inline auto dense_fields(size_t nfields, dims_type dims) -> fields_type
+{
+  return fields_type{nfields, dims[0] * nfields, dims[0] * dims[1] * nfields};
+}
+
+// nfields containers back to back into `cap` bytes of device memory at d_out (sperrhip_compress_fields_dev);
+// `offsets` receives nfields + 1 entries, container f at [offsets[f], offsets[f + 1])
+template <typename T>
+inline auto compress_fields_dev(const T* d_src, const fields_type* layout, size_t nfields, dims_type dims,
+                                dims_type chunks, CompMode mode, double quality, void* d_out, size_t cap,
+                                std::vector<size_t>& offsets, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const int m = mode == CompMode::Rate ? 1 : mode == CompMode::PSNR ? 2 : mode == CompMode::PWE ? 3 : 0;
+  if (m == 0)
+    return RTNType::CompModeUnknown;
+  offsets.assign(nfields + 1, 0);
+  const int rtn = sperrhip_compress_fields_dev(d_src, layout, nfields, sizeof(T) == 4, dims[0], dims[1], dims[2],
+                                               chunks[0], chunks[1], chunks[2], m, quality, d_out, cap, offsets.data(),
+                                               hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
+// The containers at [offsets[f], offsets[f + 1]) of d_streams, each a volume of `dims`, into the fields of d_out that
+// `layout` names, within `cap_bytes` from d_out (sperrhip_decompress_fields_dev).  Nothing but those fields is written.
+template <typename T>
+inline auto decompress_fields_dev(const void* d_streams, const std::vector<size_t>& offsets, dims_type dims, T* d_out,
+                                  const fields_type* layout, size_t cap_bytes, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  if (offsets.size() < 2)
+    return RTNType::Error;
+  const int rtn = sperrhip_decompress_fields_dev(d_streams, offsets.data(), offsets.size() - 1, sizeof(T) == 4, dims[0],
+                                                 dims[1], dims[2], d_out, layout, cap_bytes, hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
+// quality_dev of every field of two interleaved arrays; `out` receives eight figures per field
+// (sperrhip_quality_fields_dev)
+template <typename T>
+inline auto quality_fields_dev(const T* d_orig, const fields_type* layout_orig, const T* d_recon,
+                               const fields_type* layout_recon, size_t nfields, dims_type dims,
+                               std::vector<std::array<double, 8>>& out, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  out.assign(nfields, std::array<double, 8>{});
+  const int rtn = sperrhip_quality_fields_dev(d_orig, layout_orig, d_recon, layout_recon, nfields, sizeof(T) == 4,
+                                              dims[0], dims[1], dims[2], nfields ? out[0].data() : nullptr, hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
 }  // namespace sperr
 
 #endif

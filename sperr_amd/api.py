@@ -42,6 +42,8 @@ EXPORTS = [
     "sperrhip_trunc_dev", "sperrhip_trunc_batch_dev",
     "sperrhip_quality_dev", "sperrhip_quality_batch_dev",
     "sperrhip_compress_view_dev", "sperrhip_decompress_view_dev", "sperrhip_quality_view_dev",
+    "sperrhip_compress_fields_dev", "sperrhip_decompress_fields_dev", "sperrhip_quality_fields_dev",
+    "sperrhip_fields_gather_dev", "sperrhip_fields_scatter_dev",
 ]
 
 
@@ -52,6 +54,11 @@ class SperrHipError(RuntimeError):
 class View(C.Structure):
     """sperrhip_view: the pitches of a strided view in elements (include/sperr_hip.h)"""
     _fields_ = [("pitch_y", _sz), ("pitch_z", _sz)]
+
+
+class Fields(C.Structure):
+    """sperrhip_fields: the layout of an interleaved array in elements (include/sperr_hip.h)"""
+    _fields_ = [("stride_x", _sz), ("pitch_y", _sz), ("pitch_z", _sz)]
 
 
 class Quality:
@@ -194,6 +201,19 @@ def load_library():
     lib.sperrhip_quality_view_dev.restype = C.c_int
     lib.sperrhip_quality_view_dev.argtypes = [_vp, C.POINTER(View), _vp, C.POINTER(View), C.c_int, _sz, _sz, _sz,
                                               C.POINTER(C.c_double), _vp]
+    lib.sperrhip_compress_fields_dev.restype = C.c_int
+    lib.sperrhip_compress_fields_dev.argtypes = [_vp, C.POINTER(Fields), _sz, C.c_int] + [_sz] * 6 + \
+        [C.c_int, C.c_double, _vp, _sz, C.POINTER(_sz), _vp]
+    lib.sperrhip_decompress_fields_dev.restype = C.c_int
+    lib.sperrhip_decompress_fields_dev.argtypes = [_vp, C.POINTER(_sz), _sz, C.c_int, _sz, _sz, _sz, _vp,
+                                                   C.POINTER(Fields), _sz, _vp]
+    lib.sperrhip_quality_fields_dev.restype = C.c_int
+    lib.sperrhip_quality_fields_dev.argtypes = [_vp, C.POINTER(Fields), _vp, C.POINTER(Fields), _sz, C.c_int, _sz, _sz,
+                                                _sz, C.POINTER(C.c_double), _vp]
+    lib.sperrhip_fields_gather_dev.restype = C.c_int
+    lib.sperrhip_fields_gather_dev.argtypes = [_vp, C.POINTER(Fields), _sz, C.c_int, _sz, _sz, _sz, _vp, _sz, _vp]
+    lib.sperrhip_fields_scatter_dev.restype = C.c_int
+    lib.sperrhip_fields_scatter_dev.argtypes = [_vp, _sz, C.c_int, _sz, _sz, _sz, _vp, C.POINTER(Fields), _sz, _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -583,6 +603,140 @@ class SperrHip:
         if rtn != 0:
             raise SperrHipError(f"sperrhip_quality_batch_dev returned {rtn}")
         return [Quality(out[8 * v:8 * v + 8], n) for v in range(nvol)]
+
+    # ---- interleaved fields ------------------------------------------------------------------
+    @staticmethod
+    def fields_of(t, field_dim=-1):
+        """(Fields, nfields, (z, y, x)) of a 4-D cuda tensor whose dimension `field_dim` is the field axis: that axis
+        has stride 1, the other three are read as (z, y, x) and their strides are the layout's pitch_z, pitch_y and
+        stride_x, which must obey the rule of include/sperr_hip.h (a record at least nfields wide, rows and slices
+        that do not overlap).  A contiguous (z, y, x, c) tensor, its slices t[..., a:b], its halo interiors, and with
+        field_dim=0 the (c, z, y, x) view of a channels-last tensor all are.  data_ptr() is the first selected field.
+        Raises SperrHipError for anything else: nothing is ever copied silently."""
+        if t.dim() != 4:
+            raise SperrHipError(f"interleaved fields are a 4-D tensor, not {t.dim()}-D")
+        fd = field_dim % 4
+        nf, sf = int(t.shape[fd]), int(t.stride(fd))
+        (dz, dy, dx) = (int(t.shape[a]) for a in range(4) if a != fd)
+        (sz, sy, sx) = (int(t.stride(a)) for a in range(4) if a != fd)
+        if min(nf, dz, dy, dx) < 1:
+            raise SperrHipError("interleaved fields have no empty dimension")
+        if nf > 1 and sf != 1:
+            raise SperrHipError(f"the field axis has stride 1, dimension {field_dim} of this tensor has {sf}")
+        # (the stride of a dimension of size 1 says nothing: take the tightest that fits)
+        if dx == 1:
+            sx = nf
+        if dy == 1:
+            sy = sz if dz > 1 and sz >= dx * sx else dx * sx
+        if dz == 1:
+            sz = sy * dy
+        if sx < nf or sy < dx * sx or sz < sy * dy:
+            raise SperrHipError(f"strides {tuple(t.stride())} of shape {tuple(t.shape)} are no interleaved layout: the "
+                                "record must be at least the fields wide, the row pitch at least x records and the "
+                                "slice pitch at least y rows")
+        return Fields(sx, sy, sz), nf, (dz, dy, dx)
+
+    def _fields_args(self, t, field_dim):
+        torch = self.torch
+        assert t.is_cuda and t.dtype in (torch.float32, torch.float64)
+        return self.fields_of(t, field_dim)
+
+    def compress_fields(self, t, chunks_xyz, quality, mode=1, field_dim=-1, out=None):
+        """The fields of an interleaved cuda tensor (fields_of), one container each: a list of cuda uint8 views into
+        one buffer (`out` when it is large enough) in order; container f is what compress() makes of the packed copy
+        of field f.  The tensor is read where it lies."""
+        torch = self.torch
+        lay, nf, (dz, dy, dx) = self._fields_args(t, field_dim)
+        cap = self.max_compressed_size_batch(nf, (dz, dy, dx), chunks_xyz, quality, mode)
+        if cap == 0:
+            raise SperrHipError("sperrhip_max_compressed_size_batch overflows")
+        if out is None or out.numel() < cap:
+            out = torch.empty(cap, dtype=torch.uint8, device=t.device)
+        offs = (_sz * (nf + 1))()
+        rtn = self.lib.sperrhip_compress_fields_dev(t.data_ptr(), C.byref(lay), nf, int(t.dtype == torch.float32), dx,
+                                                    dy, dz, *chunks_xyz, mode, float(quality), out.data_ptr(),
+                                                    out.numel(), offs, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_fields_dev returned {rtn}")
+        return [out[offs[f]:offs[f + 1]] for f in range(nf)]
+
+    def decompress_fields(self, containers, out=None, field_dim=-1, output_float=True):
+        """containers: a list of cuda uint8 tensors, container f the volume of field f, all of the same dims (they are
+        concatenated first unless they already lie back to back in one buffer).  They are decoded into the fields of
+        `out`, an interleaved cuda tensor (fields_of) with as many fields as containers -- a slice t[..., a:b] of a
+        wider one, a halo interior --, and nothing else of it is written; out=None makes a contiguous (z, y, x, c)
+        tensor.  Returns `out`."""
+        torch = self.torch
+        assert len(containers) > 0
+        for c in containers:
+            assert c.is_cuda and c.dtype == torch.uint8 and c.dim() == 1 and c.is_contiguous()
+        nf = len(containers)
+        packed = all(b.data_ptr() == a.data_ptr() + a.numel() and
+                     b.untyped_storage().data_ptr() == a.untyped_storage().data_ptr()
+                     for a, b in zip(containers, containers[1:]))
+        src = containers[0] if packed else torch.cat(list(containers))
+        offs = (_sz * (nf + 1))()
+        for f, c in enumerate(containers):
+            offs[f + 1] = offs[f] + c.numel()
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            shape_zyx, _, _ = self.parse_header(src[:offs[1]])
+            out = torch.empty(tuple(shape_zyx) + (nf,), dtype=dt, device=src.device)
+            field_dim = -1
+        assert out.dtype == dt and out.is_cuda
+        lay, nfo, (dz, dy, dx) = self.fields_of(out, field_dim)
+        if nfo != nf:
+            raise SperrHipError(f"{nf} containers for {nfo} fields")
+        rtn = self.lib.sperrhip_decompress_fields_dev(src.data_ptr(), offs, nf, int(output_float), dx, dy, dz,
+                                                      out.data_ptr(), C.byref(lay), self._room_bytes(out),
+                                                      self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_fields_dev returned {rtn}")
+        return out
+
+    def quality_fields(self, orig, recon, field_dim=-1):
+        """quality() of every field of two interleaved cuda tensors (fields_of) of one shape and dtype, whose layouts
+        may differ: a list of Quality records, each the figures of the two packed copies of that field."""
+        lo, nf, zyx = self._fields_args(orig, field_dim)
+        lr, nfr, zyxr = self._fields_args(recon, field_dim)
+        if orig.dtype != recon.dtype or nf != nfr or zyx != zyxr:
+            raise SperrHipError(f"the two tensors differ in dtype or shape: {tuple(orig.shape)} and {tuple(recon.shape)}")
+        dz, dy, dx = zyx
+        out = (C.c_double * (8 * nf))()
+        rtn = self.lib.sperrhip_quality_fields_dev(orig.data_ptr(), C.byref(lo), recon.data_ptr(), C.byref(lr), nf,
+                                                   int(orig.dtype == self.torch.float32), dx, dy, dz, out,
+                                                   self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_quality_fields_dev returned {rtn}")
+        return [Quality(out[8 * f:8 * f + 8], dz * dy * dx) for f in range(nf)]
+
+    def fields_gather(self, t, field_dim=-1, out=None):
+        """Stage access: the fields of an interleaved cuda tensor (fields_of) as stacked volumes (c, z, y, x), what
+        compress_batch takes -- `out` when given (contiguous)."""
+        torch = self.torch
+        lay, nf, (dz, dy, dx) = self._fields_args(t, field_dim)
+        if out is None:
+            out = torch.empty((nf, dz, dy, dx), dtype=t.dtype, device=t.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == t.dtype
+        rtn = self.lib.sperrhip_fields_gather_dev(t.data_ptr(), C.byref(lay), nf, int(t.dtype == torch.float32), dx, dy,
+                                                  dz, out.data_ptr(), out.numel() * out.element_size(), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_fields_gather_dev returned {rtn}")
+        return out
+
+    def fields_scatter(self, stacked, out, field_dim=-1):
+        """Stage access: stacked volumes (c, z, y, x), contiguous, into the fields of the interleaved cuda tensor `out`
+        (fields_of); nothing else of `out` is written."""
+        torch = self.torch
+        assert stacked.is_cuda and stacked.is_contiguous() and stacked.dim() == 4 and stacked.dtype == out.dtype
+        lay, nf, (dz, dy, dx) = self._fields_args(out, field_dim)
+        if tuple(stacked.shape) != (nf, dz, dy, dx):
+            raise SperrHipError(f"stacked volumes {tuple(stacked.shape)} for fields {(nf, dz, dy, dx)}")
+        rtn = self.lib.sperrhip_fields_scatter_dev(stacked.data_ptr(), nf, int(out.dtype == torch.float32), dx, dy, dz,
+                                                   out.data_ptr(), C.byref(lay), self._room_bytes(out), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_fields_scatter_dev returned {rtn}")
+        return out
 
     # ---- stage access ----------------------------------------------------------------------
     def dwt3d(self, vals, inverse=False):

@@ -35,6 +35,7 @@
 #include "outlier.h"
 #include "quality.h"
 #include "view.h"
+#include "fields.h"
 #include "xform.h"
 
 // The decoder runs the shape groups of a volume side by side on up to eight streams; the ROCm
@@ -789,6 +790,8 @@ struct Engine {
   size_t pweHostBytes = 0;                 //   would hold the host until the stream gets there: compress_impl)
   hipEvent_t liveEv[kSubStreams][kLiveSlots] = {};
   DevBuf wideScratch;                       // 64-bit retry of a batch whose coder arrays lay over the chunk buffer
+  DevBuf fieldsStage, fieldsStage2;         // interleaved fields (fields.h): the stacked volumes the batch code works on,
+                                            //   and the quality call's other side
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
 
@@ -910,7 +913,8 @@ struct Engine {
       kv.second->tables.drop();
     plans.clear();
     planOrder.clear();
-    for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch})
+    for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
+                      &fieldsStage2})
       b->drop();
     for (auto& b : outlDec)
       b.drop();
@@ -922,11 +926,13 @@ struct Engine {
     pweBufs.clear();
   }
   // every device buffer of the engine: the arena, the containers' slots, and what point-wise error mode adds (the
-  // outlier coder's arrays, the boxes of the coarser levels, the outlier streams) -- sperrhip_debug_counter(6)
+  // outlier coder's arrays, the boxes of the coarser levels, the outlier streams) and the staging buffers of the
+  // fields calls -- sperrhip_debug_counter(6)
   size_t device_bytes() const
   {
     size_t n = 0;
-    for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch})
+    for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
+                      &fieldsStage2})
       n += b->n;
     for (const auto& b : outlDec)
       n += b.n;
@@ -5834,6 +5840,165 @@ int sperrhip_quality_view_dev(const void* d_orig, const sperrhip_view* view_orig
       return -1;
     const int rtn = quality_view_run(d_orig, po, d_recon, pr, is_float, dimx, dimy, dimz, L.e->arena.p, out, hip_stream);
     L.e->prof.collect();
+    return rtn;
+  });
+}
+
+// ---- interleaved fields (fields.h) -----------------------------------------------------------------------------
+// The fields calls stage: the selected fields are gathered into stacked volumes in a buffer the engine owns
+// (k_fields_gather), or scattered from it (k_fields_scatter), and the batch code works on that buffer.
+
+// the layout a call means (NULL: the dense interleave), once the stacked side's size is known not to overflow
+static FieldsLayout fields_layout_of(const sperrhip_fields* layout, size_t nfields, size_t dimx, size_t dimy)
+{
+  return layout ? FieldsLayout{layout->stride_x, layout->pitch_y, layout->pitch_z} : fields_dense(nfields, dimx, dimy);
+}
+
+int sperrhip_fields_gather_dev(const void* d_src, const sperrhip_fields* layout, size_t nfields, int is_float,
+                               size_t dimx, size_t dimy, size_t dimz, void* d_dst, size_t dst_cap_bytes,
+                               void* hip_stream)
+{
+  return guarded("sperrhip_fields_gather_dev", [&]() -> int {
+    size_t count = 0;
+    const size_t esz = is_float ? sizeof(float) : sizeof(double);
+    if (!d_src || !d_dst || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > dst_cap_bytes / esz)
+      return -1;
+    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
+    Lease L;
+    if (!L.e)
+      return -1;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (fields_gather_run(d_src, l, nfields, is_float, dimx, dimy, dimz, d_dst, st))
+      return -1;
+    HIP_CHECK(hipStreamSynchronize(st));
+    L.e->prof.collect();
+    return 0;
+  });
+}
+
+int sperrhip_fields_scatter_dev(const void* d_src, size_t nfields, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                                void* d_dst, const sperrhip_fields* layout, size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_fields_scatter_dev", [&]() -> int {
+    size_t count = 0;
+    const size_t esz = is_float ? sizeof(float) : sizeof(double);
+    if (!d_src || !d_dst || !fields_stacked(nfields, dimx, dimy, dimz, &count))
+      return -1;
+    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
+    if (!fields_fits(nfields, dimx, dimy, dimz, l, esz, dst_cap_bytes))
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (fields_scatter_run(d_src, nfields, is_float, dimx, dimy, dimz, d_dst, l, st))
+      return -1;
+    HIP_CHECK(hipStreamSynchronize(st));
+    L.e->prof.collect();
+    return 0;
+  });
+}
+
+int sperrhip_compress_fields_dev(const void* d_src, const sperrhip_fields* layout, size_t nfields, int is_float,
+                                 size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z,
+                                 int mode, double quality, void* d_dst, size_t dst_cap, size_t* offsets,
+                                 void* hip_stream)
+{
+  return guarded("sperrhip_compress_fields_dev", [&]() -> int {
+    if (quality <= 0.0)
+      return 2;
+    if (mode < 1 || mode > 3)
+      return 2;
+    size_t count = 0;
+    if (!d_src || !d_dst || !offsets || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > SIZE_MAX / 8)
+      return -1;
+    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
+    if (!fields_valid(nfields, dimx, dimy, dimz, l))
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return with_elem(is_float, [&](auto t) {
+      using T = decltype(t);
+      if (E.fieldsStage.ensure(count * sizeof(T)) ||
+          fields_gather_run(d_src, l, nfields, is_float, dimx, dimy, dimz, E.fieldsStage.p, st))
+        return -1;
+      return compress_batch_impl(E, static_cast<const T*>(E.fieldsStage.p), nfields, vol, ch, mode, quality,
+                                 static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
+    });
+  });
+}
+
+int sperrhip_decompress_fields_dev(const void* d_src, const size_t* offsets, size_t nfields, int output_float,
+                                   size_t dimx, size_t dimy, size_t dimz, void* d_dst, const sperrhip_fields* layout,
+                                   size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_decompress_fields_dev", [&]() -> int {
+    size_t count = 0;
+    const size_t esz = output_float ? sizeof(float) : sizeof(double);
+    if (!d_src || !offsets || !d_dst || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > SIZE_MAX / 8)
+      return -1;
+    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
+    if (!fields_fits(nfields, dimx, dimy, dimz, l, esz, dst_cap_bytes))
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    ContainerInfo all;
+    std::vector<std::array<size_t, 6>> list;
+    if (read_batch_info(E, src, offsets, nfields, all, list, st))
+      return -1;
+    if (all.vol != Dims{dimx, dimy, dimz * nfields})   // (every container names the call's dims)
+      return -1;
+    // the decode goes to the staging buffer: whatever it runs into, d_dst is as it was
+    if (E.fieldsStage.ensure(count * esz))
+      return -1;
+    DecodeRequest req;
+    req.stacked = &list;
+    const int rtn = decode_to(E, src, output_float, E.fieldsStage.p, count * esz, all, st, req);
+    if (rtn)
+      return rtn;
+    if (fields_scatter_run(E.fieldsStage.p, nfields, output_float, dimx, dimy, dimz, d_dst, l, st))
+      return -1;
+    HIP_CHECK(hipStreamSynchronize(st));
+    E.prof.collect();
+    return 0;
+  });
+}
+
+int sperrhip_quality_fields_dev(const void* d_orig, const sperrhip_fields* layout_orig, const void* d_recon,
+                                const sperrhip_fields* layout_recon, size_t nfields, int is_float, size_t dimx,
+                                size_t dimy, size_t dimz, double* out, void* hip_stream)
+{
+  return guarded("sperrhip_quality_fields_dev", [&]() -> int {
+    size_t count = 0;
+    const size_t esz = is_float ? sizeof(float) : sizeof(double);
+    if (!d_orig || !d_recon || !out || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > SIZE_MAX / 8)
+      return -1;
+    const FieldsLayout lo = fields_layout_of(layout_orig, nfields, dimx, dimy);
+    const FieldsLayout lr = fields_layout_of(layout_recon, nfields, dimx, dimy);
+    if (!fields_valid(nfields, dimx, dimy, dimz, lo) || !fields_valid(nfields, dimx, dimy, dimz, lr))
+      return -1;
+    const size_t n = count / nfields, need = quality_workspace_bytes(nfields, n, is_float);
+    if (need == 0)
+      return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    if (E.arena.ensure(need) || E.fieldsStage.ensure(count * esz) || E.fieldsStage2.ensure(count * esz))
+      return -1;
+    if (fields_gather_run(d_orig, lo, nfields, is_float, dimx, dimy, dimz, E.fieldsStage.p, hip_stream) ||
+        fields_gather_run(d_recon, lr, nfields, is_float, dimx, dimy, dimz, E.fieldsStage2.p, hip_stream))
+      return -1;
+    const int rtn = quality_run(E.fieldsStage.p, E.fieldsStage2.p, is_float, nfields, n, E.arena.p, out, hip_stream);
+    E.prof.collect();
     return rtn;
   });
 }
