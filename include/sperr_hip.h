@@ -18,7 +18,9 @@
  *    passed as void* (NULL = the default stream).  Calls are synchronous with respect to the
  *    host when they return.  Many small volumes of one shape that each want a container go
  *    through the batch calls (sperrhip_compress_batch_dev / sperrhip_decompress_batch_dev): one
- *    call for all of them, the same containers as one call per volume.
+ *    call for all of them, the same containers as one call per volume.  A box out of each of many
+ *    containers -- a region over a time series, crops for a loader -- is one call as well
+ *    (sperrhip_decompress_boxes_dev), whatever level or portion it is cut from.
  *
  * There is no CPU fallback: every entry point returns -1 (and prints the HIP error) when no
  * gfx950 device or kernel image is available.
@@ -431,6 +433,36 @@ int sperrhip_compress_batch_dev(const void* d_src, int is_float, size_t nvol, si
 int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, int output_float,
                                   void* d_dst, size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
                                   void* hip_stream);
+
+/* ---- a box per entry out of a batch of containers --------------------------------------------- */
+/* The same region of N time steps, or K crops of one shape out of a few containers, in one call: entry e is a box
+ * of container which[e], every entry with the same box dims, and the chunks of all entries are decoded together (one
+ * chain of per-plane launches for the call, not one per box).  The containers lie anywhere in device memory -- an
+ * array of pointers and lengths names them, nothing is copied together -- and only the chunks some box meets are
+ * read.  A chunk that several entries meet is decoded once: such a call decodes into a staging array the library
+ * keeps (sperrhip_release() frees it) and one more kernel moves every box's pieces out of it; a call whose entries
+ * share no chunk writes d_dst directly.  With `level` the boxes are cut from that level of the hierarchy, origins
+ * and dims in its coordinates, as sperrhip_decompress_level_dev takes them.  Box e of the result is bit for bit
+ * what sperrhip_decompress_portion_dev gives for container which[e] with the same level, box and pct.
+ * Both calls return -1, the second with d_dst as it was, for: nbox or ncont of 0, a NULL pointer (`which` and `level`
+ * may be NULL), a `which` index >= ncont, which == NULL with nbox != ncont, a box extent of 0, a box that leaves its
+ * volume or level, containers whose volume dims differ, with a level containers whose chunk dims differ or that
+ * have no such level, nbox * box_dims[2] or the staging array's z extent (the sum of the z extents of the distinct
+ * chunks) beyond INT32_MAX, more than 2^32 - 1 (entry, chunk) pairs, an output that is too small, or a container
+ * sperrhip_decompress_dev refuses.  One container passed under two indices counts as two. */
+/* host only: what a call would do.  out[5] = {slots, pairs, staged (0/1), staging values, output values}: the
+ * distinct (container, chunk) pairs decoded, the (entry, chunk) pairs written, whether the call stages.
+ * 0 ok, -1 for anything sperrhip_decompress_boxes_dev refuses that can be known from dims alone. */
+int sperrhip_boxes_plan(size_t ncont, const size_t vol_dims[3], const size_t* chunk_dims /* 3*ncont */,
+                        const uint32_t* which, const size_t* box_lo /* 3*nbox */, size_t nbox,
+                        const size_t box_dims[3], const size_t* level, size_t out[5]);
+/* d_srcs, src_lens: host arrays of ncont device pointers and byte lengths.
+ * entry e: the box [box_lo[3e..], + box_dims) of container which[e] (NULL: container e), or of its level *level;
+ * from the first pct percent of every chunk stream (0 or >= 100: all).  d_dst: nbox boxes back to back, x fastest. */
+int sperrhip_decompress_boxes_dev(const void* const* d_srcs, const size_t* src_lens, size_t ncont,
+                                  const uint32_t* which, const size_t* box_lo, size_t nbox,
+                                  const size_t box_dims[3], const size_t* level, unsigned pct,
+                                  int output_float, void* d_dst, size_t dst_cap_bytes, void* hip_stream);
 
 /* ---- a batch of same-shape 2D slices, one stream each ------------------------------------------ */
 /* N slices of the same (dimx, dimy) in one call, all of them coded side by side on the 2D coder: the

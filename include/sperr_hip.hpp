@@ -613,6 +613,31 @@ inline auto decompress_fields_dev(const void* d_streams, const std::vector<size_
   return rtn == 0 ? RTNType::Good : RTNType::Error;
 }
 
+// (this library's addition) A box per entry out of a batch of device containers, in one call
+// (sperrhip_decompress_boxes_dev): entry e is the box [box_lo[e], box_lo[e] + box_dims) of container which[e] -- of
+// container e when `which` is empty -- or, with `level`, of that level of its hierarchy in the level's coordinates;
+// from the first `pct` percent of every chunk stream (0: all).  d_streams[c] is container c, stream_lens[c] bytes of
+// device memory anywhere.  d_out receives box_lo.size() boxes back to back within `cap_bytes`.  RTNType::Error, with
+// nothing written, for what the C call refuses.
+template <typename T>
+inline auto decompress_boxes_dev(const std::vector<const void*>& d_streams, const std::vector<size_t>& stream_lens,
+                                 const std::vector<uint32_t>& which, const std::vector<dims_type>& box_lo,
+                                 dims_type box_dims, T* d_out, size_t cap_bytes, const size_t* level = nullptr,
+                                 unsigned pct = 0, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  if (d_streams.size() != stream_lens.size() || (!which.empty() && which.size() != box_lo.size()))
+    return RTNType::Error;
+  std::vector<size_t> lo;
+  for (const auto& o : box_lo)
+    lo.insert(lo.end(), o.begin(), o.end());
+  const int rtn = sperrhip_decompress_boxes_dev(d_streams.data(), stream_lens.data(), d_streams.size(),
+                                                which.empty() ? nullptr : which.data(), lo.data(), box_lo.size(),
+                                                box_dims.data(), level, pct, sizeof(T) == 4, d_out, cap_bytes,
+                                                hip_stream);
+  return rtn == 0 ? RTNType::Good : RTNType::Error;
+}
+
 // quality_dev of every field of two interleaved arrays; `out` receives eight figures per field
 // (sperrhip_quality_fields_dev)
 template <typename T>

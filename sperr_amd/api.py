@@ -44,6 +44,7 @@ EXPORTS = [
     "sperrhip_compress_view_dev", "sperrhip_decompress_view_dev", "sperrhip_quality_view_dev",
     "sperrhip_compress_fields_dev", "sperrhip_decompress_fields_dev", "sperrhip_quality_fields_dev",
     "sperrhip_fields_gather_dev", "sperrhip_fields_scatter_dev",
+    "sperrhip_boxes_plan", "sperrhip_decompress_boxes_dev",
 ]
 
 
@@ -214,6 +215,13 @@ def load_library():
     lib.sperrhip_fields_gather_dev.argtypes = [_vp, C.POINTER(Fields), _sz, C.c_int, _sz, _sz, _sz, _vp, _sz, _vp]
     lib.sperrhip_fields_scatter_dev.restype = C.c_int
     lib.sperrhip_fields_scatter_dev.argtypes = [_vp, _sz, C.c_int, _sz, _sz, _sz, _vp, C.POINTER(Fields), _sz, _vp]
+    lib.sperrhip_boxes_plan.restype = C.c_int
+    lib.sperrhip_boxes_plan.argtypes = [_sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint32), C.POINTER(_sz), _sz,
+                                        C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]
+    lib.sperrhip_decompress_boxes_dev.restype = C.c_int
+    lib.sperrhip_decompress_boxes_dev.argtypes = [C.POINTER(_vp), C.POINTER(_sz), _sz, C.POINTER(C.c_uint32),
+                                                  C.POINTER(_sz), _sz, C.POINTER(_sz), C.POINTER(_sz), C.c_uint,
+                                                  C.c_int, _vp, _sz, _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -549,6 +557,66 @@ class SperrHip:
                                                      C.byref(dz), self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decompress_batch_dev returned {rtn}")
+        return out
+
+    # ---- a box per entry out of a batch of containers --------------------------------------------
+    @staticmethod
+    def _boxes_args(ncont, box_lo_xyz, box_dims_xyz, which, level):
+        """(which, lo, nbox, dims, level) as the boxes calls take them.  box_lo_xyz: one origin for all entries, or
+        one per entry; the entries are `which`'s, or one per container"""
+        nbox = len(which) if which is not None else ncont
+        los = [box_lo_xyz] * nbox if np.ndim(box_lo_xyz) == 1 else list(box_lo_xyz)
+        if len(los) != nbox:
+            raise SperrHipError(f"{len(los)} box origins for {nbox} entries")
+        lo = (_sz * (3 * max(nbox, 1)))(*[int(v) for o in los for v in o])
+        wh = None if which is None else (C.c_uint32 * max(nbox, 1))(*[int(v) for v in which])
+        return wh, lo, nbox, (_sz * 3)(*[int(d) for d in box_dims_xyz]), None if level is None else C.byref(_sz(level))
+
+    def boxes_plan(self, shape_zyx, chunks_xyz, box_lo_xyz, box_dims_xyz, which=None, level=None):
+        """What decompress_boxes would do with containers of volume `shape_zyx`; host only.  chunks_xyz: the chunk
+        shape of every container, one (x, y, z) each.  A dict of slots (chunks decoded), pairs (pieces written),
+        staged, staging_values and output_values; raises SperrHipError for what the call would refuse."""
+        cds = [tuple(c) for c in chunks_xyz]
+        n = len(cds)
+        wh, lo, nbox, dims, lv = self._boxes_args(n, box_lo_xyz, box_dims_xyz, which, level)
+        dz, dy, dx = (int(d) for d in shape_zyx)
+        out = (_sz * 5)()
+        rtn = self.lib.sperrhip_boxes_plan(n, (_sz * 3)(dx, dy, dz), (_sz * (3 * n))(*[int(v) for c in cds for v in c]),
+                                           wh, lo, nbox, dims, lv, out)
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_boxes_plan returned {rtn}")
+        return {"slots": out[0], "pairs": out[1], "staged": bool(out[2]), "staging_values": out[3],
+                "output_values": out[4]}
+
+    def decompress_boxes(self, containers, box_lo_xyz, box_dims_xyz, which=None, level=None, pct=0, output_float=True,
+                         out=None):
+        """A box per entry out of a list of device containers, in one call: entry e is the box [lo_e, lo_e + dims)
+        (x, y, z order) of containers[which[e]] (which None: of containers[e]), or with `level` of that level of its
+        hierarchy, in the level's coordinates; box_lo_xyz is one origin for all entries or one per entry.  The
+        containers are cuda uint8 tensors wherever they lie -- they are never concatenated -- of volumes of the same
+        dims.  Only the chunks some box meets are read, and one that several entries meet is decoded once.  A cuda
+        tensor shaped (entries, dims z, dims y, dims x) -- `out` when given; entry e is bit for bit decompress_box /
+        decompress_level of its container with the same box and pct."""
+        torch = self.torch
+        for c in containers:
+            assert c.is_cuda and c.dtype == torch.uint8 and c.dim() == 1 and c.is_contiguous()
+        ncont = len(containers)
+        wh, lo, nbox, dims, lv = self._boxes_args(ncont, box_lo_xyz, box_dims_xyz, which, level)
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            if ncont == 0 or nbox == 0:
+                raise SperrHipError("decompress_boxes: no containers or no entries")
+            out = torch.empty((nbox,) + tuple(int(d) for d in reversed(box_dims_xyz)), dtype=dt,
+                              device=containers[0].device)
+        self._no_view(out, "decompress_boxes")
+        assert out.dtype == dt and out.is_cuda
+        ptrs = (_vp * max(ncont, 1))(*[c.data_ptr() for c in containers])
+        lens = (_sz * max(ncont, 1))(*[c.numel() for c in containers])
+        rtn = self.lib.sperrhip_decompress_boxes_dev(ptrs, lens, ncont, wh, lo, nbox, dims, lv, int(pct),
+                                                     int(output_float), out.data_ptr(),
+                                                     out.numel() * out.element_size(), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_boxes_dev returned {rtn}")
         return out
 
     # ---- quality figures of a reconstruction ---------------------------------------------------

@@ -36,6 +36,7 @@
 #include "quality.h"
 #include "view.h"
 #include "fields.h"
+#include "boxes.h"
 #include "xform.h"
 
 // The decoder runs the shape groups of a volume side by side on up to eight streams; the ROCm
@@ -792,6 +793,7 @@ struct Engine {
   DevBuf wideScratch;                       // 64-bit retry of a batch whose coder arrays lay over the chunk buffer
   DevBuf fieldsStage, fieldsStage2;         // interleaved fields (fields.h): the stacked volumes the batch code works on,
                                             //   and the quality call's other side
+  DevBuf boxesStage;                        // boxes of a batch (boxes.h): the staging array of the staged form
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
 
@@ -914,7 +916,7 @@ struct Engine {
     plans.clear();
     planOrder.clear();
     for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2})
+                      &fieldsStage2, &boxesStage})
       b->drop();
     for (auto& b : outlDec)
       b.drop();
@@ -932,7 +934,7 @@ struct Engine {
   {
     size_t n = 0;
     for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2})
+                      &fieldsStage2, &boxesStage})
       n += b->n;
     for (const auto& b : outlDec)
       n += b.n;
@@ -2764,19 +2766,33 @@ int read_container_info(const uint8_t* d_src, size_t src_len, ContainerInfo& ci,
 // one gather and one read-back, then the full headers of those with more to read in a second, each parsed by
 // parse_container_host into ci[v] (offsets relative to the container).  heads: 32 bytes per container, its first 26
 // (or fewer) and zeros.  No container base is assumed aligned: the gathers read bytes
+int read_headers_at(Engine& E, const uint8_t* d_src, const std::vector<uint64_t>& off, const std::vector<uint64_t>& len,
+                    std::vector<ContainerInfo>& ci, std::vector<uint8_t>& heads, hipStream_t st);
 int read_batch_headers(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, std::vector<ContainerInfo>& ci,
                        std::vector<uint8_t>& heads, hipStream_t st)
 {
   if (nvol == 0 || nvol > 0xffffffffull)
     return -1;
-  const uint32_t n = (uint32_t)nvol;
-  std::vector<uint64_t> off(nvol), len(nvol), need(nvol, 0), at(nvol + 1, 0);
+  std::vector<uint64_t> off(nvol), len(nvol);
   for (size_t v = 0; v < nvol; v++) {
     if (offs[v + 1] < offs[v])
       return -1;
     off[v] = offs[v];
     len[v] = offs[v + 1] - offs[v];
   }
+  return read_headers_at(E, d_src, off, len, ci, heads, st);
+}
+
+// The same for containers that lie anywhere: container v is the len[v] bytes at d_src + off[v] (the boxes call: d_src
+// is the lowest of its containers' addresses)
+int read_headers_at(Engine& E, const uint8_t* d_src, const std::vector<uint64_t>& off, const std::vector<uint64_t>& len,
+                    std::vector<ContainerInfo>& ci, std::vector<uint8_t>& heads, hipStream_t st)
+{
+  const size_t nvol = off.size();
+  if (nvol == 0 || nvol > 0xffffffffull || len.size() != nvol)
+    return -1;
+  const uint32_t n = (uint32_t)nvol;
+  std::vector<uint64_t> need(nvol, 0), at(nvol + 1, 0);
   const size_t arr = round_up(nvol * 8, 256);
   if (E.misc.ensure(arr * 3 + nvol * 32 + 256))
     return -1;
@@ -3220,7 +3236,8 @@ k_sub_volume(const double* vals, size_t valsStride, const CoderState* cst, const
 // box of the volume at full resolution (sperrhip_decompress_box_dev), or -- `level` -- a box of level h of the
 // hierarchy alone, coarsest first, in the level's coordinates (sperrhip_decompress_level_dev).  The level is the grid
 // of the chunks' corners of resolution cres[h], so the chunks its box meets are box_chunks of the level's dims with
-// cres[h] as the chunk size
+// cres[h] as the chunk size.  Or, with slotGeom, the output of a boxes call (boxes.h): many boxes of either kind, the
+// chunks of many containers
 struct Window {
   Dims lo, dims;
   std::vector<uint32_t> ids;
@@ -3228,6 +3245,19 @@ struct Window {
   bool level = false;   // of level h of m; otherwise of the volume
   size_t h = 0;
   MultiRes m;
+  // Boxes of a batch (boxes.h, sperrhip_decompress_boxes_dev): the window is the call's whole output -- nbox boxes back
+  // to back, or the staging array -- and every slot brings its own geometry, BoxesPlan::geom; lo is unused and `dims`
+  // the output's.  Empty: the one box [lo, lo + dims), each chunk placed by place() + crop_geom()
+  std::vector<CropGeom> slotGeom;
+  // what the chunk of slot `slot`, at `org` with dims `cd`, writes of the window, and where
+  CropGeom geom_of(uint32_t slot, const uint32_t org[3], const uint32_t cd[3]) const
+  {
+    if (!slotGeom.empty())
+      return slotGeom[slot];
+    size_t o[3], ext[3];
+    place(org, cd, o, ext);
+    return crop_geom(o, ext);
+  }
   // the chunk at `org` of dims `cd`, in the coordinates the window is given in: its origin and extent
   void place(const uint32_t org[3], const uint32_t cd[3], size_t o[3], size_t ext[3]) const
   {
@@ -3379,8 +3409,10 @@ struct DecodeRequest {
       return false;
     if (stacked && levels)   // the stacked view is no volume with a hierarchy: each container has its own
       return false;
-    if (level() && stacked)   // a level's grid of chunk corners is one container's
-      return false;
+    if (level() && stacked && window->slotGeom.empty())   // a level's grid of chunk corners is one container's: only the
+      return false;                                        //   boxes call, whose slots bring their geometry, has many
+    if (window && !window->slotGeom.empty() && (!stacked || window->slotGeom.size() != window->ids.size()))
+      return false;   // per-slot geometry is the boxes call's, one record per chunk of its list
     if (level() && level()->h >= level()->m.nlev)   // the container has no such level
       return false;
     if (outView && (stacked || slices || levels || level()))   // a view holds one volume or a box of it at full resolution
@@ -3985,11 +4017,8 @@ struct DecodeCall {
     HIP_CHECK(hipMemcpyAsync(bb.geom, S.hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, ss));
     if (req.cropped()) {   // each chunk's piece of the window and its origin relative to the window
       S.hc.resize(nb);
-      for (uint32_t i = 0; i < nb; i++) {
-        size_t o[3], ext[3];
-        req.window->place(S.hg[i].org, P.dims, o, ext);
-        S.hc[i] = req.window->crop_geom(o, ext);
-      }
+      for (uint32_t i = 0; i < nb; i++)
+        S.hc[i] = req.window->geom_of((*b.refs)[S.first + i].slot, S.hg[i].org, P.dims);
       HIP_CHECK(hipMemcpyAsync(bb.crop, S.hc.data(), nb * sizeof(CropGeom), hipMemcpyHostToDevice, ss));
     }
     HIP_CHECK(hipMemcpyAsync(bb.chunkOff, S.ho.data(), nb * 8, hipMemcpyHostToDevice, ss));
@@ -5607,6 +5636,188 @@ int sperrhip_decomp_3d_multires(const void* src, size_t src_len, int output_floa
       *dimz = ci.vol[2];
     }
     return rtn;
+  });
+}
+
+// ---- a box per entry out of a batch of containers (boxes.h) -------------------------------------
+// The grid a boxes call cuts along: the volume and every container's chunk dims, or with a level -- which the
+// containers must then share chunk dims for, and have -- the level's dims and the chunks' corner cres[h] (level_select)
+static int boxes_grid(const Dims& vol, const std::vector<Dims>& chunk, const size_t* level, Dims& full,
+                      std::vector<Dims>& cell, MultiRes& m)
+{
+  full = vol;
+  cell = chunk;
+  if (!level)
+    return 0;
+  for (const Dims& c : chunk)
+    if (c != chunk[0])
+      return -1;
+  multires_levels(vol, chunk[0], m);
+  if (*level >= m.nlev)
+    return -1;
+  Dims cr;
+  for (int a = 0; a < 3; a++) {
+    cr[a] = m.cres[*level][a];
+    full[a] = cr[a] * m.grid[a];
+  }
+  cell.assign(chunk.size(), cr);
+  return 0;
+}
+
+int sperrhip_boxes_plan(size_t ncont, const size_t vol_dims[3], const size_t* chunk_dims, const uint32_t* which,
+                        const size_t* box_lo, size_t nbox, const size_t box_dims[3], const size_t* level, size_t out[5])
+{
+  return guarded("sperrhip_boxes_plan", [&]() -> int {
+    if (!vol_dims || !chunk_dims || !box_lo || !box_dims || !out || ncont == 0 || ncont > 0xffffffffull)
+      return -1;
+    std::vector<Dims> chunk(ncont), cell;
+    for (size_t c = 0; c < ncont; c++)
+      chunk[c] = Dims{chunk_dims[3 * c], chunk_dims[3 * c + 1], chunk_dims[3 * c + 2]};
+    Dims full;
+    MultiRes m;
+    BoxesPlan P;
+    if (boxes_grid(Dims{vol_dims[0], vol_dims[1], vol_dims[2]}, chunk, level, full, cell, m) ||
+        !boxes_plan(ncont, full, cell.data(), which, box_lo, nbox, Dims{box_dims[0], box_dims[1], box_dims[2]}, P))
+      return -1;
+    out[0] = P.slots.size();
+    out[1] = P.pairs.size();
+    out[2] = P.shared ? 1 : 0;
+    out[3] = P.stageVals;
+    out[4] = P.outVals;
+    return 0;
+  });
+}
+
+// The containers are read where they lie: every offset of the call is one from the lowest of their addresses.  Each
+// header is read once; the plan (boxes.h) names the slots, whose chunks become the call's stacked list -- one chunk per
+// slot, in the slots' order -- with the plan's geometry on the window.  Direct form: the crop writers fill d_dst.
+// Staged form: they fill the engine's staging array, typed as the output, and one launch of k_boxes_copy moves every
+// pair's window into its box
+int sperrhip_decompress_boxes_dev(const void* const* d_srcs, const size_t* src_lens, size_t ncont, const uint32_t* which,
+                                  const size_t* box_lo, size_t nbox, const size_t box_dims[3], const size_t* level,
+                                  unsigned pct, int output_float, void* d_dst, size_t dst_cap_bytes, void* hip_stream)
+{
+  return guarded("sperrhip_decompress_boxes_dev", [&]() -> int {
+    if (!d_srcs || !src_lens || !box_lo || !box_dims || !d_dst || ncont == 0 || nbox == 0 || ncont > 0xffffffffull ||
+        nbox > 0xffffffffull || (!which && nbox != ncont))
+      return -1;
+    uintptr_t base = UINTPTR_MAX;
+    for (size_t c = 0; c < ncont; c++) {
+      if (!d_srcs[c])
+        return -1;
+      base = std::min(base, reinterpret_cast<uintptr_t>(d_srcs[c]));
+    }
+    for (size_t e = 0; which && e < nbox; e++)
+      if (which[e] >= ncont)
+        return -1;
+    for (int a = 0; a < 3; a++)
+      if (box_dims[a] == 0)
+        return -1;
+    Lease L;
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(base);
+    const size_t esz = output_float ? sizeof(float) : sizeof(double);
+    std::vector<uint64_t> off(ncont), len(ncont);
+    for (size_t c = 0; c < ncont; c++) {
+      off[c] = reinterpret_cast<uintptr_t>(d_srcs[c]) - base;
+      len[c] = src_lens[c];
+    }
+    std::vector<ContainerInfo> ci;
+    std::vector<uint8_t> heads;
+    if (read_headers_at(E, src, off, len, ci, heads, st))
+      return -1;
+    std::vector<Dims> chunk(ncont), cell;
+    for (size_t c = 0; c < ncont; c++) {
+      if (ci[c].vol != ci[0].vol)   // (the batch decode's rule)
+        return -1;
+      chunk[c] = ci[c].chunk;
+      keep_portion(ci[c], pct);
+    }
+    Dims full;
+    Window w;
+    BoxesPlan P;
+    if (boxes_grid(ci[0].vol, chunk, level, full, cell, w.m) ||
+        !boxes_plan(ncont, full, cell.data(), which, box_lo, nbox, Dims{box_dims[0], box_dims[1], box_dims[2]}, P))
+      return -1;
+    if (P.outVals > dst_cap_bytes / esz || P.stageVals > SIZE_MAX / 8)
+      return -1;
+    // the call's chunks: slot k is chunk P.slots[k].id of its container
+    const size_t nslots = P.slots.size();
+    ContainerInfo all;
+    std::vector<std::array<size_t, 6>> list(nslots), per;
+    all.chunk = ci[0].chunk;
+    all.off.resize(nslots);
+    all.len.resize(nslots);
+    w.ids.resize(nslots);
+    w.slotGeom.resize(nslots);
+    for (size_t k = 0, have = SIZE_MAX; k < nslots; k++) {
+      const BoxesSlot& s = P.slots[k];
+      if (s.cont != have) {   // (the slots are in container order)
+        per = chunk_volume(ci[s.cont].vol, ci[s.cont].chunk);
+        have = s.cont;
+        if (per.size() != ci[s.cont].off.size())
+          return -1;
+      }
+      if (s.id >= per.size())
+        return -1;
+      list[k] = per[s.id];
+      all.off[k] = off[s.cont] + ci[s.cont].off[s.id];
+      all.len[k] = ci[s.cont].len[s.id];
+      w.ids[k] = (uint32_t)k;
+      CropGeom& g = w.slotGeom[k];
+      for (int a = 0; a < 3; a++) {
+        g.rel[a] = P.geom[k].rel[a];
+        g.lo[a] = P.geom[k].lo[a];
+        g.hi[a] = P.geom[k].hi[a];
+      }
+    }
+    w.crop = true;
+    w.level = level != nullptr;
+    w.h = level ? *level : 0;
+    w.lo = Dims{0, 0, 0};
+    w.dims = P.shared ? P.stageDims : P.outDims;
+    all.vol = w.dims;
+    all.nvals = P.shared ? P.stageVals : P.outVals;
+    void* d_out = d_dst;
+    size_t outBytes = dst_cap_bytes;
+    if (P.shared) {
+      outBytes = P.stageVals * esz;
+      if (E.boxesStage.ensure(outBytes))
+        return -1;
+      d_out = E.boxesStage.p;
+    }
+    DecodeRequest req;
+    req.stacked = &list;
+    req.window = &w;
+    const int rtn = decode_to(E, src, output_float, d_out, outBytes, all, st, req);
+    if (rtn || !P.shared)
+      return rtn;
+    std::vector<BoxesCopyPair> pairs;
+    std::vector<uint64_t> first;
+    BoxesCopyGeom g;
+    boxes_copy_args(P, pairs, first, g);
+    const size_t pairBytes = round_up(pairs.size() * sizeof(BoxesCopyPair), 256);
+    if (E.misc.ensure(pairBytes + first.size() * 8))
+      return -1;
+    BoxesCopyPair* d_pairs = static_cast<BoxesCopyPair*>(E.misc.p);
+    uint64_t* d_first = reinterpret_cast<uint64_t*>(static_cast<char*>(E.misc.p) + pairBytes);
+    const bool vec = boxes_vec_ok(reinterpret_cast<uintptr_t>(d_out), reinterpret_cast<uintptr_t>(d_dst), pairs, g, esz);
+    auto copy = [&]() -> int {
+      HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(BoxesCopyPair), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
+      if (boxes_copy_run(d_out, d_dst, esz, d_pairs, d_first, g, vec, st))
+        return -1;
+      HIP_CHECK(hipStreamSynchronize(st));   // (also: the uploads' host arrays may go only once the copies have read them)
+      return 0;
+    };
+    const int rc = copy();
+    if (rc)
+      drain_after_error(E, st);   // (as ~DecodeCall: queued copies read the vectors above)
+    E.prof.collect();
+    return rc;
   });
 }
 
