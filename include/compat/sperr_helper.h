@@ -2,7 +2,7 @@
 // (/root/reference/include/sperr_helper.h:35-191), for callers such as utilities/sperr3d.cpp that
 // use them next to the driver classes.  Types, RTNType and the driver classes come from
 // ../sperr_hip.hpp; the helpers below are header-only host code written for this library (the
-// geometry ones are the rules the chunk farm itself follows, see sperr_amd/csrc/engine.hip).
+// geometry ones are the rules the chunk farm itself follows, see host_chunk_volume in sperr_amd/csrc/engine.hip).
 //
 // Statistics note: calc_stats / calc_mean_var sum in blocks of 8192 / 16384 values and then over
 // the blocks, left to right, like the reference (src/sperr_helper.cpp:428-511,616-659), so the

@@ -1,5 +1,5 @@
 // boxes.h -- a box per entry out of a batch of containers: the ONLY statement of which chunks such a call decodes,
-// what each of them writes and where (the entry points of engine.hip, the copy kernel of boxes.hip and the host check
+// what each of them writes and where (the entry points of abi.hip, the copy kernel of boxes.hip and the host check
 // tests/cpp/boxes_check.cpp all use these).  Plain C++: no HIP here.
 //
 // A call names `ncont` containers and `nbox` entries.  Entry e is the box [lo_e, lo_e + box) of container which[e]

@@ -1,5 +1,6 @@
 // engine.hip -- host side of the HIP engine: chunk grid, per-shape plans, batched workspaces,
-// container assembly / parsing, and the C ABI declared in include/sperr_hip.h.
+// container assembly / parsing.  The C ABI declared in include/sperr_hip.h is abi.hip and abi_stages.hip, which see
+// this unit through engine_core.h (types, globals, the encoder's front) and decode_request.h (the decoder's front).
 //
 // Host logic restated from the reference (file:line under /root/reference):
 //   src/sperr_helper.cpp:542-592            chunk_volume (x fastest, short remainders merged)
@@ -8,36 +9,12 @@
 //   src/SPERR3D_Stream_Tools.cpp:46-105     container header parsing
 //   src/SPERR3D_OMP_D.cpp:23-135            decompress driver
 //   src/SPECK_FLT.cpp:401-541               per-chunk pipeline order and the fixed-rate retry
-//   src/SPERR_C_API.cpp:135-258             C API semantics (ownership, return codes)
-#include <algorithm>
-#include <array>
 #include <chrono>
-#include <cstdlib>
-#include <cstring>
-#include <atomic>
 #include <deque>
-#include <map>
-#include <memory>
-#include <condition_variable>
-#include <mutex>
 #include <numeric>
 #include <thread>
-#include <string>
-#include <vector>
 
-#include "../../include/sperr_hip.h"
-#include "engine_internal.h"
-#include "host_container.hpp"
-#include "speck_dec.h"
-#include "dequant.h"
-#include "speck_enc.h"
-#include "speck_tree_host.hpp"
-#include "outlier.h"
-#include "quality.h"
-#include "view.h"
-#include "fields.h"
-#include "boxes.h"
-#include "xform.h"
+#include "decode_request.h"
 
 // The decoder runs the shape groups of a volume side by side on up to eight streams; the ROCm
 // runtime maps streams onto four hardware queues unless told otherwise, and reads the variable at
@@ -52,86 +29,18 @@ namespace sperrhip {
 // ------------------------------------------------------------------------------------------
 // profiling
 // ------------------------------------------------------------------------------------------
-namespace {
-
-struct ProfEntry {
-  double ms = 0.0;     // sum of the launch durations
-  double busy = 0.0;   // time during which at least one launch of the kernel was running (launches
-                       // of sub-batches on different streams overlap)
-  int launches = 0;
-};
-
-struct Profiler {
-  bool on = false;
-  std::string only;   // when not empty: only launches of this kernel are bracketed
-  std::mutex mu;      // sub-batches are enqueued from several host threads
-  std::vector<hipEvent_t> pool;
-  size_t used = 0;
-  hipEvent_t ref = nullptr;   // origin of the time axis of one collect() period
-  struct Open {
-    const char* name;
-    hipEvent_t a, b;
-  };
-  std::vector<Open> open;
-  std::map<std::string, ProfEntry> acc;
-
-  hipEvent_t get()   // (mu held)
-  {
-    if (used == pool.size()) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess)
-        return nullptr;
-      pool.push_back(e);
-    }
-    return pool[used++];
-  }
-  void collect()
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    std::map<std::string, std::vector<std::pair<float, float>>> spans;
-    for (auto& o : open) {
-      float ms = 0.f, t0 = 0.f;
-      if (o.a && o.b && hipEventElapsedTime(&ms, o.a, o.b) == hipSuccess) {
-        auto& e = acc[o.name];
-        e.ms += ms;
-        e.launches++;
-        if (ref && hipEventElapsedTime(&t0, ref, o.a) == hipSuccess)
-          spans[o.name].push_back({t0, t0 + ms});
-        else
-          e.busy += ms;
-      }
-    }
-    for (auto& kv : spans) {
-      auto& v = kv.second;
-      std::sort(v.begin(), v.end());
-      double busy = 0.0;
-      float lo = v[0].first, hi = v[0].second;
-      for (size_t i = 1; i < v.size(); i++) {
-        if (v[i].first > hi) {
-          busy += hi - lo;
-          lo = v[i].first;
-          hi = v[i].second;
-        }
-        else
-          hi = std::max(hi, v[i].second);
-      }
-      acc[kv.first].busy += busy + (hi - lo);
-    }
-    open.clear();
-    used = 0;
-    ref = nullptr;
-  }
-};
-
+// the file-scope state other units see (extern in engine_core.h)
 // global switches (sperrhip_profile_enable / _only); the accumulators live in the engines
 bool g_prof_on = false;
 std::string g_prof_only;
 std::mutex g_prof_cfg_mu;
 thread_local Profiler* t_prof = nullptr;       // the profiler of the engine this thread drives
-thread_local const char* t_prof_cur = nullptr;
-thread_local hipEvent_t t_prof_a = nullptr;
-
-}  // namespace
+static thread_local const char* t_prof_cur = nullptr;
+static thread_local hipEvent_t t_prof_a = nullptr;
+std::atomic<unsigned long long> g_dbg_counter[4];   // sperrhip_debug_counter (0..2, and [3] as counter 7)
+bool g_lis_stamps_on = false;
+std::vector<uint64_t> g_lis_stamps_host;   // chunk 0 of the last decoded batch
+EnginePool g_pool;
 
 void prof_begin(const char* name, hipStream_t stream)
 {
@@ -170,81 +79,6 @@ thread_local bool t_shared_device = false;   // (engine_internal.h)
 // ------------------------------------------------------------------------------------------
 namespace {
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  void drop()
-  {
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  int ensure(size_t bytes)
-  {
-    if (bytes <= n)
-      return 0;
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    // (a quarter more than asked for, for the small buffers whose size follows the data -- outlier
-    //  streams, slots --: a hipFree waits for every stream of the device, the other workers' included,
-    //  and a buffer that fits exactly is too small for the next call's slightly longer streams)
-    size_t want = bytes < (size_t(256) << 20) ? bytes + bytes / 4 + 4096 : bytes;
-    // (callers size their requests against the free memory they saw: when the slack is what does not fit,
-    //  the exact size still may)
-    if (want != bytes && hipMalloc(&p, want) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      want = bytes;
-    }
-    if (!p)
-      HIP_CHECK(hipMalloc(&p, want));
-    n = want;
-    return 0;
-  }
-};
-
-std::atomic<unsigned long long> g_dbg_counter[4];   // sperrhip_debug_counter (0..2, and [3] as counter 7)
-
-struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, used = 0;
-  template <typename T>
-  T* take(size_t count)
-  {
-    // sizes may come from an untrusted header: nothing here may wrap
-    if (used > cap || count > (cap - used) / sizeof(T))
-      return nullptr;
-    const size_t bytes = (count * sizeof(T) + 255) / 256 * 256;
-    if (bytes > cap - used)
-      return nullptr;
-    T* r = reinterpret_cast<T*>(base + used);
-    used += bytes;
-    return r;
-  }
-};
-
-// bytes that hold `bits` bits; bit counts read from a container may be anything up to 2^64 - 1
-inline uint64_t bytes_of_bits(uint64_t bits)
-{
-  return bits / 8 + (bits % 8 != 0);
-}
-
-size_t round_up(size_t v, size_t m)
-{
-  return (v + m - 1) / m * m;
-}
-
-using hostc::Dims;
-using hostc::chunk_count;
-using hostc::box_chunks;
-using hostc::chunk_volume;
-using hostc::ContainerInfo;
-using hostc::parse_container_host;
-using hostc::keep_portion;
-
 // src/Conditioner.cpp:137-163
 uint32_t condi_num_strides(size_t len)
 {
@@ -263,66 +97,6 @@ uint32_t condi_num_strides(size_t len)
 // ------------------------------------------------------------------------------------------
 // per-shape plan: tree tables on the device, tile maps, DWT pass list
 // ------------------------------------------------------------------------------------------
-struct LiftPass {
-  int axis;
-  uint32_t region[3];
-};
-
-// How a chunk shape's transform runs.  Decided once, when the plan is made (plan_schedule, below): the encoder's
-// launches (float_stages, pwe_stage_begin) and the decoder's memory layout and launches (compact_box, decode_group,
-// enqueue_inverse) read it, and nothing else asks the pass list these questions.
-struct LiftSchedule {
-  enum Head { kNoHead, kHeadXY, kHeadXYZ };
-  Head head = kNoHead;     // the finest level's full-size passes that one kernel runs, straight from / into the volume
-  bool fusable = false;    // the passes can collect the largest coefficient / dequantise on the way (plan_fusable)
-  bool brick = false;      // x-y-z head, fusable, at least three passes: the coarser levels can work in a compact box
-  bool level2 = false;     // passes 3 to 5 -- the second level -- run as one launch each way (plan_level2)
-  uint32_t coarseBox[3] = {1, 1, 1};   // the box the coarser levels work in: the largest region of the passes k >= 3
-  struct Pass {   // what pass_fuse_rule says of a pass: -1, 0 or 1, and the box of the later passes
-    int fuse;
-    uint32_t inner[3];
-  };
-  std::vector<Pass> pass;
-  // The passes, counted from the finest, that fused launches run instead of the per-axis kernel: the forward walk's
-  // per-axis loop starts there and the inverse walk's stops there
-  static size_t fused_passes(Head head, bool level2) { return level2 ? 6 : head == kHeadXYZ ? 3 : head == kHeadXY ? 2 : 0; }
-};
-
-struct ShapePlan {
-  uint32_t dims[3];
-  uint32_t N = 0;
-  spk::HostTree ht;
-  spk::Tree dtree{};
-  DevBuf tables;
-  const uint64_t* d_initLIS = nullptr;
-  const uint32_t* d_initLen = nullptr;
-  const uint32_t* d_levelOff = nullptr;
-  const uint16_t* d_tileLevel = nullptr;
-  const uint32_t* d_tileStart = nullptr;
-  const uint32_t* d_levelFirstTile = nullptr;
-  const uint32_t* d_levelNumTiles = nullptr;
-  const uint32_t* d_depthBlocks = nullptr;
-  const uint8_t* d_levelSlot = nullptr;
-  const uint64_t* d_iRoots = nullptr;   // (2D forest)
-  const uint8_t* d_slotLevel = nullptr;
-  const spk::LevelClass* d_levelClass = nullptr;
-  const uint32_t* d_wordLeaf = nullptr;   // nullptr: no raster word lies over leaf-word grids
-  const FusedRoot* d_fusedRoots = nullptr;   // non-null: the encoder's 32-bit pass can take k_head_fused (fused_head_roots)
-  const uint8_t* d_mxSlot = nullptr;      // k_lis_mx: column of every shape class
-  const uint8_t* d_mxLevelGroup = nullptr;
-  int l0Level = -1;                       // LIS level of 2x2x2 leaf sets that k_lis_l0 can decode
-  int l1Level = -1;                       // LIS level of 4x4x4 sets that k_lis_l1 can decode
-  int l2Level = -1;                       // LIS level of 8x8x8 sets that k_lis_l2 can decode
-  int maxK = 0;
-  std::vector<uint32_t> depthBlockOff;
-  uint32_t nListTiles = 0, nSlots = 0, nPixTiles = 0, nstrides = 0;
-  uint64_t maxPhaseBits = 0;
-  size_t lisEntries = 0;
-  std::vector<LiftPass> fwd;
-  LiftSchedule schedule;   // which kernels run the passes (plan_schedule)
-  DecPlanHost dec{};       // the list kernels the shape's decoder takes (plan_list_kernels); per-call fields at their defaults
-};
-
 // The encoder's fused head (k_head_fused, speck_enc.hip) wants workgroups that own whole pixel tiles AND whole leaf sets:
 // an all-octree forest (cubic power-of-two roots) whose every deepest grid is one pyramid_leaf4 takes (leaf4_block) with
 // even y and z origins, rows that are a power of two with at least two of them in a pixel tile, slices that are whole
@@ -562,8 +336,10 @@ static DecPlanHost plan_list_kernels(const ShapePlan& P, bool tables)
   return ph;
 }
 
+}  // namespace
+
 // twoD: the plan of a slice's DECODER, with the forest of the 2D coder (spk::kTree2D)
-int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
+int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD)
 {
   // set coordinates are packed 16 bits per axis (speck_tree.h pack_node), sample indices are 32 bits
   const unsigned __int128 samples = (unsigned __int128)dx * dy * dz;
@@ -753,305 +529,7 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD = false)
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------
-// engines: one per (device, concurrent caller)
-// ------------------------------------------------------------------------------------------
-// The reference's classes are re-entrant (one compressor object per OpenMP thread,
-// src/SPERR3D_OMP_C.cpp:61-92).  Here an engine owns everything a call needs on ONE device (streams,
-// per-shape plans, workspaces); a call leases an idle engine of the device that is current on the
-// calling thread and a new one is made when all of them are busy (up to
-// SPERR_HIP_ENGINES_PER_DEVICE, default 4; then callers wait).  The chunk farm (farm.hip) runs
-// several workers per device this way.
-constexpr uint32_t kSubStreams = 8;
-
-struct Engine {
-  int dev = -1;
-  bool busy = false;
-  bool ready = false;
-  Profiler prof;
-  hipStream_t sub[kSubStreams] = {};
-  hipEvent_t evFork = nullptr, evJoin[kSubStreams] = {};
-  hipStream_t outl = nullptr;               // the 1D decoder of outlier streams runs here, beside the chunk decoders
-  hipStream_t outlQ[kSubStreams] = {};      //   (one per sub-batch; outlQ[0] == outl; a priority of their own: init_handles)
-  hipStream_t sideQ[kSubStreams] = {};      // the encoder's census beside a part's pyramid (normal priority)
-  hipEvent_t evOutl[kSubStreams] = {}, evOutlFork[kSubStreams] = {};   // (per sub-batch)
-  hipEvent_t evPweFork = nullptr;          // encoder, point-wise error mode: the outlier stage's first half starts beside the 3D coder
-  hipEvent_t evPweJoin = nullptr;          //   ... and its end is waited for by the batch's stream, not by the host (round 6)
-  std::map<Dims, std::unique_ptr<ShapePlan>> plans;
-  std::vector<Dims> planOrder;             // least recently used first
-  DevBuf arena, slots, misc;
-  DevBuf outlFixed, outlVar, outlStream;   // point-wise error mode: workspace of the outlier coder
-  DevBuf pweBox;                           //   ... and the coarser levels' box of its reconstruction (pwe_stage_begin)
-  hipStream_t pweLastStream = nullptr;     //   stream the last batch's outlier stage ended on without a wait (round 6): the
-                                           //   next batch of the SAME call may run its stage on another one and reuses the buffers
-  DevBuf outlDec[kSubStreams];             //   (decoder: one per sub-batch of a call)
-  DevBuf decBox[kSubStreams];              //   ... and the coarser levels' box of a sub-batch with outlier streams
-  uint32_t* liveHost[kSubStreams] = {};    // pinned: answers to "do any chunks still decode" (DecPlanHost)
-  void* pweHost = nullptr;                 // pinned: the outlier stage's first read-back (a copy into pageable memory
-  size_t pweHostBytes = 0;                 //   would hold the host until the stream gets there: compress_impl)
-  hipEvent_t liveEv[kSubStreams][kLiveSlots] = {};
-  DevBuf wideScratch;                       // 64-bit retry of a batch whose coder arrays lay over the chunk buffer
-  DevBuf fieldsStage, fieldsStage2;         // interleaved fields (fields.h): the stacked volumes the batch code works on,
-                                            //   and the quality call's other side
-  DevBuf boxesStage;                        // boxes of a batch (boxes.h): the staging array of the staged form
-  std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
-  size_t freeMemAtInit = 0;
-
-  // an engine whose initialisation fails is never handed out (EnginePool::acquire): what it made
-  // up to the failure goes back at once
-  int init()
-  {
-    if (ready)
-      return 0;
-    const int rc = init_handles();
-    if (rc)
-      destroy_handles();
-    return rc;
-  }
-  void destroy_handles()
-  {
-    auto ds = [](hipStream_t& s) { if (s) (void)hipStreamDestroy(s); s = nullptr; };
-    auto de = [](hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
-    for (uint32_t q = 0; q < kSubStreams; q++) {
-      ds(sub[q]);
-      de(evJoin[q]);
-      if (q > 0)
-        ds(outlQ[q]);
-      ds(sideQ[q]);
-      de(evOutl[q]);
-      de(evOutlFork[q]);
-      if (q == 0) {
-        de(evPweFork);
-        de(evPweJoin);
-      }
-      if (liveHost[q])
-        (void)hipHostFree(liveHost[q]);
-      liveHost[q] = nullptr;
-      if (q == 0 && pweHost) {
-        (void)hipHostFree(pweHost);
-        pweHost = nullptr;
-        pweHostBytes = 0;
-      }
-      for (int k = 0; k < kLiveSlots; k++)
-        de(liveEv[q][k]);
-    }
-    de(evFork);
-    ds(outl);
-    outlQ[0] = nullptr;
-    ready = false;
-  }
-  int init_handles()
-  {
-    size_t fr = 0, tot = 0;
-    HIP_CHECK(hipMemGetInfo(&fr, &tot));
-    freeMemAtInit = fr;
-    for (uint32_t q = 0; q < kSubStreams; q++) {
-      HIP_CHECK(hipStreamCreateWithFlags(&sub[q], hipStreamNonBlocking));
-      HIP_CHECK(hipEventCreateWithFlags(&evJoin[q], hipEventDisableTiming));
-    }
-    HIP_CHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
-    // The streams of the 1D decoder (outlier lists, beside a sub-batch's chunk decoders) get a priority of
-    // their own.  The runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues PER PRIORITY, and a side
-    // stream that shares a hardware queue with the stream it is meant to run beside runs behind it instead
-    // (round 4: with eight sub-streams and eight side streams on eight queues, eight point-wise-error chunks
-    // at a tolerance of 1e-4 decoded in 44.8 ms -- the 30 ms of the 1D decoder and then the rest -- where 16
-    // queues, or this, give 31; 16 queues cost the fixed-rate compression 2 %).  Not the encoder's census
-    // streams: with a priority of their own 8 chunks compress at 63 instead of 75 GB/s.
-    int prLeast = 0, prGreatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest) != hipSuccess) {
-      (void)hipGetLastError();
-      prLeast = prGreatest = 0;
-    }
-    static const int sidePrio = getenv("SPERR_HIP_SIDE_PRIORITY") ? atoi(getenv("SPERR_HIP_SIDE_PRIORITY")) : 1;
-    const int prSide = sidePrio > 0 ? prGreatest : sidePrio < 0 ? prLeast : 0;   // (0: like every other stream)
-    HIP_CHECK(hipStreamCreateWithPriority(&outl, hipStreamNonBlocking, prSide));
-    outlQ[0] = outl;
-    for (uint32_t q = 1; q < kSubStreams; q++)
-      HIP_CHECK(hipStreamCreateWithPriority(&outlQ[q], hipStreamNonBlocking, prSide));
-    for (uint32_t q = 0; q < kSubStreams; q++)
-      HIP_CHECK(hipStreamCreateWithFlags(&sideQ[q], hipStreamNonBlocking));
-    for (uint32_t q = 0; q < kSubStreams; q++) {
-      HIP_CHECK(hipEventCreateWithFlags(&evOutl[q], hipEventDisableTiming));
-      HIP_CHECK(hipEventCreateWithFlags(&evOutlFork[q], hipEventDisableTiming));
-    }
-    HIP_CHECK(hipEventCreateWithFlags(&evPweFork, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&evPweJoin, hipEventDisableTiming));
-    for (uint32_t q = 0; q < kSubStreams; q++) {
-      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&liveHost[q]), kLiveSlots * sizeof(uint32_t), hipHostMallocDefault));
-      for (int k = 0; k < kLiveSlots; k++)
-        HIP_CHECK(hipEventCreateWithFlags(&liveEv[q][k], hipEventDisableTiming));
-    }
-    ready = true;
-    return 0;
-  }
-
-  // the device tables of at most kMaxPlans chunk shapes are kept (a ragged volume has 8 shapes)
-  static constexpr size_t kMaxPlans = 64;
-  // (dz = 0: the decoder's plan of a dx x dy slice, with the 2D coder's forest)
-  ShapePlan* plan(size_t dx, size_t dy, size_t dz)
-  {
-    const Dims key{dx, dy, dz};
-    auto it = plans.find(key);
-    if (it != plans.end()) {
-      auto pos = std::find(planOrder.begin(), planOrder.end(), key);
-      if (pos != planOrder.end())
-        planOrder.erase(pos);
-      planOrder.push_back(key);
-      return it->second.get();
-    }
-    auto p = std::make_unique<ShapePlan>();
-    if (dz == 0 ? build_plan(*p, dx, dy, 1, true) : build_plan(*p, dx, dy, dz))
-      return nullptr;
-    ShapePlan* raw = p.get();
-    plans[key] = std::move(p);
-    planOrder.push_back(key);
-    return raw;
-  }
-  // sperrhip_release(): everything an idle engine holds in HBM goes back (streams and events
-  // stay; the next call sizes the workspaces again).  The engine's device is current.
-  void drop_memory()
-  {
-    for (auto& kv : plans)
-      kv.second->tables.drop();
-    plans.clear();
-    planOrder.clear();
-    for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage})
-      b->drop();
-    for (auto& b : outlDec)
-      b.drop();
-    for (auto& b : decBox)
-      b.drop();
-    for (auto& b : pweBufs)
-      if (b)
-        b->drop();
-    pweBufs.clear();
-  }
-  // every device buffer of the engine: the arena, the containers' slots, and what point-wise error mode adds (the
-  // outlier coder's arrays, the boxes of the coarser levels, the outlier streams) and the staging buffers of the
-  // fields calls -- sperrhip_debug_counter(6)
-  size_t device_bytes() const
-  {
-    size_t n = 0;
-    for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage})
-      n += b->n;
-    for (const auto& b : outlDec)
-      n += b.n;
-    for (const auto& b : decBox)
-      n += b.n;
-    for (const auto& b : pweBufs)
-      if (b)
-        n += b->n;
-    return n;
-  }
-  // called between calls only (no kernel of this engine is in flight)
-  void trim_plans()
-  {
-    while (planOrder.size() > kMaxPlans) {
-      auto it = plans.find(planOrder.front());
-      if (it != plans.end()) {
-        if (it->second->tables.p)
-          (void)hipFree(it->second->tables.p);
-        plans.erase(it);
-      }
-      planOrder.erase(planOrder.begin());
-    }
-  }
-};
-
-struct EnginePool {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<std::unique_ptr<Engine>> all;
-
-  // an idle engine of the device current on this thread; nullptr: no device / initialisation failed
-  Engine* acquire()
-  {
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-      fprintf(stderr, "[sperr_hip] no HIP device available; this library has no CPU fallback\n");
-      return nullptr;
-    }
-    if (hipGetDevice(&dev) != hipSuccess)
-      return nullptr;
-    static const size_t perDev = getenv("SPERR_HIP_ENGINES_PER_DEVICE")
-                                     ? (size_t)std::max(1, atoi(getenv("SPERR_HIP_ENGINES_PER_DEVICE")))
-                                     : 4;
-    std::unique_lock<std::mutex> lock(mu);
-    for (;;) {
-      size_t have = 0;
-      for (auto& e : all)
-        if (e->dev == dev) {
-          have++;
-          if (!e->busy) {
-            e->busy = true;
-            return e.get();
-          }
-        }
-      if (have < perDev) {
-        auto e = std::make_unique<Engine>();
-        e->dev = dev;
-        e->busy = true;
-        Engine* raw = e.get();
-        all.push_back(std::move(e));
-        lock.unlock();
-        if (raw->init()) {
-          lock.lock();
-          raw->busy = false;
-          raw->dev = -1;   // never handed out again
-          cv.notify_all();
-          return nullptr;
-        }
-        return raw;
-      }
-      cv.wait(lock);
-    }
-  }
-  void release(Engine* e)
-  {
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      e->busy = false;
-    }
-    cv.notify_all();
-  }
-  // engines of a device that are on a call right now (the caller's own included)
-  size_t busy_on(int dev)
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    size_t n = 0;
-    for (auto& e : all)
-      n += (e->dev == dev && e->busy) ? 1 : 0;
-    return n;
-  }
-};
-
-EnginePool g_pool;
-
-// a call's hold on an engine; also makes the engine's profiler the calling thread's
-struct Lease {
-  Engine* e;
-  Lease() : e(g_pool.acquire())
-  {
-    if (e) {
-      std::lock_guard<std::mutex> lock(g_prof_cfg_mu);
-      e->prof.on = g_prof_on;
-      e->prof.only = g_prof_only;
-      t_prof = &e->prof;
-    }
-  }
-  ~Lease()
-  {
-    if (e) {
-      t_prof = nullptr;
-      e->trim_plans();
-      g_pool.release(e);
-    }
-  }
-  Lease(const Lease&) = delete;
-  Lease& operator=(const Lease&) = delete;
-};
+namespace {
 
 // How much workspace a call may use: 80 % of what is free plus what the engine already holds --
 // or SPERR_HIP_ARENA_MAX_MB when that is less (a soft cap: it bounds how many chunks of a batch
@@ -2147,6 +1625,8 @@ __global__ void k_slice_header(uint8_t* dst, const uint64_t* lens, const uint64_
   *total = pos + lens[0] + lens2[0];
 }
 
+}  // namespace
+
 // Work queued by a call that fails must not outlive the call: the caller's buffers and the engine's arena are
 // reused as soon as it returns.  A call (EncodeCall, DecodeCall) that did not end well waits for the caller's stream
 // and the engine's in its destructor, before its members -- the host buffers queued copies read and write -- go.
@@ -2160,6 +1640,8 @@ void drain_after_error(Engine& E, hipStream_t st)
   (void)hipGetLastError();
   E.pweLastStream = nullptr;
 }
+
+namespace {
 
 // The outlier stage of point-wise error mode on a reconstruction of the caller's: the batch is the nchunks chunks of
 // a volume (x, y, z * nchunks) cut along z, its chunk buffer holds d_recon, and from there on it is what compress runs
@@ -2224,13 +1706,6 @@ int outlier_encode_impl(Engine& E, hipStream_t st, const ShapePlan& P, const T* 
   E.prof.collect();
   return rtn;
 }
-
-// what a compression call makes: a 3D container, or one 2D slice without / with the 10-byte header
-enum class Coded { Container, Slice, SliceWithHeader };
-
-// How the kernels see a valid view (view.h) of a volume of dimz slices: their address is (z * rows + y) * pitch + x,
-// so the first two entries are pitches rather than extents; nothing on the device reads the third
-inline VolDesc view_desc(const ViewPitch& p, size_t dimz) { return VolDesc{{p.y, p.z / p.y, dimz}}; }
 
 // One compression call (compress_impl), stage by stage.  mode 1: fixed rate, `quality` bits per value; mode 2: fixed
 // PSNR and mode 3: fixed point-wise error, every bit plane is coded
@@ -2744,6 +2219,8 @@ void report_dec_error(uint32_t code)
     fprintf(stderr, "[sperr_hip] decoder: a chunk stream does not add up (damaged or truncated container)\n");
 }
 
+}  // namespace
+
 int read_container_info(const uint8_t* d_src, size_t src_len, ContainerInfo& ci, hipStream_t st)
 {
   std::vector<uint8_t> h(std::min<size_t>(src_len, 20));
@@ -2768,7 +2245,7 @@ int read_container_info(const uint8_t* d_src, size_t src_len, ContainerInfo& ci,
 // (or fewer) and zeros.  No container base is assumed aligned: the gathers read bytes
 int read_headers_at(Engine& E, const uint8_t* d_src, const std::vector<uint64_t>& off, const std::vector<uint64_t>& len,
                     std::vector<ContainerInfo>& ci, std::vector<uint8_t>& heads, hipStream_t st);
-int read_batch_headers(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, std::vector<ContainerInfo>& ci,
+static int read_batch_headers(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol, std::vector<ContainerInfo>& ci,
                        std::vector<uint8_t>& heads, hipStream_t st)
 {
   if (nvol == 0 || nvol > 0xffffffffull)
@@ -2950,8 +2427,7 @@ int trunc_impl(Engine& E, const uint8_t* d_src, const size_t* offs, size_t nvol,
   return 0;
 }
 
-bool g_lis_stamps_on = false;
-std::vector<uint64_t> g_lis_stamps_host;   // chunk 0 of the last decoded batch
+namespace {
 
 struct DecBatchBufs {
   DecBuffers db;
@@ -3171,15 +2647,7 @@ int reset_dec_pass(const DecBatchBufs& bb, uint32_t nb, bool wide, hipStream_t s
   return 0;
 }
 
-// multi-resolution decoding (SPERR3D_OMP_D::decompress(p, true), src/SPERR3D_OMP_D.cpp:50-150):
-// the volume at every coarsened resolution of the chunks (src/sperr_helper.cpp:70-123), coarsest
-// first.  Only for dyadic chunks that tile the volume.
-struct MultiRes {
-  size_t nlev = 0;
-  std::array<uint32_t, 3> cres[16];   // chunk resolution of level h
-  std::array<uint32_t, 3> grid;       // chunks per axis
-  double* d_level[16];
-};
+}  // namespace
 
 int multires_levels(const Dims& vol, const Dims& cdim, MultiRes& m)
 {
@@ -3210,6 +2678,8 @@ void multires_levels_2d(size_t dx, size_t dy, MultiRes& m)
   m.nlev = levels;
 }
 
+namespace {
+
 // the approximation corner of every chunk (src/CDF97.cpp:150-168,581-593), mean added back
 // (src/SPECK_FLT.cpp:592-603), placed at the chunk's position in the level's volume
 __global__ void __launch_bounds__(kThreads)
@@ -3231,54 +2701,6 @@ k_sub_volume(const double* vals, size_t valsStride, const CoderState* cst, const
     level[(((size_t)gi[2] * sz + z) * ldy + (size_t)gi[1] * sy + y) * ldx + (size_t)gi[0] * sx + x] = v;
   }
 }
-
-// A window of a call's output, [lo, lo + dims), and the chunks it meets (box_chunks, chunk_volume order).  Either a
-// box of the volume at full resolution (sperrhip_decompress_box_dev), or -- `level` -- a box of level h of the
-// hierarchy alone, coarsest first, in the level's coordinates (sperrhip_decompress_level_dev).  The level is the grid
-// of the chunks' corners of resolution cres[h], so the chunks its box meets are box_chunks of the level's dims with
-// cres[h] as the chunk size.  Or, with slotGeom, the output of a boxes call (boxes.h): many boxes of either kind, the
-// chunks of many containers
-struct Window {
-  Dims lo, dims;
-  std::vector<uint32_t> ids;
-  bool crop = false;    // the window is not all of what it is a window of (window_select)
-  bool level = false;   // of level h of m; otherwise of the volume
-  size_t h = 0;
-  MultiRes m;
-  // Boxes of a batch (boxes.h, sperrhip_decompress_boxes_dev): the window is the call's whole output -- nbox boxes back
-  // to back, or the staging array -- and every slot brings its own geometry, BoxesPlan::geom; lo is unused and `dims`
-  // the output's.  Empty: the one box [lo, lo + dims), each chunk placed by place() + crop_geom()
-  std::vector<CropGeom> slotGeom;
-  // what the chunk of slot `slot`, at `org` with dims `cd`, writes of the window, and where
-  CropGeom geom_of(uint32_t slot, const uint32_t org[3], const uint32_t cd[3]) const
-  {
-    if (!slotGeom.empty())
-      return slotGeom[slot];
-    size_t o[3], ext[3];
-    place(org, cd, o, ext);
-    return crop_geom(o, ext);
-  }
-  // the chunk at `org` of dims `cd`, in the coordinates the window is given in: its origin and extent
-  void place(const uint32_t org[3], const uint32_t cd[3], size_t o[3], size_t ext[3]) const
-  {
-    for (int a = 0; a < 3; a++) {
-      ext[a] = level ? m.cres[h][a] : cd[a];
-      o[a] = level ? org[a] / cd[a] * ext[a] : org[a];
-    }
-  }
-  // what a chunk at `o` of extent `ext` (both as place() gives them) writes of the window, and where
-  CropGeom crop_geom(const size_t o[3], const size_t ext[3]) const
-  {
-    CropGeom g;
-    for (int a = 0; a < 3; a++) {
-      const size_t hi = lo[a] + dims[a];
-      g.rel[a] = (int32_t)((int64_t)o[a] - (int64_t)lo[a]);
-      g.lo[a] = (uint32_t)(lo[a] > o[a] ? lo[a] - o[a] : 0);
-      g.hi[a] = (uint32_t)std::min<size_t>(hi - o[a], ext[a]);
-    }
-    return g;
-  }
-};
 
 // The window [lo, lo + dims) of `full`, which chunks of `chunk` tile: false when it is empty, leaves `full`, or is too
 // long along an axis for a chunk's origin relative to it (CropGeom::rel).  One that is all of `full` crops nothing
@@ -3371,90 +2793,6 @@ k_level_write(const double* vals, size_t valsStride, const CoderState* cst, cons
   const double v = cs.is_const ? cs.mean : vals[c * valsStride + ((size_t)z * by + y) * bx + x] + cs.mean;
   out[o] = (OT)v;
 }
-
-// What one decompression call decodes, and what it writes: everything DecodeCall needs to know beside the container
-// `ci` and the buffers.  The two halves are independent but for the pairs valid() excludes
-struct DecodeRequest {
-  using ChunkList = std::vector<std::array<size_t, 6>>;
-  // ---- the source: where the chunks come from
-  // a batch (sperrhip_decompress_batch_dev): the chunks of every container, z origins shifted into the stacked view
-  // that `ci` describes -- the volume (x, y, nvol z) and every chunk's absolute offset and length (null: the chunks
-  // of the one container, chunk_volume)
-  const ChunkList* stacked = nullptr;
-  // the chunks are slices, decoded on the 2D coder's forest: `ci` describes one chunk of dims (x, y, 1) whose stream
-  // starts at d_src, or with `stacked` a batch of them, chunk s of dims (x, y, 1) at (0, 0, s)
-  bool slices = false;
-  // a batch of slices whose streams carry the 10-byte header (sperrhip_decompress_2d_batch_dev): ci.off points behind
-  // each header; {dimx, dimy} that every header has to name (null: no headers)
-  const uint32_t* sliceHdr = nullptr;
-  // ---- the output: what d_dst receives
-  // null: the whole volume.  A box of it: only the chunks the box meets are read and decoded, and d_dst is the box.
-  // One level alone or a box of it: the same, the inverse passes stop at the level and no outlier stream is looked at
-  const Window* window = nullptr;
-  // beside the volume, every level of the hierarchy into levels->d_level (sperrhip_decompress_multires_dev)
-  const MultiRes* levels = nullptr;
-  // d_dst is the first element of a strided view (view.h; valid for the output's dims) of a larger array: the volume
-  // or the box goes there, and nothing outside the view is written (sperrhip_decompress_view_dev).  null: dense
-  const ViewPitch* outView = nullptr;
-
-  // (a box that is the whole volume is no window: such a call is the whole-volume decode)
-  void set_window(const Window& w) { window = (w.level || w.crop) ? &w : nullptr; }
-
-  // every combination of source and output the decoder refuses
-  bool valid() const
-  {
-    if (window && slices)   // a window is cut along a container's chunk grid; a slice is one chunk
-      return false;
-    if (window && levels)   // the side outputs are whole levels: a box reads only some chunks, a level stops before the rest
-      return false;
-    if (stacked && levels)   // the stacked view is no volume with a hierarchy: each container has its own
-      return false;
-    if (level() && stacked && window->slotGeom.empty())   // a level's grid of chunk corners is one container's: only the
-      return false;                                        //   boxes call, whose slots bring their geometry, has many
-    if (window && !window->slotGeom.empty() && (!stacked || window->slotGeom.size() != window->ids.size()))
-      return false;   // per-slot geometry is the boxes call's, one record per chunk of its list
-    if (level() && level()->h >= level()->m.nlev)   // the container has no such level
-      return false;
-    if (outView && (stacked || slices || levels || level()))   // a view holds one volume or a box of it at full resolution
-      return false;
-    return true;
-  }
-
-  // the level the inverse stops at (null: it runs to full resolution)
-  const Window* level() const { return window && window->level ? window : nullptr; }
-  // the chunks' windows travel to the device (DecBatchBufs::crop, the kCrop writers)
-  bool cropped() const { return window && window->crop; }
-  // (a level is taken before the outlier correctors are added, src/SPECK_FLT.cpp:568-603: no stream of them is read)
-  bool reads_outliers() const { return !level(); }
-  ChunkList chunks(const ContainerInfo& ci) const { return stacked ? *stacked : chunk_volume(ci.vol, ci.chunk); }
-  // The chunks of the call, slot by slot: slot i is chunk sel[i] of chunks() (all of them in order, or the window's)
-  std::vector<uint32_t> slots(size_t nchunks) const
-  {
-    if (window)
-      return window->ids;
-    std::vector<uint32_t> sel(nchunks);
-    std::iota(sel.begin(), sel.end(), 0u);
-    return sel;
-  }
-  // the output: the volume, or the window (its chunks write their pieces of it)
-  // (the non-crop writers place a chunk by its origin in the volume, the crop writers by its origin relative to the
-  //  box: with a view only the pitches differ)
-  VolDesc out_desc(const ContainerInfo& ci) const
-  {
-    const Dims& d = window ? window->dims : ci.vol;
-    return outView ? view_desc(*outView, d[2]) : VolDesc{{d[0], d[1], d[2]}};
-  }
-  // values d_dst has to hold: the output's, or with a view its extent (0: the view is not valid for the output)
-  size_t out_vals(const ContainerInfo& ci) const
-  {
-    if (outView) {
-      const Dims& d = window ? window->dims : ci.vol;
-      size_t e = 0;
-      return view_extent(d[0], d[1], d[2], *outView, &e) ? e : 0;
-    }
-    return window ? window->dims[0] * window->dims[1] * window->dims[2] : ci.nvals;
-  }
-};
 
 // bytes carve_dec takes for one chunk
 size_t dec_bytes_per_chunk(const ShapePlan& P, uint64_t maxPayload, size_t valsElems, uint32_t refNPlanes, bool crop,
@@ -4449,7 +3787,7 @@ int decode_to(Engine& E, const void* d_src, int output_float, void* d_dst, size_
 
 // the window `w` of it, once d_dst is seen to hold the window
 int decode_window(Engine& E, const void* d_src, int output_float, void* d_dst, size_t dst_cap_bytes,
-                  const ContainerInfo& ci, hipStream_t st, const Window& w, const ViewPitch* outView = nullptr)
+                  const ContainerInfo& ci, hipStream_t st, const Window& w, const ViewPitch* outView)
 {
   const size_t esz = output_float ? sizeof(float) : sizeof(double);
   if (outView ? !view_fits(w.dims[0], w.dims[1], w.dims[2], *outView, esz, dst_cap_bytes)
@@ -4461,1757 +3799,136 @@ int decode_window(Engine& E, const void* d_src, int output_float, void* d_dst, s
   return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, ci, st, req);
 }
 
-// The host entry points of a sub-box and of a level: the streams of the chunks `ids` of the host container at `h`
-// travel to the calling thread's device packed, in their order (one copy per run of chunks that lie back to back in
-// the container), `decode` runs the device path on that buffer -- `packed` is `ci` with those chunks' offsets
-// pointing into it -- and the result comes back in one copy, into a malloc'd buffer
-template <typename F>
-int decode_packed_host(const uint8_t* h, const ContainerInfo& ci, const std::vector<uint32_t>& ids, size_t outBytes,
-                       void** dst, F&& decode)
+// ------------------------------------------------------------------------------------------
+// the front (engine_core.h): the element type is chosen here, no template leaves this unit
+// ------------------------------------------------------------------------------------------
+int compress_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, int mode,
+                double quality, uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st, Coded what,
+                const ViewPitch* srcView)
 {
-  ContainerInfo packed = ci;
-  size_t total = 0;
-  for (uint32_t id : ids) {
-    packed.off[id] = total;
-    total += ci.len[id];
-  }
-  void *d_in = nullptr, *d_out = nullptr;
-  auto release = [&]() {
-    if (d_in)
-      (void)hipFree(d_in);
-    if (d_out)
-      (void)hipFree(d_out);
-  };
-  if (hipMalloc(&d_in, std::max<size_t>(total, 1)) != hipSuccess || hipMalloc(&d_out, outBytes) != hipSuccess) {
-    (void)hipGetLastError();
-    fprintf(stderr, "[sperr_hip] device allocation failed\n");
-    release();
+  return with_elem(is_float, [&](auto t) {
+    return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, chunkPref, mode, quality, d_dst, dst_cap,
+                         dst_len, st, what, srcView);
+  });
+}
+
+int compress_batch_to(Engine& E, const void* d_src, int is_float, size_t nvol, const Dims& vol, const Dims& chunkPref,
+                      int mode, double quality, uint8_t* d_dst, size_t dst_cap, size_t* offsets, hipStream_t st,
+                      Coded what)
+{
+  return with_elem(is_float, [&](auto t) {
+    return compress_batch_impl(E, static_cast<const decltype(t)*>(d_src), nvol, vol, chunkPref, mode, quality, d_dst,
+                               dst_cap, offsets, st, what);
+  });
+}
+
+int outlier_encode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_orig, int is_float,
+                         const double* d_recon, uint32_t nb, double tol, uint8_t* d_dst, size_t dst_cap, size_t* lens)
+{
+  return with_elem(is_float, [&](auto t) {
+    return outlier_encode_impl(E, st, P, static_cast<const decltype(t)*>(d_orig), d_recon, nb, tol, d_dst, dst_cap, lens);
+  });
+}
+
+int speck3d_encode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_coef, bool wide,
+                         const uint64_t* d_sign, uint64_t raw_budget, uint8_t* d_dst, size_t dst_cap, size_t* dst_len)
+{
+  if (E.arena.ensure(enc_bytes_per_chunk(P, raw_budget) + 4096) || E.misc.ensure(4096))
     return -1;
-  }
-  int rtn = 0;
-  for (size_t i = 0; rtn == 0 && i < ids.size();) {
-    size_t j = i + 1;
-    while (j < ids.size() && ci.off[ids[j]] == ci.off[ids[j - 1]] + ci.len[ids[j - 1]])
-      j++;
-    const size_t bytes = ci.off[ids[j - 1]] + ci.len[ids[j - 1]] - ci.off[ids[i]];
-    if (bytes && hipMemcpy(static_cast<uint8_t*>(d_in) + packed.off[ids[i]], h + ci.off[ids[i]], bytes,
-                           hipMemcpyHostToDevice) != hipSuccess)
-      rtn = -1;
-    i = j;
-  }
-  if (rtn == 0) {
-    Lease L;
-    rtn = L.e ? decode(*L.e, d_in, packed, d_out) : -1;
-  }
-  if (rtn == 0) {
-    void* buf = malloc(outBytes);
-    if (buf && hipMemcpy(buf, d_out, outBytes, hipMemcpyDeviceToHost) == hipSuccess)
-      *dst = buf;
-    else {
-      free(buf);
-      rtn = -1;
-    }
-  }
-  release();
-  return rtn;
-}
-
-// The host entry points of the hierarchy, the same way: the stream at `src` travels to the calling thread's device,
-// `decode` runs the device call on it -- d_out takes the outBytes of the volume (the slice), d_lv[h] the lvn[h]
-// doubles of level h -- and the volume and every level come back into malloc'd buffers
-template <typename F>
-int decode_multires_host(const void* src, size_t src_len, size_t outBytes, const std::vector<size_t>& lvn, void** dst,
-                         double** levels, F&& decode)
-{
-  std::vector<void*> dev;
-  auto release = [&]() {
-    for (void* p : dev)
-      (void)hipFree(p);
-  };
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess)
-      return nullptr;
-    dev.push_back(p);
-    return p;
-  };
-  void* d_in = dalloc(src_len);
-  void* d_out = dalloc(outBytes);
-  std::vector<double*> d_lv(lvn.size(), nullptr);
-  bool ok = d_in && d_out;
-  for (size_t h = 0; ok && h < lvn.size(); h++) {
-    d_lv[h] = static_cast<double*>(dalloc(lvn[h] * 8));
-    ok = d_lv[h] != nullptr;
-  }
-  if (!ok) {
-    fprintf(stderr, "[sperr_hip] device allocation failed\n");
-    release();
+  Arena A;
+  A.base = static_cast<char*>(E.arena.p);
+  A.cap = E.arena.n;
+  EncBatchBufs bb;
+  if (!carve_enc(A, P, 1, raw_budget, bb))
     return -1;
-  }
-  int rtn = -1;
-  if (hipMemcpy(d_in, src, src_len, hipMemcpyHostToDevice) == hipSuccess)
-    rtn = decode(d_in, d_out, d_lv.data());
-  if (rtn == 0) {
-    void* buf = malloc(outBytes);
-    if (buf && hipMemcpy(buf, d_out, outBytes, hipMemcpyDeviceToHost) == hipSuccess)
-      *dst = buf;
-    else {
-      free(buf);
-      rtn = -1;
-    }
-    for (size_t h = 0; rtn == 0 && h < lvn.size(); h++) {
-      levels[h] = static_cast<double*>(malloc(lvn[h] * 8));
-      if (!levels[h] || hipMemcpy(levels[h], d_lv[h], lvn[h] * 8, hipMemcpyDeviceToHost) != hipSuccess)
-        rtn = -1;
-    }
-  }
-  release();
-  return rtn;
-}
-
-}  // namespace sperrhip
-
-// ==========================================================================================
-// C ABI
-// ==========================================================================================
-using namespace sperrhip;
-
-// nothing thrown by the host side (std::bad_alloc of a vector, std::system_error of a thread)
-// may cross the C boundary
-template <typename F>
-static int guarded(const char* what, F&& body) noexcept
-{
-  try {
-    return body();
-  }
-  catch (const std::bad_alloc&) {
-    fprintf(stderr, "[sperr_hip] %s: out of host memory\n", what);
-  }
-  catch (const std::exception& e) {
-    fprintf(stderr, "[sperr_hip] %s: %s\n", what, e.what());
-  }
-  catch (...) {
-    fprintf(stderr, "[sperr_hip] %s: unknown exception\n", what);
-  }
-  return -1;
-}
-
-// what the device decode entry points begin with: an engine leased, the caller's stream, the container's header read
-struct DevDecode {
-  Lease L;
-  hipStream_t st;
-  ContainerInfo ci;
-  const bool ok;
-  DevDecode(const void* d_src, size_t src_len, void* hip_stream)
-      : st(static_cast<hipStream_t>(hip_stream)),
-        ok(L.e && read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st) == 0)
-  {
-  }
-};
-
-// a slice's stream (without the 10-byte header) described as a container of one chunk
-static ContainerInfo one_slice_info(size_t dimx, size_t dimy, size_t src_len, int output_float)
-{
-  ContainerInfo ci;
-  ci.vol = {dimx, dimy, 1};
-  ci.nvals = dimx * dimy;
-  ci.chunk = ci.vol;
-  ci.is_float = output_float != 0;
-  ci.off = {0};
-  ci.len = {src_len};
-  return ci;
-}
-
-extern "C" {
-
-// Gives back what the library keeps between calls: the workspaces and shape tables of every idle
-// engine, the staging and device buffers of every idle farm worker, the calling thread's slice
-// buffers.  Engines and workers in use by other threads are left alone.  For hosts that embed the
-// library (an HDF5 filter, a long-running service) and call it rarely.
-static void thread_slice_bufs_drop();
-void sperrhip_release(void)
-{
-  (void)guarded("sperrhip_release", [&]() -> int {
-    int cur = 0;
-    const bool have = hipGetDevice(&cur) == hipSuccess;
-    // The idle engines are picked (and marked busy, so nobody leases them) under the pool's lock;
-    // their memory goes with the lock released.  `all` may grow meanwhile (acquire() on another
-    // thread): only the raw pointers collected here are used, the engines themselves never move.
-    std::vector<Engine*> idle;
-    {
-      std::lock_guard<std::mutex> lock(g_pool.mu);
-      idle.reserve(g_pool.all.size());
-      for (auto& e : g_pool.all)
-        if (!e->busy && e->dev >= 0) {
-          e->busy = true;
-          idle.push_back(e.get());
-        }
-    }
-    for (Engine* e : idle)
-      if (hipSetDevice(e->dev) == hipSuccess)
-        e->drop_memory();
-    {
-      std::lock_guard<std::mutex> lock(g_pool.mu);
-      for (Engine* e : idle)
-        e->busy = false;
-    }
-    g_pool.cv.notify_all();
-    farm_release_idle();
-    if (have)
-      (void)hipSetDevice(cur);
-    thread_slice_bufs_drop();
-    return 0;
-  });
-}
-
-const char* sperrhip_version(void)
-{
-  return "sperr_hip 0.1 (gfx950; SPERR bitstream major version 0)";
-}
-
-void sperrhip_profile_enable(int on)
-{
-  std::lock_guard<std::mutex> lock(g_prof_cfg_mu);
-  g_prof_on = on != 0;
-}
-void sperrhip_profile_only(const char* kernel)
-{
-  std::lock_guard<std::mutex> lock(g_prof_cfg_mu);
-  g_prof_only = kernel ? kernel : "";
-}
-unsigned long long sperrhip_debug_counter(int which)
-{
-  if (which == 3) {   // bytes of the largest workspace arena an engine of this process holds
-    std::lock_guard<std::mutex> lock(g_pool.mu);
-    size_t most = 0;
-    for (auto& e : g_pool.all)
-      most = std::max(most, e->arena.n);
-    return (unsigned long long)most;
-  }
-  if (which == 6) {   // bytes of ALL device buffers of the engine that holds most (arena + slots + the PWE buffers)
-    std::lock_guard<std::mutex> lock(g_pool.mu);
-    size_t most = 0;
-    for (auto& e : g_pool.all)
-      most = std::max(most, e->device_bytes());
-    return (unsigned long long)most;
-  }
-  if (which == 4 || which == 5)   // pinned staging / device bytes the farm's workers hold right now
-    return farm_footprint(which == 4);
-  if (which == 7)   // batches whose 32-bit pass took the fused encoder head (k_head_fused)
-    return g_dbg_counter[3].load();
-  return which >= 0 && which < 3 ? g_dbg_counter[which].load() : 0ull;
-}
-void sperrhip_debug_lis_stamps(int on, unsigned long long* out64)
-{
-  g_lis_stamps_on = on != 0;
-  if (out64)
-    for (size_t i = 0; i < 64; i++)
-      out64[i] = i < g_lis_stamps_host.size() ? g_lis_stamps_host[i] : 0;
-}
-void sperrhip_profile_reset(void)
-{
-  std::lock_guard<std::mutex> lock(g_pool.mu);
-  for (auto& e : g_pool.all) {
-    std::lock_guard<std::mutex> l2(e->prof.mu);
-    e->prof.acc.clear();
-  }
-}
-int sperrhip_profile_get(const char** names, double* millis, int* launches, int cap)
-{
-  return guarded("sperrhip_profile_get", [&]() -> int {
-    return sperrhip_profile_get2(names, millis, nullptr, launches, cap);
-  });
-}
-int sperrhip_profile_get2(const char** names, double* busy_millis, double* sum_millis, int* launches,
-                          int cap)
-{
-  return guarded("sperrhip_profile_get2", [&]() -> int {
-    // the engines' tables merged; the names stay valid until the next call
-    static std::mutex mu;
-    static std::map<std::string, ProfEntry> merged;
-    std::lock_guard<std::mutex> lock(mu);
-    merged.clear();
-    {
-      std::lock_guard<std::mutex> lp(g_pool.mu);
-      for (auto& e : g_pool.all) {
-        std::lock_guard<std::mutex> l2(e->prof.mu);
-        for (auto& kv : e->prof.acc) {
-          ProfEntry& m = merged[kv.first];
-          m.ms += kv.second.ms;
-          m.busy += kv.second.busy;
-          m.launches += kv.second.launches;
-        }
-      }
-    }
-    int i = 0;
-    for (auto& kv : merged) {
-      if (i < cap) {
-        names[i] = kv.first.c_str();
-        busy_millis[i] = kv.second.busy;
-        if (sum_millis)
-          sum_millis[i] = kv.second.ms;
-        launches[i] = kv.second.launches;
-      }
-      i++;
-    }
-    return i;
-  });
-}
-
-size_t sperrhip_max_compressed_size(size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
-                                    size_t chunk_y, size_t chunk_z, int mode, double quality)
-{
-  const Dims vol{dimx, dimy, dimz};
-  Dims cd{chunk_x, chunk_y, chunk_z};
-  for (int a = 0; a < 3; a++)
-    cd[a] = std::min(std::max<size_t>(1, cd[a]), vol[a]);
-  const auto chunks = chunk_volume(vol, cd);
-  size_t total = 20 + 4 * chunks.size();
-  for (auto& c : chunks)
-    total += host_chunk_stream_bound(c[1] * c[3] * c[5], mode, quality);
-  return total;
-}
-
-int sperrhip_compress_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz,
-                          size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
-                          void* d_dst, size_t dst_cap, size_t* dst_len, void* hip_stream)
-{
-  return guarded("sperrhip_compress_dev", [&]() -> int {
-    if (quality <= 0.0)
-      return 2;
-    if (mode < 1 || mode > 3)
-      return 2;
-    if (!d_src || !d_dst || !dst_len || dimx == 0 || dimy == 0 || dimz == 0)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return with_elem(is_float, [&](auto t) {
-      return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, ch, mode, quality,
-                           static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st);
-    });
-  });
-}
-
-int sperrhip_compress_view_dev(const void* d_src, const sperrhip_view* view, int is_float, size_t dimx, size_t dimy,
-                               size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
-                               void* d_dst, size_t dst_cap, size_t* dst_len, void* hip_stream)
-{
-  return guarded("sperrhip_compress_view_dev", [&]() -> int {
-    if (quality <= 0.0)
-      return 2;
-    if (mode < 1 || mode > 3)
-      return 2;
-    if (!d_src || !view || !d_dst || !dst_len)
-      return -1;
-    const ViewPitch pitch{view->pitch_y, view->pitch_z};
-    if (!view_valid(dimx, dimy, dimz, pitch))
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return with_elem(is_float, [&](auto t) {
-      return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, ch, mode, quality,
-                           static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st, Coded::Container, &pitch);
-    });
-  });
-}
-
-int sperrhip_parse_header_dev(const void* d_src, size_t src_len, size_t* dimx, size_t* dimy,
-                              size_t* dimz, int* is_float, size_t* chunk_x, size_t* chunk_y,
-                              size_t* chunk_z)
-{
-  return guarded("sperrhip_parse_header_dev", [&]() -> int {
-    DevDecode d(d_src, src_len, nullptr);
-    if (!d.ok)
-      return -1;
-    const ContainerInfo& ci = d.ci;
-    *dimx = ci.vol[0];
-    *dimy = ci.vol[1];
-    *dimz = ci.vol[2];
-    *is_float = ci.is_float ? 1 : 0;
-    if (chunk_x)
-      *chunk_x = ci.chunk[0];
-    if (chunk_y)
-      *chunk_y = ci.chunk[1];
-    if (chunk_z)
-      *chunk_z = ci.chunk[2];
-    return 0;
-  });
-}
-
-int sperrhip_decompress_dev(const void* d_src, size_t src_len, int output_float, void* d_dst,
-                            size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
-                            void* hip_stream)
-{
-  return guarded("sperrhip_decompress_dev", [&]() -> int {
-    if (!d_src || !d_dst)
-      return -1;
-    DevDecode d(d_src, src_len, hip_stream);
-    if (!d.ok)
-      return -1;
-    if (dimx)
-      *dimx = d.ci.vol[0];
-    if (dimy)
-      *dimy = d.ci.vol[1];
-    if (dimz)
-      *dimz = d.ci.vol[2];
-    return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, DecodeRequest{});
-  });
-}
-
-size_t sperrhip_max_compressed_size_batch(size_t nvol, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
-                                          size_t chunk_y, size_t chunk_z, int mode, double quality)
-{
-  const size_t one = sperrhip_max_compressed_size(dimx, dimy, dimz, chunk_x, chunk_y, chunk_z, mode, quality);
-  if (nvol != 0 && one > SIZE_MAX / nvol)
-    return 0;
-  return nvol * one;
-}
-
-int sperrhip_compress_batch_dev(const void* d_src, int is_float, size_t nvol, size_t dimx, size_t dimy, size_t dimz,
-                                size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
-                                void* d_dst, size_t dst_cap, size_t* offsets, void* hip_stream)
-{
-  return guarded("sperrhip_compress_batch_dev", [&]() -> int {
-    if (quality <= 0.0)
-      return 2;
-    if (mode < 1 || mode > 3)
-      return 2;
-    if (!d_src || !d_dst || !offsets || nvol == 0 || dimx == 0 || dimy == 0 || dimz == 0)
-      return -1;
-    if (nvol > 0xffffffffull / dimz)   // (chunk origins of the stacked view are 32-bit)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return with_elem(is_float, [&](auto t) {
-      return compress_batch_impl(E, static_cast<const decltype(t)*>(d_src), nvol, vol, ch, mode, quality,
-                                 static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
-    });
-  });
-}
-
-int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, int output_float,
-                                  void* d_dst, size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
-                                  void* hip_stream)
-{
-  return guarded("sperrhip_decompress_batch_dev", [&]() -> int {
-    if (!d_src || !offsets || !d_dst || nvol == 0)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const uint8_t* src = static_cast<const uint8_t*>(d_src);
-    ContainerInfo all;
-    std::vector<std::array<size_t, 6>> list;
-    if (read_batch_info(E, src, offsets, nvol, all, list, st))
-      return -1;
-    if (all.nvals > dst_cap_bytes / (output_float ? sizeof(float) : sizeof(double)))
-      return -1;
-    if (dimx)
-      *dimx = all.vol[0];
-    if (dimy)
-      *dimy = all.vol[1];
-    if (dimz)
-      *dimz = all.vol[2] / nvol;
-    DecodeRequest req;
-    req.stacked = &list;
-    return decode_to(E, src, output_float, d_dst, dst_cap_bytes, all, st, req);
-  });
-}
-
-int sperrhip_box_chunks(size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y,
-                        size_t chunk_z, const size_t box_lo[3], const size_t box_dims[3], uint32_t* ids,
-                        size_t cap, size_t* count)
-{
-  return guarded("sperrhip_box_chunks", [&]() -> int {
-    if (!box_lo || !box_dims || !count)
-      return -1;
-    std::vector<uint32_t> v;
-    if (!box_chunks(Dims{dimx, dimy, dimz}, Dims{chunk_x, chunk_y, chunk_z}, Dims{box_lo[0], box_lo[1], box_lo[2]},
-                    Dims{box_dims[0], box_dims[1], box_dims[2]}, v))
-      return -1;
-    *count = v.size();
-    if (!ids || cap < v.size())
-      return 1;
-    memcpy(ids, v.data(), v.size() * sizeof(uint32_t));
-    return 0;
-  });
-}
-
-int sperrhip_decompress_box_dev(const void* d_src, size_t src_len, int output_float, const size_t box_lo[3],
-                                const size_t box_dims[3], void* d_dst, size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_box_dev", [&]() -> int {
-    if (!d_src || !d_dst || !box_lo || !box_dims)
-      return -1;
-    DevDecode d(d_src, src_len, hip_stream);
-    Window w;
-    if (!d.ok || box_select(d.ci, box_lo, box_dims, w))
-      return -1;
-    return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w);
-  });
-}
-
-int sperrhip_decompress_level_dev(const void* d_src, size_t src_len, int output_float, size_t level,
-                                  const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
-                                  size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_level_dev", [&]() -> int {
-    if (!d_src || !d_dst)
-      return -1;
-    DevDecode d(d_src, src_len, hip_stream);
-    Window w;
-    if (!d.ok || level_select(d.ci, level, box_lo, box_dims, w))
-      return -1;
-    return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w);
-  });
-}
-
-int sperrhip_multires_levels(size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y,
-                             size_t chunk_z, size_t* nlev, size_t* level_dims)
-{
-  return guarded("sperrhip_multires_levels", [&]() -> int {
-    const Dims vol{dimx, dimy, dimz};
-    Dims cd{chunk_x, chunk_y, chunk_z};
-    if (!nlev || dimx == 0 || dimy == 0 || dimz == 0)
-      return -1;
-    for (int a = 0; a < 3; a++)
-      cd[a] = std::min(std::max<size_t>(1, cd[a]), vol[a]);
-    MultiRes m;
-    multires_levels(vol, cd, m);
-    *nlev = m.nlev;
-    if (level_dims)
-      for (size_t h = 0; h < m.nlev; h++)
-        for (int a = 0; a < 3; a++)
-          level_dims[3 * h + a] = (size_t)m.cres[h][a] * m.grid[a];
-    return 0;
-  });
-}
-
-int sperrhip_decompress_multires_dev(const void* d_src, size_t src_len, int output_float,
-                                     void* d_dst, size_t dst_cap_bytes, size_t nlev,
-                                     double* const* d_levels, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_multires_dev", [&]() -> int {
-    if (!d_src || !d_dst || (nlev && !d_levels))
-      return -1;
-    DevDecode d(d_src, src_len, hip_stream);
-    if (!d.ok)
-      return -1;
-    MultiRes m;
-    multires_levels(d.ci.vol, d.ci.chunk, m);
-    if (m.nlev != nlev)
-      return -1;   // (sperrhip_multires_levels tells how many there are)
-    for (size_t h = 0; h < nlev; h++) {
-      if (!d_levels[h])
-        return -1;
-      m.d_level[h] = d_levels[h];
-    }
-    DecodeRequest req;
-    req.levels = &m;
-    return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, req);
-  });
-}
-
-// What a host thread that codes slices keeps: a stream of its own (calls of several threads then run
-// side by side; on the null stream they would queue behind each other) and two device buffers that
-// only grow (hipMalloc / hipFree per call would synchronise the device; the stream-ordered allocator
-// handed out blocks whose contents the next call did not see: not used).  Freed with the thread.
-struct ThreadSliceBufs {
-  int dev = -1;          // the device the stream and the buffers belong to
-  hipStream_t s = nullptr;
-  void* p[2] = {nullptr, nullptr};
-  size_t cap[2] = {0, 0};
-  hipStream_t stream()
-  {
-    if (!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
-      s = nullptr;
-    return s;
-  }
-  void* get(int i, size_t bytes)
-  {
-    if (bytes > cap[i]) {
-      if (p[i])
-        (void)hipFree(p[i]);
-      p[i] = nullptr;
-      cap[i] = 0;
-      if (hipMalloc(&p[i], round_up(bytes, 1 << 20)) != hipSuccess)
-        return nullptr;
-      cap[i] = round_up(bytes, 1 << 20);
-    }
-    return p[i];
-  }
-  void drop()
-  {
-    for (int i = 0; i < 2; i++) {
-      if (p[i])
-        (void)hipFree(p[i]);
-      p[i] = nullptr;
-      cap[i] = 0;
-    }
-    if (s)
-      (void)hipStreamDestroy(s);
-    s = nullptr;
-  }
-};
-// One set per device the thread has coded slices on: a thread that moves to another device
-// (hipSetDevice between two calls) leases an engine of THAT device, whose arena, sub-streams and
-// events must not meet a stream or buffers of the device it came from.
-struct ThreadSliceCache {
-  std::vector<ThreadSliceBufs> sets;
-  ThreadSliceBufs& of_current_device()
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-      dev = 0;
-    for (auto& b : sets)
-      if (b.dev == dev)
-        return b;
-    sets.emplace_back();
-    sets.back().dev = dev;
-    return sets.back();
-  }
-  ~ThreadSliceCache()
-  {
-    int cur = 0;
-    const bool have = hipGetDevice(&cur) == hipSuccess;
-    for (auto& b : sets) {
-      if (have && b.dev != cur)
-        (void)hipSetDevice(b.dev);
-      b.drop();
-    }
-    if (have)
-      (void)hipSetDevice(cur);
-  }
-};
-static ThreadSliceCache& thread_slice_cache()
-{
-  static thread_local ThreadSliceCache t;
-  return t;
-}
-static ThreadSliceBufs& thread_slice_bufs()
-{
-  return thread_slice_cache().of_current_device();
-}
-static void thread_slice_bufs_drop()
-{
-  ThreadSliceCache& c = thread_slice_cache();
-  int cur = 0;
-  const bool have = hipGetDevice(&cur) == hipSuccess;
-  for (auto& b : c.sets) {
-    if (have && b.dev != cur)
-      (void)hipSetDevice(b.dev);
-    if (b.s)
-      (void)hipStreamSynchronize(b.s);
-    b.drop();
-  }
-  c.sets.clear();
-  if (have)
-    (void)hipSetDevice(cur);
-}
-
-// ---- 2D slices (include/SPERR_C_API.h:53-81, src/SPERR_C_API.cpp:7-134) ------------------------
-size_t sperrhip_max_compressed_size_2d(size_t dimx, size_t dimy, int mode, double quality)
-{
-  return 10 + sperrhip_max_compressed_size(dimx, dimy, 1, dimx, dimy, 1, mode, quality);
-}
-
-int sperrhip_compress_2d_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, int mode,
-                             double quality, int out_inc_header, void* d_dst, size_t dst_cap,
-                             size_t* dst_len, void* hip_stream)
-{
-  return guarded("sperrhip_compress_2d_dev", [&]() -> int {
-    if (quality <= 0.0)
-      return 2;
-    if (mode < 1 || mode > 3)
-      return 2;
-    if (!d_src || !d_dst || !dst_len || dimx == 0 || dimy == 0)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    const Dims vol{dimx, dimy, 1};
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const Coded what = out_inc_header ? Coded::SliceWithHeader : Coded::Slice;
-    return with_elem(is_float, [&](auto t) {
-      return compress_impl(E, static_cast<const decltype(t)*>(d_src), vol, vol, mode, quality,
-                           static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st, what);
-    });
-  });
-}
-
-// d_src: the stream WITHOUT the optional 10-byte header, as sperr_decomp_2d takes it
-int sperrhip_decompress_2d_dev(const void* d_src, size_t src_len, int output_float, size_t dimx,
-                               size_t dimy, void* d_dst, size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_2d_dev", [&]() -> int {
-    if (!d_src || !d_dst || dimx == 0 || dimy == 0 || src_len < 17)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    DecodeRequest req;
-    req.slices = true;
-    return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, one_slice_info(dimx, dimy, src_len, output_float),
-                     st, req);
-  });
-}
-
-// ---- a batch of same-shape slices (the stacked view of DESIGN.md section 0c: N slices read as one volume of
-// (x, y, N) whose chunk s is slice s, one shape group on the 2D coder's forest) ------------------------------------
-size_t sperrhip_max_compressed_size_2d_batch(size_t nslice, size_t dimx, size_t dimy, int mode, double quality)
-{
-  const size_t one = sperrhip_max_compressed_size_2d(dimx, dimy, mode, quality);
-  if (nslice != 0 && one > SIZE_MAX / nslice)
-    return 0;
-  return nslice * one;
-}
-
-int sperrhip_compress_2d_batch_dev(const void* d_src, int is_float, size_t nslice, size_t dimx, size_t dimy,
-                                   int mode, double quality, int out_inc_header,
-                                   void* d_dst, size_t dst_cap, size_t* offsets, void* hip_stream)
-{
-  return guarded("sperrhip_compress_2d_batch_dev", [&]() -> int {
-    if (quality <= 0.0)
-      return 2;
-    if (mode < 1 || mode > 3)
-      return 2;
-    if (!d_src || !d_dst || !offsets || nslice == 0 || dimx == 0 || dimy == 0)
-      return -1;
-    if (nslice > 0xffffffffull)   // (chunk origins of the stacked view are 32-bit)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    const Dims vol{dimx, dimy, 1};
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const Coded what = out_inc_header ? Coded::SliceWithHeader : Coded::Slice;
-    return with_elem(is_float, [&](auto t) {
-      return compress_batch_impl(E, static_cast<const decltype(t)*>(d_src), nslice, vol, vol, mode, quality,
-                                 static_cast<uint8_t*>(d_dst), dst_cap, offsets, st, what);
-    });
-  });
-}
-
-int sperrhip_decompress_2d_batch_dev(const void* d_src, const size_t* offsets, size_t nslice, int has_header,
-                                     int output_float, size_t dimx, size_t dimy,
-                                     void* d_dst, size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_2d_batch_dev", [&]() -> int {
-    if (!d_src || !offsets || !d_dst || nslice == 0 || dimx == 0 || dimy == 0)
-      return -1;
-    if (nslice > 0xffffffffull || dimx > 0xffffffffull || dimy > 0xffffffffull)
-      return -1;
-    const size_t H = has_header ? 10 : 0, esz = output_float ? sizeof(float) : sizeof(double);
-    if (dimx > SIZE_MAX / dimy || dimx * dimy > SIZE_MAX / 8 / nslice)
-      return -1;
-    const size_t per = dimx * dimy;
-    if (per * nslice > dst_cap_bytes / esz)
-      return -1;
-    ContainerInfo all;
-    all.vol = {dimx, dimy, nslice};
-    all.chunk = {dimx, dimy, 1};
-    all.nvals = per * nslice;
-    all.is_float = output_float != 0;
-    std::vector<std::array<size_t, 6>> list(nslice);
-    for (size_t s = 0; s < nslice; s++) {
-      if (offsets[s + 1] < offsets[s] || offsets[s + 1] - offsets[s] < H + 17)   // (as sperrhip_decompress_2d_dev)
-        return -1;
-      all.off.push_back(offsets[s] + H);
-      all.len.push_back(offsets[s + 1] - offsets[s] - H);
-      list[s] = {0, dimx, 0, dimy, s, 1};
-    }
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const uint32_t hdrDims[2] = {(uint32_t)dimx, (uint32_t)dimy};
-    DecodeRequest req;
-    req.stacked = &list;
-    req.slices = true;
-    req.sliceHdr = has_header ? hdrDims : nullptr;
-    return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, all, st, req);
-  });
-}
-
-// ---- stage access for parity tests -----------------------------------------------------------
-
-int sperrhip_dwt3d_dev(double* d_vals, size_t dimx, size_t dimy, size_t dimz, int inverse,
-                       void* hip_stream)
-{
-  return guarded("sperrhip_dwt3d_dev", [&]() -> int {
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ShapePlan* P = E.plan(dimx, dimy, dimz);
-    if (!P || E.misc.ensure(4096))
-      return -1;
-    CoderState* cst = static_cast<CoderState*>(E.misc.p);
-    HIP_CHECK(hipMemsetAsync(cst, 0, sizeof(CoderState), st));
-    const uint32_t cd[3] = {P->dims[0], P->dims[1], P->dims[2]};
-    if (!inverse) {
-      for (const LiftPass& ps : P->fwd)
-        if (launch_lift(st, true, d_vals, P->N, 1, cd, ps.axis, ps.region, cst))
-          return -1;
-    }
-    else {
-      for (size_t k = P->fwd.size(); k-- > 0;)
-        if (launch_lift(st, false, d_vals, P->N, 1, cd, P->fwd[k].axis, P->fwd[k].region, cst))
-          return -1;
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-    E.prof.collect();
-    return 0;
-  });
-}
-
-int sperrhip_speck3d_encode_dev(const void* d_coef, int width, const uint64_t* d_sign, size_t dimx,
-                                size_t dimy, size_t dimz, size_t budget_bits, void* d_dst,
-                                size_t dst_cap, size_t* dst_len, void* hip_stream)
-{
-  return guarded("sperrhip_speck3d_encode_dev", [&]() -> int {
-    if (width != 4 && width != 8)
-      return 2;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ShapePlan* P = E.plan(dimx, dimy, dimz);
-    if (!P)
-      return -1;
-    const uint64_t raw_budget = budget_bits;
-    if (E.arena.ensure(enc_bytes_per_chunk(*P, raw_budget) + 4096) || E.misc.ensure(4096))
-      return -1;
-    Arena A;
-    A.base = static_cast<char*>(E.arena.p);
-    A.cap = E.arena.n;
-    EncBatchBufs bb;
-    if (!carve_enc(A, *P, 1, raw_budget, bb))
-      return -1;
-    const bool wide = width == 8;
-    if (wide && bb.aliased && unalias_coder(st, E, *P, bb, 1))   // (the 64-bit magnitudes go into the chunk buffer)
-      return -1;
-    EncBuffers e = bb.eb;
-    CoderState hcs;
-    memset(&hcs, 0, sizeof(hcs));
-    hcs.need_retry = wide ? 1u : 0u;  // the 64-bit pass only encodes chunks flagged for it
-    hcs.wide = wide ? 1u : 0u;
-    HIP_CHECK(hipMemcpyAsync(e.cst, &hcs, sizeof(CoderState), hipMemcpyHostToDevice, st));
-    if (reset_enc_pass(st, bb, 1))
-      return -1;
-    const uint32_t n = P->N;
-    HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t*>(e.sign), d_sign, ((n + 63) / 64) * 8,
-                             hipMemcpyDeviceToDevice, st));
-    if (wide) {
-      HIP_CHECK(hipMemcpyAsync(bb.vals, d_coef, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-      e.coef = bb.vals;
-      e.coefStride = bb.valsStride;
-      LAUNCH_K(k_msb_of<uint64_t>, dim3((n + 255) / 256), dim3(256), 0, st,
-               reinterpret_cast<const uint64_t*>(bb.vals), bb.msb, n);
-    }
-    else {
-      HIP_CHECK(hipMemcpyAsync(bb.coef32, d_coef, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-      LAUNCH_K(k_msb_of<uint32_t>, dim3((n + 255) / 256), dim3(256), 0, st,
-               reinterpret_cast<const uint32_t*>(bb.coef32), bb.msb, n);
-    }
-    EncPlanHost ph{P->d_initLIS, P->d_initLen, P->d_depthBlocks, P->depthBlockOff, P->ht.nsets};
-    if (launch_speck_encode(st, e, ph, raw_budget, false, wide))
-      return -1;
-    uint64_t* d_len = static_cast<uint64_t*>(E.misc.p);
-    LAUNCH_K(k_speck_stream_out, dim3(1024), dim3(kThreads), 0, st, e.cst, e.stream,
-             static_cast<uint8_t*>(d_dst), (uint64_t)dst_cap, d_len);
-    uint64_t len = 0;
-    HIP_CHECK(hipMemcpyAsync(&len, d_len, 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    E.prof.collect();
-    if (len > dst_cap)
-      return -1;
-    *dst_len = (size_t)len;
-    return 0;
-  });
-}
-
-int sperrhip_outlier_encode_dev(const void* d_orig, int is_float, const double* d_recon, size_t dimx, size_t dimy,
-                                size_t dimz, size_t nchunks, double tol, void* d_dst, size_t dst_cap, size_t* lens,
-                                void* hip_stream)
-{
-  return guarded("sperrhip_outlier_encode_dev", [&]() -> int {
-    if (!d_orig || !d_recon || !lens || !(tol > 0.0) || nchunks == 0 || dimx == 0 || dimy == 0 || dimz == 0)
-      return 2;
-    if (nchunks > 0xffffffffull / dimz)   // (a chunk's origin along z is a uint32)
-      return 2;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ShapePlan* P = E.plan(dimx, dimy, dimz);
-    if (!P)
-      return -1;
-    uint8_t* dst = static_cast<uint8_t*>(d_dst);
-    return is_float ? outlier_encode_impl<float>(E, st, *P, static_cast<const float*>(d_orig), d_recon, (uint32_t)nchunks,
-                                                 tol, dst, dst_cap, lens)
-                    : outlier_encode_impl<double>(E, st, *P, static_cast<const double*>(d_orig), d_recon,
-                                                  (uint32_t)nchunks, tol, dst, dst_cap, lens);
-  });
-}
-
-int sperrhip_speck3d_decode_dev(const void* d_stream, size_t stream_len, size_t dimx, size_t dimy,
-                                size_t dimz, void* d_coef, uint64_t* d_sign, int* width_out,
-                                void* hip_stream)
-{
-  return guarded("sperrhip_speck3d_decode_dev", [&]() -> int {
-    if (stream_len < 9)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    ShapePlan* P = E.plan(dimx, dimy, dimz);
-    if (!P)
-      return -1;
-    uint8_t head[9];
-    HIP_CHECK(hipMemcpyAsync(head, d_stream, 9, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const int nbp = head[0];
-    const bool wide = nbp > 32;
-    if (nbp > kMaxPlanes)
-      return -1;
-    // wrap the bare SPECK stream into a chunk stream with a dummy conditioner header
-    if (E.misc.ensure(round_up(17 + stream_len + 64, 256)))
-      return -1;
-    uint8_t* wrap = static_cast<uint8_t*>(E.misc.p);
-    LAUNCH_K(k_fake_condi_header, dim3(1), dim3(1), 0, st, wrap);
-    HIP_CHECK(hipMemcpyAsync(wrap + 17, d_stream, stream_len, hipMemcpyDeviceToDevice, st));
-    const uint32_t refNPlanes = !wide ? (uint32_t)nbp : 0u;   // (refinement bit planes like decompress_impl's)
-    if (E.arena.ensure(dec_bytes_per_chunk(*P, 17 + stream_len, 0, refNPlanes, false) + 4096))
-      return -1;
-    Arena A;
-    A.base = static_cast<char*>(E.arena.p);
-    A.cap = E.arena.n;
-    DecBatchBufs bb;
-    if (!carve_dec(A, *P, 1, 17 + stream_len, bb, 0, refNPlanes))
-      return -1;
-    DecBuffers d = bb.db;
-    const uint64_t off = 0, len = 17 + stream_len;
-    HIP_CHECK(hipMemcpyAsync(bb.chunkOff, &off, 8, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(bb.chunkLen, &len, 8, hipMemcpyHostToDevice, st));
-    if (reset_dec_call(d, 1, st) || reset_dec_pass(bb, 1, wide, st))
-      return -1;
-    const uint32_t n = P->N;
-    if (wide) {
-      d.coef = bb.vals;
-      d.coefStride = bb.valsStride;
-    }
-    const DecPlanHost ph = dec_plan_host(*P);
-    if (launch_speck_decode(st, d, ph, wrap, bb.chunkOff, bb.chunkLen, wide, nbp))
-      return -1;
-    HIP_CHECK(hipMemcpyAsync(d_coef, d.coef, (size_t)n * (wide ? 8 : 4), hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(d_sign, d.sign, ((n + 63) / 64) * 8, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    E.prof.collect();
-    *width_out = wide ? 8 : 4;
-    return 0;
-  });
-}
-
-// ---- reference-compatible host API (src/SPERR_C_API.cpp:135-258) ---------------------------
-
-void sperr_parse_header(const void* src, size_t* dimx, size_t* dimy, size_t* dimz, int* is_float)
-{
-  const uint8_t* p = static_cast<const uint8_t*>(src);
-  const bool is_3d = (p[1] & 0x40) != 0;
-  *is_float = (p[1] & 0x20) ? 1 : 0;
-  uint32_t d[3] = {1, 1, 1};
-  memcpy(d, p + 2, is_3d ? 12 : 8);
-  *dimx = d[0];
-  *dimy = d[1];
-  *dimz = d[2];
-}
-
-// include/SPERR_C_API.h:138-156, src/SPERR_C_API.cpp:260-280,
-// src/SPERR3D_Stream_Tools.cpp:134-226: host-side byte surgery, no GPU involved.  Every chunk
-// stream keeps `pct` percent of its bytes (at least 64, at most what it has), the container is
-// flagged as a portion and the chunk lengths are rewritten; the decoder zero-pads what is missing.
-int sperr_trunc_3d(const void* src, size_t src_len, unsigned pct, void** dst, size_t* dst_len)
-{
-  return guarded("sperr_trunc_3d", [&]() -> int {
-    return hostc::truncate_container(static_cast<const uint8_t*>(src), src_len, pct, dst, dst_len);
-  });
-}
-
-// include/SPERR_C_API.h:53-62, src/SPERR_C_API.cpp:7-97
-int sperr_comp_2d(const void* src, int is_float, size_t dimx, size_t dimy, int mode, double quality,
-                  int out_inc_header, void** dst, size_t* dst_len)
-{
-  return guarded("sperr_comp_2d", [&]() -> int {
-    if (*dst != nullptr)
-      return 1;
-    if (quality <= 0.0)
-      return 2;
-    if (mode < 1 || mode > 3)
-      return 2;
-    const size_t n = dimx * dimy, esz = is_float ? 4 : 8;
-    const size_t cap = sperrhip_max_compressed_size_2d(dimx, dimy, mode, quality);
-    // on the calling thread's own stream, with its own device buffers: slices coded from several host
-    // threads run side by side
-    ThreadSliceBufs& tb = thread_slice_bufs();
-    hipStream_t ts = tb.stream();
-    void *d_in = tb.get(0, n * esz), *d_out = tb.get(1, cap);
-    if (!d_in || !d_out) {
-      fprintf(stderr, "[sperr_hip] device allocation failed\n");
-      return -1;
-    }
-    int rtn = -1;
-    size_t len = 0;
-    if (hipMemcpyAsync(d_in, src, n * esz, hipMemcpyHostToDevice, ts) == hipSuccess)
-      rtn = sperrhip_compress_2d_dev(d_in, is_float, dimx, dimy, mode, quality, out_inc_header, d_out,
-                                     cap, &len, ts);
-    if (rtn == 0) {
-      void* buf = malloc(len);
-      if (buf && hipMemcpyAsync(buf, d_out, len, hipMemcpyDeviceToHost, ts) == hipSuccess &&
-          hipStreamSynchronize(ts) == hipSuccess) {
-        *dst = buf;
-        *dst_len = len;
-      }
-      else {
-        free(buf);
-        rtn = -1;
-      }
-    }
-    (void)hipStreamSynchronize(ts);
-    return rtn;
-  });
-}
-
-// include/SPERR_C_API.h:75-81, src/SPERR_C_API.cpp:99-134
-int sperrhip_multires_levels_2d(size_t dimx, size_t dimy, size_t* nlev, size_t* level_dims)
-{
-  return guarded("sperrhip_multires_levels_2d", [&]() -> int {
-    if (!nlev || !level_dims || dimx == 0 || dimy == 0 || dimx > 0xffff || dimy > 0xffff)
-      return -1;
-    MultiRes m;
-    multires_levels_2d(dimx, dimy, m);
-    *nlev = m.nlev;
-    for (size_t h = 0; h < m.nlev; h++) {
-      level_dims[2 * h] = m.cres[h][0];
-      level_dims[2 * h + 1] = m.cres[h][1];
-    }
-    return 0;
-  });
-}
-
-int sperrhip_decompress_2d_multires_dev(const void* d_src, size_t src_len, int output_float, size_t dimx,
-                                        size_t dimy, void* d_dst, size_t dst_cap_bytes, size_t nlev,
-                                        double* const* d_levels, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_2d_multires_dev", [&]() -> int {
-    if (!d_src || !d_dst || dimx == 0 || dimy == 0 || src_len < 17 || (nlev && !d_levels))
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    MultiRes m;
-    multires_levels_2d(dimx, dimy, m);
-    if (m.nlev != nlev)
-      return -1;   // (sperrhip_multires_levels_2d tells how many there are)
-    for (size_t h = 0; h < nlev; h++) {
-      if (!d_levels[h])
-        return -1;
-      m.d_level[h] = d_levels[h];
-    }
-    DecodeRequest req;
-    req.slices = true;
-    req.levels = &m;
-    return decode_to(E, d_src, output_float, d_dst, dst_cap_bytes, one_slice_info(dimx, dimy, src_len, output_float),
-                     st, req);
-  });
-}
-
-int sperrhip_decomp_2d_multires(const void* src, size_t src_len, int output_float, size_t dimx,
-                                size_t dimy, void** dst, size_t* nlev, size_t* level_dims, double** levels)
-{
-  return guarded("sperrhip_decomp_2d_multires", [&]() -> int {
-    if (!dst || *dst != nullptr)
-      return 1;
-    if (src_len < 17 || !nlev || !level_dims || !levels ||
-        sperrhip_multires_levels_2d(dimx, dimy, nlev, level_dims))
-      return -1;
-    const size_t outBytes = dimx * dimy * (output_float ? 4 : 8);
-    std::vector<size_t> lvn(*nlev);
-    for (size_t h = 0; h < *nlev; h++)
-      lvn[h] = level_dims[2 * h] * level_dims[2 * h + 1];
-    return decode_multires_host(src, src_len, outBytes, lvn, dst, levels, [&](void* d_in, void* d_out, double** d_lv) {
-      return sperrhip_decompress_2d_multires_dev(d_in, src_len, output_float, dimx, dimy, d_out, outBytes, *nlev, d_lv,
-                                                 nullptr);
-    });
-  });
-}
-
-int sperr_decomp_2d(const void* src, size_t src_len, int output_float, size_t dimx, size_t dimy,
-                    void** dst)
-{
-  return guarded("sperr_decomp_2d", [&]() -> int {
-    if (*dst != nullptr)
-      return 1;
-    const size_t n = dimx * dimy, esz = output_float ? 4 : 8;
-    ThreadSliceBufs& tb = thread_slice_bufs();   // (see sperr_comp_2d)
-    hipStream_t ts = tb.stream();
-    void *d_in = src_len >= 17 ? tb.get(0, src_len) : nullptr, *d_out = tb.get(1, n * esz);
-    if (!d_in || !d_out)
-      return -1;
-    int rtn = -1;
-    if (hipMemcpyAsync(d_in, src, src_len, hipMemcpyHostToDevice, ts) == hipSuccess)
-      rtn = sperrhip_decompress_2d_dev(d_in, src_len, output_float, dimx, dimy, d_out, n * esz, ts);
-    if (rtn == 0) {
-      void* buf = malloc(n * esz);
-      if (buf && hipMemcpyAsync(buf, d_out, n * esz, hipMemcpyDeviceToHost, ts) == hipSuccess &&
-          hipStreamSynchronize(ts) == hipSuccess)
-        *dst = buf;
-      else {
-        free(buf);
-        rtn = -1;
-      }
-    }
-    (void)hipStreamSynchronize(ts);
-    return rtn;
-  });
-}
-
-// host buffers in, malloc'd host buffers out: the volume and the levels of the hierarchy
-// (SPERR3D_OMP_D::decompress(p, true) + release_decoded_data / release_hierarchy)
-int sperrhip_decomp_3d_multires(const void* src, size_t src_len, int output_float, size_t* dimx,
-                                size_t* dimy, size_t* dimz, void** dst, size_t* nlev,
-                                size_t* level_dims, double** levels)
-{
-  return guarded("sperrhip_decomp_3d_multires", [&]() -> int {
-    if (!dst || *dst != nullptr)
-      return 1;
-    if (src_len < 18 || !nlev || !level_dims || !levels)
-      return -1;
-    ContainerInfo ci;
-    size_t need = 0;
-    if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
-      return -1;
-    if (sperrhip_multires_levels(ci.vol[0], ci.vol[1], ci.vol[2], ci.chunk[0], ci.chunk[1], ci.chunk[2],
-                                 nlev, level_dims))
-      return -1;
-    const size_t outBytes = ci.nvals * (output_float ? 4 : 8);
-    std::vector<size_t> lvn(*nlev);
-    for (size_t h = 0; h < *nlev; h++)
-      lvn[h] = level_dims[3 * h] * level_dims[3 * h + 1] * level_dims[3 * h + 2];
-    const int rtn =
-        decode_multires_host(src, src_len, outBytes, lvn, dst, levels, [&](void* d_in, void* d_out, double** d_lv) {
-          return sperrhip_decompress_multires_dev(d_in, src_len, output_float, d_out, outBytes, *nlev, d_lv, nullptr);
-        });
-    if (rtn == 0) {
-      *dimx = ci.vol[0];
-      *dimy = ci.vol[1];
-      *dimz = ci.vol[2];
-    }
-    return rtn;
-  });
-}
-
-// ---- a box per entry out of a batch of containers (boxes.h) -------------------------------------
-// The grid a boxes call cuts along: the volume and every container's chunk dims, or with a level -- which the
-// containers must then share chunk dims for, and have -- the level's dims and the chunks' corner cres[h] (level_select)
-static int boxes_grid(const Dims& vol, const std::vector<Dims>& chunk, const size_t* level, Dims& full,
-                      std::vector<Dims>& cell, MultiRes& m)
-{
-  full = vol;
-  cell = chunk;
-  if (!level)
-    return 0;
-  for (const Dims& c : chunk)
-    if (c != chunk[0])
-      return -1;
-  multires_levels(vol, chunk[0], m);
-  if (*level >= m.nlev)
+  if (wide && bb.aliased && unalias_coder(st, E, P, bb, 1))   // (the 64-bit magnitudes go into the chunk buffer)
     return -1;
-  Dims cr;
-  for (int a = 0; a < 3; a++) {
-    cr[a] = m.cres[*level][a];
-    full[a] = cr[a] * m.grid[a];
+  EncBuffers e = bb.eb;
+  CoderState hcs;
+  memset(&hcs, 0, sizeof(hcs));
+  hcs.need_retry = wide ? 1u : 0u;  // the 64-bit pass only encodes chunks flagged for it
+  hcs.wide = wide ? 1u : 0u;
+  HIP_CHECK(hipMemcpyAsync(e.cst, &hcs, sizeof(CoderState), hipMemcpyHostToDevice, st));
+  if (reset_enc_pass(st, bb, 1))
+    return -1;
+  const uint32_t n = P.N;
+  HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t*>(e.sign), d_sign, ((n + 63) / 64) * 8,
+                           hipMemcpyDeviceToDevice, st));
+  if (wide) {
+    HIP_CHECK(hipMemcpyAsync(bb.vals, d_coef, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    e.coef = bb.vals;
+    e.coefStride = bb.valsStride;
+    LAUNCH_K(k_msb_of<uint64_t>, dim3((n + 255) / 256), dim3(256), 0, st,
+             reinterpret_cast<const uint64_t*>(bb.vals), bb.msb, n);
   }
-  cell.assign(chunk.size(), cr);
+  else {
+    HIP_CHECK(hipMemcpyAsync(bb.coef32, d_coef, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    LAUNCH_K(k_msb_of<uint32_t>, dim3((n + 255) / 256), dim3(256), 0, st,
+             reinterpret_cast<const uint32_t*>(bb.coef32), bb.msb, n);
+  }
+  EncPlanHost ph{P.d_initLIS, P.d_initLen, P.d_depthBlocks, P.depthBlockOff, P.ht.nsets};
+  if (launch_speck_encode(st, e, ph, raw_budget, false, wide))
+    return -1;
+  uint64_t* d_len = static_cast<uint64_t*>(E.misc.p);
+  LAUNCH_K(k_speck_stream_out, dim3(1024), dim3(kThreads), 0, st, e.cst, e.stream, d_dst, (uint64_t)dst_cap, d_len);
+  uint64_t len = 0;
+  HIP_CHECK(hipMemcpyAsync(&len, d_len, 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  HIP_CHECK(hipGetLastError());
+  E.prof.collect();
+  if (len > dst_cap)
+    return -1;
+  *dst_len = (size_t)len;
   return 0;
 }
 
-int sperrhip_boxes_plan(size_t ncont, const size_t vol_dims[3], const size_t* chunk_dims, const uint32_t* which,
-                        const size_t* box_lo, size_t nbox, const size_t box_dims[3], const size_t* level, size_t out[5])
+// stage access (engine_core.h): the integer decoder alone, on a bare SPECK stream
+int speck3d_decode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_stream, size_t stream_len,
+                         void* d_coef, uint64_t* d_sign, int* width_out)
 {
-  return guarded("sperrhip_boxes_plan", [&]() -> int {
-    if (!vol_dims || !chunk_dims || !box_lo || !box_dims || !out || ncont == 0 || ncont > 0xffffffffull)
-      return -1;
-    std::vector<Dims> chunk(ncont), cell;
-    for (size_t c = 0; c < ncont; c++)
-      chunk[c] = Dims{chunk_dims[3 * c], chunk_dims[3 * c + 1], chunk_dims[3 * c + 2]};
-    Dims full;
-    MultiRes m;
-    BoxesPlan P;
-    if (boxes_grid(Dims{vol_dims[0], vol_dims[1], vol_dims[2]}, chunk, level, full, cell, m) ||
-        !boxes_plan(ncont, full, cell.data(), which, box_lo, nbox, Dims{box_dims[0], box_dims[1], box_dims[2]}, P))
-      return -1;
-    out[0] = P.slots.size();
-    out[1] = P.pairs.size();
-    out[2] = P.shared ? 1 : 0;
-    out[3] = P.stageVals;
-    out[4] = P.outVals;
-    return 0;
-  });
-}
-
-// The containers are read where they lie: every offset of the call is one from the lowest of their addresses.  Each
-// header is read once; the plan (boxes.h) names the slots, whose chunks become the call's stacked list -- one chunk per
-// slot, in the slots' order -- with the plan's geometry on the window.  Direct form: the crop writers fill d_dst.
-// Staged form: they fill the engine's staging array, typed as the output, and one launch of k_boxes_copy moves every
-// pair's window into its box
-int sperrhip_decompress_boxes_dev(const void* const* d_srcs, const size_t* src_lens, size_t ncont, const uint32_t* which,
-                                  const size_t* box_lo, size_t nbox, const size_t box_dims[3], const size_t* level,
-                                  unsigned pct, int output_float, void* d_dst, size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_boxes_dev", [&]() -> int {
-    if (!d_srcs || !src_lens || !box_lo || !box_dims || !d_dst || ncont == 0 || nbox == 0 || ncont > 0xffffffffull ||
-        nbox > 0xffffffffull || (!which && nbox != ncont))
-      return -1;
-    uintptr_t base = UINTPTR_MAX;
-    for (size_t c = 0; c < ncont; c++) {
-      if (!d_srcs[c])
-        return -1;
-      base = std::min(base, reinterpret_cast<uintptr_t>(d_srcs[c]));
-    }
-    for (size_t e = 0; which && e < nbox; e++)
-      if (which[e] >= ncont)
-        return -1;
-    for (int a = 0; a < 3; a++)
-      if (box_dims[a] == 0)
-        return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(base);
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    std::vector<uint64_t> off(ncont), len(ncont);
-    for (size_t c = 0; c < ncont; c++) {
-      off[c] = reinterpret_cast<uintptr_t>(d_srcs[c]) - base;
-      len[c] = src_lens[c];
-    }
-    std::vector<ContainerInfo> ci;
-    std::vector<uint8_t> heads;
-    if (read_headers_at(E, src, off, len, ci, heads, st))
-      return -1;
-    std::vector<Dims> chunk(ncont), cell;
-    for (size_t c = 0; c < ncont; c++) {
-      if (ci[c].vol != ci[0].vol)   // (the batch decode's rule)
-        return -1;
-      chunk[c] = ci[c].chunk;
-      keep_portion(ci[c], pct);
-    }
-    Dims full;
-    Window w;
-    BoxesPlan P;
-    if (boxes_grid(ci[0].vol, chunk, level, full, cell, w.m) ||
-        !boxes_plan(ncont, full, cell.data(), which, box_lo, nbox, Dims{box_dims[0], box_dims[1], box_dims[2]}, P))
-      return -1;
-    if (P.outVals > dst_cap_bytes / esz || P.stageVals > SIZE_MAX / 8)
-      return -1;
-    // the call's chunks: slot k is chunk P.slots[k].id of its container
-    const size_t nslots = P.slots.size();
-    ContainerInfo all;
-    std::vector<std::array<size_t, 6>> list(nslots), per;
-    all.chunk = ci[0].chunk;
-    all.off.resize(nslots);
-    all.len.resize(nslots);
-    w.ids.resize(nslots);
-    w.slotGeom.resize(nslots);
-    for (size_t k = 0, have = SIZE_MAX; k < nslots; k++) {
-      const BoxesSlot& s = P.slots[k];
-      if (s.cont != have) {   // (the slots are in container order)
-        per = chunk_volume(ci[s.cont].vol, ci[s.cont].chunk);
-        have = s.cont;
-        if (per.size() != ci[s.cont].off.size())
-          return -1;
-      }
-      if (s.id >= per.size())
-        return -1;
-      list[k] = per[s.id];
-      all.off[k] = off[s.cont] + ci[s.cont].off[s.id];
-      all.len[k] = ci[s.cont].len[s.id];
-      w.ids[k] = (uint32_t)k;
-      CropGeom& g = w.slotGeom[k];
-      for (int a = 0; a < 3; a++) {
-        g.rel[a] = P.geom[k].rel[a];
-        g.lo[a] = P.geom[k].lo[a];
-        g.hi[a] = P.geom[k].hi[a];
-      }
-    }
-    w.crop = true;
-    w.level = level != nullptr;
-    w.h = level ? *level : 0;
-    w.lo = Dims{0, 0, 0};
-    w.dims = P.shared ? P.stageDims : P.outDims;
-    all.vol = w.dims;
-    all.nvals = P.shared ? P.stageVals : P.outVals;
-    void* d_out = d_dst;
-    size_t outBytes = dst_cap_bytes;
-    if (P.shared) {
-      outBytes = P.stageVals * esz;
-      if (E.boxesStage.ensure(outBytes))
-        return -1;
-      d_out = E.boxesStage.p;
-    }
-    DecodeRequest req;
-    req.stacked = &list;
-    req.window = &w;
-    const int rtn = decode_to(E, src, output_float, d_out, outBytes, all, st, req);
-    if (rtn || !P.shared)
-      return rtn;
-    std::vector<BoxesCopyPair> pairs;
-    std::vector<uint64_t> first;
-    BoxesCopyGeom g;
-    boxes_copy_args(P, pairs, first, g);
-    const size_t pairBytes = round_up(pairs.size() * sizeof(BoxesCopyPair), 256);
-    if (E.misc.ensure(pairBytes + first.size() * 8))
-      return -1;
-    BoxesCopyPair* d_pairs = static_cast<BoxesCopyPair*>(E.misc.p);
-    uint64_t* d_first = reinterpret_cast<uint64_t*>(static_cast<char*>(E.misc.p) + pairBytes);
-    const bool vec = boxes_vec_ok(reinterpret_cast<uintptr_t>(d_out), reinterpret_cast<uintptr_t>(d_dst), pairs, g, esz);
-    auto copy = [&]() -> int {
-      HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(BoxesCopyPair), hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
-      if (boxes_copy_run(d_out, d_dst, esz, d_pairs, d_first, g, vec, st))
-        return -1;
-      HIP_CHECK(hipStreamSynchronize(st));   // (also: the uploads' host arrays may go only once the copies have read them)
-      return 0;
-    };
-    const int rc = copy();
-    if (rc)
-      drain_after_error(E, st);   // (as ~DecodeCall: queued copies read the vectors above)
-    E.prof.collect();
-    return rc;
-  });
-}
-
-// host container in, malloc'd host box out: only the chunks the box meets travel to the device (decode_packed_host),
-// are decoded there by the device path on the calling thread's device and stream 0, and the box comes back in one copy
-int sperrhip_decomp_3d_box(const void* src, size_t src_len, int output_float, const size_t box_lo[3],
-                           const size_t box_dims[3], void** dst)
-{
-  return guarded("sperrhip_decomp_3d_box", [&]() -> int {
-    if (!dst || *dst != nullptr)
-      return 1;
-    if (!src || !box_lo || !box_dims)
-      return -1;
-    ContainerInfo ci;
-    size_t need = 0;
-    if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
-      return -1;
-    Window w;
-    if (box_select(ci, box_lo, box_dims, w))
-      return -1;
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    const size_t outBytes = w.dims[0] * w.dims[1] * w.dims[2] * esz;
-    return decode_packed_host(static_cast<const uint8_t*>(src), ci, w.ids, outBytes, dst,
-                              [&](Engine& E, const void* d_in, const ContainerInfo& packed, void* d_out) {
-                                return decode_window(E, d_in, output_float, d_out, outBytes, packed, nullptr, w);
-                              });
-  });
-}
-
-// host container in, malloc'd host level (or box of it) out, the same way
-int sperrhip_decomp_3d_level(const void* src, size_t src_len, int output_float, size_t level, const size_t box_lo[3],
-                             const size_t box_dims[3], size_t out_dims[3], void** dst)
-{
-  return guarded("sperrhip_decomp_3d_level", [&]() -> int {
-    if (!dst || *dst != nullptr)
-      return 1;
-    if (!src || !out_dims)
-      return -1;
-    ContainerInfo ci;
-    size_t need = 0;
-    if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
-      return -1;
-    Window w;
-    if (level_select(ci, level, box_lo, box_dims, w))
-      return -1;
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    const size_t outBytes = w.dims[0] * w.dims[1] * w.dims[2] * esz;
-    const int rtn = decode_packed_host(static_cast<const uint8_t*>(src), ci, w.ids, outBytes, dst,
-                                       [&](Engine& E, const void* d_in, const ContainerInfo& packed, void* d_out) {
-                                         return decode_window(E, d_in, output_float, d_out, outBytes, packed, nullptr, w);
-                                       });
-    if (rtn == 0)
-      for (int a = 0; a < 3; a++)
-        out_dims[a] = w.dims[a];
-    return rtn;
-  });
-}
-
-// ---- a portion: decoding, and truncating on the device ------------------------------------------
-size_t sperrhip_portion_len(size_t chunk_len, unsigned pct)
-{
-  return hostc::portion_len(chunk_len, pct);
-}
-
-// The decodes of sperrhip_decompress_dev / _box_dev / _level_dev of the first `pct` percent of every chunk stream: the
-// call's own ContainerInfo takes the kept lengths (keep_portion) and the existing path runs on it, so nothing behind
-// a kept prefix is read, the workspace follows the kept lengths and no copy of the container is made
-int sperrhip_decompress_portion_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
-                                    const size_t* level, const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
-                                    size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_portion_dev", [&]() -> int {
-    if (!d_src || !d_dst || (box_lo == nullptr) != (box_dims == nullptr))
-      return -1;
-    DevDecode d(d_src, src_len, hip_stream);
-    if (!d.ok)
-      return -1;
-    keep_portion(d.ci, pct);
-    if (!level && !box_lo)
-      return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, DecodeRequest{});
-    Window w;
-    if (level ? level_select(d.ci, *level, box_lo, box_dims, w) : box_select(d.ci, box_lo, box_dims, w))
-      return -1;
-    return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w);
-  });
-}
-
-// The volume or a box of it, of the first `pct` percent of every chunk stream, into a strided view of d_dst: the
-// request names the view, and every writer takes its pitches from DecodeRequest::out_desc
-int sperrhip_decompress_view_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
-                                 const size_t box_lo[3], const size_t box_dims[3], void* d_dst,
-                                 const sperrhip_view* view, size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_view_dev", [&]() -> int {
-    if (!d_src || !d_dst || !view || (box_lo == nullptr) != (box_dims == nullptr))
-      return -1;
-    const ViewPitch pitch{view->pitch_y, view->pitch_z};
-    DevDecode d(d_src, src_len, hip_stream);
-    if (!d.ok)
-      return -1;
-    keep_portion(d.ci, pct);
-    if (box_lo) {
-      Window w;
-      if (box_select(d.ci, box_lo, box_dims, w))
-        return -1;
-      return decode_window(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, w, &pitch);
-    }
-    if (!view_fits(d.ci.vol[0], d.ci.vol[1], d.ci.vol[2], pitch, output_float ? sizeof(float) : sizeof(double),
-                   dst_cap_bytes))
-      return -1;
-    DecodeRequest req;
-    req.outView = &pitch;
-    return decode_to(*d.L.e, d_src, output_float, d_dst, dst_cap_bytes, d.ci, d.st, req);
-  });
-}
-
-// host container in, malloc'd host volume, box or level out: only the kept prefixes of the chosen chunks travel to the
-// device (decode_packed_host; the prefixes do not lie back to back, so each is a copy of its own)
-int sperrhip_decomp_3d_portion(const void* src, size_t src_len, unsigned pct, int output_float, const size_t* level,
-                               const size_t box_lo[3], const size_t box_dims[3], size_t out_dims[3], void** dst)
-{
-  return guarded("sperrhip_decomp_3d_portion", [&]() -> int {
-    if (!dst || *dst != nullptr)
-      return 1;
-    if (!src || (box_lo == nullptr) != (box_dims == nullptr))
-      return -1;
-    ContainerInfo ci;
-    size_t need = 0;
-    if (parse_container_host(static_cast<const uint8_t*>(src), src_len, src_len, ci, &need) != 0)
-      return -1;
-    keep_portion(ci, pct);
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    const bool all = !level && !box_lo;
-    Window w;
-    std::vector<uint32_t> every;
-    if (all) {
-      if (ci.len.size() > 0xffffffffull)
-        return -1;
-      every.resize(ci.len.size());
-      for (size_t i = 0; i < every.size(); i++)
-        every[i] = (uint32_t)i;
-    }
-    else if (level ? level_select(ci, *level, box_lo, box_dims, w) : box_select(ci, box_lo, box_dims, w))
-      return -1;
-    const Dims od = all ? ci.vol : w.dims;
-    const size_t outBytes = od[0] * od[1] * od[2] * esz;
-    const int rtn = decode_packed_host(
-        static_cast<const uint8_t*>(src), ci, all ? every : w.ids, outBytes, dst,
-        [&](Engine& E, const void* d_in, const ContainerInfo& packed, void* d_out) {
-          return all ? decode_to(E, d_in, output_float, d_out, outBytes, packed, nullptr, DecodeRequest{})
-                     : decode_window(E, d_in, output_float, d_out, outBytes, packed, nullptr, w);
-        });
-    if (rtn == 0 && out_dims)
-      for (int a = 0; a < 3; a++)
-        out_dims[a] = od[a];
-    return rtn;
-  });
-}
-
-int sperrhip_trunc_batch_dev(const void* d_src, const size_t* offsets, size_t nvol, unsigned pct, void* d_dst,
-                             size_t dst_cap, size_t* out_offsets, void* hip_stream)
-{
-  return guarded("sperrhip_trunc_batch_dev", [&]() -> int {
-    if (!d_src || !offsets || !out_offsets || nvol == 0)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    return trunc_impl(*L.e, static_cast<const uint8_t*>(d_src), offsets, nvol, pct, static_cast<uint8_t*>(d_dst),
-                      dst_cap, out_offsets, static_cast<hipStream_t>(hip_stream));
-  });
-}
-
-int sperrhip_trunc_dev(const void* d_src, size_t src_len, unsigned pct, void* d_dst, size_t dst_cap, size_t* dst_len,
-                       void* hip_stream)
-{
-  if (!dst_len)
+  uint8_t head[9];
+  HIP_CHECK(hipMemcpyAsync(head, d_stream, 9, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  const int nbp = head[0];
+  const bool wide = nbp > 32;
+  if (nbp > kMaxPlanes)
     return -1;
-  const size_t offs[2] = {0, src_len};
-  size_t out[2] = {0, 0};
-  const int rtn = sperrhip_trunc_batch_dev(d_src, offs, 1, pct, d_dst, dst_cap, out, hip_stream);
-  if (rtn >= 0)
-    *dst_len = out[1];
-  return rtn;
+  // wrap the bare SPECK stream into a chunk stream with a dummy conditioner header
+  if (E.misc.ensure(round_up(17 + stream_len + 64, 256)))
+    return -1;
+  uint8_t* wrap = static_cast<uint8_t*>(E.misc.p);
+  LAUNCH_K(k_fake_condi_header, dim3(1), dim3(1), 0, st, wrap);
+  HIP_CHECK(hipMemcpyAsync(wrap + 17, d_stream, stream_len, hipMemcpyDeviceToDevice, st));
+  const uint32_t refNPlanes = !wide ? (uint32_t)nbp : 0u;   // (refinement bit planes like decompress_impl's)
+  if (E.arena.ensure(dec_bytes_per_chunk(P, 17 + stream_len, 0, refNPlanes, false) + 4096))
+    return -1;
+  Arena A;
+  A.base = static_cast<char*>(E.arena.p);
+  A.cap = E.arena.n;
+  DecBatchBufs bb;
+  if (!carve_dec(A, P, 1, 17 + stream_len, bb, 0, refNPlanes))
+    return -1;
+  DecBuffers d = bb.db;
+  const uint64_t off = 0, len = 17 + stream_len;
+  HIP_CHECK(hipMemcpyAsync(bb.chunkOff, &off, 8, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(bb.chunkLen, &len, 8, hipMemcpyHostToDevice, st));
+  if (reset_dec_call(d, 1, st) || reset_dec_pass(bb, 1, wide, st))
+    return -1;
+  const uint32_t n = P.N;
+  if (wide) {
+    d.coef = bb.vals;
+    d.coefStride = bb.valsStride;
+  }
+  const DecPlanHost ph = dec_plan_host(P);
+  if (launch_speck_decode(st, d, ph, wrap, bb.chunkOff, bb.chunkLen, wide, nbp))
+    return -1;
+  HIP_CHECK(hipMemcpyAsync(d_coef, d.coef, (size_t)n * (wide ? 8 : 4), hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d_sign, d.sign, ((n + 63) / 64) * 8, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  HIP_CHECK(hipGetLastError());
+  E.prof.collect();
+  *width_out = wide ? 8 : 4;
+  return 0;
 }
 
-// the figures of nvol reconstructions against their originals (quality.hip); the partials' workspace is the
-// leased engine's arena, like every other call's
-int sperrhip_quality_batch_dev(const void* d_orig, const void* d_recon, int is_float, size_t nvol, size_t n,
-                               double* out, void* hip_stream)
-{
-  return guarded("sperrhip_quality_batch_dev", [&]() -> int {
-    if (!d_orig || !d_recon || !out || nvol == 0 || n == 0)
-      return -1;
-    const size_t need = quality_workspace_bytes(nvol, n, is_float);
-    if (need == 0)
-      return -1;
-    Lease L;
-    if (!L.e || L.e->arena.ensure(need))
-      return -1;
-    const int rtn = quality_run(d_orig, d_recon, is_float, nvol, n, L.e->arena.p, out, hip_stream);
-    L.e->prof.collect();
-    return rtn;
-  });
-}
-
-int sperrhip_quality_dev(const void* d_orig, const void* d_recon, int is_float, size_t n, double* out,
-                         void* hip_stream)
-{
-  return sperrhip_quality_batch_dev(d_orig, d_recon, is_float, 1, n, out, hip_stream);
-}
-
-// the same of two arrays read through strided views (a NULL view: dense), by the view form of the rows kernel
-int sperrhip_quality_view_dev(const void* d_orig, const sperrhip_view* view_orig, const void* d_recon,
-                              const sperrhip_view* view_recon, int is_float, size_t dimx, size_t dimy, size_t dimz,
-                              double* out, void* hip_stream)
-{
-  return guarded("sperrhip_quality_view_dev", [&]() -> int {
-    if (!d_orig || !d_recon || !out)
-      return -1;
-    const size_t need = quality_view_workspace_bytes(dimx, dimy, dimz, is_float);
-    if (need == 0)
-      return -1;
-    const ViewPitch dense = view_dense(dimx, dimy);   // (its products fit: the workspace's size has multiplied them)
-    const ViewPitch po = view_orig ? ViewPitch{view_orig->pitch_y, view_orig->pitch_z} : dense;
-    const ViewPitch pr = view_recon ? ViewPitch{view_recon->pitch_y, view_recon->pitch_z} : dense;
-    if (!view_valid(dimx, dimy, dimz, po) || !view_valid(dimx, dimy, dimz, pr))
-      return -1;
-    Lease L;
-    if (!L.e || L.e->arena.ensure(need))
-      return -1;
-    const int rtn = quality_view_run(d_orig, po, d_recon, pr, is_float, dimx, dimy, dimz, L.e->arena.p, out, hip_stream);
-    L.e->prof.collect();
-    return rtn;
-  });
-}
-
-// ---- interleaved fields (fields.h) -----------------------------------------------------------------------------
-// The fields calls stage: the selected fields are gathered into stacked volumes in a buffer the engine owns
-// (k_fields_gather), or scattered from it (k_fields_scatter), and the batch code works on that buffer.
-
-// the layout a call means (NULL: the dense interleave), once the stacked side's size is known not to overflow
-static FieldsLayout fields_layout_of(const sperrhip_fields* layout, size_t nfields, size_t dimx, size_t dimy)
-{
-  return layout ? FieldsLayout{layout->stride_x, layout->pitch_y, layout->pitch_z} : fields_dense(nfields, dimx, dimy);
-}
-
-int sperrhip_fields_gather_dev(const void* d_src, const sperrhip_fields* layout, size_t nfields, int is_float,
-                               size_t dimx, size_t dimy, size_t dimz, void* d_dst, size_t dst_cap_bytes,
-                               void* hip_stream)
-{
-  return guarded("sperrhip_fields_gather_dev", [&]() -> int {
-    size_t count = 0;
-    const size_t esz = is_float ? sizeof(float) : sizeof(double);
-    if (!d_src || !d_dst || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > dst_cap_bytes / esz)
-      return -1;
-    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
-    Lease L;
-    if (!L.e)
-      return -1;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (fields_gather_run(d_src, l, nfields, is_float, dimx, dimy, dimz, d_dst, st))
-      return -1;
-    HIP_CHECK(hipStreamSynchronize(st));
-    L.e->prof.collect();
-    return 0;
-  });
-}
-
-int sperrhip_fields_scatter_dev(const void* d_src, size_t nfields, int is_float, size_t dimx, size_t dimy, size_t dimz,
-                                void* d_dst, const sperrhip_fields* layout, size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_fields_scatter_dev", [&]() -> int {
-    size_t count = 0;
-    const size_t esz = is_float ? sizeof(float) : sizeof(double);
-    if (!d_src || !d_dst || !fields_stacked(nfields, dimx, dimy, dimz, &count))
-      return -1;
-    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
-    if (!fields_fits(nfields, dimx, dimy, dimz, l, esz, dst_cap_bytes))
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (fields_scatter_run(d_src, nfields, is_float, dimx, dimy, dimz, d_dst, l, st))
-      return -1;
-    HIP_CHECK(hipStreamSynchronize(st));
-    L.e->prof.collect();
-    return 0;
-  });
-}
-
-int sperrhip_compress_fields_dev(const void* d_src, const sperrhip_fields* layout, size_t nfields, int is_float,
-                                 size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z,
-                                 int mode, double quality, void* d_dst, size_t dst_cap, size_t* offsets,
-                                 void* hip_stream)
-{
-  return guarded("sperrhip_compress_fields_dev", [&]() -> int {
-    if (quality <= 0.0)
-      return 2;
-    if (mode < 1 || mode > 3)
-      return 2;
-    size_t count = 0;
-    if (!d_src || !d_dst || !offsets || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > SIZE_MAX / 8)
-      return -1;
-    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
-    if (!fields_valid(nfields, dimx, dimy, dimz, l))
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return with_elem(is_float, [&](auto t) {
-      using T = decltype(t);
-      if (E.fieldsStage.ensure(count * sizeof(T)) ||
-          fields_gather_run(d_src, l, nfields, is_float, dimx, dimy, dimz, E.fieldsStage.p, st))
-        return -1;
-      return compress_batch_impl(E, static_cast<const T*>(E.fieldsStage.p), nfields, vol, ch, mode, quality,
-                                 static_cast<uint8_t*>(d_dst), dst_cap, offsets, st);
-    });
-  });
-}
-
-int sperrhip_decompress_fields_dev(const void* d_src, const size_t* offsets, size_t nfields, int output_float,
-                                   size_t dimx, size_t dimy, size_t dimz, void* d_dst, const sperrhip_fields* layout,
-                                   size_t dst_cap_bytes, void* hip_stream)
-{
-  return guarded("sperrhip_decompress_fields_dev", [&]() -> int {
-    size_t count = 0;
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    if (!d_src || !offsets || !d_dst || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > SIZE_MAX / 8)
-      return -1;
-    const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
-    if (!fields_fits(nfields, dimx, dimy, dimz, l, esz, dst_cap_bytes))
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const uint8_t* src = static_cast<const uint8_t*>(d_src);
-    ContainerInfo all;
-    std::vector<std::array<size_t, 6>> list;
-    if (read_batch_info(E, src, offsets, nfields, all, list, st))
-      return -1;
-    if (all.vol != Dims{dimx, dimy, dimz * nfields})   // (every container names the call's dims)
-      return -1;
-    // the decode goes to the staging buffer: whatever it runs into, d_dst is as it was
-    if (E.fieldsStage.ensure(count * esz))
-      return -1;
-    DecodeRequest req;
-    req.stacked = &list;
-    const int rtn = decode_to(E, src, output_float, E.fieldsStage.p, count * esz, all, st, req);
-    if (rtn)
-      return rtn;
-    if (fields_scatter_run(E.fieldsStage.p, nfields, output_float, dimx, dimy, dimz, d_dst, l, st))
-      return -1;
-    HIP_CHECK(hipStreamSynchronize(st));
-    E.prof.collect();
-    return 0;
-  });
-}
-
-int sperrhip_quality_fields_dev(const void* d_orig, const sperrhip_fields* layout_orig, const void* d_recon,
-                                const sperrhip_fields* layout_recon, size_t nfields, int is_float, size_t dimx,
-                                size_t dimy, size_t dimz, double* out, void* hip_stream)
-{
-  return guarded("sperrhip_quality_fields_dev", [&]() -> int {
-    size_t count = 0;
-    const size_t esz = is_float ? sizeof(float) : sizeof(double);
-    if (!d_orig || !d_recon || !out || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > SIZE_MAX / 8)
-      return -1;
-    const FieldsLayout lo = fields_layout_of(layout_orig, nfields, dimx, dimy);
-    const FieldsLayout lr = fields_layout_of(layout_recon, nfields, dimx, dimy);
-    if (!fields_valid(nfields, dimx, dimy, dimz, lo) || !fields_valid(nfields, dimx, dimy, dimz, lr))
-      return -1;
-    const size_t n = count / nfields, need = quality_workspace_bytes(nfields, n, is_float);
-    if (need == 0)
-      return -1;
-    Lease L;
-    if (!L.e)
-      return -1;
-    Engine& E = *L.e;
-    if (E.arena.ensure(need) || E.fieldsStage.ensure(count * esz) || E.fieldsStage2.ensure(count * esz))
-      return -1;
-    if (fields_gather_run(d_orig, lo, nfields, is_float, dimx, dimy, dimz, E.fieldsStage.p, hip_stream) ||
-        fields_gather_run(d_recon, lr, nfields, is_float, dimx, dimy, dimz, E.fieldsStage2.p, hip_stream))
-      return -1;
-    const int rtn = quality_run(E.fieldsStage.p, E.fieldsStage2.p, is_float, nfields, n, E.arena.p, out, hip_stream);
-    E.prof.collect();
-    return rtn;
-  });
-}
-
-}  // extern "C"
+}  // namespace sperrhip

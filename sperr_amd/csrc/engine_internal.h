@@ -1,4 +1,5 @@
-// engine_internal.h -- host-side helpers of engine.hip that the chunk farm (farm.hip) shares.
+// engine_internal.h -- host-side helpers of engine.hip that the chunk farm (farm.hip) shares: all the farm sees of
+// the engine.  What the engine's own units share is engine_core.h.
 #ifndef SPERR_AMD_ENGINE_INTERNAL_H
 #define SPERR_AMD_ENGINE_INTERNAL_H
 

@@ -1,4 +1,4 @@
-// fields.h -- interleaved fields of a device array: the ONLY statement of the layout (the entry points of engine.hip,
+// fields.h -- interleaved fields of a device array: the ONLY statement of the layout (the entry points of abi.hip,
 // the two kernels of fields.hip and the host check tests/cpp/fields_check.cpp all use these).  Plain C++: no HIP here.
 //
 // An interleaved array keeps several variables per sample, the variables innermost: (z, y, x, nvar), a detector's

@@ -1,5 +1,5 @@
 // host_container.hpp -- the byte-level host code of the container layer: chunk grid, container
-// header parsing, progressive truncation.  No GPU, no HIP header: engine.hip includes it for the
+// header parsing, progressive truncation.  No GPU, no HIP header: engine_core.h includes it for the
 // product, tests/cpp/host_fuzz.cpp compiles it with -fsanitize=address,undefined and feeds it
 // damaged containers (this code parses untrusted bytes).
 //

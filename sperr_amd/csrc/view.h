@@ -1,4 +1,4 @@
-// view.h -- a strided view of a device array: the ONLY statement of what one is (the entry points of engine.hip, the
+// view.h -- a strided view of a device array: the ONLY statement of what one is (the entry points of abi.hip, the
 // view form of k_quality_rows and the host check tests/cpp/view_check.cpp all use these).  Plain C++: no HIP here.
 //
 // A view is a volume of dims (dimx, dimy, dimz), x fastest with unit x stride, given by the address of its first

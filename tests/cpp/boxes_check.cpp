@@ -179,7 +179,7 @@ static void check_plan(size_t ncont, const Dims& full, const std::vector<Dims>& 
   }
 }
 
-// The rule of a single box as the decoder has had it (Window::place + crop_geom, engine.hip), written out again: a
+// The rule of a single box as the decoder has had it (Window::place + crop_geom, decode_request.h), written out again: a
 // chunk at origin o of extent ext and the box [lo, lo + dims) give rel = o - lo, lo = max(lo - o, 0) and
 // hi = min(lo + dims - o, ext)
 static void check_single_entry(const Dims& full, const Dims& cell, const Dims& lo, const Dims& box)
