@@ -493,6 +493,66 @@ int sperrhip_decompress_2d_batch_dev(const void* d_src, const size_t* offsets, s
                                      int output_float, size_t dimx, size_t dimy,
                                      void* d_dst, size_t dst_cap_bytes, void* hip_stream);
 
+/* ---- missing values: masked volumes ------------------------------------------------------------ */
+/* A volume with missing samples (NaNs, or a sentinel such as 1e20) becomes two things: an ordinary container of
+ * the IN-FILLED volume -- every missing sample replaced by one finite value F -- which any SPERR reader decodes,
+ * and a small MASK STREAM that says which samples were missing.  The dense calls themselves still define nothing
+ * for non-finite input.
+ *   missing  SPERRHIP_MISSING_NAN: x != x.  SPERRHIP_MISSING_ABS_GE: !(fabs(x) < threshold), the sample widened to
+ *            double -- the sentinel, both infinities and NaN; threshold must be finite and > 0.
+ *   F        lo and hi are the smallest and largest valid sample under the total order of the sign-magnitude bit
+ *            patterns (-0.0 < +0.0); F = 0.5 * lo + 0.5 * hi in double, narrowed once to float for fp32 data; 0 when
+ *            no sample is valid.  An infinite lo or hi (rule NAN only) fails the call with -1.
+ *   stream   little-endian, sample index = linear index (x fastest), bit 1 = missing:
+ *            bytes 0-3 "SPMK", 4 version (1), 5 kind, 6-7 zero, 8-15 n, 16-23 nmissing, 24-31 count, 32- payload.
+ *            kind 0: nothing missing, no payload.  kind 1: `count` ascending uint32 positions p where
+ *            bit(p) != bit(p - 1), bit(-1) = 0.  kind 2: count = ceil(n / 64) uint64 words, sample i is bit i % 64 of
+ *            word i / 64, tail bits 0.  nmissing == 0 gives kind 0; otherwise kind 1 when n <= 2^32 and
+ *            4 * toggles < 8 * ceil(n / 64); otherwise kind 2.
+ * A stream's device pointer must be 8-byte aligned.  A stream that is handed in has its header checked (magic,
+ * version, kind, n against the volume, count and the payload's length against mask_len); its payload is trusted: a
+ * damaged one gives wrong samples, never a write outside the output.
+ * Out of scope: views, batches, interleaved fields, 2D slices, levels and multires, the host calls and the farm. */
+#define SPERRHIP_MISSING_NAN 1
+#define SPERRHIP_MISSING_ABS_GE 2
+/* 32 + 8 * ceil(n / 64): what any stream of n samples fits in.  Host only. */
+size_t sperrhip_mask_max_size(size_t n);
+/* The mask stream of the n samples at d_src into d_mask, and with d_filled the in-filled samples (NULL: none; it may
+ * be d_src).  One host wait.  0 ok, *mask_len and *nmissing set; 1 when mask_cap is too small: nothing is written
+ * and *mask_len is the size needed; -1 (nothing written) for a NULL pointer, n == 0, an unknown rule, a threshold
+ * that is not finite and > 0, or an infinite lo / hi. */
+int sperrhip_mask_make_dev(const void* d_src, int is_float, size_t n, int rule, double threshold,
+                           void* d_filled /* NULL: none; may be d_src */, void* d_mask, size_t mask_cap,
+                           size_t* mask_len, size_t* nmissing, void* hip_stream);
+/* the header of a stream on the device; any of n, nmissing, kind may be NULL.  -1: the header is refused */
+int sperrhip_mask_parse_dev(const void* d_mask, size_t mask_len, size_t* n, size_t* nmissing, int* kind);
+/* d_vol holds the box [box_lo, box_lo + box_dims) of a volume of vol_dims densely (both NULL: the whole volume):
+ * `value` -- its bits for doubles, (float)value for floats, NaN allowed -- is stored at the box's missing samples
+ * and NOTHING else is written.  -1, nothing written: a refused stream, n != the volume's, a box that leaves it. */
+int sperrhip_mask_apply_dev(void* d_vol, int is_float, const size_t vol_dims[3], const size_t box_lo[3],
+                            const size_t box_dims[3] /* both NULL: d_vol is the whole volume */,
+                            const void* d_mask, size_t mask_len, double value, void* hip_stream);
+/* the mask as n bytes of 0 / 1 */
+int sperrhip_mask_expand_dev(const void* d_mask, size_t mask_len, unsigned char* d_out, size_t n, void* hip_stream);
+/* sperrhip_mask_make_dev into a buffer the library keeps, then sperrhip_compress_dev of the in-filled volume: the
+ * container is byte for byte that call's.  With nothing missing it is the dense call's of d_src and the stream is 32
+ * bytes.  Modes and return codes as sperrhip_compress_dev, and those of sperrhip_mask_make_dev for the mask. */
+int sperrhip_compress_masked_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                                 size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
+                                 int rule, double threshold, void* d_dst, size_t dst_cap, size_t* dst_len,
+                                 void* d_mask, size_t mask_cap, size_t* mask_len, size_t* nmissing, void* hip_stream);
+/* sperrhip_decompress_portion_dev (pct 0: everything; box_lo and box_dims both NULL: the whole volume), then
+ * sperrhip_mask_apply_dev with the box: bit for bit the dense decode with `value` at the missing samples.  -1
+ * before anything is written where the dense calls return it, for a refused stream, and when the stream's n is not
+ * the container's volume.  There is no level form: a mask has no coarser level. */
+int sperrhip_decompress_masked_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
+                                   const size_t box_lo[3], const size_t box_dims[3], const void* d_mask,
+                                   size_t mask_len, double value, void* d_dst, size_t dst_cap_bytes, void* hip_stream);
+/* out[8] as sperrhip_quality_dev of the two arrays compacted to their valid samples in linear order, bit for bit.
+ * -1 when no sample is valid. */
+int sperrhip_quality_masked_dev(const void* d_orig, const void* d_recon, int is_float, size_t n,
+                                const void* d_mask, size_t mask_len, double* out, void* hip_stream);
+
 /* ---- profiling ------------------------------------------------------------------------------ */
 
 /* When enabled, the engine brackets every pipeline stage with HIP events on the launch stream

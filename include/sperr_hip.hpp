@@ -652,6 +652,81 @@ inline auto quality_fields_dev(const T* d_orig, const fields_type* layout_orig, 
   return rtn == 0 ? RTNType::Good : RTNType::Error;
 }
 
+// (this library's addition) Missing values (include/sperr_hip.h, "masked volumes"): a container of the in-filled
+// volume and a mask stream.  MissingRule::NaN takes no threshold; AbsGE takes one, finite and > 0.
+// RTNType::WrongLength: the mask's (or the container's) buffer is too small, mask_len then names the size needed.
+enum class MissingRule : int { NaN = SPERRHIP_MISSING_NAN, AbsGE = SPERRHIP_MISSING_ABS_GE };
+
+namespace detail {
+inline auto mask_rtn(int rtn) -> RTNType
+{
+  return rtn == 0 ? RTNType::Good : rtn == 1 ? RTNType::WrongLength : rtn == 2 ? RTNType::CompModeUnknown : RTNType::Error;
+}
+}  // namespace detail
+
+// the stream of n samples into d_mask, the in-filled samples into d_filled (null: none; may be d_src)
+template <typename T>
+inline auto mask_make_dev(const T* d_src, size_t n, MissingRule rule, double threshold, T* d_filled, void* d_mask,
+                          size_t mask_cap, size_t& mask_len, size_t& nmissing, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_mask_make_dev(d_src, sizeof(T) == 4, n, static_cast<int>(rule), threshold, d_filled,
+                                                 d_mask, mask_cap, &mask_len, &nmissing, hip_stream));
+}
+
+// `value` at the missing samples of the box of a volume that d_vol holds (null box: the whole volume); nothing else
+template <typename T>
+inline auto mask_apply_dev(T* d_vol, dims_type vol_dims, const dims_type* box_lo, const dims_type* box_dims,
+                           const void* d_mask, size_t mask_len, double value, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_mask_apply_dev(d_vol, sizeof(T) == 4, vol_dims.data(),
+                                                  box_lo ? box_lo->data() : nullptr,
+                                                  box_dims ? box_dims->data() : nullptr, d_mask, mask_len, value,
+                                                  hip_stream));
+}
+
+template <typename T>
+inline auto compress_masked_dev(const T* d_src, dims_type dims, dims_type chunks, CompMode mode, double quality,
+                                MissingRule rule, double threshold, void* d_out, size_t cap, size_t& out_len,
+                                void* d_mask, size_t mask_cap, size_t& mask_len, size_t& nmissing,
+                                void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const int m = mode == CompMode::Rate ? 1 : mode == CompMode::PSNR ? 2 : mode == CompMode::PWE ? 3 : 0;
+  if (m == 0)
+    return RTNType::CompModeUnknown;
+  return detail::mask_rtn(sperrhip_compress_masked_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0],
+                                                       chunks[1], chunks[2], m, quality, static_cast<int>(rule),
+                                                       threshold, d_out, cap, &out_len, d_mask, mask_cap, &mask_len,
+                                                       &nmissing, hip_stream));
+}
+
+// the volume (null box) or a box of it, from the first pct percent of every chunk stream (0: all), `value` at the
+// missing samples
+template <typename T>
+inline auto decompress_masked_dev(const void* d_stream, size_t stream_len, const void* d_mask, size_t mask_len,
+                                  double value, T* d_out, size_t cap_bytes, const dims_type* box_lo = nullptr,
+                                  const dims_type* box_dims = nullptr, unsigned pct = 0, void* hip_stream = nullptr)
+    -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_decompress_masked_dev(d_stream, stream_len, pct, sizeof(T) == 4,
+                                                         box_lo ? box_lo->data() : nullptr,
+                                                         box_dims ? box_dims->data() : nullptr, d_mask, mask_len, value,
+                                                         d_out, cap_bytes, hip_stream));
+}
+
+// quality_dev of the valid samples of two arrays
+template <typename T>
+inline auto quality_masked_dev(const T* d_orig, const T* d_recon, size_t n, const void* d_mask, size_t mask_len,
+                               std::array<double, 8>& out, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_quality_masked_dev(d_orig, d_recon, sizeof(T) == 4, n, d_mask, mask_len, out.data(),
+                                                      hip_stream));
+}
+
 }  // namespace sperr
 
 #endif

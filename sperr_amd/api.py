@@ -45,6 +45,9 @@ EXPORTS = [
     "sperrhip_compress_fields_dev", "sperrhip_decompress_fields_dev", "sperrhip_quality_fields_dev",
     "sperrhip_fields_gather_dev", "sperrhip_fields_scatter_dev",
     "sperrhip_boxes_plan", "sperrhip_decompress_boxes_dev",
+    "sperrhip_mask_max_size", "sperrhip_mask_make_dev", "sperrhip_mask_parse_dev", "sperrhip_mask_apply_dev",
+    "sperrhip_mask_expand_dev", "sperrhip_compress_masked_dev", "sperrhip_decompress_masked_dev",
+    "sperrhip_quality_masked_dev",
 ]
 
 
@@ -222,6 +225,27 @@ def load_library():
     lib.sperrhip_decompress_boxes_dev.argtypes = [C.POINTER(_vp), C.POINTER(_sz), _sz, C.POINTER(C.c_uint32),
                                                   C.POINTER(_sz), _sz, C.POINTER(_sz), C.POINTER(_sz), C.c_uint,
                                                   C.c_int, _vp, _sz, _vp]
+    lib.sperrhip_mask_max_size.restype = _sz
+    lib.sperrhip_mask_max_size.argtypes = [_sz]
+    lib.sperrhip_mask_make_dev.restype = C.c_int
+    lib.sperrhip_mask_make_dev.argtypes = [_vp, C.c_int, _sz, C.c_int, C.c_double, _vp, _vp, _sz, C.POINTER(_sz),
+                                           C.POINTER(_sz), _vp]
+    lib.sperrhip_mask_parse_dev.restype = C.c_int
+    lib.sperrhip_mask_parse_dev.argtypes = [_vp, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_int)]
+    lib.sperrhip_mask_apply_dev.restype = C.c_int
+    lib.sperrhip_mask_apply_dev.argtypes = [_vp, C.c_int, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _vp, _sz,
+                                            C.c_double, _vp]
+    lib.sperrhip_mask_expand_dev.restype = C.c_int
+    lib.sperrhip_mask_expand_dev.argtypes = [_vp, _sz, _vp, _sz, _vp]
+    lib.sperrhip_compress_masked_dev.restype = C.c_int
+    lib.sperrhip_compress_masked_dev.argtypes = [_vp, C.c_int] + [_sz] * 6 + [C.c_int, C.c_double, C.c_int, C.c_double,
+                                                                             _vp, _sz, C.POINTER(_sz), _vp, _sz,
+                                                                             C.POINTER(_sz), C.POINTER(_sz), _vp]
+    lib.sperrhip_decompress_masked_dev.restype = C.c_int
+    lib.sperrhip_decompress_masked_dev.argtypes = [_vp, _sz, C.c_uint, C.c_int, C.POINTER(_sz), C.POINTER(_sz), _vp,
+                                                   _sz, C.c_double, _vp, _sz, _vp]
+    lib.sperrhip_quality_masked_dev.restype = C.c_int
+    lib.sperrhip_quality_masked_dev.argtypes = [_vp, _vp, C.c_int, _sz, _vp, _sz, C.POINTER(C.c_double), _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -805,6 +829,143 @@ class SperrHip:
         if rtn != 0:
             raise SperrHipError(f"sperrhip_fields_scatter_dev returned {rtn}")
         return out
+
+    # ---- missing values ----------------------------------------------------------------------
+    @staticmethod
+    def _missing_rule(missing):
+        """(rule, threshold) of include/sperr_hip.h: "nan", or the threshold of the absolute-value rule"""
+        if isinstance(missing, str):
+            if missing != "nan":
+                raise ValueError(f'missing is "nan" or a threshold, not {missing!r}')
+            return 1, 0.0
+        return 2, float(missing)
+
+    def _mask_arg(self, mask):
+        torch = self.torch
+        assert mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous()
+        if mask.data_ptr() % 8:
+            raise SperrHipError("a mask stream starts on an 8-byte boundary")
+
+    def mask_max_size(self, n):
+        return self.lib.sperrhip_mask_max_size(n)
+
+    def mask_make(self, vol, missing="nan", filled_out=None):
+        """The mask stream of a contiguous cuda tensor (float32 / float64, any shape): which samples are missing --
+        NaNs, or with a number those whose absolute value is not below it -- as (cuda uint8 tensor, nmissing).
+        filled_out (same dtype and numel; may be `vol` itself) receives the in-filled samples."""
+        torch = self.torch
+        assert vol.is_cuda and vol.is_contiguous() and vol.dtype in (torch.float32, torch.float64)
+        if filled_out is not None:
+            assert filled_out.is_cuda and filled_out.is_contiguous() and filled_out.dtype == vol.dtype
+            assert filled_out.numel() == vol.numel()
+        rule, thr = self._missing_rule(missing)
+        n = vol.numel()
+        mask = torch.empty(self.mask_max_size(n), dtype=torch.uint8, device=vol.device)
+        mlen, nmiss = _sz(0), _sz(0)
+        rtn = self.lib.sperrhip_mask_make_dev(vol.data_ptr(), int(vol.dtype == torch.float32), n, rule, thr,
+                                              None if filled_out is None else filled_out.data_ptr(), mask.data_ptr(),
+                                              mask.numel(), C.byref(mlen), C.byref(nmiss), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_mask_make_dev returned {rtn}")
+        return mask[:mlen.value], nmiss.value
+
+    def mask_parse(self, mask):
+        """(n, nmissing, kind) of a mask stream's header"""
+        self._mask_arg(mask)
+        n, nmiss, kind = _sz(0), _sz(0), C.c_int(0)
+        rtn = self.lib.sperrhip_mask_parse_dev(mask.data_ptr(), mask.numel(), C.byref(n), C.byref(nmiss), C.byref(kind))
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_mask_parse_dev returned {rtn}")
+        return n.value, nmiss.value, kind.value
+
+    def mask_apply(self, vol, mask, value, box_lo_xyz=None, box_dims_xyz=None, vol_shape_zyx=None):
+        """`value` into the missing samples of `vol`, a contiguous cuda tensor, in place; nothing else is written.
+        With a box, `vol` is the box [lo, lo + dims) (x, y, z order) of a volume of vol_shape_zyx."""
+        torch = self.torch
+        assert vol.is_cuda and vol.is_contiguous() and vol.dtype in (torch.float32, torch.float64)
+        self._mask_arg(mask)
+        lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
+        if dims is None:   # (the whole volume is one run of samples: only their number matters)
+            vd = (_sz * 3)(vol.numel(), 1, 1)
+        else:
+            if vol_shape_zyx is None:
+                raise ValueError("a box needs vol_shape_zyx")
+            if vol.numel() != math.prod(box_dims_xyz):
+                raise SperrHipError(f"a tensor of {vol.numel()} samples for a box (x, y, z) {tuple(box_dims_xyz)}")
+            vd = (_sz * 3)(*(int(d) for d in reversed(vol_shape_zyx)))
+        rtn = self.lib.sperrhip_mask_apply_dev(vol.data_ptr(), int(vol.dtype == torch.float32), vd, lo, dims,
+                                               mask.data_ptr(), mask.numel(), float(value), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_mask_apply_dev returned {rtn}")
+        return vol
+
+    def mask_bits(self, mask):
+        """The mask as a flat cuda torch.bool tensor of n entries, True where a sample is missing"""
+        torch = self.torch
+        n, _, _ = self.mask_parse(mask)
+        out = torch.empty(n, dtype=torch.uint8, device=mask.device)
+        rtn = self.lib.sperrhip_mask_expand_dev(mask.data_ptr(), mask.numel(), out.data_ptr(), n, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_mask_expand_dev returned {rtn}")
+        return out.view(torch.bool)
+
+    def compress_masked(self, vol, chunks_xyz, quality, mode=1, missing="nan"):
+        """A contiguous cuda tensor (z, y, x) with missing samples (mask_make) as (container, mask): the container is
+        compress() of the in-filled volume, which any SPERR reader decodes; the mask says which samples were missing."""
+        torch = self.torch
+        assert vol.is_cuda and vol.dim() == 3 and vol.dtype in (torch.float32, torch.float64)
+        self._no_view(vol, "compress_masked")
+        rule, thr = self._missing_rule(missing)
+        dz, dy, dx = vol.shape
+        out = torch.empty(self.max_compressed_size(vol.shape, chunks_xyz, quality, mode), dtype=torch.uint8,
+                          device=vol.device)
+        mask = torch.empty(self.mask_max_size(vol.numel()), dtype=torch.uint8, device=vol.device)
+        n, mlen, nmiss = _sz(0), _sz(0), _sz(0)
+        rtn = self.lib.sperrhip_compress_masked_dev(vol.data_ptr(), int(vol.dtype == torch.float32), dx, dy, dz,
+                                                    *chunks_xyz, mode, float(quality), rule, thr, out.data_ptr(),
+                                                    out.numel(), C.byref(n), mask.data_ptr(), mask.numel(),
+                                                    C.byref(mlen), C.byref(nmiss), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_masked_dev returned {rtn}")
+        return out[:n.value], mask[:mlen.value]
+
+    def decompress_masked(self, container, mask, value=float("nan"), box_lo_xyz=None, box_dims_xyz=None, pct=0,
+                          output_float=True, out=None, level=None):
+        """decompress() or, with a box, decompress_box() of a container, with `value` at the samples `mask` names.
+        A level is refused, here alone: the C call has no level argument, because a mask has no coarser level."""
+        torch = self.torch
+        assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
+        self._mask_arg(mask)
+        if level is not None:
+            raise SperrHipError("decompress_masked decodes no level: a mask has no coarser level")
+        lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            zyx = self.parse_header(container)[0] if dims is None else tuple(int(d) for d in reversed(box_dims_xyz))
+            out = torch.empty(zyx, dtype=dt, device=container.device)
+        assert out.dtype == dt and out.is_cuda
+        self._no_view(out, "decompress_masked")
+        rtn = self.lib.sperrhip_decompress_masked_dev(container.data_ptr(), container.numel(), int(pct),
+                                                      int(output_float), lo, dims, mask.data_ptr(), mask.numel(),
+                                                      float(value), out.data_ptr(), out.numel() * out.element_size(),
+                                                      self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_masked_dev returned {rtn}")
+        return out
+
+    def quality_masked(self, orig, recon, mask):
+        """quality() of the valid samples of two contiguous cuda tensors: the figures of the arrays compacted to the
+        samples `mask` does not name, in linear order."""
+        self._quality_args(orig, recon)
+        self._mask_arg(mask)
+        out = (C.c_double * 8)()
+        rtn = self.lib.sperrhip_quality_masked_dev(orig.data_ptr(), recon.data_ptr(),
+                                                   int(orig.dtype == self.torch.float32), orig.numel(),
+                                                   mask.data_ptr(), mask.numel(), out, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_quality_masked_dev returned {rtn}")
+        n, nmiss, _ = self.mask_parse(mask)
+        return Quality(out[:8], n - nmiss)
 
     # ---- stage access ----------------------------------------------------------------------
     def dwt3d(self, vals, inverse=False):

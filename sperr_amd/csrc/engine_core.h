@@ -300,6 +300,9 @@ struct Engine {
   DevBuf fieldsStage, fieldsStage2;         // interleaved fields (fields.h): the stacked volumes the batch code works on,
                                             //   and the quality call's other side
   DevBuf boxesStage;                        // boxes of a batch (boxes.h): the staging array of the staged form
+  DevBuf maskStage, maskStage2;             // missing values (mask.h): the in-filled volume the encoder reads; the
+                                            //   compacted arrays of the quality call
+  DevBuf maskWork;                          //   ... and the bit array, the tile counts and the partials of mask.hip
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
 
@@ -422,7 +425,7 @@ struct Engine {
     plans.clear();
     planOrder.clear();
     for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage})
+                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork})
       b->drop();
     for (auto& b : outlDec)
       b.drop();
@@ -435,12 +438,12 @@ struct Engine {
   }
   // every device buffer of the engine: the arena, the containers' slots, and what point-wise error mode adds (the
   // outlier coder's arrays, the boxes of the coarser levels, the outlier streams) and the staging buffers of the
-  // fields calls -- sperrhip_debug_counter(6)
+  // fields and mask calls -- sperrhip_debug_counter(6)
   size_t device_bytes() const
   {
     size_t n = 0;
     for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage})
+                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork})
       n += b->n;
     for (const auto& b : outlDec)
       n += b.n;
