@@ -15,8 +15,13 @@
  * 2. Device-resident entry points (sperrhip_*): the volume and the container stay in HBM, which
  *    is what bench.py times and what an application that already holds its field on the GPU
  *    should call.  All pointers marked `d_` are device pointers; `hip_stream` is a hipStream_t
- *    passed as void* (NULL = the default stream).  Calls are synchronous with respect to the
- *    host when they return.  Many small volumes of one shape that each want a container go
+ *    passed as void* (NULL = the default stream).  A call is ordered on hip_stream: its inputs may
+ *    still be pending there (work enqueued on hip_stream before the call writes them), and work
+ *    enqueued there after the call returns sees its outputs.  Every call but sperrhip_mask_apply_dev
+ *    and sperrhip_mask_expand_dev has also finished when it returns; those two return with their
+ *    kernel enqueued (and sperrhip_decompress_masked_dev with its last one, the same store of
+ *    `value`).  Concurrent callers pass a stream each; when more call at once than a device
+ *    has engines (SPERR_HIP_ENGINES_PER_DEVICE, 4), the others wait on the host.  Many small volumes of one shape that each want a container go
  *    through the batch calls (sperrhip_compress_batch_dev / sperrhip_decompress_batch_dev): one
  *    call for all of them, the same containers as one call per volume.  A box out of each of many
  *    containers -- a region over a time series, crops for a loader -- is one call as well
@@ -142,10 +147,16 @@ int sperrhip_decompress_dev(const void* d_src, size_t src_len, int output_float,
                             size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
                             void* hip_stream);
 
-/* Reads the container header of a device-resident container. Returns 0 ok. */
+/* Reads the container header of a device-resident container on the default stream, which does not wait for a
+ * non-blocking stream: for a container that work on another stream is still writing, use the _stream_ call.
+ * Returns 0 ok. */
 int sperrhip_parse_header_dev(const void* d_src, size_t src_len, size_t* dimx, size_t* dimy,
                               size_t* dimz, int* is_float, size_t* chunk_x, size_t* chunk_y,
                               size_t* chunk_z);
+/* The same on hip_stream: the header is read behind everything enqueued there (NULL: the call above). */
+int sperrhip_parse_header_stream_dev(const void* d_src, size_t src_len, size_t* dimx, size_t* dimy,
+                                     size_t* dimz, int* is_float, size_t* chunk_x, size_t* chunk_y,
+                                     size_t* chunk_z, void* hip_stream);
 
 /* ---- stage access for parity tests (device pointers; one chunk = the whole array) ------------- */
 
@@ -524,8 +535,12 @@ size_t sperrhip_mask_max_size(size_t n);
 int sperrhip_mask_make_dev(const void* d_src, int is_float, size_t n, int rule, double threshold,
                            void* d_filled /* NULL: none; may be d_src */, void* d_mask, size_t mask_cap,
                            size_t* mask_len, size_t* nmissing, void* hip_stream);
-/* the header of a stream on the device; any of n, nmissing, kind may be NULL.  -1: the header is refused */
+/* the header of a stream on the device, read on the default stream (which does not wait for a non-blocking stream);
+ * any of n, nmissing, kind may be NULL.  -1: the header is refused */
 int sperrhip_mask_parse_dev(const void* d_mask, size_t mask_len, size_t* n, size_t* nmissing, int* kind);
+/* the same on hip_stream: read behind everything enqueued there (NULL: the call above) */
+int sperrhip_mask_parse_stream_dev(const void* d_mask, size_t mask_len, size_t* n, size_t* nmissing, int* kind,
+                                   void* hip_stream);
 /* d_vol holds the box [box_lo, box_lo + box_dims) of a volume of vol_dims densely (both NULL: the whole volume):
  * `value` -- its bits for doubles, (float)value for floats, NaN allowed -- is stored at the box's missing samples
  * and NOTHING else is written.  -1, nothing written: a refused stream, n != the volume's, a box that leaves it. */

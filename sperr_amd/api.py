@@ -23,7 +23,7 @@ _sz, _vp = C.c_size_t, C.c_void_p
 EXPORTS = [
     "sperr_comp_3d", "sperr_decomp_3d", "sperr_parse_header", "sperr_trunc_3d",
     "sperrhip_max_compressed_size", "sperrhip_compress_dev", "sperrhip_decompress_dev",
-    "sperrhip_parse_header_dev", "sperrhip_dwt3d_dev", "sperrhip_speck3d_encode_dev",
+    "sperrhip_parse_header_dev", "sperrhip_parse_header_stream_dev", "sperrhip_dwt3d_dev", "sperrhip_speck3d_encode_dev",
     "sperrhip_speck3d_decode_dev", "sperrhip_outlier_encode_dev", "sperrhip_profile_enable", "sperrhip_profile_reset",
     "sperrhip_profile_get", "sperrhip_profile_get2", "sperrhip_profile_only",
     "sperrhip_multires_levels", "sperrhip_decompress_multires_dev", "sperrhip_decomp_3d_multires",
@@ -45,7 +45,8 @@ EXPORTS = [
     "sperrhip_compress_fields_dev", "sperrhip_decompress_fields_dev", "sperrhip_quality_fields_dev",
     "sperrhip_fields_gather_dev", "sperrhip_fields_scatter_dev",
     "sperrhip_boxes_plan", "sperrhip_decompress_boxes_dev",
-    "sperrhip_mask_max_size", "sperrhip_mask_make_dev", "sperrhip_mask_parse_dev", "sperrhip_mask_apply_dev",
+    "sperrhip_mask_max_size", "sperrhip_mask_make_dev", "sperrhip_mask_parse_dev", "sperrhip_mask_parse_stream_dev",
+    "sperrhip_mask_apply_dev",
     "sperrhip_mask_expand_dev", "sperrhip_compress_masked_dev", "sperrhip_decompress_masked_dev",
     "sperrhip_quality_masked_dev",
 ]
@@ -232,6 +233,8 @@ def load_library():
                                            C.POINTER(_sz), _vp]
     lib.sperrhip_mask_parse_dev.restype = C.c_int
     lib.sperrhip_mask_parse_dev.argtypes = [_vp, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_int)]
+    lib.sperrhip_mask_parse_stream_dev.restype = C.c_int
+    lib.sperrhip_mask_parse_stream_dev.argtypes = [_vp, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_int), _vp]
     lib.sperrhip_mask_apply_dev.restype = C.c_int
     lib.sperrhip_mask_apply_dev.argtypes = [_vp, C.c_int, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _vp, _sz,
                                             C.c_double, _vp]
@@ -249,6 +252,8 @@ def load_library():
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
+    lib.sperrhip_parse_header_stream_dev.restype = C.c_int
+    lib.sperrhip_parse_header_stream_dev.argtypes = lib.sperrhip_parse_header_dev.argtypes + [_vp]
     lib.sperrhip_dwt3d_dev.restype = C.c_int
     lib.sperrhip_dwt3d_dev.argtypes = [_vp, _sz, _sz, _sz, C.c_int, _vp]
     lib.sperrhip_speck3d_encode_dev.restype = C.c_int
@@ -375,14 +380,16 @@ class SperrHip:
         return out[:n.value]
 
     def parse_header(self, container):
+        """((z, y, x), is_float, chunks (x, y, z)) of a device container's header, read on the current stream: behind
+        whatever is still writing the container there"""
         d = [_sz(0) for _ in range(6)]
         isf = C.c_int(0)
-        rtn = self.lib.sperrhip_parse_header_dev(container.data_ptr(), container.numel(),
-                                                 C.byref(d[0]), C.byref(d[1]), C.byref(d[2]),
-                                                 C.byref(isf), C.byref(d[3]), C.byref(d[4]),
-                                                 C.byref(d[5]))
+        rtn = self.lib.sperrhip_parse_header_stream_dev(container.data_ptr(), container.numel(),
+                                                        C.byref(d[0]), C.byref(d[1]), C.byref(d[2]),
+                                                        C.byref(isf), C.byref(d[3]), C.byref(d[4]),
+                                                        C.byref(d[5]), self._stream())
         if rtn != 0:
-            raise SperrHipError(f"sperrhip_parse_header_dev returned {rtn}")
+            raise SperrHipError(f"sperrhip_parse_header_stream_dev returned {rtn}")
         return (d[2].value, d[1].value, d[0].value), bool(isf.value), \
                (d[3].value, d[4].value, d[5].value)
 
@@ -870,12 +877,13 @@ class SperrHip:
         return mask[:mlen.value], nmiss.value
 
     def mask_parse(self, mask):
-        """(n, nmissing, kind) of a mask stream's header"""
+        """(n, nmissing, kind) of a mask stream's header, read on the current stream"""
         self._mask_arg(mask)
         n, nmiss, kind = _sz(0), _sz(0), C.c_int(0)
-        rtn = self.lib.sperrhip_mask_parse_dev(mask.data_ptr(), mask.numel(), C.byref(n), C.byref(nmiss), C.byref(kind))
+        rtn = self.lib.sperrhip_mask_parse_stream_dev(mask.data_ptr(), mask.numel(), C.byref(n), C.byref(nmiss),
+                                                      C.byref(kind), self._stream())
         if rtn != 0:
-            raise SperrHipError(f"sperrhip_mask_parse_dev returned {rtn}")
+            raise SperrHipError(f"sperrhip_mask_parse_stream_dev returned {rtn}")
         return n.value, nmiss.value, kind.value
 
     def mask_apply(self, vol, mask, value, box_lo_xyz=None, box_dims_xyz=None, vol_shape_zyx=None):

@@ -359,8 +359,18 @@ int sperrhip_parse_header_dev(const void* d_src, size_t src_len, size_t* dimx, s
                               size_t* dimz, int* is_float, size_t* chunk_x, size_t* chunk_y,
                               size_t* chunk_z)
 {
-  return guarded("sperrhip_parse_header_dev", [&]() -> int {
-    DevDecode d(d_src, src_len, nullptr);
+  return sperrhip_parse_header_stream_dev(d_src, src_len, dimx, dimy, dimz, is_float, chunk_x, chunk_y, chunk_z,
+                                          nullptr);
+}
+
+// (the header is read behind whatever `hip_stream` still has to do: the NULL stream does not wait for a non-blocking
+// stream, so a container that is still being written there would be parsed from the bytes before it)
+int sperrhip_parse_header_stream_dev(const void* d_src, size_t src_len, size_t* dimx, size_t* dimy,
+                                     size_t* dimz, int* is_float, size_t* chunk_x, size_t* chunk_y,
+                                     size_t* chunk_z, void* hip_stream)
+{
+  return guarded("sperrhip_parse_header_stream_dev", [&]() -> int {
+    DevDecode d(d_src, src_len, hip_stream);
     if (!d.ok)
       return -1;
     const ContainerInfo& ci = d.ci;

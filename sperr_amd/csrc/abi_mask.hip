@@ -103,9 +103,16 @@ int sperrhip_mask_make_dev(const void* d_src, int is_float, size_t n, int rule, 
 
 int sperrhip_mask_parse_dev(const void* d_mask, size_t mask_len, size_t* n, size_t* nmissing, int* kind)
 {
-  return guarded("sperrhip_mask_parse_dev", [&]() -> int {
+  return sperrhip_mask_parse_stream_dev(d_mask, mask_len, n, nmissing, kind, nullptr);
+}
+
+// (read behind what `hip_stream` still has to do; see sperrhip_parse_header_stream_dev)
+int sperrhip_mask_parse_stream_dev(const void* d_mask, size_t mask_len, size_t* n, size_t* nmissing, int* kind,
+                                   void* hip_stream)
+{
+  return guarded("sperrhip_mask_parse_stream_dev", [&]() -> int {
     MaskStream m;
-    if (read_mask_stream(d_mask, mask_len, m, nullptr))
+    if (read_mask_stream(d_mask, mask_len, m, static_cast<hipStream_t>(hip_stream)))
       return -1;
     if (n)
       *n = (size_t)m.h.n;
