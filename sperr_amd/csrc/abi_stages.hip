@@ -1,7 +1,7 @@
 // abi_stages.hip -- stage access for the parity tests: the entry points of include/sperr_hip.h that run ONE stage of
 // the pipeline on the caller's data -- the transform, the integer coder each way, the outlier coder -- so that a test
 // can compare it with the reference's stage alone.  Each leases an engine, takes the plan of the chunk shape and calls
-// the stage's front (engine_core.h); the kernels that feed and drain a stage sit with it in engine.hip.
+// the stage's front (engine_core.h); the kernels that feed and drain a stage sit with it in encode.hip and decode.hip.
 #include "engine_core.h"
 
 using namespace sperrhip;

@@ -10,7 +10,7 @@
 // per container `cell`, the extent of the pieces that tile it, in chunk_volume's manner (all but the last segment of
 // an axis start at multiples of the cell, the last one runs to the end of `full`).  At full resolution `full` is the
 // volume and `cell` the container's chunk dims; for level h of the hierarchy `full` is the level's dims and `cell` the
-// chunks' corner cres[h] (level_select, engine.hip), origins and box dims in the level's coordinates.  Either way cell
+// chunks' corner cres[h] (level_select, decode.hip), origins and box dims in the level's coordinates.  Either way cell
 // id i of container c is chunk i of that container.
 //
 //   slots    the distinct (container, cell id) pairs that any entry's box meets (box_chunks per entry).  A slot is

@@ -1,4 +1,4 @@
-// decode_request.h -- the decoder's front (engine.hip), as the C ABI (abi.hip) calls it: what a container's header says,
+// decode_request.h -- the decoder's front (decode.hip), as the C ABI (abi.hip) calls it: what a container's header says,
 // which levels and windows a container has, what one decompression call decodes and writes (DecodeRequest), and the
 // calls themselves.  Internal, like engine_core.h.
 #ifndef SPERR_AMD_DECODE_REQUEST_H

@@ -1,5 +1,5 @@
-// engine_core.h -- what engine.hip (plans, pool, the encode and decode calls) shares with the C ABI (abi.hip,
-// abi_stages.hip): the profiler, device buffers and arenas, a chunk shape's plan, the engine, the pool and a call's
+// engine_core.h -- what engine.hip (plans, pool), encode.hip and decode.hip (the two calls) share with the C ABI
+// (abi.hip, abi_stages.hip): the profiler, device buffers and arenas, a chunk shape's plan, the engine, the pool and a call's
 // lease; the file-scope state; and the encoder's front, which abi.hip calls the way it calls the decoder's
 // (decode_request.h).  Internal: farm.hip sees engine_internal.h only.
 //
@@ -570,7 +570,7 @@ void drain_after_error(Engine& E, hipStream_t st);
 inline VolDesc view_desc(const ViewPitch& p, size_t dimz) { return VolDesc{{p.y, p.z / p.y, dimz}}; }
 
 // ------------------------------------------------------------------------------------------
-// the encoder's front (engine.hip); the decoder's is decode_request.h
+// the encoder's front (encode.hip); the decoder's is decode_request.h
 // ------------------------------------------------------------------------------------------
 // what a compression call makes: a 3D container, or one 2D slice without / with the 10-byte header
 enum class Coded { Container, Slice, SliceWithHeader };
@@ -588,6 +588,7 @@ int compress_batch_to(Engine& E, const void* d_src, int is_float, size_t nvol, c
                       Coded what = Coded::Container);
 
 // ---- stage access for the parity tests (abi_stages.hip): one stage of a chunk of the plan's shape on the caller's data
+// (the encoder's stages are encode.hip's, speck3d_decode_stage is decode.hip's)
 // the integer coder on coefficients of 4 or 8 bytes (wide) and their sign words: {u8 planes, u64 total_bits, payload}
 int speck3d_encode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_coef, bool wide,
                          const uint64_t* d_sign, uint64_t raw_budget, uint8_t* d_dst, size_t dst_cap, size_t* dst_len);

@@ -7,7 +7,7 @@
 // of a chunk, at most kRegionGroups of them; a region takes the walker's state from the tagged words of the region
 // before it (DecBuffers::hiFlags, tag = plane + 1 at kRegionTagShift) and publishes its own.  Who does what:
 //
-//   carve_dec (engine.hip)   sizes the chunk's birth and leaf-event arrays: SegArray::pitch() slots each, the segment
+//   carve_dec (decode.hip)   sizes the chunk's birth and leaf-event arrays: SegArray::pitch() slots each, the segment
 //                            size by region_seg_slots
 //   dec_scan_chunk           before a plane: ticket, shared counters and the groups' counts back to zero
 //   k_lis_hi / k_lis_mx      take tickets (region_ticket); wait for the predecessor (LookBackWait); claim slots of

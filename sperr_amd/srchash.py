@@ -9,8 +9,9 @@ import os
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# what EncodeCall / DecodeCall (engine.hip) of a regular 3D volume run: transform, encoder, decoder, engine + headers
-BENCH_PATH_SOURCES = ["xform.hip", "speck_enc.hip", "speck_dec.hip", "engine.hip"]
+# what EncodeCall (encode.hip) / DecodeCall (decode.hip) of a regular 3D volume run: transform, encoder, decoder, the
+# engine's plans and its two calls + headers
+BENCH_PATH_SOURCES = ["xform.hip", "speck_enc.hip", "speck_dec.hip", "engine.hip", "encode.hip", "decode.hip"]
 
 
 def bench_path_hash():

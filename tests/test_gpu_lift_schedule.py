@@ -1,5 +1,5 @@
-"""GPU: the launches of the transform's two walks (float_stages and enqueue_inverse, engine.hip) and of the brick
-inverse (enqueue_brick_inverse: the encoder's point-wise-error reconstruction and the decoder's, with outlier correctors),
+"""GPU: the launches of the transform's two walks (float_stages, encode.hip, and enqueue_inverse, decode.hip) and of the brick
+inverse (enqueue_brick_inverse, engine.hip: the encoder's point-wise-error reconstruction and the decoder's, with outlier correctors),
 call by call.
 
 A chunk shape's schedule (ShapePlan::schedule) says which kernels run its transform; the launch tables of

@@ -667,7 +667,7 @@ def test_long_rows_and_odd_tiles(eng, oracle, shape, chunks, dtype):
 
 def test_many_chunks_decode_in_sub_batches(eng, oracle):
     """48 chunks of one shape: the decoder splits the batch into sub-batches on separate streams
-    (engine.hip, DecodeCall::pick_sub_batches); same values as the oracle."""
+    (decode.hip, DecodeCall::pick_sub_batches); same values as the oracle."""
     v = turbulence((192, 256, 256))
     want = oracle.comp_3d(v, (64, 64, 64), 1, 2.0, nthreads=8)
     got = eng.compress(cuda(v), (64, 64, 64), 2.0)

@@ -1,4 +1,4 @@
-"""GPU: calls whose shape groups need more than one batch of workspace (encode_group / decode_group, engine.hip).
+"""GPU: calls whose shape groups need more than one batch of workspace (encode_group, encode.hip / decode_group, decode.hip).
 
 A group is coded in batches of B = min(group size, max(1, budget / bytes per chunk), 256) chunks.  With B below the
 group size the batch loops run more than once: the arena is carved again for every batch, chunk ids come from
