@@ -535,6 +535,35 @@ size_t sperrhip_mask_max_size(size_t n);
 int sperrhip_mask_make_dev(const void* d_src, int is_float, size_t n, int rule, double threshold,
                            void* d_filled /* NULL: none; may be d_src */, void* d_mask, size_t mask_cap,
                            size_t* mask_len, size_t* nmissing, void* hip_stream);
+/* What stands at the missing samples of the in-filled volume.  The decode does not care: it overwrites them, and the
+ * figures of sperrhip_quality_masked_dev skip them.  The mask stream is the same for every kind.
+ *   SPERRHIP_FILL_MIDRANGE  F above, bit for bit: what the calls without a fill argument use.
+ *   SPERRHIP_FILL_VALUE     fill_value, narrowed once to float for fp32 data; -1 when it is not finite, or not finite
+ *                           after narrowing.  lo and hi are not looked at: an infinite valid sample fails nothing.
+ *   SPERRHIP_FILL_SMOOTH    a pull-push fill, which puts no cliff at the mask's boundary and so compresses better.
+ *                           Level 0 has the volume's dims, level l + 1 has ceil(d / 2) along each axis, L is the first
+ *                           level of one cell; every operation is one IEEE double operation, no fma.
+ *                           Pull, l = 0 .. L-1: a level-0 cell is known when its sample is valid, its value the sample
+ *                           widened; cell (X, Y, Z) of level l + 1 sums its known children (2X + a, 2Y + b, 2Z + c)
+ *                           inside level l from s = +0.0, through c, then b, then a, each ascending, and is known when
+ *                           it has k > 0 of them, with value s / (double)k.  An unknown top cell becomes 0.0.  A sum
+ *                           that is not finite fails the call with -1 (in the place of the midrange's lo / hi rule).
+ *                           Push, l = L-1 .. 0: an unknown cell (x, y, z) of level l, per axis with coordinate i and
+ *                           level l + 1's dim: P = i >> 1, Q = i odd ? min(P + 1, dim - 1) : (P == 0 ? 0 : P - 1);
+ *                           t = 0.75 * v(Px, Y, Z) + 0.25 * v(Qx, Y, Z) for (Y, Z) in {Py, Qy} x {Pz, Qz}, then
+ *                           u = 0.75 * t(Py, Z) + 0.25 * t(Qy, Z), then w = 0.75 * u(Pz) + 0.25 * u(Qz), every product
+ *                           and sum rounded on its own.  A missing sample becomes w, narrowed once for fp32 data.
+ *                           A volume of one sample is filled with 0.0.  Without d_filled nothing is pulled or refused. */
+#define SPERRHIP_FILL_MIDRANGE 0
+#define SPERRHIP_FILL_VALUE 1
+#define SPERRHIP_FILL_SMOOTH 2
+/* sperrhip_mask_make_dev of a volume of dimx * dimy * dimz samples (x fastest) with a fill kind: the smooth fill
+ * needs the shape.  Return codes as that call; -1 also for an unknown fill kind, a fill_value that SPERRHIP_FILL_VALUE
+ * refuses and a smooth fill's sum that is not finite, each before anything of the caller's is written.  One host wait. */
+int sperrhip_mask_make_vol_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, int rule,
+                               double threshold, int fill, double fill_value,
+                               void* d_filled /* NULL: none; may be d_src */, void* d_mask, size_t mask_cap,
+                               size_t* mask_len, size_t* nmissing, void* hip_stream);
 /* the header of a stream on the device, read on the default stream (which does not wait for a non-blocking stream);
  * any of n, nmissing, kind may be NULL.  -1: the header is refused */
 int sperrhip_mask_parse_dev(const void* d_mask, size_t mask_len, size_t* n, size_t* nmissing, int* kind);
@@ -556,6 +585,13 @@ int sperrhip_compress_masked_dev(const void* d_src, int is_float, size_t dimx, s
                                  size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
                                  int rule, double threshold, void* d_dst, size_t dst_cap, size_t* dst_len,
                                  void* d_mask, size_t mask_cap, size_t* mask_len, size_t* nmissing, void* hip_stream);
+/* the same with a fill kind (sperrhip_mask_make_vol_dev): the container is sperrhip_compress_dev's of that in-filled
+ * volume.  fill = SPERRHIP_FILL_MIDRANGE is the call above, byte for byte. */
+int sperrhip_compress_masked_fill_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                                      size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
+                                      int rule, double threshold, int fill, double fill_value, void* d_dst,
+                                      size_t dst_cap, size_t* dst_len, void* d_mask, size_t mask_cap,
+                                      size_t* mask_len, size_t* nmissing, void* hip_stream);
 /* sperrhip_decompress_portion_dev (pct 0: everything; box_lo and box_dims both NULL: the whole volume), then
  * sperrhip_mask_apply_dev with the box: bit for bit the dense decode with `value` at the missing samples.  -1
  * before anything is written where the dense calls return it, for a refused stream, and when the stream's n is not

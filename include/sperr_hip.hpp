@@ -674,6 +674,23 @@ inline auto mask_make_dev(const T* d_src, size_t n, MissingRule rule, double thr
                                                  d_mask, mask_cap, &mask_len, &nmissing, hip_stream));
 }
 
+// What stands at the missing samples of the in-filled volume (include/sperr_hip.h, SPERRHIP_FILL_*): the midrange of
+// the valid samples, a value of the caller's, or the smooth pull-push fill
+enum class FillKind : int { Midrange = SPERRHIP_FILL_MIDRANGE, Value = SPERRHIP_FILL_VALUE, Smooth = SPERRHIP_FILL_SMOOTH };
+
+// ... of a volume of dims (x, y, z) with a fill; fill_value is read by FillKind::Value alone
+template <typename T>
+inline auto mask_make_dev(const T* d_src, dims_type dims, MissingRule rule, double threshold, FillKind fill,
+                          double fill_value, T* d_filled, void* d_mask, size_t mask_cap, size_t& mask_len,
+                          size_t& nmissing, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_mask_make_vol_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2],
+                                                     static_cast<int>(rule), threshold, static_cast<int>(fill),
+                                                     fill_value, d_filled, d_mask, mask_cap, &mask_len, &nmissing,
+                                                     hip_stream));
+}
+
 // `value` at the missing samples of the box of a volume that d_vol holds (null box: the whole volume); nothing else
 template <typename T>
 inline auto mask_apply_dev(T* d_vol, dims_type vol_dims, const dims_type* box_lo, const dims_type* box_dims,
@@ -700,6 +717,24 @@ inline auto compress_masked_dev(const T* d_src, dims_type dims, dims_type chunks
                                                        chunks[1], chunks[2], m, quality, static_cast<int>(rule),
                                                        threshold, d_out, cap, &out_len, d_mask, mask_cap, &mask_len,
                                                        &nmissing, hip_stream));
+}
+
+// ... with a fill
+template <typename T>
+inline auto compress_masked_dev(const T* d_src, dims_type dims, dims_type chunks, CompMode mode, double quality,
+                                MissingRule rule, double threshold, FillKind fill, double fill_value, void* d_out,
+                                size_t cap, size_t& out_len, void* d_mask, size_t mask_cap, size_t& mask_len,
+                                size_t& nmissing, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const int m = mode == CompMode::Rate ? 1 : mode == CompMode::PSNR ? 2 : mode == CompMode::PWE ? 3 : 0;
+  if (m == 0)
+    return RTNType::CompModeUnknown;
+  return detail::mask_rtn(sperrhip_compress_masked_fill_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0],
+                                                            chunks[1], chunks[2], m, quality, static_cast<int>(rule),
+                                                            threshold, static_cast<int>(fill), fill_value, d_out, cap,
+                                                            &out_len, d_mask, mask_cap, &mask_len, &nmissing,
+                                                            hip_stream));
 }
 
 // the volume (null box) or a box of it, from the first pct percent of every chunk stream (0: all), `value` at the

@@ -48,7 +48,7 @@ EXPORTS = [
     "sperrhip_mask_max_size", "sperrhip_mask_make_dev", "sperrhip_mask_parse_dev", "sperrhip_mask_parse_stream_dev",
     "sperrhip_mask_apply_dev",
     "sperrhip_mask_expand_dev", "sperrhip_compress_masked_dev", "sperrhip_decompress_masked_dev",
-    "sperrhip_quality_masked_dev",
+    "sperrhip_quality_masked_dev", "sperrhip_mask_make_vol_dev", "sperrhip_compress_masked_fill_dev",
 ]
 
 
@@ -231,6 +231,13 @@ def load_library():
     lib.sperrhip_mask_make_dev.restype = C.c_int
     lib.sperrhip_mask_make_dev.argtypes = [_vp, C.c_int, _sz, C.c_int, C.c_double, _vp, _vp, _sz, C.POINTER(_sz),
                                            C.POINTER(_sz), _vp]
+    lib.sperrhip_mask_make_vol_dev.restype = C.c_int
+    lib.sperrhip_mask_make_vol_dev.argtypes = [_vp, C.c_int, _sz, _sz, _sz, C.c_int, C.c_double, C.c_int, C.c_double,
+                                               _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp]
+    lib.sperrhip_compress_masked_fill_dev.restype = C.c_int
+    lib.sperrhip_compress_masked_fill_dev.argtypes = [_vp, C.c_int] + [_sz] * 6 + \
+        [C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, _vp, _sz, C.POINTER(_sz), _vp, _sz,
+         C.POINTER(_sz), C.POINTER(_sz), _vp]
     lib.sperrhip_mask_parse_dev.restype = C.c_int
     lib.sperrhip_mask_parse_dev.argtypes = [_vp, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_int)]
     lib.sperrhip_mask_parse_stream_dev.restype = C.c_int
@@ -856,24 +863,50 @@ class SperrHip:
     def mask_max_size(self, n):
         return self.lib.sperrhip_mask_max_size(n)
 
-    def mask_make(self, vol, missing="nan", filled_out=None):
+    @staticmethod
+    def _fill_kind(fill):
+        """(kind, value) of include/sperr_hip.h, SPERRHIP_FILL_*: "midrange", "smooth", or the caller's number"""
+        if isinstance(fill, str):
+            if fill not in ("midrange", "smooth"):
+                raise ValueError(f'fill is "midrange", "smooth" or a number, not {fill!r}')
+            return (0 if fill == "midrange" else 2), 0.0
+        return 1, float(fill)
+
+    def mask_make(self, vol, missing="nan", filled_out=None, fill="midrange"):
         """The mask stream of a contiguous cuda tensor (float32 / float64, any shape): which samples are missing --
         NaNs, or with a number those whose absolute value is not below it -- as (cuda uint8 tensor, nmissing).
-        filled_out (same dtype and numel; may be `vol` itself) receives the in-filled samples."""
+        filled_out (same dtype and numel; may be `vol` itself) receives the in-filled samples: the missing ones hold
+        the midrange of the valid ones, the number given as `fill`, or with "smooth" a pull-push extension of the valid
+        samples into the missing region, for which the tensor's shape is (z, y, x) -- fewer dimensions lead with 1s,
+        more than three are refused."""
         torch = self.torch
         assert vol.is_cuda and vol.is_contiguous() and vol.dtype in (torch.float32, torch.float64)
         if filled_out is not None:
             assert filled_out.is_cuda and filled_out.is_contiguous() and filled_out.dtype == vol.dtype
             assert filled_out.numel() == vol.numel()
         rule, thr = self._missing_rule(missing)
+        kind, value = self._fill_kind(fill)
         n = vol.numel()
         mask = torch.empty(self.mask_max_size(n), dtype=torch.uint8, device=vol.device)
         mlen, nmiss = _sz(0), _sz(0)
-        rtn = self.lib.sperrhip_mask_make_dev(vol.data_ptr(), int(vol.dtype == torch.float32), n, rule, thr,
-                                              None if filled_out is None else filled_out.data_ptr(), mask.data_ptr(),
-                                              mask.numel(), C.byref(mlen), C.byref(nmiss), self._stream())
+        filled = None if filled_out is None else filled_out.data_ptr()
+        if kind == 0:
+            rtn = self.lib.sperrhip_mask_make_dev(vol.data_ptr(), int(vol.dtype == torch.float32), n, rule, thr,
+                                                  filled, mask.data_ptr(), mask.numel(), C.byref(mlen),
+                                                  C.byref(nmiss), self._stream())
+            if rtn != 0:
+                raise SperrHipError(f"sperrhip_mask_make_dev returned {rtn}")
+            return mask[:mlen.value], nmiss.value
+        dx, dy, dz = n, 1, 1
+        if kind == 2:
+            if vol.dim() > 3:
+                raise SperrHipError(f"a smooth fill takes a shape (z, y, x): {vol.dim()} dimensions are refused")
+            dz, dy, dx = (1,) * (3 - vol.dim()) + tuple(vol.shape)
+        rtn = self.lib.sperrhip_mask_make_vol_dev(vol.data_ptr(), int(vol.dtype == torch.float32), dx, dy, dz, rule,
+                                                  thr, kind, value, filled, mask.data_ptr(), mask.numel(),
+                                                  C.byref(mlen), C.byref(nmiss), self._stream())
         if rtn != 0:
-            raise SperrHipError(f"sperrhip_mask_make_dev returned {rtn}")
+            raise SperrHipError(f"sperrhip_mask_make_vol_dev returned {rtn}")
         return mask[:mlen.value], nmiss.value
 
     def mask_parse(self, mask):
@@ -917,24 +950,35 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_mask_expand_dev returned {rtn}")
         return out.view(torch.bool)
 
-    def compress_masked(self, vol, chunks_xyz, quality, mode=1, missing="nan"):
+    def compress_masked(self, vol, chunks_xyz, quality, mode=1, missing="nan", fill="midrange"):
         """A contiguous cuda tensor (z, y, x) with missing samples (mask_make) as (container, mask): the container is
-        compress() of the in-filled volume, which any SPERR reader decodes; the mask says which samples were missing."""
+        compress() of the in-filled volume, which any SPERR reader decodes; the mask says which samples were missing.
+        `fill` as in mask_make: "smooth" gives the smaller container, the decode is the same for every fill."""
         torch = self.torch
         assert vol.is_cuda and vol.dim() == 3 and vol.dtype in (torch.float32, torch.float64)
         self._no_view(vol, "compress_masked")
         rule, thr = self._missing_rule(missing)
+        kind, value = self._fill_kind(fill)
         dz, dy, dx = vol.shape
         out = torch.empty(self.max_compressed_size(vol.shape, chunks_xyz, quality, mode), dtype=torch.uint8,
                           device=vol.device)
         mask = torch.empty(self.mask_max_size(vol.numel()), dtype=torch.uint8, device=vol.device)
         n, mlen, nmiss = _sz(0), _sz(0), _sz(0)
-        rtn = self.lib.sperrhip_compress_masked_dev(vol.data_ptr(), int(vol.dtype == torch.float32), dx, dy, dz,
-                                                    *chunks_xyz, mode, float(quality), rule, thr, out.data_ptr(),
-                                                    out.numel(), C.byref(n), mask.data_ptr(), mask.numel(),
-                                                    C.byref(mlen), C.byref(nmiss), self._stream())
+        if kind == 0:
+            name = "sperrhip_compress_masked_dev"
+            rtn = self.lib.sperrhip_compress_masked_dev(vol.data_ptr(), int(vol.dtype == torch.float32), dx, dy, dz,
+                                                        *chunks_xyz, mode, float(quality), rule, thr, out.data_ptr(),
+                                                        out.numel(), C.byref(n), mask.data_ptr(), mask.numel(),
+                                                        C.byref(mlen), C.byref(nmiss), self._stream())
+        else:
+            name = "sperrhip_compress_masked_fill_dev"
+            rtn = self.lib.sperrhip_compress_masked_fill_dev(vol.data_ptr(), int(vol.dtype == torch.float32), dx, dy,
+                                                             dz, *chunks_xyz, mode, float(quality), rule, thr, kind,
+                                                             value, out.data_ptr(), out.numel(), C.byref(n),
+                                                             mask.data_ptr(), mask.numel(), C.byref(mlen),
+                                                             C.byref(nmiss), self._stream())
         if rtn != 0:
-            raise SperrHipError(f"sperrhip_compress_masked_dev returned {rtn}")
+            raise SperrHipError(f"{name} returned {rtn}")
         return out[:n.value], mask[:mlen.value]
 
     def decompress_masked(self, container, mask, value=float("nan"), box_lo_xyz=None, box_dims_xyz=None, pct=0,

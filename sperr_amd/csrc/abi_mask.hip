@@ -4,6 +4,7 @@
 // dense, box or portion decode through DecodeRequest and then stores `value` at the missing samples.
 #include "decode_request.h"
 #include "mask.h"
+#include "mask_fill.h"
 #include "quality.h"
 
 using namespace sperrhip;
@@ -47,19 +48,46 @@ int drain_call(Engine& E, hipStream_t st, int rtn)
   return rtn;
 }
 
-// The first half of making a mask of the n samples at d_src: the survey and the ONE host wait.  0 ok; 1 mask_cap too
-// small (*res names the size); -1 otherwise.  Nothing of the caller's is written yet
+// The first half of making a mask of the n samples at d_src: the survey, under a smooth fill the pull, and the ONE host
+// wait.  0 ok; 1 mask_cap too small (*res names the size); -1 otherwise.  Nothing of the caller's is written yet
 int mask_survey(Engine& E, const void* d_src, int is_float, size_t n, int rule, double threshold, const void* d_mask,
-                size_t mask_cap, MaskResult* res, hipStream_t st)
+                size_t mask_cap, MaskResult* res, hipStream_t st, MaskFill* fill = nullptr)
 {
   const size_t ws = mask_workspace_bytes(n);
   if (ws == 0 || (uintptr_t)d_mask % 8 != 0 || E.maskWork.ensure(ws))
     return -1;
-  if (mask_scan_run(d_src, is_float, n, rule, threshold, E.maskWork.p, res, st))
+  if (fill && fill->kind == kMaskFillSmooth) {
+    if (E.maskPyramid.ensure(fill->plan->bytes))
+      return -1;
+    fill->pyr = E.maskPyramid.p;
+  }
+  if (mask_scan_run(d_src, is_float, n, rule, threshold, E.maskWork.p, res, st, fill))
     return -1;
-  if (!res->finite)
+  // (lo and hi belong to the midrange rule: a caller's value does not look at them, the smooth rule has its own refusal)
+  if (!res->finite && !(fill && fill->kind == kMaskFillValue))
     return -1;
   return res->mask_len > mask_cap ? 1 : 0;
+}
+
+// The fill of a call: false when the kind is unknown or the caller's value is not finite as the samples hold it.  A
+// smooth fill needs the volume's dims (`plan` receives its levels); of one sample it is the value 0.0
+bool fill_of(int kind, double value, int is_float, size_t dimx, size_t dimy, size_t dimz, MaskFillPlan* plan,
+             MaskFill* fill)
+{
+  *fill = MaskFill{kind, 0.0, nullptr, nullptr};
+  if (!mask_fill_kind_ok(kind))
+    return false;
+  if (kind == kMaskFillValue)
+    return mask_fill_value_ok(value, is_float != 0, &fill->value);
+  if (kind == kMaskFillSmooth) {
+    if (!mask_fill_plan(dimx, dimy, dimz, plan))
+      return false;
+    if (plan->L == 0)
+      *fill = MaskFill{kMaskFillValue, 0.0, nullptr, nullptr};
+    else
+      fill->plan = plan;
+  }
+  return true;
 }
 
 bool volume_count(size_t dimx, size_t dimy, size_t dimz, size_t* n)
@@ -79,24 +107,39 @@ size_t sperrhip_mask_max_size(size_t n)
 int sperrhip_mask_make_dev(const void* d_src, int is_float, size_t n, int rule, double threshold, void* d_filled,
                            void* d_mask, size_t mask_cap, size_t* mask_len, size_t* nmissing, void* hip_stream)
 {
-  return guarded("sperrhip_mask_make_dev", [&]() -> int {
-    if (!d_src || !d_mask || !mask_len || !nmissing || n == 0 || n > SIZE_MAX / 8 || !mask_rule_ok(rule, threshold))
+  return sperrhip_mask_make_vol_dev(d_src, is_float, n, 1, 1, rule, threshold, SPERRHIP_FILL_MIDRANGE, 0.0, d_filled,
+                                    d_mask, mask_cap, mask_len, nmissing, hip_stream);
+}
+
+int sperrhip_mask_make_vol_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, int rule,
+                               double threshold, int fill, double fill_value, void* d_filled, void* d_mask,
+                               size_t mask_cap, size_t* mask_len, size_t* nmissing, void* hip_stream)
+{
+  return guarded("sperrhip_mask_make_vol_dev", [&]() -> int {
+    size_t n = 0;
+    MaskFillPlan plan;
+    MaskFill mf;
+    if (!d_src || !d_mask || !mask_len || !nmissing || !volume_count(dimx, dimy, dimz, &n) ||
+        !mask_rule_ok(rule, threshold) || !fill_of(fill, fill_value, is_float, dimx, dimy, dimz, &plan, &mf))
       return -1;
     Lease L;
     if (!L.e)
       return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     MaskResult res{};
-    int rtn = mask_survey(*L.e, d_src, is_float, n, rule, threshold, d_mask, mask_cap, &res, st);
+    // (without d_filled a smooth fill has nothing to fill: its pull, and its refusal, are left out)
+    if (!d_filled && mf.kind == kMaskFillSmooth)
+      mf = MaskFill{kMaskFillValue, 0.0, nullptr, nullptr};
+    int rtn = mask_survey(*L.e, d_src, is_float, n, rule, threshold, d_mask, mask_cap, &res, st, &mf);
     if (rtn >= 0)
       *mask_len = (size_t)res.mask_len;
     if (rtn == 0) {
       *nmissing = (size_t)res.nmissing;
       // (nothing missing and the fill in place: the samples are what they were)
       void* filled = res.nmissing == 0 && d_filled == d_src ? nullptr : d_filled;
-      rtn = mask_pack_fill_run(d_src, is_float, n, L.e->maskWork.p, res, d_mask, filled, st) ? -1 : 0;
+      rtn = mask_pack_fill_run(d_src, is_float, n, L.e->maskWork.p, res, d_mask, filled, st, &mf) ? -1 : 0;
     }
-    // (k_mask_pack and k_mask_fill read the engine's word array, offsets and fill value)
+    // (k_mask_pack and the fill kernels read the engine's word array, offsets, fill value and pyramid)
     return drain_call(*L.e, st, rtn);
   });
 }
@@ -175,12 +218,25 @@ int sperrhip_compress_masked_dev(const void* d_src, int is_float, size_t dimx, s
                                  double threshold, void* d_dst, size_t dst_cap, size_t* dst_len, void* d_mask,
                                  size_t mask_cap, size_t* mask_len, size_t* nmissing, void* hip_stream)
 {
-  return guarded("sperrhip_compress_masked_dev", [&]() -> int {
+  return sperrhip_compress_masked_fill_dev(d_src, is_float, dimx, dimy, dimz, chunk_x, chunk_y, chunk_z, mode, quality,
+                                           rule, threshold, SPERRHIP_FILL_MIDRANGE, 0.0, d_dst, dst_cap, dst_len, d_mask,
+                                           mask_cap, mask_len, nmissing, hip_stream);
+}
+
+int sperrhip_compress_masked_fill_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                                      size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality, int rule,
+                                      double threshold, int fill, double fill_value, void* d_dst, size_t dst_cap,
+                                      size_t* dst_len, void* d_mask, size_t mask_cap, size_t* mask_len,
+                                      size_t* nmissing, void* hip_stream)
+{
+  return guarded("sperrhip_compress_masked_fill_dev", [&]() -> int {
     if (quality <= 0.0 || mode < 1 || mode > 3)   // (before any -1, as every compress entry point)
       return 2;
     size_t n = 0;
+    MaskFillPlan plan;
+    MaskFill mf;
     if (!d_src || !d_dst || !dst_len || !d_mask || !mask_len || !nmissing || !volume_count(dimx, dimy, dimz, &n) ||
-        !mask_rule_ok(rule, threshold))
+        !mask_rule_ok(rule, threshold) || !fill_of(fill, fill_value, is_float, dimx, dimy, dimz, &plan, &mf))
       return -1;
     Lease L;
     if (!L.e)
@@ -189,7 +245,7 @@ int sperrhip_compress_masked_dev(const void* d_src, int is_float, size_t dimx, s
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const size_t esz = is_float ? sizeof(float) : sizeof(double);
     MaskResult res{};
-    const int made = mask_survey(E, d_src, is_float, n, rule, threshold, d_mask, mask_cap, &res, st);
+    const int made = mask_survey(E, d_src, is_float, n, rule, threshold, d_mask, mask_cap, &res, st, &mf);
     if (made >= 0)
       *mask_len = (size_t)res.mask_len;
     if (made != 0)
@@ -199,7 +255,7 @@ int sperrhip_compress_masked_dev(const void* d_src, int is_float, size_t dimx, s
     if (res.nmissing && E.maskStage.ensure(n * esz))
       return drain_call(E, st, -1);
     void* stage = res.nmissing ? E.maskStage.p : nullptr;
-    if (mask_pack_fill_run(d_src, is_float, n, E.maskWork.p, res, d_mask, stage, st))
+    if (mask_pack_fill_run(d_src, is_float, n, E.maskWork.p, res, d_mask, stage, st, &mf))
       return drain_call(E, st, -1);
     // (compress_to waits for the stream at its end, behind the pack and the fill)
     const void* filled = stage ? stage : d_src;

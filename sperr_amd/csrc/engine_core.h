@@ -303,6 +303,7 @@ struct Engine {
   DevBuf maskStage, maskStage2;             // missing values (mask.h): the in-filled volume the encoder reads; the
                                             //   compacted arrays of the quality call
   DevBuf maskWork;                          //   ... and the bit array, the tile counts and the partials of mask.hip
+  DevBuf maskPyramid;                       //   ... and the levels of a smooth in-fill (mask_fill.h) in global memory
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
 
@@ -425,7 +426,7 @@ struct Engine {
     plans.clear();
     planOrder.clear();
     for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork})
+                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork, &maskPyramid})
       b->drop();
     for (auto& b : outlDec)
       b.drop();
@@ -443,7 +444,7 @@ struct Engine {
   {
     size_t n = 0;
     for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork})
+                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork, &maskPyramid})
       n += b->n;
     for (const auto& b : outlDec)
       n += b.n;

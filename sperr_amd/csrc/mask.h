@@ -283,16 +283,33 @@ struct MaskResult {
 
 // bytes of workspace mask_scan_run needs for n samples (0: n is 0 or the sizes overflow), and mask_compact_run
 size_t mask_workspace_bytes(size_t n);
+// in that workspace: the bit array k_mask_survey stores, and MaskResult::finite of the read-back record (NULL: n is
+// refused).  mask_fill.hip reads the one and sets the other
+const uint64_t* mask_bit_words(void* ws, size_t n);
+uint64_t* mask_result_finite(void* ws, size_t n);
 
-// The first half of making a mask: k_mask_survey and k_mask_finish on `hip_stream`, then ONE host wait for *res.
+// what stands at the missing samples (mask_fill.h: the kinds, the smooth rule).  kMaskFillValue: `value` as the
+// samples hold it.  kMaskFillSmooth: the levels of the volume and the pyramid buffer, plan->bytes of device memory
+struct MaskFillPlan;
+struct MaskFill {
+  int kind;
+  double value;
+  const MaskFillPlan* plan;
+  void* pyr;
+};
+
+// The first half of making a mask: k_mask_survey and k_mask_finish on `hip_stream` -- and behind them the pull of a
+// smooth fill (mask_fill_pull_run) --, then ONE host wait for *res.  res->finite is the midrange rule's refusal, and
+// under a smooth fill the smooth rule's.
 // `ws`: mask_workspace_bytes(n) of device memory, 256-byte aligned; it keeps the bit array, the fill value and the
 // header for the second half.  0 ok, -1 a HIP error
 int mask_scan_run(const void* d_src, int is_float, size_t n, int rule, double threshold, void* ws, MaskResult* res,
-                  void* hip_stream);
+                  void* hip_stream, const MaskFill* fill = nullptr);
 // The second half, no host wait: the stream of res.mask_len bytes into d_mask (k_mask_pack; NULL: none) and the
-// in-filled samples into d_filled (k_mask_fill; NULL: none; may be d_src)
+// in-filled samples into d_filled (NULL: none; may be d_src): k_mask_fill with F (`fill` NULL or the midrange) or
+// with the caller's value, or the push of a smooth fill (mask_fill_push_run)
 int mask_pack_fill_run(const void* d_src, int is_float, size_t n, const void* ws, const MaskResult& res, void* d_mask,
-                       void* d_filled, void* hip_stream);
+                       void* d_filled, void* hip_stream, const MaskFill* fill = nullptr);
 
 // a stream on the device, header already parsed: d_payload is d_mask + 32 (8-byte aligned)
 struct MaskStream {

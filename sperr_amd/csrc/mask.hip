@@ -4,7 +4,8 @@
 //                            (k_mask_scan is taken: the encoder's, speck_enc.hip)
 //   k_mask_finish            one workgroup: F, the kind, the tiles' toggle offsets, the header, the read-back record
 //   k_mask_pack              the stream: header, and toggles at tile offset + rank (kind 1) or the words (kind 2)
-//   k_mask_fill<T, kVec>     dst[i] = missing ? F : src[i]; dst may be src
+//   k_mask_fill<T, kVec>     dst[i] = missing ? F : src[i], F the midrange value or the caller's; dst may be src
+//                            (the smooth fill's kernels are mask_fill.hip's)
 //   k_mask_apply<T>          `value` into the missing samples of a box of a volume, and nothing else
 //   k_mask_expand            the mask as bytes of 0 / 1
 //   k_mask_unpack            a stream of toggles as the bit array
@@ -18,6 +19,7 @@
 // The other form moves element by element and needs the alignment of T only.
 #include "common.h"
 #include "mask.h"
+#include "mask_fill.h"
 
 namespace sperrhip {
 
@@ -309,11 +311,11 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pack(const uint64_t* __re
 template <typename T, bool kVec>
 __global__ __launch_bounds__(kMaskThreads) void k_mask_fill(const T* src, T* dst, uint64_t n,
                                                             const uint64_t* __restrict__ words,
-                                                            const MaskFin* __restrict__ fin)
+                                                            const MaskFin* __restrict__ fin, double value)
 {
   constexpr uint32_t P = kVec ? kMaskPackBytes / sizeof(T) : 1;
   using Pack = typename MaskPack<T>::type;
-  const T fill = (T)fin->fill;
+  const T fill = (T)(fin ? fin->fill : value);   // (fin NULL: the caller's value)
   const uint64_t npacks = (n + P - 1) / P;
   for (uint64_t p = (uint64_t)blockIdx.x * kMaskThreads + threadIdx.x; p < npacks; p += (uint64_t)gridDim.x * kMaskThreads) {
     const uint64_t i = p * P;
@@ -511,17 +513,21 @@ int scan_launch(const T* src, size_t n, int rule, double threshold, const MaskWs
 }
 
 template <typename T>
-int fill_launch(const T* src, T* dst, size_t n, const MaskWs& w, hipStream_t st)
+int fill_launch(const T* src, T* dst, size_t n, const MaskWs& w, const MaskFill* fill, hipStream_t st)
 {
+  const MaskFin* fin = fill && fill->kind == kMaskFillValue ? nullptr : w.fin;
+  const double value = fill ? fill->value : 0.0;
   const bool vec = (uintptr_t)src % kMaskPackBytes == 0 && (uintptr_t)dst % kMaskPackBytes == 0;
   const uint64_t packs = vec ? (n + kMaskPackBytes / sizeof(T) - 1) / (kMaskPackBytes / sizeof(T)) : n;
   uint32_t groups = 0;
   if (mask_grid((packs + 63) / 64, &groups))
     return -1;
   if (vec)
-    LAUNCH_K((k_mask_fill<T, true>), dim3(groups), dim3(kMaskThreads), 0, st, src, dst, (uint64_t)n, w.words, w.fin);
+    LAUNCH_K((k_mask_fill<T, true>), dim3(groups), dim3(kMaskThreads), 0, st, src, dst, (uint64_t)n, w.words, fin,
+             value);
   else
-    LAUNCH_K((k_mask_fill<T, false>), dim3(groups), dim3(kMaskThreads), 0, st, src, dst, (uint64_t)n, w.words, w.fin);
+    LAUNCH_K((k_mask_fill<T, false>), dim3(groups), dim3(kMaskThreads), 0, st, src, dst, (uint64_t)n, w.words, fin,
+             value);
   HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -534,8 +540,20 @@ size_t mask_workspace_bytes(size_t n)
   return mask_ws(n, nullptr, kMaskMaxGroups, w) ? w.bytes : 0;
 }
 
+const uint64_t* mask_bit_words(void* ws, size_t n)
+{
+  MaskWs w;
+  return ws && mask_ws(n, ws, kMaskMaxGroups, w) ? w.words : nullptr;
+}
+
+uint64_t* mask_result_finite(void* ws, size_t n)
+{
+  MaskWs w;
+  return ws && mask_ws(n, ws, kMaskMaxGroups, w) ? &w.fin->res.finite : nullptr;
+}
+
 int mask_scan_run(const void* d_src, int is_float, size_t n, int rule, double threshold, void* ws, MaskResult* res,
-                  void* hip_stream)
+                  void* hip_stream, const MaskFill* fill)
 {
   MaskWs w;
   if (!d_src || !ws || !res || !mask_rule_ok(rule, threshold) || !mask_ws(n, ws, kMaskMaxGroups, w))
@@ -551,13 +569,18 @@ int mask_scan_run(const void* d_src, int is_float, size_t n, int rule, double th
   LAUNCH_K(k_mask_finish, dim3(1), dim3(kFinishThreads), 0, st, w.partials, groups, w.tileCnt, w.tileOff, ntiles,
            (uint64_t)n, is_float, w.fin);
   HIP_CHECK(hipGetLastError());
+  // (k_mask_top, behind k_mask_finish, sets res.finite anew: the smooth rule's refusal in the place of the midrange's)
+  if (fill && fill->kind == kMaskFillSmooth &&
+      (!fill->plan || fill->plan->cells[0] != n ||
+       mask_fill_pull_run(d_src, is_float, *fill->plan, ws, fill->pyr, hip_stream)))
+    return -1;
   HIP_CHECK(hipMemcpyAsync(res, &w.fin->res, sizeof(MaskResult), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   return 0;
 }
 
 int mask_pack_fill_run(const void* d_src, int is_float, size_t n, const void* ws, const MaskResult& res, void* d_mask,
-                       void* d_filled, void* hip_stream)
+                       void* d_filled, void* hip_stream, const MaskFill* fill)
 {
   MaskWs w;
   if (!d_src || !ws || !mask_ws(n, const_cast<void*>(ws), kMaskMaxGroups, w))
@@ -576,9 +599,14 @@ int mask_pack_fill_run(const void* d_src, int is_float, size_t n, const void* ws
              static_cast<uint8_t*>(d_mask));
     HIP_CHECK(hipGetLastError());
   }
-  if (d_filled) {
-    if (is_float ? fill_launch(static_cast<const float*>(d_src), static_cast<float*>(d_filled), n, w, st)
-                 : fill_launch(static_cast<const double*>(d_src), static_cast<double*>(d_filled), n, w, st))
+  if (d_filled && fill && fill->kind == kMaskFillSmooth) {
+    if (!fill->plan || fill->plan->cells[0] != n ||
+        mask_fill_push_run(d_src, is_float, *fill->plan, ws, fill->pyr, d_filled, hip_stream))
+      return -1;
+  }
+  else if (d_filled) {
+    if (is_float ? fill_launch(static_cast<const float*>(d_src), static_cast<float*>(d_filled), n, w, fill, st)
+                 : fill_launch(static_cast<const double*>(d_src), static_cast<double*>(d_filled), n, w, fill, st))
       return -1;
   }
   return 0;
