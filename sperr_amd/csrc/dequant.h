@@ -1,5 +1,6 @@
 // dequant.h -- how a decoded integer coefficient becomes a wavelet sample: the ONLY statement of it (the kernels of
-// speck_dec.hip, xform.hip and decode.hip that do it on their way all call these; compiled for the host as well,
+// speck_dec.hip, xform.hip (k_inv_quantize), lift_axis.hip, lift_xyz_inv.h and decode.hip that do it on their way all
+// call these; compiled for the host as well,
 // where tests/test_dequant_host.py compares every function bit for bit with the reference's two statements)
 //
 //   1. A coefficient that became significant but was never refined still holds 0 and is completed: 1.5 * 2^p - 1, p the

@@ -1,4 +1,4 @@
-// lift_window.h -- the CDF 9/7 lifting steps on a window of a row in registers (the kernels of xform.hip;
+// lift_window.h -- the CDF 9/7 lifting steps on a window of a row in registers (k_lift_xy of lift_axis.hip, the x and y passes of lift_xyz.h;
 // compiled for the host as well, where tests/test_lift_window_host.py compares the window widths bit for bit)
 #ifndef SPERR_AMD_LIFT_WINDOW_H
 #define SPERR_AMD_LIFT_WINDOW_H

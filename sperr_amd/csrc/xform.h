@@ -1,4 +1,5 @@
-// xform.h -- launchers of the floating-point stage kernels (xform.hip)
+// xform.h -- launchers of the floating-point stage kernels (conditioner and quantiser: xform.hip; lifting:
+// lift_axis.hip, lift_xyz_fwd.hip, lift_xyz_inv.hip, lift_xyz_inv_crop.hip)
 #ifndef SPERR_AMD_XFORM_H
 #define SPERR_AMD_XFORM_H
 

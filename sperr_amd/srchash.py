@@ -11,7 +11,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # what EncodeCall (encode.hip) / DecodeCall (decode.hip) of a regular 3D volume run: transform, encoder, decoder, the
 # engine's plans and its two calls + headers
-BENCH_PATH_SOURCES = ["xform.hip", "speck_enc.hip", "speck_dec.hip", "engine.hip", "encode.hip", "decode.hip"]
+BENCH_PATH_SOURCES = ["xform.hip", "lift_axis.hip", "lift_xyz_fwd.hip", "lift_xyz_inv.hip", "lift_xyz_inv_crop.hip", "speck_enc.hip", "speck_dec.hip", "engine.hip", "encode.hip", "decode.hip"]
 
 
 def bench_path_hash():

@@ -97,7 +97,7 @@ static void check_plan(size_t ncont, const Dims& full, const std::vector<Dims>& 
         for (size_t x = 0; x < box[0]; x++)
           want[((e * box[2] + z) * box[1] + y) * box[0] + x] =
               name_of(cont_of(e), lo[3 * e] + x, lo[3 * e + 1] + y, lo[3 * e + 2] + z);
-  // the crop writers' rule (crop_has / crop_addr, xform.hip): sample (x, y, z) of a chunk inside [lo, hi) goes to
+  // the crop writers' rule (crop_has / crop_addr, lift_dev.h): sample (x, y, z) of a chunk inside [lo, hi) goes to
   // ((rel[2] + z) * dims[1] + rel[1] + y) * dims[0] + rel[0] + x of an array of dims `dims`
   auto write_slots = [&](const Dims& dims, std::vector<uint64_t>& arr, std::vector<uint32_t>& hits) {
     for (size_t k = 0; k < P.slots.size(); k++) {

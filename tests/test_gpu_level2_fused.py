@@ -1,4 +1,4 @@
-"""GPU: the second transform level as one launch each way (k_lift2_fwd, k_lift2_inv<SG>, xform.hip; plan_level2,
+"""GPU: the second transform level as one launch each way (k_lift2_fwd, lift_xyz_fwd.hip; k_lift2_inv<SG>, lift_xyz_inv.hip; plan_level2,
 engine.hip) against the three per-axis passes it replaces.
 
 Every case runs with the new kernels on and with SPERR_HIP_XYZ_LEVEL2=0: the switch is read whenever a chunk shape's

@@ -1,4 +1,4 @@
-"""GPU: the fused finest-level kernels (k_lift_xyz_fwd, k_lift_xyz_inv, xform.hip) with the y and x passes in narrower
+"""GPU: the fused finest-level kernels (k_lift_xyz_fwd, lift_xyz_fwd.hip; k_lift_xyz_inv, lift_xyz_inv.hip) with the y and x passes in narrower
 windows (lift_window: 4 outputs of a 12-sample window where the workgroup then has a task per thread).
 
 Everything is compared against the CPU oracle, never against the library itself: a compressed container byte for byte

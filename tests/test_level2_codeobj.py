@@ -1,17 +1,16 @@
-"""CPU (hipcc cross-compiles gfx950 here): the kernels of the fused second transform level (k_lift2_fwd, k_lift2_inv<SG>,
-sperr_amd/csrc/xform.hip) in the code object metadata of the ISA the compiler emits with the Makefile's flags.
+"""CPU (hipcc cross-compiles gfx950 here): the kernels of the fused second transform level (k_lift2_fwd in
+sperr_amd/csrc/lift_xyz_fwd.hip, k_lift2_inv<SG> in lift_xyz_inv.hip) in the code object metadata of the ISA the
+compiler emits with the Makefile's flags.
 
 They wrap the bodies of the finest-level kernels at half the positions per thread (rows of at most 128 samples): one
 workgroup of 1024 threads per compute unit leaves a thread 128 VGPRs, and at that size neither direction may spill a
 vector register or use a byte of scratch -- a reload inside the slice loop waits for every prefetch and store in flight
 (DESIGN.md section 2b), and test_xyz_codeobj.py allows a kernel that is not in its table no scratch at all."""
-import os
 import shutil
-import subprocess
 
 import pytest
 
-from test_xyz_codeobj import FLAGS, SRC, kernel_meta
+from test_xyz_codeobj import LIFT2_UNITS, UNITS, units_meta
 
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
 
@@ -21,10 +20,7 @@ KERNELS = {"k_lift2_fwdE": "k_lift2_fwd", "k_lift2_invILb0EE": "k_lift2_inv<fals
 
 @pytest.fixture(scope="module")
 def meta(tmp_path_factory):
-    s_path = str(tmp_path_factory.mktemp("level2_codeobj") / "xform.s")
-    r = subprocess.run(["hipcc", *FLAGS, "-S", SRC, "-o", s_path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return kernel_meta(open(s_path).read())
+    return units_meta(LIFT2_UNITS, tmp_path_factory.mktemp("level2_codeobj"))
 
 
 @pytest.mark.parametrize("key", list(KERNELS))
@@ -44,4 +40,5 @@ def test_no_level2_kernel_answers_to_a_finest_level_name(meta):
     for name in meta:
         if "k_lift2_" in name:
             assert "k_lift_xyz_" not in name, name
-    assert os.path.basename(SRC) == "xform.hip"
+    # ... among the kernels of these very units: the ones it compiles include both of this test's
+    assert set(LIFT2_UNITS) <= set(UNITS) and LIFT2_UNITS == ["lift_xyz_fwd.hip", "lift_xyz_inv.hip"]

@@ -1,6 +1,8 @@
 """CPU (hipcc cross-compiles gfx950 here): registers, spills and scratch of the fused finest-level kernels
-(k_lift_xyz_fwd, k_lift_xyz_inv, sperr_amd/csrc/xform.hip), read from the code object metadata of the ISA the compiler emits
-with the Makefile's flags.
+(k_lift_xyz_fwd in sperr_amd/csrc/lift_xyz_fwd.hip, k_lift_xyz_inv in lift_xyz_inv.hip and, its crop variants,
+lift_xyz_inv_crop.hip), read from the code object metadata of the ISA the compiler emits with the Makefile's flags.  The
+kernels judged are those of the five units that were one file, xform.hip, when the figures below were taken: the
+conditioner and quantiser (xform.hip today) and the lifting units.
 
 Both kernels run one workgroup of 1024 threads per compute unit: 128 VGPRs a thread, not one more.  The forward kernel fits
 them.  The inverse kernel does not -- six z pipelines of four fp64 values per thread plus a window of the y / x pass -- and
@@ -8,7 +10,8 @@ what it spills decides whether a reload lands inside the slice loop, where `s_wa
 waits for every prefetch and store in flight.  The figures before the passes took 12-sample windows
 (lift_window) and the x pass wrote the volume itself were 44 / 52 spilled VGPRs and 100 / 108 bytes of scratch for
 <1, true, false> / <2, true, false>, the instantiations the benchmark runs; the ceilings below are what that change
-reached, so a later one cannot give it back silently.  No other kernel of the file may use more scratch than it did then."""
+reached, so a later one cannot give it back silently.  No other kernel of these units may use more scratch than it did then."""
+import concurrent.futures
 import os
 import re
 import shutil
@@ -17,7 +20,11 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "sperr_amd", "csrc", "xform.hip")
+CSRC = os.path.join(ROOT, "sperr_amd", "csrc")
+# the units with the fused second level's kernels (test_level2_codeobj.py compiles only these) and all the lifting units
+LIFT2_UNITS = ["lift_xyz_fwd.hip", "lift_xyz_inv.hip"]
+LIFT_UNITS = ["lift_axis.hip", "lift_xyz_inv_crop.hip"] + LIFT2_UNITS
+UNITS = ["xform.hip"] + LIFT_UNITS
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wno-unused-value", "--cuda-device-only"]
 
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
@@ -26,7 +33,7 @@ pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not
 PARENT = {1: (44, 100), 2: (52, 108)}
 # what the change reached (the same, pinned)
 REACHED = {1: (16, 52), 2: (22, 60)}
-# bytes of scratch of every kernel of the file that had any before the change; all others had none
+# bytes of scratch of every kernel of the units that had any before the change; all others had none
 SCRATCH_BEFORE = {
     "k_lift_axisILb0ELi1ELb1E": 40, "k_lift_axisILb0ELi2ELb1E": 40,
     "k_lift_xyz_invILi1ELb0ELb0E": 108, "k_lift_xyz_invILi2ELb0ELb0E": 108,
@@ -46,12 +53,26 @@ def kernel_meta(s_text):
     return meta
 
 
+def units_meta(units, tmp_dir):
+    """kernel_meta of the union of `units`, compiled side by side; a kernel lives in one unit"""
+    def one(unit):
+        s_path = os.path.join(str(tmp_dir), unit[:-4] + ".s")
+        r = subprocess.run(["hipcc", *FLAGS, "-S", os.path.join(CSRC, unit), "-o", s_path], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return kernel_meta(open(s_path).read())
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=len(units)) as pool:
+        metas = list(pool.map(one, units))
+    union = {}
+    for unit, m in zip(units, metas):
+        assert not set(m) & set(union), (unit, sorted(set(m) & set(union)), "a kernel in two units")
+        union.update(m)
+    return union
+
+
 @pytest.fixture(scope="module")
 def meta(tmp_path_factory):
-    s_path = str(tmp_path_factory.mktemp("xyz_codeobj") / "xform.s")
-    r = subprocess.run(["hipcc", *FLAGS, "-S", SRC, "-o", s_path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    m = kernel_meta(open(s_path).read())
+    m = units_meta(UNITS, tmp_path_factory.mktemp("xyz_codeobj"))
     assert len(m) >= 40, sorted(m)
     return m
 
