@@ -53,7 +53,7 @@ int decode_packed_host(const uint8_t* h, const ContainerInfo& ci, const std::vec
     i = j;
   }
   if (rtn == 0) {
-    Lease L;
+    Lease L(nullptr);   // (the host entry points run on stream 0)
     rtn = L.e ? decode(*L.e, d_in, packed, d_out) : -1;
   }
   if (rtn == 0) {
@@ -132,12 +132,13 @@ using namespace sperrhip;
 
 // what the device decode entry points begin with: an engine leased, the caller's stream, the container's header read
 struct DevDecode {
+  hipStream_t st;   // (before the lease, which takes it)
   Lease L;
-  hipStream_t st;
   ContainerInfo ci;
   const bool ok;
   DevDecode(const void* d_src, size_t src_len, void* hip_stream)
       : st(static_cast<hipStream_t>(hip_stream)),
+        L(st),
         ok(L.e && read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st) == 0)
   {
   }
@@ -322,7 +323,7 @@ int sperrhip_compress_dev(const void* d_src, int is_float, size_t dimx, size_t d
       return 2;
     if (!d_src || !d_dst || !dst_len || dimx == 0 || dimy == 0 || dimz == 0)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -344,7 +345,7 @@ int sperrhip_compress_view_dev(const void* d_src, const sperrhip_view* view, int
     const ViewPitch pitch{view->pitch_y, view->pitch_z};
     if (!view_valid(dimx, dimy, dimz, pitch))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -428,7 +429,7 @@ int sperrhip_compress_batch_dev(const void* d_src, int is_float, size_t nvol, si
       return -1;
     if (nvol > 0xffffffffull / dimz)   // (chunk origins of the stacked view are 32-bit)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -446,7 +447,7 @@ int sperrhip_decompress_batch_dev(const void* d_src, const size_t* offsets, size
   return guarded("sperrhip_decompress_batch_dev", [&]() -> int {
     if (!d_src || !offsets || !d_dst || nvol == 0)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -676,7 +677,7 @@ int sperrhip_compress_2d_dev(const void* d_src, int is_float, size_t dimx, size_
       return 2;
     if (!d_src || !d_dst || !dst_len || dimx == 0 || dimy == 0)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -695,7 +696,7 @@ int sperrhip_decompress_2d_dev(const void* d_src, size_t src_len, int output_flo
   return guarded("sperrhip_decompress_2d_dev", [&]() -> int {
     if (!d_src || !d_dst || dimx == 0 || dimy == 0 || src_len < 17)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -728,7 +729,7 @@ int sperrhip_compress_2d_batch_dev(const void* d_src, int is_float, size_t nslic
       return -1;
     if (nslice > 0xffffffffull)   // (chunk origins of the stacked view are 32-bit)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -768,7 +769,7 @@ int sperrhip_decompress_2d_batch_dev(const void* d_src, const size_t* offsets, s
       all.len.push_back(offsets[s + 1] - offsets[s] - H);
       list[s] = {0, dimx, 0, dimy, s, 1};
     }
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -873,7 +874,7 @@ int sperrhip_decompress_2d_multires_dev(const void* d_src, size_t src_len, int o
   return guarded("sperrhip_decompress_2d_multires_dev", [&]() -> int {
     if (!d_src || !d_dst || dimx == 0 || dimy == 0 || src_len < 17 || (nlev && !d_levels))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -1054,7 +1055,7 @@ int sperrhip_decompress_boxes_dev(const void* const* d_srcs, const size_t* src_l
     for (int a = 0; a < 3; a++)
       if (box_dims[a] == 0)
         return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -1324,7 +1325,7 @@ int sperrhip_trunc_batch_dev(const void* d_src, const size_t* offsets, size_t nv
   return guarded("sperrhip_trunc_batch_dev", [&]() -> int {
     if (!d_src || !offsets || !out_offsets || nvol == 0)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     return trunc_impl(*L.e, static_cast<const uint8_t*>(d_src), offsets, nvol, pct, static_cast<uint8_t*>(d_dst),
@@ -1356,7 +1357,7 @@ int sperrhip_quality_batch_dev(const void* d_orig, const void* d_recon, int is_f
     const size_t need = quality_workspace_bytes(nvol, n, is_float);
     if (need == 0)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e || L.e->arena.ensure(need))
       return -1;
     const int rtn = quality_run(d_orig, d_recon, is_float, nvol, n, L.e->arena.p, out, hip_stream);
@@ -1387,7 +1388,7 @@ int sperrhip_quality_view_dev(const void* d_orig, const sperrhip_view* view_orig
     const ViewPitch pr = view_recon ? ViewPitch{view_recon->pitch_y, view_recon->pitch_z} : dense;
     if (!view_valid(dimx, dimy, dimz, po) || !view_valid(dimx, dimy, dimz, pr))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e || L.e->arena.ensure(need))
       return -1;
     const int rtn = quality_view_run(d_orig, po, d_recon, pr, is_float, dimx, dimy, dimz, L.e->arena.p, out, hip_stream);
@@ -1416,7 +1417,7 @@ int sperrhip_fields_gather_dev(const void* d_src, const sperrhip_fields* layout,
     if (!d_src || !d_dst || !fields_stacked(nfields, dimx, dimy, dimz, &count) || count > dst_cap_bytes / esz)
       return -1;
     const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -1439,7 +1440,7 @@ int sperrhip_fields_scatter_dev(const void* d_src, size_t nfields, int is_float,
     const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
     if (!fields_fits(nfields, dimx, dimy, dimz, l, esz, dst_cap_bytes))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -1465,7 +1466,7 @@ int sperrhip_compress_fields_dev(const void* d_src, const sperrhip_fields* layou
     const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
     if (!fields_valid(nfields, dimx, dimy, dimz, l))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -1491,7 +1492,7 @@ int sperrhip_decompress_fields_dev(const void* d_src, const size_t* offsets, siz
     const FieldsLayout l = fields_layout_of(layout, nfields, dimx, dimy);
     if (!fields_fits(nfields, dimx, dimy, dimz, l, esz, dst_cap_bytes))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -1535,7 +1536,7 @@ int sperrhip_quality_fields_dev(const void* d_orig, const sperrhip_fields* layou
     const size_t n = count / nfields, need = quality_workspace_bytes(nfields, n, is_float);
     if (need == 0)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;

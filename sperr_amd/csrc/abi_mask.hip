@@ -122,7 +122,7 @@ int sperrhip_mask_make_vol_dev(const void* d_src, int is_float, size_t dimx, siz
     if (!d_src || !d_mask || !mask_len || !nmissing || !volume_count(dimx, dimy, dimz, &n) ||
         !mask_rule_ok(rule, threshold) || !fill_of(fill, fill_value, is_float, dimx, dimy, dimz, &plan, &mf))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -186,7 +186,7 @@ int sperrhip_mask_apply_dev(void* d_vol, int is_float, const size_t vol_dims[3],
     MaskStream m;
     if (read_mask_stream(d_mask, mask_len, m, st) || m.h.n != n)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     if (mask_apply_run(d_vol, is_float, vol_dims, lo, dims, m, value, st))
@@ -204,7 +204,7 @@ int sperrhip_mask_expand_dev(const void* d_mask, size_t mask_len, unsigned char*
     MaskStream m;
     if (read_mask_stream(d_mask, mask_len, m, st) || m.h.n != n)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     if (mask_expand_run(m, d_out, st))
@@ -238,7 +238,7 @@ int sperrhip_compress_masked_fill_dev(const void* d_src, int is_float, size_t di
     if (!d_src || !d_dst || !dst_len || !d_mask || !mask_len || !nmissing || !volume_count(dimx, dimy, dimz, &n) ||
         !mask_rule_ok(rule, threshold) || !fill_of(fill, fill_value, is_float, dimx, dimy, dimz, &plan, &mf))
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -277,7 +277,7 @@ int sperrhip_decompress_masked_dev(const void* d_src, size_t src_len, unsigned p
     if (read_mask_stream(d_mask, mask_len, m, st))
       return -1;
     // (the lease, the stream, the container's header: what every device decode begins with)
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     ContainerInfo ci;
     if (!L.e || read_container_info(static_cast<const uint8_t*>(d_src), src_len, ci, st) != 0)
       return -1;
@@ -320,7 +320,7 @@ int sperrhip_quality_masked_dev(const void* d_orig, const void* d_recon, int is_
     const size_t need = quality_workspace_bytes(1, nvalid, is_float), ws = mask_workspace_bytes(n);
     if (need == 0 || ws == 0)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;

@@ -12,7 +12,7 @@ int sperrhip_dwt3d_dev(double* d_vals, size_t dimx, size_t dimy, size_t dimz, in
                        void* hip_stream)
 {
   return guarded("sperrhip_dwt3d_dev", [&]() -> int {
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -46,7 +46,7 @@ int sperrhip_speck3d_encode_dev(const void* d_coef, int width, const uint64_t* d
   return guarded("sperrhip_speck3d_encode_dev", [&]() -> int {
     if (width != 4 && width != 8)
       return 2;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -68,7 +68,7 @@ int sperrhip_outlier_encode_dev(const void* d_orig, int is_float, const double* 
       return 2;
     if (nchunks > 0xffffffffull / dimz)   // (a chunk's origin along z is a uint32)
       return 2;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;
@@ -88,7 +88,7 @@ int sperrhip_speck3d_decode_dev(const void* d_stream, size_t stream_len, size_t 
   return guarded("sperrhip_speck3d_decode_dev", [&]() -> int {
     if (stream_len < 9)
       return -1;
-    Lease L;
+    Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
     Engine& E = *L.e;

@@ -752,6 +752,7 @@ struct DecodeCall {
   // decode through the serial walk, one wavefront each) are not waited for one by one: each gets
   // its own piece of the arena and one of the sub-streams, and all of them are drained together.
   bool deferOK = false, deferSized = false, deferForked = false;
+  bool arenaCarved = false;   // a batch of this call has carved the arena (decode_batch: the poison fill of the next)
   std::vector<SubHost*> pending;
   size_t deferOff = 0;
   uint32_t deferNext = 0;
@@ -1016,6 +1017,18 @@ struct DecodeCall {
     A.base = static_cast<char*>(E.arena.p) + (b.deferG ? deferOff : 0);
     A.cap = E.arena.n - (b.deferG ? deferOff : 0);
     b.deferStream = nullptr;
+    // A batch at the arena's start lies over what the call carved before, and nothing of that is in flight: a batch that
+    // is not deferred ends in a wait (collect_states), the deferred ones have been drained.  Under the poison switch
+    // the arena is filled again on the caller's stream, which the sub-streams are forked from (again, below).  Deferred
+    // groups further in lie beside groups in flight, over memory that fill has covered
+    if (!b.deferG || deferOff == 0) {
+      bool filled = false;
+      if (arenaCarved && E.poison_arena(st, &filled))
+        return -1;
+      if (filled)
+        deferForked = false;
+      arenaCarved = true;
+    }
     if (b.deferG) {
       if (!deferForked) {   // the sub-streams start behind what the caller's stream holds
         HIP_CHECK(hipEventRecord(E.evFork, st));

@@ -1213,6 +1213,10 @@ struct EncodeCall {
   {
     const uint32_t nb = b.nb;
     const uint32_t* cd = b.P->dims;
+    // (a further batch of workspace lies over the earlier one's, whose work this stream is behind: under the poison
+    //  switch the arena is filled again.  Groups side by side have a piece each, carved once)
+    if (!sideBySide && batches.size() > 1 && E.poison_arena(b.ss))
+      return -1;
     Arena A;
     A.base = static_cast<char*>(E.arena.p) + (sideBySide ? groupOff[gi] : 0);
     A.cap = E.arena.n - (sideBySide ? groupOff[gi] : 0);

@@ -28,6 +28,7 @@ bool g_prof_on = false;
 std::string g_prof_only;
 std::mutex g_prof_cfg_mu;
 thread_local Profiler* t_prof = nullptr;       // the profiler of the engine this thread drives
+thread_local hipStream_t t_call_stream = nullptr;   // ... and the stream of its call (Lease; the poison fills)
 static thread_local const char* t_prof_cur = nullptr;
 static thread_local hipEvent_t t_prof_a = nullptr;
 std::atomic<unsigned long long> g_dbg_counter[4];   // sperrhip_debug_counter (0..2, and [3] as counter 7)
@@ -467,7 +468,7 @@ int build_plan(ShapePlan& P, size_t dx, size_t dy, size_t dz, bool twoD)
         P.l2Level = (int)l;
       break;
     }
-  if (P.tables.ensure(blob.bytes.size()))
+  if (P.tables.ensure(blob.bytes.size(), false))   // (constant data: not a workspace, never poisoned)
     return -1;
   HIP_CHECK(hipMemcpy(P.tables.p, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice));
   char* base = static_cast<char*>(P.tables.p);

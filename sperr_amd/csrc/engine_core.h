@@ -28,6 +28,7 @@
 #include "speck_enc.h"
 #include "speck_tree_host.hpp"
 #include "outlier.h"
+#include "poison_env.h"
 #include "view.h"
 #include "xform.h"
 
@@ -119,6 +120,22 @@ extern std::vector<uint64_t> g_lis_stamps_host;            //   chunk 0 of the l
 // ------------------------------------------------------------------------------------------
 // small helpers
 // ------------------------------------------------------------------------------------------
+// The workspace poison (poison_env.h).  The stream of the call this thread makes, set by its Lease:
+// what a call allocates on the way is filled there.  A sub-batch's own host thread has none: stream 0
+extern thread_local hipStream_t t_call_stream;
+
+// `n` bytes at `p` that were allocated just now, filled before their first use, whichever stream that is on: the host
+// waits for the fill.  Nothing is queued with the switch off
+inline int poison_fresh(void* p, size_t n)
+{
+  const int v = poison_env();
+  if (v < 0 || !p || !n)
+    return 0;
+  HIP_CHECK(hipMemsetAsync(p, v, n, t_call_stream));
+  HIP_CHECK(hipStreamSynchronize(t_call_stream));
+  return 0;
+}
+
 struct DevBuf {
   void* p = nullptr;
   size_t n = 0;
@@ -129,7 +146,9 @@ struct DevBuf {
     p = nullptr;
     n = 0;
   }
-  int ensure(size_t bytes)
+  // workspace: the buffer is a call's working memory, which the poison switch fills (not a plan's tables, which are
+  // uploaded whole and once)
+  int ensure(size_t bytes, bool workspace = true)
   {
     if (bytes <= n)
       return 0;
@@ -151,7 +170,7 @@ struct DevBuf {
     if (!p)
       HIP_CHECK(hipMalloc(&p, want));
     n = want;
-    return 0;
+    return workspace ? poison_fresh(p, n) : 0;
   }
 };
 
@@ -419,41 +438,81 @@ struct Engine {
   }
   // sperrhip_release(): everything an idle engine holds in HBM goes back (streams and events
   // stay; the next call sizes the workspaces again).  The engine's device is current.
+  // THE list of the engine's workspace buffers: the arena, the containers' slots, and what point-wise error mode adds
+  // (the outlier coder's arrays, the boxes of the coarser levels, the outlier streams) and the staging buffers of the
+  // fields, boxes and mask calls.  drop_memory, device_bytes and the poison fill walk it, so a buffer added here is
+  // dropped, counted and poisoned alike.  (Not the plans' tables: constant data, uploaded once)
+  template <typename Self, typename F>
+  static void walk_buffers(Self& e, F&& f)
+  {
+    for (auto* b : {&e.arena, &e.slots, &e.misc, &e.outlFixed, &e.outlVar, &e.outlStream, &e.pweBox, &e.wideScratch,
+                    &e.fieldsStage, &e.fieldsStage2, &e.boxesStage, &e.maskStage, &e.maskStage2, &e.maskWork,
+                    &e.maskPyramid})
+      f(*b);
+    for (auto& b : e.outlDec)
+      f(b);
+    for (auto& b : e.decBox)
+      f(b);
+    for (auto& b : e.pweBufs)
+      if (b)
+        f(*b);
+  }
   void drop_memory()
   {
     for (auto& kv : plans)
       kv.second->tables.drop();
     plans.clear();
     planOrder.clear();
-    for (DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork, &maskPyramid})
-      b->drop();
-    for (auto& b : outlDec)
-      b.drop();
-    for (auto& b : decBox)
-      b.drop();
-    for (auto& b : pweBufs)
-      if (b)
-        b->drop();
+    walk_buffers(*this, [](DevBuf& b) { b.drop(); });
     pweBufs.clear();
   }
-  // every device buffer of the engine: the arena, the containers' slots, and what point-wise error mode adds (the
-  // outlier coder's arrays, the boxes of the coarser levels, the outlier streams) and the staging buffers of the
-  // fields and mask calls -- sperrhip_debug_counter(6)
+  // every workspace buffer of the engine -- sperrhip_debug_counter(6)
   size_t device_bytes() const
   {
     size_t n = 0;
-    for (const DevBuf* b : {&arena, &slots, &misc, &outlFixed, &outlVar, &outlStream, &pweBox, &wideScratch, &fieldsStage,
-                      &fieldsStage2, &boxesStage, &maskStage, &maskStage2, &maskWork, &maskPyramid})
-      n += b->n;
-    for (const auto& b : outlDec)
-      n += b.n;
-    for (const auto& b : decBox)
-      n += b.n;
-    for (const auto& b : pweBufs)
-      if (b)
-        n += b->n;
+    walk_buffers(*this, [&n](const DevBuf& b) { n += b.n; });
     return n;
+  }
+  // ---- the workspace poison (SPERR_HIP_POISON, poison_env.h) ----
+  // A call has leased the engine and has queued nothing yet: every buffer the engine holds is filled on the call's
+  // stream, and every stream of the engine waits for the fill, so that it stands in front of the call's first kernel
+  // wherever the call forks to.  (Nothing of the engine is in flight: a call ends in a wait of the host.)  With the
+  // switch off nothing is queued; *filled says whether anything was
+  int poison_fill(hipStream_t st, bool* filled)
+  {
+    *filled = false;
+    const int v = poison_env();
+    if (v < 0)
+      return 0;
+    int rc = 0;
+    walk_buffers(*this, [&](DevBuf& b) {
+      if (rc == 0 && b.p && hipMemsetAsync(b.p, v, b.n, st) != hipSuccess)
+        rc = -1;
+    });
+    if (rc) {
+      fprintf(stderr, "[sperr_hip] the poison fill failed: %s\n", hipGetErrorString(hipGetLastError()));
+      return -1;
+    }
+    *filled = true;
+    HIP_CHECK(hipEventRecord(evFork, st));
+    for (uint32_t q = 0; q < kSubStreams; q++) {
+      HIP_CHECK(hipStreamWaitEvent(sub[q], evFork, 0));
+      HIP_CHECK(hipStreamWaitEvent(outlQ[q], evFork, 0));
+      HIP_CHECK(hipStreamWaitEvent(sideQ[q], evFork, 0));
+    }
+    return 0;
+  }
+  // A call carves the arena again for a further batch of workspace (a cap on the arena, more than 256 chunks of a
+  // shape, a second shape group): `ss` is the stream that uses the arena first, and the earlier batch has been waited
+  // for by the host.  *filled as above
+  int poison_arena(hipStream_t ss, bool* filled = nullptr)
+  {
+    const int v = poison_env();
+    if (filled)
+      *filled = v >= 0 && arena.p;
+    if (v >= 0 && arena.p)
+      HIP_CHECK(hipMemsetAsync(arena.p, v, arena.n, ss));
+    return 0;
   }
   // called between calls only (no kernel of this engine is in flight)
   void trim_plans()
@@ -540,20 +599,39 @@ struct EnginePool {
 extern EnginePool g_pool;   // (engine.hip)
 
 // a call's hold on an engine; also makes the engine's profiler the calling thread's
+// `st` is the call's stream: under the poison switch the engine's buffers are filled on it before the call does anything
+// (Engine::poison_fill; a fill that fails gives the engine back: e is null)
 struct Lease {
   Engine* e;
-  Lease() : e(g_pool.acquire())
+  hipStream_t st;
+  bool poisoned = false;
+  explicit Lease(hipStream_t stream) : e(g_pool.acquire()), st(stream)
   {
     if (e) {
-      std::lock_guard<std::mutex> lock(g_prof_cfg_mu);
-      e->prof.on = g_prof_on;
-      e->prof.only = g_prof_only;
-      t_prof = &e->prof;
+      {
+        std::lock_guard<std::mutex> lock(g_prof_cfg_mu);
+        e->prof.on = g_prof_on;
+        e->prof.only = g_prof_only;
+        t_prof = &e->prof;
+      }
+      t_call_stream = st;
+      if (e->poison_fill(st, &poisoned)) {
+        (void)hipStreamSynchronize(st);
+        t_prof = nullptr;
+        t_call_stream = nullptr;
+        g_pool.release(e);
+        e = nullptr;
+      }
     }
   }
   ~Lease()
   {
     if (e) {
+      // (a call whose kernels use nothing of the engine's may end without a wait, abi_mask.hip: the fill it queued must
+      //  not run into the engine's next call on another stream)
+      if (poisoned)
+        (void)hipStreamSynchronize(st);
+      t_call_stream = nullptr;
       t_prof = nullptr;
       e->trim_plans();
       g_pool.release(e);
