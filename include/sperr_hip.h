@@ -604,6 +604,67 @@ int sperrhip_decompress_masked_dev(const void* d_src, size_t src_len, unsigned p
 int sperrhip_quality_masked_dev(const void* d_orig, const void* d_recon, int is_float, size_t n,
                                 const void* d_mask, size_t mask_len, double* out, void* hip_stream);
 
+/* ---- relative error ------------------------------------------------------------------------- */
+
+/* A point-wise RELATIVE bound, |x' - x| <= eps * |x| per sample, zeros and signs exact.  A volume x is an ordinary
+ * container of a DOUBLE volume y in point-wise error mode, which any SPERR reader opens, and a side stream with the
+ * samples' zero bits and sign bits.  The rule (sperr_amd/csrc/rel.h is its one statement, with the derivation):
+ *   forward    d = (double)x.  Zero class: fabs(d) < 0x1p-1022 (+-0.0, double subnormals; no nonzero float).  Sign:
+ *              d's sign bit.  Outside the zero class, E the biased exponent field of d and M its 52 mantissa bits,
+ *              y = (double)((int)E - 1023) + (double)M * 0x1p-52; for fp32 data a y < -126 (a subnormal float, whose
+ *              narrowing has an absolute grid) becomes -126 + 2 * (y + 126); in the zero class y is the NaN
+ *              0x7ff8000000000000, which the encoder in-fills as a missing value (SPERRHIP_MISSING_NAN, the fill given)
+ *   tolerance  t = eps / (1.0 + eps) - s in double, s = 0x1p-22 for fp32 data and 0x1p-40 for fp64 data; eps is
+ *              refused unless it is finite, eps <= 0.5 and t >= s.  The container is mode 3 at quality t
+ *   inverse    zero bit: a zero with its sign bit.  Otherwise, the source fp32 data and y' < -126:
+ *              y' = -126 + 0.5 * (y' + 126); then y' clamped into [-1080, nextafter(1024, 0)],
+ *              e = floor(y'), m = y' - e, ldexp(1.0 + m, (int)e), narrowed once for float output (FLT_MAX where that
+ *              overflows), then the sign bit
+ *   stream     "SPRL", little-endian, 8-byte aligned: 0-3 "SPRL" | 4 version 1 | 5 is_float of the source | 6-7 0 |
+ *              8-15 the bits of eps (+0.0 from sperrhip_rel_forward_dev, which states no bound) | 16-23 n |
+ *              24-31 length of the zero stream | 32-39 length of the sign stream | 40-47 0 | the zero stream,
+ *              padding to 8 bytes, the sign stream: two mask streams as above, bit 1 = zero class / negative
+ * A portion decode (pct other than 0 or 100) carries no bound: finite values, zeros and
+ * signs exact.  A side stream that is handed in has its three headers checked; its payload is trusted, as a mask's.
+ * Return codes follow the masked calls: 0 ok; 1 side_cap too small, *side_len the size needed; -1, before anything
+ * of the caller's is written: NULL pointers, n == 0, a refused eps, a sample that is not finite, a refused side
+ * stream, n against the container's volume, a container that is not a double one, a box that leaves the volume.
+ * Out of scope, refused where it can be reached: samples that are not finite, rate and PSNR modes of y, views,
+ * batches, fields, slices, levels and multires, the host calls and the farm, the command line tools. */
+/* t of eps.  Host only.  -1: eps is refused */
+int sperrhip_rel_tolerance(double eps, int is_float, double* t);
+/* 48 + 2 * sperrhip_mask_max_size(n).  Host only. */
+size_t sperrhip_rel_max_size(size_t n);
+/* y of the n samples at d_src into d_y (n doubles, no overlap with d_src) and the side stream into d_side.  One host
+ * wait. */
+int sperrhip_rel_forward_dev(const void* d_src, int is_float, size_t n, void* d_y, void* d_side, size_t side_cap,
+                             size_t* side_len, size_t* nzero, size_t* nneg, void* hip_stream);
+/* d_y holds y' of the box [box_lo, box_lo + box_dims) of a volume of vol_dims densely (both NULL: the whole volume):
+ * x' into d_dst, floats or doubles; d_dst may be d_y when doubles. */
+int sperrhip_rel_inverse_dev(const void* d_y, const size_t vol_dims[3], const size_t box_lo[3],
+                             const size_t box_dims[3], const void* d_side, size_t side_len, int output_float,
+                             void* d_dst, void* hip_stream);
+/* The forward map into a buffer the library keeps, then sperrhip_compress_masked_fill_dev of y with is_float = 0,
+ * mode 3, quality t, SPERRHIP_MISSING_NAN and the fill given (fill_value in y's domain): the container and the zero
+ * stream are byte for byte that call's.  Return codes as that call and as above. */
+int sperrhip_compress_rel_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                              size_t chunk_y, size_t chunk_z, double eps, int fill, double fill_value, void* d_dst,
+                              size_t dst_cap, size_t* dst_len, void* d_side, size_t side_cap, size_t* side_len,
+                              void* hip_stream);
+/* sperrhip_decompress_masked_dev's decode (pct, box) as doubles into a buffer the library keeps, then the inverse
+ * into d_dst.  One host wait more than that call. */
+int sperrhip_decompress_rel_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
+                                const size_t box_lo[3], const size_t box_dims[3], const void* d_side, size_t side_len,
+                                void* d_dst, size_t dst_cap_bytes, void* hip_stream);
+/* the headers of a side stream, read on hip_stream; any of the outputs may be NULL.  -1: the stream is refused */
+int sperrhip_rel_parse_stream_dev(const void* d_side, size_t side_len, int* is_float, double* eps, size_t* n,
+                                  size_t* nzero, size_t* nneg, void* hip_stream);
+/* out[4]: over the samples whose original is outside the zero class the largest |x' - x| / |x| in double and how
+ * many have |x' - x| > eps * |x|; how many samples differ in zero class or in sign; the count of samples outside the
+ * zero class.  One kernel, one host wait.  -1: a NULL pointer, n == 0, eps not finite or negative. */
+int sperrhip_rel_check_dev(const void* d_orig, const void* d_recon, int is_float, size_t n, double eps, double* out,
+                           void* hip_stream);
+
 /* ---- profiling ------------------------------------------------------------------------------ */
 
 /* When enabled, the engine brackets every pipeline stage with HIP events on the launch stream

@@ -762,6 +762,74 @@ inline auto quality_masked_dev(const T* d_orig, const T* d_recon, size_t n, cons
                                                       hip_stream));
 }
 
+// (this library's addition) Point-wise relative error (include/sperr_hip.h, "relative error"): |x' - x| <= eps |x|, zeros
+// and signs exact; a container of the double volume y and a side stream.  RTNType::WrongLength: the side buffer (or the
+// container's) is too small, side_len then names the size needed.
+// t of eps for fp32 (T = float) or fp64 data; Error: eps is refused
+template <typename T>
+inline auto rel_tolerance(double eps, double& t) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_rel_tolerance(eps, sizeof(T) == 4, &t));
+}
+
+// y of n samples into d_y and their side stream (which states no bound) into d_side
+template <typename T>
+inline auto rel_forward_dev(const T* d_src, size_t n, double* d_y, void* d_side, size_t side_cap, size_t& side_len,
+                            size_t& nzero, size_t& nneg, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_rel_forward_dev(d_src, sizeof(T) == 4, n, d_y, d_side, side_cap, &side_len, &nzero,
+                                                   &nneg, hip_stream));
+}
+
+// x' of y' of the box of a volume that d_y holds (null box: the whole volume); d_out may be d_y when T is double
+template <typename T>
+inline auto rel_inverse_dev(const double* d_y, dims_type vol_dims, const dims_type* box_lo, const dims_type* box_dims,
+                            const void* d_side, size_t side_len, T* d_out, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_rel_inverse_dev(d_y, vol_dims.data(), box_lo ? box_lo->data() : nullptr,
+                                                   box_dims ? box_dims->data() : nullptr, d_side, side_len,
+                                                   sizeof(T) == 4, d_out, hip_stream));
+}
+
+// fill_value (y's domain) is read by FillKind::Value alone
+template <typename T>
+inline auto compress_rel_dev(const T* d_src, dims_type dims, dims_type chunks, double eps, FillKind fill,
+                             double fill_value, void* d_out, size_t cap, size_t& out_len, void* d_side, size_t side_cap,
+                             size_t& side_len, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_compress_rel_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0],
+                                                    chunks[1], chunks[2], eps, static_cast<int>(fill), fill_value, d_out,
+                                                    cap, &out_len, d_side, side_cap, &side_len, hip_stream));
+}
+
+// the volume (null box) or a box of it, from the first pct percent of every chunk stream (0: all; a portion carries no
+// bound)
+template <typename T>
+inline auto decompress_rel_dev(const void* d_stream, size_t stream_len, const void* d_side, size_t side_len, T* d_out,
+                               size_t cap_bytes, const dims_type* box_lo = nullptr, const dims_type* box_dims = nullptr,
+                               unsigned pct = 0, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_decompress_rel_dev(d_stream, stream_len, pct, sizeof(T) == 4,
+                                                      box_lo ? box_lo->data() : nullptr,
+                                                      box_dims ? box_dims->data() : nullptr, d_side, side_len, d_out,
+                                                      cap_bytes, hip_stream));
+}
+
+// out: the largest |x' - x| / |x|, the samples beyond eps, the samples that differ in zero class or sign, the samples
+// whose original is no zero
+template <typename T>
+inline auto rel_check_dev(const T* d_orig, const T* d_recon, size_t n, double eps, std::array<double, 4>& out,
+                          void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_rel_check_dev(d_orig, d_recon, sizeof(T) == 4, n, eps, out.data(), hip_stream));
+}
+
 }  // namespace sperr
 
 #endif

@@ -49,6 +49,9 @@ EXPORTS = [
     "sperrhip_mask_apply_dev",
     "sperrhip_mask_expand_dev", "sperrhip_compress_masked_dev", "sperrhip_decompress_masked_dev",
     "sperrhip_quality_masked_dev", "sperrhip_mask_make_vol_dev", "sperrhip_compress_masked_fill_dev",
+    "sperrhip_rel_tolerance", "sperrhip_rel_max_size", "sperrhip_rel_forward_dev", "sperrhip_rel_inverse_dev",
+    "sperrhip_compress_rel_dev", "sperrhip_decompress_rel_dev", "sperrhip_rel_parse_stream_dev",
+    "sperrhip_rel_check_dev",
 ]
 
 
@@ -256,6 +259,27 @@ def load_library():
                                                    _sz, C.c_double, _vp, _sz, _vp]
     lib.sperrhip_quality_masked_dev.restype = C.c_int
     lib.sperrhip_quality_masked_dev.argtypes = [_vp, _vp, C.c_int, _sz, _vp, _sz, C.POINTER(C.c_double), _vp]
+    lib.sperrhip_rel_tolerance.restype = C.c_int
+    lib.sperrhip_rel_tolerance.argtypes = [C.c_double, C.c_int, C.POINTER(C.c_double)]
+    lib.sperrhip_rel_max_size.restype = _sz
+    lib.sperrhip_rel_max_size.argtypes = [_sz]
+    lib.sperrhip_rel_forward_dev.restype = C.c_int
+    lib.sperrhip_rel_forward_dev.argtypes = [_vp, C.c_int, _sz, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz),
+                                             C.POINTER(_sz), _vp]
+    lib.sperrhip_rel_inverse_dev.restype = C.c_int
+    lib.sperrhip_rel_inverse_dev.argtypes = [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, C.c_int,
+                                             _vp, _vp]
+    lib.sperrhip_compress_rel_dev.restype = C.c_int
+    lib.sperrhip_compress_rel_dev.argtypes = [_vp, C.c_int] + [_sz] * 6 + [C.c_double, C.c_int, C.c_double, _vp, _sz,
+                                                                          C.POINTER(_sz), _vp, _sz, C.POINTER(_sz), _vp]
+    lib.sperrhip_decompress_rel_dev.restype = C.c_int
+    lib.sperrhip_decompress_rel_dev.argtypes = [_vp, _sz, C.c_uint, C.c_int, C.POINTER(_sz), C.POINTER(_sz), _vp, _sz,
+                                                _vp, _sz, _vp]
+    lib.sperrhip_rel_parse_stream_dev.restype = C.c_int
+    lib.sperrhip_rel_parse_stream_dev.argtypes = [_vp, _sz, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(_sz),
+                                                  C.POINTER(_sz), C.POINTER(_sz), _vp]
+    lib.sperrhip_rel_check_dev.restype = C.c_int
+    lib.sperrhip_rel_check_dev.argtypes = [_vp, _vp, C.c_int, _sz, C.c_double, C.POINTER(C.c_double), _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
     lib.sperrhip_parse_header_dev.argtypes = [_vp, _sz] + [C.POINTER(_sz)] * 3 + \
         [C.POINTER(C.c_int)] + [C.POINTER(_sz)] * 3
@@ -1018,6 +1042,132 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_quality_masked_dev returned {rtn}")
         n, nmiss, _ = self.mask_parse(mask)
         return Quality(out[:8], n - nmiss)
+
+    # ---- relative error ----------------------------------------------------------------------
+    def rel_tolerance(self, eps, is_float=True):
+        """t of eps (include/sperr_hip.h, "relative error"): the point-wise tolerance of the y volume.  A refused eps
+        raises."""
+        t = C.c_double(0.0)
+        if self.lib.sperrhip_rel_tolerance(float(eps), int(bool(is_float)), C.byref(t)) != 0:
+            raise SperrHipError(f"a relative bound of {eps!r} is refused")
+        return t.value
+
+    def rel_max_size(self, n):
+        return self.lib.sperrhip_rel_max_size(n)
+
+    def _side_arg(self, side):
+        torch = self.torch
+        assert side.is_cuda and side.dtype == torch.uint8 and side.is_contiguous()
+        if side.data_ptr() % 8:
+            raise SperrHipError("a side stream starts on an 8-byte boundary")
+
+    def rel_forward(self, vol):
+        """(y, side, nzero, nneg) of a contiguous cuda tensor (float32 / float64, any shape): y as a float64 tensor of
+        the same shape, NaN in the zero class, and the side stream with the zero and sign bits (its eps is 0.0: a
+        forward call states no bound)."""
+        torch = self.torch
+        assert vol.is_cuda and vol.is_contiguous() and vol.dtype in (torch.float32, torch.float64)
+        n = vol.numel()
+        y = torch.empty(vol.shape, dtype=torch.float64, device=vol.device)
+        side = torch.empty(self.rel_max_size(n), dtype=torch.uint8, device=vol.device)
+        slen, nzero, nneg = _sz(0), _sz(0), _sz(0)
+        rtn = self.lib.sperrhip_rel_forward_dev(vol.data_ptr(), int(vol.dtype == torch.float32), n, y.data_ptr(),
+                                                side.data_ptr(), side.numel(), C.byref(slen), C.byref(nzero),
+                                                C.byref(nneg), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_rel_forward_dev returned {rtn}")
+        return y, side[:slen.value], nzero.value, nneg.value
+
+    def rel_inverse(self, y, side, box_lo_xyz=None, box_dims_xyz=None, vol_shape_zyx=None, output_float=True,
+                    out=None):
+        """x' of y', a contiguous cuda float64 tensor: the whole volume, or with a box the box [lo, lo + dims)
+        (x, y, z order) of a volume of vol_shape_zyx.  out=y works in place when output_float is False."""
+        torch = self.torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == torch.float64
+        self._side_arg(side)
+        lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
+        if dims is None:   # (the whole volume is one run of samples: only their number matters)
+            vd = (_sz * 3)(y.numel(), 1, 1)
+        else:
+            if vol_shape_zyx is None:
+                raise ValueError("a box needs vol_shape_zyx")
+            if y.numel() != math.prod(box_dims_xyz):
+                raise SperrHipError(f"a tensor of {y.numel()} samples for a box (x, y, z) {tuple(box_dims_xyz)}")
+            vd = (_sz * 3)(*(int(d) for d in reversed(vol_shape_zyx)))
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            out = torch.empty(y.shape, dtype=dt, device=y.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() == y.numel()
+        rtn = self.lib.sperrhip_rel_inverse_dev(y.data_ptr(), vd, lo, dims, side.data_ptr(), side.numel(),
+                                                int(output_float), out.data_ptr(), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_rel_inverse_dev returned {rtn}")
+        return out
+
+    def compress_rel(self, vol, chunks_xyz, eps, fill="smooth"):
+        """A contiguous cuda tensor (z, y, x) of finite samples as (container, side) under the point-wise relative
+        bound |x' - x| <= eps |x|, zeros and signs exact: the container is compress_masked() of the double volume y in
+        point-wise error mode at rel_tolerance(eps), which any SPERR reader decodes; the side stream holds the zero
+        and sign bits.  `fill` as in mask_make, in y's domain: what stands where a sample is zero."""
+        torch = self.torch
+        assert vol.is_cuda and vol.dim() == 3 and vol.dtype in (torch.float32, torch.float64)
+        self._no_view(vol, "compress_rel")
+        is_float = vol.dtype == torch.float32
+        t = self.rel_tolerance(eps, is_float)
+        kind, value = self._fill_kind(fill)
+        dz, dy, dx = vol.shape
+        out = torch.empty(self.max_compressed_size(vol.shape, chunks_xyz, t, 3), dtype=torch.uint8, device=vol.device)
+        side = torch.empty(self.rel_max_size(vol.numel()), dtype=torch.uint8, device=vol.device)
+        n, slen = _sz(0), _sz(0)
+        rtn = self.lib.sperrhip_compress_rel_dev(vol.data_ptr(), int(is_float), dx, dy, dz, *chunks_xyz, float(eps),
+                                                 kind, value, out.data_ptr(), out.numel(), C.byref(n),
+                                                 side.data_ptr(), side.numel(), C.byref(slen), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_rel_dev returned {rtn}")
+        return out[:n.value], side[:slen.value]
+
+    def decompress_rel(self, container, side, box_lo_xyz=None, box_dims_xyz=None, pct=0, output_float=True, out=None):
+        """x' of a container and side stream of compress_rel: the whole volume or, with a box, the box.  A portion
+        (pct other than 0 or 100) carries no bound: finite values, zeros and signs exact."""
+        torch = self.torch
+        assert container.is_cuda and container.dtype == torch.uint8 and container.is_contiguous()
+        self._side_arg(side)
+        lo, dims = self._box_args(box_lo_xyz, box_dims_xyz)
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            zyx = self.parse_header(container)[0] if dims is None else tuple(int(d) for d in reversed(box_dims_xyz))
+            out = torch.empty(zyx, dtype=dt, device=container.device)
+        assert out.dtype == dt and out.is_cuda
+        self._no_view(out, "decompress_rel")
+        rtn = self.lib.sperrhip_decompress_rel_dev(container.data_ptr(), container.numel(), int(pct),
+                                                   int(output_float), lo, dims, side.data_ptr(), side.numel(),
+                                                   out.data_ptr(), out.numel() * out.element_size(), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_rel_dev returned {rtn}")
+        return out
+
+    def rel_parse(self, side):
+        """(is_float, eps, n, nzero, nneg) of a side stream's headers, read on the current stream"""
+        self._side_arg(side)
+        isf, eps, n, nzero, nneg = C.c_int(0), C.c_double(0.0), _sz(0), _sz(0), _sz(0)
+        rtn = self.lib.sperrhip_rel_parse_stream_dev(side.data_ptr(), side.numel(), C.byref(isf), C.byref(eps),
+                                                     C.byref(n), C.byref(nzero), C.byref(nneg), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_rel_parse_stream_dev returned {rtn}")
+        return bool(isf.value), eps.value, n.value, nzero.value, nneg.value
+
+    def rel_check(self, orig, recon, eps):
+        """(worst, violations, mismatches, counted) of two contiguous cuda tensors of one dtype: over the samples
+        whose original is no zero the largest |x' - x| / |x| and how many exceed eps, how many samples differ in zero
+        class or sign, and how many originals are no zeros."""
+        self._quality_args(orig, recon)
+        out = (C.c_double * 4)()
+        rtn = self.lib.sperrhip_rel_check_dev(orig.data_ptr(), recon.data_ptr(),
+                                              int(orig.dtype == self.torch.float32), orig.numel(), float(eps), out,
+                                              self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_rel_check_dev returned {rtn}")
+        return out[0], int(out[1]), int(out[2]), int(out[3])
 
     # ---- stage access ----------------------------------------------------------------------
     def dwt3d(self, vals, inverse=False):

@@ -323,6 +323,8 @@ struct Engine {
                                             //   compacted arrays of the quality call
   DevBuf maskWork;                          //   ... and the bit array, the tile counts and the partials of mask.hip
   DevBuf maskPyramid;                       //   ... and the levels of a smooth in-fill (mask_fill.h) in global memory
+  DevBuf relStage;                          // relative error (rel.h): the double volume or box y that the coder sees
+  DevBuf relWork;                           //   ... and the sign bits' workspace with the read-back record of rel.hip
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
 
@@ -440,14 +442,14 @@ struct Engine {
   // stay; the next call sizes the workspaces again).  The engine's device is current.
   // THE list of the engine's workspace buffers: the arena, the containers' slots, and what point-wise error mode adds
   // (the outlier coder's arrays, the boxes of the coarser levels, the outlier streams) and the staging buffers of the
-  // fields, boxes and mask calls.  drop_memory, device_bytes and the poison fill walk it, so a buffer added here is
-  // dropped, counted and poisoned alike.  (Not the plans' tables: constant data, uploaded once)
+  // fields, boxes, mask and relative error calls.  drop_memory, device_bytes and the poison fill walk it, so a buffer
+  // added here is dropped, counted and poisoned alike.  (Not the plans' tables: constant data, uploaded once)
   template <typename Self, typename F>
   static void walk_buffers(Self& e, F&& f)
   {
     for (auto* b : {&e.arena, &e.slots, &e.misc, &e.outlFixed, &e.outlVar, &e.outlStream, &e.pweBox, &e.wideScratch,
                     &e.fieldsStage, &e.fieldsStage2, &e.boxesStage, &e.maskStage, &e.maskStage2, &e.maskWork,
-                    &e.maskPyramid})
+                    &e.maskPyramid, &e.relStage, &e.relWork})
       f(*b);
     for (auto& b : e.outlDec)
       f(b);

@@ -311,6 +311,24 @@ int mask_scan_run(const void* d_src, int is_float, size_t n, int rule, double th
 int mask_pack_fill_run(const void* d_src, int is_float, size_t n, const void* ws, const MaskResult& res, void* d_mask,
                        void* d_filled, void* hip_stream, const MaskFill* fill = nullptr);
 
+// ---- a bit array another unit's kernel made (rel.hip: the signs of a volume) ----------------------------------------
+// Where such a kernel leaves what k_mask_survey would, in a workspace `ws` of mask_workspace_bytes(n): the words of the
+// bit array (tail bits 0), every tile's toggle count against the sample before the tile, and per workgroup the record
+// {lo key, hi key, bits set} -- mask_key of doubles; a kernel with no order of its own writes mask_key(0.0) twice.
+// *res is the device address of the read-back record.  At most kMaskBitsMaxGroups workgroups.  false: n is refused
+constexpr uint32_t kMaskBitsMaxGroups = 8192;
+struct MaskBitsParts {
+  uint64_t* words;
+  uint32_t* tileTog;
+  uint64_t* partials;
+  const MaskResult* res;
+};
+bool mask_bits_parts(void* ws, size_t n, MaskBitsParts* parts);
+// k_mask_finish over `ngroups` such records on `hip_stream`: the kind, the tiles' toggle offsets, the header and *res.
+// No host wait; mask_pack_fill_run with the record read back (d_src any non-null pointer, d_filled NULL) then writes
+// the stream
+int mask_bits_finish_run(void* ws, size_t n, uint32_t ngroups, void* hip_stream);
+
 // a stream on the device, header already parsed: d_payload is d_mask + 32 (8-byte aligned)
 struct MaskStream {
   MaskHeader h;

@@ -552,6 +552,29 @@ uint64_t* mask_result_finite(void* ws, size_t n)
   return ws && mask_ws(n, ws, kMaskMaxGroups, w) ? &w.fin->res.finite : nullptr;
 }
 
+static_assert(kMaskBitsMaxGroups == kMaskMaxGroups, "the workspace holds a record per workgroup");
+
+bool mask_bits_parts(void* ws, size_t n, MaskBitsParts* parts)
+{
+  MaskWs w;
+  if (!ws || !parts || !mask_ws(n, ws, kMaskMaxGroups, w))
+    return false;
+  *parts = MaskBitsParts{w.words, w.tileCnt, w.partials, &w.fin->res};
+  return true;
+}
+
+int mask_bits_finish_run(void* ws, size_t n, uint32_t ngroups, void* hip_stream)
+{
+  MaskWs w;
+  if (!ws || ngroups == 0 || ngroups > kMaskMaxGroups || !mask_ws(n, ws, kMaskMaxGroups, w))
+    return -1;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  LAUNCH_K(k_mask_finish, dim3(1), dim3(kFinishThreads), 0, st, w.partials, ngroups, w.tileCnt, w.tileOff,
+           (uint64_t)((n + kMaskTile - 1) / kMaskTile), (uint64_t)n, 0, w.fin);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int mask_scan_run(const void* d_src, int is_float, size_t n, int rule, double threshold, void* ws, MaskResult* res,
                   void* hip_stream, const MaskFill* fill)
 {
