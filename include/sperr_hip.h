@@ -620,27 +620,47 @@ int sperrhip_quality_masked_dev(const void* d_orig, const void* d_recon, int is_
  *              y' = -126 + 0.5 * (y' + 126); then y' clamped into [-1080, nextafter(1024, 0)],
  *              e = floor(y'), m = y' - e, ldexp(1.0 + m, (int)e), narrowed once for float output (FLT_MAX where that
  *              overflows), then the sign bit
- *   stream     "SPRL", little-endian, 8-byte aligned: 0-3 "SPRL" | 4 version 1 | 5 is_float of the source | 6-7 0 |
+ *   stream     "SPRL", little-endian, 8-byte aligned: 0-3 the magic | 4 version 1 | 5 is_float of the source | 6-7 0 |
  *              8-15 the bits of eps (+0.0 from sperrhip_rel_forward_dev, which states no bound) | 16-23 n |
  *              24-31 length of the zero stream | 32-39 length of the sign stream | 40-47 0 | the zero stream,
  *              padding to 8 bytes, the sign stream: two mask streams as above, bit 1 = zero class / negative
+ * That is the map kind SPERRHIP_REL_LINEAR (0), the default and what every call without a kind means: y is the
+ * piecewise linear interpolant of log2|x| between the powers of two.  SPERRHIP_REL_LOG (1) codes the true logarithm:
+ * a larger tolerance and no kink at the powers of two, so a smaller container, much smaller on fields that are smooth
+ * in the exponent.  Zero class, sign, the stretch of the subnormal floats, the un-stretch, the clamp, the narrowing and
+ * the refusals are the same.  What differs, every operation an IEEE double operation rounded once in the order written
+ * (no libm, no fused multiply-add), the constants and the derivation in rel.h:
+ *   forward    m = 1.M folded into [sqrt(1/2), sqrt(2)) with its exponent e, s = (m - 1) / (m + 1), an 11-term
+ *              Horner polynomial P in s * s; y = (double)e + s * P
+ *   tolerance  t = y(1.0 + eps) - s with the same s; refused unless eps is finite, 0 < eps <= 0.5 and t >= s
+ *   inverse    e = floor(y'), f = y' - e folded into (-1/2, 1/2], a degree-13 Horner polynomial Q in f * ln 2,
+ *              ldexp(Q, (int)e); finite: DBL_MAX where the last rounding would overflow, +0.0 below 2^-1075
+ *   stream     the same layout under the magic "SPLG".  A reader accepts either magic, takes the kind from it and
+ *              checks eps against that kind's tolerance rule; a library from before this kind refuses "SPLG"
  * A portion decode (pct other than 0 or 100) carries no bound: finite values, zeros and
  * signs exact.  A side stream that is handed in has its three headers checked; its payload is trusted, as a mask's.
  * Return codes follow the masked calls: 0 ok; 1 side_cap too small, *side_len the size needed; -1, before anything
- * of the caller's is written: NULL pointers, n == 0, a refused eps, a sample that is not finite, a refused side
+ * of the caller's is written: NULL pointers, n == 0, an unknown kind, a refused eps, a sample that is not finite, a refused side
  * stream, n against the container's volume, a container that is not a double one, a box that leaves the volume.
  * Out of scope, refused where it can be reached: samples that are not finite, rate and PSNR modes of y, views,
  * batches, fields, slices, levels and multires, the host calls and the farm, the command line tools. */
+/* The map kinds.  A call named *_kind is the call beside it with the kind as one more argument; the call without it
+ * means SPERRHIP_REL_LINEAR.  An unknown kind returns -1 before anything is written. */
+#define SPERRHIP_REL_LINEAR 0
+#define SPERRHIP_REL_LOG 1
 /* t of eps.  Host only.  -1: eps is refused */
 int sperrhip_rel_tolerance(double eps, int is_float, double* t);
+int sperrhip_rel_tolerance_kind(double eps, int is_float, int kind, double* t);
 /* 48 + 2 * sperrhip_mask_max_size(n).  Host only. */
 size_t sperrhip_rel_max_size(size_t n);
 /* y of the n samples at d_src into d_y (n doubles, no overlap with d_src) and the side stream into d_side.  One host
  * wait. */
 int sperrhip_rel_forward_dev(const void* d_src, int is_float, size_t n, void* d_y, void* d_side, size_t side_cap,
                              size_t* side_len, size_t* nzero, size_t* nneg, void* hip_stream);
+int sperrhip_rel_forward_kind_dev(const void* d_src, int is_float, size_t n, int kind, void* d_y, void* d_side,
+                                  size_t side_cap, size_t* side_len, size_t* nzero, size_t* nneg, void* hip_stream);
 /* d_y holds y' of the box [box_lo, box_lo + box_dims) of a volume of vol_dims densely (both NULL: the whole volume):
- * x' into d_dst, floats or doubles; d_dst may be d_y when doubles. */
+ * x' into d_dst, floats or doubles; d_dst may be d_y when doubles.  The map kind is the side stream's. */
 int sperrhip_rel_inverse_dev(const void* d_y, const size_t vol_dims[3], const size_t box_lo[3],
                              const size_t box_dims[3], const void* d_side, size_t side_len, int output_float,
                              void* d_dst, void* hip_stream);
@@ -651,14 +671,20 @@ int sperrhip_compress_rel_dev(const void* d_src, int is_float, size_t dimx, size
                               size_t chunk_y, size_t chunk_z, double eps, int fill, double fill_value, void* d_dst,
                               size_t dst_cap, size_t* dst_len, void* d_side, size_t side_cap, size_t* side_len,
                               void* hip_stream);
+int sperrhip_compress_rel_kind_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                                   size_t chunk_x, size_t chunk_y, size_t chunk_z, double eps, int kind, int fill,
+                                   double fill_value, void* d_dst, size_t dst_cap, size_t* dst_len, void* d_side,
+                                   size_t side_cap, size_t* side_len, void* hip_stream);
 /* sperrhip_decompress_masked_dev's decode (pct, box) as doubles into a buffer the library keeps, then the inverse
- * into d_dst.  One host wait more than that call. */
+ * of the side stream's map kind into d_dst.  One host wait more than that call. */
 int sperrhip_decompress_rel_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
                                 const size_t box_lo[3], const size_t box_dims[3], const void* d_side, size_t side_len,
                                 void* d_dst, size_t dst_cap_bytes, void* hip_stream);
 /* the headers of a side stream, read on hip_stream; any of the outputs may be NULL.  -1: the stream is refused */
 int sperrhip_rel_parse_stream_dev(const void* d_side, size_t side_len, int* is_float, double* eps, size_t* n,
                                   size_t* nzero, size_t* nneg, void* hip_stream);
+int sperrhip_rel_parse_stream_kind_dev(const void* d_side, size_t side_len, int* is_float, double* eps, size_t* n,
+                                       size_t* nzero, size_t* nneg, int* kind, void* hip_stream);
 /* out[4]: over the samples whose original is outside the zero class the largest |x' - x| / |x| in double and how
  * many have |x' - x| > eps * |x|; how many samples differ in zero class or in sign; the count of samples outside the
  * zero class.  One kernel, one host wait.  -1: a NULL pointer, n == 0, eps not finite or negative. */

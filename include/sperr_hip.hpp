@@ -765,22 +765,27 @@ inline auto quality_masked_dev(const T* d_orig, const T* d_recon, size_t n, cons
 // (this library's addition) Point-wise relative error (include/sperr_hip.h, "relative error"): |x' - x| <= eps |x|, zeros
 // and signs exact; a container of the double volume y and a side stream.  RTNType::WrongLength: the side buffer (or the
 // container's) is too small, side_len then names the size needed.
+// The map kind: y is the piecewise linear interpolant of log2|x| (the default) or log2|x| itself, which gives the smaller
+// container.  A decode takes it from the side stream.
+enum class RelMap : int { linear = SPERRHIP_REL_LINEAR, log = SPERRHIP_REL_LOG };
+
 // t of eps for fp32 (T = float) or fp64 data; Error: eps is refused
 template <typename T>
-inline auto rel_tolerance(double eps, double& t) -> RTNType
+inline auto rel_tolerance(double eps, double& t, RelMap map = RelMap::linear) -> RTNType
 {
   static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
-  return detail::mask_rtn(sperrhip_rel_tolerance(eps, sizeof(T) == 4, &t));
+  return detail::mask_rtn(sperrhip_rel_tolerance_kind(eps, sizeof(T) == 4, static_cast<int>(map), &t));
 }
 
 // y of n samples into d_y and their side stream (which states no bound) into d_side
 template <typename T>
 inline auto rel_forward_dev(const T* d_src, size_t n, double* d_y, void* d_side, size_t side_cap, size_t& side_len,
-                            size_t& nzero, size_t& nneg, void* hip_stream = nullptr) -> RTNType
+                            size_t& nzero, size_t& nneg, void* hip_stream = nullptr, RelMap map = RelMap::linear)
+    -> RTNType
 {
   static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
-  return detail::mask_rtn(sperrhip_rel_forward_dev(d_src, sizeof(T) == 4, n, d_y, d_side, side_cap, &side_len, &nzero,
-                                                   &nneg, hip_stream));
+  return detail::mask_rtn(sperrhip_rel_forward_kind_dev(d_src, sizeof(T) == 4, n, static_cast<int>(map), d_y, d_side,
+                                                        side_cap, &side_len, &nzero, &nneg, hip_stream));
 }
 
 // x' of y' of the box of a volume that d_y holds (null box: the whole volume); d_out may be d_y when T is double
@@ -798,12 +803,13 @@ inline auto rel_inverse_dev(const double* d_y, dims_type vol_dims, const dims_ty
 template <typename T>
 inline auto compress_rel_dev(const T* d_src, dims_type dims, dims_type chunks, double eps, FillKind fill,
                              double fill_value, void* d_out, size_t cap, size_t& out_len, void* d_side, size_t side_cap,
-                             size_t& side_len, void* hip_stream = nullptr) -> RTNType
+                             size_t& side_len, void* hip_stream = nullptr, RelMap map = RelMap::linear) -> RTNType
 {
   static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
-  return detail::mask_rtn(sperrhip_compress_rel_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0],
-                                                    chunks[1], chunks[2], eps, static_cast<int>(fill), fill_value, d_out,
-                                                    cap, &out_len, d_side, side_cap, &side_len, hip_stream));
+  return detail::mask_rtn(sperrhip_compress_rel_kind_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0],
+                                                         chunks[1], chunks[2], eps, static_cast<int>(map),
+                                                         static_cast<int>(fill), fill_value, d_out, cap, &out_len,
+                                                         d_side, side_cap, &side_len, hip_stream));
 }
 
 // the volume (null box) or a box of it, from the first pct percent of every chunk stream (0: all; a portion carries no

@@ -52,6 +52,8 @@ EXPORTS = [
     "sperrhip_rel_tolerance", "sperrhip_rel_max_size", "sperrhip_rel_forward_dev", "sperrhip_rel_inverse_dev",
     "sperrhip_compress_rel_dev", "sperrhip_decompress_rel_dev", "sperrhip_rel_parse_stream_dev",
     "sperrhip_rel_check_dev",
+    "sperrhip_rel_tolerance_kind", "sperrhip_rel_forward_kind_dev", "sperrhip_compress_rel_kind_dev",
+    "sperrhip_rel_parse_stream_kind_dev",
 ]
 
 
@@ -278,6 +280,19 @@ def load_library():
     lib.sperrhip_rel_parse_stream_dev.restype = C.c_int
     lib.sperrhip_rel_parse_stream_dev.argtypes = [_vp, _sz, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(_sz),
                                                   C.POINTER(_sz), C.POINTER(_sz), _vp]
+    lib.sperrhip_rel_tolerance_kind.restype = C.c_int
+    lib.sperrhip_rel_tolerance_kind.argtypes = [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib.sperrhip_rel_forward_kind_dev.restype = C.c_int
+    lib.sperrhip_rel_forward_kind_dev.argtypes = [_vp, C.c_int, _sz, C.c_int, _vp, _vp, _sz, C.POINTER(_sz),
+                                                  C.POINTER(_sz), C.POINTER(_sz), _vp]
+    lib.sperrhip_compress_rel_kind_dev.restype = C.c_int
+    lib.sperrhip_compress_rel_kind_dev.argtypes = [_vp, C.c_int] + [_sz] * 6 + [C.c_double, C.c_int, C.c_int, C.c_double,
+                                                                               _vp, _sz, C.POINTER(_sz), _vp, _sz,
+                                                                               C.POINTER(_sz), _vp]
+    lib.sperrhip_rel_parse_stream_kind_dev.restype = C.c_int
+    lib.sperrhip_rel_parse_stream_kind_dev.argtypes = [_vp, _sz, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                                       C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz),
+                                                       C.POINTER(C.c_int), _vp]
     lib.sperrhip_rel_check_dev.restype = C.c_int
     lib.sperrhip_rel_check_dev.argtypes = [_vp, _vp, C.c_int, _sz, C.c_double, C.POINTER(C.c_double), _vp]
     lib.sperrhip_parse_header_dev.restype = C.c_int
@@ -1044,11 +1059,19 @@ class SperrHip:
         return Quality(out[:8], n - nmiss)
 
     # ---- relative error ----------------------------------------------------------------------
-    def rel_tolerance(self, eps, is_float=True):
-        """t of eps (include/sperr_hip.h, "relative error"): the point-wise tolerance of the y volume.  A refused eps
+    REL_MAPS = {"linear": 0, "log": 1}   # the map kinds of include/sperr_hip.h: SPERRHIP_REL_LINEAR, SPERRHIP_REL_LOG
+
+    def _rel_map(self, map):
+        if map not in self.REL_MAPS:
+            raise ValueError(f"map is 'linear' or 'log', not {map!r}")
+        return self.REL_MAPS[map]
+
+    def rel_tolerance(self, eps, is_float=True, map="linear"):
+        """t of eps (include/sperr_hip.h, "relative error"): the point-wise tolerance of the y volume under the map
+        kind `map`, "linear" (y the piecewise linear interpolant of log2|x|) or "log" (y = log2|x|).  A refused eps
         raises."""
         t = C.c_double(0.0)
-        if self.lib.sperrhip_rel_tolerance(float(eps), int(bool(is_float)), C.byref(t)) != 0:
+        if self.lib.sperrhip_rel_tolerance_kind(float(eps), int(bool(is_float)), self._rel_map(map), C.byref(t)) != 0:
             raise SperrHipError(f"a relative bound of {eps!r} is refused")
         return t.value
 
@@ -1061,27 +1084,29 @@ class SperrHip:
         if side.data_ptr() % 8:
             raise SperrHipError("a side stream starts on an 8-byte boundary")
 
-    def rel_forward(self, vol):
+    def rel_forward(self, vol, map="linear"):
         """(y, side, nzero, nneg) of a contiguous cuda tensor (float32 / float64, any shape): y as a float64 tensor of
         the same shape, NaN in the zero class, and the side stream with the zero and sign bits (its eps is 0.0: a
-        forward call states no bound)."""
+        forward call states no bound).  `map` as in rel_tolerance; the side stream names it."""
         torch = self.torch
         assert vol.is_cuda and vol.is_contiguous() and vol.dtype in (torch.float32, torch.float64)
         n = vol.numel()
         y = torch.empty(vol.shape, dtype=torch.float64, device=vol.device)
         side = torch.empty(self.rel_max_size(n), dtype=torch.uint8, device=vol.device)
         slen, nzero, nneg = _sz(0), _sz(0), _sz(0)
-        rtn = self.lib.sperrhip_rel_forward_dev(vol.data_ptr(), int(vol.dtype == torch.float32), n, y.data_ptr(),
-                                                side.data_ptr(), side.numel(), C.byref(slen), C.byref(nzero),
-                                                C.byref(nneg), self._stream())
+        kind = self._rel_map(map)
+        rtn = self.lib.sperrhip_rel_forward_kind_dev(vol.data_ptr(), int(vol.dtype == torch.float32), n, kind,
+                                                     y.data_ptr(), side.data_ptr(), side.numel(), C.byref(slen),
+                                                     C.byref(nzero), C.byref(nneg), self._stream())
         if rtn != 0:
-            raise SperrHipError(f"sperrhip_rel_forward_dev returned {rtn}")
+            raise SperrHipError(f"sperrhip_rel_forward_kind_dev returned {rtn}")
         return y, side[:slen.value], nzero.value, nneg.value
 
     def rel_inverse(self, y, side, box_lo_xyz=None, box_dims_xyz=None, vol_shape_zyx=None, output_float=True,
                     out=None):
         """x' of y', a contiguous cuda float64 tensor: the whole volume, or with a box the box [lo, lo + dims)
-        (x, y, z order) of a volume of vol_shape_zyx.  out=y works in place when output_float is False."""
+        (x, y, z order) of a volume of vol_shape_zyx.  out=y works in place when output_float is False.  The map kind
+        is the side stream's."""
         torch = self.torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == torch.float64
         self._side_arg(side)
@@ -1104,26 +1129,28 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_rel_inverse_dev returned {rtn}")
         return out
 
-    def compress_rel(self, vol, chunks_xyz, eps, fill="smooth"):
+    def compress_rel(self, vol, chunks_xyz, eps, fill="smooth", map="linear"):
         """A contiguous cuda tensor (z, y, x) of finite samples as (container, side) under the point-wise relative
         bound |x' - x| <= eps |x|, zeros and signs exact: the container is compress_masked() of the double volume y in
         point-wise error mode at rel_tolerance(eps), which any SPERR reader decodes; the side stream holds the zero
-        and sign bits.  `fill` as in mask_make, in y's domain: what stands where a sample is zero."""
+        and sign bits.  `fill` as in mask_make, in y's domain: what stands where a sample is zero.  `map` as in
+        rel_tolerance: "log" gives the smaller container; decompress_rel reads the kind off the side stream."""
         torch = self.torch
         assert vol.is_cuda and vol.dim() == 3 and vol.dtype in (torch.float32, torch.float64)
         self._no_view(vol, "compress_rel")
         is_float = vol.dtype == torch.float32
-        t = self.rel_tolerance(eps, is_float)
+        t = self.rel_tolerance(eps, is_float, map)
         kind, value = self._fill_kind(fill)
         dz, dy, dx = vol.shape
         out = torch.empty(self.max_compressed_size(vol.shape, chunks_xyz, t, 3), dtype=torch.uint8, device=vol.device)
         side = torch.empty(self.rel_max_size(vol.numel()), dtype=torch.uint8, device=vol.device)
         n, slen = _sz(0), _sz(0)
-        rtn = self.lib.sperrhip_compress_rel_dev(vol.data_ptr(), int(is_float), dx, dy, dz, *chunks_xyz, float(eps),
-                                                 kind, value, out.data_ptr(), out.numel(), C.byref(n),
-                                                 side.data_ptr(), side.numel(), C.byref(slen), self._stream())
+        rtn = self.lib.sperrhip_compress_rel_kind_dev(vol.data_ptr(), int(is_float), dx, dy, dz, *chunks_xyz,
+                                                      float(eps), self._rel_map(map), kind, value, out.data_ptr(),
+                                                      out.numel(), C.byref(n), side.data_ptr(), side.numel(),
+                                                      C.byref(slen), self._stream())
         if rtn != 0:
-            raise SperrHipError(f"sperrhip_compress_rel_dev returned {rtn}")
+            raise SperrHipError(f"sperrhip_compress_rel_kind_dev returned {rtn}")
         return out[:n.value], side[:slen.value]
 
     def decompress_rel(self, container, side, box_lo_xyz=None, box_dims_xyz=None, pct=0, output_float=True, out=None):
@@ -1146,15 +1173,24 @@ class SperrHip:
             raise SperrHipError(f"sperrhip_decompress_rel_dev returned {rtn}")
         return out
 
+    def _rel_parse(self, side):
+        self._side_arg(side)
+        isf, eps, n, nzero, nneg, kind = C.c_int(0), C.c_double(0.0), _sz(0), _sz(0), _sz(0), C.c_int(0)
+        rtn = self.lib.sperrhip_rel_parse_stream_kind_dev(side.data_ptr(), side.numel(), C.byref(isf), C.byref(eps),
+                                                          C.byref(n), C.byref(nzero), C.byref(nneg), C.byref(kind),
+                                                          self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_rel_parse_stream_kind_dev returned {rtn}")
+        return (bool(isf.value), eps.value, n.value, nzero.value, nneg.value), kind.value
+
     def rel_parse(self, side):
         """(is_float, eps, n, nzero, nneg) of a side stream's headers, read on the current stream"""
-        self._side_arg(side)
-        isf, eps, n, nzero, nneg = C.c_int(0), C.c_double(0.0), _sz(0), _sz(0), _sz(0)
-        rtn = self.lib.sperrhip_rel_parse_stream_dev(side.data_ptr(), side.numel(), C.byref(isf), C.byref(eps),
-                                                     C.byref(n), C.byref(nzero), C.byref(nneg), self._stream())
-        if rtn != 0:
-            raise SperrHipError(f"sperrhip_rel_parse_stream_dev returned {rtn}")
-        return bool(isf.value), eps.value, n.value, nzero.value, nneg.value
+        return self._rel_parse(side)[0]
+
+    def rel_kind(self, side):
+        """"linear" or "log": the map kind a side stream names"""
+        kind = self._rel_parse(side)[1]
+        return next(name for name, k in self.REL_MAPS.items() if k == kind)
 
     def rel_check(self, orig, recon, eps):
         """(worst, violations, mismatches, counted) of two contiguous cuda tensors of one dtype: over the samples

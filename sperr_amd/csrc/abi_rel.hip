@@ -4,6 +4,8 @@
 // the masked decode call as doubles into that buffer -- without its last step: nothing reads an in-filled sample as a
 // value -- and then k_rel_inverse.  Host waits: compress has the masked call's (the sign record arrives with the
 // survey's); decode has one more than the masked call, at its end, because k_rel_inverse reads the engine's buffer.
+// The map kind (rel.h: linear or log) is an argument of the *_kind calls going in -- the calls without it mean the
+// linear kind -- and the side stream's magic coming back.
 #include "mask_calls.h"
 #include "rel.h"
 
@@ -64,12 +66,12 @@ bool box_of(const size_t vol[3], const size_t box_lo[3], const size_t box_dims[3
 
 // What a forward call knows after the survey's host wait: 0 ok, `h` the side stream's header; 1 side_cap too small;
 // -1 a sample that is not finite.  *side_len is set unless -1
-int side_header(const RelForward& fwd, const MaskResult& zero, int is_float, double eps, size_t n, size_t side_cap,
-                size_t* side_len, RelHeader* h)
+int side_header(const RelForward& fwd, const MaskResult& zero, int is_float, double eps, size_t n, int kind,
+                size_t side_cap, size_t* side_len, RelHeader* h)
 {
   if (fwd.nonfinite)
     return -1;
-  *h = RelHeader{is_float != 0, eps, n, zero.mask_len, fwd.sign.mask_len};
+  *h = RelHeader{is_float != 0, eps, n, zero.mask_len, fwd.sign.mask_len, kind};
   *side_len = (size_t)rel_stream_bytes(*h);
   return *side_len > side_cap ? 1 : 0;
 }
@@ -78,9 +80,14 @@ int side_header(const RelForward& fwd, const MaskResult& zero, int is_float, dou
 
 extern "C" {
 
+int sperrhip_rel_tolerance_kind(double eps, int is_float, int kind, double* t)
+{
+  return t && rel_tolerance(eps, is_float != 0, t, kind) ? 0 : -1;
+}
+
 int sperrhip_rel_tolerance(double eps, int is_float, double* t)
 {
-  return t && rel_tolerance(eps, is_float != 0, t) ? 0 : -1;
+  return sperrhip_rel_tolerance_kind(eps, is_float, kRelLinear, t);
 }
 
 size_t sperrhip_rel_max_size(size_t n)
@@ -88,13 +95,13 @@ size_t sperrhip_rel_max_size(size_t n)
   return rel_max_size(n);
 }
 
-int sperrhip_rel_forward_dev(const void* d_src, int is_float, size_t n, void* d_y, void* d_side, size_t side_cap,
-                             size_t* side_len, size_t* nzero, size_t* nneg, void* hip_stream)
+int sperrhip_rel_forward_kind_dev(const void* d_src, int is_float, size_t n, int kind, void* d_y, void* d_side,
+                                  size_t side_cap, size_t* side_len, size_t* nzero, size_t* nneg, void* hip_stream)
 {
-  return guarded("sperrhip_rel_forward_dev", [&]() -> int {
+  return guarded("sperrhip_rel_forward_kind_dev", [&]() -> int {
     const size_t ws = rel_workspace_bytes(n);
     if (!d_src || !d_y || !d_side || !side_len || !nzero || !nneg || n == 0 || n > SIZE_MAX / 8 || ws == 0 ||
-        (uintptr_t)d_side % 8 != 0 || (uintptr_t)d_y % 8 != 0)
+        !rel_kind_ok(kind) || (uintptr_t)d_side % 8 != 0 || (uintptr_t)d_y % 8 != 0)
       return -1;
     Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
@@ -107,12 +114,12 @@ int sperrhip_rel_forward_dev(const void* d_src, int is_float, size_t n, void* d_
       return -1;
     RelForward fwd{};
     MaskResult zero{};
-    if (rel_forward_run(d_src, is_float, n, static_cast<double*>(E.relStage.p), E.relWork.p, &fwd, st))
+    if (rel_forward_run(d_src, is_float, n, static_cast<double*>(E.relStage.p), E.relWork.p, &fwd, st, kind))
       return drain_call(E, st, -1);
     if (mask_survey(E, E.relStage.p, 0, n, kMaskRuleNan, 0.0, nullptr, SIZE_MAX, &zero, st) != 0)
       return drain_call(E, st, -1);
     RelHeader h;
-    int rtn = side_header(fwd, zero, is_float, 0.0, n, side_cap, side_len, &h);
+    int rtn = side_header(fwd, zero, is_float, 0.0, n, kind, side_cap, side_len, &h);
     if (rtn == 0) {
       *nzero = (size_t)zero.nmissing;
       *nneg = (size_t)fwd.sign.nmissing;
@@ -124,6 +131,13 @@ int sperrhip_rel_forward_dev(const void* d_src, int is_float, size_t n, void* d_
     }
     return drain_call(E, st, rtn);
   });
+}
+
+int sperrhip_rel_forward_dev(const void* d_src, int is_float, size_t n, void* d_y, void* d_side, size_t side_cap,
+                             size_t* side_len, size_t* nzero, size_t* nneg, void* hip_stream)
+{
+  return sperrhip_rel_forward_kind_dev(d_src, is_float, n, kRelLinear, d_y, d_side, side_cap, side_len, nzero, nneg,
+                                       hip_stream);
 }
 
 int sperrhip_rel_inverse_dev(const void* d_y, const size_t vol_dims[3], const size_t box_lo[3],
@@ -144,25 +158,25 @@ int sperrhip_rel_inverse_dev(const void* d_y, const size_t vol_dims[3], const si
     if (!L.e)
       return -1;
     if (rel_inverse_run(static_cast<const double*>(d_y), vol_dims, lo, dims, s.zero, s.sign, s.h.is_float, output_float,
-                        d_dst, st))
+                        d_dst, st, s.h.kind))
       return -1;
     return end_call(*L.e, st);
   });
 }
 
-int sperrhip_compress_rel_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
-                              size_t chunk_y, size_t chunk_z, double eps, int fill, double fill_value, void* d_dst,
-                              size_t dst_cap, size_t* dst_len, void* d_side, size_t side_cap, size_t* side_len,
-                              void* hip_stream)
+int sperrhip_compress_rel_kind_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                                   size_t chunk_x, size_t chunk_y, size_t chunk_z, double eps, int kind, int fill,
+                                   double fill_value, void* d_dst, size_t dst_cap, size_t* dst_len, void* d_side,
+                                   size_t side_cap, size_t* side_len, void* hip_stream)
 {
-  return guarded("sperrhip_compress_rel_dev", [&]() -> int {
+  return guarded("sperrhip_compress_rel_kind_dev", [&]() -> int {
     size_t n = 0;
     double t = 0.0;
     MaskFillPlan plan;
     MaskFill mf;
     // (the fill is y's: a value in the domain of doubles)
     if (!d_src || !d_dst || !dst_len || !d_side || !side_len || (uintptr_t)d_side % 8 != 0 ||
-        !volume_count(dimx, dimy, dimz, &n) || !rel_tolerance(eps, is_float != 0, &t) ||
+        !volume_count(dimx, dimy, dimz, &n) || !rel_tolerance(eps, is_float != 0, &t, kind) ||
         !fill_of(fill, fill_value, 0, dimx, dimy, dimz, &plan, &mf))
       return -1;
     const size_t ws = rel_workspace_bytes(n);
@@ -175,14 +189,14 @@ int sperrhip_compress_rel_dev(const void* d_src, int is_float, size_t dimx, size
       return -1;
     double* y = static_cast<double*>(E.relStage.p);
     RelForward fwd{};
-    if (rel_forward_run(d_src, is_float, n, y, E.relWork.p, &fwd, st))
+    if (rel_forward_run(d_src, is_float, n, y, E.relWork.p, &fwd, st, kind))
       return drain_call(E, st, -1);
     // ---- from here the body of sperrhip_compress_masked_fill_dev on y; its one wait brings the sign record too
     MaskResult zero{};
     if (mask_survey(E, y, 0, n, kMaskRuleNan, 0.0, nullptr, SIZE_MAX, &zero, st, &mf) != 0)
       return drain_call(E, st, -1);
     RelHeader h;
-    const int made = side_header(fwd, zero, is_float, eps, n, side_cap, side_len, &h);
+    const int made = side_header(fwd, zero, is_float, eps, n, kind, side_cap, side_len, &h);
     if (made != 0)
       return drain_call(E, st, made);
     // (with no zero y is the in-filled volume: no staged copy is made of it)
@@ -196,6 +210,16 @@ int sperrhip_compress_rel_dev(const void* d_src, int is_float, size_t dimx, size
     const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
     return compress_to(E, stage ? stage : y, 0, vol, ch, 3, t, static_cast<uint8_t*>(d_dst), dst_cap, dst_len, st);
   });
+}
+
+int sperrhip_compress_rel_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                              size_t chunk_y, size_t chunk_z, double eps, int fill, double fill_value, void* d_dst,
+                              size_t dst_cap, size_t* dst_len, void* d_side, size_t side_cap, size_t* side_len,
+                              void* hip_stream)
+{
+  return sperrhip_compress_rel_kind_dev(d_src, is_float, dimx, dimy, dimz, chunk_x, chunk_y, chunk_z, eps, kRelLinear,
+                                        fill, fill_value, d_dst, dst_cap, dst_len, d_side, side_cap, side_len,
+                                        hip_stream);
 }
 
 int sperrhip_decompress_rel_dev(const void* d_src, size_t src_len, unsigned pct, int output_float,
@@ -241,17 +265,17 @@ int sperrhip_decompress_rel_dev(const void* d_src, size_t src_len, unsigned pct,
     if (rtn != 0)
       return rtn;
     if (rel_inverse_run(static_cast<const double*>(E.relStage.p), vol, lo, dims, s.zero, s.sign, s.h.is_float, output_float,
-                        d_dst, st))
+                        d_dst, st, s.h.kind))
       rtn = -1;
     // (k_rel_inverse reads the engine's buffer)
     return drain_call(E, st, rtn);
   });
 }
 
-int sperrhip_rel_parse_stream_dev(const void* d_side, size_t side_len, int* is_float, double* eps, size_t* n,
-                                  size_t* nzero, size_t* nneg, void* hip_stream)
+int sperrhip_rel_parse_stream_kind_dev(const void* d_side, size_t side_len, int* is_float, double* eps, size_t* n,
+                                       size_t* nzero, size_t* nneg, int* kind, void* hip_stream)
 {
-  return guarded("sperrhip_rel_parse_stream_dev", [&]() -> int {
+  return guarded("sperrhip_rel_parse_stream_kind_dev", [&]() -> int {
     RelSide s;
     if (read_rel_side(d_side, side_len, s, static_cast<hipStream_t>(hip_stream)))
       return -1;
@@ -265,8 +289,16 @@ int sperrhip_rel_parse_stream_dev(const void* d_side, size_t side_len, int* is_f
       *nzero = (size_t)s.zero.h.nmissing;
     if (nneg)
       *nneg = (size_t)s.sign.h.nmissing;
+    if (kind)
+      *kind = s.h.kind;
     return 0;
   });
+}
+
+int sperrhip_rel_parse_stream_dev(const void* d_side, size_t side_len, int* is_float, double* eps, size_t* n,
+                                  size_t* nzero, size_t* nneg, void* hip_stream)
+{
+  return sperrhip_rel_parse_stream_kind_dev(d_side, side_len, is_float, eps, n, nzero, nneg, nullptr, hip_stream);
 }
 
 int sperrhip_rel_check_dev(const void* d_orig, const void* d_recon, int is_float, size_t n, double eps, double* out,

@@ -6,31 +6,16 @@
 //   k_rel_header             the 48 bytes of the side stream's header and the padding between its two streams
 //   k_rel_inverse<OT>        a dense box of y' with the zero and sign bits at the box's volume positions into x'
 //   k_rel_check<T, kVec>     the four figures of sperrhip_rel_check_dev
+// k_rel_forward and k_rel_inverse are the LINEAR map kind's; the log kind's two are rel_log.hip's, launched from here.
 //
 // The walks are mask.hip's: a wavefront takes a tile of kMaskTile samples at a time and walks the tiles beyond a grid
 // capped at kMaskGroupsPerCU workgroups per CU; no kernel waits on another workgroup.  kVec moves 16 bytes per lane and
 // is chosen when the pointers allow; the other form moves element by element.  LDS holds a workgroup's partials only.
-#include "common.h"
-#include "rel.h"
+#include "rel_walk.h"
 
 namespace sperrhip {
 
 namespace {
-
-constexpr uint32_t kWavesPerGroup = kMaskThreads / 64;
-
-typedef float Float4 __attribute__((ext_vector_type(4)));
-typedef double Double2 __attribute__((ext_vector_type(2)));
-template <typename T>
-struct RelPack;
-template <>
-struct RelPack<float> {
-  typedef Float4 type;
-};
-template <>
-struct RelPack<double> {
-  typedef Double2 type;
-};
 
 // what the forward kernel leaves beside the sign bits' workspace, and the check's four words
 struct RelRecord {
@@ -39,17 +24,6 @@ struct RelRecord {
 };
 
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-int rel_grid(uint64_t items, uint32_t* groups)
-{
-  int dev = 0, cus = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const uint64_t cap = std::min<uint64_t>((uint64_t)std::max(cus, 1) * kMaskGroupsPerCU, kMaskBitsMaxGroups);
-  const uint64_t want = (items + kWavesPerGroup - 1) / kWavesPerGroup;
-  *groups = (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
-  return 0;
-}
 
 template <typename T, bool kVec>
 __global__ __launch_bounds__(kMaskThreads) void k_rel_forward(const T* __restrict__ src, uint64_t n,
@@ -164,58 +138,6 @@ __global__ __launch_bounds__(64) void k_rel_header(RelHeadBytes h, uint8_t* __re
   if (threadIdx.x < npad)
     d_side[pad_at + threadIdx.x] = 0;
 }
-
-// ---- readers of an SPMK stream, as mask.hip's kernels read one (its MaskSrc, mask_cursor and mask_next64 are private to
-// that unit, whose code object this one leaves as it is) --------------------------------------------------------------
-struct BitSrc {
-  const uint64_t* words;   // kind 2
-  const uint32_t* tog;     // kind 1
-  uint64_t count;
-  int kind;
-};
-
-struct BitCursor {
-  uint64_t idx, state;
-};
-
-__device__ __forceinline__ BitCursor bit_cursor(const BitSrc& m, uint64_t s)
-{
-  BitCursor c{0, 0};
-  if (m.kind == kMaskKindToggles) {
-    c.idx = mask_toggle_lower_bound(m.tog, m.count, s);
-    c.state = c.idx & 1;
-  }
-  return c;
-}
-
-// the samples [s, s + 64) as a word (the bits at or behind n mean nothing); calls of a cursor go upwards in s
-__device__ __forceinline__ uint64_t bit_next64(const BitSrc& m, BitCursor& c, uint64_t s)
-{
-  if (m.kind == kMaskKindBits) {
-    const uint64_t wi = s >> 6;
-    const uint32_t sh = (uint32_t)(s & 63);
-    uint64_t w = m.words[wi] >> sh;
-    if (sh && wi + 1 < m.count)
-      w |= m.words[wi + 1] << (64 - sh);
-    return w;
-  }
-  if (m.kind == kMaskKindToggles)
-    return mask_word_from_toggles(m.tog, m.count, s, &c.idx, &c.state);
-  return 0;
-}
-
-BitSrc bit_src(const MaskStream& m)
-{
-  return BitSrc{static_cast<const uint64_t*>(m.d_payload), static_cast<const uint32_t*>(m.d_payload), m.h.count,
-                m.h.kind};
-}
-
-struct RelBox {
-  uint64_t vx, vy;          // the volume's row and slice extents
-  uint64_t lx, ly, lz;      // the box's origin
-  uint64_t bx, by, rows;    // the box's row length, rows per slice, rows in all
-  uint64_t pieces;          // kMaskTile pieces of a row
-};
 
 // (dst may be yp when OT is double: a lane loads its samples of a piece before it stores any, and nobody else's.  All
 //  the loads of a piece go out before the first store: the two pointers may alias, so the compiler cannot move them)
@@ -368,10 +290,11 @@ size_t rel_workspace_bytes(size_t n)
   return ws ? up256(ws) + up256(sizeof(RelRecord)) : 0;
 }
 
-int rel_forward_run(const void* d_src, int is_float, size_t n, double* d_y, void* ws, RelForward* res, void* hip_stream)
+int rel_forward_run(const void* d_src, int is_float, size_t n, double* d_y, void* ws, RelForward* res, void* hip_stream,
+                    int kind)
 {
   MaskBitsParts w;
-  if (!d_src || !d_y || !res || !ws || rel_workspace_bytes(n) == 0 || !mask_bits_parts(ws, n, &w))
+  if (!d_src || !d_y || !res || !ws || !rel_kind_ok(kind) || rel_workspace_bytes(n) == 0 || !mask_bits_parts(ws, n, &w))
     return -1;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   RelRecord* rec = rel_record(ws, n);
@@ -379,8 +302,9 @@ int rel_forward_run(const void* d_src, int is_float, size_t n, double* d_y, void
   if (rel_grid((n + kMaskTile - 1) / kMaskTile, &groups))
     return -1;
   HIP_CHECK(hipMemsetAsync(&rec->nonfinite, 0, sizeof(uint32_t), st));
-  if (is_float ? forward_launch(static_cast<const float*>(d_src), n, d_y, w, &rec->nonfinite, groups, st)
-               : forward_launch(static_cast<const double*>(d_src), n, d_y, w, &rec->nonfinite, groups, st))
+  if (kind == kRelLog ? rel_log_forward_launch(d_src, is_float, n, d_y, w, &rec->nonfinite, groups, hip_stream)
+      : is_float      ? forward_launch(static_cast<const float*>(d_src), n, d_y, w, &rec->nonfinite, groups, st)
+                      : forward_launch(static_cast<const double*>(d_src), n, d_y, w, &rec->nonfinite, groups, st))
     return -1;
   if (mask_bits_finish_run(ws, n, groups, hip_stream))
     return -1;
@@ -408,17 +332,13 @@ int rel_side_run(const RelHeader& h, const void* ws, const MaskResult& sign, voi
 
 int rel_inverse_run(const double* d_y, const size_t vol[3], const size_t lo[3], const size_t dims[3],
                     const MaskStream& zero, const MaskStream& sign, int src_float, int output_float, void* d_dst,
-                    void* hip_stream)
+                    void* hip_stream, int kind)
 {
-  if (!d_y || !d_dst || !zero.d_payload || !sign.d_payload)
+  if (kind == kRelLog)
+    return rel_log_inverse_run(d_y, vol, lo, dims, zero, sign, src_float, output_float, d_dst, hip_stream);
+  if (!d_y || !d_dst || !zero.d_payload || !sign.d_payload || kind != kRelLinear)
     return -1;
-  RelBox g;
-  const bool whole = dims[0] == vol[0] && dims[1] == vol[1] && dims[2] == vol[2];
-  if (whole)   // one row of n samples
-    g = RelBox{zero.h.n, 1, 0, 0, 0, zero.h.n, 1, 1, 0};
-  else
-    g = RelBox{vol[0], vol[1], lo[0], lo[1], lo[2], dims[0], dims[1], (uint64_t)dims[1] * dims[2], 0};
-  g.pieces = (g.bx + kMaskTile - 1) / kMaskTile;
+  const RelBox g = rel_box_of(vol, lo, dims, zero.h.n);
   uint32_t groups = 0;
   if (rel_grid(g.rows * g.pieces, &groups))
     return -1;

@@ -3,14 +3,17 @@
 
   kernels     n^3 (512) fp32 and fp64: rel_forward and rel_inverse as calls, and k_rel_forward / k_rel_inverse alone (the
               library's profiler brackets each launch with events), against the torch passes they replace -- frexp,
-              signbit, == 0 and back.  The kernels move 12 (fp32) or 16 (fp64) bytes a sample forward and 12 or 16 back
+              signbit, == 0 and back; and the same for the LOG map kind (map="log": k_rel_log_forward /
+              k_rel_log_inverse, which add some forty fp64 operations a sample to the same traffic), each with its ratio
+              to the linear kind's kernel of the same run.  The kernels move 12 (fp32) or 16 (fp64) bytes a sample forward and 12 or 16 back
               (8 of y', 4 or 8 of x'; the bit streams are a sixty-fourth of that); reported as a fraction of the HBM peak.
               The forward CALL also surveys y for its zeros, packs two streams and copies y to the caller.
   composites  m^3 (256): compress_rel / decompress_rel against compress in mode 3 at t / decompress of the same y
               volume, in-filled, already resident as doubles: the difference is the feature's cost
-  kinks       on the same synthetic field (six decades, both signs) at eps 1e-2 and 1e-4: the container of compress_rel
-              against mode 3 on log2|x| computed by torch at the tolerance log2(1 + eps) -- what the piecewise linear
-              logarithm costs against the true one.  A record for a later decision, no pass criterion.
+  kinks       on the same synthetic field (six decades, both signs) at eps 1e-2 and 1e-4, three containers: compress_rel
+              of the linear kind, compress_rel of the log kind, and mode 3 on log2|x| computed by torch at the
+              tolerance log2(1 + eps) -- what the piecewise linear logarithm costs against the true one, and that the
+              library's own log kind collects it.  A record, no pass criterion.
 
 Every time is the median (and min ... max) of --runs calls after --warmup, each timed with events on the current stream
 around the call alone; the sides of a comparison alternate run by run.
@@ -103,24 +106,33 @@ def bench_kernels(torch, eng, n, runs, warmup):
         v = synthetic(torch, n, dtype)
         nsamp, esz = v.numel(), v.element_size()
         y, side, nzero, nneg = eng.rel_forward(v)
+        ylog, slog, _, _ = eng.rel_forward(v, map="log")
         ty, tneg, tzero = torch_forward(torch, v)
         back = torch.empty_like(v)
-        calls = {"rel_forward": lambda: eng.rel_forward(v), "torch_forward": lambda: torch_forward(torch, v),
-                 "rel_inverse": lambda: eng.rel_inverse(y, side, output_float=(dtype == torch.float32), out=back),
+        isf = dtype == torch.float32
+        calls = {"rel_forward": lambda: eng.rel_forward(v), "rel_forward_log": lambda: eng.rel_forward(v, map="log"),
+                 "torch_forward": lambda: torch_forward(torch, v),
+                 "rel_inverse": lambda: eng.rel_inverse(y, side, output_float=isf, out=back),
+                 "rel_inverse_log": lambda: eng.rel_inverse(ylog, slog, output_float=isf, out=back),
                  "torch_inverse": lambda: torch_inverse(torch, ty, tneg, tzero, dtype)}
         ms = timed(torch, calls, runs, warmup)
         rec = {k: stats(vv) for k, vv in ms.items()}
-        for kernel, fn, nbytes in (("k_rel_forward", calls["rel_forward"], nsamp * (esz + 8) + nsamp // 8),
-                                   ("k_rel_inverse", calls["rel_inverse"], nsamp * (8 + esz) + nsamp // 4)):
+        fwd_bytes, inv_bytes = nsamp * (esz + 8) + nsamp // 8, nsamp * (8 + esz) + nsamp // 4
+        for kernel, fn, nbytes in (("k_rel_forward", calls["rel_forward"], fwd_bytes),
+                                   ("k_rel_log_forward", calls["rel_forward_log"], fwd_bytes),
+                                   ("k_rel_inverse", calls["rel_inverse"], inv_bytes),
+                                   ("k_rel_log_inverse", calls["rel_inverse_log"], inv_bytes)):
             k = stats(kernel_ms(torch, eng, fn, kernel, runs, warmup))
             k["bytes"] = nbytes
             k["TB_per_s"] = round(nbytes / (k["median"] * 1e-3) / 1e12, 3)
             k["fraction_of_hbm_peak"] = round(nbytes / (k["median"] * 1e-3) / HBM_PEAK, 3)
             rec[kernel] = k
+        for way in ("forward", "inverse"):
+            rec["log_over_linear_" + way] = round(rec["k_rel_log_" + way]["median"] / rec["k_rel_" + way]["median"], 3)
         rec["samples"], rec["zeros"], rec["negative"], rec["side_bytes"] = nsamp, nzero, nneg, side.numel()
         out[name] = rec
         print(name, json.dumps(rec), flush=True)
-        del v, y, side, ty, tneg, tzero, back
+        del v, y, side, ylog, slog, ty, tneg, tzero, back
         eng.release()
         torch.cuda.empty_cache()
     return out
@@ -139,9 +151,12 @@ def bench_composites(torch, eng, m, runs, warmup):
         eng.mask_make(y, "nan", filled_out=filled, fill="smooth")
         dense = eng.compress(filled, chunks, t, mode=3)
         assert bytes(dense.cpu().numpy()) == bytes(container.cpu().numpy())
+        lcont, lside = eng.compress_rel(v, chunks, eps, map="log")
         calls = {"compress_rel": lambda: eng.compress_rel(v, chunks, eps),
+                 "compress_rel_log": lambda: eng.compress_rel(v, chunks, eps, map="log"),
                  "compress_mode3_of_y": lambda: eng.compress(filled, chunks, t, mode=3),
                  "decompress_rel": lambda: eng.decompress_rel(container, side),
+                 "decompress_rel_log": lambda: eng.decompress_rel(lcont, lside),
                  "decompress_of_y": lambda: eng.decompress(dense, output_float=False)}
         ms = timed(torch, calls, runs, warmup)
         rec = {k: stats(vv) for k, vv in ms.items()}
@@ -160,6 +175,11 @@ def bench_composites(torch, eng, m, runs, warmup):
         clog = eng.compress(flog, chunks, tl, mode=3)
         rec.update(true_log_tolerance=tl, true_log_container_bytes=clog.numel(),
                    kink_ratio=round(container.numel() / clog.numel(), 4))
+        # the library's own log kind: its container, its guarantee
+        lworst, lviol, lmis, _ = eng.rel_check(v, eng.decompress_rel(lcont, lside), eps)
+        rec.update(log_kind_t=eng.rel_tolerance(eps, True, map="log"), log_kind_container_bytes=lcont.numel(),
+                   log_kind_side_bytes=lside.numel(), linear_over_log_kind=round(container.numel() / lcont.numel(), 4),
+                   log_kind_worst_relative_error=lworst, log_kind_violations=lviol, log_kind_class_mismatches=lmis)
         out["eps_%g" % eps] = rec
         print("eps", eps, json.dumps(rec), flush=True)
     return out
