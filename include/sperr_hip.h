@@ -147,6 +147,36 @@ int sperrhip_decompress_dev(const void* d_src, size_t src_len, int output_float,
                             size_t dst_cap_bytes, size_t* dimx, size_t* dimy, size_t* dimz,
                             void* hip_stream);
 
+/* ---- compression to a byte target (the size mode) ------------------------------------------------
+ * Fixed-rate mode gives every chunk the same bits per sample, whatever it holds.  These calls give a whole volume a
+ * byte target and deal it to the chunks so that all of them stop at (nearly) the same ABSOLUTE threshold q_c 2^p: a
+ * chunk of background gets a few bytes, the chunk that holds the feature the rest.  The result is an ordinary
+ * fixed-rate container (chunk lengths are in its header): every reader of mode-1 containers opens it.
+ *
+ * sperrhip_chunk_count: the chunks the container of such a volume has (0: a dimension is 0) -- the entries the calls
+ * below write into the caller's host arrays.  nchunks_cap / budgets_cap state how many entries those arrays hold: a
+ * call whose arrays are too short returns -1 and writes nothing.
+ *
+ * sperrhip_size_survey_dev: what any threshold would cost, without compressing.  Per chunk, in container order (host
+ * arrays of nchunks entries): q[c] the fixed-rate quantisation step, nbp[c] the number of bit planes, end[c * 32 + p]
+ * the chunk stream's payload bits at the end of plane p under an unlimited budget (zeros from nbp[c] on), is_const[c]
+ * whether the chunk is constant (17 bytes, no planes).  Coding chunk c down to plane p leaves an error of the order
+ * of q[c] 2^p and takes 26 + end[c * 32 + p] / 8 bytes.
+ *
+ * sperrhip_compress_size_dev: a container of at most target_bytes bytes.  budgets (host, nchunks entries, may be NULL)
+ * receives every chunk's budget in bits: a multiple of 8, 0 for a constant chunk.  The container is shorter than the
+ * target by less than nchunks + 1 bytes, or by more when the target is beyond every chunk's 32 planes coded in full
+ * (this call never widens the coefficients to 64 bits).  Returns 0 ok; -1, with nothing written to d_dst, when the
+ * target does not hold the headers and one payload byte per chunk that is not constant.
+ * Volumes as sperrhip_compress_dev takes them in mode 1; no views, batches, fields, masked or relative volumes. */
+size_t sperrhip_chunk_count(size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z);
+int sperrhip_size_survey_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                             size_t chunk_y, size_t chunk_z, size_t nchunks_cap, double* q, int32_t* nbp, uint64_t* end,
+                             uint8_t* is_const, void* hip_stream);
+int sperrhip_compress_size_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                               size_t chunk_y, size_t chunk_z, size_t target_bytes, void* d_dst, size_t dst_cap,
+                               size_t* dst_len, uint64_t* budgets, size_t budgets_cap, void* hip_stream);
+
 /* Reads the container header of a device-resident container on the default stream, which does not wait for a
  * non-blocking stream: for a container that work on another stream is still writing, use the _stream_ call.
  * Returns 0 ok. */
@@ -172,6 +202,14 @@ int sperrhip_dwt3d_dev(double* d_vals, size_t dimx, size_t dimy, size_t dimz, in
 int sperrhip_speck3d_encode_dev(const void* d_coef, int width, const uint64_t* d_sign, size_t dimx,
                                 size_t dimy, size_t dimz, size_t budget_bits, void* d_dst,
                                 size_t dst_cap, size_t* dst_len, void* hip_stream);
+
+/* The plane table of one chunk of quantised coefficients, as given to sperrhip_speck3d_encode_dev: end[p], p < 64 (host
+ * memory), receives the stream's length in bits at the end of bit plane p -- after its sorting and its refinement pass --
+ * under an unlimited budget, zeros from the plane count *nbp on.  It is counted from the set pyramid and the pixel
+ * census; no stream is written.  width must be 4; the 64-bit coefficient pass and 2D slices (dimz = 0) are refused
+ * with -1. */
+int sperrhip_speck3d_plane_bits_dev(const void* d_coef, int width, const uint64_t* d_sign, size_t dimx, size_t dimy,
+                                    size_t dimz, uint64_t* end, int* nbp, void* hip_stream);
 
 /* The outlier coder of point-wise error mode (mode 3) on its own: d_orig (floats when is_float,
  * else doubles) and d_recon (doubles) hold nchunks chunks of dimx*dimy*dimz samples stacked along

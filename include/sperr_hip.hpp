@@ -836,6 +836,48 @@ inline auto rel_check_dev(const T* d_orig, const T* d_recon, size_t n, double ep
   return detail::mask_rtn(sperrhip_rel_check_dev(d_orig, d_recon, sizeof(T) == 4, n, eps, out.data(), hip_stream));
 }
 
+// ---- compression to a byte target (the size mode, sperr_hip.h) ----
+// A volume's survey: what every threshold would cost.  The vectors get one entry per chunk in container order, `end`
+// 32 per chunk (end[c * 32 + p]: the payload bits of chunk c's stream at the end of bit plane p)
+struct SizeSurvey {
+  std::vector<double> q;
+  std::vector<int32_t> nbp;
+  std::vector<uint64_t> end;
+  std::vector<uint8_t> is_const;
+};
+
+template <typename T>
+inline auto size_survey_dev(const T* d_src, dims_type dims, dims_type chunks, SizeSurvey& out, void* hip_stream = nullptr)
+    -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  const size_t n = sperrhip_chunk_count(dims[0], dims[1], dims[2], chunks[0], chunks[1], chunks[2]);
+  out.q.assign(n, 0.0);
+  out.nbp.assign(n, 0);
+  out.end.assign(n * 32, 0);
+  out.is_const.assign(n, 0);
+  return detail::mask_rtn(sperrhip_size_survey_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0], chunks[1],
+                                                   chunks[2], n, out.q.data(), out.nbp.data(), out.end.data(),
+                                                   out.is_const.data(), hip_stream));
+}
+
+// A container of at most target_bytes bytes whose chunks all stop at (nearly) the same absolute threshold; budgets (may
+// be null): every chunk's budget in bits.  Error, with nothing written to d_out, when the target does not hold the
+// headers and a payload byte per chunk
+template <typename T>
+inline auto compress_size_dev(const T* d_src, dims_type dims, dims_type chunks, size_t target_bytes, void* d_out, size_t cap,
+                              size_t& out_len, std::vector<uint64_t>* budgets = nullptr, void* hip_stream = nullptr)
+    -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  if (budgets)
+    budgets->assign(sperrhip_chunk_count(dims[0], dims[1], dims[2], chunks[0], chunks[1], chunks[2]), 0);
+  return detail::mask_rtn(sperrhip_compress_size_dev(d_src, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0], chunks[1],
+                                                     chunks[2], target_bytes, d_out, cap, &out_len,
+                                                     budgets ? budgets->data() : nullptr, budgets ? budgets->size() : 0,
+                                                     hip_stream));
+}
+
 }  // namespace sperr
 
 #endif

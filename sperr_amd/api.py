@@ -54,6 +54,7 @@ EXPORTS = [
     "sperrhip_rel_check_dev",
     "sperrhip_rel_tolerance_kind", "sperrhip_rel_forward_kind_dev", "sperrhip_compress_rel_kind_dev",
     "sperrhip_rel_parse_stream_kind_dev",
+    "sperrhip_speck3d_plane_bits_dev", "sperrhip_chunk_count", "sperrhip_size_survey_dev", "sperrhip_compress_size_dev",
 ]
 
 
@@ -302,6 +303,15 @@ def load_library():
     lib.sperrhip_parse_header_stream_dev.argtypes = lib.sperrhip_parse_header_dev.argtypes + [_vp]
     lib.sperrhip_dwt3d_dev.restype = C.c_int
     lib.sperrhip_dwt3d_dev.argtypes = [_vp, _sz, _sz, _sz, C.c_int, _vp]
+    lib.sperrhip_speck3d_plane_bits_dev.restype = C.c_int
+    lib.sperrhip_speck3d_plane_bits_dev.argtypes = [_vp, C.c_int, _vp, _sz, _sz, _sz, _vp, C.POINTER(C.c_int), _vp]
+    lib.sperrhip_size_survey_dev.restype = C.c_int
+    lib.sperrhip_chunk_count.restype = _sz
+    lib.sperrhip_chunk_count.argtypes = [_sz] * 6
+    lib.sperrhip_size_survey_dev.argtypes = [_vp, C.c_int, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp]
+    lib.sperrhip_compress_size_dev.restype = C.c_int
+    lib.sperrhip_compress_size_dev.argtypes = [_vp, C.c_int, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _sz,
+                                               C.POINTER(_sz), _vp, _sz, _vp]
     lib.sperrhip_speck3d_encode_dev.restype = C.c_int
     lib.sperrhip_speck3d_encode_dev.argtypes = [_vp, C.c_int, _vp, _sz, _sz, _sz, _sz, _vp, _sz,
                                                 C.POINTER(_sz), _vp]
@@ -424,6 +434,60 @@ class SperrHip:
         if rtn != 0:
             raise SperrHipError(f"sperrhip_compress_dev returned {rtn}")
         return out[:n.value]
+
+    # ---- compression to a byte target (the size mode) ---------------------------------------
+    def _chunk_count(self, shape_zyx, chunks_xyz):
+        dz, dy, dx = (int(d) for d in shape_zyx)
+        return int(self.lib.sperrhip_chunk_count(dx, dy, dz, *(int(c) for c in chunks_xyz)))
+
+    def _size_args(self, vol, what):
+        torch = self.torch
+        if not (vol.is_cuda and vol.dim() == 3 and vol.dtype in (torch.float32, torch.float64)):
+            raise SperrHipError(f"{what} takes a 3-D cuda tensor of float32 or float64")
+        self._no_view(vol, what)
+
+    def size_survey(self, vol, chunks_xyz):
+        """What any absolute threshold would cost, without compressing.  vol as compress() takes it (contiguous).
+        Returns a dict of numpy arrays, one entry per chunk in container order: "q" the fixed-rate quantisation
+        step, "nbp" the number of bit planes, "end" (nchunks, 32) uint64 -- end[c, p] the payload bits of chunk c's
+        stream at the end of plane p under an unlimited budget, zeros from nbp[c] on --, "is_const" bool.  Coding
+        chunk c down to plane p leaves an error of the order of q[c] * 2**p and takes 26 + end[c, p] / 8 bytes."""
+        self._size_args(vol, "size_survey")
+        dz, dy, dx = vol.shape
+        n = self._chunk_count(vol.shape, chunks_xyz)
+        q, nbp = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int32)
+        end, ic = np.zeros((n, 32), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        rtn = self.lib.sperrhip_size_survey_dev(vol.data_ptr(), int(vol.dtype == self.torch.float32), dx, dy, dz,
+                                                *chunks_xyz, n, q.ctypes.data, nbp.ctypes.data, end.ctypes.data,
+                                                ic.ctypes.data, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_size_survey_dev returned {rtn}")
+        return {"q": q, "nbp": nbp, "end": end, "is_const": ic.astype(bool)}
+
+    def compress_to_size(self, vol, chunks_xyz, nbytes, out=None, return_plan=False):
+        """A container of at most `nbytes` bytes: an ordinary fixed-rate container whose chunks each got a budget of
+        their own, dealt so that all of them stop at (nearly) the same absolute threshold (budget.h).  vol as
+        compress() takes it (contiguous); `out`, when given and at least nbytes long, receives the container and is
+        not written when the call is refused (SperrHipError: the target does not hold the headers and a payload
+        byte per chunk).  Returns the container (a cuda uint8 view), with return_plan the pair (container, budgets):
+        every chunk's budget in bits as a numpy uint64 array, 0 for a constant chunk."""
+        self._size_args(vol, "compress_to_size")
+        torch = self.torch
+        dz, dy, dx = vol.shape
+        nbytes = int(nbytes)
+        if nbytes < 0:
+            raise SperrHipError("a byte target is not negative")
+        n = self._chunk_count(vol.shape, chunks_xyz)
+        if out is None or out.numel() < nbytes:
+            out = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=vol.device)
+        budgets = np.zeros(n, dtype=np.uint64)
+        ln = _sz(0)
+        rtn = self.lib.sperrhip_compress_size_dev(vol.data_ptr(), int(vol.dtype == torch.float32), dx, dy, dz,
+                                                  *chunks_xyz, nbytes, out.data_ptr(), out.numel(), C.byref(ln),
+                                                  budgets.ctypes.data, n, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_size_dev returned {rtn}")
+        return (out[:ln.value], budgets) if return_plan else out[:ln.value]
 
     def parse_header(self, container):
         """((z, y, x), is_float, chunks (x, y, z)) of a device container's header, read on the current stream: behind
@@ -1236,6 +1300,20 @@ class SperrHip:
         if rtn != 0:
             raise SperrHipError(f"sperrhip_speck3d_encode_dev returned {rtn}")
         return bytes(out[:ln.value].cpu().numpy())
+
+    def speck3d_plane_bits(self, coef, sign):
+        """The plane table of one chunk's quantised coefficients (cuda int32 holding uint32 bits, (z, y, x); sign as in
+        speck3d_encode): (end, nbp) -- end[p], a numpy uint64 array of 64, the stream's bits at the end of plane p
+        under an unlimited budget, zeros from the plane count nbp on.  Counted, not coded: no stream is written."""
+        assert coef.is_cuda and coef.is_contiguous() and sign.is_cuda and coef.dim() == 3
+        dz, dy, dx = coef.shape
+        end = np.zeros(64, dtype=np.uint64)
+        nbp = C.c_int(0)
+        rtn = self.lib.sperrhip_speck3d_plane_bits_dev(coef.data_ptr(), coef.element_size(), sign.data_ptr(), dx, dy, dz,
+                                                       end.ctypes.data, C.byref(nbp), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_speck3d_plane_bits_dev returned {rtn}")
+        return end, nbp.value
 
     def speck2d_encode(self, coef, sign, budget_bits=0):
         """The 2D coder (the quadtree forest and the type-I set of a slice) on its own.  coef: cuda int32 (uint32

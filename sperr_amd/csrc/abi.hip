@@ -333,6 +333,48 @@ int sperrhip_compress_dev(const void* d_src, int is_float, size_t dimx, size_t d
   });
 }
 
+// ---- the size mode (budget.h) ----
+size_t sperrhip_chunk_count(size_t dimx, size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z)
+{
+  const size_t n = container_chunk_count(Dims{dimx, dimy, dimz}, Dims{chunk_x, chunk_y, chunk_z});
+  return n == SIZE_MAX ? 0 : n;
+}
+
+int sperrhip_size_survey_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                             size_t chunk_y, size_t chunk_z, size_t nchunks_cap, double* q, int32_t* nbp, uint64_t* end,
+                             uint8_t* is_const, void* hip_stream)
+{
+  return guarded("sperrhip_size_survey_dev", [&]() -> int {
+    if (!d_src || !q || !nbp || !end || !is_const || dimx == 0 || dimy == 0 || dimz == 0)
+      return -1;
+    if (nchunks_cap < sperrhip_chunk_count(dimx, dimy, dimz, chunk_x, chunk_y, chunk_z))
+      return -1;   // (the caller's arrays are too short)
+    Lease L(static_cast<hipStream_t>(hip_stream));
+    if (!L.e)
+      return -1;
+    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
+    return size_survey_to(*L.e, d_src, is_float, vol, ch, q, nbp, end, is_const, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int sperrhip_compress_size_dev(const void* d_src, int is_float, size_t dimx, size_t dimy, size_t dimz, size_t chunk_x,
+                               size_t chunk_y, size_t chunk_z, size_t target_bytes, void* d_dst, size_t dst_cap,
+                               size_t* dst_len, uint64_t* budgets, size_t budgets_cap, void* hip_stream)
+{
+  return guarded("sperrhip_compress_size_dev", [&]() -> int {
+    if (!d_src || !d_dst || !dst_len || dimx == 0 || dimy == 0 || dimz == 0)
+      return -1;
+    if (budgets && budgets_cap < sperrhip_chunk_count(dimx, dimy, dimz, chunk_x, chunk_y, chunk_z))
+      return -1;   // (the caller's array is too short)
+    Lease L(static_cast<hipStream_t>(hip_stream));
+    if (!L.e)
+      return -1;
+    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
+    return compress_size_to(*L.e, d_src, is_float, vol, ch, target_bytes, static_cast<uint8_t*>(d_dst), dst_cap, dst_len,
+                            budgets, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
 int sperrhip_compress_view_dev(const void* d_src, const sperrhip_view* view, int is_float, size_t dimx, size_t dimy,
                                size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
                                void* d_dst, size_t dst_cap, size_t* dst_len, void* hip_stream)

@@ -59,6 +59,25 @@ int sperrhip_speck3d_encode_dev(const void* d_coef, int width, const uint64_t* d
   });
 }
 
+int sperrhip_speck3d_plane_bits_dev(const void* d_coef, int width, const uint64_t* d_sign, size_t dimx, size_t dimy,
+                                    size_t dimz, uint64_t* end, int* nbp, void* hip_stream)
+{
+  return guarded("sperrhip_speck3d_plane_bits_dev", [&]() -> int {
+    // (refused: the 64-bit coefficient pass, and 2D slices -- the type-I set's bits are not in the table)
+    if (width != 4 || !d_coef || !d_sign || !end || !nbp || dimx == 0 || dimy == 0 || dimz == 0)
+      return -1;
+    Lease L(static_cast<hipStream_t>(hip_stream));
+    if (!L.e)
+      return -1;
+    Engine& E = *L.e;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    ShapePlan* P = E.plan(dimx, dimy, dimz);
+    if (!P)
+      return -1;
+    return speck3d_plane_bits_stage(E, st, *P, d_coef, d_sign, end, nbp);
+  });
+}
+
 int sperrhip_outlier_encode_dev(const void* d_orig, int is_float, const double* d_recon, size_t dimx, size_t dimy,
                                 size_t dimz, size_t nchunks, double tol, void* d_dst, size_t dst_cap, size_t* lens,
                                 void* hip_stream)

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <deque>
 
+#include "budget.h"
 #include "engine_parts.h"
 
 namespace sperrhip {
@@ -272,6 +273,70 @@ struct ChunkRef {
   uint32_t gid;
   uint32_t org[3];
 };
+
+// ---- the size mode (budget.h) ----
+// a volume's survey on the device, by chunk number: the deal's table
+struct SizeSurveyDev {
+  double* q;
+  int32_t* nbp;
+  uint64_t* end;       // [nchunks][kBudgetPlanes]
+  uint8_t* is_const;
+};
+// arena bytes a chunk of a size-mode batch takes beside the coder's arrays (EncodeCall::code)
+constexpr size_t kSizeBytesPerChunk = (3 * kMaxPlanes + kMaxPlanes) * 8 + 1024;
+
+// a batch's plane table (rows of kMaxPlanes, by local index) into the volume's (rows of kBudgetPlanes, by chunk number).
+// The 32-bit pass has at most 32 planes: a fixed-rate step is maxabs / (2^32 - 1)
+__global__ void k_survey_gather(const CoderState* cst, const uint64_t* end, const int32_t* nbp, const uint32_t* gids,
+                                uint32_t nb, SizeSurveyDev sv)
+{
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nb)
+    return;
+  const uint32_t g = gids[c];
+  const CoderState& cs = cst[c];
+  sv.is_const[g] = cs.is_const ? 1 : 0;
+  sv.q[g] = cs.is_const ? 0.0 : cs.q;
+  sv.nbp[g] = cs.is_const ? 0 : nbp[c];
+  for (int p = 0; p < kBudgetPlanes; p++)
+    sv.end[(size_t)g * kBudgetPlanes + p] = cs.is_const ? 0ull : end[(size_t)c * kMaxPlanes + p];
+}
+
+// the deal on the device: one workgroup is budget.h's team
+struct BudgetBlock {
+  uint32_t rank, size;
+  uint64_t* sm;   // [kThreads / 64 + 1]
+  template <class Op>
+  __device__ uint64_t reduce(uint64_t v, Op op)
+  {
+    for (int d = 32; d > 0; d >>= 1) {
+      const uint64_t o = __shfl_xor(v, d, 64);
+      v = op(v, o);
+    }
+    __syncthreads();   // (the words of the reduction before this one have been read)
+    if ((threadIdx.x & 63) == 0)
+      sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t r = sm[0];
+    for (uint32_t w = 1; w < blockDim.x / 64; w++)
+      r = op(r, sm[w]);
+    return r;
+  }
+  __device__ uint64_t sum(uint64_t v) { return reduce(v, [](uint64_t a, uint64_t b) { return a + b; }); }
+  __device__ uint64_t min(uint64_t v) { return reduce(v, [](uint64_t a, uint64_t b) { return a < b ? a : b; }); }
+  __device__ uint64_t max(uint64_t v) { return reduce(v, [](uint64_t a, uint64_t b) { return a > b ? a : b; }); }
+};
+
+// out[0]: 0 ok, 1 refused; out[1..2]: the bit patterns of T* and T'
+__global__ void __launch_bounds__(kThreads) k_budget_deal(SizeSurveyDev sv, uint32_t nchunks, uint64_t W, uint64_t* budgets, uint64_t* out)
+{
+  __shared__ uint64_t sm[kThreads / 64 + 1];
+  BudgetBlock team{threadIdx.x, blockDim.x, sm};
+  const BudgetTable t{nchunks, sv.q, sv.nbp, sv.end, sv.is_const};
+  const int rc = budget_deal(t, W, budgets, out + 1, team);
+  if (threadIdx.x == 0)
+    out[0] = rc ? 1ull : 0ull;
+}
 
 struct EncBatchBufs {
   EncBuffers eb;
@@ -1022,6 +1087,8 @@ struct EncodeCall {
     std::vector<CoderState> hc;
     std::vector<ChunkGeom> hg;
     std::vector<uint32_t> hid;
+    std::vector<uint64_t> hbud;   // (size mode: the batch's budgets, the source of a queued copy)
+    uint64_t* d_bud = nullptr;    //   ... and where they land: EncPlanHost::d_budgets of every head of the batch
     bool orgAligned = true;
     EncPlanHost ph;
   };
@@ -1063,6 +1130,28 @@ struct EncodeCall {
   uint64_t total = 0;
   std::vector<uint64_t> bases;   // (a batch: where each container starts, then the total)
   bool ok = false;
+  // The size mode (compress_size_impl; budget.h), two calls over the same volume in fixed-rate mode.  sizePass 1, the
+  // SURVEY: float stages and the coder's head per batch, then the plane table instead of the plane loop -- every chunk's
+  // q, plane count, table row and constness land in `sv`, by chunk number; no stream, no slot, no container.  sizePass 2:
+  // the fixed-rate flow with a budget per chunk, hBudgets[chunk number] in bits, which each batch uploads for
+  // k_enc_state_init; a group's workspace is sized by its largest budget.  Both run one shape group after the other
+  // and a group in one part: the survey's read-back and the deal stand between the passes anyway
+  int sizePass = 0;
+  SizeSurveyDev sv{};
+  const uint64_t* hBudgets = nullptr;
+  // a shape group's raw budget in bits (src/SPECK_FLT.cpp:491), which sizes its streams, masks and slots
+  uint64_t raw_of(const ShapePlan& P, const std::vector<ChunkRef>& refs) const
+  {
+    if (sizePass == 1)
+      return 8;   // (nothing is written)
+    if (sizePass == 2) {
+      uint64_t m = 8;
+      for (auto& r : refs)
+        m = std::max(m, hBudgets[r.gid]);
+      return m;
+    }
+    return (uint64_t)(bpp * (double)P.N);
+  }
   ~EncodeCall() { if (!ok) drain_after_error(E, st); }
   // (a slice is coded on the 2D coder's forest, the plan with z extent 0)
   ShapePlan* plan_of(const GKey& d) { return E.plan(d[0], d[1], slice ? 0 : d[2]); }
@@ -1097,6 +1186,10 @@ struct EncodeCall {
         return -1;
     if (late_planes() || late_retry())
       return -1;
+    if (sizePass == 1) {   // (the caller reads the survey back)
+      ok = true;
+      return 0;
+    }
     if (sideBySide)
       for (uint32_t q = 0; q < kSubStreams; q++) {
         HIP_CHECK(hipEventRecord(E.evJoin[q], E.sub[q]));
@@ -1120,7 +1213,7 @@ struct EncodeCall {
       const Dims d{c[1], c[3], c[5]};
       const uint32_t n = count[d], k = seen[d]++;
       static const uint32_t partsMin = tune_getenv("SPERR_HIP_ENC_PARTS_MIN") ? (uint32_t)std::max(2, atoi(tune_getenv("SPERR_HIP_ENC_PARTS_MIN"))) : 64u;
-      const uint32_t parts = (mode == 1 && !slice && n >= partsMin && n <= 512) ? std::min<uint32_t>(std::min<uint32_t>(partsEnv, n / 4), kSubStreams) : 1u;
+      const uint32_t parts = (mode == 1 && !slice && !sizePass && n >= partsMin && n <= 512) ? std::min<uint32_t>(std::min<uint32_t>(partsEnv, n / 4), kSubStreams) : 1u;
       groups[GKey{c[1], c[3], c[5], (size_t)((uint64_t)k * parts / n)}].push_back(
           {i, {(uint32_t)c[0], (uint32_t)c[2], (uint32_t)c[4]}});
     }
@@ -1135,7 +1228,7 @@ struct EncodeCall {
       if (!P)
         return -1;
       groupPlan.push_back(P);
-      const uint64_t raw = (uint64_t)(bpp * (double)P->N);
+      const uint64_t raw = raw_of(*P, g.second);
       const uint64_t len = 26 + (max_payload_bits(*P, raw) + 7) / 8;
       for (auto& r : g.second)
         slotLen[r.gid] = round_up(len, 256);
@@ -1160,7 +1253,7 @@ struct EncodeCall {
   // waits until all groups are enqueued
   int plan_side_by_side()
   {
-    sideBySide = mode == 1 && !slice && groups.size() > 1;
+    sideBySide = mode == 1 && !slice && !sizePass && groups.size() > 1;
     if (!sideBySide)
       return 0;
     size_t fr = 0, tot = 0, need = 0;
@@ -1186,11 +1279,12 @@ struct EncodeCall {
   {
     hipStream_t ss = sideBySide ? E.sub[gi % kSubStreams] : st;
     ShapePlan* P = groupPlan[gi];
-    const uint64_t raw_budget = (uint64_t)(bpp * (double)P->N);  // SPECK_FLT.cpp:491
+    const uint64_t raw_budget = raw_of(*P, refs);  // SPECK_FLT.cpp:491
     // (point-wise error mode: the coder's arrays get memory of their own -- 127 MB more per 256^3 chunk --, so that the
     //  outlier stage's reconstruction can be written into the chunk buffer while the coder runs, see below)
     const bool encAlias = mode != 3;
-    const size_t per = enc_bytes_per_chunk(*P, raw_budget, encAlias);
+    // (the size mode's per-chunk words beside the coder's arrays: the plane table's accumulators and rows, or a budget)
+    const size_t per = enc_bytes_per_chunk(*P, raw_budget, encAlias) + (sizePass ? kSizeBytesPerChunk : 0);
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const size_t budgetBytes = arena_budget(E.arena.n, fr);
@@ -1198,7 +1292,7 @@ struct EncodeCall {
     B = std::min<uint32_t>(B, 256);
     if (sideBySide)
       B = (uint32_t)refs.size();
-    else if (E.arena.ensure(std::max((size_t)B * per, enc_bytes_for(*P, B, raw_budget, encAlias)) + 4096))
+    else if (E.arena.ensure(std::max((size_t)B * per, enc_bytes_for(*P, B, raw_budget, encAlias) + (sizePass ? B * kSizeBytesPerChunk : 0)) + 4096))
       return -1;
     for (size_t b0 = 0; b0 < refs.size(); b0 += B) {
       Batch& b = batches.emplace_back(Batch{P, {}, (uint32_t)std::min<size_t>(B, refs.size() - b0), 0, raw_budget, ss});
@@ -1233,6 +1327,15 @@ struct EncodeCall {
         b.hg[i].org[a] = r.org[a];
       b.orgAligned = b.orgAligned && r.org[0] % (16 / sizeof(T)) == 0;   // (lets the conditioner stream rows with 16-byte loads)
     }
+    if (sizePass == 2) {   // (in front of the quantiser: the fused head initialises the chunks' states)
+      b.hbud.resize(nb);
+      for (uint32_t i = 0; i < nb; i++)
+        b.hbud[i] = hBudgets[b.hid[i]];
+      b.d_bud = A.take<uint64_t>(nb);
+      if (!b.d_bud)
+        return -1;
+      HIP_CHECK(hipMemcpyAsync(b.d_bud, b.hbud.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, b.ss));
+    }
     bool pweWide = false;
     if (quantise(b, &pweWide))
       return -1;
@@ -1263,6 +1366,10 @@ struct EncodeCall {
     }
     if (sideBySide) {   // (a read-back into pageable memory would block the host until this group's stream has
       late[gi] = &b;    //  drained: the retry is looked at once every group is enqueued, late_retry)
+      return 0;
+    }
+    if (sizePass == 1) {   // (the next batch carves the arena again)
+      HIP_CHECK(hipStreamSynchronize(b.ss));
       return 0;
     }
     b.hc.resize(nb);
@@ -1310,7 +1417,8 @@ struct EncodeCall {
       // kernel writes, have memory of their own; what else lies over the chunk buffer is written after it)
       if (reset_enc_pass(b.ss, bb, nb, true))
         return -1;
-      const EncPlanHost ph{b.P->d_initLIS, b.P->d_initLen, b.P->d_depthBlocks, b.P->depthBlockOff, b.P->ht.nsets};
+      EncPlanHost ph{b.P->d_initLIS, b.P->d_initLen, b.P->d_depthBlocks, b.P->depthBlockOff, b.P->ht.nsets};
+      ph.d_budgets = b.d_bud;
       g_dbg_counter[3]++;
       return launch_speck_encode_fused_head(b.ss, e, ph, b.raw_budget, bb.vals, bb.valsStride, b.P->d_fusedRoots);
     }
@@ -1345,6 +1453,23 @@ struct EncodeCall {
     }
     if (!ph.d_bound)
       ph.h_bound = nullptr;
+    if (sizePass == 1) {
+      // the survey: the head alone (no bound: no plane loop follows), then the table, dealt out by chunk number
+      ph.d_bound = nullptr;
+      ph.h_bound = nullptr;
+      ph.evBound = nullptr;
+      uint64_t* d_acc = A.take<uint64_t>((size_t)b.nb * speck_plane_table_acc_words());
+      uint64_t* d_end = A.take<uint64_t>((size_t)b.nb * kMaxPlanes);
+      int32_t* d_nbp = A.take<int32_t>(b.nb);
+      if (!d_acc || !d_end || !d_nbp)
+        return -1;
+      if (launch_speck_encode_head(b.ss, e, ph, 0, false, false) || launch_speck_plane_table(b.ss, e, ph, d_acc, d_end, d_nbp))
+        return -1;
+      LAUNCH_K(k_survey_gather, dim3((b.nb + 63) / 64), dim3(64), 0, b.ss, e.cst, d_end, d_nbp, b.bb.gids, b.nb, sv);
+      HIP_CHECK(hipGetLastError());
+      return 0;
+    }
+    ph.d_budgets = b.d_bud;   // (size mode: the batch's budgets, uploaded in front of the quantiser; null otherwise)
     if (sideBySide && ph.h_bound
             ? launch_speck_encode_head(b.ss, e, ph, b.raw_budget, rate, false)   // (its planes: late_planes)
             : launch_speck_encode(b.ss, e, ph, b.raw_budget, rate, false))
@@ -1566,6 +1691,139 @@ int compress_batch_to(Engine& E, const void* d_src, int is_float, size_t nvol, c
   });
 }
 
+// ---- the size mode's front ----
+namespace {
+
+// the survey's arrays and the deal's words in Engine::sizeWork, for a volume of n chunks
+struct SizeWork {
+  SizeSurveyDev sv;
+  uint64_t* budgets;
+  uint64_t* out;   // k_budget_deal's three words
+};
+int size_work(Engine& E, uint32_t n, SizeWork& w)
+{
+  const size_t bytes = round_up((size_t)n * 8, 256) * 2 + round_up((size_t)n * kBudgetPlanes * 8, 256) +
+                       round_up((size_t)n * 4, 256) + round_up((size_t)n, 256) + 256;
+  if (E.sizeWork.ensure(bytes))
+    return -1;
+  Arena A;
+  A.base = static_cast<char*>(E.sizeWork.p);
+  A.cap = E.sizeWork.n;
+  w.sv.q = A.take<double>(n);
+  w.sv.end = A.take<uint64_t>((size_t)n * kBudgetPlanes);
+  w.budgets = A.take<uint64_t>(n);
+  w.sv.nbp = A.take<int32_t>(n);
+  w.sv.is_const = A.take<uint8_t>(n);
+  w.out = A.take<uint64_t>(4);
+  return w.sv.q && w.sv.end && w.budgets && w.sv.nbp && w.sv.is_const && w.out ? 0 : -1;
+}
+
+uint32_t size_chunk_count(const Dims& vol, const Dims& chunkPref)
+{
+  const size_t n = container_chunk_count(vol, chunkPref);
+  return n > 0xffffffffull ? 0u : (uint32_t)n;   // (0: refused)
+}
+
+// pass 1: the survey of the volume into w (device)
+template <typename T>
+int survey_pass(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkPref, hipStream_t st, const SizeWork& w)
+{
+  EncodeCall<T> call{E, d_src, vol, 1, 0.0, nullptr, 0, st, Coded::Container, 1, nullptr};
+  call.sizePass = 1;
+  call.sv = w.sv;
+  return call.run(chunkPref) ? -1 : 0;
+}
+
+template <typename T>
+int size_survey_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkPref, double* q, int32_t* nbp,
+                     uint64_t* end, uint8_t* is_const, hipStream_t st)
+{
+  const uint32_t n = size_chunk_count(vol, chunkPref);
+  SizeWork w;
+  if (n == 0 || size_work(E, n, w) || survey_pass(E, d_src, vol, chunkPref, st, w))
+    return -1;
+  HIP_CHECK(hipMemcpyAsync(q, w.sv.q, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(nbp, w.sv.nbp, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(end, w.sv.end, (size_t)n * kBudgetPlanes * 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(is_const, w.sv.is_const, (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  HIP_CHECK(hipGetLastError());
+  E.prof.collect();
+  return 0;
+}
+
+template <typename T>
+int compress_size_impl(Engine& E, const T* d_src, const Dims& vol, const Dims& chunkPref, size_t target_bytes,
+                       uint8_t* d_dst, size_t dst_cap, size_t* dst_len, uint64_t* budgets_out, hipStream_t st)
+{
+  const uint32_t n = size_chunk_count(vol, chunkPref);
+  SizeWork w;
+  if (n == 0 || budget_header_bytes(n) > target_bytes || size_work(E, n, w) || survey_pass(E, d_src, vol, chunkPref, st, w))
+    return -1;
+  // the deal: constness decides W, which the host states (budget_payload_bits) -- a first, small read-back --; the
+  // kernel deals; a second read-back brings the budgets, which size pass 2's buffers
+  std::vector<uint8_t> hconst(n);
+  HIP_CHECK(hipMemcpyAsync(hconst.data(), w.sv.is_const, n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  uint64_t nconst = 0, W = 0;
+  for (uint8_t c : hconst)
+    nconst += c ? 1 : 0;
+  if (!budget_payload_bits(target_bytes, n, nconst, &W)) {
+    fprintf(stderr, "[sperr_hip] a target of %zu bytes does not hold the headers of %u chunks and a byte of each\n", target_bytes, n);
+    return -1;
+  }
+  LAUNCH_K(k_budget_deal, dim3(1), dim3(kThreads), 0, st, w.sv, n, W, w.budgets, w.out);
+  std::vector<uint64_t> hb(n);
+  uint64_t hout[3] = {1, 0, 0};
+  HIP_CHECK(hipMemcpyAsync(hb.data(), w.budgets, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hout, w.out, sizeof(hout), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  HIP_CHECK(hipGetLastError());
+  if (hout[0] != 0)
+    return -1;
+  uint64_t sum = 0;
+  for (uint32_t c = 0; c < n; c++) {
+    if (hconst[c] ? hb[c] != 0 : (hb[c] < 8 || hb[c] % 8 != 0))
+      return -1;   // (not a deal)
+    sum += hb[c];
+  }
+  if (sum > W)
+    return -1;
+  // pass 2: the fixed-rate flow on those budgets
+  EncodeCall<T> call{E, d_src, vol, 1, 0.0, d_dst, dst_cap, st, Coded::Container, 1, nullptr};
+  call.sizePass = 2;
+  call.hBudgets = hb.data();
+  if (call.run(chunkPref))
+    return -1;
+  if (call.total > target_bytes) {
+    fprintf(stderr, "[sperr_hip] the dealt container has %llu bytes, beyond the target of %zu\n", (unsigned long long)call.total, target_bytes);
+    return -1;
+  }
+  *dst_len = (size_t)call.total;
+  if (budgets_out)
+    memcpy(budgets_out, hb.data(), (size_t)n * 8);
+  return 0;
+}
+
+}  // namespace
+
+int size_survey_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, double* q, int32_t* nbp,
+                   uint64_t* end, uint8_t* is_const, hipStream_t st)
+{
+  return with_elem(is_float, [&](auto t) {
+    return size_survey_impl(E, static_cast<const decltype(t)*>(d_src), vol, chunkPref, q, nbp, end, is_const, st);
+  });
+}
+
+int compress_size_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, size_t target_bytes,
+                     uint8_t* d_dst, size_t dst_cap, size_t* dst_len, uint64_t* budgets_out, hipStream_t st)
+{
+  return with_elem(is_float, [&](auto t) {
+    return compress_size_impl(E, static_cast<const decltype(t)*>(d_src), vol, chunkPref, target_bytes, d_dst, dst_cap, dst_len,
+                              budgets_out, st);
+  });
+}
+
 int outlier_encode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_orig, int is_float,
                          const double* d_recon, uint32_t nb, double tol, uint8_t* d_dst, size_t dst_cap, size_t* lens)
 {
@@ -1623,6 +1881,51 @@ int speck3d_encode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const vo
   if (len > dst_cap)
     return -1;
   *dst_len = (size_t)len;
+  return 0;
+}
+
+// The plane table of one chunk's integer coefficients: the head of the 32-bit pass (pyramid, chain, census) and
+// launch_speck_plane_table; no plane loop, no stream.  end[0 .. 63] and *nbp are the host's
+int speck3d_plane_bits_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_coef, const uint64_t* d_sign,
+                             uint64_t* end, int* nbp)
+{
+  if (P.dtree.flags & spk::kTree2D)
+    return -1;
+  const uint64_t raw_budget = 8;   // (sizes the stream and the birth masks, which nothing here writes)
+  const size_t accWords = speck_plane_table_acc_words();
+  if (E.arena.ensure(enc_bytes_per_chunk(P, raw_budget) + 8192) || E.misc.ensure(4096))
+    return -1;
+  Arena A;
+  A.base = static_cast<char*>(E.arena.p);
+  A.cap = E.arena.n;
+  EncBatchBufs bb;
+  if (!carve_enc(A, P, 1, raw_budget, bb))
+    return -1;
+  uint64_t* d_acc = A.take<uint64_t>(accWords);
+  uint64_t* d_end = A.take<uint64_t>(kMaxPlanes);
+  int32_t* d_nbp = A.take<int32_t>(1);
+  if (!d_acc || !d_end || !d_nbp)
+    return -1;
+  EncBuffers e = bb.eb;
+  CoderState hcs;
+  memset(&hcs, 0, sizeof(hcs));
+  HIP_CHECK(hipMemcpyAsync(e.cst, &hcs, sizeof(CoderState), hipMemcpyHostToDevice, st));
+  if (reset_enc_pass(st, bb, 1))
+    return -1;
+  const uint32_t n = P.N;
+  HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t*>(e.sign), d_sign, ((n + 63) / 64) * 8, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(bb.coef32, d_coef, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+  LAUNCH_K(k_msb_of<uint32_t>, dim3((n + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(bb.coef32), bb.msb, n);
+  EncPlanHost ph{P.d_initLIS, P.d_initLen, P.d_depthBlocks, P.depthBlockOff, P.ht.nsets};
+  if (launch_speck_encode_head(st, e, ph, 0, false, false) || launch_speck_plane_table(st, e, ph, d_acc, d_end, d_nbp))
+    return -1;
+  int32_t hn = 0;
+  HIP_CHECK(hipMemcpyAsync(end, d_end, kMaxPlanes * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(&hn, d_nbp, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  HIP_CHECK(hipGetLastError());
+  E.prof.collect();
+  *nbp = hn;
   return 0;
 }
 

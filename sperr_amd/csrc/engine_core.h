@@ -325,6 +325,7 @@ struct Engine {
   DevBuf maskPyramid;                       //   ... and the levels of a smooth in-fill (mask_fill.h) in global memory
   DevBuf relStage;                          // relative error (rel.h): the double volume or box y that the coder sees
   DevBuf relWork;                           //   ... and the sign bits' workspace with the read-back record of rel.hip
+  DevBuf sizeWork;                          // size mode (budget.h): the survey's table of the volume and the dealt budgets
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
 
@@ -449,7 +450,7 @@ struct Engine {
   {
     for (auto* b : {&e.arena, &e.slots, &e.misc, &e.outlFixed, &e.outlVar, &e.outlStream, &e.pweBox, &e.wideScratch,
                     &e.fieldsStage, &e.fieldsStage2, &e.boxesStage, &e.maskStage, &e.maskStage2, &e.maskWork,
-                    &e.maskPyramid, &e.relStage, &e.relWork})
+                    &e.maskPyramid, &e.relStage, &e.relWork, &e.sizeWork})
       f(*b);
     for (auto& b : e.outlDec)
       f(b);
@@ -668,11 +669,38 @@ int compress_batch_to(Engine& E, const void* d_src, int is_float, size_t nvol, c
                       int mode, double quality, uint8_t* d_dst, size_t dst_cap, size_t* offsets, hipStream_t st,
                       Coded what = Coded::Container);
 
+// chunks the container of a volume has (the reference's rule, hostc::chunk_segments; SIZE_MAX: too many to count)
+inline size_t container_chunk_count(const Dims& vol, const Dims& chunkPref)
+{
+  Dims cdim;
+  for (int a = 0; a < 3; a++) {
+    if (vol[a] == 0)
+      return 0;
+    cdim[a] = std::min(std::max<size_t>(1, chunkPref[a]), vol[a]);
+  }
+  return chunk_count(vol, cdim);
+}
+
+// The size mode (budget.h).  The survey: per chunk of the volume, in container order, the fixed-rate
+// step q, the plane count, the plane table's row of 32 (the stream's bits at the end of plane p under an unlimited budget)
+// and whether the chunk is constant -- host arrays; no stream is written
+int size_survey_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, double* q, int32_t* nbp,
+                   uint64_t* end, uint8_t* is_const, hipStream_t st);
+// ... and a container of at most target_bytes bytes, every chunk's budget dealt by budget_deal on the survey; budgets_out
+// (host, may be null): the budgets in bits.  -1, with nothing of d_dst written, when the target does not hold the headers
+// and a payload byte per chunk that is not constant
+int compress_size_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, size_t target_bytes,
+                     uint8_t* d_dst, size_t dst_cap, size_t* dst_len, uint64_t* budgets_out, hipStream_t st);
+
 // ---- stage access for the parity tests (abi_stages.hip): one stage of a chunk of the plan's shape on the caller's data
 // (the encoder's stages are encode.hip's, speck3d_decode_stage is decode.hip's)
 // the integer coder on coefficients of 4 or 8 bytes (wide) and their sign words: {u8 planes, u64 total_bits, payload}
 int speck3d_encode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_coef, bool wide,
                          const uint64_t* d_sign, uint64_t raw_budget, uint8_t* d_dst, size_t dst_cap, size_t* dst_len);
+// the plane table of such coefficients (32-bit; 3D forests): end[p], p < 64, the stream's bits at the end of plane p under an
+// unlimited budget, zeros from the plane count *nbp on (launch_speck_plane_table) -- host memory
+int speck3d_plane_bits_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_coef, const uint64_t* d_sign,
+                             uint64_t* end, int* nbp);
 // ... and back: such a stream into coefficients and sign words; *width_out the coefficients' bytes
 int speck3d_decode_stage(Engine& E, hipStream_t st, const ShapePlan& P, const void* d_stream, size_t stream_len,
                          void* d_coef, uint64_t* d_sign, int* width_out);

@@ -113,6 +113,9 @@ struct EncPlanHost {
   // launch_speck_encode_fused_head() has run for this batch's 32-bit pass: the states are initialised, the leaf parents'
   // pyramid level and the census are done -- launch_speck_encode_head() does the rest (ignored by the 64-bit pass)
   bool fusedHead = false;
+  // a budget per chunk of the batch, in bits and multiples of 8, on the device (the size mode's deal, budget.h): every
+  // kernel reads EncState::budget, which k_enc_state_init then fills from here.  Null: raw_budget for all, as ever
+  const uint64_t* d_budgets = nullptr;
 };
 
 int launch_speck_encode(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan,
@@ -129,6 +132,14 @@ int launch_speck_encode_planes(hipStream_t stream, const EncBuffers& b, const En
 // plan.fusedHead set.
 int launch_speck_encode_fused_head(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan, uint64_t raw_budget,
                                    const double* vals, size_t valsStride, const FusedRoot* roots);
+
+// The plane table of a batch whose head has run (launch_speck_encode_head): d_end[c * kMaxPlanes + p] = the stream
+// position in bits at the end of plane p of chunk c under an unlimited budget, zeros from the chunk's plane count on;
+// d_nbp[c] that count (0 of a constant chunk).  d_acc: nchunks * speck_plane_table_acc_words() words of workspace.
+// 3D forests only (-1 for the 2D coder's).
+size_t speck_plane_table_acc_words();
+int launch_speck_plane_table(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan, uint64_t* d_acc,
+                             uint64_t* d_end, int32_t* d_nbp);
 
 }  // namespace sperrhip
 #endif

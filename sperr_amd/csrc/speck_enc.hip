@@ -37,8 +37,9 @@ using namespace spk;
     return;
 
 // ------------------------------------------------------------------------------------------
+// (budgets: a budget per chunk, in bits and multiples of 8 -- the size mode's deal, budget.h; null: `budget` for all)
 __global__ void k_enc_state_init(EncBuffers b, const uint64_t* initLIS, const uint32_t* initLen,
-                                 uint64_t budget, int wide_pass)
+                                 uint64_t budget, int wide_pass, const uint64_t* budgets)
 {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= b.nchunks)
@@ -54,7 +55,7 @@ __global__ void k_enc_state_init(EncBuffers b, const uint64_t* initLIS, const ui
   s.bornCount = 0;
   s.pos = 0;
   s.total_bits = 0;
-  s.budget = budget;
+  s.budget = budgets ? budgets[c] : budget;
   s.lisBits = 0;
   s.cur = 0;
   s.iPart = b.iLevels;
@@ -533,6 +534,99 @@ __global__ void k_enc_planes_setup(EncBuffers b)
   if (nbp == 0) {  // all coefficients are zero (SPECK_INT.cpp:130-133)
     s.done = 1;
     s.total_bits = 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// the plane table: bits of every plane's list phase, counted from the pyramid alone
+// ------------------------------------------------------------------------------------------
+// every bit of the list phase follows from M, the birth planes and E.  A set S that is born on plane
+// b -- the plane its parent splits on, M(parent); the roots are born above the chunk's top plane, b = nbp -- and whose own
+// largest coefficient lies lower, M(S) < b, sits in the list from then on: it is tested once on every plane
+// b > p >= max(M(S), 0) (k_list_count: one bit per entry), and on plane M(S) it heads a chain of splits that takes E(S)
+// bits (k_list_count adds E of the entries that split; every nested split is inside the head's E: k_pyramid).  A set
+// with M(S) == b is coded inside its parent's split, a set whose parent never splits is never listed.
+//   acc[c][0 .. 63]     sets whose tests start at plane q (counted at q = max(M, 0))
+//   acc[c][64 .. 127]   sets born at plane q + 1 (their tests end at q)
+//   acc[c][128 .. 191]  E of the chain heads that split at plane q
+// so that the list phase of plane p takes  #(start <= p) - #(born <= p) + E[p]  bits (k_plane_table).  One thread per
+// node, `per` node blocks a workgroup as k_pyramid and k_chain take them; a histogram per wavefront (wave_hist_add),
+// then one atomic per plane and workgroup.  acc is zero on entry.
+constexpr int kLisAccWords = 3 * kMaxPlanes;
+__global__ void __launch_bounds__(kNodeBlock)
+k_lis_bits(EncBuffers b, const uint32_t* depthBlocks, uint32_t nblk, uint32_t per, unsigned long long* acc)
+{
+  const uint32_t c = blockIdx.y;
+  const EncState& s = b.st[c];
+  if (!s.active || s.nbp <= 0)
+    return;
+  __shared__ uint32_t h[kLisAccWords];
+  if (threadIdx.x < kLisAccWords)
+    h[threadIdx.x] = 0;
+  static_assert(kLisAccWords <= kNodeBlock, "one word per thread");
+  __syncthreads();
+  const Tree& t = b.tree;
+  const int8_t* M = b.M + c * b.nodeStride;
+  const uint32_t* E = b.E + c * b.nodeStride;
+  const int nbp = s.nbp;
+  for (uint32_t q = 0, bi = blockIdx.x * per; q < per && bi < nblk; q++, bi++) {   // (uniform)
+    const uint32_t id = depthBlocks[bi] * kNodeBlock + threadIdx.x;
+    Node nd;
+    int lo = -1, born = -1;   // tests on planes lo .. born - 1
+    uint32_t e = 0;
+    int m = -1;
+    if (node_from_flat(t, id, nd)) {
+      const Grid& g = t.grids[nd.grid];
+      bool isset = (g.kind & kGridOct) != 0;
+      if (!isset) {
+        const NodeGeom qg = node_geom(t, nd);
+        isset = qg.count > 1 || (g.depth == 0 && qg.count == 1);
+      }
+      if (isset) {
+        m = (int)M[id];
+        const int bp = g.depth == 0 ? nbp : (int)M[flat_id(t, node_parent(t, nd))];
+        if (bp > m && bp > 0) {   // (listed: born, and not coded inside its parent's split)
+          born = bp;
+          lo = max(m, 0);
+          if (m >= 0)
+            e = E[id];
+        }
+      }
+    }
+    wave_hist_add(h, lo);                            // (lo <= 63)
+    wave_hist_add(h + kMaxPlanes, born - 1);         // (born in 1 .. 64; -2 of an unlisted node takes no part either)
+    if (e)
+      atomicAdd(&h[2 * kMaxPlanes + m], e);   // (the heads of one workgroup are disjoint sets: their E sum to less than the
+                                              //  chunk's bits of the plane, under 2^32 for every chunk the header can state)
+  }
+  __syncthreads();
+  if (threadIdx.x < kLisAccWords && h[threadIdx.x])
+    atomicAdd(&acc[(size_t)c * kLisAccWords + threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+// end[c][p]: the stream position at the end of plane p -- after its LIP scan, its list phase and its refinement pass -- with
+// an unlimited budget: what plane_end would leave in s.pos.  One thread per chunk: the running sums over acc, then over the
+// planes from the top one down.  A chunk that takes no part (constant) or has no plane gets zeros; nbp[c] its plane count.
+__global__ void k_plane_table(EncBuffers b, const unsigned long long* acc, uint64_t* end, int32_t* nbpOut)
+{
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= b.nchunks)
+    return;
+  const EncState& s = b.st[c];
+  uint64_t* out = end + (size_t)c * kMaxPlanes;
+  const int nbp = s.active ? s.nbp : 0;
+  nbpOut[c] = nbp;
+  const unsigned long long* a = acc + (size_t)c * kLisAccWords;
+  uint64_t started = 0, born = 0;
+  for (int p = 0; p < kMaxPlanes; p++) {   // list-phase bits of plane p, parked in out[p]
+    started += a[p];
+    born += p > 0 ? a[kMaxPlanes + p - 1] : 0ull;
+    out[p] = p < nbp ? started - born + a[2 * kMaxPlanes + p] : 0ull;
+  }
+  uint64_t pos = 0;
+  for (int p = nbp - 1; p >= 0; p--) {
+    pos += s.lipTot[p] + out[p] + s.refTot[p];
+    out[p] = pos;
   }
 }
 
@@ -1855,7 +1949,8 @@ k_emit_pixels(EncBuffers b)
 
 
 // stream length and the fixed-rate retry test (SPECK_INT.cpp:264-282, SPECK_FLT.cpp:530-538)
-__global__ void k_enc_finalize(EncBuffers b, uint64_t raw_budget, int rate_mode, int wide_pass)
+// (budgets: see k_enc_state_init -- the retry test is on the chunk's own budget, which a payload never falls short of)
+__global__ void k_enc_finalize(EncBuffers b, uint64_t raw_budget, int rate_mode, int wide_pass, const uint64_t* budgets)
 {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= b.nchunks)
@@ -1875,7 +1970,7 @@ __global__ void k_enc_finalize(EncBuffers b, uint64_t raw_budget, int rate_mode,
   cs.nbp = s.nbp;
   cs.total_bits = s.total_bits;
   if (rate_mode)   // (src/SPECK_FLT.cpp:530-538; other modes choose the width before coding)
-    cs.need_retry = (!wide_pass && (9 + payload) * 8 < raw_budget) ? 1u : 0u;
+    cs.need_retry = (!wide_pass && (9 + payload) * 8 < (budgets ? budgets[c] : raw_budget)) ? 1u : 0u;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1952,7 +2047,7 @@ int launch_speck_encode_fused_head(hipStream_t stream, const EncBuffers& b, cons
     return -1;
   }
   LAUNCH_K(k_enc_state_init, dim3((nc + 63) / 64), dim3(64), 0, stream, b, plan.d_initLIS, plan.d_initLen,
-           coder_budget(raw_budget), 0);
+           coder_budget(raw_budget), 0, plan.d_budgets);
   LAUNCH_K(k_head_fused, dim3(b.nPixTiles / 2, nc), dim3(kThreads), 0, stream, b, vals, valsStride,
            const_cast<uint32_t*>(static_cast<const uint32_t*>(b.coef)), const_cast<uint64_t*>(b.sign),
            const_cast<int8_t*>(b.msb), roots, lgRow, 32);
@@ -1970,7 +2065,7 @@ int launch_speck_encode_head(hipStream_t stream, const EncBuffers& b, const EncP
   const bool fused = plan.fusedHead && !wide_pass;
   if (!fused)
     LAUNCH_K(k_enc_state_init, perChunk, dim3(64), 0, stream, b, plan.d_initLIS,
-                       plan.d_initLen, budget, wide_pass ? 1 : 0);
+                       plan.d_initLen, budget, wide_pass ? 1 : 0, plan.d_budgets);
   const int maxPlanes = wide_pass ? kMaxPlanes : 32;
   const bool sideCensus = !fused && plan.side && plan.evFork && plan.evJoin && b.tree.maxDepth >= 2;
   for (int d = (int)b.tree.maxDepth - 1; d >= 0; d--) {
@@ -2025,6 +2120,35 @@ int launch_speck_encode_head(hipStream_t stream, const EncBuffers& b, const EncP
   return 0;
 }
 
+size_t speck_plane_table_acc_words()
+{
+  return (size_t)kLisAccWords;
+}
+
+int launch_speck_plane_table(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan, uint64_t* d_acc,
+                             uint64_t* d_end, int32_t* d_nbp)
+{
+  if (b.tree.flags & kTree2D) {
+    fprintf(stderr, "[sperr_hip] the plane table does not take the 2D coder's forest\n");
+    return -1;
+  }
+  const uint32_t nc = b.nchunks;
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the accumulators are 64-bit words");
+  HIP_CHECK(hipMemsetAsync(d_acc, 0, (size_t)nc * kLisAccWords * sizeof(uint64_t), stream));
+  for (int d = 0; d < (int)b.tree.maxDepth; d++) {
+    const uint32_t nb = plan.depthBlockOff[d + 1] - plan.depthBlockOff[d];
+    if (nb) {
+      const uint32_t per = node_blocks_per_group(nb, nc);
+      LAUNCH_K(k_lis_bits, dim3((nb + per - 1) / per, nc), dim3(kNodeBlock), 0, stream, b,
+               plan.d_depthBlocks + plan.depthBlockOff[d], nb, per, reinterpret_cast<unsigned long long*>(d_acc));
+    }
+  }
+  LAUNCH_K(k_plane_table, dim3((nc + 63) / 64), dim3(64), 0, stream, b, reinterpret_cast<const unsigned long long*>(d_acc),
+           d_end, d_nbp);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int launch_speck_encode_planes(hipStream_t stream, const EncBuffers& b, const EncPlanHost& plan,
                                uint64_t raw_budget, bool rate_mode, bool wide_pass)
 {
@@ -2073,7 +2197,7 @@ int launch_speck_encode_planes(hipStream_t stream, const EncBuffers& b, const En
     LAUNCH_K(k_emit_pixels<uint32_t>, dim3(b.nPixTiles, nc), dim3(kThreads), 0, stream,
                        b);
   LAUNCH_K(k_enc_finalize, perChunk, dim3(64), 0, stream, b, raw_budget,
-                     rate_mode ? 1 : 0, wide_pass ? 1 : 0);
+                     rate_mode ? 1 : 0, wide_pass ? 1 : 0, plan.d_budgets);
   HIP_CHECK(hipGetLastError());
   return 0;
 }
