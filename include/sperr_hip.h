@@ -407,6 +407,38 @@ int sperrhip_quality_view_dev(const void* d_orig, const sperrhip_view* view_orig
                               const sperrhip_view* view_recon, int is_float, size_t dimx, size_t dimy, size_t dimz,
                               double* out, void* hip_stream);
 
+/* ---- compression to a PSNR of the whole volume -----------------------------------------------------
+ * Mode 2 is the reference's rule chunk by chunk: every chunk is coded to `psnr` dB of the range of its OWN samples, so a
+ * chunk of still air beside the plume is coded to 80 dB of its own tiny range.  These calls take the range once, of
+ * the whole volume or from the caller, and give every chunk the same target error
+ *   t = (range * range) * pow(10, -psnr / 10),
+ * from which each chunk's quantisation step is the reference's own search started at q_0 = 2 sqrt(3 t): the first of
+ * q_k = q_0 / 2^(k/4), k = 0 .. 4, whose estimated error is at most t (five rungs are all a mid-tread quantiser can
+ * need).  The result is an ordinary container -- its header records no mode --, and every chunk stream in it is the
+ * reference's for that chunk at that q.  As in mode 2 the target is the reference's estimate, not a guarantee.
+ *
+ * sperrhip_psnr_ladder: t and the five q of a range (positive, finite) and a target (finite), host libm in the
+ * reference's order of operations; -1 when they give no positive finite step.  Host only.
+ *
+ * sperrhip_range_dev: the smallest and the largest sample of a volume, dense (view NULL) or a view; one streaming read
+ * and one wait of the host.  -1 (vmin, vmax untouched) for a NULL pointer, an empty or invalid view, and when a sample
+ * is a NaN; an infinity is an extreme like any other.
+ *
+ * sperrhip_compress_psnr_dev: the container.  range 0 means the volume's own, double(max) - double(min); a positive one
+ * is taken as it is (a time series' common range, a range known from the simulation).  dst_cap as
+ * sperrhip_max_compressed_size(..., 2, psnr) says.  Returns -1 before anything is launched for a NULL pointer, an
+ * invalid view, a zero dimension, a psnr that is not finite, a range that is negative or not finite; -1 with *dst_len
+ * and d_dst untouched for a volume whose own range is not finite (a NaN or an infinity among the samples, also when a
+ * range is given) and when a chunk's largest coefficient is 2^63 steps or more.  A constant volume gives the container
+ * of constant chunks.  One volume; no batches, fields, masked or relative volumes, no 2D slices. */
+int sperrhip_psnr_ladder(double range, double psnr, double* t, double* q /* [5] */);
+int sperrhip_range_dev(const void* d_src, const sperrhip_view* view /* NULL: dense */, int is_float, size_t dimx,
+                       size_t dimy, size_t dimz, double* vmin, double* vmax, void* hip_stream);
+int sperrhip_compress_psnr_dev(const void* d_src, const sperrhip_view* view /* NULL: dense */, int is_float, size_t dimx,
+                               size_t dimy, size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, double psnr,
+                               double range /* 0: the volume's own */, void* d_dst, size_t dst_cap, size_t* dst_len,
+                               void* hip_stream);
+
 /* ---- interleaved fields of a device array ---------------------------------------------------------
  * An array that keeps several variables per sample, the variables innermost -- a solver's (z, y, x, nvar), a detector's
  * (y, x, channel), a channels-last tensor -- compressed to and decoded from one container per field without a packed

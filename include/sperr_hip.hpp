@@ -878,6 +878,28 @@ inline auto compress_size_dev(const T* d_src, dims_type dims, dims_type chunks, 
                                                      hip_stream));
 }
 
+// ---- compression to a PSNR of the whole volume (sperr_hip.h) ----
+// The smallest and the largest sample of a device volume, dense (view null) or a view.  Error when a sample is a NaN
+template <typename T>
+inline auto range_dev(const T* d_src, dims_type dims, double& vmin, double& vmax, const view_type* view = nullptr,
+                      void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_range_dev(d_src, view, sizeof(T) == 4, dims[0], dims[1], dims[2], &vmin, &vmax, hip_stream));
+}
+
+// A container whose chunks are all coded to `psnr` dB of one range: the volume's own (range 0) or the caller's.  cap as
+// sperrhip_max_compressed_size(..., 2, psnr) says.  Error, with nothing written, for a volume with a NaN or an infinity
+template <typename T>
+inline auto compress_psnr_dev(const T* d_src, dims_type dims, dims_type chunks, double psnr, void* d_out, size_t cap,
+                              size_t& out_len, double range = 0.0, const view_type* view = nullptr,
+                              void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_compress_psnr_dev(d_src, view, sizeof(T) == 4, dims[0], dims[1], dims[2], chunks[0], chunks[1],
+                                                     chunks[2], psnr, range, d_out, cap, &out_len, hip_stream));
+}
+
 }  // namespace sperr
 
 #endif

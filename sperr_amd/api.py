@@ -55,6 +55,7 @@ EXPORTS = [
     "sperrhip_rel_tolerance_kind", "sperrhip_rel_forward_kind_dev", "sperrhip_compress_rel_kind_dev",
     "sperrhip_rel_parse_stream_kind_dev",
     "sperrhip_speck3d_plane_bits_dev", "sperrhip_chunk_count", "sperrhip_size_survey_dev", "sperrhip_compress_size_dev",
+    "sperrhip_psnr_ladder", "sperrhip_range_dev", "sperrhip_compress_psnr_dev",
 ]
 
 
@@ -312,6 +313,13 @@ def load_library():
     lib.sperrhip_compress_size_dev.restype = C.c_int
     lib.sperrhip_compress_size_dev.argtypes = [_vp, C.c_int, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _sz,
                                                C.POINTER(_sz), _vp, _sz, _vp]
+    lib.sperrhip_psnr_ladder.restype = C.c_int
+    lib.sperrhip_psnr_ladder.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double), _vp]
+    lib.sperrhip_range_dev.restype = C.c_int
+    lib.sperrhip_range_dev.argtypes = [_vp, _vp, C.c_int, _sz, _sz, _sz, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]
+    lib.sperrhip_compress_psnr_dev.restype = C.c_int
+    lib.sperrhip_compress_psnr_dev.argtypes = [_vp, _vp, C.c_int, _sz, _sz, _sz, _sz, _sz, _sz, C.c_double, C.c_double,
+                                               _vp, _sz, C.POINTER(_sz), _vp]
     lib.sperrhip_speck3d_encode_dev.restype = C.c_int
     lib.sperrhip_speck3d_encode_dev.argtypes = [_vp, C.c_int, _vp, _sz, _sz, _sz, _sz, _vp, _sz,
                                                 C.POINTER(_sz), _vp]
@@ -433,6 +441,57 @@ class SperrHip:
                                              out.numel(), C.byref(n), self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_compress_dev returned {rtn}")
+        return out[:n.value]
+
+    # ---- compression to a PSNR of the whole volume (psnr_vol.h) -----------------------------
+    def _psnr_args(self, vol, what):
+        torch = self.torch
+        if not (vol.is_cuda and vol.dim() == 3 and vol.dtype in (torch.float32, torch.float64)):
+            raise SperrHipError(f"{what} takes a 3-D cuda tensor of float32 or float64")
+        return None if vol.is_contiguous() else C.byref(self.view_of(vol))
+
+    def psnr_ladder(self, range, psnr):
+        """(t, q): the target mean squared error of a range and a PSNR in dB, and the five quantisation steps a chunk
+        can end on (a numpy float64 array) -- sperrhip_psnr_ladder, host only"""
+        t, q = C.c_double(0.0), np.zeros(5, dtype=np.float64)
+        if self.lib.sperrhip_psnr_ladder(float(range), float(psnr), C.byref(t), q.ctypes.data) != 0:
+            raise SperrHipError(f"a range of {range} at {psnr} dB gives no quantisation step")
+        return t.value, q
+
+    def value_range(self, vol):
+        """(min, max) of a cuda tensor (z, y, x) of float32 or float64, contiguous or a strided view (view_of), as
+        Python floats: one streaming read on the device.  Raises SperrHipError when a sample is a NaN."""
+        view = self._psnr_args(vol, "value_range")
+        dz, dy, dx = vol.shape
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        rtn = self.lib.sperrhip_range_dev(vol.data_ptr(), view, int(vol.dtype == self.torch.float32), dx, dy, dz,
+                                          C.byref(lo), C.byref(hi), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_range_dev returned {rtn}")
+        return lo.value, hi.value
+
+    def compress_to_psnr(self, vol, chunks_xyz, psnr, range=None, out=None):
+        """A container coded to `psnr` dB of the WHOLE volume's range (mode 2 codes every chunk to `psnr` dB of its
+        own): every chunk takes the same target error t = range^2 10^(-psnr/10) and the reference's own search for
+        its quantisation step.  range None: the volume's own, max - min; a positive number is taken as it is (a time
+        series' common range).  vol as compress() takes it, contiguous or a view.  An ordinary container: decompress,
+        decompress_box and the rest open it.  Raises SperrHipError for a volume with a NaN or an infinity and for a
+        target so fine that a coefficient would be 2^63 steps or more."""
+        torch = self.torch
+        view = self._psnr_args(vol, "compress_to_psnr")
+        dz, dy, dx = vol.shape
+        rng = 0.0 if range is None else float(range)
+        if range is not None and not rng > 0.0:
+            raise SperrHipError("a range is a positive number (None: the volume's own)")
+        cap = self.max_compressed_size(vol.shape, chunks_xyz, float(psnr), 2)
+        if out is None or out.numel() < cap:
+            out = torch.empty(cap, dtype=torch.uint8, device=vol.device)
+        n = _sz(0)
+        rtn = self.lib.sperrhip_compress_psnr_dev(vol.data_ptr(), view, int(vol.dtype == torch.float32), dx, dy, dz,
+                                                  *chunks_xyz, float(psnr), rng, out.data_ptr(), out.numel(),
+                                                  C.byref(n), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_psnr_dev returned {rtn}")
         return out[:n.value]
 
     # ---- compression to a byte target (the size mode) ---------------------------------------

@@ -375,6 +375,56 @@ int sperrhip_compress_size_dev(const void* d_src, int is_float, size_t dimx, siz
   });
 }
 
+// ---- PSNR of the whole volume (psnr_vol.h) ----
+int sperrhip_psnr_ladder(double range, double psnr, double* t, double* q)
+{
+  PsnrLadder L;
+  if (!t || !q || !std::isfinite(psnr) || !(range > 0.0) || !std::isfinite(range) || !psnr_vol_ladder(range, psnr, &L))
+    return -1;
+  *t = L.t;
+  for (int k = 0; k < kPsnrRungs; k++)
+    q[k] = L.q[k];
+  return 0;
+}
+
+int sperrhip_range_dev(const void* d_src, const sperrhip_view* view, int is_float, size_t dimx, size_t dimy, size_t dimz,
+                       double* vmin, double* vmax, void* hip_stream)
+{
+  return guarded("sperrhip_range_dev", [&]() -> int {
+    if (!d_src || !vmin || !vmax || dimx == 0 || dimy == 0 || dimz == 0)
+      return -1;
+    const ViewPitch pitch = view ? ViewPitch{view->pitch_y, view->pitch_z} : view_dense(dimx, dimy);
+    if (!view_valid(dimx, dimy, dimz, pitch))
+      return -1;
+    Lease L(static_cast<hipStream_t>(hip_stream));
+    if (!L.e)
+      return -1;
+    return range_to(*L.e, d_src, is_float, Dims{dimx, dimy, dimz}, view ? &pitch : nullptr, vmin, vmax,
+                    static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int sperrhip_compress_psnr_dev(const void* d_src, const sperrhip_view* view, int is_float, size_t dimx, size_t dimy,
+                               size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, double psnr, double range,
+                               void* d_dst, size_t dst_cap, size_t* dst_len, void* hip_stream)
+{
+  return guarded("sperrhip_compress_psnr_dev", [&]() -> int {
+    if (!d_src || !d_dst || !dst_len || dimx == 0 || dimy == 0 || dimz == 0)
+      return -1;
+    if (!std::isfinite(psnr) || !(range >= 0.0) || !std::isfinite(range))
+      return -1;
+    const ViewPitch pitch = view ? ViewPitch{view->pitch_y, view->pitch_z} : view_dense(dimx, dimy);
+    if (!view_valid(dimx, dimy, dimz, pitch))
+      return -1;
+    Lease L(static_cast<hipStream_t>(hip_stream));
+    if (!L.e)
+      return -1;
+    const Dims vol{dimx, dimy, dimz}, ch{chunk_x, chunk_y, chunk_z};
+    return compress_psnr_to(*L.e, d_src, is_float, vol, ch, psnr, range, static_cast<uint8_t*>(d_dst), dst_cap, dst_len,
+                            static_cast<hipStream_t>(hip_stream), view ? &pitch : nullptr);
+  });
+}
+
 int sperrhip_compress_view_dev(const void* d_src, const sperrhip_view* view, int is_float, size_t dimx, size_t dimy,
                                size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, int mode, double quality,
                                void* d_dst, size_t dst_cap, size_t* dst_len, void* hip_stream)

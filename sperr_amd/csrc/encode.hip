@@ -1089,6 +1089,7 @@ struct EncodeCall {
     std::vector<uint32_t> hid;
     std::vector<uint64_t> hbud;   // (size mode: the batch's budgets, the source of a queued copy)
     uint64_t* d_bud = nullptr;    //   ... and where they land: EncPlanHost::d_budgets of every head of the batch
+    double* d_ladder = nullptr;   // (PSNR of the whole volume: the ladder's partials, [chunk][rung][stride])
     bool orgAligned = true;
     EncPlanHost ph;
   };
@@ -1139,6 +1140,14 @@ struct EncodeCall {
   int sizePass = 0;
   SizeSurveyDev sv{};
   const uint64_t* hBudgets = nullptr;
+  // PSNR of the whole volume (compress_psnr_impl; psnr_vol.h): mode 2's flow, but every chunk's q comes from the ladder
+  // of ONE target, made once per call -- k_mse_ladder and k_mse_ladder_pick decide q, width and refusal on the device,
+  // quantise() waits for nothing, and the refusal rides the read-back behind code().  No per-chunk range is taken
+  const PsnrLadder* volLadder = nullptr;
+  bool chunk_range() const { return mode == 2 && !volLadder; }
+  // the ladder's partials of one chunk, [rung][stride], beside the coder's arrays
+  static size_t ladder_stride(const ShapePlan& P) { return round_up((size_t)psnr_vol_strides(P.N), 32); }
+  size_t ladder_bytes(const ShapePlan& P) const { return volLadder ? round_up(kPsnrRungs * ladder_stride(P) * sizeof(double), 256) : 0; }
   // a shape group's raw budget in bits (src/SPECK_FLT.cpp:491), which sizes its streams, masks and slots
   uint64_t raw_of(const ShapePlan& P, const std::vector<ChunkRef>& refs) const
   {
@@ -1284,7 +1293,7 @@ struct EncodeCall {
     //  outlier stage's reconstruction can be written into the chunk buffer while the coder runs, see below)
     const bool encAlias = mode != 3;
     // (the size mode's per-chunk words beside the coder's arrays: the plane table's accumulators and rows, or a budget)
-    const size_t per = enc_bytes_per_chunk(*P, raw_budget, encAlias) + (sizePass ? kSizeBytesPerChunk : 0);
+    const size_t per = enc_bytes_per_chunk(*P, raw_budget, encAlias) + (sizePass ? kSizeBytesPerChunk : 0) + ladder_bytes(*P);
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const size_t budgetBytes = arena_budget(E.arena.n, fr);
@@ -1292,7 +1301,7 @@ struct EncodeCall {
     B = std::min<uint32_t>(B, 256);
     if (sideBySide)
       B = (uint32_t)refs.size();
-    else if (E.arena.ensure(std::max((size_t)B * per, enc_bytes_for(*P, B, raw_budget, encAlias) + (sizePass ? B * kSizeBytesPerChunk : 0)) + 4096))
+    else if (E.arena.ensure(std::max((size_t)B * per, enc_bytes_for(*P, B, raw_budget, encAlias) + (sizePass ? B * kSizeBytesPerChunk : 0) + B * ladder_bytes(*P)) + 4096))
       return -1;
     for (size_t b0 = 0; b0 < refs.size(); b0 += B) {
       Batch& b = batches.emplace_back(Batch{P, {}, (uint32_t)std::min<size_t>(B, refs.size() - b0), 0, raw_budget, ss});
@@ -1336,6 +1345,11 @@ struct EncodeCall {
         return -1;
       HIP_CHECK(hipMemcpyAsync(b.d_bud, b.hbud.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, b.ss));
     }
+    if (volLadder) {
+      b.d_ladder = A.take<double>(kPsnrRungs * ladder_stride(*b.P) * nb);
+      if (!b.d_ladder)
+        return -1;
+    }
     bool pweWide = false;
     if (quantise(b, &pweWide))
       return -1;
@@ -1378,6 +1392,15 @@ struct EncodeCall {
     bool retry = false;
     for (auto& c : b.hc)
       retry |= (c.need_retry != 0);
+    if (volLadder)   // (the pick's refusals: the chunk was coded with a stand-in q, nothing of it has left the workspace)
+      for (uint32_t i = 0; i < nb; i++)
+        if (!b.hc[i].is_const && b.hc[i].mse_active != 0) {
+          fprintf(stderr, b.hc[i].mse_active == kPsnrRefusedNoRung
+                              ? "[sperr_hip] chunk %u: no rung of the ladder brings its error estimate under the target\n"
+                              : "[sperr_hip] chunk %u: its largest coefficient is 2^63 steps or more, or not a number\n",
+                  b.hid[i]);
+          return -1;
+        }
     if (retry) {
       if (pweEarly) {   // (cannot be: this mode knows the width before it codes, pwe_q_setup)
         fprintf(stderr, "[sperr_hip] a chunk asked for 64-bit coefficients after its outlier stage had run\n");
@@ -1404,11 +1427,13 @@ struct EncodeCall {
     HIP_CHECK(hipMemcpyAsync(bb.geom, b.hg.data(), nb * sizeof(ChunkGeom), hipMemcpyHostToDevice, b.ss));
     HIP_CHECK(hipMemcpyAsync(bb.gids, b.hid.data(), nb * 4, hipMemcpyHostToDevice, b.ss));
     HIP_CHECK(hipMemsetAsync(e.cst, 0, nb * sizeof(CoderState), b.ss));
-    if (float_stages<T>(b.ss, *b.P, bb, nb, b.P->dims, d_src, vd, b.orgAligned, mode == 2))
+    if (float_stages<T>(b.ss, *b.P, bb, nb, b.P->dims, d_src, vd, b.orgAligned, chunk_range()))
       return -1;
     if (launch_maxabs_q(b.ss, bb.vals, bb.valsStride, nb, b.P->N, e.cst, b.P->schedule.fusable))
       return -1;
-    if (mode == 2 && psnr_q_search(b.ss, *b.P, bb, nb, quality, hcKeep.emplace_back(), hcKeep.emplace_back()))
+    if (chunk_range() && psnr_q_search(b.ss, *b.P, bb, nb, quality, hcKeep.emplace_back(), hcKeep.emplace_back()))
+      return -1;
+    if (volLadder && launch_mse_ladder(b.ss, bb.vals, bb.valsStride, nb, b.P->N, b.d_ladder, ladder_stride(*b.P), e.cst, *volLadder))
       return -1;
     if (mode == 3 && pwe_q_setup(b.ss, bb, nb, quality, hcKeep.emplace_back(), pweWide))
       return -1;
@@ -1493,7 +1518,7 @@ struct EncodeCall {
     EncBuffers& e = bb.eb;
     // the DWT coefficients again when the coder's arrays were written over them, and memory of
     // their own for those arrays (the 64-bit magnitudes live in the chunk buffer)
-    if (bb.aliased && wide_retry_prepare<T>(b.ss, E, *b.P, bb, b.nb, b.P->dims, d_src, vd, b.orgAligned, mode == 2))
+    if (bb.aliased && wide_retry_prepare<T>(b.ss, E, *b.P, bb, b.nb, b.P->dims, d_src, vd, b.orgAligned, chunk_range()))
       return -1;
     if ((rate ? launch_make_q_wide(b.ss, b.nb, e.cst) : launch_mark_wide(b.ss, b.nb, e.cst)) ||
         reset_enc_pass(b.ss, bb, b.nb))
@@ -1821,6 +1846,37 @@ int compress_size_to(Engine& E, const void* d_src, int is_float, const Dims& vol
   return with_elem(is_float, [&](auto t) {
     return compress_size_impl(E, static_cast<const decltype(t)*>(d_src), vol, chunkPref, target_bytes, d_dst, dst_cap, dst_len,
                               budgets_out, st);
+  });
+}
+
+// ---- PSNR of the whole volume: the front ----
+int compress_psnr_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, double psnr,
+                     double range, uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st,
+                     const ViewPitch* srcView)
+{
+  // the volume's own range, also when the caller gives one: a NaN or an infinity among the samples is refused here,
+  // before anything is coded, and a constant volume is known
+  double vmin = 0.0, vmax = 0.0;
+  if (range_to(E, d_src, is_float, vol, srcView, &vmin, &vmax, st))
+    return -1;
+  const double own = vmax - vmin;
+  if (!std::isfinite(own)) {
+    fprintf(stderr, "[sperr_hip] the volume's range [%g, %g] is not finite\n", vmin, vmax);
+    return -1;
+  }
+  PsnrLadder L;
+  // (a constant volume has constant chunks only, which take no q: the table is not looked at)
+  if (!psnr_vol_ladder(range > 0.0 ? range : own, psnr, &L) && own != 0.0) {
+    fprintf(stderr, "[sperr_hip] a range of %g at %g dB gives no quantisation step\n", range > 0.0 ? range : own, psnr);
+    return -1;
+  }
+  return with_elem(is_float, [&](auto t) {
+    EncodeCall<decltype(t)> call{E, static_cast<const decltype(t)*>(d_src), vol, 2, psnr, d_dst, dst_cap, st, Coded::Container, 1, srcView};
+    call.volLadder = &L;
+    if (call.run(chunkPref))
+      return -1;
+    *dst_len = (size_t)call.total;
+    return 0;
   });
 }
 

@@ -692,6 +692,17 @@ int size_survey_to(Engine& E, const void* d_src, int is_float, const Dims& vol, 
 int compress_size_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, size_t target_bytes,
                      uint8_t* d_dst, size_t dst_cap, size_t* dst_len, uint64_t* budgets_out, hipStream_t st);
 
+// PSNR of the whole volume (psnr_vol.h).  The smallest and largest sample of a volume (with srcView:
+// of a valid strided view) -- psnr_vol.hip; -1 when a sample is a NaN.  One wait of the host
+int range_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const ViewPitch* srcView, double* vmin,
+             double* vmax, hipStream_t st);
+// ... and the container whose chunks all take their q from the ladder of one target: range 0 means the volume's own.
+// Everything behind the q is mode 2's flow.  -1, with *dst_len and d_dst untouched, for a volume whose own range is not
+// finite and when a chunk is refused by k_mse_ladder_pick
+int compress_psnr_to(Engine& E, const void* d_src, int is_float, const Dims& vol, const Dims& chunkPref, double psnr,
+                     double range, uint8_t* d_dst, size_t dst_cap, size_t* dst_len, hipStream_t st,
+                     const ViewPitch* srcView);
+
 // ---- stage access for the parity tests (abi_stages.hip): one stage of a chunk of the plan's shape on the caller's data
 // (the encoder's stages are encode.hip's, speck3d_decode_stage is decode.hip's)
 // the integer coder on coefficients of 4 or 8 bytes (wide) and their sign words: {u8 planes, u64 total_bits, payload}

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "psnr_vol.h"
 
 namespace sperrhip {
 
@@ -135,6 +136,12 @@ int launch_mark_wide(hipStream_t stream, uint32_t nchunks, CoderState* st);
 // (partial: n / 4096 + 1 doubles per chunk)
 int launch_mse(hipStream_t stream, const double* vals, size_t valsStride, uint32_t nchunks,
                uint32_t n, double* partial, size_t partialStride, CoderState* st);
+
+// PSNR of the whole volume (psnr_vol.h): every chunk's q, mse, need_retry and refusal mark (CoderState::mse_active) from
+// the common ladder L, on the device -- k_mse_ladder, then k_mse_ladder_pick.  partial: kPsnrRungs * rungStride doubles per
+// chunk, rungStride at least n / 4096 + 1
+int launch_mse_ladder(hipStream_t stream, const double* vals, size_t valsStride, uint32_t nchunks, uint32_t n,
+                      double* partial, size_t rungStride, CoderState* st, const PsnrLadder& L);
 
 // doubles as unsigned keys of the same order (the keys of a zeroed state are below every value)
 __host__ __device__ inline unsigned long long order_key(double v)

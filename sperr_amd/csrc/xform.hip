@@ -12,6 +12,7 @@
 #include "xform.h"
 #include "lift_dev.h"
 #include "dequant.h"
+#include "psnr_vol.h"
 
 namespace sperrhip {
 
@@ -322,6 +323,90 @@ __global__ void k_mse_final(uint32_t n, const double* partial, size_t partialStr
   st[c].mse = total / (double)n;
 }
 
+// PSNR of the whole volume (psnr_vol.h): every chunk walks the same ladder of five q, so one pass over the coefficients
+// takes all five estimates -- k_mse_strides' staging, five accumulators a lane, each rung's chain of 4096 dependent
+// fused multiply-adds independent of the others'.  partial[chunk][rung][stride]; every entry k_mse_ladder_pick reads
+// is written here, the short or empty last stride included.
+__global__ void __launch_bounds__(kThreads)
+k_mse_ladder(const double* vals, size_t valsStride, uint32_t n, double* partial, size_t rungStride,
+             const CoderState* st, PsnrLadder L)
+{
+  __shared__ double tile[kSumStrides][kSumSeg + 1];
+  const uint32_t c = blockIdx.y;
+  if (st[c].is_const)
+    return;
+  double q[kPsnrRungs], rcp_q[kPsnrRungs], acc[kPsnrRungs];
+#pragma unroll
+  for (int k = 0; k < kPsnrRungs; k++) {
+    q[k] = L.q[k];
+    rcp_q[k] = 1.0 / q[k];
+    acc[k] = 0.0;
+  }
+  const double* in = vals + c * valsStride;
+  const uint32_t npart = psnr_vol_strides(n);
+  const uint32_t s0 = blockIdx.x * kSumStrides;
+  for (uint32_t seg = 0; seg < kPsnrStride; seg += kSumSeg) {
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < (uint32_t)(kSumStrides * kSumSeg); k += kThreads) {
+      const uint32_t r = k / kSumSeg, j = k % kSumSeg;
+      const uint64_t e = (uint64_t)(s0 + r) * kPsnrStride + seg + j;
+      tile[r][j] = (s0 + r < npart && e < n) ? in[e] : 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)kSumStrides && s0 + threadIdx.x < npart) {
+      const uint64_t e0 = (uint64_t)(s0 + threadIdx.x) * kPsnrStride + seg;
+      const uint32_t len = e0 >= n ? 0u : (uint32_t)min((uint64_t)kSumSeg, n - e0);
+      for (uint32_t j = 0; j < len; j++) {
+        const double v = tile[threadIdx.x][j];
+#pragma unroll
+        for (int k = 0; k < kPsnrRungs; k++)
+          acc[k] = psnr_vol_term(acc[k], v, q[k], rcp_q[k]);
+      }
+    }
+  }
+  if (threadIdx.x < (uint32_t)kSumStrides && s0 + threadIdx.x < npart) {
+    double* out = partial + (size_t)c * kPsnrRungs * rungStride + s0 + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kPsnrRungs; k++)
+      out[k * rungStride] = acc[k];
+  }
+}
+
+// One lane per chunk: each rung's stride sums in order, the first rung at or under t, the width rule.  A chunk that is
+// refused keeps a q the coder can run on (the call is refused once the batch's states are read back)
+__global__ void k_mse_ladder_pick(uint32_t n, const double* partial, size_t rungStride, CoderState* st,
+                                  uint32_t nchunks, PsnrLadder L)
+{
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nchunks)
+    return;
+  CoderState& s = st[c];
+  s.mse_active = 0;
+  s.wide = 0;
+  s.need_retry = 0;
+  if (s.is_const)
+    return;
+  const uint32_t npart = psnr_vol_strides(n);
+  const double* pp = partial + (size_t)c * kPsnrRungs * rungStride;
+  int rung = -1;
+  double mse = 0.0;
+  for (int k = 0; k < kPsnrRungs && rung < 0; k++) {
+    mse = psnr_vol_total(pp + k * rungStride, npart, n);
+    if (mse <= L.t)
+      rung = k;
+  }
+  const int width = rung < 0 ? -1 : psnr_vol_width(s.maxabs, L.q[rung]);
+  s.mse = mse;
+  if (width < 0) {
+    const double q = s.maxabs / 4294967295.0;
+    s.q = q > 0.0 && q < INFINITY ? q : 1.0;
+    s.mse_active = rung < 0 ? kPsnrRefusedNoRung : kPsnrRefusedWidth;
+    return;
+  }
+  s.q = L.q[rung];
+  s.need_retry = (uint32_t)width;
+}
+
 // SPECK_FLT.cpp:282-301 (fixed-rate q) ; `wide` selects the high-precision retry
 __global__ void k_make_q_rate(CoderState* st, uint32_t nchunks, int wide_pass)
 {
@@ -551,6 +636,19 @@ int launch_mse(hipStream_t stream, const double* vals, size_t valsStride, uint32
            stream, vals, valsStride, n, partial, partialStride, st);
   LAUNCH_K(k_mse_final, dim3((nchunks + 63) / 64), dim3(64), 0, stream, n, partial, partialStride,
            st, nchunks);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_mse_ladder(hipStream_t stream, const double* vals, size_t valsStride, uint32_t nchunks, uint32_t n,
+                      double* partial, size_t rungStride, CoderState* st, const PsnrLadder& L)
+{
+  const uint32_t npart = psnr_vol_strides(n);
+  if (rungStride < npart)
+    return -1;
+  LAUNCH_K(k_mse_ladder, dim3((npart + kSumStrides - 1) / kSumStrides, nchunks), dim3(kThreads), 0, stream, vals,
+           valsStride, n, partial, rungStride, st, L);
+  LAUNCH_K(k_mse_ladder_pick, dim3((nchunks + 63) / 64), dim3(64), 0, stream, n, partial, rungStride, st, nchunks, L);
   HIP_CHECK(hipGetLastError());
   return 0;
 }
