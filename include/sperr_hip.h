@@ -761,6 +761,87 @@ int sperrhip_rel_parse_stream_kind_dev(const void* d_side, size_t side_len, int*
 int sperrhip_rel_check_dev(const void* d_orig, const void* d_recon, int is_float, size_t n, double eps, double* out,
                            void* hip_stream);
 
+/* ---- time series ------------------------------------------------------------------------------ */
+
+/* N time steps of one field, compressed together: an orthonormal Haar transform ACROSS the steps, point by point in
+ * space, and every band of it an ordinary container of a double volume.  Consecutive steps are nearly equal, so the
+ * detail bands are nearly zero.  A series of N steps is N containers back to back and a 64-byte info record; boxes,
+ * portions, chunking and every container reader keep working on the bands, and one step of an 8-step group decodes
+ * from 4 containers.  The rule (sperr_amd/csrc/series.h is its one statement, with the derivations):
+ *   plan       levels L in 0 .. 4.  Steps 0 .. N-1 are cut into consecutive groups of 2^L; a remainder r < 2^L is cut by
+ *              the binary digits of r, largest first (N = 11, L = 3: 8, 2, 1).  A group of 2^l steps gets l levels; a
+ *              group of one is the step itself as a double.  levels = 0 is the plain batch
+ *   bands      inside a group of g = 2^l: slot 0 the approximation a_l, slot 1 d_l, slots 2 .. 3 d_{l-1}, ..., slots
+ *              g/2 .. g-1 d_1.  Band b of the series is group start + slot
+ *   forward    fp64, no fused multiply-add, s = 0x1.6a09e667f3bcdp-1; fp32 samples are widened first:
+ *              a = (e + o) * s, d = (e - o) * s, e and o the even and odd entries of the level below
+ *   inverse    e = (a + d) * s, o = (a - d) * s; narrowed with one (float) for fp32 output
+ *   needs      slot (level k, index j) covers the steps [j 2^k, (j+1) 2^k) of its group.  A decode of the steps
+ *              [t0, t0 + nt) decodes exactly the bands whose cover meets it; no other container is read
+ *   tolerance  |x' - x| <= tol at every sample of every step (double output; the narrowing of an fp32 output can add
+ *              to it, as in mode 3): the bands of a group of 2^l are coded in mode 3 at tau_l = (tol - rho) / A_l,
+ *              A_0 = 1, A_{l+1} = s (A_l + 1) (1.414, 1.707, 1.914, 2.061), rho = K_L 2^-53 max(M, tol) the rounding of
+ *              the two butterflies, K = 0, 13, 28, 46, 67 for L = 0 .. 4, M the largest |sample| of the series.  Refused
+ *              when rho >= tol / 2
+ *   psnr       the transform is orthonormal, so the series' squared error is the sum of the bands': every band is
+ *              coded by the rule of sperrhip_compress_psnr_dev with `range` the series' (or the caller's), hence the same
+ *              target error.  As there, the target is the reference's estimate, not a guarantee
+ *   info       64 bytes in HOST memory, little-endian: 0-3 "SPTS" | 4 version 1 | 5 levels | 6 is_float of the steps |
+ *              7 kind | 8-11 N | 12-23 dimx, dimy, dimz (32 bits each) | 24-31 tol or psnr | 32-39 the range |
+ *              40-47 M | 48-55 rho (0 in psnr mode) | 56-63 0
+ * The transform pays when steps are close and costs when a step moves the field by a sample of its shortest waves
+ * (README, DESIGN.md section 0l have the figures).  Every call returns -1 before anything is launched for a NULL
+ * pointer, N = 0 or N > 2^32 - 1, levels > 4, a zero dimension, a range of steps outside the series, and the decode
+ * for containers whose dims differ from the record's.
+ * Out of scope, refused or not offered: a byte target over a series, fixed-rate mode, views, fields, masked and
+ * relative volumes, 2D slices, levels of the spatial hierarchy, the host calls, the farm and the command line tools,
+ * any wavelet other than Haar. */
+#define SPERRHIP_SERIES_TOL 0
+#define SPERRHIP_SERIES_PSNR 1
+#define SPERRHIP_SERIES_INFO_BYTES 64
+/* Host only.  The groups: *ngroups their count; with starts / group_levels (either may be NULL; `cap` entries each) the
+ * first step and the level count of every group, 1 when cap is too small. */
+int sperrhip_series_plan(size_t nsteps, unsigned levels, size_t* ngroups, size_t* starts, unsigned* group_levels,
+                         size_t cap);
+/* Host only.  need[b] = 1 for the bands a decode of [t0, t0 + nt) needs, 0 otherwise (nsteps entries); *count (may be
+ * NULL) how many. */
+int sperrhip_series_needs(size_t nsteps, unsigned levels, size_t t0, size_t nt, unsigned char* need, size_t* count);
+/* Host only.  rho and tau[0 .. levels] of a tolerance and the largest |sample|; -1 where the compression refuses. */
+int sperrhip_series_tolerance(double tol, double maxabs, unsigned levels, double* rho, double* tau);
+/* Host only.  The fields of an info record; any output may be NULL.  -1: not a record. */
+int sperrhip_series_parse(const void* info, size_t* nsteps, unsigned* levels, size_t dims[3], int* is_float, int* kind,
+                          double* quality, double* range, double* maxabs, double* rho);
+/* Stage access: the two kernels alone.  d_steps, d_outs: HOST arrays of device pointers, one per step (of the range);
+ * every volume holds n samples and needs the alignment of its type only.  d_bands: nsteps dense volumes of n doubles,
+ * band b at element b * n.  The inverse reads only the bands the range needs -- the others count as zero -- and writes
+ * only the nt outputs.  No step and no output may overlap d_bands: such a call returns -1.  Both wait for the stream. */
+int sperrhip_series_forward_dev(const void* const* d_steps, int is_float, size_t nsteps, unsigned levels, size_t n,
+                                void* d_bands, void* hip_stream);
+int sperrhip_series_inverse_dev(const void* d_bands, size_t nsteps, unsigned levels, size_t n, size_t t0, size_t nt,
+                                int output_float, void* const* d_outs, void* hip_stream);
+/* nsteps containers back to back in d_dst, container b -- band b -- at [offsets[b], offsets[b + 1]) (offsets: host,
+ * nsteps + 1 entries), and the info record (64 bytes, host).  kind SPERRHIP_SERIES_TOL: quality is tol; container b is
+ * byte for byte sperrhip_compress_dev of band b as a double volume in mode 3 at its tau.  SPERRHIP_SERIES_PSNR: quality
+ * is the target in dB and range the common range (0: the series' own, max - min over all steps); container b is byte
+ * for byte sperrhip_compress_psnr_dev of band b with that range.  dst_cap as sperrhip_max_compressed_size_batch(nsteps,
+ * ..., 3 or 2, quality) says.  The bands are staged in a buffer the library keeps (sperrhip_release() frees it) of at
+ * most SPERR_HIP_SERIES_MAX_MB MiB (default 2048): a longer series runs in windows of whole groups, a single group
+ * larger than the cap is taken whole, and the containers do not depend on the cap.  -1 also for a NaN or an infinity
+ * in a step, a tol that is not positive and finite or within 2 rho of zero, a psnr that is not finite, a range that
+ * is negative or not finite; other return codes as sperrhip_compress_batch_dev. */
+int sperrhip_compress_series_dev(const void* const* d_steps, int is_float, size_t nsteps, size_t dimx, size_t dimy,
+                                 size_t dimz, size_t chunk_x, size_t chunk_y, size_t chunk_z, unsigned levels, int kind,
+                                 double quality, double range, void* d_dst, size_t dst_cap, size_t* offsets, void* info,
+                                 void* hip_stream);
+/* The steps [t0, t0 + nt) of the series that `info` and the containers at d_src + offsets[b] describe, whole or the
+ * box [box_lo, box_lo + box_dims) (both NULL: whole), from the first pct percent of every chunk stream (0 or >= 100:
+ * all), as floats or doubles into the nt device pointers of d_outs (a host array), each a dense volume or box.  Only
+ * the needed bands are decoded -- as doubles into the library's buffer, by the body of sperrhip_decompress_boxes_dev --,
+ * then the inverse kernel runs: after any refusal or decoder error the outputs are as they were. */
+int sperrhip_decompress_series_dev(const void* info, const void* d_src, const size_t* offsets, size_t t0, size_t nt,
+                                   const size_t box_lo[3], const size_t box_dims[3], unsigned pct, int output_float,
+                                   void* const* d_outs, void* hip_stream);
+
 /* ---- profiling ------------------------------------------------------------------------------ */
 
 /* When enabled, the engine brackets every pipeline stage with HIP events on the launch stream
@@ -794,7 +875,8 @@ void sperrhip_debug_lis_stamps(int on, unsigned long long* out64);
  * arena an engine of this process holds right now, 4 / 5 = bytes of pinned staging memory / of device
  * buffers the chunk farm's workers hold right now (all devices), 7 = compression batches whose 32-bit
  * pass took the fused encoder head (quantiser, leaf level of the pyramid and census in one kernel;
- * SPERR_HIP_ENC_FUSED_HEAD=0 switches it off).  Other values: 0. */
+ * SPERR_HIP_ENC_FUSED_HEAD=0 switches it off), 8 = windows of bands the series compression calls ran (one per call
+ * unless SPERR_HIP_SERIES_MAX_MB cuts it).  Other values: 0. */
 unsigned long long sperrhip_debug_counter(int which);
 
 /* Gives back what the library keeps between calls (it keeps workspaces, shape tables, pinned staging

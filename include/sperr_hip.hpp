@@ -900,6 +900,97 @@ inline auto compress_psnr_dev(const T* d_src, dims_type dims, dims_type chunks, 
                                                      chunks[2], psnr, range, d_out, cap, &out_len, hip_stream));
 }
 
+// ---- time series: a Haar transform across the steps (sperr_hip.h) ----
+enum class SeriesKind : int { tol = SPERRHIP_SERIES_TOL, psnr = SPERRHIP_SERIES_PSNR };
+using series_info_type = std::array<uint8_t, SPERRHIP_SERIES_INFO_BYTES>;
+
+// the groups of a series: {first step, levels} each.  Host only; empty for arguments the library refuses
+inline auto series_plan(size_t nsteps, unsigned levels) -> std::vector<std::pair<size_t, unsigned>>
+{
+  size_t ng = 0;
+  if (sperrhip_series_plan(nsteps, levels, &ng, nullptr, nullptr, 0) != 0)
+    return {};
+  std::vector<size_t> starts(ng);
+  std::vector<unsigned> lv(ng);
+  std::vector<std::pair<size_t, unsigned>> out;
+  if (sperrhip_series_plan(nsteps, levels, &ng, starts.data(), lv.data(), ng) == 0)
+    for (size_t i = 0; i < ng; i++)
+      out.emplace_back(starts[i], lv[i]);
+  return out;
+}
+
+// the bands (= containers) a decode of the steps [t0, t0 + nt) needs, in order.  Host only; empty when refused
+inline auto series_needs(size_t nsteps, unsigned levels, size_t t0, size_t nt) -> std::vector<size_t>
+{
+  std::vector<unsigned char> need(nsteps);
+  std::vector<size_t> out;
+  if (nsteps != 0 && sperrhip_series_needs(nsteps, levels, t0, nt, need.data(), nullptr) == 0)
+    for (size_t b = 0; b < nsteps; b++)
+      if (need[b])
+        out.push_back(b);
+  return out;
+}
+
+// rho and tau[0 .. levels] of a tolerance and the series' largest |sample|.  Host only
+inline auto series_tolerance(double tol, double maxabs, unsigned levels, double& rho, std::vector<double>& tau) -> RTNType
+{
+  tau.assign(5, 0.0);
+  const int rtn = sperrhip_series_tolerance(tol, maxabs, levels, &rho, tau.data());
+  tau.resize(rtn == 0 ? levels + 1 : 0);
+  return detail::mask_rtn(rtn);
+}
+
+// Stage access: the steps (device pointers, one per step, n samples each) into nsteps dense bands of n doubles at d_bands
+template <typename T>
+inline auto series_forward_dev(const std::vector<const T*>& d_steps, unsigned levels, size_t n, double* d_bands,
+                               void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_series_forward_dev(reinterpret_cast<const void* const*>(d_steps.data()), sizeof(T) == 4,
+                                                      d_steps.size(), levels, n, d_bands, hip_stream));
+}
+
+// ... and the steps [t0, t0 + d_outs.size()) of the bands back
+template <typename T>
+inline auto series_inverse_dev(const double* d_bands, size_t nsteps, unsigned levels, size_t n, size_t t0,
+                               const std::vector<T*>& d_outs, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_series_inverse_dev(d_bands, nsteps, levels, n, t0, d_outs.size(), sizeof(T) == 4,
+                                                      reinterpret_cast<void* const*>(d_outs.data()), hip_stream));
+}
+
+// A series of d_steps.size() steps into as many containers back to back at d_out: container b at [offsets[b],
+// offsets[b + 1]).  quality: the tolerance, or the PSNR in dB of `range` (0: the series' own).  cap as
+// sperrhip_max_compressed_size_batch(steps, ..., 3 or 2, quality) says
+template <typename T>
+inline auto compress_series_dev(const std::vector<const T*>& d_steps, dims_type dims, dims_type chunks, unsigned levels,
+                                SeriesKind kind, double quality, void* d_out, size_t cap, std::vector<size_t>& offsets,
+                                series_info_type& info, double range = 0.0, void* hip_stream = nullptr) -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  offsets.assign(d_steps.size() + 1, 0);
+  return detail::mask_rtn(sperrhip_compress_series_dev(reinterpret_cast<const void* const*>(d_steps.data()), sizeof(T) == 4,
+                                                       d_steps.size(), dims[0], dims[1], dims[2], chunks[0], chunks[1],
+                                                       chunks[2], levels, static_cast<int>(kind), quality, range, d_out, cap,
+                                                       offsets.data(), info.data(), hip_stream));
+}
+
+// The steps [t0, t0 + d_outs.size()) of a series, whole or a box of every step (both null: whole), from the first pct
+// percent of every chunk stream.  The outputs are untouched when the call fails
+template <typename T>
+inline auto decompress_series_dev(const series_info_type& info, const void* d_streams, const std::vector<size_t>& offsets,
+                                  size_t t0, const std::vector<T*>& d_outs, const dims_type* box_lo = nullptr,
+                                  const dims_type* box_dims = nullptr, unsigned pct = 0, void* hip_stream = nullptr)
+    -> RTNType
+{
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+  return detail::mask_rtn(sperrhip_decompress_series_dev(info.data(), d_streams, offsets.data(), t0, d_outs.size(),
+                                                         box_lo ? box_lo->data() : nullptr,
+                                                         box_dims ? box_dims->data() : nullptr, pct, sizeof(T) == 4,
+                                                         reinterpret_cast<void* const*>(d_outs.data()), hip_stream));
+}
+
 }  // namespace sperr
 
 #endif

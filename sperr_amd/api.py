@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SPERR_HIP_LIB: another build of the same library, e.g. one with diagnostic switches compiled in)
 LIB_PATH = os.environ.get("SPERR_HIP_LIB") or os.path.join(_HERE, "libsperr_hip.so")
 _sz, _vp = C.c_size_t, C.c_void_p
+builtins_range = range   # (compress_to_psnr and compress_series have a parameter of that name)
 
 # every symbol include/sperr_hip.h declares
 EXPORTS = [
@@ -56,6 +57,9 @@ EXPORTS = [
     "sperrhip_rel_parse_stream_kind_dev",
     "sperrhip_speck3d_plane_bits_dev", "sperrhip_chunk_count", "sperrhip_size_survey_dev", "sperrhip_compress_size_dev",
     "sperrhip_psnr_ladder", "sperrhip_range_dev", "sperrhip_compress_psnr_dev",
+    "sperrhip_series_plan", "sperrhip_series_needs", "sperrhip_series_tolerance", "sperrhip_series_parse",
+    "sperrhip_series_forward_dev", "sperrhip_series_inverse_dev", "sperrhip_compress_series_dev",
+    "sperrhip_decompress_series_dev",
 ]
 
 
@@ -320,6 +324,26 @@ def load_library():
     lib.sperrhip_compress_psnr_dev.restype = C.c_int
     lib.sperrhip_compress_psnr_dev.argtypes = [_vp, _vp, C.c_int, _sz, _sz, _sz, _sz, _sz, _sz, C.c_double, C.c_double,
                                                _vp, _sz, C.POINTER(_sz), _vp]
+    _dp = C.POINTER(C.c_double)
+    lib.sperrhip_series_plan.restype = C.c_int
+    lib.sperrhip_series_plan.argtypes = [_sz, C.c_uint, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint), _sz]
+    lib.sperrhip_series_needs.restype = C.c_int
+    lib.sperrhip_series_needs.argtypes = [_sz, C.c_uint, _sz, _sz, C.POINTER(C.c_ubyte), C.POINTER(_sz)]
+    lib.sperrhip_series_tolerance.restype = C.c_int
+    lib.sperrhip_series_tolerance.argtypes = [C.c_double, C.c_double, C.c_uint, _dp, _dp]
+    lib.sperrhip_series_parse.restype = C.c_int
+    lib.sperrhip_series_parse.argtypes = [C.c_char_p, C.POINTER(_sz), C.POINTER(C.c_uint), C.POINTER(_sz),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp, _dp, _dp]
+    lib.sperrhip_series_forward_dev.restype = C.c_int
+    lib.sperrhip_series_forward_dev.argtypes = [C.POINTER(_vp), C.c_int, _sz, C.c_uint, _sz, _vp, _vp]
+    lib.sperrhip_series_inverse_dev.restype = C.c_int
+    lib.sperrhip_series_inverse_dev.argtypes = [_vp, _sz, C.c_uint, _sz, _sz, _sz, C.c_int, C.POINTER(_vp), _vp]
+    lib.sperrhip_compress_series_dev.restype = C.c_int
+    lib.sperrhip_compress_series_dev.argtypes = [C.POINTER(_vp), C.c_int] + [_sz] * 7 + \
+        [C.c_uint, C.c_int, C.c_double, C.c_double, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_ubyte), _vp]
+    lib.sperrhip_decompress_series_dev.restype = C.c_int
+    lib.sperrhip_decompress_series_dev.argtypes = [C.c_char_p, _vp, C.POINTER(_sz), _sz, _sz, C.POINTER(_sz),
+                                                   C.POINTER(_sz), C.c_uint, C.c_int, C.POINTER(_vp), _vp]
     lib.sperrhip_speck3d_encode_dev.restype = C.c_int
     lib.sperrhip_speck3d_encode_dev.argtypes = [_vp, C.c_int, _vp, _sz, _sz, _sz, _sz, _vp, _sz,
                                                 C.POINTER(_sz), _vp]
@@ -817,6 +841,181 @@ class SperrHip:
                                                      out.numel() * out.element_size(), self._stream())
         if rtn != 0:
             raise SperrHipError(f"sperrhip_decompress_boxes_dev returned {rtn}")
+        return out
+
+    # ---- time series: a Haar transform across the steps ------------------------------------------
+    def series_plan(self, nsteps, levels=3):
+        """The groups of a series, host only: a list of (first step, levels of the group)."""
+        ng = _sz(0)
+        if self.lib.sperrhip_series_plan(int(nsteps), int(levels), C.byref(ng), None, None, 0) != 0:
+            raise SperrHipError("sperrhip_series_plan refuses these arguments")
+        starts, lv = (_sz * ng.value)(), (C.c_uint * ng.value)()
+        rtn = self.lib.sperrhip_series_plan(int(nsteps), int(levels), C.byref(ng), starts, lv, ng.value)
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_series_plan returned {rtn}")
+        return [(int(starts[i]), int(lv[i])) for i in range(ng.value)]
+
+    def series_needs(self, nsteps, levels, t0=0, nt=None):
+        """The bands (= containers) a decode of the steps [t0, t0 + nt) needs, host only: a sorted list."""
+        nt = int(nsteps) - int(t0) if nt is None else int(nt)
+        if nsteps <= 0 or t0 < 0 or nt < 0:
+            raise SperrHipError("sperrhip_series_needs refuses these arguments")
+        need = (C.c_ubyte * int(nsteps))()
+        if self.lib.sperrhip_series_needs(int(nsteps), int(levels), int(t0), nt, need, None) != 0:
+            raise SperrHipError("sperrhip_series_needs refuses these arguments")
+        return [b for b in range(int(nsteps)) if need[b]]
+
+    def series_tolerance(self, tol, maxabs, levels=3):
+        """(rho, [tau_0 .. tau_levels]) of a tolerance and the series' largest |sample|, host only."""
+        rho, tau = C.c_double(0.0), (C.c_double * 5)()
+        if self.lib.sperrhip_series_tolerance(float(tol), float(maxabs), int(levels), C.byref(rho), tau) != 0:
+            raise SperrHipError(f"sperrhip_series_tolerance refuses tol {tol} at a largest sample of {maxabs}")
+        return rho.value, [tau[l] for l in range(int(levels) + 1)]
+
+    def series_parse(self, info):
+        """The fields of an info record (64 bytes), host only."""
+        rec = bytes(info)
+        n, lv, dims, isf, kind = _sz(0), C.c_uint(0), (_sz * 3)(), C.c_int(0), C.c_int(0)
+        q, rng, M, rho = C.c_double(0), C.c_double(0), C.c_double(0), C.c_double(0)
+        if len(rec) != 64 or self.lib.sperrhip_series_parse(rec, C.byref(n), C.byref(lv), dims, C.byref(isf),
+                                                            C.byref(kind), C.byref(q), C.byref(rng), C.byref(M),
+                                                            C.byref(rho)) != 0:
+            raise SperrHipError("not a series info record")
+        return {"nsteps": n.value, "levels": lv.value, "shape_zyx": (dims[2], dims[1], dims[0]),
+                "is_float": bool(isf.value), "kind": "tol" if kind.value == 0 else "psnr", "quality": q.value,
+                "range": rng.value, "maxabs": M.value, "rho": rho.value}
+
+    def _series_steps(self, vols, what):
+        """the steps of a series as a list of dense cuda tensors of one shape and dtype"""
+        torch = self.torch
+        steps = list(vols) if isinstance(vols, (list, tuple)) else [vols[t] for t in range(vols.shape[0])]
+        if not steps:
+            raise SperrHipError(f"{what}: a series has at least one step")
+        for s in steps:
+            assert s.is_cuda and s.dtype in (torch.float32, torch.float64)
+            if s.dtype != steps[0].dtype or s.shape != steps[0].shape:
+                raise SperrHipError(f"{what}: the steps of a series share shape and dtype")
+            self._no_view(s, what)
+        return steps
+
+    def series_forward(self, vols, levels=3, out=None):
+        """Stage access, k_series_fwd alone: the N steps (a list of dense cuda tensors of one shape, anywhere in
+        memory, or a tensor whose steps are dense) into the N fp64 bands, a cuda tensor shaped (N,) + step shape."""
+        torch = self.torch
+        steps = self._series_steps(vols, "series_forward")
+        n = steps[0].numel()
+        if out is None:
+            out = torch.empty((len(steps),) + tuple(steps[0].shape), dtype=torch.float64, device=steps[0].device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == len(steps) * n
+        ptrs = (_vp * len(steps))(*[s.data_ptr() for s in steps])
+        rtn = self.lib.sperrhip_series_forward_dev(ptrs, int(steps[0].dtype == torch.float32), len(steps), int(levels),
+                                                   n, out.data_ptr(), self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_series_forward_dev returned {rtn}")
+        return out
+
+    def series_inverse(self, bands, levels=3, t0=0, nt=None, output_float=True, out=None):
+        """Stage access, k_series_inv alone: the steps [t0, t0 + nt) of the fp64 bands (N, ...), of which only the
+        needed ones are read.  out: a list of nt dense cuda tensors, or a tensor shaped (nt, ...); made when None."""
+        torch = self.torch
+        assert bands.is_cuda and bands.dtype == torch.float64 and bands.is_contiguous() and bands.dim() >= 2
+        nsteps = bands.shape[0]
+        nt = nsteps - t0 if nt is None else nt
+        n = bands[0].numel()
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            out = torch.empty((max(nt, 0),) + tuple(bands.shape[1:]), dtype=dt, device=bands.device)
+        outs = list(out) if isinstance(out, (list, tuple)) else [out[t] for t in range(out.shape[0])]
+        if len(outs) != nt or nt <= 0 or t0 < 0:
+            raise SperrHipError(f"series_inverse: {len(outs)} outputs for the steps [{t0}, {t0 + nt})")
+        for o in outs:
+            assert o.is_cuda and o.dtype == dt and o.numel() == n
+            self._no_view(o, "series_inverse")
+        ptrs = (_vp * nt)(*[o.data_ptr() for o in outs])
+        rtn = self.lib.sperrhip_series_inverse_dev(bands.data_ptr(), nsteps, int(levels), n, int(t0), int(nt),
+                                                   int(output_float), ptrs, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_series_inverse_dev returned {rtn}")
+        return out
+
+    def compress_series(self, vols, chunks_xyz, tol=None, psnr=None, levels=3, range=None, out=None):
+        """N time steps of one field -- a list of dense cuda tensors (z, y, x) of one shape and dtype, anywhere in
+        memory, or a (t, z, y, x) tensor whose steps are dense -- into N containers, one per band of a Haar transform
+        across the steps, and the 64-byte info record.  Exactly one of `tol` (every sample of every step within tol)
+        and `psnr` (dB of `range`, default the series' own) is given.  Returns (containers, info): N cuda uint8
+        views into one buffer, and bytes."""
+        torch = self.torch
+        steps = self._series_steps(vols, "compress_series")
+        if (tol is None) == (psnr is None):
+            raise SperrHipError("compress_series takes exactly one of tol and psnr")
+        if steps[0].dim() != 3:
+            raise SperrHipError("compress_series takes steps shaped (z, y, x)")
+        kind, quality = (0, float(tol)) if psnr is None else (1, float(psnr))
+        nsteps = len(steps)
+        dz, dy, dx = steps[0].shape
+        cap = self.max_compressed_size_batch(nsteps, steps[0].shape, chunks_xyz, quality, 3 if kind == 0 else 2)
+        if cap == 0:
+            raise SperrHipError("sperrhip_max_compressed_size_batch overflows")
+        if out is None or out.numel() < cap:
+            out = torch.empty(cap, dtype=torch.uint8, device=steps[0].device)
+        offs = (_sz * (nsteps + 1))()
+        info = (C.c_ubyte * 64)()
+        ptrs = (_vp * nsteps)(*[s.data_ptr() for s in steps])
+        rtn = self.lib.sperrhip_compress_series_dev(ptrs, int(steps[0].dtype == torch.float32), nsteps, dx, dy, dz,
+                                                    *chunks_xyz, int(levels), kind, quality,
+                                                    0.0 if range is None else float(range), out.data_ptr(),
+                                                    out.numel(), offs, info, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_compress_series_dev returned {rtn}")
+        return [out[offs[b]:offs[b + 1]] for b in builtins_range(nsteps)], bytes(info)
+
+    def decompress_series(self, containers, info, t0=0, nt=None, box_lo_xyz=None, box_dims_xyz=None, pct=0,
+                          output_float=True, out=None):
+        """The steps [t0, t0 + nt) of a series (nt None: to its end), whole or a box of every step, from the first pct
+        percent of every chunk stream.  containers: compress_series' list; only those the range needs (series_needs)
+        are decoded, and unless the list lies back to back in one buffer only those are concatenated first.  out: a list of nt dense cuda tensors or a
+        tensor shaped (nt, z, y, x) of the volume's or the box's shape; made when None.  It is untouched when the
+        call fails."""
+        torch = self.torch
+        rec = bytes(info)
+        if len(rec) != 64:
+            raise SperrHipError("not a series info record")
+        h = self.series_parse(rec)
+        nsteps = h["nsteps"]
+        if len(containers) != nsteps:
+            raise SperrHipError(f"{len(containers)} containers for a series of {nsteps} steps")
+        for c in containers:
+            assert c.is_cuda and c.dtype == torch.uint8 and c.dim() == 1 and c.is_contiguous()
+        nt = nsteps - t0 if nt is None else nt
+        packed = all(b.data_ptr() == a.data_ptr() + a.numel() and
+                     b.untyped_storage().data_ptr() == a.untyped_storage().data_ptr()
+                     for a, b in zip(containers, containers[1:]))
+        # (containers that do not lie back to back are concatenated, but only those the range needs: the others get
+        #  an empty byte range, which the call never looks at)
+        need = range(nsteps) if packed else self.series_needs(nsteps, h["levels"], t0, nt)
+        src = containers[0] if packed else torch.cat([containers[b] for b in need])
+        offs = (_sz * (nsteps + 1))()
+        for v, c in enumerate(containers):
+            offs[v + 1] = offs[v] + (c.numel() if v in need else 0)
+        if (box_lo_xyz is None) != (box_dims_xyz is None):
+            raise SperrHipError("decompress_series takes a box's origin and dims together")
+        lo, dims = (None, None) if box_lo_xyz is None else self._box_args(box_lo_xyz, box_dims_xyz)
+        shape = h["shape_zyx"] if box_dims_xyz is None else tuple(int(d) for d in reversed(box_dims_xyz))
+        dt = torch.float32 if output_float else torch.float64
+        if out is None:
+            out = torch.empty((max(nt, 0),) + tuple(shape), dtype=dt, device=src.device)
+        outs = list(out) if isinstance(out, (list, tuple)) else [out[t] for t in builtins_range(out.shape[0])]
+        if len(outs) != nt:
+            raise SperrHipError(f"decompress_series: {len(outs)} outputs for {nt} steps")
+        n = int(np.prod(shape))
+        for o in outs:
+            assert o.is_cuda and o.dtype == dt and o.numel() == n
+            self._no_view(o, "decompress_series")
+        ptrs = (_vp * max(nt, 1))(*[o.data_ptr() for o in outs])
+        rtn = self.lib.sperrhip_decompress_series_dev(rec, src.data_ptr(), offs, int(t0), int(nt), lo, dims, int(pct),
+                                                      int(output_float), ptrs, self._stream())
+        if rtn != 0:
+            raise SperrHipError(f"sperrhip_decompress_series_dev returned {rtn}")
         return out
 
     # ---- quality figures of a reconstruction ---------------------------------------------------

@@ -241,6 +241,8 @@ unsigned long long sperrhip_debug_counter(int which)
     return farm_footprint(which == 4);
   if (which == 7)   // batches whose 32-bit pass took the fused encoder head (k_head_fused)
     return g_dbg_counter[3].load();
+  if (which == 8)   // windows of bands the series compression calls ran (abi_series.hip)
+    return g_dbg_counter[4].load();
   return which >= 0 && which < 3 ? g_dbg_counter[which].load() : 0ull;
 }
 void sperrhip_debug_lis_stamps(int on, unsigned long long* out64)
@@ -1073,6 +1075,8 @@ int sperrhip_decomp_3d_multires(const void* src, size_t src_len, int output_floa
   });
 }
 
+}  // extern "C"
+
 // ---- a box per entry out of a batch of containers (boxes.h) -------------------------------------
 // The grid a boxes call cuts along: the volume and every container's chunk dims, or with a level -- which the
 // containers must then share chunk dims for, and have -- the level's dims and the chunks' corner cres[h] (level_select)
@@ -1098,6 +1102,125 @@ static int boxes_grid(const Dims& vol, const std::vector<Dims>& chunk, const siz
   return 0;
 }
 
+// sperrhip_decompress_boxes_dev behind its refusals of arguments and its lease (decode_request.h); abi_series.hip
+// decodes a series' bands with it.
+// The containers are read where they lie: every offset of the call is one from the lowest of their addresses.  Each
+// header is read once; the plan (boxes.h) names the slots, whose chunks become the call's stacked list -- one chunk per
+// slot, in the slots' order -- with the plan's geometry on the window.  Direct form: the crop writers fill d_dst.
+// Staged form: they fill the engine's staging array, typed as the output, and one launch of k_boxes_copy moves every
+// pair's window into its box
+int sperrhip::decode_boxes_to(Engine& E, const void* const* d_srcs, const size_t* src_lens, size_t ncont,
+                              const uint32_t* which, const size_t* box_lo, size_t nbox, const size_t box_dims[3],
+                              const size_t* level, unsigned pct, int output_float, void* d_dst, size_t dst_cap_bytes,
+                              hipStream_t st, const Dims* vol)
+{
+  uintptr_t base = UINTPTR_MAX;
+  for (size_t c = 0; c < ncont; c++)
+    base = std::min(base, reinterpret_cast<uintptr_t>(d_srcs[c]));
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(base);
+  const size_t esz = output_float ? sizeof(float) : sizeof(double);
+  std::vector<uint64_t> off(ncont), len(ncont);
+  for (size_t c = 0; c < ncont; c++) {
+    off[c] = reinterpret_cast<uintptr_t>(d_srcs[c]) - base;
+    len[c] = src_lens[c];
+  }
+  std::vector<ContainerInfo> ci;
+  std::vector<uint8_t> heads;
+  if (read_headers_at(E, src, off, len, ci, heads, st))
+    return -1;
+  std::vector<Dims> chunk(ncont), cell;
+  for (size_t c = 0; c < ncont; c++) {
+    if (ci[c].vol != ci[0].vol || (vol && ci[c].vol != *vol))   // (the batch decode's rule)
+      return -1;
+    chunk[c] = ci[c].chunk;
+    keep_portion(ci[c], pct);
+  }
+  Dims full;
+  Window w;
+  BoxesPlan P;
+  if (boxes_grid(ci[0].vol, chunk, level, full, cell, w.m) ||
+      !boxes_plan(ncont, full, cell.data(), which, box_lo, nbox, Dims{box_dims[0], box_dims[1], box_dims[2]}, P))
+    return -1;
+  if (P.outVals > dst_cap_bytes / esz || P.stageVals > SIZE_MAX / 8)
+    return -1;
+  // the call's chunks: slot k is chunk P.slots[k].id of its container
+  const size_t nslots = P.slots.size();
+  ContainerInfo all;
+  std::vector<std::array<size_t, 6>> list(nslots), per;
+  all.chunk = ci[0].chunk;
+  all.off.resize(nslots);
+  all.len.resize(nslots);
+  w.ids.resize(nslots);
+  w.slotGeom.resize(nslots);
+  for (size_t k = 0, have = SIZE_MAX; k < nslots; k++) {
+    const BoxesSlot& s = P.slots[k];
+    if (s.cont != have) {   // (the slots are in container order)
+      per = chunk_volume(ci[s.cont].vol, ci[s.cont].chunk);
+      have = s.cont;
+      if (per.size() != ci[s.cont].off.size())
+        return -1;
+    }
+    if (s.id >= per.size())
+      return -1;
+    list[k] = per[s.id];
+    all.off[k] = off[s.cont] + ci[s.cont].off[s.id];
+    all.len[k] = ci[s.cont].len[s.id];
+    w.ids[k] = (uint32_t)k;
+    CropGeom& g = w.slotGeom[k];
+    for (int a = 0; a < 3; a++) {
+      g.rel[a] = P.geom[k].rel[a];
+      g.lo[a] = P.geom[k].lo[a];
+      g.hi[a] = P.geom[k].hi[a];
+    }
+  }
+  w.crop = true;
+  w.level = level != nullptr;
+  w.h = level ? *level : 0;
+  w.lo = Dims{0, 0, 0};
+  w.dims = P.shared ? P.stageDims : P.outDims;
+  all.vol = w.dims;
+  all.nvals = P.shared ? P.stageVals : P.outVals;
+  void* d_out = d_dst;
+  size_t outBytes = dst_cap_bytes;
+  if (P.shared) {
+    outBytes = P.stageVals * esz;
+    if (E.boxesStage.ensure(outBytes))
+      return -1;
+    d_out = E.boxesStage.p;
+  }
+  DecodeRequest req;
+  req.stacked = &list;
+  req.window = &w;
+  const int rtn = decode_to(E, src, output_float, d_out, outBytes, all, st, req);
+  if (rtn || !P.shared)
+    return rtn;
+  std::vector<BoxesCopyPair> pairs;
+  std::vector<uint64_t> first;
+  BoxesCopyGeom g;
+  boxes_copy_args(P, pairs, first, g);
+  const size_t pairBytes = round_up(pairs.size() * sizeof(BoxesCopyPair), 256);
+  if (E.misc.ensure(pairBytes + first.size() * 8))
+    return -1;
+  BoxesCopyPair* d_pairs = static_cast<BoxesCopyPair*>(E.misc.p);
+  uint64_t* d_first = reinterpret_cast<uint64_t*>(static_cast<char*>(E.misc.p) + pairBytes);
+  const bool vec = boxes_vec_ok(reinterpret_cast<uintptr_t>(d_out), reinterpret_cast<uintptr_t>(d_dst), pairs, g, esz);
+  auto copy = [&]() -> int {
+    HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(BoxesCopyPair), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
+    if (boxes_copy_run(d_out, d_dst, esz, d_pairs, d_first, g, vec, st))
+      return -1;
+    HIP_CHECK(hipStreamSynchronize(st));   // (also: the uploads' host arrays may go only once the copies have read them)
+    return 0;
+  };
+  const int rc = copy();
+  if (rc)
+    drain_after_error(E, st);   // (as ~DecodeCall: queued copies read the vectors above)
+  E.prof.collect();
+  return rc;
+}
+
+extern "C" {
+
 int sperrhip_boxes_plan(size_t ncont, const size_t vol_dims[3], const size_t* chunk_dims, const uint32_t* which,
                         const size_t* box_lo, size_t nbox, const size_t box_dims[3], const size_t* level, size_t out[5])
 {
@@ -1122,11 +1245,7 @@ int sperrhip_boxes_plan(size_t ncont, const size_t vol_dims[3], const size_t* ch
   });
 }
 
-// The containers are read where they lie: every offset of the call is one from the lowest of their addresses.  Each
-// header is read once; the plan (boxes.h) names the slots, whose chunks become the call's stacked list -- one chunk per
-// slot, in the slots' order -- with the plan's geometry on the window.  Direct form: the crop writers fill d_dst.
-// Staged form: they fill the engine's staging array, typed as the output, and one launch of k_boxes_copy moves every
-// pair's window into its box
+// (the refusals of arguments and the lease; the rest is decode_boxes_to)
 int sperrhip_decompress_boxes_dev(const void* const* d_srcs, const size_t* src_lens, size_t ncont, const uint32_t* which,
                                   const size_t* box_lo, size_t nbox, const size_t box_dims[3], const size_t* level,
                                   unsigned pct, int output_float, void* d_dst, size_t dst_cap_bytes, void* hip_stream)
@@ -1135,12 +1254,9 @@ int sperrhip_decompress_boxes_dev(const void* const* d_srcs, const size_t* src_l
     if (!d_srcs || !src_lens || !box_lo || !box_dims || !d_dst || ncont == 0 || nbox == 0 || ncont > 0xffffffffull ||
         nbox > 0xffffffffull || (!which && nbox != ncont))
       return -1;
-    uintptr_t base = UINTPTR_MAX;
-    for (size_t c = 0; c < ncont; c++) {
+    for (size_t c = 0; c < ncont; c++)
       if (!d_srcs[c])
         return -1;
-      base = std::min(base, reinterpret_cast<uintptr_t>(d_srcs[c]));
-    }
     for (size_t e = 0; which && e < nbox; e++)
       if (which[e] >= ncont)
         return -1;
@@ -1150,108 +1266,8 @@ int sperrhip_decompress_boxes_dev(const void* const* d_srcs, const size_t* src_l
     Lease L(static_cast<hipStream_t>(hip_stream));
     if (!L.e)
       return -1;
-    Engine& E = *L.e;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(base);
-    const size_t esz = output_float ? sizeof(float) : sizeof(double);
-    std::vector<uint64_t> off(ncont), len(ncont);
-    for (size_t c = 0; c < ncont; c++) {
-      off[c] = reinterpret_cast<uintptr_t>(d_srcs[c]) - base;
-      len[c] = src_lens[c];
-    }
-    std::vector<ContainerInfo> ci;
-    std::vector<uint8_t> heads;
-    if (read_headers_at(E, src, off, len, ci, heads, st))
-      return -1;
-    std::vector<Dims> chunk(ncont), cell;
-    for (size_t c = 0; c < ncont; c++) {
-      if (ci[c].vol != ci[0].vol)   // (the batch decode's rule)
-        return -1;
-      chunk[c] = ci[c].chunk;
-      keep_portion(ci[c], pct);
-    }
-    Dims full;
-    Window w;
-    BoxesPlan P;
-    if (boxes_grid(ci[0].vol, chunk, level, full, cell, w.m) ||
-        !boxes_plan(ncont, full, cell.data(), which, box_lo, nbox, Dims{box_dims[0], box_dims[1], box_dims[2]}, P))
-      return -1;
-    if (P.outVals > dst_cap_bytes / esz || P.stageVals > SIZE_MAX / 8)
-      return -1;
-    // the call's chunks: slot k is chunk P.slots[k].id of its container
-    const size_t nslots = P.slots.size();
-    ContainerInfo all;
-    std::vector<std::array<size_t, 6>> list(nslots), per;
-    all.chunk = ci[0].chunk;
-    all.off.resize(nslots);
-    all.len.resize(nslots);
-    w.ids.resize(nslots);
-    w.slotGeom.resize(nslots);
-    for (size_t k = 0, have = SIZE_MAX; k < nslots; k++) {
-      const BoxesSlot& s = P.slots[k];
-      if (s.cont != have) {   // (the slots are in container order)
-        per = chunk_volume(ci[s.cont].vol, ci[s.cont].chunk);
-        have = s.cont;
-        if (per.size() != ci[s.cont].off.size())
-          return -1;
-      }
-      if (s.id >= per.size())
-        return -1;
-      list[k] = per[s.id];
-      all.off[k] = off[s.cont] + ci[s.cont].off[s.id];
-      all.len[k] = ci[s.cont].len[s.id];
-      w.ids[k] = (uint32_t)k;
-      CropGeom& g = w.slotGeom[k];
-      for (int a = 0; a < 3; a++) {
-        g.rel[a] = P.geom[k].rel[a];
-        g.lo[a] = P.geom[k].lo[a];
-        g.hi[a] = P.geom[k].hi[a];
-      }
-    }
-    w.crop = true;
-    w.level = level != nullptr;
-    w.h = level ? *level : 0;
-    w.lo = Dims{0, 0, 0};
-    w.dims = P.shared ? P.stageDims : P.outDims;
-    all.vol = w.dims;
-    all.nvals = P.shared ? P.stageVals : P.outVals;
-    void* d_out = d_dst;
-    size_t outBytes = dst_cap_bytes;
-    if (P.shared) {
-      outBytes = P.stageVals * esz;
-      if (E.boxesStage.ensure(outBytes))
-        return -1;
-      d_out = E.boxesStage.p;
-    }
-    DecodeRequest req;
-    req.stacked = &list;
-    req.window = &w;
-    const int rtn = decode_to(E, src, output_float, d_out, outBytes, all, st, req);
-    if (rtn || !P.shared)
-      return rtn;
-    std::vector<BoxesCopyPair> pairs;
-    std::vector<uint64_t> first;
-    BoxesCopyGeom g;
-    boxes_copy_args(P, pairs, first, g);
-    const size_t pairBytes = round_up(pairs.size() * sizeof(BoxesCopyPair), 256);
-    if (E.misc.ensure(pairBytes + first.size() * 8))
-      return -1;
-    BoxesCopyPair* d_pairs = static_cast<BoxesCopyPair*>(E.misc.p);
-    uint64_t* d_first = reinterpret_cast<uint64_t*>(static_cast<char*>(E.misc.p) + pairBytes);
-    const bool vec = boxes_vec_ok(reinterpret_cast<uintptr_t>(d_out), reinterpret_cast<uintptr_t>(d_dst), pairs, g, esz);
-    auto copy = [&]() -> int {
-      HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(BoxesCopyPair), hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
-      if (boxes_copy_run(d_out, d_dst, esz, d_pairs, d_first, g, vec, st))
-        return -1;
-      HIP_CHECK(hipStreamSynchronize(st));   // (also: the uploads' host arrays may go only once the copies have read them)
-      return 0;
-    };
-    const int rc = copy();
-    if (rc)
-      drain_after_error(E, st);   // (as ~DecodeCall: queued copies read the vectors above)
-    E.prof.collect();
-    return rc;
+    return decode_boxes_to(*L.e, d_srcs, src_lens, ncont, which, box_lo, nbox, box_dims, level, pct, output_float, d_dst,
+                           dst_cap_bytes, static_cast<hipStream_t>(hip_stream), nullptr);
   });
 }
 

@@ -187,6 +187,13 @@ int decode_to(Engine& E, const void* d_src, int output_float, void* d_dst, size_
 int decode_window(Engine& E, const void* d_src, int output_float, void* d_dst, size_t dst_cap_bytes,
                   const ContainerInfo& ci, hipStream_t st, const Window& w, const ViewPitch* outView = nullptr);
 
+// sperrhip_decompress_boxes_dev (boxes.h) on an engine the caller holds, its arguments seen to be no NULL pointers, no
+// zero counts, no index of `which` beyond ncont and no zero box extent.  vol (may be null): the dims every container
+// has to name
+int decode_boxes_to(Engine& E, const void* const* d_srcs, const size_t* src_lens, size_t ncont, const uint32_t* which,
+                    const size_t* box_lo, size_t nbox, const size_t box_dims[3], const size_t* level, unsigned pct,
+                    int output_float, void* d_dst, size_t dst_cap_bytes, hipStream_t st, const Dims* vol);
+
 }  // namespace sperrhip
 
 #endif

@@ -31,7 +31,7 @@ thread_local Profiler* t_prof = nullptr;       // the profiler of the engine thi
 thread_local hipStream_t t_call_stream = nullptr;   // ... and the stream of its call (Lease; the poison fills)
 static thread_local const char* t_prof_cur = nullptr;
 static thread_local hipEvent_t t_prof_a = nullptr;
-std::atomic<unsigned long long> g_dbg_counter[4];   // sperrhip_debug_counter (0..2, and [3] as counter 7)
+std::atomic<unsigned long long> g_dbg_counter[5];   // sperrhip_debug_counter (0..2, [3] as counter 7, [4] as counter 8)
 bool g_lis_stamps_on = false;
 std::vector<uint64_t> g_lis_stamps_host;   // chunk 0 of the last decoded batch
 EnginePool g_pool;

@@ -112,7 +112,7 @@ extern bool g_prof_on;
 extern std::string g_prof_only;
 extern std::mutex g_prof_cfg_mu;
 extern thread_local Profiler* t_prof;   // the profiler of the engine this thread drives (Lease; prof_begin, engine.hip)
-extern std::atomic<unsigned long long> g_dbg_counter[4];   // sperrhip_debug_counter (0..2, and [3] as counter 7)
+extern std::atomic<unsigned long long> g_dbg_counter[5];   // sperrhip_debug_counter (0..2, [3] as counter 7, [4] as counter 8)
 extern bool g_lis_stamps_on;                               // sperrhip_debug_lis_stamps
 extern std::vector<uint64_t> g_lis_stamps_host;            //   chunk 0 of the last decoded batch
 // (t_shared_device: engine_internal.h; g_pool: below, after its type)
@@ -326,6 +326,8 @@ struct Engine {
   DevBuf relStage;                          // relative error (rel.h): the double volume or box y that the coder sees
   DevBuf relWork;                           //   ... and the sign bits' workspace with the read-back record of rel.hip
   DevBuf sizeWork;                          // size mode (budget.h): the survey's table of the volume and the dealt budgets
+  DevBuf seriesStage;                       // time series (series.h): the fp64 bands between the butterflies and the coder
+  DevBuf seriesTab;                         //   ... and the kernels' tables of step, band and output pointers
   std::vector<std::unique_ptr<DevBuf>> pweBufs;   // outlier streams of the batches of one call
   size_t freeMemAtInit = 0;
 
@@ -450,7 +452,7 @@ struct Engine {
   {
     for (auto* b : {&e.arena, &e.slots, &e.misc, &e.outlFixed, &e.outlVar, &e.outlStream, &e.pweBox, &e.wideScratch,
                     &e.fieldsStage, &e.fieldsStage2, &e.boxesStage, &e.maskStage, &e.maskStage2, &e.maskWork,
-                    &e.maskPyramid, &e.relStage, &e.relWork, &e.sizeWork})
+                    &e.maskPyramid, &e.relStage, &e.relWork, &e.sizeWork, &e.seriesStage, &e.seriesTab})
       f(*b);
     for (auto& b : e.outlDec)
       f(b);
